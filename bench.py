@@ -3,7 +3,7 @@
 fine-level smoother (BASELINE.json metric), on synthetic interior-liquid cubes.
 
     python bench.py --gpus N --steps K --warmup W [--size 256|512|1024] [--levels L]
-                    [--smoother jacobi|gs] [--no-cpu]
+                    [--smoother jacobi|gs] [--no-cpu] [--dump-outputs DIR]
 
 Default workload: BASELINE config 4, the 1024^3 interior-liquid cube (7 levels), on every N, so the
 per-N values form the strong-scaling curve the metric asks for; N > 1 splits the grid into Z-slabs
@@ -29,6 +29,8 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SMOOTHER_BYTES_PER_CELL = 13.0  # x r 4 + b r 4 + label 1 + x' w 4
 VCYCLE_BYTES_PER_FINE_CELL = 60.7
+DUMP_MAX_CELLS = 8 << 20  # --dump-outputs: whole grids up to 32 MB of float32, beyond that a sample of this many cells
+DUMP_SAMPLE_SEED = 1234
 
 
 def parse():
@@ -67,7 +69,16 @@ def parse():
                     help="test hook (--rehearse-gloo): the host-staged transport drops every N-th exchange during the check cycles; the check must fail")
     ap.add_argument("--workload", choices=["vcycle", "free_surface_pcg"], default="vcycle",
                     help="free_surface_pcg = BASELINE config 3 (single GPU): MG-PCG to 1e-5 on the free-surface pool")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="vcycle workload, one GPU: after the timed steps write the iterate the last one left in x as DIR/<name>.npy "
+                         "(float32; the whole grid up to 32 MB, a fixed seeded sample of larger grids), for output-by-output "
+                         "comparison of two builds")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "vcycle" or args.gpus != 1 or args.force_slab):
+        ap.error("--dump-outputs covers the single-GPU vcycle workload only")
+    return args
 
 
 def default_levels(n):
@@ -75,6 +86,24 @@ def default_levels(n):
     while (n >> (lev - 1)) > 16:
         lev += 1
     return lev  # 256 -> 5 (BASELINE config 2), 512 -> 6, 1024 -> 7
+
+
+def dump_outputs(out_dir, x):
+    """--dump-outputs: the fine-level iterate x the timed V-cycles left behind (what a caller of applyVCycle receives), as
+    float32 .npy files.  A grid of at most DUMP_MAX_CELLS cells goes whole into x.npy.  A larger one is sampled: its middle
+    z-plane into x_mid_plane.npy, and into x_sample.npy the cells at the sorted, distinct flat (C-order) indices of
+    np.unique(Generator(PCG64(DUMP_SAMPLE_SEED)).integers(0, x.numel(), DUMP_MAX_CELLS)) -- fixed for a given grid size."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    if x.numel() <= DUMP_MAX_CELLS:
+        arrays = {"x": x}
+    else:
+        idx = np.unique(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).integers(0, x.numel(), DUMP_MAX_CELLS))
+        arrays = {"x_mid_plane": x[x.shape[0] // 2], "x_sample": x.reshape(-1)[torch.from_numpy(idx).to(x.device)]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline(n, levels, use_gs, budget_s, sweeps=1, same_grid=False):
@@ -371,6 +400,8 @@ def main():
     own_elapsed = time.perf_counter() - t0  # this rank's own clock: its queue drained, before it waits for the others
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # before the untimed cycles below move x on
+        dump_outputs(args.dump_outputs, x)
     exchanges_per_cycle = ((solver.exchange_count - exchanges0) / args.steps) if slab_run else 0
     smooth_ms, smooth_groups = solver.profile_read()
     solver.profile_enable(2)  # stage breakdown: a few extra cycles outside the timed region (its event records cost a few %)
