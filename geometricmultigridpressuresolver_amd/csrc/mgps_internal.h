@@ -377,6 +377,13 @@ int launchFromHalf(void *stream, float *dst, const void *srcH, const float *sigm
 int launchMixSigma(void *stream, const double *maxAbsDev, float *sigmaDev);
 int launchZeroActiveHalf(void *stream, const GridP &g, void *aH);
 int launchProlongAdd(void *stream, const GridP &fine, float *fineInOut, const float *coarse, float *snap = nullptr, const uint8_t *snapTile = nullptr);
+// The up-stroke's prolongation inside its Jacobi sweep (fp32, single device): out = Jacobi(x + 4 P coarse) over the level's plane
+// blocks (prolongJacobiPlaneKernel; g.nbnd = 0: the band stage computes the BOUNDARY cells), and the closure launch whose input is
+// x + 4 P coarse (launchBandBox's closure mode with dst == nullptr).  Results: those of launchProlongAdd and then the plain launches.
+bool prolongJacobiPlaneFits(const GridP &g);
+int launchProlongJacobi(void *stream, const GridP &g, float *out, const float *x, const float *b, const float *coarse, float omega);
+int launchBandBoxClosureProlonged(void *stream, const GridP &g, const BandBoxesDev &bx, const float *src, const float *coarse, const float *b, float *snap,
+                                  float omega);
 size_t planeBlockCount(const GridP &g);
 int launchPlaneBlockFlags(void *stream, const GridP &g, uint8_t *flags);
 // dense coarsest matrix (n x n doubles, zeroed by the caller) from the level's labels; fp32 inverse from the triangle potri left

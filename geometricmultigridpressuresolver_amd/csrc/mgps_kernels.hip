@@ -330,8 +330,11 @@ __global__ __launch_bounds__(256) void stencilQuadKernel(GridP g, TX *__restrict
 // the quad kernel since the end of round 3, larger planes this one.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPlanePitch = 256 + 8;  // 4 floats of halo on each side keep the rows 16-byte aligned
-// lerp of Ops.h:841-871: (1 - f) a + f b, this exact form (HDK's SYSlerp breaks the R / P symmetry, Ops.h:837-839)
-__device__ __forceinline__ float lerpRef(float a, float b, float f) { return (1.f - f) * a + f * b; }
+// lerp of Ops.h:841-871: (1 - f) a + f b, this exact form (HDK's SYSlerp breaks the R / P symmetry, Ops.h:837-839).  The
+// contraction is pinned -- fma(1 - f, a, f b), the form the compiler had chosen for the plain expression in most places (not in
+// one lerp of prolongAddKernel: round 6 moved the last bits of the prolongation there) -- so that the kernels that interpolate the
+// same values in different places (prolongJacobiPlaneKernel, the closure launch's coarse input) round them alike
+__device__ __forceinline__ float lerpRef(float a, float b, float f) { return __builtin_fmaf(1.f - f, a, f * b); }
 
 // A wave-uniform pointer pinned to a scalar register pair, its derivation hidden from the optimiser (an empty asm): in the
 // plane-marching kernels below the loop optimiser otherwise folds "plane base + lane offset" into one 64-bit vector induction
@@ -357,6 +360,12 @@ __device__ __forceinline__ float4 gLoad4nt(const float *base, unsigned cell)
     return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ float gLoad1(const float *base, unsigned cell) { return *(const MGPS_GLOBAL_AS float *)((const MGPS_GLOBAL_AS char *)base + cell * 4u); }
+__device__ __forceinline__ float2 gLoad2(const float *base, unsigned cell)
+{
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const v2f v = *(const MGPS_GLOBAL_AS v2f *)((const MGPS_GLOBAL_AS char *)base + cell * 4u);
+    return make_float2(v.x, v.y);
+}
 __device__ __forceinline__ uchar4 gLoadCodes4nt(const uint8_t *base, unsigned cell)
 {
     const v4b v = __builtin_nontemporal_load((const MGPS_GLOBAL_AS v4b *)((const MGPS_GLOBAL_AS char *)base + cell));
@@ -487,6 +496,216 @@ GridP g, float *__restrict__ out,
     if (DOT) {
         __syncthreads();  // (the LDS planes are done with)
         blockDotStore(dotAcc, dotPartials, blockIdx.x);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The up-stroke's prolongation inside its Jacobi sweep (round 6).  An up-stroke is x'' = x' + 4 P e (Ops.h:841-871, e the coarse
+// correction) and then "band passes, sweep, band passes" on x''.  This kernel is stencilPlaneKernel<OP_JACOBI> whose input is x'',
+// formed as x' is staged: the fine level's read-modify-write pass of the prolongation (prolongAddBlockKernel, 8 B per cell) is
+// gone, and the coarse grid (0.5 B per fine cell) is read instead.
+//   * Coarse data through LDS.  A tile's fine rows j0 - 1 .. j0 + kPlaneRows interpolate from coarse rows j0/2 - 1 .. j0/2 + 8,
+//     its fine columns i0 - 1 .. i0 + 256 from coarse columns i0/2 - 1 .. i0/2 + 128.  Once per coarse plane the workgroup lerps
+//     those rows along x to fine-x resolution (the first lerp of the reference order) into a ring of kUpRing planes in LDS; a
+//     thread then forms 4 P e of a fine value from four staged words per cell: lerp along y on two planes, then along z.  Fine
+//     plane k reads coarse planes (k - 1) >> 1 and the one after: step k corrects the halo of plane k and the thread's own quad
+//     of plane k + 1 (its z + 1 neighbours) before its barrier, from up to three planes.
+//   * Each x'' value is formed once per tile: the own quad as it becomes the z + 1 plane, the y-halo rows and x-halo cells
+//     when they are staged; the z - 1 quad comes back from LDS corrected.
+//   * Masking.  prolongAddBlockKernel adds to active cells only.  The own quad takes the correction where its codes say active
+//     (codes of plane k + 1 are requested a step ahead for that), so the values of the grid this thread owns are those of
+//     "prolongation, then sweep" everywhere, inactive cells included.  The halo values take it unconditionally: only a cell
+//     with an inactive face neighbour can read a wrong halo value, and no such cell keeps this launch's result -- it is either
+//     inactive (its own value is written) or a BOUNDARY cell, and every BOUNDARY cell lies in the band closure, which the plain
+//     band launch after this one rewrites (the same invariant lets the sweep run with nbnd = 0; LABNOTES R5).
+// Bits: the lerps are lerpRef's (pinned fma), in the order of prolongAddBlockKernel (x, y, z, then x + 4 t), the epilogue is
+// stencilPlaneKernel's: the output equals "launchProlongAdd, then launchStencil(OP_JACOBI)" bit for bit.
+// Needs an even march depth (zc) and even extents; no slab ghost planes (prolongJacobiPlaneFits).  Resources: 63 VGPRs at 8 waves
+// per SIMD, no scratch, 69 696 B of LDS (two workgroups per CU).
+// ---------------------------------------------------------------------------------------------
+constexpr int kUpRows = kPlaneRows / 2 + 2;         // coarse rows a tile reads
+constexpr int kUpQuads = 256 / 4 + 2;               // fine-x quads of a staged row: i0 - 4 .. i0 + 259
+constexpr int kUpRing = 3;                          // coarse planes in LDS
+constexpr int kUpStagers = kUpRows * kUpQuads;      // threads that stage a coarse plane: one quad of one row each
+static_assert(kUpStagers <= 64 * kPlaneRows, "one staged quad per thread");
+__global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(GridP g, float *__restrict__ out, const float *__restrict__ x,
+                                                                              const float *__restrict__ b, const float *__restrict__ coarse, float omega,
+                                                                              unsigned nbx, unsigned nby, int zc, const int32_t *__restrict__ blocks)
+{
+    __shared__ float plane[2][(kPlaneRows + 2) * kPlanePitch];
+    __shared__ float crow[kUpRing][kUpRows * kPlanePitch];  // coarse rows lerped along x; fine column i at 4 + i - i0, as in `plane`
+    unsigned bid = remapBlock(blockIdx.x, gridDim.x);
+    if (blocks) bid = unsigned(blocks[bid]);
+    bid = __builtin_amdgcn_readfirstlane(bid);
+    const unsigned bx = bid % nbx, by = (bid / nbx) % nby, bz = bid / (nbx * nby);
+    const int lane = threadIdx.x & (kWave - 1), ty = threadIdx.x / kWave;
+    const int i = int(bx) * 256 + lane * 4, j = int(by) * kPlaneRows + ty;
+    const int ic = min(i, g.nx - 4), jc = min(j, g.ny - 1);
+    const bool live = ic >= g.xlo && ic < g.xhi;
+    const bool valid = i < g.nx && j < g.ny && live;
+    const ptrdiff_t sz = ptrdiff_t(g.nx) * g.ny;
+    const int k0 = int(bz) * zc, k1 = min(k0 + zc, g.nz);
+    const unsigned off = unsigned(jc) * unsigned(g.nx) + unsigned(ic);
+    const unsigned offYm = jc > 0 ? off - unsigned(g.nx) : off, offYp = jc < g.ny - 1 ? off + unsigned(g.nx) : off;
+    auto planeOf = [&](const float *p, int k) { return scalarBase(p + ptrdiff_t(min(max(k, 0), g.nz - 1)) * sz); };
+    const bool rowTop = ty == 0, rowBot = ty == kPlaneRows - 1, colL = lane == 0, colR = lane == kWave - 1;
+    const bool useHx = live && ((colL && ic > 0) || (colR && ic + 4 < g.nx));
+    const unsigned offHx = !useHx ? off : (colL ? off - 1u : off + 4u);
+    // (every 32-bit offset goes through `opq` where a load uses it: otherwise the loop optimiser hoists its 64-bit zero extension
+    // out of the march -- two registers per offset, and the saddr + voffset form of the loads is lost; that alone spilled 16 VGPRs)
+    auto opq = [](unsigned v) {
+        asm volatile("" : "+v"(v));
+        return v;
+    };
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uchar4 ext4 = make_uchar4(MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL);
+
+    // this thread's share of a coarse plane: quad sq of staged row sr (clamped indices: they bite for the EXTERIOR shell and
+    // for columns / rows past the grid only, whose values nobody keeps; prolongAddBlockKernel clamps the same way)
+    const int cnx = g.nx >> 1, cny = g.ny >> 1, cnz = g.nz >> 1;
+    const ptrdiff_t csz = ptrdiff_t(cnx) * cny;
+    const int tid = threadIdx.x;
+    const bool stager = tid < kUpStagers;
+    const int sr = tid / kUpQuads, sq = tid - sr * kUpQuads;
+    const int mq = min(max(int(bx) * 64 - 1 + sq, 0), (g.nx >> 2) - 1);
+    const int crw = min(max(int(by) * (kPlaneRows / 2) - 1 + sr, 0), cny - 1);
+    const unsigned cOff1 = unsigned(crw) * unsigned(cnx) + unsigned(2 * mq);
+    auto slotOf = [](int P) { return (P + kUpRing) % kUpRing; };  // (P >= -1)
+    auto cplane = [&](int P) { return scalarBase(coarse + ptrdiff_t(min(max(P, 0), cnz - 1)) * csz); };  // (outside the stagers' branches)
+    auto loadC = [&](const float *p) {
+        const float2 c12 = gLoad2(p, opq(cOff1));
+        return make_float4(gLoad1(p, opq(mq > 0 ? cOff1 - 1u : cOff1)), c12.x, c12.y, gLoad1(p, opq(2 * mq + 2 < cnx ? cOff1 + 2u : cOff1 + 1u)));
+    };
+    auto stageC = [&](int P, float4 c) {  // x lerps of prolongAddBlockKernel
+        *reinterpret_cast<float4 *>(&crow[slotOf(P)][sr * kPlanePitch + 4 * sq]) =
+            make_float4(lerpRef(c.x, c.y, 0.75f), lerpRef(c.y, c.z, 0.25f), lerpRef(c.y, c.z, 0.75f), lerpRef(c.z, c.w, 0.25f));
+    };
+    // 4 P e at fine plane kk, fine row jj (nominal: row slot ((jj - 1) >> 1) - j0/2 + 1 and the next), staged column xi
+    const int rowBase = 1 - int(by) * (kPlaneRows / 2);
+    auto rowsAt = [&](int kk, int jj, int xi, const float *&pa, const float *&pb, float &fy, float &fz) {
+        const int Pa = (kk - 1) >> 1;
+        const int o = (((jj - 1) >> 1) + rowBase) * kPlanePitch + xi;
+        pa = &crow[slotOf(Pa)][o];
+        pb = &crow[slotOf(Pa + 1)][o];
+        fy = (jj & 1) ? 0.25f : 0.75f;
+        fz = (kk & 1) ? 0.25f : 0.75f;
+    };
+    auto trilerp = [](float a0, float a1, float b0, float b1, float fy, float fz) { return lerpRef(lerpRef(a0, a1, fy), lerpRef(b0, b1, fy), fz); };
+    // x + 4 t on a quad; `act`: only where the codes say active (else every component)
+    auto corr4 = [&](int kk, int jj, float4 v, uchar4 lc, bool act) {
+        const float *pa, *pb;
+        float fy, fz;
+        rowsAt(kk, jj, 4 + lane * 4, pa, pb, fy, fz);
+        // (the two planes one after the other: eight words of LDS in registers at a time, not sixteen)
+        const float4 a0 = *reinterpret_cast<const float4 *>(pa), a1 = *reinterpret_cast<const float4 *>(pa + kPlanePitch);
+        const float4 ya = make_float4(lerpRef(a0.x, a1.x, fy), lerpRef(a0.y, a1.y, fy), lerpRef(a0.z, a1.z, fy), lerpRef(a0.w, a1.w, fy));
+        asm volatile("" ::: "memory");
+        const float4 b0 = *reinterpret_cast<const float4 *>(pb), b1 = *reinterpret_cast<const float4 *>(pb + kPlanePitch);
+        const float t0 = lerpRef(ya.x, lerpRef(b0.x, b1.x, fy), fz), t1 = lerpRef(ya.y, lerpRef(b0.y, b1.y, fy), fz);
+        const float t2 = lerpRef(ya.z, lerpRef(b0.z, b1.z, fy), fz), t3 = lerpRef(ya.w, lerpRef(b0.w, b1.w, fy), fz);
+        return make_float4(!act || activeLabel(lc.x) ? v.x + 4.f * t0 : v.x, !act || activeLabel(lc.y) ? v.y + 4.f * t1 : v.y,
+                           !act || activeLabel(lc.z) ? v.z + 4.f * t2 : v.z, !act || activeLabel(lc.w) ? v.w + 4.f * t3 : v.w);
+    };
+    auto corr1 = [&](int kk, int jj, float v) {  // the x-halo cell of the first / last lane
+        const float *pa, *pb;
+        float fy, fz;
+        rowsAt(kk, jj, colL ? 3 : 4 + 256, pa, pb, fy, fz);
+        return v + 4.f * trilerp(pa[0], pa[kPlanePitch], pb[0], pb[kPlanePitch], fy, fz);
+    };
+
+    // coarse planes k0/2 - 1 .. k0/2 + 1: what planes k0 - 1 .. k0 + 1 interpolate from (k0 is even)
+    {
+        const float *p0 = cplane((k0 >> 1) - 1), *p1 = cplane(k0 >> 1), *p2 = cplane((k0 >> 1) + 1);
+        const float4 c0 = stager ? loadC(p0) : zero4, c1 = stager ? loadC(p1) : zero4, c2 = stager ? loadC(p2) : zero4;
+        if (stager) {
+            stageC((k0 >> 1) - 1, c0);
+            stageC(k0 >> 1, c1);
+            stageC((k0 >> 1) + 1, c2);
+        }
+    }
+    float *const mine0 = plane[0] + (ty + 1) * kPlanePitch + 4 + lane * 4;
+    constexpr int kBufFloats = (kPlaneRows + 2) * kPlanePitch;
+    float4 xm0 = live ? gLoad4(planeOf(x, k0 - 1), off) : zero4;
+    const float *xk = planeOf(x, k0);
+    float4 xc = live ? gLoad4(xk, off) : zero4;
+    float4 xp = live ? gLoad4(planeOf(x, k0 + 1), off) : zero4;
+    const uint8_t *lab0 = scalarBase(g.lab + ptrdiff_t(k0) * sz);
+    uchar4 lc = live ? gLoadCodes4nt(lab0, off) : ext4;                                           // codes of the step's plane
+    uchar4 lcn = live ? gLoadCodes4nt(scalarBase(g.lab + ptrdiff_t(k0 + 1) * sz), off) : ext4;    // ... and of the next one
+    float4 hy = zero4;
+    if (live && rowTop) hy = gLoad4(xk, offYm);
+    if (live && rowBot) hy = gLoad4(xk, offYp);
+    float hx = live ? gLoad1(xk, offHx) : 0.f;
+    __syncthreads();  // (the coarse rows)
+    if (live) {
+        xm0 = corr4(k0 - 1, j, xm0, lc, false);
+        xc = corr4(k0, j, xc, lc, true);
+    }
+    *reinterpret_cast<float4 *>(mine0 + kBufFloats) = xm0;
+
+    // Step k: before the barrier the halo of plane k and the own quad of plane k + 1 take their corrections (from coarse planes
+    // (k - 1) >> 1 .. (k >> 1) + 1, staged before the previous barrier); an even step requests coarse plane k/2 + 2 and stages
+    // it right after its barrier, into the slot whose last reader was this step's halo.
+    int buf = 0;
+    for (int k = k0; k < k1; ++k) {
+        float *me = mine0 + buf * kBufFloats;
+        if (live) {
+            if (rowTop) hy = corr4(k, j - 1, hy, lc, false);
+            if (rowBot) hy = corr4(k, j + 1, hy, lc, false);
+            if (useHx) hx = corr1(k, j, hx);
+            xp = corr4(k + 1, j, xp, lcn, k + 1 < k1);  // (plane k1 is this block's z + 1 neighbour only)
+        }
+        *reinterpret_cast<float4 *>(me) = xc;
+        if (rowTop) *reinterpret_cast<float4 *>(me - kPlanePitch) = hy;
+        if (rowBot) *reinterpret_cast<float4 *>(me + kPlanePitch) = hy;
+        if (colL) me[-1] = useHx ? hx : 0.f;
+        if (colR) me[4] = useHx ? hx : 0.f;
+        float4 bc = zero4;
+        uchar4 lcq = ext4;  // codes of plane k + 2
+        const float *bk = scalarBase(b + ptrdiff_t(k) * sz);
+        const uint8_t *labq = scalarBase(g.lab + ptrdiff_t(min(k + 2, g.nz - 1)) * sz);
+        if (live) {
+            bc = gLoad4nt(bk, opq(off));
+            if (k + 2 < k1) lcq = gLoadCodes4nt(labq, opq(off));
+        }
+        float4 xq = zero4, hyn = hy;
+        float hxn = hx;
+        if (k + 1 < k1 && live) {
+            const float *xn = planeOf(x, k + 1);
+            xq = gLoad4(planeOf(x, k + 2), opq(off));
+            if (rowTop) hyn = gLoad4(xn, opq(offYm));
+            if (rowBot) hyn = gLoad4(xn, opq(offYp));
+            hxn = gLoad1(xn, opq(offHx));
+        }
+        const bool stageNext = !(k & 1) && k + 2 < k1;
+        const float *pn = cplane((k >> 1) + 2);
+        float4 cnext = zero4;
+        if (stageNext && stager) cnext = loadC(pn);
+        __syncthreads();
+        if (stageNext && stager) stageC((k >> 1) + 2, cnext);
+        const float4 ym = *reinterpret_cast<const float4 *>(me - kPlanePitch);
+        const float4 yp = *reinterpret_cast<const float4 *>(me + kPlanePitch);
+        const float4 xm = *reinterpret_cast<const float4 *>(mine0 + (buf ^ 1) * kBufFloats);
+        const float xs[6] = {me[-1], xc.x, xc.y, xc.z, xc.w, me[4]};
+        const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
+        const float zms[4] = {xm.x, xm.y, xm.z, xm.w}, zps[4] = {xp.x, xp.y, xp.z, xp.w};
+        const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
+        const unsigned ls[4] = {lc.x, lc.y, lc.z, lc.w};
+        float res[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float diag = simpleDiag(ls[e]);
+            const float lap = diag * xs[e + 1] - (xs[e] + xs[e + 2] + yms[e] + yps[e] + zms[e] + zps[e]);
+            res[e] = simpleCell(ls[e]) ? epilogueRcp<OP_JACOBI>(xs[e + 1], bs[e], lap, simpleRcp(diag), omega) : inactiveValue<OP_JACOBI>(xs[e + 1]);
+        }
+        if (valid) gStore4nt(scalarBase(out + ptrdiff_t(k) * sz), opq(off), make_float4(res[0], res[1], res[2], res[3]));
+        xc = xp;
+        xp = xq;
+        hy = hyn;
+        hx = hxn;
+        lc = lcn;
+        lcn = lcq;
+        buf ^= 1;
     }
 }
 
@@ -823,14 +1042,19 @@ __device__ __forceinline__ bool boxBand(unsigned cls) { return cls >= kBoxGenera
 // XZERO: src is zero everywhere (see stencilQuadKernel): no value of it is loaded -- closure mode, and the plain mode of a
 // Gauss-Seidel down-stroke, which then writes the iterate in place
 // (the body: bandBoxKernel runs group remapBlock(blockIdx.x), strokeFrontKernel its first workgroups)
-template <class TX, bool CLOSURE, bool DOT, bool GEN, bool XZERO>
+// PRO (closure mode, fp32): the iterate is src + 4 P coarse (an up-stroke whose sweep takes the prolongation in,
+// prolongJacobiPlaneKernel): every value staged of src takes its correction, with prolongAddKernel's lerps, as it is loaded.  The
+// cells a list loads are active ones (the lists hold no entries for inactive cells), the cells prolongAdd adds to.
+template <class TX, bool CLOSURE, bool DOT, bool GEN, bool XZERO, bool PRO = false>
 // (dst and dotOld carry no __restrict__: the gathered dot of a Jacobi stroke reads the sweep's value of a cell through dotOld == dst
 // right before the store that replaces it)
 __device__ __forceinline__ void bandBoxBody(const GridP &g, const TX *__restrict__ src, const float *__restrict__ b, TX *dst,
                                             TX *__restrict__ snap, const int32_t *__restrict__ info, const uint32_t *__restrict__ list,
                                             const int32_t *__restrict__ general, float omega, int depth, const MixScale &ms,
-                                            double *__restrict__ dotPartials, const TX *dotOld, int outClosure, unsigned group, unsigned slot)
+                                            double *__restrict__ dotPartials, const TX *dotOld, int outClosure, unsigned group, unsigned slot,
+                                            const float *__restrict__ coarse = nullptr)
 {
+    static_assert(!PRO || (CLOSURE && !XZERO && std::is_same<TX, float>::value), "the prolonged input: closure mode, fp32");
     constexpr bool kMixed = !std::is_same<TX, float>::value;
     constexpr int kGenRows = GEN ? kBoxMaxGeneral : 1;
     __shared__ __attribute__((aligned(16))) float val[2][kBoxMaxNodes];
@@ -928,6 +1152,34 @@ __device__ __forceinline__ void bandBoxBody(const GridP &g, const TX *__restrict
             }
     }
     __syncthreads();
+    if (PRO) {
+        // the region's origin in cells (wave-uniform); a cell's coarse neighbourhood as in prolongAddKernel (clamped: the clamps
+        // bite for the EXTERIOR shell only, which no list loads).  A phase of its own, one slot at a time: in the load batch above
+        // the eight coarse values of every slot made the kernel spill
+        const int ox = int(origin % g.nx), oy = int((origin / g.nx) % g.ny), oz = int(origin / sz);
+        const int cnx = g.nx >> 1, cny = g.ny >> 1, cnz = g.nz >> 1;
+        const unsigned csy = unsigned(cnx), csz = unsigned(cnx) * unsigned(cny);
+        const float *cb = scalarBase(coarse);
+#pragma unroll
+        for (int m = 0; m < kBoxSlots; ++m) {
+            if (m > 0) asm volatile("" ::: "memory");
+            const uint32_t e = ue[m];
+            const unsigned cls = (e >> 16) & 15u;
+            if (tid + m * kBoxThreads < nList && cls != kBoxSkip && cls != kBoxZero) {
+                const int ci = ox + int(e & 31u), cj = oy + int((e >> 5) & 31u), ck = oz + int((e >> 10) & 31u);
+                const int bi = min(max((ci - 1) >> 1, 0), cnx - 2), bj = min(max((cj - 1) >> 1, 0), cny - 2), bk = min(max((ck - 1) >> 1, 0), cnz - 2);
+                const float fx = (ci & 1) ? 0.25f : 0.75f, fy = (cj & 1) ? 0.25f : 0.75f, fz = (ck & 1) ? 0.25f : 0.75f;
+                const unsigned o = unsigned(bk) * csz + unsigned(bj) * csy + unsigned(bi);
+                const float v00 = lerpRef(gLoad1(cb, o), gLoad1(cb, o + 1u), fx), v10 = lerpRef(gLoad1(cb, o + csy), gLoad1(cb, o + csy + 1u), fx);
+                const float v01 = lerpRef(gLoad1(cb, o + csz), gLoad1(cb, o + csz + 1u), fx), v11 = lerpRef(gLoad1(cb, o + csz + csy), gLoad1(cb, o + csz + csy + 1u), fx);
+                const int n = nodeOf(e);
+                const float v = val[0][n] + 4.f * lerpRef(lerpRef(v00, v10, fy), lerpRef(v01, v11, fy), fz);
+                val[0][n] = v;
+                val[1][n] = v;
+            }
+        }
+        __syncthreads();
+    }
     for (int p = 1; p <= H; ++p) {
         const float *from = val[(p - 1) & 1];
         float *to = val[p & 1];
@@ -981,14 +1233,15 @@ __device__ __forceinline__ void bandBoxBody(const GridP &g, const TX *__restrict
     }
     if (DOT) blockDotStore(acc, dotPartials, slot);
 }
-template <class TX, bool CLOSURE, bool DOT, bool GEN, bool XZERO = false>
+template <class TX, bool CLOSURE, bool DOT, bool GEN, bool XZERO = false, bool PRO = false>
 __global__ __launch_bounds__(kBoxThreads, 8) void bandBoxKernel(GridP g, const TX *__restrict__ src, const float *__restrict__ b, TX *dst,
                                                               TX *__restrict__ snap, const int32_t *__restrict__ info, const uint32_t *__restrict__ list,
                                                               const int32_t *__restrict__ general, float omega, int depth, MixScale ms,
-                                                              double *__restrict__ dotPartials, const TX *dotOld, int outClosure)
+                                                              double *__restrict__ dotPartials, const TX *dotOld, int outClosure,
+                                                              const float *__restrict__ coarse = nullptr)
 {
-    bandBoxBody<TX, CLOSURE, DOT, GEN, XZERO>(g, src, b, dst, snap, info, list, general, omega, depth, ms, dotPartials, dotOld, outClosure,
-                                              remapBlock(blockIdx.x, gridDim.x), blockIdx.x);
+    bandBoxBody<TX, CLOSURE, DOT, GEN, XZERO, PRO>(g, src, b, dst, snap, info, list, general, omega, depth, ms, dotPartials, dotOld, outClosure,
+                                                   remapBlock(blockIdx.x, gridDim.x), blockIdx.x, coarse);
 }
 
 // The front of a smoothing stroke in ONE launch: the closure launch of the band boxes (workgroups [0, ngroups)) and the sweep
@@ -2459,6 +2712,23 @@ int launchBandBox(void *stream, const GridP &g, const BandBoxesDev &bx, bool clo
     return launchBandBoxT<float>(s, g, bx, closure, static_cast<const float *>(src), b, static_cast<float *>(dst), static_cast<float *>(snap), omega, ms,
                                  dotPartials, static_cast<const float *>(dotOld), outClosure ? 1 : 0);
 }
+// the closure launch of an up-stroke whose sweep takes the prolongation in: its input is src + 4 P coarse (bandBoxBody, PRO)
+int launchBandBoxClosureProlonged(void *stream, const GridP &g, const BandBoxesDev &bx, const float *src, const float *coarse, const float *b, float *snap,
+                                  float omega)
+{
+    if (bx.ngroups <= 0) return 0;
+    if (!boxPlaneFits(Dims{g.nx, g.ny, g.nz}) || !src || !coarse || !snap || src == snap || (g.nx | g.ny | g.nz) & 1 || g.nx < 4 || g.ny < 4 || g.nz < 4)
+        return int(hipErrorInvalidValue);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned ng = unsigned(bx.ngroups);
+    if (bx.anyGeneral)
+        bandBoxKernel<float, true, false, true, false, true><<<ng, kBoxThreads, 0, s>>>(g, src, b, nullptr, snap, bx.info, bx.list, bx.general, omega, bx.depth,
+                                                                                      MixScale{}, nullptr, nullptr, 0, coarse);
+    else
+        bandBoxKernel<float, true, false, false, false, true><<<ng, kBoxThreads, 0, s>>>(g, src, b, nullptr, snap, bx.info, bx.list, bx.general, omega, bx.depth,
+                                                                                       MixScale{}, nullptr, nullptr, 0, coarse);
+    return int(hipGetLastError());
+}
 // closure launch + sweep of a stroke in one launch (strokeFrontKernel): levels that take the quad sweep, fp32, no gathered dot.
 // x == nullptr: the zero iterate.  keep: launchMarkClosure's bits
 int launchStrokeFront(void *stream, const GridP &g, const BandBoxesDev &bx, float *out, const float *x, const float *b, float *snap, float omega, const uint32_t *keep)
@@ -2793,6 +3063,23 @@ int launchProlongAdd(void *stream, const GridP &fine, float *fineInOut, const fl
         if (nb > 0) prolongAddQuadKernel<<<nb, 256, 0, static_cast<hipStream_t>(stream)>>>(fine, fineInOut, coarse, nb, snap, snapTile);
     } else
         prolongAddKernel<<<blocksFor(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(fine, fineInOut, coarse, snap, snapTile);
+    return int(hipGetLastError());
+}
+
+// the up-stroke's sweep with the prolongation inside (prolongJacobiPlaneKernel): out = Jacobi(x + 4 P coarse) on the level's plane
+// blocks; single-device fp32 levels that kept their plane blocks (an even march depth: planeSweepZc), even extents
+bool prolongJacobiPlaneFits(const GridP &g)
+{
+    return g.planeZc > 0 && (g.planeZc & 1) == 0 && (g.nx & 3) == 0 && g.nx >= 8 && (g.ny & 1) == 0 && (g.nz & 1) == 0 && g.ny >= 4 && g.nz >= 4 &&
+           !g.ghostLo && !g.ghostHi;
+}
+int launchProlongJacobi(void *stream, const GridP &g, float *out, const float *x, const float *b, const float *coarse, float omega)
+{
+    if (!prolongJacobiPlaneFits(g) || !out || !x || !coarse || out == x || g.nbnd > 0) return int(hipErrorInvalidValue);
+    const int zc = g.planeZc;
+    const unsigned nbx = (g.nx + 255) / 256, nby = (g.ny + kPlaneRows - 1) / kPlaneRows, nbz = (g.nz + zc - 1) / zc;
+    const unsigned nb = g.planeBlocks ? unsigned(g.nplaneBlocks) : nbx * nby * nbz;
+    if (nb > 0) prolongJacobiPlaneKernel<<<nb, 64 * kPlaneRows, 0, static_cast<hipStream_t>(stream)>>>(g, out, x, b, coarse, omega, nbx, nby, zc, g.planeBlocks);
     return int(hipGetLastError());
 }
 

@@ -798,6 +798,54 @@ bool strokeFrontMerges(const mgps_solver *h, int l)
     const DevLevel &L = h->lv[l];
     return !h->dist && L.d.cells() <= maxCells && stencilKernelOf(L.g) == 1 && (L.d.cells() & 31) == 0;  // (512^3 level: 618-629 -> 565-593 cycles/s merged)
 }
+// An up-stroke whose Jacobi sweep takes the prolongation in (prolongJacobiPlaneKernel, round 6): instead of "prolongation (x'' =
+// x' + 4 P e in place), closure launch, sweep, plain launch" three launches -- the closure launch and the sweep read x' and the
+// coarse correction e and form x'' where they stage it; the plain launch is unchanged.  The fine level's prolongation pass (a
+// read-modify-write of the iterate, 1.27 ms at 1024^3) is gone.  Single-device fp32 Jacobi strokes of one post-sweep on levels
+// with band boxes (not in box form) that kept their plane blocks; not a stroke that gathers <z, r> (its sweep is the dot launch).
+// By size: x-y planes of 4 MiB and more.  Same-box A/B (LABNOTES R6): 1024^3 106.5 -> 118.0 cycles/s; 512^3 with the path forced
+// on 658.1 -> 664.8 (+1.0 %, inside the box-to-box spread of 2.5 %): 512^2 planes keep the separate pass.  The sweep timer takes the fused launch -- the
+// up-stroke's sweep -- so profiling does not switch it off.  MGPS_FUSE_UP=0: never (A/B); =1: every level where it is valid (tests).
+bool upStrokeFuses(const mgps_solver *h, int l, const float *cur, const float *other, const float *b, bool dot)
+{
+    static const int mode = [] {  // -1: by size
+        const char *e = getenv("MGPS_FUSE_UP");
+        return !e ? -1 : (e[0] == '0' ? 0 : 1);
+    }();
+    if (mode == 0 || l + 1 >= int(h->lv.size())) return false;
+    const DevLevel &L = h->lv[l];
+    if (mode < 0 && size_t(L.g.nx) * L.g.ny * sizeof(float) < kPlaneSweepMinPlaneBytes) return false;
+    const bool r = L.r != nullptr;
+    return !dot && !h->useGS && !h->dist && !h->tailOfSlabRun && h->opt.precision == 0 && h->opt.band_iterations > 0 && h->opt.post_sweeps == 1 &&
+           levelHasBoxes(h, l) && !L.boxForm && prolongJacobiPlaneFits(L.g) && boxPlaneFits(L.d) && (!r || (cur != L.r && other != L.r && b != L.r));
+}
+// `cur` holds the iterate before the prolongation, `coarse` the correction of the level below; on return cur is the smoothed
+// iterate (smoothStroke's three-launch form, with x'' = cur + 4 P coarse formed inside the first two launches)
+int fusedUpStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, const float *coarse)
+{
+    DevLevel &L = h->lv[l];
+    const bool timed = h->profiling && l == 0;
+    {
+        StageScope scope(h, ST_BAND, l);
+        MGPS_LAUNCH(h, launchBandBoxClosureProlonged(h->stream, L.g, L.bandBoxes, cur, coarse, b, L.r, h->opt.jacobi_weight));
+    }
+    {
+        StageScope scope(h, ST_SMOOTH, l);
+        if (timed) MGPS_TRY(profMark(h, true));
+        GridP gs = L.g;
+        gs.nbnd = 0;  // every BOUNDARY cell lies in the band closure (see smoothStroke)
+        MGPS_LAUNCH(h, launchProlongJacobi(h->stream, gs, other, cur, b, coarse, h->opt.jacobi_weight));
+        if (timed) {
+            MGPS_TRY(profMark(h, false));
+            ++h->profSweeps;
+        }
+    }
+    StageScope scope(h, ST_BAND, l);
+    std::swap(cur, other);
+    MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight, false, MixScale{}, nullptr, nullptr, true));
+    return MGPS_OK;
+}
+
 int ensureKeepBits(mgps_solver *h, int l)
 {
     DevLevel &L = h->lv[l];
@@ -1110,6 +1158,10 @@ int vcycle(mgps_solver *h, float *x, const float *b, bool useInitialGuess, bool 
             if (stopRequested()) return failH(h, MGPS_ERR_INTERRUPTED, "mgps_apply_vcycle: interrupted");
             const float *rhsUp = l == 0 ? b : F.b;
             bool upSnap = false;
+            if (upStrokeFuses(h, l, cur[l], other[l], rhsUp, h->gatherDot && l == 0)) {
+                MGPS_TRY(fusedUpStroke(h, l, cur[l], other[l], rhsUp, cur[l + 1]));
+                continue;
+            }
             {
                 StageScope scope(h, ST_PROLONG, l);
                 MGPS_TRY(exchangeGhosts(h, l + 1, cur[l + 1]));
@@ -1156,6 +1208,10 @@ int innerCycle(mgps_solver *h, int first, float **result)
     cur[nsmooth] = B.x;
     for (int l = nsmooth - 1; l >= first; --l) {
         DevLevel &F = h->lv[l];
+        if (upStrokeFuses(h, l, cur[l], other[l], F.b, false)) {
+            MGPS_TRY(fusedUpStroke(h, l, cur[l], other[l], F.b, cur[l + 1]));
+            continue;
+        }
         const bool snap = gsStrokeSnapshots(h, l, cur[l], F.b);
         if (snap) MGPS_TRY(ensureSnapTiles(h, l));
         MGPS_LAUNCH(h, launchProlongAdd(h->stream, F.g, cur[l], cur[l + 1], snap ? F.r : nullptr, snap ? F.snapTile : nullptr));
@@ -4185,6 +4241,13 @@ int mgps_residual_restrict_fused(const mgps_solver *h, int level, int *fused)
 try {
     if (!h || !fused || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
     *fused = (h->opt.precision == 0 || level > 0) && residualRestrictFuses(h, level) ? 1 : 0;
+    return MGPS_OK;
+}
+MGPS_API_CATCH(h)
+int mgps_up_stroke_fused(const mgps_solver *h, int level, int *fused)
+try {
+    if (!h || !fused || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
+    *fused = upStrokeFuses(h, level, nullptr, nullptr, nullptr, false) ? 1 : 0;
     return MGPS_OK;
 }
 MGPS_API_CATCH(h)

@@ -406,6 +406,12 @@ class GeometricMultigridPoissonSolver:
         check(lib().mgps_residual_restrict_fused(self.h, int(level), C.byref(f)), self.h)
         return bool(f.value)
 
+    def up_stroke_fused(self, level=0):
+        """mgps_up_stroke_fused: does an up-stroke of this level run the prolongation inside its Jacobi sweep?"""
+        f = C.c_int()
+        check(lib().mgps_up_stroke_fused(self.h, int(level), C.byref(f)), self.h)
+        return bool(f.value)
+
     def stencil_kernel(self, level=0):
         """'quad' | 'plane' | 'scalar': the kernel the Jacobi / residual / A.x sweeps of `level` launch"""
         k = C.c_int()

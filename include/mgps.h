@@ -469,6 +469,12 @@ int mgps_band_stage_form(const mgps_solver *h, int level, int *form);
  * the residual grid.  By size (x-y planes >= 4 MiB) on levels whose shape the pair takes; MGPS_FUSE_RR=0 / 1 forces it off /
  * onto every level that fits (tests).  The same products either way, added along z first instead of last. */
 int mgps_residual_restrict_fused(const mgps_solver *h, int level, int *fused);
+/* *fused = 1 when an up-stroke of level `level` runs its prolongation inside the Jacobi sweep (prolongJacobiPlaneKernel, and the
+ * closure launch reading x + 4 P e; no prolongation pass), 0 when the prolongation is a pass of its own.  By size (x-y planes
+ * >= 4 MiB) on single-device fp32 Jacobi levels with band boxes and plane blocks, one post-sweep; MGPS_FUSE_UP=0 / 1 forces it
+ * off / onto every level where it is valid (tests).  The stroke that gathers <z, r> for MG-PCG keeps the separate pass on level 0.
+ * The same bits either way. */
+int mgps_up_stroke_fused(const mgps_solver *h, int level, int *fused);
 /* kept for callers of round 4's ABI: always 0.  Round 4 queued the ghost exchanges that follow a sweep on a second stream beside
  * the sweep's interior part; round 5 runs every exchange on the solver's stream until a first run on real links has shown
  * where the time goes. */
