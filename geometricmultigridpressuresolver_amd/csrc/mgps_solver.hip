@@ -568,9 +568,13 @@ int haloListExchange(mgps_solver *h, int l, float *a0, float *a1, bool withPlane
     return MGPS_OK;
 }
 
-// true: the band stage of level l leaves the ghost planes of x complete (never since round 5: the box form of a cut level exchanges
-// the planes the next operator reads when it needs them)
-bool bandStageCompletesGhosts(const mgps_solver *, int) { return false; }
+// the next n partial-sum slots of the gathered dot (mgps_solver::gatherDot)
+double *takeDotSink(mgps_solver *h, unsigned n)
+{
+    double *p = h->dotPartials + h->dotUsed;
+    h->dotUsed += n;
+    return p;
+}
 
 // the level runs the box form of the fused band stage (BandBoxes: whole-grid levels, options.fuse_band_passes)
 // (a cut level of a slab run: every rank runs the box protocol, also a rank whose planes hold no band cell)
@@ -587,19 +591,9 @@ const GridP &boxGrid(const mgps_solver *h, int l) { return h->lv[l].boxForm ? h-
 int bandPasses(mgps_solver *h, int l, float *x, const float *b, GhostMode first, bool dot = false)
 {
     DevLevel &L = h->lv[l];
-    auto sink = [&]() -> double * {
-        if (!dot || L.nband <= 0) return nullptr;
-        double *p = h->dotPartials + h->dotUsed;
-        h->dotUsed += bandScatterBlocks(L.nband);
-        return p;
-    };
     if (levelHasBoxes(h, l)) {  // level is not cut: no exchanges.  No snapshot of x exists here: out of place into the level's
                                 // residual grid (free during a stroke), then the band cells copied back
-        double *s = nullptr;
-        if (dot) {
-            s = h->dotPartials + h->dotUsed;
-            h->dotUsed += unsigned(L.bandBoxes.ngroups);
-        }
+        double *s = dot ? takeDotSink(h, unsigned(L.bandBoxes.ngroups)) : nullptr;
         if (x == L.r || b == L.r) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "band stage: the level's residual grid is its scratch");
         // (a cut level: the boundary plane and the neighbours' cells the boxes read arrive first, x and rhs in one message)
         if (L.boxForm) MGPS_TRY(haloListExchange(h, l, x, const_cast<float *>(b), true));
@@ -609,7 +603,8 @@ int bandPasses(mgps_solver *h, int l, float *x, const float *b, GhostMode first,
     }
     for (int it = 0; it < h->opt.band_iterations; ++it) {
         MGPS_TRY(exchangeGhosts(h, l, x, it == 0 ? first : GHOST_BAND));
-        MGPS_LAUNCH(h, launchBandJacobi(h->stream, L.g, x, b, L.band, L.nband, L.bandTmp, h->opt.jacobi_weight, sink()));
+        double *sink = dot && L.nband > 0 ? takeDotSink(h, bandScatterBlocks(L.nband)) : nullptr;
+        MGPS_LAUNCH(h, launchBandJacobi(h->stream, L.g, x, b, L.band, L.nband, L.bandTmp, h->opt.jacobi_weight, sink));
     }
     return MGPS_OK;
 }
@@ -663,6 +658,13 @@ void stageFlush(mgps_solver *h)
     h->stageMarks.clear();
 }
 
+// end of a V-cycle for the stage timers (profiling without print_stats: the marks pile up until mgps_stage_times reads them)
+void stageCycleDone(mgps_solver *h)
+{
+    if (stageTimingOn(h)) ++h->stageCycles;
+    if (h->opt.print_stats) stageFlush(h);
+}
+
 // measurement hook: an event pair strictly around the launches of a fine-level full-domain sweep (after its ghost
 // exchange, so that on slab runs the figure is kernel time, not kernel + communication time)
 int profMark(mgps_solver *h, bool begin)
@@ -678,41 +680,43 @@ int profMark(mgps_solver *h, bool begin)
     if (!begin) h->profUsed += 2;
     return MGPS_OK;
 }
+// the sweep timer: when `on`, an event pair around what `launch` enqueues (one launch of a sweep) and `sweeps` more full sweeps
+// in profSweeps (a Gauss-Seidel sweep is two colour launches: the second one counts it)
+template <class Launch> int timedSweep(mgps_solver *h, bool on, int sweeps, Launch &&launch)
+{
+    if (on) MGPS_TRY(profMark(h, true));
+    MGPS_TRY(launch());
+    if (!on) return MGPS_OK;
+    MGPS_TRY(profMark(h, false));
+    h->profSweeps += sweeps;
+    return MGPS_OK;
+}
+// the sweeps the sweep timer takes: the fine level's
+inline bool sweepTimed(const mgps_solver *h, int l) { return h->profiling && l == 0; }
 
-// snap: the tiles the band boxes read also leave their result in the level's residual grid (see gsStrokeSnapshots)
+// snap: the tiles the band boxes read also leave their result in the level's residual grid (see SF_GS_SNAPSHOT)
 int gsHalfSweep(mgps_solver *h, int l, float *x, const float *b, int odd, int forward, GhostMode ghosts = GHOST_FULL, bool dot = false,
-                bool timed = false, bool snap = false)
+                bool snap = false, bool timed = false, int sweeps = 0)
 {
     DevLevel &L = h->lv[l];
     MGPS_TRY(exchangeGhosts(h, l, x, ghosts));  // the other colour's tiles across the cut changed in the previous pass
-    double *sink = nullptr;
-    if (dot) {  // every tile is swept once per sweep: its values after its colour's pass are the sweep's
-        sink = h->dotPartials + h->dotUsed;
-        h->dotUsed += unsigned(L.npure[odd] + L.nmixed[odd]);
-    }
-    if (timed) MGPS_TRY(profMark(h, true));
-    MGPS_LAUNCH(h, launchTiledGS(h->stream, L.g, x, b, L.pure[odd], L.npure[odd], L.mixed[odd], L.nmixed[odd],
-                                 L.tileBndStart, forward, sink, snap ? L.r : nullptr, snap ? L.snapTile : nullptr));
-    if (timed) MGPS_TRY(profMark(h, false));
-    return MGPS_OK;
+    // (dot: every tile is swept once per sweep: its values after its colour's pass are the sweep's)
+    double *sink = dot ? takeDotSink(h, unsigned(L.npure[odd] + L.nmixed[odd])) : nullptr;
+    return timedSweep(h, timed, sweeps, [&]() -> int {
+        MGPS_LAUNCH(h, launchTiledGS(h->stream, L.g, x, b, L.pure[odd], L.npure[odd], L.mixed[odd], L.nmixed[odd], L.tileBndStart, forward, sink,
+                                     snap ? L.r : nullptr, snap ? L.snapTile : nullptr));
+        return MGPS_OK;
+    });
+}
+// one Gauss-Seidel sweep: odd tiles forward, then even tiles forward down (MG.cpp:466-479); even tiles backward, then odd tiles
+// backward up (MG.cpp:740-751).  `before`: what the ghosts of x need before the first colour pass
+int gsSweep(mgps_solver *h, int l, float *x, const float *b, bool down, GhostMode before, bool dot, bool snap = false)
+{
+    const int first = down ? 1 : 0, forward = down ? 1 : 0;
+    MGPS_TRY(gsHalfSweep(h, l, x, b, first, forward, before, dot, snap, sweepTimed(h, l), 0));
+    return gsHalfSweep(h, l, x, b, 1 - first, forward, GHOST_FULL, dot, snap, sweepTimed(h, l), 1);
 }
 
-// Gauss-Seidel strokes on a level with band boxes (round 4).  The sweep runs in place, so no closure launch can compute "what the
-// sweep will hold"; but the box launch only must not read what another group writes.  Whoever writes the iterate last before a
-// band stage therefore leaves a copy of the cells the boxes read in the level's residual grid (free during a stroke) -- the
-// Gauss-Seidel tile kernels after their colour pass, the prolongation in front of an up-stroke; only tiles flagged in
-// L.snapTile, a fifth of the tiles on the cube -- and the stage reads that snapshot and writes the iterate IN PLACE: one launch
-// per stage instead of "out of place + copy" (round 3: bandBoxCopyKernel 39 us per stage at 512^3, and the plugin's own
-// smoother 10 % slower than in round 2).  A stroke that starts from the cleared iterate needs no snapshot: nothing is read.
-// MGPS_GS_SNAPSHOT=0: the round-3 form (A/B).
-bool gsStrokeSnapshots(const mgps_solver *h, int l, const float *cur, const float *b)
-{
-    static const bool allowed = [] {
-        const char *e = getenv("MGPS_GS_SNAPSHOT");
-        return !(e && e[0] == '0');
-    }();
-    return allowed && h->useGS && !h->dist && h->opt.band_iterations > 0 && levelHasBoxes(h, l) && cur != h->lv[l].r && b != h->lv[l].r;
-}
 int ensureSnapTiles(mgps_solver *h, int l)
 {
     DevLevel &L = h->lv[l];
@@ -722,20 +726,87 @@ int ensureSnapTiles(mgps_solver *h, int l)
     MGPS_LAUNCH(h, launchMarkSnapTiles(h->stream, L.g, L.bandBoxes, L.snapTile));
     return MGPS_OK;
 }
+int ensureKeepBits(mgps_solver *h, int l)
+{
+    DevLevel &L = h->lv[l];
+    if (L.keepBits) return MGPS_OK;
+    MGPS_TRY(devAlloc(h, &L.keepBits, L.d.cells() / 32, true));
+    MGPS_LAUNCH(h, launchMarkClosure(h->stream, L.g, L.bandBoxes, L.keepBits));
+    return MGPS_OK;
+}
 
-// A down-stroke that starts from the cleared iterate (MG.cpp:439-440, 566) can skip the clearing launch when it runs as "sweep,
-// closure launch, plain launch" on a level that takes the quad or the plane-marching sweep: both readers of the iterate take it as zero, and the grid
-// itself becomes the stroke's spare.  Own grids only: their chunks without active cells hold 0 already.
+// The forms a stroke runs in: 3 x band Jacobi -> full-domain smoother -> 3 x band Jacobi (MG.cpp:445-513 down, 806-879 up), the
+// smoother run options.pre_sweeps (down) / post_sweeps (up) times.  strokeForm picks one; smoothStroke runs it.
+enum StrokeForm {
+    SF_GS_SNAPSHOT,    // Gauss-Seidel, band stages in place on a snapshot (gsSnapshotStroke)
+    SF_THREE_LAUNCH,   // Jacobi, one sweep: closure launch, sweep, plain launch (threeLaunchStroke)
+    SF_FRONT,          // the same with the closure launch and the sweep merged (frontStroke)
+    SF_PROLONG_FUSED,  // an up-stroke of the three-launch form with the prolongation inside its first two launches (prolongFusedStroke)
+    SF_FIRST_FUSED,    // Jacobi, several sweeps: the first band stage and the first sweep in two launches (firstFusedStroke)
+    SF_GENERIC,        // band passes, sweeps, band passes
+};
+
+// The form of a stroke of level l: cur holds the iterate, other its Jacobi partner, b the rhs; dot: the stroke gathers <z, r>
+// (mgps_solver::gatherDot).  The box forms need the level's residual grid as their scratch: none of the three may be it
+// (nullptr: the public queries, which ask about the cycle's own grids).
+//
+// SF_GS_SNAPSHOT (round 4): a Gauss-Seidel sweep runs in place, so no closure launch can compute "what the sweep will hold";
+// but the box launch only must not read what another group writes.  Whoever writes the iterate last before a band stage
+// therefore leaves a copy of the cells the boxes read in the level's residual grid (free during a stroke) -- the Gauss-Seidel
+// tile kernels after their colour pass, the prolongation in front of an up-stroke; only tiles flagged in L.snapTile, a fifth of
+// the tiles on the cube -- and the stage reads that snapshot and writes the iterate IN PLACE: one launch per stage instead of
+// "out of place + copy" (round 3: bandBoxCopyKernel 39 us per stage at 512^3, and the plugin's own smoother 10 % slower than in
+// round 2).  A stroke that starts from the cleared iterate needs no snapshot: nothing is read.  MGPS_GS_SNAPSHOT=0: the round-3
+// form (A/B).
+//
+// SF_PROLONG_FUSED (prolongJacobiPlaneKernel, round 6): instead of "prolongation (x'' = x' + 4 P e in place), closure launch,
+// sweep, plain launch" three launches -- the closure launch and the sweep read x' and the coarse correction e and form x'' where
+// they stage it; the plain launch is unchanged.  The fine level's prolongation pass (a read-modify-write of the iterate, 1.27 ms
+// at 1024^3) is gone.  Single-device fp32 strokes on levels not in box form that kept their plane blocks; not a stroke that
+// gathers <z, r> (its sweep is the dot launch).  By size: x-y planes of 4 MiB and more.  Same-box A/B (LABNOTES R6): 1024^3
+// 106.5 -> 118.0 cycles/s; 512^3 with the path forced on 658.1 -> 664.8 (+1.0 %, inside the box-to-box spread of 2.5 %): 512^2
+// planes keep the separate pass.  The sweep timer takes the fused launch -- the up-stroke's sweep -- so profiling does not
+// switch it off.  MGPS_FUSE_UP=0: never (A/B); =1: every level where it is valid (tests).
+//
+// SF_FRONT (launchStrokeFront): whole-grid levels that take the quad sweep, up to 2^24 cells (a 256^3 level) -- where a launch is
+// a latency chain, one chain instead of two (512^3 level: 618-629 -> 565-593 cycles/s merged).  Stage timers and the sweep timer
+// want the launches apart.
+StrokeForm strokeForm(const mgps_solver *h, int l, bool down, const float *cur, const float *other, const float *b, bool dot)
+{
+    static const bool gsSnapshots = [] {
+        const char *e = getenv("MGPS_GS_SNAPSHOT");
+        return !(e && e[0] == '0');
+    }();
+    static const int fuseUp = [] {  // -1: by size
+        const char *e = getenv("MGPS_FUSE_UP");
+        return !e ? -1 : (e[0] == '0' ? 0 : 1);
+    }();
+    const DevLevel &L = h->lv[l];
+    const bool boxes = h->opt.band_iterations > 0 && levelHasBoxes(h, l) && (!L.r || (cur != L.r && other != L.r && b != L.r));
+    if (h->useGS) return boxes && gsSnapshots && !h->dist ? SF_GS_SNAPSHOT : SF_GENERIC;
+    const int reps = down ? h->opt.pre_sweeps : h->opt.post_sweeps;
+    if (!boxes || reps != 1) return boxes && reps > 1 && !L.boxForm ? SF_FIRST_FUSED : SF_GENERIC;
+    const bool planes = size_t(L.g.nx) * L.g.ny * sizeof(float) >= kPlaneSweepMinPlaneBytes;
+    if (!down && fuseUp != 0 && (fuseUp > 0 || planes) && l + 1 < int(h->lv.size()) && !dot && !h->dist && !h->tailOfSlabRun && h->opt.precision == 0 &&
+        !L.boxForm && prolongJacobiPlaneFits(L.g) && boxPlaneFits(L.d))
+        return SF_PROLONG_FUSED;
+    if (!dot && !sweepTimed(h, l) && !stageTimingOn(h) && !h->dist && L.d.cells() <= (size_t(1) << 24) && stencilKernelOf(L.g) == 1 && (L.d.cells() & 31) == 0)
+        return SF_FRONT;
+    return SF_THREE_LAUNCH;
+}
+
+// A down-stroke that starts from the cleared iterate (MG.cpp:439-440, 566) can skip the clearing launch when it runs as "closure
+// launch, sweep, plain launch" on a level that takes the quad or the plane-marching sweep: both readers of the iterate take it as
+// zero, and the grid itself becomes the stroke's spare.  Own grids only: their chunks without active cells hold 0 already.
+// (a slab run: cut levels in box form -- the stroke's first message then carries the rhs at the neighbours' cells and nothing of the iterate)
 bool strokeTakesZero(const mgps_solver *h, int l, const float *cur, const float *other, const float *b, bool dot)
 {
     static const bool allowed = [] {  // MGPS_ZERO_START=0: clear and read the grid (A/B timing)
         const char *e = getenv("MGPS_ZERO_START");
         return !(e && e[0] == '0');
     }();
-    const DevLevel &L = h->lv[l];
-    // (a slab run: cut levels in box form -- the stroke's first message then carries the rhs at the neighbours' cells and nothing of the iterate)
-    return allowed && !dot && (!h->dist || L.boxForm) && !h->useGS && h->opt.pre_sweeps == 1 && h->opt.band_iterations > 0 && levelHasBoxes(h, l) && stencilKernelOf(L.g) != 3 &&
-           !(h->profiling && l == 0) && cur != L.r && other != L.r && b != L.r;
+    const StrokeForm f = strokeForm(h, l, true, cur, other, b, dot);
+    return allowed && !dot && (f == SF_THREE_LAUNCH || f == SF_FRONT) && (!h->dist || h->lv[l].boxForm) && stencilKernelOf(h->lv[l].g) != 3 && !sweepTimed(h, l);
 }
 
 // Residual + restriction of a down-stroke without the residual grid (launchResidualZ + launchRestrictXY): whole-grid fp32 levels
@@ -745,13 +816,14 @@ bool strokeTakesZero(const mgps_solver *h, int l, const float *cur, const float 
 // workgroups of 1024 threads are one and a half rounds of the chip, and the residual it never writes would have stayed in the
 // Infinity Cache); 256^3 0.027 + 0.019 against 0.048 + 0.014.  MGPS_FUSE_RR=0: never; =1: every level that fits (tests).  The
 // terms of a coarse cell are added along z first instead of last: the last bits of the coarse rhs differ from the separate passes'.
+// (the binary16 fine level of a mixed-precision cycle takes its own pair: vcycleMixed)
 bool residualRestrictFuses(const mgps_solver *h, int l)
 {
     static const int mode = [] {  // -1: by size
         const char *e = getenv("MGPS_FUSE_RR");
         return !e ? -1 : (e[0] == '0' ? 0 : 1);
     }();
-    if (mode == 0 || l + 1 >= int(h->lv.size())) return false;
+    if (mode == 0 || l + 1 >= int(h->lv.size()) || (h->opt.precision != 0 && l == 0)) return false;
     const GridP &F = h->lv[l].g;
     if (mode < 0 && size_t(F.nx) * F.ny * sizeof(float) < kPlaneSweepMinPlaneBytes) return false;
     return residualRestrictFits(F, h->lv[l + 1].g);
@@ -790,55 +862,120 @@ int residualRestrict(mgps_solver *h, int l, const float *x, const float *rhs, fl
     return MGPS_OK;
 }
 
-// The closure launch and the sweep of a stroke in one launch (launchStrokeFront): whole-grid levels that take the quad sweep, up to
-// 2^24 cells (a 256^3 level) -- where a launch is a latency chain, one chain instead of two
-bool strokeFrontMerges(const mgps_solver *h, int l)
+// the prolongation in front of an up-stroke, cur += 4 P coarse (MG.cpp:695-784 coarser, 787-880 fine); snap: the cells the band
+// boxes read also into the level's residual grid (SF_GS_SNAPSHOT)
+int prolongAdd(mgps_solver *h, int l, float *cur, float *coarse, bool snap)
 {
-    constexpr size_t maxCells = size_t(1) << 24;
-    const DevLevel &L = h->lv[l];
-    return !h->dist && L.d.cells() <= maxCells && stencilKernelOf(L.g) == 1 && (L.d.cells() & 31) == 0;  // (512^3 level: 618-629 -> 565-593 cycles/s merged)
+    DevLevel &F = h->lv[l];
+    StageScope scope(h, ST_PROLONG, l);
+    MGPS_TRY(exchangeGhosts(h, l + 1, coarse));
+    if (snap) MGPS_TRY(ensureSnapTiles(h, l));
+    MGPS_LAUNCH(h, launchProlongAdd(h->stream, F.g, cur, coarse, snap ? F.r : nullptr, snap ? F.snapTile : nullptr));
+    return MGPS_OK;
 }
-// An up-stroke whose Jacobi sweep takes the prolongation in (prolongJacobiPlaneKernel, round 6): instead of "prolongation (x'' =
-// x' + 4 P e in place), closure launch, sweep, plain launch" three launches -- the closure launch and the sweep read x' and the
-// coarse correction e and form x'' where they stage it; the plain launch is unchanged.  The fine level's prolongation pass (a
-// read-modify-write of the iterate, 1.27 ms at 1024^3) is gone.  Single-device fp32 Jacobi strokes of one post-sweep on levels
-// with band boxes (not in box form) that kept their plane blocks; not a stroke that gathers <z, r> (its sweep is the dot launch).
-// By size: x-y planes of 4 MiB and more.  Same-box A/B (LABNOTES R6): 1024^3 106.5 -> 118.0 cycles/s; 512^3 with the path forced
-// on 658.1 -> 664.8 (+1.0 %, inside the box-to-box spread of 2.5 %): 512^2 planes keep the separate pass.  The sweep timer takes the fused launch -- the
-// up-stroke's sweep -- so profiling does not switch it off.  MGPS_FUSE_UP=0: never (A/B); =1: every level where it is valid (tests).
-bool upStrokeFuses(const mgps_solver *h, int l, const float *cur, const float *other, const float *b, bool dot)
-{
-    static const int mode = [] {  // -1: by size
-        const char *e = getenv("MGPS_FUSE_UP");
-        return !e ? -1 : (e[0] == '0' ? 0 : 1);
-    }();
-    if (mode == 0 || l + 1 >= int(h->lv.size())) return false;
-    const DevLevel &L = h->lv[l];
-    if (mode < 0 && size_t(L.g.nx) * L.g.ny * sizeof(float) < kPlaneSweepMinPlaneBytes) return false;
-    const bool r = L.r != nullptr;
-    return !dot && !h->useGS && !h->dist && !h->tailOfSlabRun && h->opt.precision == 0 && h->opt.band_iterations > 0 && h->opt.post_sweeps == 1 &&
-           levelHasBoxes(h, l) && !L.boxForm && prolongJacobiPlaneFits(L.g) && boxPlaneFits(L.d) && (!r || (cur != L.r && other != L.r && b != L.r));
-}
-// `cur` holds the iterate before the prolongation, `coarse` the correction of the level below; on return cur is the smoothed
-// iterate (smoothStroke's three-launch form, with x'' = cur + 4 P coarse formed inside the first two launches)
-int fusedUpStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, const float *coarse)
+
+// SF_GS_SNAPSHOT.  fresh (down-strokes): the iterate was cleared; preSnap (up-strokes): the prolongation left the boxes' input in L.r
+int gsSnapshotStroke(mgps_solver *h, int l, float *cur, const float *b, bool down, bool fresh, bool dot, bool preSnap)
 {
     DevLevel &L = h->lv[l];
-    const bool timed = h->profiling && l == 0;
+    MGPS_TRY(ensureSnapTiles(h, l));
+    {
+        StageScope scope(h, ST_BAND, l);
+        if (down && fresh)  // the iterate was cleared (MG.cpp:439-440, 566): nothing is read, the stage writes it in place
+            MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, nullptr, b, cur, nullptr, h->opt.jacobi_weight));
+        else if (preSnap)
+            MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight));
+        else
+            MGPS_TRY(bandPasses(h, l, cur, b, GHOST_NONE));
+    }
+    const int reps = down ? h->opt.pre_sweeps : h->opt.post_sweeps;
+    for (int rep = 0; rep < reps; ++rep) {
+        StageScope scope(h, ST_SMOOTH, l);
+        const bool last = rep == reps - 1;  // (the last sweep's values are the stage's input)
+        MGPS_TRY(gsSweep(h, l, cur, b, down, GHOST_NONE, dot && last, last));
+    }
+    StageScope scope(h, ST_BAND, l);
+    double *sink = dot ? takeDotSink(h, unsigned(L.bandBoxes.ngroups)) : nullptr;
+    // (old values: the snapshot holds every band cell of a flagged tile)
+    MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight, false, MixScale{}, sink, L.r));
+    return MGPS_OK;
+}
+
+// SF_THREE_LAUNCH: "band passes, sweep, band passes" in three launches, nothing scattered (launchBandBox): the closure launch, which
+// computes on the band closure what the sweep would write there after the band passes and leaves it as a snapshot in the level's
+// residual grid (free during a stroke); the sweep over the un-smoothed grid; the second band stage, which reads the snapshot and
+// writes the band cells AND the closure-output cells into the sweep's output (4 bytes less per closure cell than a closure launch
+// that patches the sweep's output itself: +1.5 % at 512^3, +0.7 % at 1024^3).  The two launches before the plain one are
+// independent of each other; running the closure launch on a second stream beside the sweep was measured and lost -- 1024^3:
+// sweep 1.72 -> 2.02 ms with the closure launch at 1.57 ms beside it, cycle 10.81 -> 10.91 ms; on small levels the two event hops
+// cost ~17 us per stroke.
+// A cut level of a slab run (DevLevel::boxForm) runs the same three launches on its own planes with two messages: before the
+// closure launch the boundary plane of the iterate (the sweep's ghost plane) and, packed, iterate and rhs at the neighbours' cells
+// its regions read (up to depth + 1 planes deep: they live in the deep ghost planes of the grids); before the plain launch the
+// snapshot at the same cells.  The stroke leaves the ghost planes of its result stale: whoever reads across the cut next
+// exchanges them (the residual, the finer level's prolongation).
+int threeLaunchStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, bool dot, bool xZero)
+{
+    DevLevel &L = h->lv[l];
+    const float *src = xZero ? nullptr : cur;
+    {
+        StageScope scope(h, ST_BAND, l);
+        if (L.boxForm && xZero) MGPS_TRY(haloListExchange(h, l, const_cast<float *>(b), nullptr, false));  // (the iterate is zero on every rank: the rhs alone)
+        else if (L.boxForm) MGPS_TRY(haloListExchange(h, l, cur, const_cast<float *>(b), true));
+        MGPS_LAUNCH(h, launchBandBox(h->stream, boxGrid(h, l), L.bandBoxes, true, src, b, nullptr, L.r, h->opt.jacobi_weight));
+    }
+    {
+        StageScope scope(h, ST_SMOOTH, l);
+        MGPS_TRY(timedSweep(h, sweepTimed(h, l), 1, [&]() -> int {
+            if (dot) {
+                unsigned used = 0;
+                MGPS_LAUNCH(h, launchStencilDot(h->stream, OP_JACOBI, L.g, other, cur, b, h->opt.jacobi_weight, h->dotPartials + h->dotUsed, &used));
+                h->dotUsed += used;
+                return MGPS_OK;
+            }
+            GridP gs = L.g;
+            gs.nbnd = 0;  // every BOUNDARY cell lies in the band closure: the box launches compute the general ones as well
+            MGPS_LAUNCH(h, launchStencil(h->stream, OP_JACOBI, gs, other, src, b, h->opt.jacobi_weight, true));
+            return MGPS_OK;
+        }));
+    }
+    double *sinkB = dot ? takeDotSink(h, unsigned(L.bandBoxes.ngroups)) : nullptr;
+    StageScope scope(h, ST_BAND, l);
+    std::swap(cur, other);
+    if (L.boxForm) MGPS_TRY(haloListExchange(h, l, L.r, nullptr, false));
+    // (the gathered dot: the sweep left sum x' b with its own values everywhere; this launch adds (new - sweep's) b on every cell it writes)
+    MGPS_LAUNCH(h, launchBandBox(h->stream, boxGrid(h, l), L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight, false, MixScale{}, sinkB, cur, true));
+    return MGPS_OK;
+}
+
+// SF_FRONT: the closure launch and the sweep of SF_THREE_LAUNCH in one launch, then the plain launch
+int frontStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, bool xZero)
+{
+    DevLevel &L = h->lv[l];
+    MGPS_TRY(ensureKeepBits(h, l));
+    MGPS_LAUNCH(h, launchStrokeFront(h->stream, L.g, L.bandBoxes, other, xZero ? nullptr : cur, b, L.r, h->opt.jacobi_weight, L.keepBits));
+    std::swap(cur, other);
+    MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight, false, MixScale{}, nullptr, nullptr, true));
+    return MGPS_OK;
+}
+
+// SF_PROLONG_FUSED: `cur` holds the iterate before the prolongation, `coarse` the correction of the level below; on return cur is
+// the smoothed iterate (SF_THREE_LAUNCH with x'' = cur + 4 P coarse formed inside the first two launches)
+int prolongFusedStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, const float *coarse)
+{
+    DevLevel &L = h->lv[l];
     {
         StageScope scope(h, ST_BAND, l);
         MGPS_LAUNCH(h, launchBandBoxClosureProlonged(h->stream, L.g, L.bandBoxes, cur, coarse, b, L.r, h->opt.jacobi_weight));
     }
     {
         StageScope scope(h, ST_SMOOTH, l);
-        if (timed) MGPS_TRY(profMark(h, true));
         GridP gs = L.g;
-        gs.nbnd = 0;  // every BOUNDARY cell lies in the band closure (see smoothStroke)
-        MGPS_LAUNCH(h, launchProlongJacobi(h->stream, gs, other, cur, b, coarse, h->opt.jacobi_weight));
-        if (timed) {
-            MGPS_TRY(profMark(h, false));
-            ++h->profSweeps;
-        }
+        gs.nbnd = 0;  // every BOUNDARY cell lies in the band closure (see threeLaunchStroke)
+        MGPS_TRY(timedSweep(h, sweepTimed(h, l), 1, [&]() -> int {
+            MGPS_LAUNCH(h, launchProlongJacobi(h->stream, gs, other, cur, b, coarse, h->opt.jacobi_weight));
+            return MGPS_OK;
+        }));
     }
     StageScope scope(h, ST_BAND, l);
     std::swap(cur, other);
@@ -846,181 +983,88 @@ int fusedUpStroke(mgps_solver *h, int l, float *&cur, float *&other, const float
     return MGPS_OK;
 }
 
-int ensureKeepBits(mgps_solver *h, int l)
+// the full-domain sweeps from sweep `from` on, then the last band stage (SF_GENERIC, and SF_FIRST_FUSED after its first sweep).
+// `before`: what the ghosts of cur need before sweep `from`
+int sweepsThenBands(mgps_solver *h, int l, float *&cur, float *&other, const float *b, bool down, int from, GhostMode before, bool dot)
 {
     DevLevel &L = h->lv[l];
-    if (L.keepBits) return MGPS_OK;
-    MGPS_TRY(devAlloc(h, &L.keepBits, L.d.cells() / 32, true));
-    MGPS_LAUNCH(h, launchMarkClosure(h->stream, L.g, L.bandBoxes, L.keepBits));
-    return MGPS_OK;
-}
-
-// 3 x band Jacobi -> full-domain smoother -> 3 x band Jacobi (MG.cpp:445-513 down, 806-879 up).
-// The smoother runs options.pre_sweeps (down) / post_sweeps (up) times; the reference's count is one.
-// Jacobi runs out of place: `cur` holds the current iterate, `other` the spare grid; they swap.
-// ghostsFresh: the ghosts of `cur` are known to be complete on entry (all zero after a clear).
-// Ghost traffic of a stroke: whole planes after whatever rewrote the whole grid (the caller's
-// prolongation / initial guess, the full-domain smoother), packed band cells after band passes.
-// dot: see mgps_solver::gatherDot (the caller folds the partials afterwards)
-// xZero: `cur` is known to be zero everywhere and was NOT cleared (strokeTakesZero said the stroke needs no copy of it): the sweep
-// and the closure launch take the iterate as zero
-// preSnap (Gauss-Seidel up-strokes): the prolongation left the band boxes' input in L.r (gsStrokeSnapshots)
-int smoothStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, bool down, bool ghostsFresh, bool dot = false, bool xZero = false,
-                 bool preSnap = false)
-{
-    DevLevel &L = h->lv[l];
-    const bool bands = h->opt.band_iterations > 0;
-    if (gsStrokeSnapshots(h, l, cur, b)) {
-        MGPS_TRY(ensureSnapTiles(h, l));
-        const bool timed = h->profiling && l == 0;
-        {
-            StageScope scope(h, ST_BAND, l);
-            if (down && ghostsFresh)  // the iterate was cleared (MG.cpp:439-440, 566): nothing is read, the stage writes it in place
-                MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, nullptr, b, cur, nullptr, h->opt.jacobi_weight));
-            else if (preSnap)
-                MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight));
-            else
-                MGPS_TRY(bandPasses(h, l, cur, b, GHOST_NONE));
-        }
-        const int reps = down ? h->opt.pre_sweeps : h->opt.post_sweeps;
-        for (int rep = 0; rep < reps; ++rep) {
-            StageScope scope(h, ST_SMOOTH, l);
-            const bool d = dot && rep == reps - 1, sn = rep == reps - 1;  // (the last sweep's values are the stage's input)
-            if (down) {  // odd tiles forward, then even tiles forward (MG.cpp:466-479)
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 1, 1, GHOST_NONE, d, timed, sn));
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 0, 1, GHOST_NONE, d, timed, sn));
-            } else {  // even tiles backward, then odd tiles backward (MG.cpp:740-751)
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 0, 0, GHOST_NONE, d, timed, sn));
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 1, 0, GHOST_NONE, d, timed, sn));
-            }
-            if (timed) ++h->profSweeps;
-        }
-        StageScope scope(h, ST_BAND, l);
-        double *sink = nullptr;
-        if (dot) {
-            sink = h->dotPartials + h->dotUsed;
-            h->dotUsed += unsigned(L.bandBoxes.ngroups);
-        }
-        if (reps > 0)
-            MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight, false, MixScale{}, sink, L.r));  // (old values: the snapshot holds every band cell of a flagged tile)
-        else
-            MGPS_TRY(bandPasses(h, l, cur, b, GHOST_NONE, dot));
-        return MGPS_OK;
-    }
-    if (bands && !h->useGS && (down ? h->opt.pre_sweeps : h->opt.post_sweeps) == 1 && levelHasBoxes(h, l) && cur != L.r && other != L.r && b != L.r) {
-        // "band passes, sweep, band passes" in three launches, nothing scattered (launchBandBox): the closure launch, which
-        // computes on the band closure what the sweep would write there after the band passes and leaves it as a snapshot in
-        // the level's residual grid (free during a stroke); the sweep over the un-smoothed grid; the second band stage, which
-        // reads the snapshot and writes the band cells AND the closure-output cells into the sweep's output (4 bytes less per
-        // closure cell than a closure launch that patches the sweep's output itself: +1.5 % at 512^3, +0.7 % at 1024^3).  The two
-        // launches before the plain one are independent of each other; running the closure launch on a second stream beside the
-        // sweep was measured and lost -- 1024^3: sweep 1.72 -> 2.02 ms with the closure launch at 1.57 ms beside it, cycle 10.81 ->
-        // 10.91 ms; on small levels the two event hops cost ~17 us per stroke)
-        const bool timed = h->profiling && l == 0;
-        double *sinkB = nullptr;
-        const float *src = xZero ? nullptr : cur;
-        if (!dot && !timed && !stageTimingOn(h) && strokeFrontMerges(h, l)) {  // (stage timers and the sweep timer want the launches apart)
-            MGPS_TRY(ensureKeepBits(h, l));
-            MGPS_LAUNCH(h, launchStrokeFront(h->stream, L.g, L.bandBoxes, other, src, b, L.r, h->opt.jacobi_weight, L.keepBits));
-            std::swap(cur, other);
-            MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight, false, MixScale{}, nullptr, nullptr, true));
-            return MGPS_OK;
-        }
-        // A cut level of a slab run (DevLevel::boxForm) runs the same three launches on its own planes with two messages: before
-        // the closure launch the boundary plane of the iterate (the sweep's ghost plane) and, packed, iterate and rhs at the
-        // neighbours' cells its regions read (up to depth + 1 planes deep: they live in the deep ghost planes of the grids); before
-        // the plain launch the snapshot at the same cells.  The stroke leaves the ghost planes of its result stale: whoever reads
-        // across the cut next exchanges them (the residual, the finer level's prolongation).
-        {
-            StageScope scope(h, ST_BAND, l);
-            if (L.boxForm && xZero) MGPS_TRY(haloListExchange(h, l, const_cast<float *>(b), nullptr, false));  // (the iterate is zero on every rank: the rhs alone)
-            else if (L.boxForm) MGPS_TRY(haloListExchange(h, l, cur, const_cast<float *>(b), true));
-            MGPS_LAUNCH(h, launchBandBox(h->stream, boxGrid(h, l), L.bandBoxes, true, src, b, nullptr, L.r, h->opt.jacobi_weight));
-        }
-        {
-            StageScope scope(h, ST_SMOOTH, l);
-            if (timed) MGPS_TRY(profMark(h, true));
-            if (dot) {
-                unsigned used = 0;
-                MGPS_LAUNCH(h, launchStencilDot(h->stream, OP_JACOBI, L.g, other, cur, b, h->opt.jacobi_weight, h->dotPartials + h->dotUsed, &used));
-                h->dotUsed += used;
-                sinkB = h->dotPartials + h->dotUsed;
-                h->dotUsed += unsigned(L.bandBoxes.ngroups);
-            } else {
-                GridP gs = L.g;
-                gs.nbnd = 0;  // every BOUNDARY cell lies in the band closure: the box launches compute the general ones as well
-                MGPS_LAUNCH(h, launchStencil(h->stream, OP_JACOBI, gs, other, src, b, h->opt.jacobi_weight, true));
-            }
-            if (timed) {
-                MGPS_TRY(profMark(h, false));
-                ++h->profSweeps;
-            }
-        }
-        StageScope scope(h, ST_BAND, l);
-        std::swap(cur, other);
-        if (L.boxForm) MGPS_TRY(haloListExchange(h, l, L.r, nullptr, false));
-        // (the gathered dot: the sweep left sum x' b with its own values everywhere; this launch adds (new - sweep's) b on every cell it writes)
-        MGPS_LAUNCH(h, launchBandBox(h->stream, boxGrid(h, l), L.bandBoxes, false, L.r, b, cur, nullptr, h->opt.jacobi_weight, false, MixScale{}, sinkB, cur, true));
-        return MGPS_OK;
-    }
     const int reps = down ? h->opt.pre_sweeps : h->opt.post_sweeps;
-    // Several Jacobi sweeps per stroke (options.pre_sweeps / post_sweeps > 1, BASELINE config 1's "2 + 2") on a level with boxes: the
-    // first band stage and the first sweep as above -- sweep over the un-smoothed grid, then the closure launch writes what the
-    // sweep should hold on the band closure straight into its output (no snapshot: the next sweep reads the grid) -- two launches
-    // instead of three (band stage out of place, copy, sweep); the remaining sweeps and the last band stage as below
-    const bool firstFused = bands && !h->useGS && reps > 1 && levelHasBoxes(h, l) && !L.boxForm && cur != L.r && other != L.r && b != L.r;
-    if (firstFused) {
-        {
-            StageScope scope(h, ST_SMOOTH, l);
-            GridP gs = L.g;
-            gs.nbnd = 0;
-            const bool timedFirst = h->profiling && l == 0;  // (the sweep is a launch of its own here: the sweep timer takes it)
-            if (timedFirst) MGPS_TRY(profMark(h, true));
-            MGPS_LAUNCH(h, launchStencil(h->stream, OP_JACOBI, gs, other, cur, b, h->opt.jacobi_weight, true));
-            if (timedFirst) {
-                MGPS_TRY(profMark(h, false));
-                ++h->profSweeps;
-            }
-        }
-        StageScope scope(h, ST_BAND, l);
-        MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, true, cur, b, other, nullptr, h->opt.jacobi_weight));
-        std::swap(cur, other);
-    } else {
-        StageScope scope(h, ST_BAND, l);
-        MGPS_TRY(bandPasses(h, l, cur, b, ghostsFresh ? GHOST_NONE : GHOST_FULL));
-    }
-    // after the band passes only band cells are stale across the cut -- unless there were none
-    const GhostMode afterBands = bands ? GHOST_BAND : (ghostsFresh ? GHOST_NONE : GHOST_FULL);
-    const bool timed = h->profiling && l == 0;
-    for (int rep = firstFused ? 1 : 0; rep < reps; ++rep) {
+    for (int rep = from; rep < reps; ++rep) {
         StageScope scope(h, ST_SMOOTH, l);
-        const GhostMode before = rep == 0 ? afterBands : GHOST_FULL;  // a sweep rewrote everything
+        const GhostMode ghosts = rep == from ? before : GHOST_FULL;  // a sweep rewrote everything
         const bool d = dot && rep == reps - 1;  // <x, b> of the stroke's result: the last sweep's values
         if (h->useGS) {
-            if (down) {  // odd tiles forward, then even tiles forward (MG.cpp:466-479)
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 1, 1, before, d, timed));
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 0, 1, GHOST_FULL, d, timed));
-            } else {  // even tiles backward, then odd tiles backward (MG.cpp:740-751)
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 0, 0, before, d, timed));
-                MGPS_TRY(gsHalfSweep(h, l, cur, b, 1, 0, GHOST_FULL, d, timed));
-            }
-        } else {
-            MGPS_TRY(exchangeGhosts(h, l, cur, before));
-            if (timed) MGPS_TRY(profMark(h, true));
+            MGPS_TRY(gsSweep(h, l, cur, b, down, ghosts, d));
+            continue;
+        }
+        MGPS_TRY(exchangeGhosts(h, l, cur, ghosts));
+        MGPS_TRY(timedSweep(h, sweepTimed(h, l), 1, [&]() -> int {
             if (d) {
                 unsigned used = 0;
                 MGPS_LAUNCH(h, launchStencilDot(h->stream, OP_JACOBI, L.g, other, cur, b, h->opt.jacobi_weight, h->dotPartials + h->dotUsed, &used));
                 h->dotUsed += used;
             } else
                 MGPS_LAUNCH(h, launchStencil(h->stream, OP_JACOBI, L.g, other, cur, b, h->opt.jacobi_weight, true));
-            if (timed) MGPS_TRY(profMark(h, false));
-            std::swap(cur, other);
-        }
-        if (timed) ++h->profSweeps;
+            return MGPS_OK;
+        }));
+        std::swap(cur, other);
     }
     StageScope scope(h, ST_BAND, l);
-    MGPS_TRY(bandPasses(h, l, cur, b, GHOST_FULL, dot));  // the full-domain smoother rewrote everything
-    return MGPS_OK;
+    return bandPasses(h, l, cur, b, GHOST_FULL, dot);  // the full-domain smoother rewrote everything
+}
+
+// SF_FIRST_FUSED (options.pre_sweeps / post_sweeps > 1, BASELINE config 1's "2 + 2"): the first band stage and the first sweep as in
+// SF_THREE_LAUNCH -- sweep over the un-smoothed grid, then the closure launch writes what the sweep should hold on the band closure
+// straight into its output (no snapshot: the next sweep reads the grid) -- two launches instead of three (band stage out of place,
+// copy, sweep); the remaining sweeps and the last band stage as SF_GENERIC's
+int firstFusedStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, bool down, bool dot)
+{
+    DevLevel &L = h->lv[l];
+    {
+        StageScope scope(h, ST_SMOOTH, l);
+        GridP gs = L.g;
+        gs.nbnd = 0;
+        MGPS_TRY(timedSweep(h, sweepTimed(h, l), 1, [&]() -> int {
+            MGPS_LAUNCH(h, launchStencil(h->stream, OP_JACOBI, gs, other, cur, b, h->opt.jacobi_weight, true));
+            return MGPS_OK;
+        }));
+    }
+    {
+        StageScope scope(h, ST_BAND, l);
+        MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, true, cur, b, other, nullptr, h->opt.jacobi_weight));
+        std::swap(cur, other);
+    }
+    return sweepsThenBands(h, l, cur, other, b, down, 1, GHOST_FULL, dot);
+}
+
+// One stroke of level l in the form strokeForm picks.  Jacobi runs out of place: `cur` holds the current iterate, `other` the
+// spare grid; they swap.  Up-strokes (coarse: the correction of the level below) prolong it into cur first.
+// ghostsFresh: the ghosts of `cur` are known to be complete on entry (all zero after a clear).
+// Ghost traffic of a stroke: whole planes after whatever rewrote the whole grid (the caller's
+// prolongation / initial guess, the full-domain smoother), packed band cells after band passes.
+// dot: see mgps_solver::gatherDot (the caller folds the partials afterwards)
+// xZero: `cur` is known to be zero everywhere and was NOT cleared (strokeTakesZero said the stroke needs no copy of it): the sweep
+// and the closure launch take the iterate as zero
+int smoothStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, bool down, bool ghostsFresh, bool dot = false, bool xZero = false,
+                 float *coarse = nullptr)
+{
+    const StrokeForm form = strokeForm(h, l, down, cur, other, b, dot);
+    if (coarse && form != SF_PROLONG_FUSED) MGPS_TRY(prolongAdd(h, l, cur, coarse, form == SF_GS_SNAPSHOT));
+    switch (form) {
+    case SF_GS_SNAPSHOT: return gsSnapshotStroke(h, l, cur, b, down, ghostsFresh, dot, coarse != nullptr);
+    case SF_THREE_LAUNCH: return threeLaunchStroke(h, l, cur, other, b, dot, xZero);
+    case SF_FRONT: return frontStroke(h, l, cur, other, b, xZero);
+    case SF_PROLONG_FUSED: return prolongFusedStroke(h, l, cur, other, b, coarse);
+    case SF_FIRST_FUSED: return firstFusedStroke(h, l, cur, other, b, down, dot);
+    case SF_GENERIC: break;
+    }
+    {
+        StageScope scope(h, ST_BAND, l);
+        MGPS_TRY(bandPasses(h, l, cur, b, ghostsFresh ? GHOST_NONE : GHOST_FULL));
+    }
+    // after the band passes only band cells are stale across the cut -- unless there were none
+    const GhostMode afterBands = h->opt.band_iterations > 0 ? GHOST_BAND : (ghostsFresh ? GHOST_NONE : GHOST_FULL);
+    return sweepsThenBands(h, l, cur, other, b, down, 0, afterBands, dot);
 }
 
 int vcycle(mgps_solver *h, float *x, const float *b, bool useInitialGuess, bool ownGrid = false, bool wantDot = false);
@@ -1086,6 +1130,69 @@ int zeroOwnGrid(mgps_solver *h, int l, float *a, bool withGhosts)
     return MGPS_OK;
 }
 
+// the down-stroke of level l from the cleared iterate (MG.cpp:439-440, 566).  own: cur is one of the solver's own grids (see
+// zeroOwnGrid; the only kind strokeTakesZero may leave uncleared)
+int downStrokeFromZero(mgps_solver *h, int l, float *&cur, float *&other, const float *b, bool own, bool dot)
+{
+    const bool zero = own && strokeTakesZero(h, l, cur, other, b, dot);
+    if (zero) MGPS_TRY(poisonSpares(h, l, cur, other));
+    else if (own) MGPS_TRY(zeroOwnGrid(h, l, cur, true));
+    else MGPS_TRY(zeroGrid(h, cur, h->lv[l].d, h->dist));
+    return smoothStroke(h, l, cur, other, b, true, true, dot, zero);
+}
+
+// Levels first .. the bottom of the V and back (MG.cpp:519-784): x / spare are level first's iterate and its Jacobi partner, b its
+// rhs; on return x holds the level's result.  Level 0 (vcycle) comes with its down-stroke done; a coarser level starts from zero.
+// poll: options.interrupt is polled once per level and stroke (single-device fp32 cycles: the reference polls inside every
+// operator loop, e.g. Ops.h:319; slab runs poll between CG iterations only, where the ranks can agree)
+int cycleLevels(mgps_solver *h, int first, float *&x, float *spare, const float *b, bool poll)
+{
+    const int nlv = int(h->lv.size()), bottom = nlv - 1;
+    std::vector<float *> cur(nlv, nullptr), other(nlv, nullptr);
+    cur[first] = x;
+    other[first] = spare;
+    auto rhsOf = [&](int l) -> const float * { return l == first ? b : h->lv[l].b; };
+    auto stopRequested = [&] { return poll && h->opt.interrupt && h->opt.interrupt(h->opt.interrupt_user); };
+    for (int l = first; l < bottom; ++l) {  // MG.cpp:519-553 (fine), 557-667 (coarser)
+        DevLevel &F = h->lv[l], &C = h->lv[l + 1];
+        if (l > 0) {
+            if (stopRequested()) return failH(h, MGPS_ERR_INTERRUPTED, "mgps_apply_vcycle: interrupted");
+            if (l > first) {
+                cur[l] = F.x;
+                other[l] = F.tmp;
+            }
+            MGPS_TRY(downStrokeFromZero(h, l, cur[l], other[l], rhsOf(l), true, false));
+        }
+        if (residualRestrictFuses(h, l)) {
+            MGPS_TRY(residualRestrict(h, l, cur[l], rhsOf(l)));
+            continue;
+        }
+        {
+            StageScope scope(h, ST_RESIDUAL, l);
+            // (a cut level in box form: the stroke's last launch rewrote band and closure cells of a grid whose ghost planes are
+            // the sweep's input -- whole planes; per-pass band smoothing: only band cells changed since the last whole plane)
+            MGPS_TRY(exchangeGhosts(h, l, cur[l], F.boxForm ? GHOST_FULL : h->opt.band_iterations > 0 ? GHOST_BAND : GHOST_FULL));
+            MGPS_LAUNCH(h, launchStencil(h->stream, OP_RESIDUAL, F.g, F.r, cur[l], rhsOf(l), 0.f, true));
+        }
+        StageScope scope(h, ST_RESTRICT, l);
+        MGPS_TRY(exchangeGhosts(h, l, F.r));
+        MGPS_LAUNCH(h, launchRestrict(h->stream, C.g, C.b, F.r));
+    }
+    DevLevel &B = h->lv[bottom];
+    {
+        StageScope scope(h, ST_COARSE, bottom);
+        if (h->dist) MGPS_TRY(collapsedTail(h));
+        else MGPS_LAUNCH(h, launchCoarseSolve(h->stream, h->cn, h->cinv, h->ccells, B.x, B.b, h->cvec));  // MG.cpp:669-692
+    }
+    cur[bottom] = B.x;
+    for (int l = bottom - 1; l >= first; --l) {  // MG.cpp:695-784 (coarser), 787-880 (fine)
+        if (stopRequested()) return failH(h, MGPS_ERR_INTERRUPTED, "mgps_apply_vcycle: interrupted");
+        MGPS_TRY(smoothStroke(h, l, cur[l], other[l], rhsOf(l), false, false, h->gatherDot && l == 0, false, cur[l + 1]));
+    }
+    x = cur[first];
+    return MGPS_OK;
+}
+
 // ownGrid: x is one of the solver's own grids (see zeroOwnGrid).  wantDot (single-device runs, after ensurePcgGrids):
 // <x, b> of the result is left in h->resultDev as a by-product of the last stroke (mgps_solver::gatherDot)
 int vcycle(mgps_solver *h, float *x, const float *b, bool useInitialGuess, bool ownGrid, bool wantDot)
@@ -1100,124 +1207,15 @@ int vcycle(mgps_solver *h, float *x, const float *b, bool useInitialGuess, bool 
     }
     // levels this object smooths on: all but its last one (direct solve, or the collapse level of a
     // slab run), unless the whole hierarchy is a single level (MG.cpp:516-517)
-    const int nsmooth = nlv > 1 ? nlv - 1 : 1;
     const bool hasBottom = nlv > 1;
-    std::vector<float *> cur(nlv, nullptr), other(nlv, nullptr);
-    cur[0] = x;
-    other[0] = h->lv[0].tmp;
-    bool fresh = false, zero0 = false;
-    if (!useInitialGuess) {  // MG.cpp:439-440
-        zero0 = ownGrid && strokeTakesZero(h, 0, cur[0], other[0], b, h->gatherDot && !hasBottom);
-        if (zero0) MGPS_TRY(poisonSpares(h, 0, cur[0], other[0]));
-        else if (ownGrid) MGPS_TRY(zeroOwnGrid(h, 0, x, true));
-        else MGPS_TRY(zeroGrid(h, x, h->lv[0].d, h->dist));
-        fresh = true;
-    }
-    MGPS_TRY(smoothStroke(h, 0, cur[0], other[0], b, true, fresh, h->gatherDot && !hasBottom, zero0));
-    if (hasBottom) {
-        const float *rhs = b;
-        // options.interrupt is also polled once per level and stroke of a single-device cycle (the reference polls inside
-        // every operator loop, e.g. Ops.h:319); slab runs poll between CG iterations only, where the ranks can agree
-        auto stopRequested = [&] { return !h->dist && !h->tailOfSlabRun && h->opt.interrupt && h->opt.interrupt(h->opt.interrupt_user); };
-        for (int l = 0; l < nsmooth; ++l) {  // MG.cpp:519-553 (fine), 557-667 (coarser)
-            DevLevel &F = h->lv[l], &C = h->lv[l + 1];
-            if (l > 0 && stopRequested()) return failH(h, MGPS_ERR_INTERRUPTED, "mgps_apply_vcycle: interrupted");
-            if (l > 0) {
-                cur[l] = F.x;
-                other[l] = F.tmp;
-                rhs = F.b;
-                const bool zl = strokeTakesZero(h, l, cur[l], other[l], rhs, false);
-                if (!zl) MGPS_TRY(zeroOwnGrid(h, l, F.x, true));  // MG.cpp:566
-                else MGPS_TRY(poisonSpares(h, l, cur[l], other[l]));
-                MGPS_TRY(smoothStroke(h, l, cur[l], other[l], rhs, true, true, false, zl));
-            }
-            if (residualRestrictFuses(h, l)) {
-                MGPS_TRY(residualRestrict(h, l, cur[l], rhs));
-                continue;
-            }
-            {
-                StageScope scope(h, ST_RESIDUAL, l);
-                // (a cut level in box form: the stroke's last launch rewrote band and closure cells of a grid whose ghost planes are
-                // the sweep's input -- whole planes; per-pass band smoothing: only band cells changed since the last whole plane)
-                MGPS_TRY(exchangeGhosts(h, l, cur[l], F.boxForm ? GHOST_FULL : h->opt.band_iterations > 0 ? GHOST_BAND : GHOST_FULL));
-                MGPS_LAUNCH(h, launchStencil(h->stream, OP_RESIDUAL, F.g, F.r, cur[l], rhs, 0.f, true));
-            }
-            StageScope scope(h, ST_RESTRICT, l);
-            MGPS_TRY(exchangeGhosts(h, l, F.r));
-            MGPS_LAUNCH(h, launchRestrict(h->stream, C.g, C.b, F.r));
-        }
-        DevLevel &B = h->lv[nsmooth];
-        {
-            StageScope scope(h, ST_COARSE, nsmooth);
-            if (h->dist) MGPS_TRY(collapsedTail(h));
-            else MGPS_LAUNCH(h, launchCoarseSolve(h->stream, h->cn, h->cinv, h->ccells, B.x, B.b, h->cvec));  // MG.cpp:669-692
-        }
-        cur[nsmooth] = B.x;
-        for (int l = nsmooth - 1; l >= 0; --l) {  // MG.cpp:695-784 (coarser), 787-880 (fine)
-            DevLevel &F = h->lv[l];
-            if (stopRequested()) return failH(h, MGPS_ERR_INTERRUPTED, "mgps_apply_vcycle: interrupted");
-            const float *rhsUp = l == 0 ? b : F.b;
-            bool upSnap = false;
-            if (upStrokeFuses(h, l, cur[l], other[l], rhsUp, h->gatherDot && l == 0)) {
-                MGPS_TRY(fusedUpStroke(h, l, cur[l], other[l], rhsUp, cur[l + 1]));
-                continue;
-            }
-            {
-                StageScope scope(h, ST_PROLONG, l);
-                MGPS_TRY(exchangeGhosts(h, l + 1, cur[l + 1]));
-                const bool snap = gsStrokeSnapshots(h, l, cur[l], rhsUp);
-                if (snap) MGPS_TRY(ensureSnapTiles(h, l));
-                MGPS_LAUNCH(h, launchProlongAdd(h->stream, F.g, cur[l], cur[l + 1], snap ? F.r : nullptr, snap ? F.snapTile : nullptr));
-                upSnap = snap;
-            }
-            MGPS_TRY(smoothStroke(h, l, cur[l], other[l], rhsUp, false, false, h->gatherDot && l == 0, false, upSnap));
-        }
-    }
-    if (cur[0] != x)  // single-level Jacobi cycle: the iterate ended in the spare grid
-        MGPS_HIP(h, hipMemcpyAsync(x, cur[0], h->lv[0].d.cells() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    float *cur = x, *other = h->lv[0].tmp;
+    if (useInitialGuess) MGPS_TRY(smoothStroke(h, 0, cur, other, b, true, false, h->gatherDot && !hasBottom));
+    else MGPS_TRY(downStrokeFromZero(h, 0, cur, other, b, ownGrid, h->gatherDot && !hasBottom));
+    if (hasBottom) MGPS_TRY(cycleLevels(h, 0, cur, other, b, !h->dist && !h->tailOfSlabRun));
+    if (cur != x)  // single-level Jacobi cycle: the iterate ended in the spare grid
+        MGPS_HIP(h, hipMemcpyAsync(x, cur, h->lv[0].d.cells() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     if (h->gatherDot) MGPS_LAUNCH(h, launchFoldDot(h->stream, h->dotPartials, h->dotUsed, h->dotTarget ? h->dotTarget : h->resultDev));
-    if (stageTimingOn(h)) ++h->stageCycles;
-    if (h->opt.print_stats) stageFlush(h);  // (profiling without print_stats: the marks pile up until mgps_stage_times reads them)
-    return MGPS_OK;
-}
-
-// levels first .. last of a single-device solver: rhs in lv[first].b, *result = the grid that ends up holding the
-// correction (MG.cpp:557-784 from level `first` on)
-int innerCycle(mgps_solver *h, int first, float **result)
-{
-    const int nlv = int(h->lv.size());
-    const int nsmooth = nlv - 1;  // the last level is the direct solve
-    std::vector<float *> cur(nlv, nullptr), other(nlv, nullptr);
-    for (int l = first; l < nsmooth; ++l) {
-        DevLevel &F = h->lv[l], &C = h->lv[l + 1];
-        cur[l] = F.x;
-        other[l] = F.tmp;
-        const bool zl = strokeTakesZero(h, l, cur[l], other[l], F.b, false);
-        if (!zl) MGPS_TRY(zeroOwnGrid(h, l, F.x, true));  // MG.cpp:566
-        else MGPS_TRY(poisonSpares(h, l, cur[l], other[l]));
-        MGPS_TRY(smoothStroke(h, l, cur[l], other[l], F.b, true, true, false, zl));
-        if (residualRestrictFuses(h, l)) {
-            MGPS_TRY(residualRestrict(h, l, cur[l], F.b));
-            continue;
-        }
-        MGPS_LAUNCH(h, launchStencil(h->stream, OP_RESIDUAL, F.g, F.r, cur[l], F.b, 0.f, true));
-        MGPS_LAUNCH(h, launchRestrict(h->stream, C.g, C.b, F.r));
-    }
-    DevLevel &B = h->lv[nsmooth];
-    MGPS_LAUNCH(h, launchCoarseSolve(h->stream, h->cn, h->cinv, h->ccells, B.x, B.b, h->cvec));  // MG.cpp:669-692
-    cur[nsmooth] = B.x;
-    for (int l = nsmooth - 1; l >= first; --l) {
-        DevLevel &F = h->lv[l];
-        if (upStrokeFuses(h, l, cur[l], other[l], F.b, false)) {
-            MGPS_TRY(fusedUpStroke(h, l, cur[l], other[l], F.b, cur[l + 1]));
-            continue;
-        }
-        const bool snap = gsStrokeSnapshots(h, l, cur[l], F.b);
-        if (snap) MGPS_TRY(ensureSnapTiles(h, l));
-        MGPS_LAUNCH(h, launchProlongAdd(h->stream, F.g, cur[l], cur[l + 1], snap ? F.r : nullptr, snap ? F.snapTile : nullptr));
-        MGPS_TRY(smoothStroke(h, l, cur[l], other[l], F.b, false, false, false, false, snap));
-    }
-    *result = cur[first];
+    stageCycleDone(h);
     return MGPS_OK;
 }
 
@@ -1276,13 +1274,9 @@ int vcycleMixed(mgps_solver *h, float *x, const float *b, bool useInitialGuess, 
     const MixScale smooth{h->mixSigma, xs, 1.f};  // the iterate's units: rhs sigma 2^-e b
     const bool gather = dotDev != nullptr && h->dotPartials != nullptr && !h->useGS;  // (the binary16 tile kernels gather nothing: a separate pass below)
     h->dotUsed = 0;
-    // (the box form of the band stage, binary16 grids: see smoothStroke; the scratch / snapshot grid is the binary16 residual)
+    // (the box form of the band stage, binary16 grids: see bandPasses; the scratch / snapshot grid is the binary16 residual)
     auto bandStage = [&](bool dot) -> int {  // no snapshot: out of place, band cells copied back
-        double *sink = nullptr;
-        if (dot && F.bandBoxes.ngroups > 0) {
-            sink = h->dotPartials + h->dotUsed;
-            h->dotUsed += unsigned(F.bandBoxes.ngroups);
-        }
+        double *sink = dot && F.bandBoxes.ngroups > 0 ? takeDotSink(h, unsigned(F.bandBoxes.ngroups)) : nullptr;
         MGPS_LAUNCH(h, launchBandBox(h->stream, F.g, F.bandBoxes, false, cur, b, h->mixR, nullptr, omega, true, smooth, sink, cur));
         MGPS_LAUNCH(h, launchBandBoxCopy(h->stream, F.g, F.bandBoxes, h->mixR, cur, true));
         return MGPS_OK;
@@ -1291,42 +1285,34 @@ int vcycleMixed(mgps_solver *h, float *x, const float *b, bool useInitialGuess, 
         unsigned used = 0;
         GridP gs = F.g;
         if (!patchGeneral) gs.nbnd = 0;
-        if (h->profiling) MGPS_TRY(profMark(h, true));  // the measurement hook of smoothStroke: event pair around the fine sweep
-        MGPS_LAUNCH(h, launchStencilMixed(h->stream, OP_JACOBI, gs, other, xZero ? nullptr : cur, b, omega, smooth, d ? h->dotPartials + h->dotUsed : nullptr, &used));
-        if (h->profiling) {
-            MGPS_TRY(profMark(h, false));
-            ++h->profSweeps;
-        }
+        MGPS_TRY(timedSweep(h, h->profiling, 1, [&]() -> int {
+            MGPS_LAUNCH(h, launchStencilMixed(h->stream, OP_JACOBI, gs, other, xZero ? nullptr : cur, b, omega, smooth, d ? h->dotPartials + h->dotUsed : nullptr, &used));
+            return MGPS_OK;
+        }));
         h->dotUsed += used;
         return MGPS_OK;
     };
     auto stroke = [&](bool down, bool dot, bool xZero) -> int {
         const int reps = down ? h->opt.pre_sweeps : h->opt.post_sweeps;
-        if (reps == 1 && F.bandBoxes.ngroups > 0 && !h->useGS) {  // closure launch (snapshot only), sweep, plain launch: see smoothStroke
+        if (reps == 1 && F.bandBoxes.ngroups > 0 && !h->useGS) {  // closure launch (snapshot only), sweep, plain launch: see threeLaunchStroke
             MGPS_LAUNCH(h, launchBandBox(h->stream, F.g, F.bandBoxes, true, xZero ? nullptr : cur, b, nullptr, h->mixR, omega, true, smooth));
             MGPS_TRY(sweep(dot, dot, xZero));
-            double *sinkB = nullptr;
-            if (dot) {
-                sinkB = h->dotPartials + h->dotUsed;
-                h->dotUsed += unsigned(F.bandBoxes.ngroups);
-            }
+            double *sinkB = dot ? takeDotSink(h, unsigned(F.bandBoxes.ngroups)) : nullptr;
             std::swap(cur, other);
             MGPS_LAUNCH(h, launchBandBox(h->stream, F.g, F.bandBoxes, false, h->mixR, b, cur, nullptr, omega, true, smooth, sinkB, cur, true));
             return MGPS_OK;
         }
         MGPS_TRY(bandStage(false));
         for (int rep = 0; rep < reps; ++rep) {
-            if (h->useGS) {  // the colour passes of smoothStroke (MG.cpp:466-479 down, 740-751 up), in place on the binary16 iterate
+            if (h->useGS) {  // the colour passes of gsSweep (MG.cpp:466-479 down, 740-751 up), in place on the binary16 iterate
                 const int first = down ? 1 : 0, forward = down ? 1 : 0;
-                if (h->profiling) MGPS_TRY(profMark(h, true));
-                for (int pass = 0; pass < 2; ++pass) {
-                    const int odd = pass == 0 ? first : 1 - first;
-                    MGPS_LAUNCH(h, launchTiledGSMixed(h->stream, F.g, cur, b, F.pure[odd], F.npure[odd], F.mixed[odd], F.nmixed[odd], F.tileBndStart, forward, smooth));
-                }
-                if (h->profiling) {
-                    MGPS_TRY(profMark(h, false));
-                    ++h->profSweeps;
-                }
+                MGPS_TRY(timedSweep(h, h->profiling, 1, [&]() -> int {  // (one event pair around both colour passes)
+                    for (int pass = 0; pass < 2; ++pass) {
+                        const int odd = pass == 0 ? first : 1 - first;
+                        MGPS_LAUNCH(h, launchTiledGSMixed(h->stream, F.g, cur, b, F.pure[odd], F.npure[odd], F.mixed[odd], F.nmixed[odd], F.tileBndStart, forward, smooth));
+                    }
+                    return MGPS_OK;
+                }));
                 continue;
             }
             MGPS_TRY(sweep(dot && rep == reps - 1, true, false));
@@ -1342,8 +1328,8 @@ int vcycleMixed(mgps_solver *h, float *x, const float *b, bool useInitialGuess, 
         const MixScale res{h->mixSigma, 256.f, 256.f * xsInv};
         MGPS_LAUNCH(h, launchStencilMixed(h->stream, OP_RESIDUAL, F.g, h->mixR, cur, b, 0.f, res));
         MGPS_LAUNCH(h, launchRestrictMixed(h->stream, C.g, C.b, h->mixR, 1.f / 256.f));
-        float *corr = nullptr;
-        MGPS_TRY(innerCycle(h, 1, &corr));
+        float *corr = C.x;
+        MGPS_TRY(cycleLevels(h, 1, corr, C.tmp, C.b, false));  // (not polled)
         MGPS_LAUNCH(h, launchProlongAddMixed(h->stream, F.g, cur, corr, xs));
         MGPS_TRY(stroke(false, gather, false));
     }
@@ -1354,6 +1340,7 @@ int vcycleMixed(mgps_solver *h, float *x, const float *b, bool useInitialGuess, 
     h->mixResult = cur;
     if (dotDev && !gather) MGPS_LAUNCH(h, launchHalfDot(h->stream, F.g, cur, b, h->mixSigma, xsInv, h->partials, dotDev));
     if (x) MGPS_LAUNCH(h, launchFromHalf(h->stream, x, cur, h->mixSigma, xsInv, n));
+    stageCycleDone(h);  // (the stage timers see the coarse levels: the binary16 fine level has none)
     return MGPS_OK;
 }
 
@@ -4240,14 +4227,14 @@ int mgps_ghost_planes(const mgps_solver *h) { return h ? h->ghost : 1; }
 int mgps_residual_restrict_fused(const mgps_solver *h, int level, int *fused)
 try {
     if (!h || !fused || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
-    *fused = (h->opt.precision == 0 || level > 0) && residualRestrictFuses(h, level) ? 1 : 0;
+    *fused = residualRestrictFuses(h, level) ? 1 : 0;
     return MGPS_OK;
 }
 MGPS_API_CATCH(h)
 int mgps_up_stroke_fused(const mgps_solver *h, int level, int *fused)
 try {
     if (!h || !fused || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
-    *fused = upStrokeFuses(h, level, nullptr, nullptr, nullptr, false) ? 1 : 0;
+    *fused = strokeForm(h, level, false, nullptr, nullptr, nullptr, false) == SF_PROLONG_FUSED ? 1 : 0;  // (the cycle's own grids)
     return MGPS_OK;
 }
 MGPS_API_CATCH(h)
