@@ -54,6 +54,7 @@ class Options(C.Structure):
         ("precision", C.c_int),
         ("host_setup", C.c_int),
         ("borrow_device_weights", C.c_int),
+        ("enclosed_liquid", C.c_int),
     ]
 
 

@@ -616,6 +616,8 @@ try {
     p->liquid_cells = div[2];
     std::memset(&p->stats, 0, sizeof(p->stats));
     p->residual_inf = p->residual_l2 = p->divergence_sum = p->divergence_max = 0;
+    p->enclosed_components = 0;
+    p->rhs_mean_removed_max = 0;
     if (div[2] == 0) {
         if (copy.s && (he = hipStreamSynchronize(copy.s)) != hipSuccess) return failHip("upload", he);
         if ((he = hipMemsetAsync(pressure, 0, cells * sizeof(float), s)) != hipSuccess) return failHip("pressure clear", he);
@@ -642,6 +644,12 @@ try {
     PROJ_TRY(mgps_fields_rhs(rhs, material, vel[0], vel[1], vel[2], svel[0], svel[1], svel[2], cw[0], cw[1], cw[2], gx, gy, gz, ex, ey, ez, offset, s));
     rc = mgps_grid_alloc(mg, 0, &x);  // zero-filled
     if (rc == MGPS_OK && p->use_old_pressure) rc = mgps_fields_pressure_to_solution(x, pressure, material, gx, gy, gz, ex, ey, ez, offset, s);
+    if (rc == MGPS_OK && o.enclosed_liquid) {  // the rhs as the solve sees it (P b): the residual below is then that of the solved system
+        int64_t m = 0;
+        rc = mgps_enclosed_components(mg, &m, nullptr);
+        p->enclosed_components = int(m);
+        if (rc == MGPS_OK && m > 0) rc = mgps_project_enclosed(mg, rhs, &p->rhs_mean_removed_max);
+    }
     if (rc != MGPS_OK) {
         setLastGlobalError(mgps_last_error(mg));
         return rc;

@@ -1097,6 +1097,50 @@ using namespace mgps;
 // #active + #DIRICHLET neighbours; unknowns numbered tile by tile, x fastest inside a tile.
 // Factorised as a banded Cholesky (an exact SPD direct solve like Eigen::SimplicialCholesky).
 static int factorCoarseOnHost(mgps_hierarchy &H);
+// options.enclosed_liquid: the unknown of the minimum-index cell of every component of the coarsest level's active cells (unit
+// coupling: the matrix below) that has no DIRICHLET neighbour -- the null space of the matrix, one constant per such component
+static void findCoarsePins(mgps_hierarchy &H)
+{
+    H.coarsePinned.clear();
+    H.coarseComp.clear();
+    if (!H.pinEnclosed) return;
+    std::vector<size_t> members;
+    const HostLevel &L = H.lv[H.levels - 1];
+    const Dims d = L.d;
+    const ptrdiff_t stride[3] = {1, d.nx, ptrdiff_t(d.nx) * d.ny};
+    std::vector<uint8_t> seen(d.cells(), 0);
+    std::vector<size_t> stack;
+    for (size_t c0 = 0; c0 < d.cells(); ++c0) {  // ascending: c0 is the minimum of the component it starts
+        if (seen[c0] || !isActive(L.labels[c0])) continue;
+        bool open = false;
+        seen[c0] = 1;
+        stack.assign(1, c0);
+        members.clear();
+        while (!stack.empty()) {
+            const size_t c = stack.back();
+            stack.pop_back();
+            members.push_back(c);
+            for (int a = 0; a < 3; ++a)
+                for (int s = -1; s <= 1; s += 2) {
+                    const size_t nb = size_t(ptrdiff_t(c) + s * stride[a]);  // (the EXTERIOR shell keeps nb inside the grid)
+                    if (isActive(L.labels[nb])) {
+                        if (!seen[nb]) {
+                            seen[nb] = 1;
+                            stack.push_back(nb);
+                        }
+                    } else if (L.labels[nb] == MGPS_DIRICHLET_CELL)
+                        open = true;
+                }
+        }
+        if (!open) {
+            if (H.coarseComp.empty()) H.coarseComp.assign(H.coarseCell.size(), -1);
+            for (size_t c : members) H.coarseComp[size_t(H.coarseIndex[c])] = int32_t(H.coarsePinned.size());
+            H.coarsePinned.push_back(H.coarseIndex[c0]);
+        }
+    }
+    std::sort(H.coarsePinned.begin(), H.coarsePinned.end());
+}
+
 static int buildCoarseSolver(mgps_hierarchy &H, int maxUnknowns)
 {
     const HostLevel &L = H.lv[H.levels - 1];
@@ -1117,6 +1161,7 @@ static int buildCoarseSolver(mgps_hierarchy &H, int maxUnknowns)
     }
     const int cn = int(H.coarseCell.size());
     H.coarseN = cn;
+    findCoarsePins(H);
     if (cn > maxUnknowns)
         return fail(MGPS_ERR_COARSE_TOO_LARGE,
                     "coarsest level has " + std::to_string(cn) + " unknowns (cap " + std::to_string(maxUnknowns) +
@@ -1156,14 +1201,20 @@ static int factorCoarseOnHost(mgps_hierarchy &H)
     std::vector<double> &A = H.coarseL;
     A.assign(size_t(cn) * W, 0.0);
     auto at = [&](int r, int c) -> double & { return A[size_t(r) * W + (bw - (r - c))]; };
+    std::vector<uint8_t> pinned(H.coarsePinned.empty() ? 0 : size_t(cn), 0);
+    for (int32_t p : H.coarsePinned) pinned[size_t(p)] = 1;
     for (int r = 0; r < cn; ++r) {
+        if (!pinned.empty() && pinned[size_t(r)]) {  // (a pinned unknown: the identity's row and column)
+            at(r, r) = 1.0;
+            continue;
+        }
         double diag = 0;
         for (int a = 0; a < 3; ++a)
             for (int s = -1; s <= 1; s += 2) {
                 const size_t nb = H.coarseCell[r] + s * stride[a];
                 if (isActive(L.labels[nb])) {
                     const int q = H.coarseIndex[nb];
-                    if (q < r) at(r, q) = -1.0;
+                    if (q < r && (pinned.empty() || !pinned[size_t(q)])) at(r, q) = -1.0;
                     diag += 1.0;
                 } else if (L.labels[nb] == MGPS_DIRICHLET_CELL)
                     diag += 1.0;
@@ -1208,6 +1259,7 @@ void mgps_hierarchy::bandedSolve(double *v) const
     if (coarseOnDevice) return;  // (no host factor: callers check)
     const int n = coarseN, bw = coarseBW, W = bw + 1;
     const double *Lm = coarseL.data();
+    for (int32_t p : coarsePinned) v[p] = 0.0;  // (decoupled identity rows: the pinned unknowns come out 0)
     for (int r = 0; r < n; ++r) {
         double sum = v[r];
         for (int c = std::max(0, r - bw); c < r; ++c) sum -= Lm[size_t(r) * W + (bw - (r - c))] * v[c];
@@ -1271,6 +1323,105 @@ void mgps_hierarchy::buildDenseInverse()
     for (int t = 1; t < nt; ++t) pool.emplace_back(work);
     work();
     for (auto &th : pool) th.join();
+    for (int32_t p : coarsePinned) coarseInverse[size_t(p) * n + p] = 0.f;  // (row and column are 0 already: the identity's block)
+    projectPinnedInverse(coarseInverse.data(), n, coarseComp, int(coarsePinned.size()));
+}
+
+// inv <- (I - Q) inv (I - Q), Q = the mean over each pinned component (the coarse correction of the V-cycle becomes the
+// pseudo-inverse).  The pinned inverse is block-diagonal across components, so with w_j = mean over j's component of row j:
+// inv_ij -= w_i + w_j - mean(w over the component) for i, j of the same component
+void mgps::projectPinnedInverse(float *inv, int n, const std::vector<int32_t> &comp, int ncomp)
+{
+    if (ncomp == 0 || comp.empty()) return;
+    std::vector<double> w(size_t(n), 0.0), T(size_t(ncomp), 0.0);
+    std::vector<int64_t> count(size_t(ncomp), 0);
+    for (int i = 0; i < n; ++i)
+        if (comp[size_t(i)] >= 0) ++count[size_t(comp[size_t(i)])];
+    parallelFor(n, [&](int64_t r0, int64_t r1) {
+        for (int64_t i = r0; i < r1; ++i) {
+            const int c = comp[size_t(i)];
+            if (c < 0) continue;
+            double s = 0.0;
+            for (int k = 0; k < n; ++k)
+                if (comp[size_t(k)] == c) s += double(inv[size_t(i) * n + k]);
+            w[size_t(i)] = s / double(count[size_t(c)]);
+        }
+    }, 64);
+    for (int i = 0; i < n; ++i)
+        if (comp[size_t(i)] >= 0) T[size_t(comp[size_t(i)])] += w[size_t(i)];
+    for (int c = 0; c < ncomp; ++c) T[size_t(c)] /= double(count[size_t(c)]);
+    parallelFor(n, [&](int64_t r0, int64_t r1) {
+        for (int64_t i = r0; i < r1; ++i) {
+            const int c = comp[size_t(i)];
+            if (c < 0) continue;
+            for (int j = 0; j < n; ++j)
+                if (comp[size_t(j)] == c) inv[size_t(i) * n + j] = float(double(inv[size_t(i) * n + j]) - w[size_t(i)] - w[size_t(j)] + T[size_t(c)]);
+        }
+    }, 64);
+}
+
+// Fine-level components for options.enclosed_liquid, serial union-find (the checker: the device labelling must match it entry for entry)
+void mgps::enclosedComponentsHost(const uint8_t *labels, const float *wx, const float *wy, const float *wz, const Dims &d, std::vector<int32_t> &offsets,
+                                  std::vector<int32_t> &cells)
+{
+    const size_t n = d.cells();
+    const float *w[3] = {wx, wy, wz};
+    const ptrdiff_t stride[3] = {1, d.nx, ptrdiff_t(d.nx) * d.ny};
+    std::vector<int32_t> parent(n, -1);
+    auto find = [&](int32_t c) {
+        while (parent[size_t(c)] != c) {
+            parent[size_t(c)] = parent[size_t(parent[size_t(c)])];
+            c = parent[size_t(c)];
+        }
+        return c;
+    };
+    for (size_t c = 0; c < n; ++c)
+        if (isActive(labels[c])) parent[c] = int32_t(c);
+    std::vector<uint8_t> open(n, 0);
+    for (int k = 0; k < d.nz; ++k)
+        for (int j = 0; j < d.ny; ++j)
+            for (int i = 0; i < d.nx; ++i) {
+                const size_t c = d.idx(i, j, k);
+                const uint8_t lc = labels[c];
+                if (!isActive(lc)) continue;
+                const int ijk[3] = {i, j, k}, ext[3] = {d.nx, d.ny, d.nz};
+                for (int a = 0; a < 3; ++a)
+                    for (int p = 0; p < 2; ++p) {
+                        if (p ? ijk[a] + 1 >= ext[a] : ijk[a] == 0) continue;
+                        const size_t nb = size_t(ptrdiff_t(c) + (p ? stride[a] : -stride[a]));
+                        const uint8_t ln = labels[nb];
+                        const int fi = i + (a == 0 && p), fj = j + (a == 1 && p), fk = k + (a == 2 && p);  // (face grids: one more entry along a)
+                        const float wf = w[a][(size_t(fk) * (d.ny + (a == 1)) + fj) * (d.nx + (a == 0)) + fi];
+                        if (lc == MGPS_BOUNDARY_CELL && ln == MGPS_DIRICHLET_CELL && wf > 0.f) open[c] = 1;
+                        if (p && isActive(ln) && (lc == MGPS_INTERIOR_CELL || ln == MGPS_INTERIOR_CELL || wf > 0.f)) {
+                            int32_t ra = find(int32_t(c)), rb = find(int32_t(nb));
+                            if (ra != rb) parent[size_t(std::max(ra, rb))] = std::min(ra, rb);  // the root stays the minimum cell
+                        }
+                    }
+            }
+    for (size_t c = 0; c < n; ++c)
+        if (parent[c] >= 0 && open[c]) open[size_t(find(int32_t(c)))] = 1;
+    std::vector<int32_t> rank(n, -1);
+    offsets.assign(1, 0);
+    std::vector<int32_t> count;
+    for (size_t c = 0; c < n; ++c)
+        if (parent[c] == int32_t(c) && !open[c]) {
+            rank[c] = int32_t(count.size());
+            count.push_back(0);
+        }
+    for (size_t c = 0; c < n; ++c)
+        if (parent[c] >= 0) {
+            const int32_t r = rank[size_t(find(int32_t(c)))];
+            if (r >= 0) ++count[size_t(r)];
+        }
+    for (int32_t v : count) offsets.push_back(offsets.back() + v);
+    cells.resize(size_t(offsets.back()));
+    std::vector<int32_t> at(offsets.begin(), offsets.end() - 1);
+    for (size_t c = 0; c < n; ++c)
+        if (parent[c] >= 0) {
+            const int32_t r = rank[size_t(find(int32_t(c)))];
+            if (r >= 0) cells[size_t(at[size_t(r)]++)] = int32_t(c);
+        }
 }
 
 extern "C" {
@@ -1561,10 +1712,13 @@ int mgps::hierarchyCreate(mgps_hierarchy **out, int nx, int ny, int nz, const ui
             return fail(MGPS_ERR_INVALID_ARGUMENT, "mgps_hierarchy_create: extents are not divisible by 2^(levels-1)");
     if (o.band_width < 1 || o.band_iterations < 0)
         return fail(MGPS_ERR_INVALID_ARGUMENT, "mgps_hierarchy_create: band_width >= 1, band_iterations >= 0");
+    if (o.enclosed_liquid != 0 && o.enclosed_liquid != 1)
+        return fail(MGPS_ERR_INVALID_ARGUMENT, "mgps_options.enclosed_liquid must be 0 or 1");
 
     HostLap lap;
     auto H = new mgps_hierarchy();
     H->bandWidth = o.band_width;
+    H->pinEnclosed = o.enclosed_liquid == 1;
     H->lv.resize(mg_levels);
     H->lv[0].d = Dims{nx, ny, nz};
     H->lv[0].labels.resize(H->lv[0].d.cells());
@@ -1663,6 +1817,7 @@ int mgps::hierarchyLight(mgps_hierarchy **out, int nx, int ny, int nz, int level
     auto H = new mgps_hierarchy();
     H->light = true;
     H->bandWidth = o.band_width;
+    H->pinEnclosed = o.enclosed_liquid == 1;
     H->levels = levels;
     H->lv.resize(size_t(levels));
     for (int l = 0; l < levels; ++l) H->lv[size_t(l)].d = Dims{nx >> l, ny >> l, nz >> l};
@@ -1678,7 +1833,8 @@ int mgps::hierarchyLight(mgps_hierarchy **out, int nx, int ny, int nz, int level
             Dims d;
             std::vector<uint8_t> labels;
             int n = 0, bw = 0;
-            std::vector<int32_t> cell, index;
+            bool pinEnclosed = false;  // (part of the key: the same labels give another matrix with the pins)
+            std::vector<int32_t> cell, index, pinned, comp;
             std::vector<double> factor;
             std::vector<float> inverse;
         };
@@ -1689,6 +1845,7 @@ int mgps::hierarchyLight(mgps_hierarchy **out, int nx, int ny, int nz, int level
             std::lock_guard<std::mutex> lock(guard);
             for (auto &k : kept)
                 if (k->d.nx == C.d.nx && k->d.ny == C.d.ny && k->d.nz == C.d.nz && k->n <= o.max_coarse_unknowns && k->n <= kHostCoarseMax &&
+                    k->pinEnclosed == H->pinEnclosed &&
                     std::memcmp(k->labels.data(), coarsestLabels, C.d.cells()) == 0) {
                     hit = k;
                     break;
@@ -1699,6 +1856,8 @@ int mgps::hierarchyLight(mgps_hierarchy **out, int nx, int ny, int nz, int level
             H->coarseBW = hit->bw;
             H->coarseCell = hit->cell;
             H->coarseIndex = hit->index;
+            H->coarsePinned = hit->pinned;
+            H->coarseComp = hit->comp;
             H->coarseL = hit->factor;
             H->coarseInverse = hit->inverse;
         } else {
@@ -1716,6 +1875,9 @@ int mgps::hierarchyLight(mgps_hierarchy **out, int nx, int ny, int nz, int level
                 k->bw = H->coarseBW;
                 k->cell = H->coarseCell;
                 k->index = H->coarseIndex;
+                k->pinEnclosed = H->pinEnclosed;
+                k->pinned = H->coarsePinned;
+                k->comp = H->coarseComp;
                 k->factor = H->coarseL;
                 k->inverse = H->coarseInverse;
                 std::lock_guard<std::mutex> lock(guard);
@@ -2000,6 +2162,13 @@ try {
     }
     std::vector<double> v(hier->coarseN);
     for (int r = 0; r < hier->coarseN; ++r) v[r] = b[hier->coarseCell[r]];
+    if (!hier->coarseComp.empty()) {  // (options.enclosed_liquid: the rhs's mean over a pinned component is removed first -- the consistent part)
+        std::vector<double> sum(hier->coarsePinned.size(), 0.0), cnt(hier->coarsePinned.size(), 0.0);
+        for (int r = 0; r < hier->coarseN; ++r)
+            if (hier->coarseComp[size_t(r)] >= 0) sum[size_t(hier->coarseComp[size_t(r)])] += v[r], cnt[size_t(hier->coarseComp[size_t(r)])] += 1.0;
+        for (int r = 0; r < hier->coarseN; ++r)
+            if (hier->coarseComp[size_t(r)] >= 0) v[r] -= sum[size_t(hier->coarseComp[size_t(r)])] / cnt[size_t(hier->coarseComp[size_t(r)])];
+    }
     hier->bandedSolve(v.data());
     for (int r = 0; r < hier->coarseN; ++r) x[hier->coarseCell[r]] = float(v[r]);
     return MGPS_OK;

@@ -387,8 +387,12 @@ int launchBandBoxClosureProlonged(void *stream, const GridP &g, const BandBoxesD
 size_t planeBlockCount(const GridP &g);
 int launchPlaneBlockFlags(void *stream, const GridP &g, uint8_t *flags);
 // dense coarsest matrix (n x n doubles, zeroed by the caller) from the level's labels; fp32 inverse from the triangle potri left
-int launchCoarseAssemble(void *stream, int n, int nx, int ny, const int32_t *cells, const int32_t *index, const uint8_t *lab, double *A);
+int launchCoarseAssemble(void *stream, int n, int nx, int ny, const int32_t *cells, const int32_t *index, const uint8_t *lab, double *A,
+                         const uint8_t *pinned = nullptr);  // pinned: a byte per unknown (mgps_hierarchy::coarsePinned), nullptr = none
 int launchCoarseNarrow(void *stream, int n, const double *A, float *inv);
+// inv <- (I - Q) inv (I - Q) over the pinned components (comp: a component id per unknown, -1 = none; counts: cells per component;
+// w: n doubles of scratch).  inv must be block-diagonal across components (the pinned inverse is)
+int launchCoarseInverseProject(void *stream, int n, float *inv, const int32_t *comp, int ncomp, const int32_t *counts, double *w, double *T);
 int launchCoarseSolve(void *stream, int n, const float *inverse, const int32_t *cells, float *x, const float *b,
                       float *gathered);
 int launchAxpy(void *stream, const GridP &g, float *dst, const float *src, const float *scaleDev, float scaleHost,
@@ -501,6 +505,22 @@ int launchBandBoxesCount(void *stream, const Dims &d, const uint8_t *lab, const 
 int launchBandBoxesFill(void *stream, const Dims &d, const uint8_t *lab, const uint32_t *mask, const uint16_t *prefix, const int32_t *tileStart,
                         const int32_t *bandEntry, const uint8_t *bandDiag, int depth, const int32_t *tiles, int ntiles, const int32_t *const at[3],
                         int32_t *info, uint32_t *list, int32_t *general, int *broken, const SlabWindow *win = nullptr);
+// options.enclosed_liquid, fine level (mgps_setup.hip): union-find over the cell codes and face weights on `stream` (synchronised).
+// m = 0: nothing is kept (both pointers nullptr).  Else *cells: the cells of the enclosed components grouped by rank (components
+// ranked by their minimum cell index), ascending inside a group; *offsets: m + 1 entries.  Both are deviceAlloc blocks of the caller
+int enclosedComponentsDevice(void *stream, const Dims &d, const uint8_t *codes, const float *wx, const float *wy, const float *wz, int32_t **cells,
+                             int32_t **offsets, int64_t *m, int64_t *cellCount);
+// P v for those components (mgps_kernels.hip): chunks = 3 ints per chunk of at most kEncChunkCells cells of one component (component,
+// first entry, end entry), compChunk = m + 1 entries (each component's first chunk); partials: one double per chunk, mean: m doubles.
+// v[c] -= mean of v over c's component on the listed cells, sums in fp64 in a fixed order
+constexpr int kEncChunkCells = 4096;
+int launchEnclosedProject(void *stream, float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, const int32_t *offsets,
+                          int64_t m, double *partials, double *mean);
+int launchEnclosedProject64(void *stream, double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk,
+                            const int32_t *offsets, int64_t m, double *partials, double *mean);
+// rank[c] = r on the cells of component r (rank filled with -1 by the caller)
+int launchEnclosedRanks(void *stream, int32_t *rank, const int32_t *cells, const int32_t *chunks, int nchunks);
+int launchWidenAdd(void *stream, double *x64, const float *x32, size_t n);  // x64 += x32 (the pending fp32 updates of the fp64-iterate loop)
 int launchZero(void *stream, float *a, size_t count);
 int launchZeroInactive(void *stream, const GridP &g, float *a);  // a = 0 on the cells of level g that are not active
 // the same for a grid of level g whose chunks without active cells already hold 0 (solver-owned grids)
@@ -519,6 +539,12 @@ constexpr double kHostFactorFlops = 4e9;  // n x bandwidth^2 of the host's bande
 
 struct mgps_hierarchy;
 namespace mgps {
+// options.enclosed_liquid on the fine level, host form (the checker of the device labelling): the components of the active cells
+// (coupled when either cell is INTERIOR, or two BOUNDARY cells across a face of weight > 0) that have no DIRICHLET neighbour behind a
+// face of weight > 0, ranked by their minimum cell index.  offsets: m + 1 entries; cells: each component's cells ascending
+void enclosedComponentsHost(const uint8_t *labels, const float *wx, const float *wy, const float *wz, const Dims &d, std::vector<int32_t> &offsets,
+                            std::vector<int32_t> &cells);
+void projectPinnedInverse(float *inv, int n, const std::vector<int32_t> &comp, int ncomp);  // see mgps_hierarchy::coarseComp
 int hostCoarseFallback(mgps_hierarchy *H);  // coarseOnDevice -> a host factor after all (<= kHostCoarseMax unknowns; mgps_host.cpp)
 }
 
@@ -539,6 +565,15 @@ struct mgps_hierarchy {
     // more unknowns than kHostCoarseMax or a banded factor past kHostFactorFlops: no factor on the host (the reference's tile
     // numbering gives the banded factor a width of thousands there); the solver factorises and inverts the dense matrix on the device (hipSOLVER potrf / potri in fp64)
     bool coarseOnDevice = false;
+    // options.enclosed_liquid: the coarsest level's components without a DIRICHLET neighbour (unit coupling, labels only) have
+    // their minimum-index cell pinned to 0 -- its row and column of the matrix are the identity's, its rhs entry is ignored and
+    // its inverse row / column are 0 (unknown ids, ascending)
+    // The V-cycle's coarse correction is then the pseudo-inverse (I - Q) A_pinned^-1 (I - Q), Q = the mean over each pinned
+    // component: the pinned solve alone turns the mean that restriction leaves in the coarse rhs of such a component into a large
+    // smooth error around the pin (the 512^3 sealed tank stalled on it).  coarseComp: per unknown the pinned component it belongs
+    // to (-1: none; empty without pins)
+    bool pinEnclosed = false;
+    std::vector<int32_t> coarsePinned, coarseComp;
     void bandedSolve(double *v) const;
     void buildDenseInverse();
 };

@@ -3104,18 +3104,24 @@ int launchPlaneBlockFlags(void *stream, const GridP &g, uint8_t *flags)
 // Coarsest levels past kHostCoarseMax unknowns: the dense matrix of MG.cpp:359-382 assembled on the device in fp64 (row r =
 // unknown r: -1 per active neighbour, diagonal = active + DIRICHLET neighbours), factorised and inverted by hipSOLVER
 // (potrf / potri leave one triangle), then folded into the fp32 inverse that coarseMatVecKernel multiplies with.
+// pinned (options.enclosed_liquid; nullptr = none): a byte per unknown, 1 = the identity's row and column
 __global__ __launch_bounds__(256) void coarseAssembleKernel(int n, int nx, int ny, const int32_t *__restrict__ cells, const int32_t *__restrict__ index,
-                                                            const uint8_t *__restrict__ lab, double *__restrict__ A)
+                                                            const uint8_t *__restrict__ lab, const uint8_t *__restrict__ pinned, double *__restrict__ A)
 {
     const int r = int(blockIdx.x * blockDim.x + threadIdx.x);
     if (r >= n) return;
+    if (pinned && pinned[r]) {
+        A[size_t(r) * n + r] = 1.0;
+        return;
+    }
     const ptrdiff_t c = cells[r], off[6] = {-1, 1, -ptrdiff_t(nx), ptrdiff_t(nx), -ptrdiff_t(nx) * ny, ptrdiff_t(nx) * ny};
     double diag = 0.0;
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
         const unsigned l = lab[c + off[q]];
         if (activeLabel(l)) {
-            A[size_t(r) * n + index[c + off[q]]] = -1.0;
+            const int32_t u = index[c + off[q]];
+            if (!(pinned && pinned[u])) A[size_t(r) * n + u] = -1.0;
             diag += 1.0;
         } else if (l == MGPS_DIRICHLET_CELL)
             diag += 1.0;
@@ -3131,11 +3137,59 @@ __global__ __launch_bounds__(256) void coarseNarrowKernel(int n, const double *_
     const size_t r = t / n, c = t - r * n;
     inv[t] = float(r <= c ? A[t] : A[c * n + r]);
 }
-int launchCoarseAssemble(void *stream, int n, int nx, int ny, const int32_t *cells, const int32_t *index, const uint8_t *lab, double *A)
+int launchCoarseAssemble(void *stream, int n, int nx, int ny, const int32_t *cells, const int32_t *index, const uint8_t *lab, double *A, const uint8_t *pinned)
 {
-    coarseAssembleKernel<<<blocksFor(size_t(n), 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n, nx, ny, cells, index, lab, A);
+    coarseAssembleKernel<<<blocksFor(size_t(n), 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n, nx, ny, cells, index, lab, pinned, A);
     return int(hipGetLastError());
 }
+// options.enclosed_liquid: inv <- (I - Q) inv (I - Q) over the pinned components (see mgps_hierarchy::coarseComp).  w_j = the mean of
+// row j over j's component (a wavefront per row, fixed order), T_c = the mean of w over component c (a thread per component),
+// then inv_ij -= w_i + w_j - T_c where i and j share component c
+__global__ __launch_bounds__(256) void coarseProjRowKernel(int n, const float *__restrict__ inv, const int32_t *__restrict__ comp,
+                                                           const int32_t *__restrict__ counts, double *__restrict__ w)
+{
+    const int row = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+    const int lane = threadIdx.x & (kWave - 1);
+    if (row >= n) return;
+    const int c = comp[row];
+    double acc = 0.0;
+    if (c >= 0)
+        for (int k = lane; k < n; k += kWave)
+            if (comp[k] == c) acc += double(inv[size_t(row) * n + k]);
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+    if (lane == 0) w[row] = c >= 0 ? acc / double(counts[c]) : 0.0;
+}
+__global__ __launch_bounds__(64) void coarseProjMeanKernel(int n, int ncomp, const int32_t *__restrict__ comp, const int32_t *__restrict__ counts,
+                                                          const double *__restrict__ w, double *__restrict__ T)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncomp) return;
+    double s = 0.0;
+    for (int i = 0; i < n; ++i)
+        if (comp[i] == c) s += w[i];
+    T[c] = s / double(counts[c]);
+}
+__global__ __launch_bounds__(256) void coarseProjApplyKernel(int n, float *__restrict__ inv, const int32_t *__restrict__ comp, const double *__restrict__ w,
+                                                            const double *__restrict__ T)
+{
+    const size_t t = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (t >= size_t(n) * n) return;
+    const size_t i = t / n, j = t - i * n;
+    const int c = comp[i];
+    if (c < 0 || comp[j] != c) return;
+    inv[t] = float(double(inv[t]) - w[i] - w[j] + T[c]);
+}
+int launchCoarseInverseProject(void *stream, int n, float *inv, const int32_t *comp, int ncomp, const int32_t *counts, double *w, double *T)
+{
+    if (n <= 0 || ncomp <= 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    coarseProjRowKernel<<<blocksFor(size_t(n), 4), 256, 0, s>>>(n, inv, comp, counts, w);
+    coarseProjMeanKernel<<<blocksFor(size_t(ncomp), 64), 64, 0, s>>>(n, ncomp, comp, counts, w, T);
+    coarseProjApplyKernel<<<blocksFor(size_t(n) * n, 256), 256, 0, s>>>(n, inv, comp, w, T);
+    return int(hipGetLastError());
+}
+
 int launchCoarseNarrow(void *stream, int n, const double *A, float *inv)
 {
     coarseNarrowKernel<<<blocksFor(size_t(n) * n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(n, A, inv);
@@ -3830,6 +3884,102 @@ int launchReduce(void *stream, int kind, const GridP &g, const float *a, const f
             reduceFinalKernel<3><<<1, 256, 0, s>>>(int(nb), partials, resultDev);
             break;
     }
+    return int(hipGetLastError());
+}
+
+// ---- options.enclosed_liquid: v -= mean over each enclosed component ---------------------------------------------------
+// Fixed order everywhere (same input, same bits): a workgroup per chunk of at most kEncChunkCells cells of one component sums
+// its cells thread by thread in list order and folds the 256 sums as a tree; a workgroup per component folds its chunk partials
+// the same way; the subtract pass reads the mean in fp64.  No atomics.
+namespace {
+template <class T>
+__global__ __launch_bounds__(256) void encChunkSumKernel(const T *__restrict__ v, const int32_t *__restrict__ cells, const int32_t *__restrict__ chunks,
+                                                        double *__restrict__ partials)
+{
+    __shared__ double red[256];
+    const int q = blockIdx.x;
+    const int32_t e0 = chunks[3 * q + 1], e1 = chunks[3 * q + 2];
+    double acc = 0.0;
+    for (int32_t e = e0 + int32_t(threadIdx.x); e < e1; e += 256) acc += double(v[cells[e]]);
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (int(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[q] = red[0];
+}
+__global__ __launch_bounds__(256) void encMeanKernel(const double *__restrict__ partials, const int32_t *__restrict__ compChunk,
+                                                     const int32_t *__restrict__ offsets, double *__restrict__ mean)
+{
+    __shared__ double red[256];
+    const int r = blockIdx.x;
+    double acc = 0.0;
+    for (int32_t q = compChunk[r] + int32_t(threadIdx.x); q < compChunk[r + 1]; q += 256) acc += partials[q];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (int(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) mean[r] = red[0] / double(offsets[r + 1] - offsets[r]);
+}
+template <class T>
+__global__ __launch_bounds__(256) void encSubtractKernel(T *__restrict__ v, const int32_t *__restrict__ cells, const int32_t *__restrict__ chunks,
+                                                        const double *__restrict__ mean)
+{
+    const int q = blockIdx.x;
+    const double mu = mean[chunks[3 * q]];
+    const int32_t e0 = chunks[3 * q + 1], e1 = chunks[3 * q + 2];
+    for (int32_t e = e0 + int32_t(threadIdx.x); e < e1; e += 256) {
+        const int32_t c = cells[e];
+        v[c] = T(double(v[c]) - mu);
+    }
+}
+__global__ __launch_bounds__(256) void encRankKernel(int32_t *__restrict__ rank, const int32_t *__restrict__ cells, const int32_t *__restrict__ chunks)
+{
+    const int q = blockIdx.x;
+    const int32_t r = chunks[3 * q], e0 = chunks[3 * q + 1], e1 = chunks[3 * q + 2];
+    for (int32_t e = e0 + int32_t(threadIdx.x); e < e1; e += 256) rank[cells[e]] = r;
+}
+template <class T>
+int enclosedProject(void *stream, T *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, const int32_t *offsets, int64_t m,
+                    double *partials, double *mean)
+{
+    if (m <= 0 || nchunks <= 0) return 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    encChunkSumKernel<T><<<unsigned(nchunks), 256, 0, s>>>(v, cells, chunks, partials);
+    encMeanKernel<<<unsigned(m), 256, 0, s>>>(partials, compChunk, offsets, mean);
+    encSubtractKernel<T><<<unsigned(nchunks), 256, 0, s>>>(v, cells, chunks, mean);
+    return int(hipGetLastError());
+}
+}  // namespace
+
+int launchEnclosedProject(void *stream, float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, const int32_t *offsets,
+                          int64_t m, double *partials, double *mean)
+{
+    return enclosedProject(stream, v, cells, chunks, nchunks, compChunk, offsets, m, partials, mean);
+}
+int launchEnclosedProject64(void *stream, double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk,
+                            const int32_t *offsets, int64_t m, double *partials, double *mean)
+{
+    return enclosedProject(stream, v, cells, chunks, nchunks, compChunk, offsets, m, partials, mean);
+}
+namespace {
+__global__ __launch_bounds__(256) void widenAddKernel(double *__restrict__ x64, const float *__restrict__ x32, size_t n)
+{
+    const size_t t = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (t < n) x64[t] += double(x32[t]);
+}
+}  // namespace
+int launchWidenAdd(void *stream, double *x64, const float *x32, size_t n)
+{
+    if (n > 0) widenAddKernel<<<blocksFor(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(x64, x32, n);
+    return int(hipGetLastError());
+}
+int launchEnclosedRanks(void *stream, int32_t *rank, const int32_t *cells, const int32_t *chunks, int nchunks)
+{
+    if (nchunks > 0) encRankKernel<<<unsigned(nchunks), 256, 0, static_cast<hipStream_t>(stream)>>>(rank, cells, chunks);
     return int(hipGetLastError());
 }
 

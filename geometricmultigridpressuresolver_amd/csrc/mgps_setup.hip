@@ -13,6 +13,8 @@
 
 #include <algorithm>
 
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include "mgps_internal.h"
 
 namespace mgps {
@@ -1591,6 +1593,249 @@ int launchGhostPlaneBlockFlags(void *stream, const Dims &d, const uint8_t *lab, 
     const int nbx = (d.nx + 255) / 256, nby = (d.ny + kPlaneRows - 1) / kPlaneRows;
     ghostPlaneBlockFlagsKernel<<<blocksFor(size_t(d.nx) * d.ny / 4, 256), 256, 0, S(stream)>>>(d, lab, k, zc, nbx, nby, flags);
     return int(hipGetLastError());
+}
+
+// ---- options.enclosed_liquid: connected components of the fine level's active cells ----------------------------------
+// Union-find over int32 parents, one thread per cell.  Two active cells are coupled when either is INTERIOR or, both BOUNDARY,
+// their face weight is > 0 (the operator's coupling).  Every link goes from the larger root to the smaller one, so a root is
+// the minimum cell index of its component: the canonical id the host builder (enclosedComponentsHost) gives it as well.
+namespace {
+
+__device__ __forceinline__ bool encCoupled(unsigned a, unsigned b, float w) { return activeCode(a) && activeCode(b) && (a == MGPS_INTERIOR_CELL || b == MGPS_INTERIOR_CELL || w > 0.f); }
+
+__device__ __forceinline__ int32_t encFind(const int32_t *parent, int32_t c)
+{
+    const volatile int32_t *p = parent;
+    int32_t q = p[c];
+    while (q != c) {
+        c = q;
+        q = p[c];
+    }
+    return c;
+}
+
+// parent = the head of the cell's x-run of coupled cells inside its wavefront (ballot over the 64 lanes: the nearest lane at or
+// below this one whose left link is missing), -1 on inactive cells; the runs that cross a wavefront boundary are hooked later
+__global__ __launch_bounds__(256) void encInitKernel(Dims d, const uint8_t *__restrict__ lab, const float *__restrict__ wx, int32_t *__restrict__ parent)
+{
+    const size_t n = cellCount(d);
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    const int lane = int(threadIdx.x & 63);
+    bool act = false, link = false;
+    if (c < n) {
+        const int i = int(c % size_t(d.nx));
+        const size_t row = c / size_t(d.nx);
+        act = activeCode(lab[c]);
+        link = act && i > 0 && encCoupled(lab[c - 1], lab[c], wx[row * size_t(d.nx + 1) + i]);
+    }
+    const unsigned long long heads = __ballot(!link);
+    const unsigned long long upTo = lane == 63 ? ~0ull : ((2ull << lane) - 1);
+    const unsigned long long m = heads & upTo;
+    const int head = m ? 63 - __clzll(m) : 0;
+    if (c < n) parent[c] = act ? int32_t(c - size_t(lane) + size_t(head)) : -1;
+}
+
+__device__ void encUnite(int32_t *parent, int32_t a, int32_t b)
+{
+    a = encFind(parent, a);
+    b = encFind(parent, b);
+    while (a != b) {
+        if (a < b) {
+            const int32_t t = a;
+            a = b;
+            b = t;
+        }
+        const int32_t old = atomicCAS(parent + a, a, b);  // root a (the larger) under root b
+        if (old == a) return;
+        a = encFind(parent, old);
+        b = encFind(parent, b);
+    }
+}
+
+// hook every active cell to its coupled +y / +z neighbours, and the first cell of a wavefront to its -x neighbour
+__global__ __launch_bounds__(256) void encHookKernel(Dims d, const uint8_t *__restrict__ lab, const float *__restrict__ wx, const float *__restrict__ wy,
+                                                     const float *__restrict__ wz, int32_t *__restrict__ parent)
+{
+    const size_t n = cellCount(d);
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (c >= n) return;
+    const unsigned l = lab[c];
+    if (!activeCode(l)) return;
+    const int i = int(c % size_t(d.nx)), j = int((c / size_t(d.nx)) % size_t(d.ny)), k = int(c / (size_t(d.nx) * d.ny));
+    const size_t plane = size_t(d.nx) * d.ny;
+    if ((c & 63) == 0 && i > 0 && encCoupled(lab[c - 1], l, wx[(size_t(k) * d.ny + j) * size_t(d.nx + 1) + i])) encUnite(parent, int32_t(c - 1), int32_t(c));
+    if (j + 1 < d.ny && encCoupled(l, lab[c + d.nx], wy[(size_t(k) * (d.ny + 1) + j + 1) * d.nx + i]) && parent[c] != parent[c + d.nx])
+        encUnite(parent, int32_t(c), int32_t(c + d.nx));
+    if (k + 1 < d.nz && encCoupled(l, lab[c + plane], wz[(size_t(k + 1) * d.ny + j) * d.nx + i]) && parent[c] != parent[c + plane])
+        encUnite(parent, int32_t(c), int32_t(c + plane));
+}
+
+// parent = root on every active cell; open[root] = 1 where a BOUNDARY cell has a DIRICHLET neighbour behind a face of weight > 0
+__global__ __launch_bounds__(256) void encCompressKernel(Dims d, const uint8_t *__restrict__ lab, const float *__restrict__ wx, const float *__restrict__ wy,
+                                                         const float *__restrict__ wz, int32_t *__restrict__ parent, uint8_t *__restrict__ open)
+{
+    const size_t n = cellCount(d);
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (c >= n) return;
+    const unsigned l = lab[c];
+    if (!activeCode(l)) return;
+    const int32_t root = encFind(parent, int32_t(c));
+    parent[c] = root;
+    if (l < MGPS_BOUNDARY_CELL) return;
+    const int i = int(c % size_t(d.nx)), j = int((c / size_t(d.nx)) % size_t(d.ny)), k = int(c / (size_t(d.nx) * d.ny));
+    const size_t plane = size_t(d.nx) * d.ny;
+    const size_t fx = (size_t(k) * d.ny + j) * size_t(d.nx + 1) + i, fy = (size_t(k) * (d.ny + 1) + j) * d.nx + i, fz = (size_t(k) * d.ny + j) * d.nx + i;
+    bool o = false;
+    o = o || (i > 0 && lab[c - 1] == MGPS_DIRICHLET_CELL && wx[fx] > 0.f);
+    o = o || (i + 1 < d.nx && lab[c + 1] == MGPS_DIRICHLET_CELL && wx[fx + 1] > 0.f);
+    o = o || (j > 0 && lab[c - d.nx] == MGPS_DIRICHLET_CELL && wy[fy] > 0.f);
+    o = o || (j + 1 < d.ny && lab[c + d.nx] == MGPS_DIRICHLET_CELL && wy[fy + d.nx] > 0.f);
+    o = o || (k > 0 && lab[c - plane] == MGPS_DIRICHLET_CELL && wz[fz] > 0.f);
+    o = o || (k + 1 < d.nz && lab[c + plane] == MGPS_DIRICHLET_CELL && wz[fz + plane] > 0.f);
+    if (o) open[root] = 1;
+}
+
+// flag (optional) = 1 on the roots of enclosed components; count[0] += their number, count[1] += the cells of enclosed components
+__global__ __launch_bounds__(256) void encRootKernel(size_t n, const int32_t *__restrict__ parent, const uint8_t *__restrict__ open, int32_t *__restrict__ flag,
+                                                     unsigned long long *__restrict__ count)
+{
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    bool root = false, cell = false;
+    if (c < n) {
+        const int32_t p = parent[c];
+        cell = p >= 0 && !open[p];
+        root = cell && p == int32_t(c);
+        if (flag) flag[c] = root ? 1 : 0;
+    }
+    const unsigned long long br = __ballot(root), bc = __ballot(cell);
+    if ((threadIdx.x & 63) == 0 && (br | bc)) {
+        atomicAdd(count, (unsigned long long)__popcll(br));
+        atomicAdd(count + 1, (unsigned long long)__popcll(bc));
+    }
+}
+
+// flag = 1 on every cell of an enclosed component (input of the compaction scan)
+__global__ __launch_bounds__(256) void encCellFlagKernel(size_t n, const int32_t *__restrict__ parent, const uint8_t *__restrict__ open, int32_t *__restrict__ flag)
+{
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (c >= n) return;
+    const int32_t p = parent[c];
+    flag[c] = p >= 0 && !open[p] ? 1 : 0;
+}
+
+// the enclosed cells in index order with their component ranks (the keys of the stable sort that groups them)
+__global__ __launch_bounds__(256) void encCompactKernel(size_t n, const int32_t *__restrict__ parent, const uint8_t *__restrict__ open,
+                                                        const int32_t *__restrict__ pos, const int32_t *__restrict__ rootRank, int32_t *__restrict__ key,
+                                                        int32_t *__restrict__ cell)
+{
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (c >= n) return;
+    const int32_t p = parent[c];
+    if (p < 0 || open[p]) return;
+    key[pos[c]] = rootRank[p];
+    cell[pos[c]] = int32_t(c);
+}
+
+// offsets[r] = the first entry of rank r in the sorted keys (every rank has a cell), offsets[m] = e
+__global__ __launch_bounds__(256) void encOffsetsKernel(int64_t e, int64_t m, const int32_t *__restrict__ key, int32_t *__restrict__ offsets)
+{
+    const int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (t >= e) return;
+    if (t == 0 || key[t] != key[t - 1]) offsets[key[t]] = int32_t(t);
+    if (t == 0) offsets[m] = int32_t(e);
+}
+
+template <class T>
+int encAlloc(T **p, size_t count) { return deviceAlloc(reinterpret_cast<void **>(p), std::max<size_t>(1, count) * sizeof(T)); }
+
+}  // namespace
+
+int enclosedComponentsDevice(void *stream, const Dims &d, const uint8_t *codes, const float *wx, const float *wy, const float *wz, int32_t **cellsOut,
+                             int32_t **offsetsOut, int64_t *mOut, int64_t *cellsCount)
+{
+    *cellsOut = *offsetsOut = nullptr;
+    *mOut = *cellsCount = 0;
+    const size_t n = d.cells();
+    if (n == 0) return 0;
+    hipStream_t s = S(stream);
+    int32_t *parent = nullptr, *flag = nullptr, *rank = nullptr, *scratch = nullptr, *pos = nullptr, *key = nullptr, *cell = nullptr, *keySorted = nullptr,
+            *cells = nullptr, *offsets = nullptr;
+    uint8_t *open = nullptr;
+    unsigned long long *count = nullptr;
+    void *sortTemp = nullptr;
+    auto release = [&] {
+        (void)hipStreamSynchronize(s);
+        for (void *p : {(void *)parent, (void *)flag, (void *)rank, (void *)scratch, (void *)pos, (void *)key, (void *)cell, (void *)keySorted, (void *)open, (void *)count, sortTemp})
+            (void)deviceFree(p);
+    };
+    // (int32 cell indices: every constructor refuses grids of more than 2^31 - 1 cells before this runs, see setupEnclosed)
+    int e = encAlloc(&parent, n);
+    if (!e) e = encAlloc(&open, n);
+    if (!e) e = encAlloc(&count, 4);
+    if (!e) e = int(hipMemsetAsync(open, 0, n, s));
+    if (!e) e = int(hipMemsetAsync(count, 0, 4 * sizeof(unsigned long long), s));
+    const unsigned nb = blocksFor(n, 256);
+    if (!e) {
+        encInitKernel<<<nb, 256, 0, s>>>(d, codes, wx, parent);
+        encHookKernel<<<nb, 256, 0, s>>>(d, codes, wx, wy, wz, parent);
+        encCompressKernel<<<nb, 256, 0, s>>>(d, codes, wx, wy, wz, parent, open);
+        encRootKernel<<<nb, 256, 0, s>>>(n, parent, open, nullptr, count);  // (the counts only: with m = 0 that is all)
+        e = int(hipGetLastError());
+    }
+    unsigned long long hc[2] = {0, 0};
+    if (!e) e = int(hipMemcpyAsync(hc, count, sizeof(hc), hipMemcpyDeviceToHost, s));
+    if (!e) e = int(hipStreamSynchronize(s));
+    if (e || hc[0] == 0) {  // (no enclosed component: nothing persists)
+        release();
+        return e;
+    }
+    const int64_t m = int64_t(hc[0]), ne = int64_t(hc[1]);
+    // ranks of the roots in index order, then the enclosed cells in index order with their ranks, grouped by a stable sort on the rank
+    if (!e) e = encAlloc(&flag, n);
+    if (!e) {
+        encRootKernel<<<nb, 256, 0, s>>>(n, parent, open, flag, count + 2);
+        e = int(hipGetLastError());
+    }
+    if (!e) e = encAlloc(&rank, n + 1);
+    if (!e) e = encAlloc(&scratch, scanScratchInts(n));
+    if (!e) e = launchExclusiveScan(stream, flag, rank, n, scratch);
+    if (!e) {
+        encCellFlagKernel<<<nb, 256, 0, s>>>(n, parent, open, flag);
+        e = int(hipGetLastError());
+    }
+    if (!e) e = encAlloc(&key, size_t(ne));
+    if (!e) e = encAlloc(&cell, size_t(ne));
+    if (!e) e = encAlloc(&keySorted, size_t(ne));
+    if (!e) e = encAlloc(&cells, size_t(ne));
+    if (!e) e = encAlloc(&offsets, size_t(m) + 1);
+    if (!e) e = encAlloc(&pos, n + 1);
+    if (!e) e = launchExclusiveScan(stream, flag, pos, n, scratch);
+    if (!e) {
+        encCompactKernel<<<nb, 256, 0, s>>>(n, parent, open, pos, rank, key, cell);
+        e = int(hipGetLastError());
+    }
+    unsigned endBit = 1;
+    while (endBit < 31 && (int64_t(1) << endBit) < m) ++endBit;
+    size_t tempBytes = 0;
+    if (!e) e = int(rocprim::radix_sort_pairs(nullptr, tempBytes, key, keySorted, cell, cells, size_t(ne), 0u, endBit, s));
+    if (!e) e = deviceAlloc(&sortTemp, std::max<size_t>(tempBytes, 1));
+    if (!e) e = int(rocprim::radix_sort_pairs(sortTemp, tempBytes, key, keySorted, cell, cells, size_t(ne), 0u, endBit, s));
+    if (!e) {
+        encOffsetsKernel<<<blocksFor(size_t(ne), 256), 256, 0, s>>>(ne, m, keySorted, offsets);
+        e = int(hipGetLastError());
+    }
+    release();
+    if (!e) e = int(hipGetLastError());
+    if (e) {
+        (void)deviceFree(cells);
+        (void)deviceFree(offsets);
+        return e;
+    }
+    *cellsOut = cells;
+    *offsetsOut = offsets;
+    *mOut = m;
+    *cellsCount = ne;
+    return 0;
 }
 
 }  // namespace mgps

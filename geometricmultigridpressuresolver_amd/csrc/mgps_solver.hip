@@ -156,6 +156,14 @@ struct mgps_solver {
     double stageMsFine[6] = {0, 0, 0, 0, 0, 0};  // the same, level 0 only
     double stageMsFineLast[6] = {0, 0, 0, 0, 0, 0};  // what the last mgps_stage_times call covered (mgps_stage_times_fine)
     int stageCycles = 0;
+    // options.enclosed_liquid (single device): the enclosed components of level 0 -- their cells grouped by rank (ascending inside a
+    // group), offsets (m + 1), the chunks of the projection (3 ints each: component, first entry, end entry) and each component's first
+    // chunk (m + 1), the projection's fp64 partials and means.  Nothing when m = 0
+    int64_t encM = 0, encCells = 0;
+    int32_t *encCellList = nullptr, *encOffsets = nullptr, *encChunks = nullptr, *encCompChunk = nullptr;
+    int encNChunks = 0;
+    double *encPartials = nullptr, *encMean = nullptr;
+    float *encB = nullptr;  // P b for mgps_solve_pcg / mgps_apply_vcycle (the caller's b stays const; made on first use)
     std::string lastError = "";
 };
 
@@ -467,6 +475,9 @@ void freeAll(mgps_solver *h)
         for (int q = 0; q < 4; ++q) gridFree(h, h->pcg[q], h->lv[0].d);
         gridFree(h, h->dinv, h->lv[0].d);
     }
+    for (void *p : {(void *)h->encCellList, (void *)h->encOffsets, (void *)h->encChunks, (void *)h->encCompChunk, (void *)h->encPartials, (void *)h->encMean})
+        (void)cacheFree(p);
+    if (!h->lv.empty()) gridFree(h, h->encB, h->lv[0].d);
     for (void *p : h->userGrids) (void)cacheFree(p);
     for (hipEvent_t e : h->profEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->stageEvents) (void)hipEventDestroy(e);
@@ -1428,6 +1439,33 @@ struct SolveClock {
     }
 };
 
+// ---- options.enclosed_liquid: P = subtract the mean over each enclosed component of level 0 ------------------------------
+bool hasEnclosed(const mgps_solver *h) { return h->encM > 0; }
+int projectEnclosed(mgps_solver *h, float *v)
+{
+    MGPS_LAUNCH(h, launchEnclosedProject(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCompChunk, h->encOffsets, h->encM, h->encPartials,
+                                         h->encMean));
+    return MGPS_OK;
+}
+int projectEnclosed64(mgps_solver *h, double *v)
+{
+    MGPS_LAUNCH(h, launchEnclosedProject64(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCompChunk, h->encOffsets, h->encM,
+                                           h->encPartials, h->encMean));
+    return MGPS_OK;
+}
+// *out = P b in the solver's scratch grid (b itself stays untouched); b when there is no enclosed component
+int projectedRhs(mgps_solver *h, const float *b, const float **out)
+{
+    *out = b;
+    if (!hasEnclosed(h)) return MGPS_OK;
+    const DevLevel &F = h->lv[0];
+    if (!h->encB) MGPS_TRY(gridAlloc(h, &h->encB, F.d));
+    MGPS_HIP(h, hipMemcpyAsync(h->encB, b, F.d.cells() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    MGPS_TRY(projectEnclosed(h, h->encB));
+    *out = h->encB;
+    return MGPS_OK;
+}
+
 // MG-PCG with the CG vectors in fp64 (options.pcg_fp64_vectors): CG.h:18-207 step by step like pcg() below; the
 // preconditioner is the same fp32 V-cycle (or diagonal) applied to float(r), x and b are fp32 at the boundary
 int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool useMG, mgps_pcg_stats *st)
@@ -1446,23 +1484,27 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     float *r32 = h->pcg[0], *z = h->pcg[2];
     SolveClock clock(h);  // (destroys its events and resets h->dotTarget on every way out)
     if (!clock.ok) return failH(h, MGPS_ERR_HIP, "hipEventCreate failed");
+    const bool enc = hasEnclosed(h);  // options.enclosed_liquid: A x = P b, z = P M r (<z, r> then taken on the projected z)
+    bool narrowed = false;             // (the end of the loop projects x64 before narrowing it into x)
     auto finish = [&](int outcome) {
+        if (enc && !narrowed) (void)projectEnclosed(h, x);
         st->outcome = outcome;
         st->solve_ms = clock.stop();
         return MGPS_OK;
     };
-    bool gathered = false;
+    bool gathered = false;  // options.enclosed_liquid: A x = P b, z = P M r (<z, r> then taken on the projected z)
     auto precondition = [&]() -> int {  // z = M float(r)
         gathered = false;
         if (useMG && h->opt.precision == 1) return vcycleMixed(h, z, r32, false);
         if (useMG) {
-            MGPS_TRY(vcycle(h, z, r32, false, true, true));
-            gathered = h->gatherDot;
-            return MGPS_OK;
-        }
-        MGPS_LAUNCH(h, launchMulMasked(h->stream, F.g, z, r32, h->dinv));
+            MGPS_TRY(vcycle(h, z, r32, false, true, !enc));
+            gathered = h->gatherDot && !enc;
+        } else
+            MGPS_LAUNCH(h, launchMulMasked(h->stream, F.g, z, r32, h->dinv));
+        if (enc) MGPS_TRY(projectEnclosed(h, z));
         return MGPS_OK;
     };
+    MGPS_TRY(projectedRhs(h, b, &b));
     auto zDotR = [&](double *out) -> int {  // <z, float(r)>: r enters the V-cycle rounded, the same rounded r is used here
         if (gathered) return fetchReduction(h, 0, out);
         return reduceToHost(h, 0, 0, z, r32, out);
@@ -1492,6 +1534,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
         MGPS_TRY(interruptRequested(h, &stop));
         if (stop) {
             (void)launchNarrow(h->stream, x, x64, n);  // what the iterations reached so far, as the fp32 loop leaves it
+            narrowed = true;
             finish(MGPS_PCG_MAX_ITERATIONS);
             st->iterations = it;
             return failH(h, MGPS_ERR_INTERRUPTED, "mgps_solve_pcg: interrupted");
@@ -1511,6 +1554,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
         if (const int prc = precondition()) {  // CG.h:168
             if (prc == MGPS_ERR_INTERRUPTED) {  // (polled inside the V-cycle): hand back what the iterations reached
                 (void)launchNarrow(h->stream, x, x64, n);
+                narrowed = true;
                 finish(MGPS_PCG_MAX_ITERATIONS);
                 st->iterations = it;
             }
@@ -1527,7 +1571,9 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     MGPS_LAUNCH(h, launchStencil64(h->stream, 1, F.g, r64, x64, b, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:203-205, in fp64
     MGPS_TRY(fetchReduction(h, 1, &rec2));
     st->rel_residual_recomputed = std::sqrt(rec2 / rhs2);
+    if (enc) MGPS_TRY(projectEnclosed64(h, x64));  // (mean 0 on every enclosed component, before the narrowing)
     MGPS_LAUNCH(h, launchNarrow(h->stream, x, x64, n));
+    narrowed = true;
     return finish(converged ? MGPS_PCG_CONVERGED : MGPS_PCG_MAX_ITERATIONS);
 }
 
@@ -1584,8 +1630,16 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
     SolveClock clock(h);  // (destroys its events and resets h->dotTarget on every way out)
     if (!clock.ok) return failH(h, MGPS_ERR_HIP, "hipEventCreate failed");
     bool widened = false;  // (x64 holds the caller's iterate: from then on x is the sum of the pending updates)
+    const bool enc = hasEnclosed(h);  // options.enclosed_liquid with an enclosed component: see precondition below
     auto finish = [&](int outcome) {
-        if (wideX && widened) (void)launchNarrowSum(h->stream, F.g, x, x64, grouped > 0);  // (what the iterations reached, rounded once)
+        if (wideX && widened && enc) {  // mean 0 on every enclosed component, taken on the fp64 iterate (+ the pending updates) before the narrowing
+            if (grouped > 0) (void)launchWidenAdd(h->stream, x64, x, F.d.cells());
+            (void)projectEnclosed64(h, x64);
+            (void)launchNarrowSum(h->stream, F.g, x, x64, false);
+        } else if (wideX && widened)
+            (void)launchNarrowSum(h->stream, F.g, x, x64, grouped > 0);  // (what the iterations reached, rounded once)
+        else if (enc)
+            (void)projectEnclosed(h, x);  // mean 0 on every enclosed component
         st->outcome = outcome;
         st->solve_ms = clock.stop();
         return MGPS_OK;
@@ -1604,10 +1658,17 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
         return fetchReduction(h, 1, res2);
     };
     // dst = M src; gathered: <dst, src> is already in h->resultDev (a by-product of the V-cycle's last stroke)
+    // options.enclosed_liquid with an enclosed component: A x = P b, dst = P M src, and <dst, src> is taken on the projected dst
+    // (the V-cycle gathers none)
     bool gathered = false;
     auto precondition = [&](float *dst, const float *src) -> int {
         gathered = false;
         if (useMG && h->opt.precision == 1) return vcycleMixed(h, dst, src, false);  // (the first application, p = M r: CG.h:75)
+        if (enc) {
+            if (useMG) MGPS_TRY(vcycle(h, dst, src, false, true, false));
+            else MGPS_LAUNCH(h, launchMulMasked(h->stream, F.g, dst, src, h->dinv));
+            return projectEnclosed(h, dst);
+        }
         if (useMG) {
             MGPS_TRY(vcycle(h, dst, src, false, true, true));  // Plug.cpp:468-472 (dst = p or z: grids of the solver)
             gathered = h->gatherDot;
@@ -1616,6 +1677,7 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
         MGPS_LAUNCH(h, launchMulMasked(h->stream, F.g, dst, src, h->dinv));  // Plug.cpp:555-606
         return MGPS_OK;
     };
+    MGPS_TRY(projectedRhs(h, b, &b));
     static const bool checkGathered = [] {  // MGPS_CHECK_FUSED_DOT=1: compare every gathered <z, r> with a separate reduction
         const char *e = getenv("MGPS_CHECK_FUSED_DOT");
         return e && e[0] == '1';
@@ -1694,6 +1756,9 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
         // t = A p (CG.h:110) and <p, A p> (CG.h:121) in one pass over p
         MGPS_TRY(exchangeGhosts(h, 0, p));
         MGPS_LAUNCH(h, launchApplyDot(h->stream, F.g, t, p, h->dotPartials, devScal ? scal + 1 : h->resultDev));
+        // (enclosed components: A p sums to 0 over each of them only up to the rounding of the fp32 products, eps |A| |p|, which
+        // the recurrence r -= alpha A p would pile up in r as a constant no preconditioner removes -- the residual then stalls)
+        if (enc) MGPS_TRY(projectEnclosed(h, t));
         if (devScal) MGPS_TRY(sumOverRanks(scal + 1));
         double alpha = 0;
         if (!devScal) {
@@ -1985,6 +2050,7 @@ struct HipSolver {
 struct DeviceInverse {
     float *p = nullptr;
     int n = 0, device = 0;
+    bool pinned = false;  // options.enclosed_liquid pinned unknowns of the coarsest level (the same labels give another inverse)
     Dims d;
     std::vector<uint8_t> labels;
     ~DeviceInverse() { (void)cacheFree(p); }
@@ -2015,7 +2081,7 @@ int buildDeviceInverse(mgps_solver *h)
         std::lock_guard<std::mutex> lock(gDevInverseGuard);
         for (size_t q = 0; q < gDevInverseKept.size(); ++q) {
             const std::shared_ptr<DeviceInverse> k = gDevInverseKept[q];
-            if (k->n == n && k->device == h->device && k->d.nx == C.d.nx && k->d.ny == C.d.ny && k->d.nz == C.d.nz && k->labels.size() == C.labels.size() &&
+            if (k->n == n && k->device == h->device && k->pinned == !hier->coarsePinned.empty() && k->d.nx == C.d.nx && k->d.ny == C.d.ny && k->d.nz == C.d.nz && k->labels.size() == C.labels.size() &&
                 std::memcmp(k->labels.data(), C.labels.data(), C.labels.size()) == 0) {
                 std::rotate(gDevInverseKept.begin(), gDevInverseKept.begin() + ptrdiff_t(q), gDevInverseKept.begin() + ptrdiff_t(q) + 1);  // most recent first
                 h->cinvShared = k;
@@ -2034,7 +2100,7 @@ int buildDeviceInverse(mgps_solver *h)
     const int kLower = 122;  // HIPSOLVER_FILL_MODE_LOWER
     double *A = nullptr, *work = nullptr;
     int32_t *index = nullptr, *cells = nullptr;
-    uint8_t *lab = nullptr;
+    uint8_t *lab = nullptr, *pinned = nullptr;
     int *info = nullptr;
     void *handle = nullptr;
     auto cleanup = [&] {
@@ -2044,6 +2110,7 @@ int buildDeviceInverse(mgps_solver *h)
         (void)cacheFree(index);
         (void)cacheFree(cells);
         (void)cacheFree(lab);
+        (void)cacheFree(pinned);
         (void)cacheFree(info);
         if (handle) (void)solver->destroy(handle);
     };
@@ -2058,7 +2125,12 @@ int buildDeviceInverse(mgps_solver *h)
     if (hipMemsetAsync(lab, MGPS_EXTERIOR_CELL, C.labels.size() + 2 * plane, h->stream) != hipSuccess ||
         hipMemcpyAsync(lab + plane, C.labels.data(), C.labels.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess)
         return fail("label upload");
-    if (launchCoarseAssemble(h->stream, n, C.d.nx, C.d.ny, cells, index, lab + plane, A) != 0) return fail("assembly launch");
+    if (!hier->coarsePinned.empty()) {  // (options.enclosed_liquid)
+        std::vector<uint8_t> flags(size_t(n), 0);
+        for (int32_t p : hier->coarsePinned) flags[size_t(p)] = 1;
+        if (devUpload(h, &pinned, flags) != MGPS_OK) return fail("allocation");
+    }
+    if (launchCoarseAssemble(h->stream, n, C.d.nx, C.d.ny, cells, index, lab + plane, A, pinned) != 0) return fail("assembly launch");
     if (solver->create(&handle) != 0 || solver->setStream(handle, h->stream) != 0) return fail("hipsolverCreate");
     int lw1 = 0, lw2 = 0;
     if (solver->potrfSize(handle, kLower, n, A, n, &lw1) != 0 || solver->potriSize(handle, kLower, n, A, n, &lw2) != 0) return fail("workspace query");
@@ -2074,11 +2146,29 @@ int buildDeviceInverse(mgps_solver *h)
     auto inv = std::make_shared<DeviceInverse>();
     if (devAlloc(h, &inv->p, size_t(n) * n, false) != MGPS_OK) return fail("inverse allocation");
     if (launchCoarseNarrow(h->stream, n, A, inv->p) != 0) return fail("narrow launch");
+    for (int32_t p : hier->coarsePinned)  // (the identity's diagonal: a pinned unknown comes out 0)
+        if (hipMemsetAsync(inv->p + size_t(p) * n + p, 0, sizeof(float), h->stream) != hipSuccess) return fail("pin");
+    if (!hier->coarseComp.empty()) {  // the pseudo-inverse (mgps_hierarchy::coarseComp)
+        std::vector<int32_t> counts(hier->coarsePinned.size(), 0);
+        for (int32_t c : hier->coarseComp)
+            if (c >= 0) ++counts[size_t(c)];
+        int32_t *compDev = nullptr, *countsDev = nullptr;
+        double *wDev = nullptr;
+        bool ok = devUpload(h, &compDev, hier->coarseComp) == MGPS_OK && devUpload(h, &countsDev, counts) == MGPS_OK &&
+                  devAlloc(h, &wDev, size_t(n) + counts.size(), false) == MGPS_OK &&
+                  launchCoarseInverseProject(h->stream, n, inv->p, compDev, int(counts.size()), countsDev, wDev, wDev + n) == 0 &&
+                  hipStreamSynchronize(h->stream) == hipSuccess;
+        (void)cacheFree(compDev);
+        (void)cacheFree(countsDev);
+        (void)cacheFree(wDev);
+        if (!ok) return fail("projection of the pinned inverse");
+    }
     if (hipMemcpyAsync(&hinfo, info, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess || hinfo != 0)
         return fail("potri reported " + std::to_string(hinfo));
     cleanup();
     inv->n = n;
     inv->device = h->device;
+    inv->pinned = !hier->coarsePinned.empty();
     inv->d = C.d;
     inv->labels.assign(C.labels.begin(), C.labels.end());
     h->cinvShared = inv;
@@ -2251,6 +2341,10 @@ int readOptions(const mgps_options *opt, mgps_options *o)
     if (o->pre_sweeps < 1 || o->post_sweeps < 1 || o->stencil_path < 0 || o->stencil_path > 2 || o->precision < 0 || o->precision > 1)
         return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT,
                      "mgps_options: pre_sweeps / post_sweeps must be >= 1, stencil_path 0, 1 or 2, precision 0 or 1");
+    if (o->enclosed_liquid != 0 && o->enclosed_liquid != 1)
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_options.enclosed_liquid must be 0 or 1");
+    if (o->enclosed_liquid && o->precision == 1)
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_options: enclosed_liquid is not available with precision = 1 (mixed precision)");
     return MGPS_OK;
 }
 
@@ -2262,6 +2356,77 @@ bool hostSetup(const mgps_options &o)
         return e && e[0] == '1';
     }();
     return o.host_setup != 0 || env;
+}
+
+// options.enclosed_liquid: label the components of level 0 -- on the device (union-find, mgps_setup.hip), or with the host builder
+// (options.host_setup: the checker; codes and weights come down for it) -- and keep what the projection needs when some are enclosed
+int setupEnclosed(mgps_solver *h, bool onHost)
+{
+    if (h->opt.enclosed_liquid != 1) return MGPS_OK;
+    DevLevel &F = h->lv[0];
+    const Dims d = F.d;
+    if (d.cells() > size_t(INT32_MAX))  // (the component lists hold int32 cell indices; the hierarchy builders refuse such grids already)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT, "options.enclosed_liquid: more than 2^31 - 1 cells");
+    MGPS_HIP(h, hipDeviceSynchronize());  // (the set-up kernels ran on the null stream)
+    std::vector<int32_t> offsets;
+    if (onHost) {
+        std::vector<uint8_t> lab(d.cells());
+        MGPS_HIP(h, hipMemcpy(lab.data(), F.g.lab, d.cells(), hipMemcpyDeviceToHost));
+        for (uint8_t &c : lab)
+            if (c > MGPS_BOUNDARY_CELL) c = MGPS_BOUNDARY_CELL;  // (simple BOUNDARY codes)
+        const size_t wn[3] = {size_t(d.nx + 1) * d.ny * d.nz, size_t(d.nx) * (d.ny + 1) * d.nz, size_t(d.nx) * d.ny * (d.nz + 1)};
+        std::vector<float> w[3];
+        for (int a = 0; a < 3; ++a) {
+            w[a].resize(wn[a]);
+            MGPS_HIP(h, hipMemcpy(w[a].data(), h->w[a], wn[a] * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        std::vector<int32_t> cells;
+        enclosedComponentsHost(lab.data(), w[0].data(), w[1].data(), w[2].data(), d, offsets, cells);
+        h->encM = int64_t(offsets.size()) - 1;
+        h->encCells = int64_t(cells.size());
+        if (h->encM > 0) {
+            MGPS_TRY(devUpload(h, &h->encCellList, cells));
+            MGPS_TRY(devUpload(h, &h->encOffsets, offsets));
+        }
+    } else {
+        const int e = enclosedComponentsDevice(h->stream, d, F.g.lab, h->w[0], h->w[1], h->w[2], &h->encCellList, &h->encOffsets, &h->encM, &h->encCells);
+        if (e != 0) return failH(h, MGPS_ERR_HIP, std::string("enclosed-liquid labelling: ") + hipGetErrorString(hipError_t(e)));
+        if (h->encM > 0) {
+            offsets.resize(size_t(h->encM) + 1);
+            MGPS_HIP(h, hipMemcpy(offsets.data(), h->encOffsets, offsets.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        }
+    }
+    if (h->encM == 0) return MGPS_OK;
+    // chunks of at most kEncChunkCells cells of one component: the fixed summation order of the projection
+    std::vector<int32_t> chunks, compChunk;
+    for (int64_t r = 0; r < h->encM; ++r) {
+        compChunk.push_back(int32_t(chunks.size() / 3));
+        for (int32_t e0 = offsets[size_t(r)]; e0 < offsets[size_t(r) + 1]; e0 += kEncChunkCells) {
+            chunks.push_back(int32_t(r));
+            chunks.push_back(e0);
+            chunks.push_back(std::min(offsets[size_t(r) + 1], e0 + kEncChunkCells));
+        }
+    }
+    compChunk.push_back(int32_t(chunks.size() / 3));
+    h->encNChunks = int(chunks.size() / 3);
+    MGPS_TRY(devUpload(h, &h->encChunks, chunks));
+    MGPS_TRY(devUpload(h, &h->encCompChunk, compChunk));
+    MGPS_TRY(devAlloc(h, &h->encPartials, size_t(h->encNChunks), true));
+    MGPS_TRY(devAlloc(h, &h->encMean, size_t(h->encM), true));
+    MGPS_HIP(h, hipDeviceSynchronize());
+    return MGPS_OK;
+}
+// the tail of every single-device constructor: a solver that fails the labelling is not handed out
+int finishEnclosed(mgps_solver **out, int rc, bool onHost)
+{
+    if (rc != MGPS_OK || !*out) return rc;
+    const int e = setupEnclosed(*out, onHost);
+    if (e != MGPS_OK) {
+        setLastGlobalError((*out)->lastError);
+        freeAll(*out);
+        *out = nullptr;
+    }
+    return e;
 }
 
 // whole-grid solver on one device.  weights may be nullptr (unit weights: the collapsed tail)
@@ -2891,7 +3056,9 @@ try {
     MGPS_TRY(readOptions(opt, &o));
     int device = 0;
     MGPS_TRY(pickDevice(o, &device));
-    if (!hostSetup(o)) return createWholeOnDevice(out, nx, ny, nz, labels_host, wx_host, wy_host, wz_host, hipMemcpyHostToDevice, mg_levels, use_gauss_seidel != 0, o, device);
+    if (!hostSetup(o))
+        return finishEnclosed(out, createWholeOnDevice(out, nx, ny, nz, labels_host, wx_host, wy_host, wz_host, hipMemcpyHostToDevice, mg_levels, use_gauss_seidel != 0, o, device),
+                              false);
     mgps_hierarchy *hier = nullptr;
     MGPS_TRY(mgps_hierarchy_create(&hier, nx, ny, nz, labels_host, mg_levels, &o));
     {  // the fine-level invariants the reference asserts in debug builds (MG.cpp:234)
@@ -2903,7 +3070,7 @@ try {
                          "labels/weights violate the BOUNDARY-cell rules (unitTestBoundaryCells): run mgps_set_boundary_labels");
         }
     }
-    return createWhole(out, hier, wx_host, wy_host, wz_host, use_gauss_seidel != 0, o, device, false);
+    return finishEnclosed(out, createWhole(out, hier, wx_host, wy_host, wz_host, use_gauss_seidel != 0, o, device, false), true);
 }
 MGPS_API_CATCH(nullptr)
 
@@ -2959,7 +3126,8 @@ int createFromDeviceWeights(mgps_solver **out, int nx, int ny, int nz, const uin
     if (violations != 0 || !interiorOk)
         return drop(MGPS_ERR_HIERARCHY,
                     "labels/weights violate the BOUNDARY-cell rules (unitTestBoundaryCells): run mgps_fields_set_boundary_labels");
-    return createWhole(out, hier, wx_dev, wy_dev, wz_dev, use_gauss_seidel != 0, o, device, false, rows.empty() ? &kNoRows : rows.data());
+    return finishEnclosed(out, createWhole(out, hier, wx_dev, wy_dev, wz_dev, use_gauss_seidel != 0, o, device, false, rows.empty() ? &kNoRows : rows.data()),
+                          true);
 }
 }  // namespace
 
@@ -2987,7 +3155,7 @@ try {
                          ? createWholeOnDevice(out, nx, ny, nz, lab, wx_dev, wy_dev, wz_dev, hipMemcpyDeviceToDevice, mg_levels, use_gauss_seidel != 0, o, device)
                          : failH(nullptr, MGPS_ERR_HIP, "mgps_create_device_weights: label upload failed");
             (void)cacheFree(lab);
-            return rc;
+            return finishEnclosed(out, rc, false);
         }
     }
     return createFromDeviceWeights(out, nx, ny, nz, labels_host, nullptr, wx_dev, wy_dev, wz_dev, mg_levels, use_gauss_seidel, opt);
@@ -3005,7 +3173,9 @@ try {
     MGPS_TRY(readOptions(opt, &o));
     int device = 0;
     MGPS_TRY(pickDevice(o, &device));
-    if (!hostSetup(o)) return createWholeOnDevice(out, nx, ny, nz, labels_dev, wx_dev, wy_dev, wz_dev, hipMemcpyDeviceToDevice, mg_levels, use_gauss_seidel != 0, o, device);
+    if (!hostSetup(o))
+        return finishEnclosed(out, createWholeOnDevice(out, nx, ny, nz, labels_dev, wx_dev, wy_dev, wz_dev, hipMemcpyDeviceToDevice, mg_levels, use_gauss_seidel != 0, o, device),
+                              false);
     // options.host_setup: the hierarchy and the lists are built on the host from one byte per cell
     RawVec<uint8_t> labels(size_t(nx) * ny * nz);
     if (hipMemcpy(labels.data(), labels_dev, labels.size(), hipMemcpyDeviceToHost) != hipSuccess)
@@ -3952,6 +4122,8 @@ int createSlabImpl(mgps_solver **out, int nx, int ny, int nz_global, const uint8
     *out = nullptr;
     if (!labels_global_host || !wx_slab || !wy_slab || !wz_slab || !comm || !splits)
         return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: labels, the slab weights, a comm and the cuts are required");
+    if (opt && opt->struct_size == int(sizeof(mgps_options)) && opt->enclosed_liquid != 0)
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: options.enclosed_liquid is for single-device solvers only");
     // (a transport built against the header before `allreduce_device` was appended is accepted: the missing tail reads as NULL)
     if (comm->struct_size < int(offsetof(mgps_comm, allreduce_device)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange || !comm->allreduce ||
         !comm->gather || !comm->scatter || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
@@ -4212,6 +4384,21 @@ try {
     case 11: src = L.bandBoxes.info, n = size_t(kBoxInfoInts) * size_t(L.bandBoxes.ngroups); break;
     case 12: src = L.bandBoxes.list, n = L.bandBoxes.listCount; break;
     case 13: src = L.bandBoxes.general, n = L.bandBoxes.generalInts; break;
+    case 14: {  // (made here from the component lists: the solver keeps no per-cell array)
+        if (level != 0 || h->opt.enclosed_liquid != 1 || h->dist)
+            return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_level_array: array 14 exists on level 0 with options.enclosed_liquid only");
+        *count = int64_t(L.d.cells());
+        if (!out) return MGPS_OK;
+        int32_t *rank = nullptr;
+        MGPS_TRY(devAlloc(h, &rank, L.d.cells(), false));
+        int rc = MGPS_OK;
+        if (hipMemsetAsync(rank, 0xff, L.d.cells() * sizeof(int32_t), h->stream) != hipSuccess ||
+            launchEnclosedRanks(h->stream, rank, h->encCellList, h->encChunks, h->encNChunks) != 0 || hipStreamSynchronize(h->stream) != hipSuccess ||
+            hipMemcpy(out, rank, L.d.cells() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = failH(h, MGPS_ERR_HIP, "mgps_level_array: enclosed-component ranks");
+        (void)cacheFree(rank);
+        return rc;
+    }
     default: return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_level_array: unknown array");
     }
     *count = int64_t(n);
@@ -4356,6 +4543,12 @@ try {
     MGPS_TRY(checkLevel(h, 0, "mgps_apply_vcycle"));
     if (!x_dev || !b_dev || x_dev == b_dev) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_apply_vcycle: bad grid pointers");
     if (h->opt.precision == 1) return vcycleMixed(h, x_dev, b_dev, use_initial_guess != 0);
+    if (hasEnclosed(h)) {  // options.enclosed_liquid: P V(P b), a symmetric operator on the range of A
+        const float *pb = nullptr;
+        MGPS_TRY(projectedRhs(h, b_dev, &pb));
+        MGPS_TRY(vcycle(h, x_dev, pb, use_initial_guess != 0));
+        return projectEnclosed(h, x_dev);
+    }
     return vcycle(h, x_dev, b_dev, use_initial_guess != 0);
 }
 MGPS_API_CATCH(h)
@@ -4540,6 +4733,33 @@ try {
     if (!x_dev || !b_dev || x_dev == b_dev || !(tolerance >= 0) || max_iterations < 0)
         return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_solve_pcg: bad arguments");
     return pcg(h, x_dev, const_cast<float *>(b_dev), tolerance, max_iterations, use_mg_preconditioner != 0, stats);
+}
+MGPS_API_CATCH(h)
+
+int mgps_enclosed_components(const mgps_solver *h, int64_t *components, int64_t *cells)
+{
+    if (!h) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_enclosed_components: NULL handle");
+    if (components) *components = h->encM;
+    if (cells) *cells = h->encCells;
+    return MGPS_OK;
+}
+
+int mgps_project_enclosed(mgps_solver *h, float *v_dev, double *max_abs_mean_removed)
+try {
+    MGPS_TRY(checkLevel(h, 0, "mgps_project_enclosed"));
+    if (!v_dev) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_project_enclosed: v is NULL");
+    if (max_abs_mean_removed) *max_abs_mean_removed = 0.0;
+    if (!hasEnclosed(h)) return MGPS_OK;
+    MGPS_TRY(projectEnclosed(h, v_dev));
+    if (max_abs_mean_removed) {
+        std::vector<double> mean(size_t(h->encM));
+        MGPS_HIP(h, hipMemcpyAsync(mean.data(), h->encMean, mean.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        MGPS_HIP(h, hipStreamSynchronize(h->stream));
+        double mx = 0.0;
+        for (double v : mean) mx = std::max(mx, std::fabs(v));
+        *max_abs_mean_removed = mx;
+    }
+    return MGPS_OK;
 }
 MGPS_API_CATCH(h)
 

@@ -140,6 +140,7 @@ class Projection(C.Structure):
         ("liquid_cells", C.c_double), ("residual_inf", C.c_double), ("residual_l2", C.c_double),
         ("divergence_sum", C.c_double), ("divergence_max", C.c_double),
         ("setup_ms", C.c_double), ("solve_ms", C.c_double), ("total_ms", C.c_double),
+        ("enclosed_components", C.c_int), ("rhs_mean_removed_max", C.c_double),
     ]
 
 
@@ -180,5 +181,6 @@ def project_free_surface(liquid_phi, solid_phi, cut_weights, velocity, pressure,
         "expanded": (pr.expanded[2], pr.expanded[1], pr.expanded[0]), "liquid_cells": pr.liquid_cells,
         "residual_inf": pr.residual_inf, "residual_l2": pr.residual_l2, "divergence_sum": pr.divergence_sum,
         "divergence_max": pr.divergence_max, "setup_ms": pr.setup_ms, "solve_ms": pr.solve_ms, "total_ms": pr.total_ms,
+        "enclosed_components": pr.enclosed_components, "rhs_mean_removed_max": pr.rhs_mean_removed_max,
     }
     return valid, info

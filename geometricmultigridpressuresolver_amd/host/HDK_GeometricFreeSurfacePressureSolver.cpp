@@ -31,7 +31,8 @@ void initializeSIM(void *)
 HDK_GeometricFreeSurfacePressureSolver::HDK_GeometricFreeSurfacePressureSolver(const SIM_DataFactory *factory) : BaseClass(factory) {}
 HDK_GeometricFreeSurfacePressureSolver::~HDK_GeometricFreeSurfacePressureSolver() {}
 
-// The node interface: twelve parameters with the reference's tokens, labels, types, defaults and order (Plug.cpp:39-99).
+// The node interface: twelve parameters with the reference's tokens, labels, types, defaults and order (Plug.cpp:39-99), and one
+// toggle of this library's own after them ("handleEnclosedLiquid", off: options.enclosed_liquid).
 const SIM_DopDescription *HDK_GeometricFreeSurfacePressureSolver::getDopDescription()
 {
     static PRM_Name surfaceName(GAS_NAME_SURFACE, "Surface Field");
@@ -55,6 +56,8 @@ const SIM_DopDescription *HDK_GeometricFreeSurfacePressureSolver::getDopDescript
     static PRM_Name maxIterationsName("maxIterations", "Max Solver Iterations");
     static PRM_Default maxIterationsDefault(2500);
     static PRM_Name useMGName("useMGPreconditioner", "Use Multigrid Preconditioner");
+    static PRM_Name handleEnclosedName("handleEnclosedLiquid", "Handle Enclosed Liquid");
+    static PRM_Default handleEnclosedDefault(0);
 
     static PRM_Template templates[] = {PRM_Template(PRM_STRING, 1, &surfaceName, &surfaceDefault),
                                        PRM_Template(PRM_STRING, 1, &velocityName, &velocityDefault),
@@ -68,6 +71,7 @@ const SIM_DopDescription *HDK_GeometricFreeSurfacePressureSolver::getDopDescript
                                        PRM_Template(PRM_FLT, 1, &toleranceName, &toleranceDefault),
                                        PRM_Template(PRM_INT, 1, &maxIterationsName, &maxIterationsDefault),
                                        PRM_Template(PRM_TOGGLE, 1, &useMGName, PRMoneDefaults),
+                                       PRM_Template(PRM_TOGGLE, 1, &handleEnclosedName, &handleEnclosedDefault),
                                        PRM_Template()};
 
     static SIM_DopDescription description(true, "HDK_GeometricFreeSurfacePressureSolver", "HDK Geometric Free Surface Pressure Solver", "$OS",
@@ -243,8 +247,8 @@ bool HDK_GeometricFreeSurfacePressureSolver::solveGasSubclass(SIM_Engine &, SIM_
     }
     job.use_old_pressure = getUseOldPressure();
     job.use_mg_preconditioner = getUseMGPreconditioner();
-    // The reference hard-wires the tiled Gauss-Seidel smoother here (Plug.cpp:466) and so does this node: the twelve parameters stay
-    // as they are.  MGPS_DOP_SMOOTHER=jacobi in the environment of the Houdini session selects the damped-Jacobi smoother of
+    // The reference hard-wires the tiled Gauss-Seidel smoother here (Plug.cpp:466) and so does this node: the reference's twelve
+    // parameters stay as they are.  MGPS_DOP_SMOOTHER=jacobi in the environment of the Houdini session selects the damped-Jacobi smoother of
     // MG.cpp:480-486 instead -- on MI355X the faster preconditioner (512^3 free-surface pool, MG-PCG to 1e-5: 57 ms against 72 ms
     // with Gauss-Seidel, one iteration more): same solver tolerance, same pressure to that tolerance.
     const char *smoother = getenv("MGPS_DOP_SMOOTHER");
@@ -255,6 +259,8 @@ bool HDK_GeometricFreeSurfacePressureSolver::solveGasSubclass(SIM_Engine &, SIM_
     mgps_options opt;
     mgps_default_options(&opt);
     opt.interrupt = pollInterrupt;
+    // sealed pockets of liquid (a tank filled to its lid, liquid under a solid): projected instead of left singular (off by default)
+    opt.enclosed_liquid = getHandleEnclosedLiquid() ? 1 : 0;
     int rc;
     {
         UT_PerfMonAutoSolveEvent event(this, "Solve linear system");

@@ -26,6 +26,8 @@ public:
     GET_DATA_FUNC_I("maxIterations", MaxSolverIterations);
     GET_DATA_FUNC_B("useMGPreconditioner", UseMGPreconditioner);
     GET_DATA_FUNC_B("useOldPressure", UseOldPressure);
+    // no counterpart in the reference: liquid that touches no air is solved too (mgps_options.enclosed_liquid)
+    GET_DATA_FUNC_B("handleEnclosedLiquid", HandleEnclosedLiquid);
 
 protected:
     explicit HDK_GeometricFreeSurfacePressureSolver(const SIM_DataFactory *factory);

@@ -371,6 +371,27 @@ class GeometricMultigridPoissonSolver:
             "solve_ms": st.solve_ms,
         }
 
+    # -- enclosed liquid (options.enclosed_liquid) ------------------------------------------------------
+    def enclosed_components(self):
+        """(components, cells): the fine level's liquid components without a DIRICHLET contact; (0, 0) with the option off."""
+        m, n = C.c_int64(), C.c_int64()
+        check(lib().mgps_enclosed_components(self.h, C.byref(m), C.byref(n)), self.h)
+        return m.value, n.value
+
+    def enclosed_ranks(self):
+        """mgps_level_array(h, 0, 14): per fine cell the rank of its enclosed component, -1 elsewhere (options.enclosed_liquid only)."""
+        n = C.c_int64()
+        check(lib().mgps_level_array(self.h, 0, 14, None, C.byref(n)), self.h)
+        out = np.empty(n.value, dtype=np.int32)
+        check(lib().mgps_level_array(self.h, 0, 14, _p(out), C.byref(n)), self.h)
+        return out
+
+    def project_enclosed(self, v):
+        """v -= its mean over each enclosed component, in place; returns the largest |mean| removed."""
+        out = C.c_double()
+        check(lib().mgps_project_enclosed(self.h, self._g(v), C.byref(out)), self.h)
+        return out.value
+
     # -- measurement hooks ---------------------------------------------------------------------------
     def profile_enable(self, on=True):
         """on: False / True (fine-smoother events) / 2 (also per-stage events, see stage_times)"""

@@ -143,6 +143,19 @@ typedef struct mgps_options {
        they must stay valid and unchanged until mgps_destroy -- instead of keeping its own copy (12 B per cell, 13 GB and
        5 ms at 1024^3).  0 (default): copy; the caller may release them right after the constructor returns */
     int borrow_device_weights;
+    /* 1: liquid that touches no air is solved too.  Every connected body of active cells needs a DIRICHLET contact for the
+       system to be non-singular; a tank filled to its lid, liquid trapped under a solid or a region cut off by closed faces
+       (weight 0) gives a graph Laplacian whose null space is the constant on that region, and the reference's coarse Cholesky
+       only asserts (MG.cpp:409-411).  With this option a single-device solver labels the components of the fine level's
+       active cells at set-up (two active cells are coupled when either is INTERIOR, two BOUNDARY cells when their face weight
+       is > 0) and calls a component "enclosed" when none of its BOUNDARY cells has a DIRICHLET neighbour behind a face of
+       weight > 0.  With P = "subtract the mean over each enclosed component", mgps_solve_pcg solves A x = P b (rhs norm,
+       residuals and early-outs refer to P b; the preconditioner output is projected; the returned x has mean 0 on every
+       enclosed component) and mgps_apply_vcycle returns P V(P b).  The coarsest level pins the minimum-index cell of each of
+       its own components without a DIRICHLET neighbour (the pinned unknown is 0).  Domains without an enclosed component give
+       the results of 0 bit for bit (the labelling is the only extra work).  0 (default): today's behaviour.  Refused on slab
+       solvers and with precision = 1 */
+    int enclosed_liquid;
 } mgps_options;
 
 typedef struct mgps_pcg_stats {
@@ -164,7 +177,9 @@ int mgps_device_count(int *count);
  * 0 cell codes (u8, nx*ny*nz), 1 band list in device order (i32), 2 band diagonals (u8), 3 operator rows of the general
  * BOUNDARY cells (f32, 7 x count SoA), 4 activity chunks (i32), 5 plane blocks (i32), 6 / 7 pure tiles even / odd (i32),
  * 8 / 9 mixed tiles even / odd (i32), 10 per-tile start of the general BOUNDARY cells (i32), 11..13 the boxes of the fused
- * band stage: info (i32, 16 per group, in launch order), list entries (u32), general entries (i32, 2 per entry).
+ * band stage: info (i32, 16 per group, in launch order), list entries (u32), general entries (i32, 2 per entry), 14 (level 0,
+ * options.enclosed_liquid only) the rank of a cell's enclosed component (i32, nx*ny*nz; -1 on every other cell; components
+ * ranked by their minimum linear cell index).
  * *count = number of elements; out == NULL asks for the count only. */
 int mgps_level_array(mgps_solver *h, int level, int which, void *out, int64_t *count);
 
@@ -333,6 +348,15 @@ int mgps_zero_inactive(mgps_solver *h, int level, float *grid_dev);
  * preconditioner (0; Plug.cpp:485-618).  x_dev holds the initial guess and receives the solution. */
 int mgps_solve_pcg(mgps_solver *h, float *x_dev, const float *b_dev, double tolerance,
                    int max_iterations, int use_mg_preconditioner, mgps_pcg_stats *stats);
+
+/* ---- enclosed liquid (options.enclosed_liquid; the reference has no counterpart, MG.cpp:409-411 only asserts) ------------
+ * *components: the enclosed components of the fine level, *cells: the cells they hold (either may be NULL); 0 / 0 when the
+ * option is off. */
+int mgps_enclosed_components(const mgps_solver *h, int64_t *components, int64_t *cells);
+/* v = P v on a level-0 grid: the mean over each enclosed component is subtracted from its cells, every other cell is left
+ * as it is, bit for bit.  Sums in fp64 in a fixed order (same input, same bits).  max_abs_mean_removed (may be NULL): the
+ * largest |mean| removed (0 without enclosed components); synchronises the stream when it is asked for. */
+int mgps_project_enclosed(mgps_solver *h, float *v_dev, double *max_abs_mean_removed);
 
 /* ---- multi-GPU: Z-slab partition of the fine grid -------------------------------------------
  * The reference is single-process shared memory (TBB over 16^3 tiles); it has no counterpart for

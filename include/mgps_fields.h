@@ -98,6 +98,11 @@ typedef struct mgps_projection {
     double residual_inf, residual_l2;       /* of the computed solution (Plug.cpp:625-628; infNorm is the signed max) */
     double divergence_sum, divergence_max;  /* after the projection (Plug.cpp:704-706); divergence_count = liquid_cells */
     double setup_ms, solve_ms, total_ms;    /* host wall clock: everything before the solve / the solve / the whole call */
+    /* options.enclosed_liquid: the liquid components that touch no air (mgps_enclosed_components) and the largest |mean| of the
+       right-hand side removed on one of them (mgps_project_enclosed; rhs units).  On such a component the reported divergence
+       is that mean: the part no pressure can remove.  0 / 0 with the option off */
+    int enclosed_components;
+    double rhs_mean_removed_max;
 } mgps_projection;
 /* status MGPS_ERR_HIERARCHY with outcome MGPS_PCG_RHS_ZERO-like early outs are reported through stats.outcome; a domain
  * without liquid returns MGPS_OK with liquid_cells = 0 and leaves velocity and pressure untouched */
