@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -219,6 +220,143 @@ __global__ void pressureGradientKernel(Box g, int axis, float *__restrict__ velo
     velocity[f] -= grad;
 }
 
+// ---- surface tension: a non-zero interface pressure p_G on liquid/air faces ------------------------
+// p_G of the liquid/air face between cells b (behind) and c (front): sp interpolated to the interface, theta measured from
+// the liquid cell.  liquidBehind tells which of the two cells is the liquid one.
+__device__ __forceinline__ float interfacePressure(float theta, bool liquidBehind, float spb, float spc)
+{
+    const float spL = liquidBehind ? spb : spc, spA = liquidBehind ? spc : spb;
+    return (1.f - theta) * spL + theta * spA;
+}
+
+// (i, j, k) of this thread in a (ceil(gx / 256), gy, gz) launch: no 64-bit division for the index; false past the row's end
+__device__ __forceinline__ bool cellOfThread(const Box &g, int &i, int &j, int &k)
+{
+    i = int(blockIdx.x * blockDim.x + threadIdx.x);
+    j = int(blockIdx.y);
+    k = int(blockIdx.z);
+    return i < g.gx;
+}
+// LIQUID or AIR cell with a 6-neighbour of the other kind (the six labels are loaded together, not one after the other)
+__device__ __forceinline__ bool isInterfaceCell(const Box &g, const int32_t *__restrict__ material, int i, int j, int k, int m)
+{
+    const size_t c = cellAt(g, i, j, k), sy = size_t(g.gx), sz = size_t(g.gx) * g.gy;
+    const int n[6] = {material[i > 0 ? c - 1 : c], material[i + 1 < g.gx ? c + 1 : c], material[j > 0 ? c - sy : c],
+                      material[j + 1 < g.gy ? c + sy : c], material[k > 0 ? c - sz : c], material[k + 1 < g.gz ? c + sz : c]};
+    const int other = m == kLiquid ? kAir : kLiquid;
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) any |= n[q] == other;  // (an out-of-grid neighbour reads the cell itself: never `other`)
+    return (m == kLiquid || m == kAir) && any;
+}
+inline dim3 cellGrid(int gx, int gy, int gz) { return dim3(unsigned((gx + 255) / 256), unsigned(gy), unsigned(gz)); }
+
+// sp = scale * clamp(kappa, -1, 1) at every LIQUID or AIR cell with a 6-neighbour of the other kind, 0 elsewhere.  kappa is the
+// mean curvature div(grad phi / |grad phi|) from unit-spacing central differences (19 points, indices clamped into the grid),
+// evaluated in double: only interface cells do it, and they are a thin shell.
+__global__ __launch_bounds__(256) void surfacePressureKernel(Box g, float *__restrict__ sp, const float *__restrict__ phi,
+                                                             const int32_t *__restrict__ material, double scale)
+{
+    int i, j, k;
+    if (!cellOfThread(g, i, j, k)) return;
+    const size_t c = cellAt(g, i, j, k);
+    float out = 0.f;
+    if (isInterfaceCell(g, material, i, j, k, material[c])) {
+        const int im = max(i - 1, 0), ip = min(i + 1, g.gx - 1), jm = max(j - 1, 0), jp = min(j + 1, g.gy - 1), km = max(k - 1, 0),
+                  kp = min(k + 1, g.gz - 1);
+        auto at = [&](int x, int y, int z) { return double(phi[cellAt(g, x, y, z)]); };
+        const double p0 = at(i, j, k);
+        const double pxm = at(im, j, k), pxp = at(ip, j, k), pym = at(i, jm, k), pyp = at(i, jp, k), pzm = at(i, j, km), pzp = at(i, j, kp);
+        const double fx = 0.5 * (pxp - pxm), fy = 0.5 * (pyp - pym), fz = 0.5 * (pzp - pzm);
+        const double fxx = pxp - 2.0 * p0 + pxm, fyy = pyp - 2.0 * p0 + pym, fzz = pzp - 2.0 * p0 + pzm;
+        const double fxy = 0.25 * (at(ip, jp, k) - at(ip, jm, k) - at(im, jp, k) + at(im, jm, k));
+        const double fxz = 0.25 * (at(ip, j, kp) - at(ip, j, km) - at(im, j, kp) + at(im, j, km));
+        const double fyz = 0.25 * (at(i, jp, kp) - at(i, jp, km) - at(i, jm, kp) + at(i, jm, km));
+        const double gx2 = fx * fx, gy2 = fy * fy, gz2 = fz * fz, g2 = gx2 + gy2 + gz2;
+        double kappa = 0.0;
+        if (g2 >= 1e-30) {
+            const double num = fxx * (gy2 + gz2) + fyy * (gx2 + gz2) + fzz * (gx2 + gy2) - 2.0 * fx * fy * fxy - 2.0 * fx * fz * fxz -
+                               2.0 * fy * fz * fyz;
+            kappa = num / (g2 * sqrt(g2));
+        }
+        kappa = fmin(fmax(kappa, -1.0), 1.0);
+        out = float(scale * kappa);
+    }
+    sp[c] = out;
+}
+
+// rhs[L] += w_f * p_G over the liquid/air faces of every LIQUID cell L, in face order a = 0..2, d = 0..1, on top of the rhs
+// already in the expanded grid.  w_f is the expanded weight boundaryWeightsKernel wrote (cw / theta; 0 on an invalid face).
+// pGammaMax (may be NULL) is raised to the largest |p_G| met, as float bits: non-negative floats order like their bits.
+__global__ __launch_bounds__(256) void rhsSurfaceKernel(Box g, Box e, int offset, float *__restrict__ rhs, const float *wx,
+                                                        const float *wy, const float *wz, const float *__restrict__ phi,
+                                                        const int32_t *__restrict__ material, const float *__restrict__ sp,
+                                                        unsigned *__restrict__ pGammaMax)
+{
+    int bi, bj, bk;
+    float amax = 0.f;
+    // (no early return: every lane reaches the wave reduction below)
+    const bool inside = cellOfThread(g, bi, bj, bk);
+    const size_t c = inside ? cellAt(g, bi, bj, bk) : 0;
+    const int m = inside ? material[c] : kSolid;
+    if (inside && isInterfaceCell(g, material, bi, bj, bk, m) && m == kLiquid) {  // (the seven labels load together)
+        const float *w[3] = {wx, wy, wz};
+        const int ext[3] = {g.gx, g.gy, g.gz};
+        const int ei = bi + offset, ej = bj + offset, ek = bk + offset;
+        const size_t ec = cellAt(e, ei, ej, ek);
+        float acc = rhs[ec];
+        bool touched = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                int n[3] = {bi, bj, bk};
+                n[a] += d ? 1 : -1;
+                if (n[a] < 0 || n[a] >= ext[a]) continue;
+                const size_t cn = cellAt(g, n[0], n[1], n[2]);
+                if (material[cn] != kAir) continue;
+                const float wf = w[a][cellFace(e, a, d, ei, ej, ek)];
+                if (wf == 0.f) continue;  // not a valid face
+                // b / c of the face: the neighbour is behind for d = 0
+                const float theta = d ? ghostFluidTheta(phi[c], phi[cn]) : ghostFluidTheta(phi[cn], phi[c]);
+                const float pg = interfacePressure(theta, d == 1, d ? sp[c] : sp[cn], d ? sp[cn] : sp[c]);
+                acc += wf * pg;
+                amax = fmaxf(amax, fabsf(pg));
+                touched = true;
+            }
+        if (touched) rhs[ec] = acc;
+    }
+    if (!pGammaMax) return;
+    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+    if ((threadIdx.x & 63) == 0 && amax > 0.f) atomicMax(pGammaMax, __float_as_uint(amax));
+}
+
+// pressureGradientKernel with the air cell's value on a liquid/air face replaced by p_G
+__global__ __launch_bounds__(256) void pressureGradientSurfaceKernel(Box g, int axis, float *__restrict__ velocity,
+                                                                     const float *__restrict__ phi, const float *__restrict__ pressure,
+                                                                     const float *__restrict__ sp, const uint8_t *__restrict__ valid,
+                                                                     const int32_t *__restrict__ material)
+{
+    int i, j, k;
+    if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), i, j, k)) return;
+    const size_t f = faceAt(g, axis, i, j, k);
+    if (!valid[f]) return;  // valid faces have both cells inside the grid
+    int b[3] = {i, j, k};
+    b[axis] -= 1;
+    const size_t cb = cellAt(g, b[0], b[1], b[2]), cf = cellAt(g, i, j, k);
+    const bool lb = material[cb] == kLiquid, lf = material[cf] == kLiquid;
+    float pb = pressure[cb], pf = pressure[cf], grad;
+    if (lb && lf) grad = pf - pb;
+    else {  // a valid face that is not liquid/liquid is liquid/air
+        const float theta = ghostFluidTheta(phi[cb], phi[cf]);
+        const float pg = interfacePressure(theta, lb, sp[cb], sp[cf]);
+        if (lb) pf = pg;
+        else pb = pg;
+        grad = (pf - pb) / theta;
+    }
+    velocity[f] -= grad;
+}
+
 constexpr int kDivBlocks = 1024;
 __global__ __launch_bounds__(256) void divergenceKernel(Box g, double *__restrict__ partials, const int32_t *__restrict__ material,
                                                         const float *vx, const float *vy, const float *vz, const float *svx,
@@ -270,6 +408,7 @@ int done(const char *what)
 }
 inline unsigned blocks(size_t n) { return unsigned((n + 255) / 256); }
 inline bool okBox(int x, int y, int z) { return x > 0 && y > 0 && z > 0; }
+inline bool okCellGrid(int y, int z) { return y <= 65535 && z <= 65535; }  // cellGrid: y and z extents are launch-grid dimensions
 inline bool okExpanded(int gx, int gy, int gz, int ex, int ey, int ez, int off)
 {
     return okBox(ex, ey, ez) && off >= 0 && gx + off <= ex && gy + off <= ey && gz + off <= ez;
@@ -391,6 +530,43 @@ try {
 }
 MGPS_API_CATCH(nullptr)
 
+int mgps_fields_surface_pressure(float *sp, const float *liquid_phi, const int32_t *material, double scale, int gx, int gy, int gz,
+                                 void *stream)
+try {
+    if (!sp || !liquid_phi || !material || !okBox(gx, gy, gz) || !okCellGrid(gy, gz)) return bad("mgps_fields_surface_pressure");
+    const Box g{gx, gy, gz};
+    surfacePressureKernel<<<cellGrid(gx, gy, gz), 256, 0, static_cast<hipStream_t>(stream)>>>(g, sp, liquid_phi, material, scale);
+    return done("mgps_fields_surface_pressure");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_rhs_surface(float *expanded_rhs, const float *wx, const float *wy, const float *wz, const float *liquid_phi,
+                            const int32_t *material, const float *sp, float *p_gamma_max, int gx, int gy, int gz, int ex, int ey,
+                            int ez, int offset, void *stream)
+try {
+    if (!expanded_rhs || !wx || !wy || !wz || !liquid_phi || !material || !sp || !okBox(gx, gy, gz) || !okCellGrid(gy, gz) ||
+        !okExpanded(gx, gy, gz, ex, ey, ez, offset))
+        return bad("mgps_fields_rhs_surface");
+    const Box g{gx, gy, gz}, e{ex, ey, ez};
+    rhsSurfaceKernel<<<cellGrid(gx, gy, gz), 256, 0, static_cast<hipStream_t>(stream)>>>(g, e, offset, expanded_rhs, wx, wy, wz, liquid_phi,
+                                                                                       material, sp, reinterpret_cast<unsigned *>(p_gamma_max));
+    return done("mgps_fields_rhs_surface");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_pressure_gradient_surface(int axis, float *velocity, const float *liquid_phi, const float *pressure, const float *sp,
+                                          const uint8_t *valid, const int32_t *material, int gx, int gy, int gz, void *stream)
+try {
+    if (axis < 0 || axis > 2 || !velocity || !liquid_phi || !pressure || !sp || !valid || !material || !okBox(gx, gy, gz))
+        return bad("mgps_fields_pressure_gradient_surface");
+    const Box g{gx, gy, gz};
+    const size_t n = size_t(gx + (axis == 0)) * (gy + (axis == 1)) * (gz + (axis == 2));
+    pressureGradientSurfaceKernel<<<blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(g, axis, velocity, liquid_phi, pressure, sp,
+                                                                                         valid, material);
+    return done("mgps_fields_pressure_gradient_surface");
+}
+MGPS_API_CATCH(nullptr)
+
 int mgps_fields_divergence(double out_host[3], const int32_t *material, const float *vx, const float *vy, const float *vz,
                            const float *svx, const float *svy, const float *svz, const float *cwx, const float *cwy,
                            const float *cwz, int gx, int gy, int gz, void *stream)
@@ -489,6 +665,25 @@ try {
         setLastGlobalError("mgps_project_free_surface: missing field or bad extents (solid velocities: all three or none)");
         return MGPS_ERR_INVALID_ARGUMENT;
     }
+    // surface tension: dt, dx and density are read only with surface_tension > 0
+    const double sigma = p->surface_tension;
+    if (!std::isfinite(sigma) || sigma < 0) {
+        setLastGlobalError("mgps_project_free_surface: surface_tension must be finite and >= 0");
+        return MGPS_ERR_INVALID_ARGUMENT;
+    }
+    if (sigma > 0) {
+        const char *what = !(std::isfinite(p->dt) && p->dt > 0) ? "dt" : !(std::isfinite(p->dx) && p->dx > 0) ? "dx"
+                         : !(std::isfinite(p->density) && p->density > 0) ? "density" : nullptr;
+        if (what) {
+            setLastGlobalError(std::string("mgps_project_free_surface: surface_tension > 0 needs a finite ") + what + " > 0");
+            return MGPS_ERR_INVALID_ARGUMENT;
+        }
+        if (p->surface_pressure) {
+            setLastGlobalError("mgps_project_free_surface: surface_tension and surface_pressure are both set (pass one of them)");
+            return MGPS_ERR_INVALID_ARGUMENT;
+        }
+    }
+    const bool surface = sigma > 0 || p->surface_pressure;
     mgps_options o;
     mgps_default_options(&o);
     if (opt) {
@@ -567,6 +762,8 @@ try {
         vel[a] = uploadLater(p->velocity[a], faceCount(gx, gy, gz, a));
         if (haveSolidVel) svel[a] = uploadLater(p->solid_velocity[a], faceCount(gx, gy, gz, a));
     }
+    // the surface pressure: one more cell grid, only with the feature on (the caller's, or computed below from the labels)
+    float *sp = !surface ? nullptr : p->surface_pressure ? uploadLater(p->surface_pressure, cells) : pool.get<float>(cells);
     if (he != hipSuccess) return failHip("upload", he);
 #define PROJ_TRY(call)               \
     do {                             \
@@ -618,6 +815,7 @@ try {
     p->residual_inf = p->residual_l2 = p->divergence_sum = p->divergence_max = 0;
     p->enclosed_components = 0;
     p->rhs_mean_removed_max = 0;
+    p->surface_pressure_max = 0;
     if (div[2] == 0) {
         if (copy.s && (he = hipStreamSynchronize(copy.s)) != hipSuccess) return failHip("upload", he);
         if ((he = hipMemsetAsync(pressure, 0, cells * sizeof(float), s)) != hipSuccess) return failHip("pressure clear", he);
@@ -642,6 +840,13 @@ try {
     // Plug.cpp:386, 413
     float *rhs = pool.get<float>(ecells), *x = nullptr;
     PROJ_TRY(mgps_fields_rhs(rhs, material, vel[0], vel[1], vel[2], svel[0], svel[1], svel[2], cw[0], cw[1], cw[2], gx, gy, gz, ex, ey, ez, offset, s));
+    float *pGammaMax = nullptr;
+    if (surface) {  // b_L += w_f p_G: before the enclosed-liquid projection and the solve, which then see the system actually solved
+        if (sigma > 0) PROJ_TRY(mgps_fields_surface_pressure(sp, phi, material, sigma * p->dt / (p->density * p->dx * p->dx), gx, gy, gz, s));
+        pGammaMax = pool.get<float>(1);
+        if ((he = hipMemsetAsync(pGammaMax, 0, sizeof(float), s)) != hipSuccess) return failHip("surface pressure", he);
+        PROJ_TRY(mgps_fields_rhs_surface(rhs, w[0], w[1], w[2], phi, material, sp, pGammaMax, gx, gy, gz, ex, ey, ez, offset, s));
+    }
     rc = mgps_grid_alloc(mg, 0, &x);  // zero-filled
     if (rc == MGPS_OK && p->use_old_pressure) rc = mgps_fields_pressure_to_solution(x, pressure, material, gx, gy, gz, ex, ey, ez, offset, s);
     if (rc == MGPS_OK && o.enclosed_liquid) {  // the rhs as the solve sees it (P b): the residual below is then that of the solved system
@@ -676,7 +881,9 @@ try {
     // is air or solid now must not keep its old pressure (the gradient pass reads it across ghost-fluid faces)
     if ((he = hipMemsetAsync(pressure, 0, cells * sizeof(float), s)) != hipSuccess) return failHip("pressure clear", he);
     PROJ_TRY(mgps_fields_solution_to_pressure(pressure, x, material, gx, gy, gz, ex, ey, ez, offset, s));
-    for (int a = 0; a < 3; ++a) PROJ_TRY(mgps_fields_pressure_gradient(a, vel[a], phi, pressure, valid[a], material, gx, gy, gz, s));
+    for (int a = 0; a < 3; ++a)
+        PROJ_TRY(surface ? mgps_fields_pressure_gradient_surface(a, vel[a], phi, pressure, sp, valid[a], material, gx, gy, gz, s)
+                         : mgps_fields_pressure_gradient(a, vel[a], phi, pressure, valid[a], material, gx, gy, gz, s));
     PROJ_TRY(mgps_fields_divergence(div, material, vel[0], vel[1], vel[2], svel[0], svel[1], svel[2], cw[0], cw[1], cw[2], gx, gy, gz, s));
     p->divergence_sum = div[0];
     p->divergence_max = div[1];
@@ -685,6 +892,11 @@ try {
     for (int a = 0; a < 3; ++a) {
         download(p->velocity[a], vel[a], faceCount(gx, gy, gz, a));
         if (p->valid_faces[a] && he == hipSuccess) he = hipMemcpy(p->valid_faces[a], valid[a], faceCount(gx, gy, gz, a), hipMemcpyDeviceToHost);
+    }
+    if (surface && he == hipSuccess) {
+        float m = 0;
+        he = hipMemcpy(&m, pGammaMax, sizeof(m), hipMemcpyDeviceToHost);
+        p->surface_pressure_max = m;
     }
     if (he != hipSuccess) return failHip("download", he);
     const auto t3 = clock::now();

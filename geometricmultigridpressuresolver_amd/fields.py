@@ -107,13 +107,40 @@ def applySolutionToPressure(pressure, solution, material, offset):
     return pressure
 
 
-def applyPressureGradient(velocity, liquid_surface, pressure, valid_faces, material):
-    """Plug.cpp:1049-1131 (in place on the three velocity face grids)."""
+def applyPressureGradient(velocity, liquid_surface, pressure, valid_faces, material, surface_pressure=None):
+    """Plug.cpp:1049-1131 (in place on the three velocity face grids).  With `surface_pressure` (a cell grid, see
+    buildSurfacePressure) the air cell's pressure on a liquid/air face is the interface pressure p_G instead of 0."""
     shape = tuple(material.shape)
     for a in range(3):
-        check(lib().mgps_fields_pressure_gradient(a, _p(_chk(velocity[a], _face_shape(shape, a), torch.float32)), _p(liquid_surface),
-                                                  _p(pressure), _p(valid_faces[a]), _p(material), *_g(shape), _stream()))
+        v = _p(_chk(velocity[a], _face_shape(shape, a), torch.float32))
+        if surface_pressure is None:
+            check(lib().mgps_fields_pressure_gradient(a, v, _p(liquid_surface), _p(pressure), _p(valid_faces[a]), _p(material), *_g(shape), _stream()))
+        else:
+            check(lib().mgps_fields_pressure_gradient_surface(a, v, _p(liquid_surface), _p(pressure), _p(_chk(surface_pressure, shape, torch.float32)),
+                                                              _p(valid_faces[a]), _p(material), *_g(shape), _stream()))
     return velocity
+
+
+def buildSurfacePressure(liquid_surface, material, scale):
+    """Surface pressure scale * clamp(curvature, -1, 1) at the LIQUID / AIR cells of the free surface, 0 elsewhere (DESIGN.md
+    section 13).  scale = sigma * dt / (density * dx^2) gives the pressure of a surface tension sigma."""
+    shape = tuple(material.shape)
+    sp = torch.empty(shape, dtype=torch.float32, device=material.device)
+    check(lib().mgps_fields_surface_pressure(_p(sp), _p(_chk(liquid_surface, shape, torch.float32)), _p(_chk(material, shape, torch.int32)),
+                                             C.c_double(scale), *_g(shape), _stream()))
+    return sp
+
+
+def addSurfacePressureToRHS(rhs, weights, liquid_surface, material, surface_pressure, offset, p_gamma_max=None):
+    """rhs[L] += w_f * p_G on the liquid/air faces (in place on the expanded rhs of buildRHS; `weights` from buildMGDomain).
+    `p_gamma_max` (a one-element float32 tensor, or None) is raised to the largest |p_G|."""
+    shape, eshape = tuple(material.shape), tuple(rhs.shape)
+    w = [_chk(weights[a], _face_shape(eshape, a), torch.float32) for a in range(3)]
+    check(lib().mgps_fields_rhs_surface(_p(_chk(rhs, eshape, torch.float32)), _p(w[0]), _p(w[1]), _p(w[2]),
+                                        _p(_chk(liquid_surface, shape, torch.float32)), _p(_chk(material, shape, torch.int32)),
+                                        _p(_chk(surface_pressure, shape, torch.float32)), _p(p_gamma_max), *_g(shape), *_g(eshape),
+                                        int(offset), _stream()))
+    return rhs
 
 
 def computeResultingDivergence(material, velocity, cut_cell_weights, solid_velocity=None):
@@ -141,28 +168,32 @@ class Projection(C.Structure):
         ("divergence_sum", C.c_double), ("divergence_max", C.c_double),
         ("setup_ms", C.c_double), ("solve_ms", C.c_double), ("total_ms", C.c_double),
         ("enclosed_components", C.c_int), ("rhs_mean_removed_max", C.c_double),
+        ("surface_tension", C.c_double), ("dt", C.c_double), ("dx", C.c_double), ("density", C.c_double),
+        ("surface_pressure", C.c_void_p), ("surface_pressure_max", C.c_double),
     ]
 
 
 def project_free_surface(liquid_phi, solid_phi, cut_weights, velocity, pressure, solid_velocity=None, use_old_pressure=True,
                          use_mg_preconditioner=True, use_gauss_seidel=True, tolerance=1e-5, max_iterations=2500, power_of_two=True,
-                         options=None):
+                         options=None, surface_tension=0.0, dt=0.0, dx=0.0, density=0.0, surface_pressure=None):
     """solveGasSubclass (Plug.cpp:252-707) on numpy host arrays of one dtype (float32 or float64): `velocity` and `pressure`
-    are updated in place; returns (valid_faces[3] uint8, info dict)."""
+    are updated in place; returns (valid_faces[3] uint8, info dict).  Surface tension: sigma =
+    `surface_tension` > 0 with the time step `dt`, the cell size `dx` and the liquid `density`, or a caller's cell grid
+    `surface_pressure` in the units of `pressure`."""
     import numpy as np
 
-    dt = np.dtype(pressure.dtype)
-    assert dt in (np.dtype(np.float32), np.dtype(np.float64))
+    real = np.dtype(pressure.dtype)
+    assert real in (np.dtype(np.float32), np.dtype(np.float64))
     shape = tuple(liquid_phi.shape)
 
     def chk(a, sh):
-        assert a.dtype == dt and a.flags.c_contiguous and tuple(a.shape) == tuple(sh), (a.dtype, a.shape, sh)
+        assert a.dtype == real and a.flags.c_contiguous and tuple(a.shape) == tuple(sh), (a.dtype, a.shape, sh)
         return a.ctypes.data_as(C.c_void_p)
 
     pr = Projection()
     pr.struct_size = C.sizeof(Projection)
     pr.gz, pr.gy, pr.gx = shape
-    pr.real_bytes = dt.itemsize
+    pr.real_bytes = real.itemsize
     pr.liquid_phi, pr.solid_phi, pr.pressure = chk(liquid_phi, shape), chk(solid_phi, shape), chk(pressure, shape)
     valid = []
     for a in range(3):
@@ -174,6 +205,8 @@ def project_free_surface(liquid_phi, solid_phi, cut_weights, velocity, pressure,
         pr.valid_faces[a] = valid[a].ctypes.data_as(C.c_void_p)
     pr.use_old_pressure, pr.use_mg_preconditioner, pr.use_gauss_seidel = int(use_old_pressure), int(use_mg_preconditioner), int(use_gauss_seidel)
     pr.tolerance, pr.max_iterations, pr.power_of_two = float(tolerance), int(max_iterations), int(power_of_two)
+    pr.surface_tension, pr.dt, pr.dx, pr.density = float(surface_tension), float(dt), float(dx), float(density)
+    pr.surface_pressure = chk(surface_pressure, shape) if surface_pressure is not None else None
     check(lib().mgps_project_free_surface(C.byref(pr), C.byref(options) if options is not None else None))
     info = {
         "iterations": pr.stats.iterations, "outcome": pr.stats.outcome, "rel_residual": pr.stats.rel_residual,
@@ -182,5 +215,6 @@ def project_free_surface(liquid_phi, solid_phi, cut_weights, velocity, pressure,
         "residual_inf": pr.residual_inf, "residual_l2": pr.residual_l2, "divergence_sum": pr.divergence_sum,
         "divergence_max": pr.divergence_max, "setup_ms": pr.setup_ms, "solve_ms": pr.solve_ms, "total_ms": pr.total_ms,
         "enclosed_components": pr.enclosed_components, "rhs_mean_removed_max": pr.rhs_mean_removed_max,
+        "surface_pressure_max": pr.surface_pressure_max,
     }
     return valid, info

@@ -31,8 +31,9 @@ void initializeSIM(void *)
 HDK_GeometricFreeSurfacePressureSolver::HDK_GeometricFreeSurfacePressureSolver(const SIM_DataFactory *factory) : BaseClass(factory) {}
 HDK_GeometricFreeSurfacePressureSolver::~HDK_GeometricFreeSurfacePressureSolver() {}
 
-// The node interface: twelve parameters with the reference's tokens, labels, types, defaults and order (Plug.cpp:39-99), and one
-// toggle of this library's own after them ("handleEnclosedLiquid", off: options.enclosed_liquid).
+// The node interface: twelve parameters with the reference's tokens, labels, types, defaults and order (Plug.cpp:39-99), and two
+// of this library's own after them: the toggle "handleEnclosedLiquid" (off: options.enclosed_liquid) and the float
+// "surfaceTension" (0: off; mgps_projection.surface_tension).
 const SIM_DopDescription *HDK_GeometricFreeSurfacePressureSolver::getDopDescription()
 {
     static PRM_Name surfaceName(GAS_NAME_SURFACE, "Surface Field");
@@ -58,6 +59,8 @@ const SIM_DopDescription *HDK_GeometricFreeSurfacePressureSolver::getDopDescript
     static PRM_Name useMGName("useMGPreconditioner", "Use Multigrid Preconditioner");
     static PRM_Name handleEnclosedName("handleEnclosedLiquid", "Handle Enclosed Liquid");
     static PRM_Default handleEnclosedDefault(0);
+    static PRM_Name surfaceTensionName("surfaceTension", "Surface Tension");
+    static PRM_Default surfaceTensionDefault(0);
 
     static PRM_Template templates[] = {PRM_Template(PRM_STRING, 1, &surfaceName, &surfaceDefault),
                                        PRM_Template(PRM_STRING, 1, &velocityName, &velocityDefault),
@@ -72,6 +75,7 @@ const SIM_DopDescription *HDK_GeometricFreeSurfacePressureSolver::getDopDescript
                                        PRM_Template(PRM_INT, 1, &maxIterationsName, &maxIterationsDefault),
                                        PRM_Template(PRM_TOGGLE, 1, &useMGName, PRMoneDefaults),
                                        PRM_Template(PRM_TOGGLE, 1, &handleEnclosedName, &handleEnclosedDefault),
+                                       PRM_Template(PRM_FLT, 1, &surfaceTensionName, &surfaceTensionDefault),
                                        PRM_Template()};
 
     static SIM_DopDescription description(true, "HDK_GeometricFreeSurfacePressureSolver", "HDK Geometric Free Surface Pressure Solver", "$OS",
@@ -146,7 +150,7 @@ int pollInterrupt(void *) { return UTgetInterrupt()->opInterrupt() ? 1 : 0; }  /
 
 }  // namespace
 
-bool HDK_GeometricFreeSurfacePressureSolver::solveGasSubclass(SIM_Engine &, SIM_Object *obj, SIM_Time, SIM_Time)
+bool HDK_GeometricFreeSurfacePressureSolver::solveGasSubclass(SIM_Engine &, SIM_Object *obj, SIM_Time, SIM_Time timestep)
 {
     // ---- the fields and the reference's checks on them (Plug.cpp:119-250) -------------------------------------------
     const SIM_VectorField *solidVelocity = getConstVectorField(obj, GAS_NAME_COLLISIONVELOCITY);
@@ -211,6 +215,8 @@ bool HDK_GeometricFreeSurfacePressureSolver::solveGasSubclass(SIM_Engine &, SIM_
 
     std::cout << "//\n//\n// Starting free surface pressure solver (mgps, MI355X)\n//\n//" << std::endl;
 
+    const fpreal dx = velocity->getVoxelSize().maxComponent();
+
     // ---- flatten (SIM fields are fpreal32 voxel arrays: float is their own precision) ----------------------------------
     Staging<float> phi, solidPhi, p, cw[3], vel[3], solidVel[3];
     Staging<uint8_t> valid[3];
@@ -219,10 +225,8 @@ bool HDK_GeometricFreeSurfacePressureSolver::solveGasSubclass(SIM_Engine &, SIM_
         flattenInto(phi, *liquidSurface.field());
         flattenInto(p, *pressure->field());
         if (solidField) sampleAt(solidPhi, *solidField->getField(), liquidSurface);
-        else {  // no collision field: all fluid.  Houdini's solid SDF is positive inside (Plug.cpp:214-225)
-            const fpreal dx = velocity->getVoxelSize().maxComponent();
+        else  // no collision field: all fluid.  Houdini's solid SDF is positive inside (Plug.cpp:214-225)
             solidPhi.assign(phi.size(), float(-10. * dx));
-        }
         for (int axis : {0, 1, 2}) {
             flattenInto(cw[axis], *cutCellWeights->getField(axis)->field());
             flattenInto(vel[axis], *velocity->getField(axis)->field());
@@ -261,6 +265,11 @@ bool HDK_GeometricFreeSurfacePressureSolver::solveGasSubclass(SIM_Engine &, SIM_
     opt.interrupt = pollInterrupt;
     // sealed pockets of liquid (a tank filled to its lid, liquid under a solid): projected instead of left singular (off by default)
     opt.enclosed_liquid = getHandleEnclosedLiquid() ? 1 : 0;
+    // surface tension (off at 0): sigma kappa at the free surface, in the solver's pressure units dt / (density dx)
+    job.surface_tension = getSurfaceTension();
+    job.dt = timestep;
+    job.dx = dx;
+    job.density = constantDensity;
     int rc;
     {
         UT_PerfMonAutoSolveEvent event(this, "Solve linear system");

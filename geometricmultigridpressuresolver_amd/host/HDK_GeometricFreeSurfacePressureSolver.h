@@ -28,6 +28,8 @@ public:
     GET_DATA_FUNC_B("useOldPressure", UseOldPressure);
     // no counterpart in the reference: liquid that touches no air is solved too (mgps_options.enclosed_liquid)
     GET_DATA_FUNC_B("handleEnclosedLiquid", HandleEnclosedLiquid);
+    // no counterpart in the reference: surface tension sigma as the free surface's pressure (mgps_projection.surface_tension)
+    GET_DATA_FUNC_F("surfaceTension", SurfaceTension);
 
 protected:
     explicit HDK_GeometricFreeSurfacePressureSolver(const SIM_DataFactory *factory);

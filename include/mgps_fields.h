@@ -59,6 +59,24 @@ int mgps_fields_solution_to_pressure(float *pressure, const float *expanded_x, c
  * liquid/air faces */
 int mgps_fields_pressure_gradient(int axis, float *velocity, const float *liquid_phi, const float *pressure,
                                   const uint8_t *valid, const int32_t *material, int gx, int gy, int gz, void *stream);
+/* ---- surface tension: a non-zero interface pressure on liquid/air faces (ghost fluid) ---------------
+ * sp is a base cell grid of surface pressure in the units of `pressure`.  On a valid liquid/air face with liquid cell L, air cell
+ * A and theta = clamp(liquid fraction from L, 0.01, 1) (the theta of mgps_fields_boundary_weights), the interface pressure is
+ * p_G = (1 - theta) sp[L] + theta sp[A].  No counterpart in the reference, which holds p_G at 0. */
+/* sp = scale * clamp(kappa, -1, 1) at every LIQUID or AIR cell with a 6-neighbour of the other kind, 0 elsewhere; kappa is the
+ * mean curvature div(grad phi / |grad phi|) of liquid_phi at the cell centre (unit-spacing central differences, indices clamped
+ * into the grid; 0 where |grad phi|^2 < 1e-30).  scale = sigma dt / (density dx^2) gives the pressure of a surface tension sigma */
+int mgps_fields_surface_pressure(float *sp, const float *liquid_phi, const int32_t *material, double scale, int gx, int gy, int gz,
+                                 void *stream);
+/* expanded_rhs[L] += w_f p_G over the liquid/air faces of every LIQUID cell, on top of the rhs mgps_fields_rhs built; w_f is the
+ * expanded weight mgps_fields_boundary_weights wrote (wx/wy/wz: the expanded face grids).  p_gamma_max (device, may be NULL;
+ * initialise it) is raised to the largest |p_G| */
+int mgps_fields_rhs_surface(float *expanded_rhs, const float *wx, const float *wy, const float *wz, const float *liquid_phi,
+                            const int32_t *material, const float *sp, float *p_gamma_max, int gx, int gy, int gz, int ex, int ey,
+                            int ez, int offset, void *stream);
+/* mgps_fields_pressure_gradient with the air cell's pressure replaced by p_G on liquid/air faces */
+int mgps_fields_pressure_gradient_surface(int axis, float *velocity, const float *liquid_phi, const float *pressure, const float *sp,
+                                          const uint8_t *valid, const int32_t *material, int gx, int gy, int gz, void *stream);
 /* computeResultingDivergence (Plug.cpp:1133-1207): out_host[3] = {sum, max (starting from 0), LIQUID cell
  * count} of the weighted divergence over LIQUID cells; synchronises the stream */
 int mgps_fields_divergence(double out_host[3], const int32_t *material, const float *vx, const float *vy, const float *vz,
@@ -103,6 +121,14 @@ typedef struct mgps_projection {
        is that mean: the part no pressure can remove.  0 / 0 with the option off */
     int enclosed_components;
     double rhs_mean_removed_max;
+    /* surface tension: the liquid/air faces carry the interface pressure p_G of the surface pressure sp
+       instead of 0.  sp is either sigma * curvature, from liquid_phi (surface_tension = sigma > 0: dt, dx, density are read then,
+       and only then), or the caller's cell grid `surface_pressure` in the units of `pressure` (type: real_bytes).  Not both; with
+       neither, the call is the plain projection */
+    double surface_tension;            /* sigma, in the units of density * dx^3 / dt^2; 0 = off */
+    double dt, dx, density;            /* time step, cell size, constant liquid density */
+    const void *surface_pressure;      /* cell grid, or NULL */
+    double surface_pressure_max;       /* result: the largest |p_G| applied (pressure units); 0 when off */
 } mgps_projection;
 /* status MGPS_ERR_HIERARCHY with outcome MGPS_PCG_RHS_ZERO-like early outs are reported through stats.outcome; a domain
  * without liquid returns MGPS_OK with liquid_cells = 0 and leaves velocity and pressure untouched */
