@@ -2613,20 +2613,303 @@ void fillGridP(mgps_solver *h, DevLevel &L, bool withWeights, int nchunks, int c
     if (!L.g.planeZc) L.g.planeBlocks = nullptr;
 }
 
+// ---- the stages of a device-side level build, shared by createWholeOnDevice and createSlabOnDevice ---------------------------
+// A stage runs over a GRID -- a whole level, or a slab rank's label buffer (its owned planes and label ghost planes on either
+// side) -- and keeps the lists of the grid's OWNED part.  For a whole grid the owned part is the grid itself, at tile offset 0.
+struct LevelBuild {
+    Dims d, own;                           // the grid the kernels run over; its owned planes
+    uint8_t *lab = nullptr, *ownLab = nullptr;
+    bool slab = false;                     // a slab rank's label buffer, cut by `window`
+    SlabWindow window;
+    WeightView wv;                         // face weights of classification and rows (level 0)
+    int tkOffset = 0;                      // tile colour: global tile plane of the owned part's first one
+    int nt = 0, tileOff = 0, ntOwn = 0;    // tiles of the grid; the owned ones: first, count
+    uint32_t *mask = nullptr;
+    uint16_t *prefix = nullptr;
+    int32_t *tileCount = nullptr, *tileKind = nullptr, *tileStart = nullptr, *scan = nullptr;
+    int32_t *tileFlags = nullptr, *tileRank = nullptr, *bandTiles = nullptr, *boxTiles = nullptr;
+    uint8_t *tileBits = nullptr;
+    int32_t *sorted = nullptr, *general = nullptr, *genRank = nullptr, *bandEntry = nullptr;
+    uint8_t *diagS = nullptr;
+    int32_t *band = nullptr;               // the grid's band list and diagonals in device order (whole grid: the level's own)
+    uint8_t *diag = nullptr;
+    int32_t *ownFlag = nullptr, *ownGenFlag = nullptr, *ownRank = nullptr, *ownGenRank = nullptr;  // slab: the owned band cells (whole grid: ownGenRank = genRank)
+    uint8_t *chunkFlags = nullptr, *planeFlags = nullptr;
+    int *runCounts = nullptr;
+    int32_t *listCounts = nullptr;         // pure even / odd, mixed even / odd tiles, plane blocks
+    int32_t *gcount[3] = {nullptr, nullptr, nullptr}, *gat[3] = {nullptr, nullptr, nullptr};
+    int nband = 0, nGen = 0, planeZc = 0, nBoxTiles = 0, runCells = 0, listLen = 0, nplaneBlocks = 0;
+    size_t nfine = 0, nplane = 0;
+    const SlabWindow *win() const { return slab ? &window : nullptr; }
+};
+
+// scratch of the grid's tiles; which tiles can hold band cells at all: a streaming pass over the labels, the band kernel then
+// runs on those only
+int bandCandidates(mgps_solver *h, DevScratch &tmp, LevelBuild &t)
+{
+    const int tx = (t.d.nx + kTile - 1) / kTile, ty = (t.d.ny + kTile - 1) / kTile, tz = (t.d.nz + kTile - 1) / kTile;
+    t.nt = tx * ty * tz;
+    t.tileOff = t.slab ? (t.window.own0 / kTile) * tx * ty : 0;
+    t.ntOwn = tx * ty * ((t.own.nz + kTile - 1) / kTile);
+    MGPS_TRY(tmp.get(h, &t.mask, size_t(t.nt) * 128));
+    MGPS_TRY(tmp.get(h, &t.prefix, size_t(t.nt) * 128));
+    MGPS_TRY(tmp.get(h, &t.tileCount, size_t(t.nt)));
+    MGPS_TRY(tmp.get(h, &t.tileKind, size_t(t.nt)));
+    MGPS_TRY(tmp.get(h, &t.tileStart, size_t(t.nt) + 1));
+    MGPS_TRY(tmp.get(h, &t.scan, scanScratchInts(t.d.cells())));
+    MGPS_TRY(tmp.get(h, &t.tileFlags, size_t(t.nt)));
+    MGPS_TRY(tmp.get(h, &t.tileRank, size_t(t.nt) + 1));
+    MGPS_TRY(tmp.get(h, &t.bandTiles, size_t(t.nt)));
+    MGPS_TRY(tmp.get(h, &t.tileBits, size_t(t.nt)));
+    MGPS_HIP(h, hipMemsetAsync(t.mask, 0, size_t(t.nt) * 128 * sizeof(uint32_t), nullptr));
+    MGPS_HIP(h, hipMemsetAsync(t.prefix, 0, size_t(t.nt) * 128 * sizeof(uint16_t), nullptr));
+    MGPS_HIP(h, hipMemsetAsync(t.tileCount, 0, size_t(t.nt) * sizeof(int32_t), nullptr));
+    MGPS_LAUNCH(h, launchBandCandidates(nullptr, t.d, t.lab, t.tileKind, t.tileBits, t.tileFlags, t.tileRank, t.bandTiles, t.scan, t.win()));
+    return MGPS_OK;
+}
+
+// band masks over the candidate tiles, tile counts scanned to tile starts (tileStart[nt] = the grid's band cells)
+int bandMasks(mgps_solver *h, LevelBuild &t, int width, int *interiorBad)
+{
+    int ncand = 0;
+    MGPS_HIP(h, hipMemcpy(&ncand, t.tileRank + t.nt, sizeof(int), hipMemcpyDeviceToHost));
+    MGPS_LAUNCH(h, launchBandMasks(nullptr, t.d, t.lab, width, t.mask, t.prefix, t.tileCount, t.tileKind, interiorBad, t.bandTiles, ncand, t.win()));
+    MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.tileCount, t.tileStart, size_t(t.nt), t.scan));
+    return MGPS_OK;
+}
+
+// the band list in reference order, classification, the scan of the general cells (genRank[nband] = their count); a slab level
+// also flags and ranks the owned band cells.  A whole grid's t.band / t.diag are set by the caller
+int bandLists(mgps_solver *h, DevScratch &tmp, LevelBuild &t, int *violations)
+{
+    const size_t nb = size_t(t.nband);
+    MGPS_TRY(tmp.get(h, &t.sorted, nb));
+    MGPS_TRY(tmp.get(h, &t.general, nb));
+    MGPS_TRY(tmp.get(h, &t.genRank, nb + 1));
+    MGPS_TRY(tmp.get(h, &t.bandEntry, nb));
+    MGPS_TRY(tmp.get(h, &t.diagS, nb));
+    if (t.slab) {
+        MGPS_TRY(tmp.get(h, &t.band, nb));
+        MGPS_TRY(tmp.get(h, &t.diag, nb));
+        MGPS_TRY(tmp.get(h, &t.ownFlag, nb));
+        MGPS_TRY(tmp.get(h, &t.ownGenFlag, nb));
+        MGPS_TRY(tmp.get(h, &t.ownRank, nb + 1));
+        MGPS_TRY(tmp.get(h, &t.ownGenRank, nb + 1));
+    }
+    if (t.nband > 0) {
+        MGPS_LAUNCH(h, launchBandFill(nullptr, t.d, t.mask, t.prefix, t.tileStart, t.sorted));
+        MGPS_LAUNCH(h, launchBandClassify(nullptr, t.d, t.lab, t.wv, t.sorted, t.nband, t.diagS, t.general, violations, t.win()));
+    }
+    MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.general, t.genRank, nb, t.scan));
+    if (!t.slab) {
+        t.ownGenRank = t.genRank;
+        return MGPS_OK;
+    }
+    const size_t plane = size_t(t.d.nx) * t.d.ny;
+    MGPS_LAUNCH(h, launchOwnedFlags(nullptr, t.sorted, t.general, t.nband, int32_t(size_t(t.window.own0) * plane), int32_t(size_t(t.window.own1) * plane), t.ownFlag, t.ownGenFlag));
+    MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.ownFlag, t.ownRank, nb, t.scan));
+    MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.ownGenFlag, t.ownGenRank, nb, t.scan));
+    return MGPS_OK;
+}
+
+// the grid's device order and operator rows (t.nGen general cells); a slab level patches the buffer's codes and cuts the rank's
+// list out of the buffer's (L.nband / L.nbndGeneral read back by the caller); per owned tile (+ 1) the first of its general
+// cells in the level's list (the mixed Gauss-Seidel tiles look their rows up there)
+int bandRows(mgps_solver *h, LevelBuild &t, DevLevel &L)
+{
+    float **rows = t.slab ? &L.extRows : &L.rows;
+    MGPS_TRY(devAlloc(h, rows, size_t(7) * size_t(t.nGen), false));
+    MGPS_LAUNCH(h, launchBandSplit(nullptr, t.d, t.lab, t.wv, t.sorted, t.nband, t.diagS, t.genRank, t.band, t.diag, t.bandEntry, *rows));
+    if (t.slab) {
+        MGPS_LAUNCH(h, launchPatchSimpleCodes(nullptr, t.lab, t.band, t.diag, t.nGen, t.nband));
+        MGPS_TRY(devAlloc(h, &L.band, size_t(L.nband), false));
+        MGPS_TRY(devAlloc(h, &L.bandDiag, size_t(L.nband), false));
+        MGPS_TRY(devAlloc(h, &L.bandTmp, size_t(L.nband), false));
+        MGPS_TRY(devAlloc(h, &L.rows, size_t(7) * size_t(L.nbndGeneral), false));
+        MGPS_LAUNCH(h, launchBandSplitOwned(nullptr, t.sorted, t.nband, int32_t(size_t(t.window.own0) * size_t(t.d.nx) * t.d.ny), t.diagS, t.ownRank, t.ownGenRank, t.genRank,
+                                            L.extRows, L.band, L.bandDiag, L.rows));
+    }
+    MGPS_TRY(devAlloc(h, &L.tileBndStart, size_t(t.ntOwn) + 1, false));
+    MGPS_LAUNCH(h, launchGather(nullptr, t.ownGenRank, t.tileStart + t.tileOff, t.ntOwn + 1, L.tileBndStart));
+    return MGPS_OK;
+}
+
+// activity of the owned planes: a flag per 32 cells and per plane block, the active runs of each length counted.  ghostLo / ghostHi
+// (slab): a block next to a cut with active cells only across it still takes part in the residual + restriction pair
+int activity(mgps_solver *h, DevScratch &tmp, LevelBuild &t, bool ghostLo, bool ghostHi)
+{
+    t.nfine = (t.own.cells() + kSegCells - 1) / kSegCells;
+    t.planeZc = planeSweepZc(t.own.nx, t.own.ny, t.own.nz);
+    MGPS_TRY(tmp.get(h, &t.chunkFlags, t.nfine));
+    if (t.planeZc) {
+        t.nplane = size_t((t.own.nx + 255) / 256) * size_t((t.own.ny + kPlaneRows - 1) / kPlaneRows) * size_t((t.own.nz + t.planeZc - 1) / t.planeZc);
+        MGPS_TRY(tmp.get(h, &t.planeFlags, t.nplane));
+        MGPS_HIP(h, hipMemsetAsync(t.planeFlags, 0, t.nplane, nullptr));
+    }
+    MGPS_LAUNCH(h, launchActivityFlags(nullptr, t.own, t.ownLab, t.chunkFlags, t.planeFlags, t.planeZc));
+    if (t.planeZc) {
+        if (ghostLo) MGPS_LAUNCH(h, launchGhostPlaneBlockFlags(nullptr, t.own, t.ownLab, -1, t.planeZc, t.planeFlags));
+        if (ghostHi) MGPS_LAUNCH(h, launchGhostPlaneBlockFlags(nullptr, t.own, t.ownLab, t.own.nz, t.planeZc, t.planeFlags));
+    }
+    MGPS_TRY(tmp.get(h, &t.runCounts, 4));
+    MGPS_HIP(h, hipMemsetAsync(t.runCounts, 0, 4 * sizeof(int), nullptr));
+    MGPS_LAUNCH(h, launchCountRuns(nullptr, t.chunkFlags, t.nfine, t.runCounts));
+    return MGPS_OK;
+}
+
+// the activity list of grid d: the run length from the device's counts, the flags folded to that length, the list compacted on
+// the device -- its length is the count of active runs, rounded up to whole workgroups
+int runList(mgps_solver *h, DevScratch &tmp, const Dims &d, uint8_t *chunkFlags, size_t nfine, const int *runCounts, int32_t *scan, int32_t **list, int *runCellsOut,
+            int *listLenOut)
+{
+    int rc4[4] = {0, 0, 0, 0};
+    MGPS_HIP(h, hipMemcpy(rc4, runCounts, sizeof(rc4), hipMemcpyDeviceToHost));
+    const int64_t rc64[4] = {rc4[0], rc4[1], rc4[2], rc4[3]};
+    const int runCells = chooseRunCells(rc64);
+    const size_t nruns = (nfine + size_t(runCells / kSegCells) - 1) / size_t(runCells / kSegCells);
+    uint8_t *runFlags = chunkFlags;
+    if (runCells != kSegCells) {
+        MGPS_TRY(tmp.get(h, &runFlags, nruns));
+        MGPS_LAUNCH(h, launchFoldRunFlags(nullptr, chunkFlags, nfine, runCells, runFlags));
+    }
+    int activeRuns = 0;
+    for (int z = 0; z < 4; ++z)
+        if (kRunSizes[z] == runCells) activeRuns = rc4[z];
+    const int perGroup = kChunkCells / runCells, listLen = (activeRuns + perGroup - 1) / perGroup * perGroup;
+    int32_t *tmpFlags = nullptr, *rank = nullptr, *base = nullptr;
+    MGPS_TRY(tmp.get(h, &tmpFlags, nruns));
+    MGPS_TRY(tmp.get(h, &rank, nruns + 1));
+    MGPS_TRY(tmp.get(h, &base, 1));
+    MGPS_TRY(devAlloc(h, list, size_t(listLen), false));
+    MGPS_LAUNCH(h, launchRunList(nullptr, d, runFlags, nruns, runCells, tmpFlags, rank, scan, base, *list, listLen));
+    *runCellsOut = runCells;
+    *listLenOut = listLen;
+    return MGPS_OK;
+}
+
+// the level's lists: activity runs, the four Gauss-Seidel tile lists and the plane-block list (compacted on the device; the five
+// counts come back together in listCounts); then the level's work grids
+int levelLists(mgps_solver *h, DevScratch &tmp, LevelBuild &t, DevLevel &L, int l)
+{
+    MGPS_TRY(runList(h, tmp, t.own, t.chunkFlags, t.nfine, t.runCounts, t.scan, &L.chunks, &t.runCells, &t.listLen));
+    MGPS_TRY(tmp.get(h, &t.listCounts, 5));
+    MGPS_HIP(h, hipMemsetAsync(t.listCounts, 0, 5 * sizeof(int32_t), nullptr));
+    int32_t **cls[4] = {&L.pure[0], &L.pure[1], &L.mixed[0], &L.mixed[1]};  // pure even, pure odd, mixed even, mixed odd
+    for (int q = 0; q < 4; ++q) {
+        MGPS_TRY(devAlloc(h, cls[q], size_t(t.ntOwn) / 2 + 1, false));
+        MGPS_LAUNCH(h, launchTileClassList(nullptr, t.own, t.tileKind + t.tileOff, q & 1, q >> 1, t.tileFlags, t.tileRank, *cls[q], t.scan, t.tkOffset));
+        MGPS_HIP(h, hipMemcpyAsync(t.listCounts + q, t.tileRank + t.ntOwn, sizeof(int32_t), hipMemcpyDeviceToDevice, nullptr));
+    }
+    if (t.nplane) {
+        int32_t *pf = nullptr, *pr = nullptr;
+        MGPS_TRY(tmp.get(h, &pf, t.nplane));
+        MGPS_TRY(tmp.get(h, &pr, t.nplane + 1));
+        MGPS_TRY(devAlloc(h, &L.planeBlocks, t.nplane, false));
+        MGPS_LAUNCH(h, launchByteList(nullptr, t.planeFlags, int(t.nplane), pf, pr, L.planeBlocks, t.scan));
+        MGPS_HIP(h, hipMemcpyAsync(t.listCounts + 4, pr + t.nplane, sizeof(int32_t), hipMemcpyDeviceToDevice, nullptr));
+    }
+    if (l > 0) {
+        MGPS_TRY(gridAlloc(h, &L.x, L.d));
+        MGPS_TRY(gridAlloc(h, &L.b, L.d));
+    }
+    MGPS_TRY(gridAlloc(h, &L.r, L.d));
+    MGPS_TRY(gridAlloc(h, &L.tmp, L.d));
+    return MGPS_OK;
+}
+
+int listCounts(mgps_solver *h, LevelBuild &t, DevLevel &L)
+{
+    int32_t counts[5] = {0, 0, 0, 0, 0};
+    MGPS_HIP(h, hipMemcpy(counts, t.listCounts, sizeof(counts), hipMemcpyDeviceToHost));
+    L.npure[0] = counts[0];
+    L.npure[1] = counts[1];
+    L.nmixed[0] = counts[2];
+    L.nmixed[1] = counts[3];
+    t.nplaneBlocks = counts[4];
+    return MGPS_OK;
+}
+
+// boxes of the fused band stage (clipped to the owned planes): the tiles that can hold a band-closure cell, the counts per tile
+// scanned to offsets
+int boxCounts(mgps_solver *h, DevScratch &tmp, LevelBuild &t, int depth, int *broken)
+{
+    MGPS_TRY(tmp.get(h, &t.boxTiles, size_t(t.nt)));
+    MGPS_LAUNCH(h, launchBoxTileList(nullptr, t.d, t.tileStart, t.tileFlags, t.tileRank, t.boxTiles, t.scan));
+    MGPS_HIP(h, hipMemcpy(&t.nBoxTiles, t.tileRank + t.nt, sizeof(int), hipMemcpyDeviceToHost));
+    for (int q = 0; q < 3; ++q) {
+        MGPS_TRY(tmp.get(h, &t.gcount[q], size_t(t.nBoxTiles)));
+        MGPS_TRY(tmp.get(h, &t.gat[q], size_t(t.nBoxTiles) + 1));
+    }
+    MGPS_LAUNCH(h, launchBandBoxesCount(nullptr, t.d, t.lab, t.mask, t.prefix, t.tileStart, t.bandEntry, t.diag, depth, t.boxTiles, t.nBoxTiles, t.gcount, broken, t.win()));
+    for (int q = 0; q < 3; ++q) MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.gcount[q], t.gat[q], size_t(t.nBoxTiles), t.scan));
+    return MGPS_OK;
+}
+
+// the boxes' totals (groups, list entries, general entries) and the builder's broken flag
+int boxTotals(mgps_solver *h, const LevelBuild &t, const int *broken, int tot[3], int *brokenOut)
+{
+    for (int q = 0; q < 3; ++q) MGPS_HIP(h, hipMemcpy(&tot[q], t.gat[q] + t.nBoxTiles, sizeof(int), hipMemcpyDeviceToHost));
+    MGPS_HIP(h, hipMemcpy(brokenOut, broken, sizeof(int), hipMemcpyDeviceToHost));
+    return MGPS_OK;
+}
+
+// the boxes' arrays (none for tot[0] == 0 groups)
+int boxFill(mgps_solver *h, LevelBuild &t, DevLevel &L, int depth, const int tot[3], int *broken)
+{
+    L.bandBoxes.depth = depth;
+    L.bandBoxes.ngroups = tot[0];
+    L.bandBoxes.listCount = size_t(tot[1]);
+    L.bandBoxes.generalInts = 2 * size_t(tot[2]);
+    L.bandBoxes.anyGeneral = tot[2] > 0;
+    if (tot[0] == 0) return MGPS_OK;
+    MGPS_TRY(devAlloc(h, &L.bandBoxes.info, size_t(kBoxInfoInts) * size_t(tot[0]), false));
+    MGPS_TRY(devAlloc(h, &L.bandBoxes.list, size_t(tot[1]), false));
+    MGPS_TRY(devAlloc(h, &L.bandBoxes.general, 2 * size_t(tot[2]), false));
+    MGPS_LAUNCH(h, launchBandBoxesFill(nullptr, t.d, t.lab, t.mask, t.prefix, t.tileStart, t.bandEntry, t.diag, depth, t.boxTiles, t.nBoxTiles, t.gat, L.bandBoxes.info,
+                                       L.bandBoxes.list, L.bandBoxes.general, broken, t.win()));
+    return finishBandBoxes(h, L, nullptr, t.slab ? &t.d : nullptr);
+}
+
+// the argument rules of mgps_hierarchy_create (MG.cpp:159-161), in the words of entry point `who`
+int checkSetupArgs(const std::string &who, int minLevels, int nx, int ny, int nz, int mgLevels, const mgps_options &o, const char *bandRule)
+{
+    if (mgLevels < minLevels || nx < 2 || ny < 2 || nz < 2 || (nx & 1) || (ny & 1) || (nz & 1))
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, who + ": extents must be even and >= 2, mg_levels >= " + std::to_string(minLevels));
+    if (size_t(nx) * ny * nz > size_t(0x7fffffff)) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, who + ": more than 2^31-1 cells per grid");
+    for (int l = 1; l < mgLevels; ++l)
+        if (((nx >> (l - 1)) & 1) || ((ny >> (l - 1)) & 1) || ((nz >> (l - 1)) & 1) || (nx >> l) < 1 || (ny >> l) < 1 || (nz >> l) < 1)
+            return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, who + ": extents are not divisible by 2^(levels-1)");
+    if (o.band_width < 1 || o.band_width > 8 || o.band_iterations < 0) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, who + ": " + bandRule);
+    return MGPS_OK;
+}
+
+// the level cap (MG.cpp:238-253) from per-level flags of levels 0 .. nl - 1: flags[2 l] = the level's EXTERIOR shell is broken,
+// flags[2 l + 1] = it holds an active cell.  shell0: level 0's shell counts; `hint` ends the message of a coarse level's shell
+int levelCap(mgps_solver *h, const int *flags, int mgLevels, int nl, bool shell0, const char *hint, int *levels)
+{
+    if (flags[0] && shell0) return failH(h, MGPS_ERR_HIERARCHY, "labels need an EXTERIOR shell on all six sides (unitTestExteriorCells)");
+    if (!flags[1]) return failH(h, MGPS_ERR_HIERARCHY, "no INTERIOR or BOUNDARY cell in the domain");
+    *levels = mgLevels;
+    for (int l = 1; l < nl; ++l) {
+        if (flags[2 * l])
+            return failH(h, MGPS_ERR_HIERARCHY,
+                         "level " + std::to_string(l) + " has no EXTERIOR shell (unitTestExteriorCells, MG.cpp:252): " + std::to_string(mgLevels) +
+                             " levels need 2^(levels-1) = " + std::to_string(1 << (mgLevels - 1)) + " EXTERIOR cells on every side of the solver grid" + hint);
+        if (!flags[2 * l + 1]) {
+            *levels = l - 1;  // the reference drops the last solvable level too (MG.cpp:245)
+            break;
+        }
+    }
+    if (*levels < 1) return failH(h, MGPS_ERR_HIERARCHY, "level cap left no multigrid level (first coarse level has no solvable cell)");
+    return MGPS_OK;
+}
+
 // tail: the collapsed tail of a slab run on rank 0 -- unit weights (wx == nullptr), the coarsest solver even for a single level, no
 // shell test of its finest level (the level cap of the whole hierarchy has been applied by the ranks together)
 int createWholeOnDevice(mgps_solver **out, int nx, int ny, int nz, const uint8_t *labels, const float *wx, const float *wy, const float *wz,
                         hipMemcpyKind kind, int mgLevels, bool useGS, const mgps_options &o, int device, bool tail = false)
 {
-    // the argument rules of mgps_hierarchy_create (MG.cpp:159-161)
-    if (mgLevels < 1 || nx < 2 || ny < 2 || nz < 2 || (nx & 1) || (ny & 1) || (nz & 1))
-        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_hierarchy_create: extents must be even and >= 2, mg_levels >= 1");
-    if (size_t(nx) * ny * nz > size_t(0x7fffffff)) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_hierarchy_create: more than 2^31-1 cells per grid");
-    for (int l = 1; l < mgLevels; ++l)
-        if (((nx >> (l - 1)) & 1) || ((ny >> (l - 1)) & 1) || ((nz >> (l - 1)) & 1) || (nx >> l) < 1 || (ny >> l) < 1 || (nz >> l) < 1)
-            return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_hierarchy_create: extents are not divisible by 2^(levels-1)");
-    if (o.band_width < 1 || o.band_width > 8 || o.band_iterations < 0)
-        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_hierarchy_create: band_width >= 1 (device-side set-up: <= 8), band_iterations >= 0");
+    MGPS_TRY(checkSetupArgs("mgps_hierarchy_create", 1, nx, ny, nz, mgLevels, o, "band_width >= 1 (device-side set-up: <= 8), band_iterations >= 0"));
     auto *h = new mgps_solver();
     h->opt = o;
     h->useGS = useGS;
@@ -2658,66 +2941,40 @@ int createWholeOnDevice(mgps_solver **out, int nx, int ny, int nz, const uint8_t
     }
     StageClock clock(h->opt.print_stats != 0);
     DevScratch tmp;
-#define ODS_TRY(call)                        \
-    do {                                     \
-        int s_ = (call);                     \
-        if (s_ != MGPS_OK) return bail(s_);  \
-    } while (0)
-#define ODS_HIP(call)                                                                                                  \
-    do {                                                                                                               \
-        hipError_t e_ = (call);                                                                                        \
-        if (e_ != hipSuccess) return bail(failH(h, MGPS_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)));  \
-    } while (0)
-#define ODS_LAUNCH(call)                                                                                                       \
-    do {                                                                                                                       \
-        int e_ = (call);                                                                                                       \
-        if (e_ != 0) return bail(failH(h, MGPS_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(hipError_t(e_))));       \
-    } while (0)
-
-    // ---- labels of every level: ghost plane | the level | ghost plane
     h->lv.resize(size_t(mgLevels));
-    for (int l = 0; l < mgLevels; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        L.d = Dims{nx >> l, ny >> l, nz >> l};
-        L.z0 = 0;
-        L.z1 = L.d.nz;
-        const size_t plane = size_t(L.d.nx) * L.d.ny;
-        ODS_TRY(devAlloc(h, &L.codes, L.d.cells() + 2 * plane, false));
-        ODS_HIP(hipMemsetAsync(L.codes, MGPS_EXTERIOR_CELL, plane, nullptr));
-        ODS_HIP(hipMemsetAsync(L.codes + plane + L.d.cells(), MGPS_EXTERIOR_CELL, plane, nullptr));
-    }
     auto labOf = [&](int l) { return h->lv[size_t(l)].codes + size_t(h->lv[size_t(l)].d.nx) * h->lv[size_t(l)].d.ny; };
-    if (labels != labOf(0)) ODS_HIP(hipMemcpy(labOf(0), labels, d0.cells(), kind));
     // flags per level: [0] shell broken, [1] holds an active cell; then [2 L] interior rule broken, [2 L + 1] weight rule broken,
     // [2 L + 2 ...] band groups broken per level
     int *flags = nullptr;
     const size_t nflags = size_t(3 * mgLevels + 2);
-    ODS_TRY(tmp.get(h, &flags, nflags));
-    ODS_HIP(hipMemsetAsync(flags, 0, nflags * sizeof(int), nullptr));
-    ODS_LAUNCH(launchShellCheck(nullptr, d0, labOf(0), flags));
-    ODS_LAUNCH(launchAnyActive(nullptr, d0, labOf(0), flags + 1));
-    for (int l = 1; l < mgLevels; ++l) {
-        ODS_LAUNCH(launchCoarsenLabels(nullptr, h->lv[size_t(l - 1)].d, labOf(l - 1), labOf(l), flags + 2 * l + 1));
-        ODS_LAUNCH(launchShellCheck(nullptr, h->lv[size_t(l)].d, labOf(l), flags + 2 * l));
-        ODS_LAUNCH(launchMarkBoundary(nullptr, h->lv[size_t(l)].d, labOf(l)));
-    }
-    std::vector<int> hflags(nflags);
-    ODS_HIP(hipMemcpy(hflags.data(), flags, nflags * sizeof(int), hipMemcpyDeviceToHost));
-    if (hflags[0] && !tail) return bail(failH(h, MGPS_ERR_HIERARCHY, "labels need an EXTERIOR shell on all six sides (unitTestExteriorCells)"));
-    if (!hflags[1]) return bail(failH(h, MGPS_ERR_HIERARCHY, "no INTERIOR or BOUNDARY cell in the domain"));
     int levels = mgLevels;
-    for (int l = 1; l < mgLevels; ++l) {  // MG.cpp:238-253
-        if (hflags[size_t(2 * l)])
-            return bail(failH(h, MGPS_ERR_HIERARCHY,
-                              "level " + std::to_string(l) + " has no EXTERIOR shell (unitTestExteriorCells, MG.cpp:252): " + std::to_string(mgLevels) +
-                                  " levels need 2^(levels-1) = " + std::to_string(1 << (mgLevels - 1)) +
-                                  " EXTERIOR cells on every side of the solver grid (mgps_expanded_layout pads that much)"));
-        if (!hflags[size_t(2 * l + 1)]) {
-            levels = l - 1;  // the reference drops the last solvable level too (MG.cpp:245)
-            break;
+    int rc = [&]() -> int {
+        // ---- labels of every level: ghost plane | the level | ghost plane
+        for (int l = 0; l < mgLevels; ++l) {
+            DevLevel &L = h->lv[size_t(l)];
+            L.d = Dims{nx >> l, ny >> l, nz >> l};
+            L.z0 = 0;
+            L.z1 = L.d.nz;
+            const size_t plane = size_t(L.d.nx) * L.d.ny;
+            MGPS_TRY(devAlloc(h, &L.codes, L.d.cells() + 2 * plane, false));
+            MGPS_HIP(h, hipMemsetAsync(L.codes, MGPS_EXTERIOR_CELL, plane, nullptr));
+            MGPS_HIP(h, hipMemsetAsync(L.codes + plane + L.d.cells(), MGPS_EXTERIOR_CELL, plane, nullptr));
         }
-    }
-    if (levels < 1) return bail(failH(h, MGPS_ERR_HIERARCHY, "level cap left no multigrid level (first coarse level has no solvable cell)"));
+        if (labels != labOf(0)) MGPS_HIP(h, hipMemcpy(labOf(0), labels, d0.cells(), kind));
+        MGPS_TRY(tmp.get(h, &flags, nflags));
+        MGPS_HIP(h, hipMemsetAsync(flags, 0, nflags * sizeof(int), nullptr));
+        MGPS_LAUNCH(h, launchShellCheck(nullptr, d0, labOf(0), flags));
+        MGPS_LAUNCH(h, launchAnyActive(nullptr, d0, labOf(0), flags + 1));
+        for (int l = 1; l < mgLevels; ++l) {
+            MGPS_LAUNCH(h, launchCoarsenLabels(nullptr, h->lv[size_t(l - 1)].d, labOf(l - 1), labOf(l), flags + 2 * l + 1));
+            MGPS_LAUNCH(h, launchShellCheck(nullptr, h->lv[size_t(l)].d, labOf(l), flags + 2 * l));
+            MGPS_LAUNCH(h, launchMarkBoundary(nullptr, h->lv[size_t(l)].d, labOf(l)));
+        }
+        std::vector<int> hflags(nflags);
+        MGPS_HIP(h, hipMemcpy(hflags.data(), flags, nflags * sizeof(int), hipMemcpyDeviceToHost));
+        return levelCap(h, hflags.data(), mgLevels, mgLevels, !tail, " (mgps_expanded_layout pads that much)", &levels);
+    }();
+    if (rc != MGPS_OK) return bail(rc);
     for (int l = levels; l < mgLevels; ++l) {
         (void)cacheFree(h->lv[size_t(l)].codes);
         h->lv[size_t(l)].codes = nullptr;
@@ -2726,278 +2983,128 @@ int createWholeOnDevice(mgps_solver **out, int nx, int ny, int nz, const uint8_t
     h->totalLevels = levels;
     clock.lap("labels of all levels (device)");
 
-    // ---- the coarsest level's direct solver on host threads, beside everything below
     const bool needCoarse = levels > 1 || tail;
     int rcInverse = MGPS_OK;
-    {
-        const Dims cd = h->lv[size_t(levels - 1)].d;
-        std::vector<uint8_t> coarsest(cd.cells());
-        ODS_HIP(hipMemcpy(coarsest.data(), labOf(levels - 1), cd.cells(), hipMemcpyDeviceToHost));
-        inverseJob = std::thread([h, nx, ny, nz, levels, needCoarse, &rcInverse, lab = std::move(coarsest)] {
-            rcInverse = hierarchyLight(&h->hier, nx, ny, nz, levels, lab.data(), h->opt, needCoarse);
-            if (rcInverse == MGPS_OK && needCoarse) h->hier->buildDenseInverse();
-        });
-    }
-    // ---- face weights
-    {
-        const size_t wn[3] = {size_t(d0.nx + 1) * d0.ny * d0.nz, size_t(d0.nx) * (d0.ny + 1) * d0.nz, size_t(d0.nx) * d0.ny * (d0.nz + 1)};
-        const float *src[3] = {wx, wy, wz};
-        h->weightsBorrowed = kind == hipMemcpyDeviceToDevice && o.borrow_device_weights != 0;
-        for (int a = 0; a < 3 && wx; ++a) {
-            if (h->weightsBorrowed) {
-                h->w[a] = const_cast<float *>(src[a]);
-                continue;
-            }
-            ODS_TRY(devAlloc(h, &h->w[a], wn[a], false));
-            ODS_HIP(hipMemcpyAsync(h->w[a], src[a], wn[a] * sizeof(float), kind, nullptr));
-        }
-    }
-
-    // ---- band masks and tile counts of every level, then one round of counts to the host
-    struct LevelTmp {
-        int nt = 0, tx = 0, ty = 0, tz = 0;
-        uint32_t *mask = nullptr;
-        uint16_t *prefix = nullptr;
-        int32_t *tileCount = nullptr, *tileKind = nullptr, *tileStart = nullptr, *scan = nullptr;
-        int32_t *sorted = nullptr, *general = nullptr, *genRank = nullptr, *bandEntry = nullptr;
-        uint8_t *diagS = nullptr, *chunkFlags = nullptr, *planeFlags = nullptr;
-        int32_t *gcount[4] = {nullptr, nullptr, nullptr, nullptr}, *gat[4] = {nullptr, nullptr, nullptr, nullptr};
-        int32_t *tileFlags = nullptr, *tileRank = nullptr, *bandTiles = nullptr, *boxTiles = nullptr;
-        uint8_t *tileBits = nullptr;
-        int *runCounts = nullptr;
-        int32_t *listCounts = nullptr;  // pure even / odd, mixed even / odd tiles, plane blocks
-        int runCells = 0, listLen = 0;
-        int nband = 0, nGen = 0, planeZc = 0, nBandTiles = 0, nBoxTiles = 0;
-        size_t nfine = 0, nplane = 0;
-    };
-    std::vector<LevelTmp> T{size_t(levels)};
-    for (int l = 0; l < levels; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        t.tx = (L.d.nx + kTile - 1) / kTile;
-        t.ty = (L.d.ny + kTile - 1) / kTile;
-        t.tz = (L.d.nz + kTile - 1) / kTile;
-        t.nt = t.tx * t.ty * t.tz;
-        ODS_TRY(tmp.get(h, &t.mask, size_t(t.nt) * 128));
-        ODS_TRY(tmp.get(h, &t.prefix, size_t(t.nt) * 128));
-        ODS_TRY(tmp.get(h, &t.tileCount, size_t(t.nt)));
-        ODS_TRY(tmp.get(h, &t.tileKind, size_t(t.nt)));
-        ODS_TRY(tmp.get(h, &t.tileStart, size_t(t.nt) + 1));
-        ODS_TRY(tmp.get(h, &t.scan, scanScratchInts(L.d.cells())));
-        ODS_TRY(tmp.get(h, &t.tileFlags, size_t(t.nt)));
-        ODS_TRY(tmp.get(h, &t.tileRank, size_t(t.nt) + 1));
-        ODS_TRY(tmp.get(h, &t.bandTiles, size_t(t.nt)));
-        ODS_TRY(tmp.get(h, &t.tileBits, size_t(t.nt)));
-        // which tiles can hold band cells at all: a streaming pass over the labels; the band kernel then runs on those only
-        ODS_HIP(hipMemsetAsync(t.mask, 0, size_t(t.nt) * 128 * sizeof(uint32_t), nullptr));
-        ODS_HIP(hipMemsetAsync(t.prefix, 0, size_t(t.nt) * 128 * sizeof(uint16_t), nullptr));
-        ODS_HIP(hipMemsetAsync(t.tileCount, 0, size_t(t.nt) * sizeof(int32_t), nullptr));
-        ODS_LAUNCH(launchBandCandidates(nullptr, L.d, labOf(l), t.tileKind, t.tileBits, t.tileFlags, t.tileRank, t.bandTiles, t.scan));
-    }
-    for (int l = 0; l < levels; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        int ncand = 0;
-        ODS_HIP(hipMemcpy(&ncand, t.tileRank + t.nt, sizeof(int), hipMemcpyDeviceToHost));
-        ODS_LAUNCH(launchBandMasks(nullptr, L.d, labOf(l), o.band_width, t.mask, t.prefix, t.tileCount, t.tileKind, l == 0 ? flags + 2 * mgLevels : nullptr,
-                                   t.bandTiles, ncand));
-        ODS_LAUNCH(launchExclusiveScan(nullptr, t.tileCount, t.tileStart, size_t(t.nt), t.scan));
-        ODS_LAUNCH(launchBandTileList(nullptr, t.tileStart, t.nt, t.tileFlags, t.tileRank, t.bandTiles, t.scan));
-    }
-    for (int l = 0; l < levels; ++l) {
-        ODS_HIP(hipMemcpy(&T[size_t(l)].nband, T[size_t(l)].tileStart + T[size_t(l)].nt, sizeof(int), hipMemcpyDeviceToHost));
-        ODS_HIP(hipMemcpy(&T[size_t(l)].nBandTiles, T[size_t(l)].tileRank + T[size_t(l)].nt, sizeof(int), hipMemcpyDeviceToHost));
-    }
-    {
-        int interiorBad = 0;  // (the mask kernel of the fine level checks the INTERIOR cells on the way)
-        ODS_HIP(hipMemcpy(&interiorBad, flags + 2 * mgLevels, sizeof(int), hipMemcpyDeviceToHost));
-        if (interiorBad)
-            return bail(failH(h, MGPS_ERR_HIERARCHY,
-                              "labels/weights violate the BOUNDARY-cell rules (unitTestBoundaryCells): run mgps_fields_set_boundary_labels"));
-    }
-    clock.lap("band masks + counts");
-
-    // ---- band lists in reference order, classification, scan of the general cells
-    for (int l = 0; l < levels; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        const size_t nb = size_t(t.nband);
-        L.nband = t.nband;
-        ODS_TRY(tmp.get(h, &t.sorted, nb));
-        ODS_TRY(tmp.get(h, &t.general, nb));
-        ODS_TRY(tmp.get(h, &t.genRank, nb + 1));
-        ODS_TRY(tmp.get(h, &t.bandEntry, nb));
-        ODS_TRY(tmp.get(h, &t.diagS, nb));
-        ODS_TRY(devAlloc(h, &L.band, nb, false));
-        ODS_TRY(devAlloc(h, &L.bandDiag, nb, false));
-        ODS_TRY(devAlloc(h, &L.bandTmp, nb, false));
-        if (t.nband > 0) {
-            ODS_LAUNCH(launchBandFill(nullptr, L.d, t.mask, t.prefix, t.tileStart, t.sorted));
-            ODS_LAUNCH(launchBandClassify(nullptr, L.d, labOf(l), l == 0 ? h->w[0] : nullptr, l == 0 ? h->w[1] : nullptr, l == 0 ? h->w[2] : nullptr, t.sorted,
-                                          t.nband, t.diagS, t.general, l == 0 ? flags + 2 * mgLevels + 1 : nullptr));
-        }
-        ODS_LAUNCH(launchExclusiveScan(nullptr, t.general, t.genRank, nb, t.scan));
-    }
-    for (int l = 0; l < levels; ++l) ODS_HIP(hipMemcpy(&T[size_t(l)].nGen, T[size_t(l)].genRank + T[size_t(l)].nband, sizeof(int), hipMemcpyDeviceToHost));
-    {
-        int violations = 0;
-        ODS_HIP(hipMemcpy(&violations, flags + 2 * mgLevels + 1, sizeof(int), hipMemcpyDeviceToHost));
-        if (violations)
-            return bail(failH(h, MGPS_ERR_HIERARCHY,
-                              "labels/weights violate the BOUNDARY-cell rules (unitTestBoundaryCells): run mgps_fields_set_boundary_labels"));
-    }
-    clock.lap("band lists + classification");
-
-    // ---- device order, rows, codes, activity flags
-    for (int l = 0; l < levels; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        L.nbndGeneral = t.nGen;
-        ODS_TRY(devAlloc(h, &L.rows, size_t(7) * size_t(t.nGen), false));
-        ODS_TRY(devAlloc(h, &L.tileBndStart, size_t(t.nt) + 1, false));
-        ODS_LAUNCH(launchBandSplit(nullptr, L.d, labOf(l), l == 0 ? h->w[0] : nullptr, l == 0 ? h->w[1] : nullptr, l == 0 ? h->w[2] : nullptr, t.sorted, t.nband,
-                                   t.diagS, t.genRank, L.band, L.bandDiag, t.bandEntry, L.rows));
-        ODS_LAUNCH(launchGather(nullptr, t.genRank, t.tileStart, t.nt + 1, L.tileBndStart));
-        t.nfine = (L.d.cells() + kSegCells - 1) / kSegCells;
-        t.planeZc = planeSweepZc(L.d.nx, L.d.ny, L.d.nz);
-        ODS_TRY(tmp.get(h, &t.chunkFlags, t.nfine));
-        if (t.planeZc) {
-            t.nplane = size_t((L.d.nx + 255) / 256) * size_t((L.d.ny + kPlaneRows - 1) / kPlaneRows) * size_t((L.d.nz + t.planeZc - 1) / t.planeZc);
-            ODS_TRY(tmp.get(h, &t.planeFlags, t.nplane));
-            ODS_HIP(hipMemsetAsync(t.planeFlags, 0, t.nplane, nullptr));
-        }
-        ODS_LAUNCH(launchActivityFlags(nullptr, L.d, labOf(l), t.chunkFlags, t.planeFlags, t.planeZc));
-        ODS_TRY(tmp.get(h, &t.runCounts, 4));
-        ODS_HIP(hipMemsetAsync(t.runCounts, 0, 4 * sizeof(int), nullptr));
-        ODS_LAUNCH(launchCountRuns(nullptr, t.chunkFlags, t.nfine, t.runCounts));
-        // (the groups below read the labels for activity only: patched or not makes no difference)
-        ODS_LAUNCH(launchPatchSimpleCodes(nullptr, labOf(l), L.band, L.bandDiag, L.nbndGeneral, L.nband));
-    }
-    // ---- boxes of the fused band stage: counts
-    const bool wantGroups = o.fuse_band_passes && o.band_iterations >= 1 && o.band_iterations <= kBandMaxDepth;
-    std::vector<int> haveGroups(size_t(levels), 0);
-    for (int l = 0; l < levels && wantGroups; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        if (t.nband == 0 || !boxPlaneFits(L.d)) continue;
-        haveGroups[size_t(l)] = 1;
-        ODS_TRY(tmp.get(h, &t.boxTiles, size_t(t.nt)));
-        ODS_LAUNCH(launchBoxTileList(nullptr, L.d, t.tileStart, t.tileFlags, t.tileRank, t.boxTiles, t.scan));
-        ODS_HIP(hipMemcpy(&t.nBoxTiles, t.tileRank + t.nt, sizeof(int), hipMemcpyDeviceToHost));
-        for (int q = 0; q < 3; ++q) {
-            ODS_TRY(tmp.get(h, &t.gcount[q], size_t(t.nBoxTiles)));
-            ODS_TRY(tmp.get(h, &t.gat[q], size_t(t.nBoxTiles) + 1));
-        }
-        ODS_LAUNCH(launchBandBoxesCount(nullptr, L.d, labOf(l), t.mask, t.prefix, t.tileStart, t.bandEntry, L.bandDiag, o.band_iterations, t.boxTiles, t.nBoxTiles,
-                                        t.gcount, flags + 2 * mgLevels + 2 + l));
-        for (int q = 0; q < 3; ++q) ODS_LAUNCH(launchExclusiveScan(nullptr, t.gcount[q], t.gat[q], size_t(t.nBoxTiles), t.scan));
-    }
-    // ---- host side of the lists: flags and kinds come back, lists go up
-    for (int l = 0; l < levels; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        StageClock sub(h->opt.print_stats > 1);
-        // run length of the activity list from the device's counts; the flags come back folded to that length
-        int rc4[4] = {0, 0, 0, 0};
-        ODS_HIP(hipMemcpy(rc4, t.runCounts, sizeof(rc4), hipMemcpyDeviceToHost));
-        const int64_t rc64[4] = {rc4[0], rc4[1], rc4[2], rc4[3]};
-        const int runCells = chooseRunCells(rc64);
-        const size_t nruns = (t.nfine + size_t(runCells / kSegCells) - 1) / size_t(runCells / kSegCells);
-        uint8_t *runFlags = t.chunkFlags;
-        if (runCells != kSegCells) {
-            ODS_TRY(tmp.get(h, &runFlags, nruns));
-            ODS_LAUNCH(launchFoldRunFlags(nullptr, t.chunkFlags, t.nfine, runCells, runFlags));
-        }
-        // the list on the device: its length is the count of active runs, rounded up to whole workgroups
-        int activeRuns = 0;
-        for (int z = 0; z < 4; ++z)
-            if (kRunSizes[z] == runCells) activeRuns = rc4[z];
-        const int perGroup = kChunkCells / runCells, listLen = (activeRuns + perGroup - 1) / perGroup * perGroup;
+    rc = [&]() -> int {
+        // ---- the coarsest level's direct solver on host threads, beside everything below
         {
-            int32_t *tmpFlags = nullptr, *rank = nullptr, *base = nullptr;
-            ODS_TRY(tmp.get(h, &tmpFlags, nruns));
-            ODS_TRY(tmp.get(h, &rank, nruns + 1));
-            ODS_TRY(tmp.get(h, &base, 1));
-            ODS_TRY(devAlloc(h, &L.chunks, size_t(listLen), false));
-            ODS_LAUNCH(launchRunList(nullptr, L.d, runFlags, nruns, runCells, tmpFlags, rank, t.scan, base, L.chunks, listLen));
+            const Dims cd = h->lv[size_t(levels - 1)].d;
+            std::vector<uint8_t> coarsest(cd.cells());
+            MGPS_HIP(h, hipMemcpy(coarsest.data(), labOf(levels - 1), cd.cells(), hipMemcpyDeviceToHost));
+            inverseJob = std::thread([h, nx, ny, nz, levels, needCoarse, &rcInverse, lab = std::move(coarsest)] {
+                rcInverse = hierarchyLight(&h->hier, nx, ny, nz, levels, lab.data(), h->opt, needCoarse);
+                if (rcInverse == MGPS_OK && needCoarse) h->hier->buildDenseInverse();
+            });
         }
-        // the four Gauss-Seidel tile lists and the plane-block list: compacted on the device too; the five counts come back
-        // together below
-        ODS_TRY(tmp.get(h, &t.listCounts, 5));
-        ODS_HIP(hipMemsetAsync(t.listCounts, 0, 5 * sizeof(int32_t), nullptr));
+        // ---- face weights
         {
-            int32_t **cls[4] = {&L.pure[0], &L.pure[1], &L.mixed[0], &L.mixed[1]};  // pure even, pure odd, mixed even, mixed odd
-            for (int q = 0; q < 4; ++q) {
-                ODS_TRY(devAlloc(h, cls[q], size_t(t.nt) / 2 + 1, false));
-                ODS_LAUNCH(launchTileClassList(nullptr, L.d, t.tileKind, q & 1, q >> 1, t.tileFlags, t.tileRank, *cls[q], t.scan));
-                ODS_HIP(hipMemcpyAsync(t.listCounts + q, t.tileRank + t.nt, sizeof(int32_t), hipMemcpyDeviceToDevice, nullptr));
-            }
-            if (t.nplane) {
-                int32_t *pf = nullptr, *pr = nullptr;
-                ODS_TRY(tmp.get(h, &pf, t.nplane));
-                ODS_TRY(tmp.get(h, &pr, t.nplane + 1));
-                ODS_TRY(devAlloc(h, &L.planeBlocks, t.nplane, false));
-                ODS_LAUNCH(launchByteList(nullptr, t.planeFlags, int(t.nplane), pf, pr, L.planeBlocks, t.scan));
-                ODS_HIP(hipMemcpyAsync(t.listCounts + 4, pr + t.nplane, sizeof(int32_t), hipMemcpyDeviceToDevice, nullptr));
+            const size_t wn[3] = {size_t(d0.nx + 1) * d0.ny * d0.nz, size_t(d0.nx) * (d0.ny + 1) * d0.nz, size_t(d0.nx) * d0.ny * (d0.nz + 1)};
+            const float *src[3] = {wx, wy, wz};
+            h->weightsBorrowed = kind == hipMemcpyDeviceToDevice && o.borrow_device_weights != 0;
+            for (int a = 0; a < 3 && wx; ++a) {
+                if (h->weightsBorrowed) {
+                    h->w[a] = const_cast<float *>(src[a]);
+                    continue;
+                }
+                MGPS_TRY(devAlloc(h, &h->w[a], wn[a], false));
+                MGPS_HIP(h, hipMemcpyAsync(h->w[a], src[a], wn[a] * sizeof(float), kind, nullptr));
             }
         }
-        t.runCells = runCells;
-        t.listLen = listLen;
-        sub.lap("   lists: enqueued", l);
-        if (l > 0) {
-            ODS_TRY(gridAlloc(h, &L.x, L.d));
-            ODS_TRY(gridAlloc(h, &L.b, L.d));
+
+        // ---- band masks and tile counts of every level, then one round of counts to the host
+        std::vector<LevelBuild> T{size_t(levels)};
+        for (int l = 0; l < levels; ++l) {
+            LevelBuild &t = T[size_t(l)];
+            t.d = t.own = h->lv[size_t(l)].d;
+            t.lab = t.ownLab = labOf(l);
+            for (int a = 0; a < 3; ++a) t.wv.w[a] = l == 0 ? h->w[a] : nullptr;
+            t.wv.nz = t.d.nz;
+            MGPS_TRY(bandCandidates(h, tmp, t));
         }
-        ODS_TRY(gridAlloc(h, &L.r, L.d));
-        ODS_TRY(gridAlloc(h, &L.tmp, L.d));
-    }
-    for (int l = 0; l < levels; ++l) {
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        int32_t counts[5] = {0, 0, 0, 0, 0};
-        ODS_HIP(hipMemcpy(counts, t.listCounts, sizeof(counts), hipMemcpyDeviceToHost));
-        L.npure[0] = counts[0];
-        L.npure[1] = counts[1];
-        L.nmixed[0] = counts[2];
-        L.nmixed[1] = counts[3];
-        fillGridP(h, L, l == 0 && wx, t.listLen, t.runCells, counts[4], t.planeZc);
-    }
-    clock.lap("device order, codes, activity + tile lists");
-    // ---- boxes: totals to the host, arrays filled
-    for (int l = 0; l < levels; ++l) {
-        if (!haveGroups[size_t(l)]) continue;
-        DevLevel &L = h->lv[size_t(l)];
-        LevelTmp &t = T[size_t(l)];
-        int tot[3] = {0, 0, 0}, brokenL = 0;
-        for (int q = 0; q < 3; ++q) ODS_HIP(hipMemcpy(&tot[q], t.gat[q] + t.nBoxTiles, sizeof(int), hipMemcpyDeviceToHost));
-        ODS_HIP(hipMemcpy(&brokenL, flags + 2 * mgLevels + 2 + l, sizeof(int), hipMemcpyDeviceToHost));
-        if (brokenL || tot[0] == 0) return bail(failH(h, MGPS_ERR_INTERNAL, "band boxes: the builder failed on level " + std::to_string(l)));
-        L.bandBoxes.depth = o.band_iterations;
-        L.bandBoxes.ngroups = tot[0];
-        L.bandBoxes.listCount = size_t(tot[1]);
-        L.bandBoxes.generalInts = 2 * size_t(tot[2]);
-        L.bandBoxes.anyGeneral = tot[2] > 0;
-        ODS_TRY(devAlloc(h, &L.bandBoxes.info, size_t(kBoxInfoInts) * size_t(tot[0]), false));
-        ODS_TRY(devAlloc(h, &L.bandBoxes.list, size_t(tot[1]), false));
-        ODS_TRY(devAlloc(h, &L.bandBoxes.general, 2 * size_t(tot[2]), false));
-        ODS_LAUNCH(launchBandBoxesFill(nullptr, L.d, labOf(l), t.mask, t.prefix, t.tileStart, t.bandEntry, L.bandDiag, o.band_iterations, t.boxTiles, t.nBoxTiles,
-                                       t.gat, L.bandBoxes.info, L.bandBoxes.list, L.bandBoxes.general, flags + 2 * mgLevels + 2 + l));
-        ODS_TRY(finishBandBoxes(h, L, nullptr));
-    }
-    ODS_HIP(hipDeviceSynchronize());
-    clock.lap("band boxes");
+        for (int l = 0; l < levels; ++l) MGPS_TRY(bandMasks(h, T[size_t(l)], o.band_width, l == 0 ? flags + 2 * mgLevels : nullptr));
+        for (int l = 0; l < levels; ++l) MGPS_HIP(h, hipMemcpy(&T[size_t(l)].nband, T[size_t(l)].tileStart + T[size_t(l)].nt, sizeof(int), hipMemcpyDeviceToHost));
+        {
+            int interiorBad = 0;  // (the mask kernel of the fine level checks the INTERIOR cells on the way)
+            MGPS_HIP(h, hipMemcpy(&interiorBad, flags + 2 * mgLevels, sizeof(int), hipMemcpyDeviceToHost));
+            if (interiorBad)
+                return failH(h, MGPS_ERR_HIERARCHY, "labels/weights violate the BOUNDARY-cell rules (unitTestBoundaryCells): run mgps_fields_set_boundary_labels");
+        }
+        clock.lap("band masks + counts");
+
+        // ---- band lists in reference order, classification, scan of the general cells
+        for (int l = 0; l < levels; ++l) {
+            DevLevel &L = h->lv[size_t(l)];
+            LevelBuild &t = T[size_t(l)];
+            L.nband = t.nband;
+            MGPS_TRY(devAlloc(h, &L.band, size_t(t.nband), false));
+            MGPS_TRY(devAlloc(h, &L.bandDiag, size_t(t.nband), false));
+            MGPS_TRY(devAlloc(h, &L.bandTmp, size_t(t.nband), false));
+            t.band = L.band;
+            t.diag = L.bandDiag;
+            MGPS_TRY(bandLists(h, tmp, t, l == 0 ? flags + 2 * mgLevels + 1 : nullptr));
+        }
+        for (int l = 0; l < levels; ++l) MGPS_HIP(h, hipMemcpy(&T[size_t(l)].nGen, T[size_t(l)].genRank + T[size_t(l)].nband, sizeof(int), hipMemcpyDeviceToHost));
+        {
+            int violations = 0;
+            MGPS_HIP(h, hipMemcpy(&violations, flags + 2 * mgLevels + 1, sizeof(int), hipMemcpyDeviceToHost));
+            if (violations)
+                return failH(h, MGPS_ERR_HIERARCHY, "labels/weights violate the BOUNDARY-cell rules (unitTestBoundaryCells): run mgps_fields_set_boundary_labels");
+        }
+        clock.lap("band lists + classification");
+
+        // ---- device order, rows, codes, activity flags
+        for (int l = 0; l < levels; ++l) {
+            DevLevel &L = h->lv[size_t(l)];
+            L.nbndGeneral = T[size_t(l)].nGen;
+            MGPS_TRY(bandRows(h, T[size_t(l)], L));
+            MGPS_TRY(activity(h, tmp, T[size_t(l)], false, false));
+            // (the groups below read the labels for activity only: patched or not makes no difference)
+            MGPS_LAUNCH(h, launchPatchSimpleCodes(nullptr, labOf(l), L.band, L.bandDiag, L.nbndGeneral, L.nband));
+        }
+        // ---- boxes of the fused band stage: counts
+        const bool wantGroups = o.fuse_band_passes && o.band_iterations >= 1 && o.band_iterations <= kBandMaxDepth;
+        std::vector<int> haveGroups(size_t(levels), 0);
+        for (int l = 0; l < levels && wantGroups; ++l) {
+            if (T[size_t(l)].nband == 0 || !boxPlaneFits(h->lv[size_t(l)].d)) continue;
+            haveGroups[size_t(l)] = 1;
+            MGPS_TRY(boxCounts(h, tmp, T[size_t(l)], o.band_iterations, flags + 2 * mgLevels + 2 + l));
+        }
+        // ---- host side of the lists: flags and kinds come back, lists go up
+        for (int l = 0; l < levels; ++l) {
+            StageClock sub(h->opt.print_stats > 1);
+            MGPS_TRY(levelLists(h, tmp, T[size_t(l)], h->lv[size_t(l)], l));
+            sub.lap("   lists: enqueued", l);
+        }
+        for (int l = 0; l < levels; ++l) {
+            DevLevel &L = h->lv[size_t(l)];
+            LevelBuild &t = T[size_t(l)];
+            MGPS_TRY(listCounts(h, t, L));
+            fillGridP(h, L, l == 0 && wx, t.listLen, t.runCells, t.nplaneBlocks, t.planeZc);
+        }
+        clock.lap("device order, codes, activity + tile lists");
+        // ---- boxes: totals to the host, arrays filled
+        for (int l = 0; l < levels; ++l) {
+            if (!haveGroups[size_t(l)]) continue;
+            int *broken = flags + 2 * mgLevels + 2 + l;
+            int tot[3] = {0, 0, 0}, brokenL = 0;
+            MGPS_TRY(boxTotals(h, T[size_t(l)], broken, tot, &brokenL));
+            if (brokenL || tot[0] == 0) return failH(h, MGPS_ERR_INTERNAL, "band boxes: the builder failed on level " + std::to_string(l));
+            MGPS_TRY(boxFill(h, T[size_t(l)], h->lv[size_t(l)], o.band_iterations, tot, broken));
+        }
+        MGPS_HIP(h, hipDeviceSynchronize());
+        clock.lap("band boxes");
+        return MGPS_OK;
+    }();
+    if (rc != MGPS_OK) return bail(rc);
     inverseJob.join();
     if (rcInverse != MGPS_OK) {
         h->lastError = lastGlobalError();
         return bail(rcInverse);
     }
     clock.lap("wait for the coarse inverse");
-    int rc = commonDeviceState(h, needCoarse);
+    rc = commonDeviceState(h, needCoarse);
     if (rc != MGPS_OK) return bail(rc);
     clock.lap("coarse solver upload + scratch");
-#undef ODS_TRY
-#undef ODS_HIP
-#undef ODS_LAUNCH
     *out = h;
     return MGPS_OK;
 }
@@ -3303,8 +3410,8 @@ MGPS_API_CATCH(nullptr)
 namespace {
 // ---- a slab rank set up on the device (round 5) ---------------------------------------------------------------------------
 // What createSlabImpl below does through the host builder -- 217-280 ms for a 1024^3 / 8 rank, of which 90 ms went into coarsening
-// the GLOBAL labels on every rank's host and 80 ms into the halo groups of the graph-form band stage -- with the kernels of
-// createWholeOnDevice on a window of the labels:
+// the GLOBAL labels on every rank's host and 80 ms into the halo groups of the graph-form band stage -- with the level stages of
+// createWholeOnDevice (LevelBuild) on a window of the labels:
 //   * per level a label BUFFER: the owned planes and, on both sides, ghost planes of labels (kLabelGhost0 x 2^(Dmax-1-l) planes: the
 //     buffers of two levels nest, the coarsening kernel runs on them unchanged).  Real labels as far as the coarser levels' windows
 //     need them (the rank's window of the global labels goes up once, 1 B per cell), EXTERIOR beyond;
@@ -3317,7 +3424,7 @@ namespace {
 //     general cells);
 //   * level cap and shell tests are agreed by an all-reduce of the ranks' flags; rank 0 receives the collapse level's labels and
 //     builds the tail with createWholeOnDevice.
-// Every failure is folded into an all-reduce that all ranks take part in before the next collective: no rank leaves alone.
+// Every failure is folded into an all-reduce (agreeSlab) that all ranks take part in before the next collective: no rank leaves alone.
 constexpr int kSlabGhostPlanes = kBandMaxDepth + 1;  // planes of every grid beyond its owned ones: a box region reaches depth + 1 past its owned box
 constexpr int kLabelGhost0 = 16;                     // label ghost planes of the coarsest distributed level's buffer (>= the reach below, tile-aligned)
 
@@ -3356,17 +3463,24 @@ int uploadPageable(mgps_solver *h, void *dst, const void *src, size_t bytes, int
     return MGPS_OK;
 }
 
+// the verdict of slab set-up that all ranks share: the largest status (0 = fine), all-reduced (max) together with `n` doubles of
+// payload.  Every rank calls it at the same places; a rank that was fine names the failure of another
+int agreeSlab(mgps_solver *h, int status, double *payload = nullptr, int n = 0)
+{
+    std::vector<double> v(payload, payload + n);
+    v.push_back(double(status));
+    if (h->comm.allreduce(h->comm.user, v.data(), int(v.size()), 1) != 0) return failH(h, MGPS_ERR_COMM, "all-reduce failed during set-up");
+    std::copy(v.begin(), v.begin() + n, payload);
+    const int all = int(v[size_t(n)]);
+    if (all == MGPS_OK) return MGPS_OK;
+    if (status == MGPS_OK) failH(h, all, "slab set-up failed on another rank");
+    return status != MGPS_OK ? status : all;
+}
+
 int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t *labels_global_host, const float *wx_slab, const float *wy_slab,
                        const float *wz_slab, bool weightsOnDevice, int mgLevels, bool useGS, const mgps_options &o, const mgps_comm *comm, const int *splits, int device)
 {
-    if (mgLevels < 2 || nx < 2 || ny < 2 || nzg < 2 || (nx & 1) || (ny & 1) || (nzg & 1))
-        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: extents must be even and >= 2, mg_levels >= 2");
-    if (size_t(nx) * ny * nzg > size_t(0x7fffffff)) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: more than 2^31-1 cells per grid");
-    for (int l = 1; l < mgLevels; ++l)
-        if (((nx >> (l - 1)) & 1) || ((ny >> (l - 1)) & 1) || ((nzg >> (l - 1)) & 1) || (nx >> l) < 1 || (ny >> l) < 1 || (nzg >> l) < 1)
-            return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: extents are not divisible by 2^(levels-1)");
-    if (o.band_width < 1 || o.band_width > 8 || o.band_iterations < 0)
-        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: band_width 1 .. 8, band_iterations >= 0");
+    MGPS_TRY(checkSetupArgs("mgps_create_slab", 2, nx, ny, nzg, mgLevels, o, "band_width 1 .. 8, band_iterations >= 0"));
     const int P = comm->size, rank = comm->rank;
     const bool lo = rank > 0, hi = rank < P - 1;
     // the deepest the distributed part can be (the level cap can only shorten the hierarchy): label windows are sized for it
@@ -3393,13 +3507,6 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
     };
     StageClock sclock(setupTimingOn());
     DevScratch tmp;
-    // a verdict all ranks share: the largest status (0 = fine).  Every rank calls it at the same places.
-    auto agree = [&](int mine, int *all) -> int {
-        double v = double(mine);
-        if (h->comm.allreduce(h->comm.user, &v, 1, 1) != 0) return failH(h, MGPS_ERR_COMM, "all-reduce failed during set-up");
-        *all = int(v);
-        return MGPS_OK;
-    };
     const int z0 = splits[rank], z1 = splits[rank + 1];
     const bool wantBoxes = o.fuse_band_passes && o.deep_band_halo && o.band_iterations >= 1 && o.band_iterations <= kBandMaxDepth;
     const int depth = o.band_iterations;
@@ -3429,21 +3536,21 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
     B[size_t(Dmax)].real = 3;  // (the collapse level is marked on its owned planes: one plane of neighbours, and one for theirs)
     if (Dmax >= 1) B[size_t(Dmax) - 1].real = std::max(reach, 2 * B[size_t(Dmax)].real + 2);
     for (int l = Dmax - 2; l >= 0; --l) B[size_t(l)].real = 2 * B[size_t(l) + 1].real + 2;
-    for (int l = 0; l <= Dmax; ++l) {
-        Buf &b = B[size_t(l)];
-        if (b.real > b.elo) return bail(failH(h, MGPS_ERR_INTERNAL, "slab set-up: label window past its buffer"));
-        const size_t plane = size_t(b.d.nx) * b.d.ny;
-        int rc = tmp.get(h, &b.base, (size_t(b.d.nz) + 2) * plane);
-        if (rc != MGPS_OK) return bail(rc);
-        if (hipMemsetAsync(b.base, MGPS_EXTERIOR_CELL, (size_t(b.d.nz) + 2) * plane, nullptr) != hipSuccess) return bail(failH(h, MGPS_ERR_HIP, "memset failed"));
-    }
-    int status = MGPS_OK;
-    {  // the rank's window of the fine labels
+    for (int l = 0; l <= Dmax; ++l)
+        if (B[size_t(l)].real > B[size_t(l)].elo) return bail(failH(h, MGPS_ERR_INTERNAL, "slab set-up: label window past its buffer"));
+    // (a failure from here on is carried by the first all-reduce: no rank leaves alone)
+    int status = [&]() -> int {
+        for (Buf &b : B) {
+            const size_t bytes = (size_t(b.d.nz) + 2) * size_t(b.d.nx) * b.d.ny;
+            MGPS_TRY(tmp.get(h, &b.base, bytes));
+            if (hipMemsetAsync(b.base, MGPS_EXTERIOR_CELL, bytes, nullptr) != hipSuccess) return failH(h, MGPS_ERR_HIP, "memset failed");
+        }
+        // the rank's window of the fine labels
         const Buf &b = B[0];
         const int a = std::max(0, z0 - b.real), e = std::min(nzg, z1 + b.real);
         const size_t plane = size_t(nx) * ny;
-        status = uploadPageable(h, b.owned() + ptrdiff_t(a - z0) * ptrdiff_t(plane), labels_global_host + size_t(a) * plane, size_t(e - a) * plane, device);
-    }
+        return uploadPageable(h, b.owned() + ptrdiff_t(a - z0) * ptrdiff_t(plane), labels_global_host + size_t(a) * plane, size_t(e - a) * plane, device);
+    }();
     sclock.lap("slab: label window upload");
     // flags: per level l [2 l] shell broken, [2 l + 1] holds an active cell; then interior rule, weight rule, boxes broken per level
     const size_t nflags = size_t(2 * (mgLevels + 1) + 2 + mgLevels);
@@ -3457,8 +3564,6 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         MGPS_LAUNCH(h, launchShellCheckSlab(nullptr, B[0].own, B[0].owned(), !lo, !hi, flags));
         MGPS_LAUNCH(h, launchAnyActive(nullptr, B[0].own, B[0].owned(), flags + 1));
         for (int l = 1; l <= Dmax; ++l) {
-            int scratchFlag = 0;
-            (void)scratchFlag;
             MGPS_LAUNCH(h, launchCoarsenLabels(nullptr, B[size_t(l) - 1].d, B[size_t(l) - 1].lab(), B[size_t(l)].lab(), flags + 2 * l + 1));
             MGPS_LAUNCH(h, launchShellCheckSlab(nullptr, B[size_t(l)].own, B[size_t(l)].owned(), !lo, !hi, flags + 2 * l));
         }
@@ -3471,27 +3576,13 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
     // ---- the ranks' flags together: level cap (MG.cpp:238-253), shell tests
     int levels = mgLevels;
     {
-        std::vector<double> v(size_t(2 * mgLevels) + 1, 0.0);
+        std::vector<double> v(size_t(2 * mgLevels), 0.0);
         for (int q = 0; q < 2 * mgLevels; ++q) v[size_t(q)] = hflags[size_t(q)] ? 1.0 : 0.0;
-        v[size_t(2 * mgLevels)] = double(status);
-        if (h->comm.allreduce(h->comm.user, v.data(), int(v.size()), 1) != 0) return bail(failH(h, MGPS_ERR_COMM, "all-reduce failed during set-up"));
-        if (int(v[size_t(2 * mgLevels)]) != MGPS_OK) {
-            if (status == MGPS_OK) failH(h, int(v[size_t(2 * mgLevels)]), "slab set-up failed on another rank");
-            return bail(status != MGPS_OK ? status : int(v[size_t(2 * mgLevels)]));
-        }
-        if (v[0] != 0.0) return bail(failH(h, MGPS_ERR_HIERARCHY, "labels need an EXTERIOR shell on all six sides (unitTestExteriorCells)"));
-        if (v[1] == 0.0) return bail(failH(h, MGPS_ERR_HIERARCHY, "no INTERIOR or BOUNDARY cell in the domain"));
-        for (int l = 1; l <= Dmax && l < mgLevels; ++l) {
-            if (v[size_t(2 * l)] != 0.0)
-                return bail(failH(h, MGPS_ERR_HIERARCHY,
-                                  "level " + std::to_string(l) + " has no EXTERIOR shell (unitTestExteriorCells, MG.cpp:252): " + std::to_string(mgLevels) +
-                                      " levels need 2^(levels-1) = " + std::to_string(1 << (mgLevels - 1)) + " EXTERIOR cells on every side of the solver grid"));
-            if (v[size_t(2 * l + 1)] == 0.0) {
-                levels = l - 1;  // the reference drops the last solvable level too (MG.cpp:245)
-                break;
-            }
-        }
-        if (levels < 1) return bail(failH(h, MGPS_ERR_HIERARCHY, "level cap left no multigrid level (first coarse level has no solvable cell)"));
+        int rc = agreeSlab(h, status, v.data(), int(v.size()));
+        if (rc != MGPS_OK) return bail(rc);
+        const std::vector<int> any(v.begin(), v.end());
+        rc = levelCap(h, any.data(), mgLevels, std::min(Dmax + 1, mgLevels), true, "", &levels);
+        if (rc != MGPS_OK) return bail(rc);
     }
     const int D = distributedLevelsFor(splits, P, nx, ny, levels, useGS, o);
     if (D < 1)
@@ -3524,15 +3615,7 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         MGPS_HIP(h, hipStreamSynchronize(nullptr));
         return MGPS_OK;
     }();
-    {
-        int all = MGPS_OK;
-        const int rc = agree(status, &all);
-        if (rc != MGPS_OK) return bail(rc);
-        if (all != MGPS_OK) {
-            if (status == MGPS_OK) failH(h, all, "slab set-up failed on another rank");
-            return bail(status != MGPS_OK ? status : all);
-        }
-    }
+    if (int rc = agreeSlab(h, status); rc != MGPS_OK) return bail(rc);
     // what travels: wx / wy planes [0, gw) down and [nzl - gw, nzl) up; of wz the faces [1, gw] down and [nzl - gw, nzl - 1] up
     // (before the exchange the ghost planes hold a mirror image of the rank's own: a transport that moves nothing -- the
     // compute-bound tools -- leaves plausible weights there)
@@ -3544,15 +3627,8 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
             status = failH(h, MGPS_ERR_HIP, "weight ghost planes: copy failed");
     }
     if (hipStreamSynchronize(nullptr) != hipSuccess && status == MGPS_OK) status = failH(h, MGPS_ERR_HIP, "weight ghost planes: copy failed");
-    {  // (a rank whose copies failed must not leave its neighbours waiting in the exchange below)
-        int all = MGPS_OK;
-        const int rc = agree(status, &all);
-        if (rc != MGPS_OK) return bail(rc);
-        if (all != MGPS_OK) {
-            if (status == MGPS_OK) failH(h, all, "slab set-up failed on another rank");
-            return bail(status != MGPS_OK ? status : all);
-        }
-    }
+    // (a rank whose copies failed must not leave its neighbours waiting in the exchange below)
+    if (int rc = agreeSlab(h, status); rc != MGPS_OK) return bail(rc);
     for (int a = 0; a < 3 && nzl >= gw; ++a) {
         const size_t bytes = wplane[a] * size_t(gw) * sizeof(float);
         const float *down = h->w[a] + (a == 2 ? wplane[a] : 0), *up = h->w[a] + wplane[a] * size_t(nzl - gw);
@@ -3563,67 +3639,30 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
     sclock.lap("slab: weights + their ghost planes");
 
     // ---- the distributed levels on their buffers
-    struct LevelTmp {
-        int nt = 0, tx = 0, ty = 0, tz = 0;
-        uint32_t *mask = nullptr;
-        uint16_t *prefix = nullptr;
-        int32_t *tileCount = nullptr, *tileKind = nullptr, *tileStart = nullptr, *scan = nullptr;
-        int32_t *sorted = nullptr, *general = nullptr, *genRank = nullptr, *bandEntry = nullptr, *extBand = nullptr;
-        int32_t *own = nullptr, *ownGen = nullptr, *ownRank = nullptr, *ownGenRank = nullptr;
-        uint8_t *diagS = nullptr, *extDiag = nullptr, *chunkFlags = nullptr, *planeFlags = nullptr;
-        int32_t *gcount[3] = {nullptr, nullptr, nullptr}, *gat[3] = {nullptr, nullptr, nullptr};
-        int32_t *tileFlags = nullptr, *tileRank = nullptr, *bandTiles = nullptr, *boxTiles = nullptr;
-        uint8_t *tileBits = nullptr;
-        int *runCounts = nullptr;
-        int32_t *listCounts = nullptr;
-        int runCells = 0, listLen = 0, nbandExt = 0, nGenExt = 0, planeZc = 0, nBoxTiles = 0, nplaneBlocks = 0;
-        size_t nfine = 0, nplane = 0;
-        SlabWindow win;
-    };
-    std::vector<LevelTmp> T;
-    T.resize(size_t(D));
+    std::vector<LevelBuild> T{size_t(D)};
     std::vector<int> boxesOk(size_t(D), 0);
     status = [&]() -> int {
         for (int l = 0; l < D; ++l) {
             DevLevel &L = h->lv[size_t(l)];
-            LevelTmp &t = T[size_t(l)];
+            LevelBuild &t = T[size_t(l)];
             const Buf &b = B[size_t(l)];
             L.d = b.own;
             L.z0 = z0 >> l;
             L.z1 = z1 >> l;
             L.elo = b.elo;
-            t.win = SlabWindow{b.elo, b.elo + b.own.nz, reach};
-            t.tx = (b.d.nx + kTile - 1) / kTile;
-            t.ty = (b.d.ny + kTile - 1) / kTile;
-            t.tz = (b.d.nz + kTile - 1) / kTile;
-            t.nt = t.tx * t.ty * t.tz;
-            MGPS_TRY(tmp.get(h, &t.mask, size_t(t.nt) * 128));
-            MGPS_TRY(tmp.get(h, &t.prefix, size_t(t.nt) * 128));
-            MGPS_TRY(tmp.get(h, &t.tileCount, size_t(t.nt)));
-            MGPS_TRY(tmp.get(h, &t.tileKind, size_t(t.nt)));
-            MGPS_TRY(tmp.get(h, &t.tileStart, size_t(t.nt) + 1));
-            MGPS_TRY(tmp.get(h, &t.scan, scanScratchInts(b.d.cells())));
-            MGPS_TRY(tmp.get(h, &t.tileFlags, size_t(t.nt)));
-            MGPS_TRY(tmp.get(h, &t.tileRank, size_t(t.nt) + 1));
-            MGPS_TRY(tmp.get(h, &t.bandTiles, size_t(t.nt)));
-            MGPS_TRY(tmp.get(h, &t.tileBits, size_t(t.nt)));
-            MGPS_HIP(h, hipMemsetAsync(t.mask, 0, size_t(t.nt) * 128 * sizeof(uint32_t), nullptr));
-            MGPS_HIP(h, hipMemsetAsync(t.prefix, 0, size_t(t.nt) * 128 * sizeof(uint16_t), nullptr));
-            MGPS_HIP(h, hipMemsetAsync(t.tileCount, 0, size_t(t.nt) * sizeof(int32_t), nullptr));
-            MGPS_LAUNCH(h, launchBandCandidates(nullptr, b.d, b.lab(), t.tileKind, t.tileBits, t.tileFlags, t.tileRank, t.bandTiles, t.scan, &t.win));
+            t.d = b.d;
+            t.lab = b.lab();
+            t.own = b.own;
+            t.ownLab = b.owned();
+            t.slab = true;
+            t.window = SlabWindow{b.elo, b.elo + b.own.nz, reach};
+            t.tkOffset = ((z0 >> l) / kTile) & 1;  // (tile colours are the whole grid's; with Gauss-Seidel the cuts are multiples of 16 planes)
+            MGPS_TRY(bandCandidates(h, tmp, t));
         }
-        for (int l = 0; l < D; ++l) {
-            LevelTmp &t = T[size_t(l)];
-            const Buf &b = B[size_t(l)];
-            int ncand = 0;
-            MGPS_HIP(h, hipMemcpy(&ncand, t.tileRank + t.nt, sizeof(int), hipMemcpyDeviceToHost));
-            MGPS_LAUNCH(h, launchBandMasks(nullptr, b.d, b.lab(), o.band_width, t.mask, t.prefix, t.tileCount, t.tileKind, l == 0 ? flags + fInterior : nullptr, t.bandTiles,
-                                           ncand, &t.win));
-            MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.tileCount, t.tileStart, size_t(t.nt), t.scan));
-        }
-        for (int l = 0; l < D; ++l) MGPS_HIP(h, hipMemcpy(&T[size_t(l)].nbandExt, T[size_t(l)].tileStart + T[size_t(l)].nt, sizeof(int), hipMemcpyDeviceToHost));
+        for (int l = 0; l < D; ++l) MGPS_TRY(bandMasks(h, T[size_t(l)], o.band_width, l == 0 ? flags + fInterior : nullptr));
+        for (int l = 0; l < D; ++l) MGPS_HIP(h, hipMemcpy(&T[size_t(l)].nband, T[size_t(l)].tileStart + T[size_t(l)].nt, sizeof(int), hipMemcpyDeviceToHost));
         // band lists of the buffers in reference order, classification (level 0: with the weights and their ghost planes), rows
-        WeightView wv;
+        WeightView &wv = T[0].wv;
         for (int a = 0; a < 3; ++a) {
             wv.w[a] = h->w[a];
             wv.lo[a] = wlo[a];
@@ -3632,40 +3671,13 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         wv.nz = nzl;
         wv.gw = nzl >= gw ? gw : 0;
         wv.k0 = B[0].elo;
+        for (int l = 0; l < D; ++l) MGPS_TRY(bandLists(h, tmp, T[size_t(l)], l == 0 ? flags + fWeights : nullptr));
         for (int l = 0; l < D; ++l) {
+            LevelBuild &t = T[size_t(l)];
             DevLevel &L = h->lv[size_t(l)];
-            LevelTmp &t = T[size_t(l)];
-            const Buf &b = B[size_t(l)];
-            const size_t nb = size_t(t.nbandExt);
-            MGPS_TRY(tmp.get(h, &t.sorted, nb));
-            MGPS_TRY(tmp.get(h, &t.general, nb));
-            MGPS_TRY(tmp.get(h, &t.genRank, nb + 1));
-            MGPS_TRY(tmp.get(h, &t.bandEntry, nb));
-            MGPS_TRY(tmp.get(h, &t.diagS, nb));
-            MGPS_TRY(tmp.get(h, &t.extBand, nb));
-            MGPS_TRY(tmp.get(h, &t.extDiag, nb));
-            MGPS_TRY(tmp.get(h, &t.own, nb));
-            MGPS_TRY(tmp.get(h, &t.ownGen, nb));
-            MGPS_TRY(tmp.get(h, &t.ownRank, nb + 1));
-            MGPS_TRY(tmp.get(h, &t.ownGenRank, nb + 1));
-            if (t.nbandExt > 0) {
-                MGPS_LAUNCH(h, launchBandFill(nullptr, b.d, t.mask, t.prefix, t.tileStart, t.sorted));
-                MGPS_LAUNCH(h, launchBandClassify(nullptr, b.d, b.lab(), l == 0 ? wv : WeightView{}, t.sorted, t.nbandExt, t.diagS, t.general, l == 0 ? flags + fWeights : nullptr,
-                                                  &t.win));
-            }
-            MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.general, t.genRank, nb, t.scan));
-            const size_t plane = size_t(b.d.nx) * b.d.ny;
-            MGPS_LAUNCH(h, launchOwnedFlags(nullptr, t.sorted, t.general, t.nbandExt, int32_t(size_t(t.win.own0) * plane), int32_t(size_t(t.win.own1) * plane), t.own, t.ownGen));
-            MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.own, t.ownRank, nb, t.scan));
-            MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.ownGen, t.ownGenRank, nb, t.scan));
-            (void)L;
-        }
-        for (int l = 0; l < D; ++l) {
-            LevelTmp &t = T[size_t(l)];
-            DevLevel &L = h->lv[size_t(l)];
-            MGPS_HIP(h, hipMemcpy(&t.nGenExt, t.genRank + t.nbandExt, sizeof(int), hipMemcpyDeviceToHost));
-            MGPS_HIP(h, hipMemcpy(&L.nband, t.ownRank + t.nbandExt, sizeof(int), hipMemcpyDeviceToHost));
-            MGPS_HIP(h, hipMemcpy(&L.nbndGeneral, t.ownGenRank + t.nbandExt, sizeof(int), hipMemcpyDeviceToHost));
+            MGPS_HIP(h, hipMemcpy(&t.nGen, t.genRank + t.nband, sizeof(int), hipMemcpyDeviceToHost));
+            MGPS_HIP(h, hipMemcpy(&L.nband, t.ownRank + t.nband, sizeof(int), hipMemcpyDeviceToHost));
+            MGPS_HIP(h, hipMemcpy(&L.nbndGeneral, t.ownGenRank + t.nband, sizeof(int), hipMemcpyDeviceToHost));
         }
         MGPS_HIP(h, hipMemcpy(hflags.data() + fInterior, flags + fInterior, 2 * sizeof(int), hipMemcpyDeviceToHost));
         if (hflags[size_t(fInterior)] || hflags[size_t(fWeights)])
@@ -3673,155 +3685,35 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         sclock.lap("slab: band lists + classification");
         // the buffer's device order and rows, the codes, the rank's own lists, activity
         for (int l = 0; l < D; ++l) {
-            DevLevel &L = h->lv[size_t(l)];
-            LevelTmp &t = T[size_t(l)];
-            const Buf &b = B[size_t(l)];
-            const size_t plane = size_t(b.d.nx) * b.d.ny;
-            MGPS_TRY(devAlloc(h, &L.extRows, size_t(7) * size_t(t.nGenExt), false));
-            MGPS_LAUNCH(h, launchBandSplit(nullptr, b.d, b.lab(), l == 0 ? wv : WeightView{}, t.sorted, t.nbandExt, t.diagS, t.genRank, t.extBand, t.extDiag, t.bandEntry,
-                                           L.extRows));
-            MGPS_LAUNCH(h, launchPatchSimpleCodes(nullptr, b.lab(), t.extBand, t.extDiag, t.nGenExt, t.nbandExt));
-            MGPS_TRY(devAlloc(h, &L.band, size_t(L.nband), false));
-            MGPS_TRY(devAlloc(h, &L.bandDiag, size_t(L.nband), false));
-            MGPS_TRY(devAlloc(h, &L.bandTmp, size_t(L.nband), false));
-            MGPS_TRY(devAlloc(h, &L.rows, size_t(7) * size_t(L.nbndGeneral), false));
-            MGPS_LAUNCH(h, launchBandSplitOwned(nullptr, t.sorted, t.nbandExt, int32_t(size_t(t.win.own0) * plane), t.diagS, t.ownRank, t.ownGenRank, t.genRank, L.extRows, L.band,
-                                                L.bandDiag, L.rows));
-            // per owned tile (+ 1) the first of its general cells in the rank's list (the mixed Gauss-Seidel tiles look their rows up there)
-            const int ntOwn = t.tx * t.ty * ((b.own.nz + kTile - 1) / kTile), tileOff = (b.elo / kTile) * t.tx * t.ty;
-            MGPS_TRY(devAlloc(h, &L.tileBndStart, size_t(ntOwn) + 1, false));
-            MGPS_LAUNCH(h, launchGather(nullptr, t.ownGenRank, t.tileStart + tileOff, ntOwn + 1, L.tileBndStart));
-            // activity of the owned planes
-            t.nfine = (b.own.cells() + kSegCells - 1) / kSegCells;
-            t.planeZc = planeSweepZc(b.own.nx, b.own.ny, b.own.nz);
-            MGPS_TRY(tmp.get(h, &t.chunkFlags, t.nfine));
-            if (t.planeZc) {
-                t.nplane = size_t((b.own.nx + 255) / 256) * size_t((b.own.ny + kPlaneRows - 1) / kPlaneRows) * size_t((b.own.nz + t.planeZc - 1) / t.planeZc);
-                MGPS_TRY(tmp.get(h, &t.planeFlags, t.nplane));
-                MGPS_HIP(h, hipMemsetAsync(t.planeFlags, 0, t.nplane, nullptr));
-            }
-            MGPS_LAUNCH(h, launchActivityFlags(nullptr, b.own, b.owned(), t.chunkFlags, t.planeFlags, t.planeZc));
-            if (t.planeZc) {  // (a block next to a cut with active cells only across it still takes part in the residual + restriction pair)
-                if (lo) MGPS_LAUNCH(h, launchGhostPlaneBlockFlags(nullptr, b.own, b.owned(), -1, t.planeZc, t.planeFlags));
-                if (hi) MGPS_LAUNCH(h, launchGhostPlaneBlockFlags(nullptr, b.own, b.owned(), b.own.nz, t.planeZc, t.planeFlags));
-            }
-            MGPS_TRY(tmp.get(h, &t.runCounts, 4));
-            MGPS_HIP(h, hipMemsetAsync(t.runCounts, 0, 4 * sizeof(int), nullptr));
-            MGPS_LAUNCH(h, launchCountRuns(nullptr, t.chunkFlags, t.nfine, t.runCounts));
+            MGPS_TRY(bandRows(h, T[size_t(l)], h->lv[size_t(l)]));
+            MGPS_TRY(activity(h, tmp, T[size_t(l)], lo, hi));
         }
         // boxes of the fused band stage, clipped to the owned planes: counts
         for (int l = 0; l < D && wantBoxes; ++l) {
-            LevelTmp &t = T[size_t(l)];
-            const Buf &b = B[size_t(l)];
-            if (!boxPlaneFits(b.d)) continue;
+            if (!boxPlaneFits(T[size_t(l)].d)) continue;
             boxesOk[size_t(l)] = 1;
-            if (t.nbandExt == 0) continue;
-            MGPS_TRY(tmp.get(h, &t.boxTiles, size_t(t.nt)));
-            MGPS_LAUNCH(h, launchBoxTileList(nullptr, b.d, t.tileStart, t.tileFlags, t.tileRank, t.boxTiles, t.scan));
-            MGPS_HIP(h, hipMemcpy(&t.nBoxTiles, t.tileRank + t.nt, sizeof(int), hipMemcpyDeviceToHost));
-            for (int q = 0; q < 3; ++q) {
-                MGPS_TRY(tmp.get(h, &t.gcount[q], size_t(t.nBoxTiles)));
-                MGPS_TRY(tmp.get(h, &t.gat[q], size_t(t.nBoxTiles) + 1));
-            }
-            MGPS_LAUNCH(h, launchBandBoxesCount(nullptr, b.d, b.lab(), t.mask, t.prefix, t.tileStart, t.bandEntry, t.extDiag, depth, t.boxTiles, t.nBoxTiles, t.gcount,
-                                                flags + fBoxes + l, &t.win));
-            for (int q = 0; q < 3; ++q) MGPS_LAUNCH(h, launchExclusiveScan(nullptr, t.gcount[q], t.gat[q], size_t(t.nBoxTiles), t.scan));
+            if (T[size_t(l)].nband == 0) continue;
+            MGPS_TRY(boxCounts(h, tmp, T[size_t(l)], depth, flags + fBoxes + l));
         }
         // lists of the owned planes
-        for (int l = 0; l < D; ++l) {
-            DevLevel &L = h->lv[size_t(l)];
-            LevelTmp &t = T[size_t(l)];
-            const Buf &b = B[size_t(l)];
-            int rc4[4] = {0, 0, 0, 0};
-            MGPS_HIP(h, hipMemcpy(rc4, t.runCounts, sizeof(rc4), hipMemcpyDeviceToHost));
-            const int64_t rc64[4] = {rc4[0], rc4[1], rc4[2], rc4[3]};
-            const int runCells = chooseRunCells(rc64);
-            const size_t nruns = (t.nfine + size_t(runCells / kSegCells) - 1) / size_t(runCells / kSegCells);
-            uint8_t *runFlags = t.chunkFlags;
-            if (runCells != kSegCells) {
-                MGPS_TRY(tmp.get(h, &runFlags, nruns));
-                MGPS_LAUNCH(h, launchFoldRunFlags(nullptr, t.chunkFlags, t.nfine, runCells, runFlags));
-            }
-            int activeRuns = 0;
-            for (int z = 0; z < 4; ++z)
-                if (kRunSizes[z] == runCells) activeRuns = rc4[z];
-            const int perGroup = kChunkCells / runCells, listLen = (activeRuns + perGroup - 1) / perGroup * perGroup;
-            {
-                int32_t *tmpFlags = nullptr, *rnk = nullptr, *base = nullptr;
-                MGPS_TRY(tmp.get(h, &tmpFlags, nruns));
-                MGPS_TRY(tmp.get(h, &rnk, nruns + 1));
-                MGPS_TRY(tmp.get(h, &base, 1));
-                MGPS_TRY(devAlloc(h, &L.chunks, size_t(listLen), false));
-                MGPS_LAUNCH(h, launchRunList(nullptr, b.own, runFlags, nruns, runCells, tmpFlags, rnk, t.scan, base, L.chunks, listLen));
-            }
-            MGPS_TRY(tmp.get(h, &t.listCounts, 5));
-            MGPS_HIP(h, hipMemsetAsync(t.listCounts, 0, 5 * sizeof(int32_t), nullptr));
-            {
-                const int tileOff = (b.elo / kTile) * t.tx * t.ty, ntOwn = t.tx * t.ty * ((b.own.nz + kTile - 1) / kTile);
-                const int tkOffset = ((z0 >> l) / kTile) & 1;  // (tile colours are the whole grid's; with Gauss-Seidel the cuts are multiples of 16 planes)
-                int32_t **cls[4] = {&L.pure[0], &L.pure[1], &L.mixed[0], &L.mixed[1]};
-                for (int q = 0; q < 4; ++q) {
-                    MGPS_TRY(devAlloc(h, cls[q], size_t(ntOwn) / 2 + 1, false));
-                    MGPS_LAUNCH(h, launchTileClassList(nullptr, b.own, t.tileKind + tileOff, q & 1, q >> 1, t.tileFlags, t.tileRank, *cls[q], t.scan, tkOffset));
-                    MGPS_HIP(h, hipMemcpyAsync(t.listCounts + q, t.tileRank + ntOwn, sizeof(int32_t), hipMemcpyDeviceToDevice, nullptr));
-                }
-                if (t.nplane) {
-                    int32_t *pf = nullptr, *pr = nullptr;
-                    MGPS_TRY(tmp.get(h, &pf, t.nplane));
-                    MGPS_TRY(tmp.get(h, &pr, t.nplane + 1));
-                    MGPS_TRY(devAlloc(h, &L.planeBlocks, t.nplane, false));
-                    MGPS_LAUNCH(h, launchByteList(nullptr, t.planeFlags, int(t.nplane), pf, pr, L.planeBlocks, t.scan));
-                    MGPS_HIP(h, hipMemcpyAsync(t.listCounts + 4, pr + t.nplane, sizeof(int32_t), hipMemcpyDeviceToDevice, nullptr));
-                }
-            }
-            t.runCells = runCells;
-            t.listLen = listLen;
-            if (l > 0) {
-                MGPS_TRY(gridAlloc(h, &L.x, L.d));
-                MGPS_TRY(gridAlloc(h, &L.b, L.d));
-            }
-            MGPS_TRY(gridAlloc(h, &L.r, L.d));
-            MGPS_TRY(gridAlloc(h, &L.tmp, L.d));
-        }
-        for (int l = 0; l < D; ++l) {
-            DevLevel &L = h->lv[size_t(l)];
-            LevelTmp &t = T[size_t(l)];
-            int32_t counts[5] = {0, 0, 0, 0, 0};
-            MGPS_HIP(h, hipMemcpy(counts, t.listCounts, sizeof(counts), hipMemcpyDeviceToHost));
-            L.npure[0] = counts[0];
-            L.npure[1] = counts[1];
-            L.nmixed[0] = counts[2];
-            L.nmixed[1] = counts[3];
-            t.nplaneBlocks = counts[4];
-        }
+        for (int l = 0; l < D; ++l) MGPS_TRY(levelLists(h, tmp, T[size_t(l)], h->lv[size_t(l)], l));
+        for (int l = 0; l < D; ++l) MGPS_TRY(listCounts(h, T[size_t(l)], h->lv[size_t(l)]));
         sclock.lap("slab: own lists");
         // boxes: arrays
         for (int l = 0; l < D; ++l) {
             DevLevel &L = h->lv[size_t(l)];
-            LevelTmp &t = T[size_t(l)];
-            const Buf &b = B[size_t(l)];
-            if (!boxesOk[size_t(l)] || t.nbandExt == 0) continue;
+            LevelBuild &t = T[size_t(l)];
+            if (!boxesOk[size_t(l)] || t.nband == 0) continue;
             int tot[3] = {0, 0, 0}, brokenL = 0;
-            for (int q = 0; q < 3; ++q) MGPS_HIP(h, hipMemcpy(&tot[q], t.gat[q] + t.nBoxTiles, sizeof(int), hipMemcpyDeviceToHost));
-            MGPS_HIP(h, hipMemcpy(&brokenL, flags + fBoxes + l, sizeof(int), hipMemcpyDeviceToHost));
+            MGPS_TRY(boxTotals(h, t, flags + fBoxes + l, tot, &brokenL));
             if (brokenL) {
                 boxesOk[size_t(l)] = 0;
                 continue;
             }
-            L.bandBoxes.depth = depth;
-            L.bandBoxes.ngroups = tot[0];
-            L.bandBoxes.listCount = size_t(tot[1]);
-            L.bandBoxes.generalInts = 2 * size_t(tot[2]);
-            L.bandBoxes.anyGeneral = tot[2] > 0;
+            MGPS_TRY(boxFill(h, t, L, depth, tot, flags + fBoxes + l));
             if (tot[0] == 0) continue;  // (no band-closure cell in the rank's planes)
-            MGPS_TRY(devAlloc(h, &L.bandBoxes.info, size_t(kBoxInfoInts) * size_t(tot[0]), false));
-            MGPS_TRY(devAlloc(h, &L.bandBoxes.list, size_t(tot[1]), false));
-            MGPS_TRY(devAlloc(h, &L.bandBoxes.general, 2 * size_t(tot[2]), false));
-            MGPS_LAUNCH(h, launchBandBoxesFill(nullptr, b.d, b.lab(), t.mask, t.prefix, t.tileStart, t.bandEntry, t.extDiag, depth, t.boxTiles, t.nBoxTiles, t.gat, L.bandBoxes.info,
-                                               L.bandBoxes.list, L.bandBoxes.general, flags + fBoxes + l, &t.win));
-            MGPS_TRY(finishBandBoxes(h, L, nullptr, &b.d));
             // cells as offsets from owned cell 0 (a region below the owned planes starts at a negative one)
-            MGPS_LAUNCH(h, launchRebaseBoxes(nullptr, L.bandBoxes.info, L.bandBoxes.ngroups, int32_t(size_t(b.elo) * size_t(b.d.nx) * b.d.ny)));
+            MGPS_LAUNCH(h, launchRebaseBoxes(nullptr, L.bandBoxes.info, L.bandBoxes.ngroups, int32_t(size_t(t.window.own0) * size_t(t.d.nx) * t.d.ny)));
             MGPS_HIP(h, hipMemcpy(&brokenL, flags + fBoxes + l, sizeof(int), hipMemcpyDeviceToHost));
             if (brokenL) boxesOk[size_t(l)] = 0;
         }
@@ -3831,14 +3723,9 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
     }();
     // ---- every rank takes the same form of the band stage on a level; every rank knows whether all are still fine
     {
-        std::vector<double> v(size_t(D) + 1, 0.0);
+        std::vector<double> v(size_t(D), 0.0);
         for (int l = 0; l < D; ++l) v[size_t(l)] = boxesOk[size_t(l)] ? 0.0 : 1.0;
-        v[size_t(D)] = double(status);
-        if (h->comm.allreduce(h->comm.user, v.data(), int(v.size()), 1) != 0) return bail(failH(h, MGPS_ERR_COMM, "all-reduce failed during set-up"));
-        if (int(v[size_t(D)]) != MGPS_OK) {
-            if (status == MGPS_OK) failH(h, int(v[size_t(D)]), "slab set-up failed on another rank");
-            return bail(status != MGPS_OK ? status : int(v[size_t(D)]));
-        }
+        if (int rc = agreeSlab(h, status, v.data(), D); rc != MGPS_OK) return bail(rc);
         for (int l = 0; l < D; ++l) h->lv[size_t(l)].boxForm = v[size_t(l)] == 0.0;
     }
     // ---- level descriptions; the cells the neighbours' planes must deliver; the index lists traded
@@ -3858,7 +3745,7 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         std::vector<int32_t> hc(size_t(4 * D), 0);
         for (int l = 0; l < D; ++l) {
             DevLevel &L = h->lv[size_t(l)];
-            LevelTmp &t = T[size_t(l)];
+            const LevelBuild &t = T[size_t(l)];
             const Buf &b = B[size_t(l)];
             const size_t plane = size_t(b.d.nx) * b.d.ny;
             keepBuffer(l);  // (the label buffer is the level's codes from here on)
@@ -3868,7 +3755,7 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
             L.g.ghostHi = hi ? 1 : 0;
             L.gBox = L.g;
             L.gBox.rows = L.extRows;
-            L.gBox.nbnd = t.nGenExt;
+            L.gBox.nbnd = t.nGen;
             if (!L.boxForm) {  // (per-pass band smoothing on this level: no boxes kept)
                 (void)cacheFree(L.bandBoxes.info);
                 (void)cacheFree(L.bandBoxes.list);
@@ -3918,15 +3805,7 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         MGPS_HIP(h, hipMemcpy(countsDev, hc.data(), hc.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         return MGPS_OK;
     }();
-    {
-        int all = MGPS_OK;
-        const int rc = agree(status, &all);
-        if (rc != MGPS_OK) return bail(rc);
-        if (all != MGPS_OK) {
-            if (status == MGPS_OK) failH(h, all, "slab set-up failed on another rank");
-            return bail(status != MGPS_OK ? status : all);
-        }
-    }
+    if (int rc = agreeSlab(h, status); rc != MGPS_OK) return bail(rc);
     // counts first (one int per level and side), then the lists
     std::vector<int32_t> hc(size_t(4 * D), 0);
     for (int l = 0; l < D && P > 1; ++l) {
@@ -3961,15 +3840,7 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         MGPS_HIP(h, hipDeviceSynchronize());
         return MGPS_OK;
     }();
-    {
-        int all = MGPS_OK;
-        const int rc = agree(status, &all);
-        if (rc != MGPS_OK) return bail(rc);
-        if (all != MGPS_OK) {
-            if (status == MGPS_OK) failH(h, all, "slab set-up failed on another rank");
-            return bail(status != MGPS_OK ? status : all);
-        }
-    }
+    if (int rc = agreeSlab(h, status); rc != MGPS_OK) return bail(rc);
     for (int l = 0; l < D && P > 1; ++l) {
         DevLevel &L = h->lv[size_t(l)];
         if (!L.boxForm) continue;
@@ -4002,32 +3873,15 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
             const size_t nfine = (b.own.cells() + kSegCells - 1) / kSegCells;
             uint8_t *cf = nullptr;
             int *rcnt = nullptr;
+            int32_t *scan = nullptr;
             MGPS_TRY(tmp.get(h, &cf, nfine));
             MGPS_TRY(tmp.get(h, &rcnt, 4));
             MGPS_HIP(h, hipMemsetAsync(rcnt, 0, 4 * sizeof(int), nullptr));
             MGPS_LAUNCH(h, launchActivityFlags(nullptr, b.own, b.owned(), cf, nullptr, 0));
             MGPS_LAUNCH(h, launchCountRuns(nullptr, cf, nfine, rcnt));
-            int rc4[4] = {0, 0, 0, 0};
-            MGPS_HIP(h, hipMemcpy(rc4, rcnt, sizeof(rc4), hipMemcpyDeviceToHost));
-            const int64_t rc64[4] = {rc4[0], rc4[1], rc4[2], rc4[3]};
-            const int runCells = chooseRunCells(rc64);
-            const size_t nruns = (nfine + size_t(runCells / kSegCells) - 1) / size_t(runCells / kSegCells);
-            uint8_t *runFlags = cf;
-            if (runCells != kSegCells) {
-                MGPS_TRY(tmp.get(h, &runFlags, nruns));
-                MGPS_LAUNCH(h, launchFoldRunFlags(nullptr, cf, nfine, runCells, runFlags));
-            }
-            int activeRuns = 0;
-            for (int z = 0; z < 4; ++z)
-                if (kRunSizes[z] == runCells) activeRuns = rc4[z];
-            const int perGroup = kChunkCells / runCells, listLen = (activeRuns + perGroup - 1) / perGroup * perGroup;
-            int32_t *tmpFlags = nullptr, *rnk = nullptr, *base = nullptr, *scan = nullptr;
-            MGPS_TRY(tmp.get(h, &tmpFlags, nruns));
-            MGPS_TRY(tmp.get(h, &rnk, nruns + 1));
-            MGPS_TRY(tmp.get(h, &base, 1));
             MGPS_TRY(tmp.get(h, &scan, scanScratchInts(b.d.cells())));
-            MGPS_TRY(devAlloc(h, &C.chunks, size_t(listLen), false));
-            MGPS_LAUNCH(h, launchRunList(nullptr, b.own, runFlags, nruns, runCells, tmpFlags, rnk, scan, base, C.chunks, listLen));
+            int runCells = 0, listLen = 0;
+            MGPS_TRY(runList(h, tmp, b.own, cf, nfine, rcnt, scan, &C.chunks, &runCells, &listLen));
             MGPS_TRY(gridAlloc(h, &C.x, C.d));
             MGPS_TRY(gridAlloc(h, &C.b, C.d));
             keepBuffer(D);
@@ -4041,15 +3895,7 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
     }();
     sclock.lap("slab: halo lists + collapse level");
     if (status == MGPS_OK) status = commonDeviceState(h, false);
-    {
-        int all = MGPS_OK;
-        const int rc = agree(status, &all);
-        if (rc != MGPS_OK) return bail(rc);
-        if (all != MGPS_OK) {
-            if (status == MGPS_OK) failH(h, all, "slab set-up failed on another rank");
-            return bail(status != MGPS_OK ? status : all);
-        }
-    }
+    if (int rc = agreeSlab(h, status); rc != MGPS_OK) return bail(rc);
     // ---- the collapsed tail on rank 0: the collapse level's labels of all ranks, then the whole-grid builder
     int tailRc = MGPS_OK;
     {
@@ -4232,14 +4078,8 @@ int createSlabImpl(mgps_solver **out, int nx, int ny, int nz_global, const uint8
         else if (violations != 0)
             rowsRc = failH(h, MGPS_ERR_HIERARCHY, "labels/weights violate the BOUNDARY-cell rules (unitTestBoundaryCells): run mgps_fields_set_boundary_labels");
     }
-    {  // every rank leaves together: one with bad labels or weights must not leave the others waiting in the collectives below
-        double v = double(rowsRc);
-        if (h->comm.allreduce(h->comm.user, &v, 1, 1) != 0) return bail(failH(h, MGPS_ERR_COMM, "all-reduce failed during set-up"));
-        if (int(v) != MGPS_OK) {
-            if (rowsRc == MGPS_OK) failH(h, int(v), "slab set-up failed on another rank");
-            return bail(rowsRc != MGPS_OK ? rowsRc : int(v));
-        }
-    }
+    // every rank leaves together: one with bad labels or weights must not leave the others waiting in the collectives below
+    if (int rc = agreeSlab(h, rowsRc); rc != MGPS_OK) return bail(rc);
     sclock.lap("slab: fine rows");
     h->lv.resize(D + 1);
     for (int l = 0; l <= D; ++l) {
