@@ -510,14 +510,46 @@ int launchBandBoxesFill(void *stream, const Dims &d, const uint8_t *lab, const u
 // ranked by their minimum cell index), ascending inside a group; *offsets: m + 1 entries.  Both are deviceAlloc blocks of the caller
 int enclosedComponentsDevice(void *stream, const Dims &d, const uint8_t *codes, const float *wx, const float *wy, const float *wz, int32_t **cells,
                              int32_t **offsets, int64_t *m, int64_t *cellCount);
-// P v for those components (mgps_kernels.hip): chunks = 3 ints per chunk of at most kEncChunkCells cells of one component (component,
-// first entry, end entry), compChunk = m + 1 entries (each component's first chunk); partials: one double per chunk, mean: m doubles.
-// v[c] -= mean of v over c's component on the listed cells, sums in fp64 in a fixed order
+// The same on a slab rank, in three phases around the transport (the solver runs the collectives between them, csrc/mgps_solver.hip
+// setupEnclosedSlab).  d: the owned planes; ids are global (local index + base, base = z0 nx ny).  labLo / labHi: the label planes
+// just below / above the owned ones (nullptr = no neighbour there), read with the cut faces' weights (planes 0 and d.nz of wz).
+struct EncSlab {
+    Dims d;
+    int32_t base = 0;
+    int32_t *parent = nullptr, *flag = nullptr, *pos = nullptr, *rootRank = nullptr, *scan = nullptr;
+    uint8_t *open = nullptr, *touch = nullptr;
+    int32_t *sendRoots = nullptr, *recvRoots = nullptr;  // a plane of ints each: the global roots of plane 0 / of the plane above
+    unsigned long long *keys = nullptr, *keysSorted = nullptr;
+    void *sortTemp = nullptr;
+    size_t sortBytes = 0;
+    int32_t *payload = nullptr;  // candidates: ids, open flags; then pairs: own roots, roots above (ncand, ncand, npairs, npairs ints)
+    int32_t *candLocal = nullptr;
+    int *bad = nullptr;
+    int64_t ncand = 0, npairs = 0;
+};
+// label the owned planes, flag the roots that are open or couple across a cut, sendRoots = plane 0's global roots (-1: inactive)
+int encSlabLabel(void *stream, EncSlab &st, const uint8_t *codes, const float *wx, const float *wy, const float *wz, const uint8_t *labLo,
+                 const uint8_t *labHi);
+// after recvRoots arrived (hiFirst..hiFirst + plane - 1: the ids the rank above may send; labHi nullptr = no rank above): the
+// distinct pairs of coupled roots across the upper cut and the candidates (local roots that are closed or couple across a cut),
+// packed into payload; *bad = 1 when a received id is out of range or disagrees with the labels
+int encSlabCandidates(void *stream, EncSlab &st, const uint8_t *codes, const uint8_t *labHi, const float *wz, int32_t hiFirst, int *badHost);
+// after the merge: grank = a global rank or -1 per candidate (m global components): cells / offsets as enclosedComponentsDevice
+// (offsets: m + 1 entries; a component without a cell on this rank has an empty range), *cellCount = the rank's cells
+int encSlabLists(void *stream, EncSlab &st, const int32_t *grank, int64_t m, int32_t **cells, int32_t **offsets, int64_t *cellCount);
+void encSlabRelease(EncSlab &st);
+// P v for those components (mgps_kernels.hip), in two halves: chunks = 3 ints per chunk of at most kEncChunkCells cells of one
+// component (component, first entry, end entry), compChunk = m + 1 entries (each component's first chunk); partials: one double per
+// chunk.  Sums: sum[r] = the sum of v over the listed cells of component r (0 without a chunk), in fp64 in a fixed order.
+// Subtract: v[c] -= sum[r] / count[r] on the listed cells (count: the component's cells; a slab run sums `sum` over the ranks first
+// and passes the global counts)
 constexpr int kEncChunkCells = 4096;
-int launchEnclosedProject(void *stream, float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, const int32_t *offsets,
-                          int64_t m, double *partials, double *mean);
-int launchEnclosedProject64(void *stream, double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk,
-                            const int32_t *offsets, int64_t m, double *partials, double *mean);
+int launchEnclosedSums(void *stream, const float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, int64_t m,
+                       double *partials, double *sum);
+int launchEnclosedSums64(void *stream, const double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, int64_t m,
+                         double *partials, double *sum);
+int launchEnclosedSubtract(void *stream, float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *count, const double *sum);
+int launchEnclosedSubtract64(void *stream, double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *count, const double *sum);
 // rank[c] = r on the cells of component r (rank filled with -1 by the caller)
 int launchEnclosedRanks(void *stream, int32_t *rank, const int32_t *cells, const int32_t *chunks, int nchunks);
 int launchWidenAdd(void *stream, double *x64, const float *x32, size_t n);  // x64 += x32 (the pending fp32 updates of the fp64-iterate loop)

@@ -3890,7 +3890,8 @@ int launchReduce(void *stream, int kind, const GridP &g, const float *a, const f
 // ---- options.enclosed_liquid: v -= mean over each enclosed component ---------------------------------------------------
 // Fixed order everywhere (same input, same bits): a workgroup per chunk of at most kEncChunkCells cells of one component sums
 // its cells thread by thread in list order and folds the 256 sums as a tree; a workgroup per component folds its chunk partials
-// the same way; the subtract pass reads the mean in fp64.  No atomics.
+// the same way (0 for a component without a chunk: a slab rank that holds none of its cells); the subtract pass divides the sum
+// by the component's cell count and subtracts in fp64.  Between the two a slab run sums the m sums over the ranks.  No atomics.
 namespace {
 template <class T>
 __global__ __launch_bounds__(256) void encChunkSumKernel(const T *__restrict__ v, const int32_t *__restrict__ cells, const int32_t *__restrict__ chunks,
@@ -3909,8 +3910,7 @@ __global__ __launch_bounds__(256) void encChunkSumKernel(const T *__restrict__ v
     }
     if (threadIdx.x == 0) partials[q] = red[0];
 }
-__global__ __launch_bounds__(256) void encMeanKernel(const double *__restrict__ partials, const int32_t *__restrict__ compChunk,
-                                                     const int32_t *__restrict__ offsets, double *__restrict__ mean)
+__global__ __launch_bounds__(256) void encSumKernel(const double *__restrict__ partials, const int32_t *__restrict__ compChunk, double *__restrict__ sum)
 {
     __shared__ double red[256];
     const int r = blockIdx.x;
@@ -3922,14 +3922,15 @@ __global__ __launch_bounds__(256) void encMeanKernel(const double *__restrict__ 
         if (int(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) mean[r] = red[0] / double(offsets[r + 1] - offsets[r]);
+    if (threadIdx.x == 0) sum[r] = red[0];
 }
 template <class T>
 __global__ __launch_bounds__(256) void encSubtractKernel(T *__restrict__ v, const int32_t *__restrict__ cells, const int32_t *__restrict__ chunks,
-                                                        const double *__restrict__ mean)
+                                                        const int32_t *__restrict__ count, const double *__restrict__ sum)
 {
     const int q = blockIdx.x;
-    const double mu = mean[chunks[3 * q]];
+    const int32_t r = chunks[3 * q];
+    const double mu = sum[r] / double(count[r]);
     const int32_t e0 = chunks[3 * q + 1], e1 = chunks[3 * q + 2];
     for (int32_t e = e0 + int32_t(threadIdx.x); e < e1; e += 256) {
         const int32_t c = cells[e];
@@ -3943,27 +3944,40 @@ __global__ __launch_bounds__(256) void encRankKernel(int32_t *__restrict__ rank,
     for (int32_t e = e0 + int32_t(threadIdx.x); e < e1; e += 256) rank[cells[e]] = r;
 }
 template <class T>
-int enclosedProject(void *stream, T *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, const int32_t *offsets, int64_t m,
-                    double *partials, double *mean)
+int enclosedSums(void *stream, const T *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, int64_t m, double *partials,
+                 double *sum)
 {
-    if (m <= 0 || nchunks <= 0) return 0;
+    if (m <= 0) return 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    encChunkSumKernel<T><<<unsigned(nchunks), 256, 0, s>>>(v, cells, chunks, partials);
-    encMeanKernel<<<unsigned(m), 256, 0, s>>>(partials, compChunk, offsets, mean);
-    encSubtractKernel<T><<<unsigned(nchunks), 256, 0, s>>>(v, cells, chunks, mean);
+    if (nchunks > 0) encChunkSumKernel<T><<<unsigned(nchunks), 256, 0, s>>>(v, cells, chunks, partials);
+    encSumKernel<<<unsigned(m), 256, 0, s>>>(partials, compChunk, sum);
+    return int(hipGetLastError());
+}
+template <class T>
+int enclosedSubtract(void *stream, T *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *count, const double *sum)
+{
+    if (nchunks > 0) encSubtractKernel<T><<<unsigned(nchunks), 256, 0, static_cast<hipStream_t>(stream)>>>(v, cells, chunks, count, sum);
     return int(hipGetLastError());
 }
 }  // namespace
 
-int launchEnclosedProject(void *stream, float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, const int32_t *offsets,
-                          int64_t m, double *partials, double *mean)
+int launchEnclosedSums(void *stream, const float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, int64_t m,
+                       double *partials, double *sum)
 {
-    return enclosedProject(stream, v, cells, chunks, nchunks, compChunk, offsets, m, partials, mean);
+    return enclosedSums(stream, v, cells, chunks, nchunks, compChunk, m, partials, sum);
 }
-int launchEnclosedProject64(void *stream, double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk,
-                            const int32_t *offsets, int64_t m, double *partials, double *mean)
+int launchEnclosedSums64(void *stream, const double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *compChunk, int64_t m,
+                         double *partials, double *sum)
 {
-    return enclosedProject(stream, v, cells, chunks, nchunks, compChunk, offsets, m, partials, mean);
+    return enclosedSums(stream, v, cells, chunks, nchunks, compChunk, m, partials, sum);
+}
+int launchEnclosedSubtract(void *stream, float *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *count, const double *sum)
+{
+    return enclosedSubtract(stream, v, cells, chunks, nchunks, count, sum);
+}
+int launchEnclosedSubtract64(void *stream, double *v, const int32_t *cells, const int32_t *chunks, int nchunks, const int32_t *count, const double *sum)
+{
+    return enclosedSubtract(stream, v, cells, chunks, nchunks, count, sum);
 }
 namespace {
 __global__ __launch_bounds__(256) void widenAddKernel(double *__restrict__ x64, const float *__restrict__ x32, size_t n)

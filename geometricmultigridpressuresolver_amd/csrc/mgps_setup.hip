@@ -1670,9 +1670,12 @@ __global__ __launch_bounds__(256) void encHookKernel(Dims d, const uint8_t *__re
         encUnite(parent, int32_t(c), int32_t(c + plane));
 }
 
-// parent = root on every active cell; open[root] = 1 where a BOUNDARY cell has a DIRICHLET neighbour behind a face of weight > 0
+// parent = root on every active cell; open[root] = 1 where a BOUNDARY cell has a DIRICHLET neighbour behind a face of weight > 0.
+// A slab rank passes the label planes next to its owned ones (labLo / labHi, nullptr = none) with the cut faces' weights in planes 0
+// and d.nz of wz: the open test also looks across a cut, and touch[root] = 1 where a cell couples to a cell across one
 __global__ __launch_bounds__(256) void encCompressKernel(Dims d, const uint8_t *__restrict__ lab, const float *__restrict__ wx, const float *__restrict__ wy,
-                                                         const float *__restrict__ wz, int32_t *__restrict__ parent, uint8_t *__restrict__ open)
+                                                         const float *__restrict__ wz, int32_t *__restrict__ parent, uint8_t *__restrict__ open,
+                                                         const uint8_t *__restrict__ labLo, const uint8_t *__restrict__ labHi, uint8_t *__restrict__ touch)
 {
     const size_t n = cellCount(d);
     const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
@@ -1681,10 +1684,12 @@ __global__ __launch_bounds__(256) void encCompressKernel(Dims d, const uint8_t *
     if (!activeCode(l)) return;
     const int32_t root = encFind(parent, int32_t(c));
     parent[c] = root;
-    if (l < MGPS_BOUNDARY_CELL) return;
     const int i = int(c % size_t(d.nx)), j = int((c / size_t(d.nx)) % size_t(d.ny)), k = int(c / (size_t(d.nx) * d.ny));
     const size_t plane = size_t(d.nx) * d.ny;
     const size_t fx = (size_t(k) * d.ny + j) * size_t(d.nx + 1) + i, fy = (size_t(k) * (d.ny + 1) + j) * d.nx + i, fz = (size_t(k) * d.ny + j) * d.nx + i;
+    const unsigned below = k == 0 && labLo ? labLo[fz] : MGPS_EXTERIOR_CELL, above = k + 1 == d.nz && labHi ? labHi[size_t(j) * d.nx + i] : MGPS_EXTERIOR_CELL;
+    if (touch && (encCoupled(l, below, wz[fz]) || encCoupled(l, above, wz[fz + plane]))) touch[root] = 1;
+    if (l < MGPS_BOUNDARY_CELL) return;
     bool o = false;
     o = o || (i > 0 && lab[c - 1] == MGPS_DIRICHLET_CELL && wx[fx] > 0.f);
     o = o || (i + 1 < d.nx && lab[c + 1] == MGPS_DIRICHLET_CELL && wx[fx + 1] > 0.f);
@@ -1692,6 +1697,7 @@ __global__ __launch_bounds__(256) void encCompressKernel(Dims d, const uint8_t *
     o = o || (j + 1 < d.ny && lab[c + d.nx] == MGPS_DIRICHLET_CELL && wy[fy + d.nx] > 0.f);
     o = o || (k > 0 && lab[c - plane] == MGPS_DIRICHLET_CELL && wz[fz] > 0.f);
     o = o || (k + 1 < d.nz && lab[c + plane] == MGPS_DIRICHLET_CELL && wz[fz + plane] > 0.f);
+    o = o || (below == MGPS_DIRICHLET_CELL && wz[fz] > 0.f) || (above == MGPS_DIRICHLET_CELL && wz[fz + plane] > 0.f);
     if (o) open[root] = 1;
 }
 
@@ -1778,7 +1784,7 @@ int enclosedComponentsDevice(void *stream, const Dims &d, const uint8_t *codes, 
     if (!e) {
         encInitKernel<<<nb, 256, 0, s>>>(d, codes, wx, parent);
         encHookKernel<<<nb, 256, 0, s>>>(d, codes, wx, wy, wz, parent);
-        encCompressKernel<<<nb, 256, 0, s>>>(d, codes, wx, wy, wz, parent, open);
+        encCompressKernel<<<nb, 256, 0, s>>>(d, codes, wx, wy, wz, parent, open, nullptr, nullptr, nullptr);
         encRootKernel<<<nb, 256, 0, s>>>(n, parent, open, nullptr, count);  // (the counts only: with m = 0 that is all)
         e = int(hipGetLastError());
     }
@@ -1835,6 +1841,247 @@ int enclosedComponentsDevice(void *stream, const Dims &d, const uint8_t *codes, 
     *offsetsOut = offsets;
     *mOut = m;
     *cellsCount = ne;
+    return 0;
+}
+
+
+// ---- options.enclosed_liquid on a slab rank (setupEnclosedSlab in mgps_solver.hip runs the collectives between the phases) -------
+namespace {
+// out[q] = the global root of plane 0's cell q, -1 on inactive cells
+__global__ __launch_bounds__(256) void encPlaneRootsKernel(size_t plane, const int32_t *__restrict__ parent, int32_t base, int32_t *__restrict__ out)
+{
+    const size_t q = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (q >= plane) return;
+    const int32_t p = parent[q];
+    out[q] = p >= 0 ? p + base : -1;
+}
+// one key per cell of the top plane: (own global root, root above) where the two cells couple across the cut face, ~0 elsewhere.
+// An id above outside [hiFirst, hiFirst + plane) -- a root of a cell on the plane above is at most that cell's id -- or a cell
+// the labels call coupled that the rank above reports inactive sets *bad
+__global__ __launch_bounds__(256) void encCutPairsKernel(Dims d, const uint8_t *__restrict__ lab, const uint8_t *__restrict__ labHi, const float *__restrict__ wz,
+                                                         const int32_t *__restrict__ parent, const int32_t *__restrict__ above, int32_t base, int32_t hiFirst,
+                                                         unsigned long long *__restrict__ keys, int *__restrict__ bad)
+{
+    const size_t plane = size_t(d.nx) * d.ny;
+    const size_t q = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (q >= plane) return;
+    const size_t c = size_t(d.nz - 1) * plane + q;
+    const int32_t b = above[q];
+    unsigned long long key = ~0ull;
+    if (b != -1 && (b < hiFirst || int64_t(b) >= int64_t(hiFirst) + int64_t(plane))) *bad = 1;
+    else if (encCoupled(lab[c], labHi[q], wz[size_t(d.nz) * plane + q])) {
+        if (b < 0 || parent[c] < 0) *bad = 1;
+        else key = (static_cast<unsigned long long>(uint32_t(parent[c] + base)) << 32) | uint32_t(b);
+    }
+    keys[q] = key;
+}
+// flag[t] = 1 on the first of each run of equal sorted keys (~0: no pair)
+__global__ __launch_bounds__(256) void encUniqueFlagKernel(size_t n, const unsigned long long *__restrict__ keys, int32_t *__restrict__ flag)
+{
+    const size_t t = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (t >= n) return;
+    flag[t] = keys[t] != ~0ull && (t == 0 || keys[t] != keys[t - 1]) ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void encPairsCompactKernel(size_t n, const unsigned long long *__restrict__ keys, const int32_t *__restrict__ flag,
+                                                             const int32_t *__restrict__ pos, int32_t *__restrict__ a, int32_t *__restrict__ b)
+{
+    const size_t t = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (t >= n || !flag[t]) return;
+    a[pos[t]] = int32_t(keys[t] >> 32);
+    b[pos[t]] = int32_t(keys[t] & 0xffffffffull);
+}
+// candidates: local roots of closed pieces or of pieces that couple across a cut
+__global__ __launch_bounds__(256) void encCandFlagKernel(size_t n, const int32_t *__restrict__ parent, const uint8_t *__restrict__ open,
+                                                         const uint8_t *__restrict__ touch, int32_t *__restrict__ flag)
+{
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (c >= n) return;
+    flag[c] = parent[c] == int32_t(c) && (!open[c] || touch[c]) ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void encCandCompactKernel(size_t n, const int32_t *__restrict__ flag, const int32_t *__restrict__ pos, const uint8_t *__restrict__ open,
+                                                            int32_t base, int64_t ncand, int32_t *__restrict__ payload, int32_t *__restrict__ local)
+{
+    const size_t c = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
+    if (c >= n || !flag[c]) return;
+    payload[pos[c]] = int32_t(c) + base;
+    payload[ncand + pos[c]] = open[c];
+    local[pos[c]] = int32_t(c);
+}
+// the merge's verdict on each candidate: rootRank[root] = its global rank, open[root] = 0 on the roots of enclosed components only
+__global__ __launch_bounds__(256) void encApplyRanksKernel(int64_t ncand, const int32_t *__restrict__ local, const int32_t *__restrict__ grank,
+                                                           int32_t *__restrict__ rootRank, uint8_t *__restrict__ open)
+{
+    const int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (t >= ncand) return;
+    rootRank[local[t]] = grank[t];
+    open[local[t]] = grank[t] < 0 ? 1 : 0;
+}
+// offsets[r] = the first sorted entry with a key >= r, r = 0 .. m (a rank without a cell here gets an empty range)
+__global__ __launch_bounds__(256) void encLowerBoundKernel(int64_t e, int64_t m, const int32_t *__restrict__ key, int32_t *__restrict__ offsets)
+{
+    const int64_t r = blockIdx.x * int64_t(blockDim.x) + threadIdx.x;
+    if (r > m) return;
+    int64_t lo = 0, hi = e;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) / 2;
+        if (key[mid] < r) lo = mid + 1;
+        else hi = mid;
+    }
+    offsets[r] = int32_t(lo);
+}
+}  // namespace
+
+void encSlabRelease(EncSlab &st)
+{
+    (void)hipDeviceSynchronize();
+    for (void *p : {(void *)st.parent, (void *)st.flag, (void *)st.pos, (void *)st.rootRank, (void *)st.scan, (void *)st.open, (void *)st.touch, (void *)st.sendRoots,
+                    (void *)st.recvRoots, (void *)st.keys, (void *)st.keysSorted, st.sortTemp, (void *)st.payload, (void *)st.candLocal, (void *)st.bad})
+        (void)deviceFree(p);
+    const Dims d = st.d;
+    const int32_t base = st.base;
+    st = EncSlab{};
+    st.d = d;
+    st.base = base;
+}
+
+int encSlabLabel(void *stream, EncSlab &st, const uint8_t *codes, const float *wx, const float *wy, const float *wz, const uint8_t *labLo, const uint8_t *labHi)
+{
+    hipStream_t s = S(stream);
+    const size_t n = st.d.cells(), plane = size_t(st.d.nx) * st.d.ny;
+    int e = encAlloc(&st.parent, n);
+    if (!e) e = encAlloc(&st.open, n);
+    if (!e) e = encAlloc(&st.touch, n);
+    if (!e) e = encAlloc(&st.sendRoots, plane);
+    if (!e) e = encAlloc(&st.recvRoots, plane);
+    if (!e) e = encAlloc(&st.bad, 1);
+    if (!e) e = int(hipMemsetAsync(st.open, 0, n, s));
+    if (!e) e = int(hipMemsetAsync(st.touch, 0, n, s));
+    if (!e) e = int(hipMemsetAsync(st.recvRoots, 0xff, plane * sizeof(int32_t), s));  // (-1: what arrives from no neighbour)
+    if (!e) e = int(hipMemsetAsync(st.bad, 0, sizeof(int), s));
+    if (!e) {
+        const unsigned nb = blocksFor(n, 256);
+        encInitKernel<<<nb, 256, 0, s>>>(st.d, codes, wx, st.parent);
+        encHookKernel<<<nb, 256, 0, s>>>(st.d, codes, wx, wy, wz, st.parent);
+        encCompressKernel<<<nb, 256, 0, s>>>(st.d, codes, wx, wy, wz, st.parent, st.open, labLo, labHi, st.touch);
+        encPlaneRootsKernel<<<blocksFor(plane, 256), 256, 0, s>>>(plane, st.parent, st.base, st.sendRoots);
+        e = int(hipGetLastError());
+    }
+    if (!e) e = int(hipStreamSynchronize(s));
+    return e;
+}
+
+int encSlabCandidates(void *stream, EncSlab &st, const uint8_t *codes, const uint8_t *labHi, const float *wz, int32_t hiFirst, int *badHost)
+{
+    hipStream_t s = S(stream);
+    const size_t n = st.d.cells(), plane = size_t(st.d.nx) * st.d.ny, m = std::max(n, plane);
+    *badHost = 0;
+    int e = encAlloc(&st.flag, m);
+    if (!e) e = encAlloc(&st.pos, m + 1);
+    if (!e) e = encAlloc(&st.scan, scanScratchInts(m));
+    int32_t hc[2] = {0, 0};
+    int32_t *pairA = nullptr, *pairB = nullptr;
+    if (labHi) {  // pairs across the upper cut, sorted and made distinct on the device
+        if (!e) e = encAlloc(&st.keys, plane);
+        if (!e) e = encAlloc(&st.keysSorted, plane);
+        if (!e) {
+            encCutPairsKernel<<<blocksFor(plane, 256), 256, 0, s>>>(st.d, codes, labHi, wz, st.parent, st.recvRoots, st.base, hiFirst, st.keys, st.bad);
+            e = int(hipGetLastError());
+        }
+        if (!e) e = int(rocprim::radix_sort_keys(nullptr, st.sortBytes, st.keys, st.keysSorted, plane, 0u, 64u, s));
+        if (!e) e = deviceAlloc(&st.sortTemp, std::max<size_t>(st.sortBytes, 1));
+        if (!e) e = int(rocprim::radix_sort_keys(st.sortTemp, st.sortBytes, st.keys, st.keysSorted, plane, 0u, 64u, s));
+        if (!e) {
+            encUniqueFlagKernel<<<blocksFor(plane, 256), 256, 0, s>>>(plane, st.keysSorted, st.flag);
+            e = int(hipGetLastError());
+        }
+        if (!e) e = launchExclusiveScan(stream, st.flag, st.pos, plane, st.scan);
+        if (!e) e = int(hipMemcpyAsync(&hc[1], st.pos + plane, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (!e) e = int(hipStreamSynchronize(s));
+        if (!e) e = encAlloc(&pairA, size_t(hc[1]));
+        if (!e) e = encAlloc(&pairB, size_t(hc[1]));
+        if (!e) {
+            encPairsCompactKernel<<<blocksFor(plane, 256), 256, 0, s>>>(plane, st.keysSorted, st.flag, st.pos, pairA, pairB);
+            e = int(hipGetLastError());
+        }
+    }
+    if (!e) {
+        encCandFlagKernel<<<blocksFor(n, 256), 256, 0, s>>>(n, st.parent, st.open, st.touch, st.flag);
+        e = int(hipGetLastError());
+    }
+    if (!e) e = launchExclusiveScan(stream, st.flag, st.pos, n, st.scan);
+    if (!e) e = int(hipMemcpyAsync(&hc[0], st.pos + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (!e) e = int(hipMemcpyAsync(badHost, st.bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (!e) e = int(hipStreamSynchronize(s));
+    st.ncand = hc[0];
+    st.npairs = hc[1];
+    if (!e) e = encAlloc(&st.payload, size_t(2 * st.ncand + 2 * st.npairs));
+    if (!e) e = encAlloc(&st.candLocal, size_t(st.ncand));
+    if (!e) {
+        encCandCompactKernel<<<blocksFor(n, 256), 256, 0, s>>>(n, st.flag, st.pos, st.open, st.base, st.ncand, st.payload, st.candLocal);
+        e = int(hipGetLastError());
+    }
+    if (!e && st.npairs > 0) e = int(hipMemcpyAsync(st.payload + 2 * st.ncand, pairA, size_t(st.npairs) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (!e && st.npairs > 0)
+        e = int(hipMemcpyAsync(st.payload + 2 * st.ncand + st.npairs, pairB, size_t(st.npairs) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    (void)hipStreamSynchronize(s);
+    (void)deviceFree(pairA);
+    (void)deviceFree(pairB);
+    if (!e) e = int(hipGetLastError());
+    return e;
+}
+
+int encSlabLists(void *stream, EncSlab &st, const int32_t *grank, int64_t m, int32_t **cellsOut, int32_t **offsetsOut, int64_t *cellCount)
+{
+    hipStream_t s = S(stream);
+    *cellsOut = *offsetsOut = nullptr;
+    *cellCount = 0;
+    const size_t n = st.d.cells();
+    const unsigned nb = blocksFor(n, 256);
+    int32_t *key = nullptr, *cell = nullptr, *keySorted = nullptr, *cells = nullptr, *offsets = nullptr;
+    void *sortTemp = nullptr;
+    int e = encAlloc(&st.rootRank, n);
+    if (!e && st.ncand > 0) {
+        encApplyRanksKernel<<<blocksFor(size_t(st.ncand), 256), 256, 0, s>>>(st.ncand, st.candLocal, grank, st.rootRank, st.open);
+        e = int(hipGetLastError());
+    }
+    if (!e) {
+        encCellFlagKernel<<<nb, 256, 0, s>>>(n, st.parent, st.open, st.flag);
+        e = int(hipGetLastError());
+    }
+    if (!e) e = launchExclusiveScan(stream, st.flag, st.pos, n, st.scan);
+    int32_t ne = 0;
+    if (!e) e = int(hipMemcpyAsync(&ne, st.pos + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (!e) e = int(hipStreamSynchronize(s));
+    if (!e) e = encAlloc(&key, size_t(ne));
+    if (!e) e = encAlloc(&cell, size_t(ne));
+    if (!e) e = encAlloc(&keySorted, size_t(ne));
+    if (!e) e = encAlloc(&cells, size_t(ne));
+    if (!e) e = encAlloc(&offsets, size_t(m) + 1);
+    if (!e) {
+        encCompactKernel<<<nb, 256, 0, s>>>(n, st.parent, st.open, st.pos, st.rootRank, key, cell);
+        e = int(hipGetLastError());
+    }
+    unsigned endBit = 1;
+    while (endBit < 31 && (int64_t(1) << endBit) < m) ++endBit;
+    size_t tempBytes = 0;
+    if (!e && ne > 0) e = int(rocprim::radix_sort_pairs(nullptr, tempBytes, key, keySorted, cell, cells, size_t(ne), 0u, endBit, s));
+    if (!e && ne > 0) e = deviceAlloc(&sortTemp, std::max<size_t>(tempBytes, 1));
+    if (!e && ne > 0) e = int(rocprim::radix_sort_pairs(sortTemp, tempBytes, key, keySorted, cell, cells, size_t(ne), 0u, endBit, s));
+    if (!e) {
+        encLowerBoundKernel<<<blocksFor(size_t(m) + 1, 256), 256, 0, s>>>(ne, m, keySorted, offsets);
+        e = int(hipGetLastError());
+    }
+    (void)hipStreamSynchronize(s);
+    for (void *p : {(void *)key, (void *)cell, (void *)keySorted, sortTemp}) (void)deviceFree(p);
+    if (!e) e = int(hipGetLastError());
+    if (e) {
+        (void)deviceFree(cells);
+        (void)deviceFree(offsets);
+        return e;
+    }
+    *cellsOut = cells;
+    *offsetsOut = offsets;
+    *cellCount = ne;
     return 0;
 }
 

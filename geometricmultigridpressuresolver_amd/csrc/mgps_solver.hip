@@ -156,13 +156,16 @@ struct mgps_solver {
     double stageMsFine[6] = {0, 0, 0, 0, 0, 0};  // the same, level 0 only
     double stageMsFineLast[6] = {0, 0, 0, 0, 0, 0};  // what the last mgps_stage_times call covered (mgps_stage_times_fine)
     int stageCycles = 0;
-    // options.enclosed_liquid (single device): the enclosed components of level 0 -- their cells grouped by rank (ascending inside a
-    // group), offsets (m + 1), the chunks of the projection (3 ints each: component, first entry, end entry) and each component's first
-    // chunk (m + 1), the projection's fp64 partials and means.  Nothing when m = 0
+    // options.enclosed_liquid: the enclosed components of level 0 -- their cells grouped by rank (ascending inside a group), offsets
+    // (m + 1), the chunks of the projection (3 ints each: component, first entry, end entry) and each component's first chunk (m + 1),
+    // each component's cell count (device and host), the projection's fp64 partials and sums.  Nothing when m = 0.  On a slab rank m,
+    // the ranks, the counts and encCells are the whole grid's; the cell lists, offsets and chunks cover the rank's owned planes
     int64_t encM = 0, encCells = 0;
-    int32_t *encCellList = nullptr, *encOffsets = nullptr, *encChunks = nullptr, *encCompChunk = nullptr;
+    int32_t *encCellList = nullptr, *encOffsets = nullptr, *encChunks = nullptr, *encCompChunk = nullptr, *encCount = nullptr;
+    std::vector<int32_t> encCountHost;
     int encNChunks = 0;
-    double *encPartials = nullptr, *encMean = nullptr;
+    double *encPartials = nullptr, *encSum = nullptr;
+    std::vector<double> encSumHost;  // (slab runs whose transport has no allreduce_device: the sums go through the host)
     float *encB = nullptr;  // P b for mgps_solve_pcg / mgps_apply_vcycle (the caller's b stays const; made on first use)
     std::string lastError = "";
 };
@@ -475,7 +478,7 @@ void freeAll(mgps_solver *h)
         for (int q = 0; q < 4; ++q) gridFree(h, h->pcg[q], h->lv[0].d);
         gridFree(h, h->dinv, h->lv[0].d);
     }
-    for (void *p : {(void *)h->encCellList, (void *)h->encOffsets, (void *)h->encChunks, (void *)h->encCompChunk, (void *)h->encPartials, (void *)h->encMean})
+    for (void *p : {(void *)h->encCellList, (void *)h->encOffsets, (void *)h->encChunks, (void *)h->encCompChunk, (void *)h->encPartials, (void *)h->encSum, (void *)h->encCount})
         (void)cacheFree(p);
     if (!h->lv.empty()) gridFree(h, h->encB, h->lv[0].d);
     for (void *p : h->userGrids) (void)cacheFree(p);
@@ -1441,16 +1444,38 @@ struct SolveClock {
 
 // ---- options.enclosed_liquid: P = subtract the mean over each enclosed component of level 0 ------------------------------
 bool hasEnclosed(const mgps_solver *h) { return h->encM > 0; }
+// the m component sums of a slab run summed over the ranks, in place on the device: on the stream when the transport can (one
+// device all-reduce per projection), through the host otherwise.  Every rank projects at the same points, so the collectives pair up
+int encSumOverRanks(mgps_solver *h)
+{
+    if (!h->dist) return MGPS_OK;
+    const int m = int(h->encM);
+    if (h->comm.allreduce_device) {
+        MGPS_COMM(h, h->comm.allreduce_device(h->comm.user, h->encSum, m, 0, h->stream));
+        return MGPS_OK;
+    }
+    h->encSumHost.resize(size_t(m));
+    MGPS_HIP(h, hipMemcpyAsync(h->encSumHost.data(), h->encSum, size_t(m) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MGPS_HIP(h, hipStreamSynchronize(h->stream));
+    MGPS_COMM(h, h->comm.allreduce(h->comm.user, h->encSumHost.data(), m, 0));
+    MGPS_HIP(h, hipMemcpyAsync(h->encSum, h->encSumHost.data(), size_t(m) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    MGPS_HIP(h, hipStreamSynchronize(h->stream));
+    return MGPS_OK;
+}
+// P v: per-chunk sums, per-component sums, (slab runs: summed over the ranks), v -= sum / count.  A single device takes the same
+// double operations as a mean pass followed by the subtraction: the same bits
 int projectEnclosed(mgps_solver *h, float *v)
 {
-    MGPS_LAUNCH(h, launchEnclosedProject(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCompChunk, h->encOffsets, h->encM, h->encPartials,
-                                         h->encMean));
+    MGPS_LAUNCH(h, launchEnclosedSums(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCompChunk, h->encM, h->encPartials, h->encSum));
+    MGPS_TRY(encSumOverRanks(h));
+    MGPS_LAUNCH(h, launchEnclosedSubtract(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCount, h->encSum));
     return MGPS_OK;
 }
 int projectEnclosed64(mgps_solver *h, double *v)
 {
-    MGPS_LAUNCH(h, launchEnclosedProject64(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCompChunk, h->encOffsets, h->encM,
-                                           h->encPartials, h->encMean));
+    MGPS_LAUNCH(h, launchEnclosedSums64(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCompChunk, h->encM, h->encPartials, h->encSum));
+    MGPS_TRY(encSumOverRanks(h));
+    MGPS_LAUNCH(h, launchEnclosedSubtract64(h->stream, v, h->encCellList, h->encChunks, h->encNChunks, h->encCount, h->encSum));
     return MGPS_OK;
 }
 // *out = P b in the solver's scratch grid (b itself stays untouched); b when there is no enclosed component
@@ -2358,6 +2383,32 @@ bool hostSetup(const mgps_options &o)
     return o.host_setup != 0 || env;
 }
 
+// what the projection needs from the component lists: offsets (m + 1 entries, this solver's cells) and each component's cell count
+// (a slab rank: over all ranks; a component may have no cell here)
+int enclosedChunks(mgps_solver *h, const std::vector<int32_t> &offsets, const std::vector<int32_t> &counts)
+{
+    // chunks of at most kEncChunkCells cells of one component: the fixed summation order of the projection
+    std::vector<int32_t> chunks, compChunk;
+    for (int64_t r = 0; r < h->encM; ++r) {
+        compChunk.push_back(int32_t(chunks.size() / 3));
+        for (int32_t e0 = offsets[size_t(r)]; e0 < offsets[size_t(r) + 1]; e0 += kEncChunkCells) {
+            chunks.push_back(int32_t(r));
+            chunks.push_back(e0);
+            chunks.push_back(std::min(offsets[size_t(r) + 1], e0 + kEncChunkCells));
+        }
+    }
+    compChunk.push_back(int32_t(chunks.size() / 3));
+    h->encNChunks = int(chunks.size() / 3);
+    h->encCountHost = counts;
+    MGPS_TRY(devUpload(h, &h->encChunks, chunks));
+    MGPS_TRY(devUpload(h, &h->encCompChunk, compChunk));
+    MGPS_TRY(devUpload(h, &h->encCount, counts));
+    MGPS_TRY(devAlloc(h, &h->encPartials, size_t(h->encNChunks), true));
+    MGPS_TRY(devAlloc(h, &h->encSum, size_t(h->encM), true));
+    MGPS_HIP(h, hipDeviceSynchronize());
+    return MGPS_OK;
+}
+
 // options.enclosed_liquid: label the components of level 0 -- on the device (union-find, mgps_setup.hip), or with the host builder
 // (options.host_setup: the checker; codes and weights come down for it) -- and keep what the projection needs when some are enclosed
 int setupEnclosed(mgps_solver *h, bool onHost)
@@ -2397,24 +2448,9 @@ int setupEnclosed(mgps_solver *h, bool onHost)
         }
     }
     if (h->encM == 0) return MGPS_OK;
-    // chunks of at most kEncChunkCells cells of one component: the fixed summation order of the projection
-    std::vector<int32_t> chunks, compChunk;
-    for (int64_t r = 0; r < h->encM; ++r) {
-        compChunk.push_back(int32_t(chunks.size() / 3));
-        for (int32_t e0 = offsets[size_t(r)]; e0 < offsets[size_t(r) + 1]; e0 += kEncChunkCells) {
-            chunks.push_back(int32_t(r));
-            chunks.push_back(e0);
-            chunks.push_back(std::min(offsets[size_t(r) + 1], e0 + kEncChunkCells));
-        }
-    }
-    compChunk.push_back(int32_t(chunks.size() / 3));
-    h->encNChunks = int(chunks.size() / 3);
-    MGPS_TRY(devUpload(h, &h->encChunks, chunks));
-    MGPS_TRY(devUpload(h, &h->encCompChunk, compChunk));
-    MGPS_TRY(devAlloc(h, &h->encPartials, size_t(h->encNChunks), true));
-    MGPS_TRY(devAlloc(h, &h->encMean, size_t(h->encM), true));
-    MGPS_HIP(h, hipDeviceSynchronize());
-    return MGPS_OK;
+    std::vector<int32_t> counts(size_t(h->encM));
+    for (size_t r = 0; r < counts.size(); ++r) counts[r] = offsets[r + 1] - offsets[r];
+    return enclosedChunks(h, offsets, counts);
 }
 // the tail of every single-device constructor: a solver that fails the labelling is not handed out
 int finishEnclosed(mgps_solver **out, int rc, bool onHost)
@@ -3477,6 +3513,201 @@ int agreeSlab(mgps_solver *h, int status, double *payload = nullptr, int n = 0)
     return status != MGPS_OK ? status : all;
 }
 
+// options.enclosed_liquid on a slab rank: the components of the whole fine grid, each rank holding the cell lists of its owned planes.
+// Both set-up modes run it once the rank's levels are built (the collapsed tail pins its coarsest level by itself: mgps_hierarchy::
+// pinEnclosed).  Local labelling on the device (encSlabLabel: ids global), the roots of plane 0 to the rank below, which pairs them
+// with its own across the cut (encSlabCandidates, deduplicated on the device); rank 0 gathers every rank's candidates (closed
+// pieces, pieces that couple across a cut) with their open flags and pairs, merges them with a host union-find, ranks the enclosed
+// sets by their minimum id and scatters a rank per candidate back; the rank's lists are grouped by those ranks (encSlabLists) and the
+// components' cell counts summed by one all-reduce.  Every rank takes part in every collective; every rank-local failure is folded
+// into agreeSlab before the next one.
+int mergeEnclosedPieces(mgps_solver *h, const std::vector<int32_t> &payload, const std::vector<int64_t> &nc, const std::vector<int64_t> &np,
+                        std::vector<int32_t> &answer, std::vector<size_t> &counts, std::vector<size_t> &displs)
+{
+    const int P = h->comm.size;
+    const int64_t plane = int64_t(h->lv[0].d.nx) * h->lv[0].d.ny;
+    std::unordered_map<int32_t, int32_t> where;  // global id -> candidate
+    std::vector<int32_t> id, owner;
+    std::vector<uint8_t> open;
+    std::vector<size_t> at(size_t(P), 0);
+    size_t off = 0;
+    auto bad = [&](int r) { return failH(h, MGPS_ERR_COMM, "enclosed-liquid merge: rank " + std::to_string(r) + " sent a component id that it cannot own"); };
+    for (int r = 0; r < P; ++r) {
+        at[size_t(r)] = off;
+        const int64_t lo = int64_t(h->splits[size_t(r)]) * plane, hi = int64_t(h->splits[size_t(r) + 1]) * plane;
+        for (int64_t t = 0; t < nc[size_t(r)]; ++t) {
+            const int32_t v = payload[off + size_t(t)], o = payload[off + size_t(nc[size_t(r)] + t)];
+            if (v < lo || v >= hi || (o != 0 && o != 1) || !where.emplace(v, int32_t(id.size())).second) return bad(r);
+            id.push_back(v);
+            owner.push_back(r);
+            open.push_back(uint8_t(o));
+        }
+        off += size_t(2 * nc[size_t(r)] + 2 * np[size_t(r)]);
+    }
+    std::vector<int32_t> parent(id.size());
+    for (size_t q = 0; q < parent.size(); ++q) parent[q] = int32_t(q);
+    auto find = [&](int32_t q) {
+        while (parent[size_t(q)] != q) q = parent[size_t(q)] = parent[size_t(parent[size_t(q)])];
+        return q;
+    };
+    for (int r = 0; r < P; ++r) {
+        if (np[size_t(r)] > 0 && r == P - 1) return bad(r);
+        const size_t pa = at[size_t(r)] + size_t(2 * nc[size_t(r)]), pb = pa + size_t(np[size_t(r)]);
+        const int64_t nextLo = r + 1 < P ? int64_t(h->splits[size_t(r) + 1]) * plane : 0;
+        for (int64_t t = 0; t < np[size_t(r)]; ++t) {
+            const auto a = where.find(payload[pa + size_t(t)]), b = where.find(payload[pb + size_t(t)]);
+            if (a == where.end() || b == where.end() || owner[size_t(a->second)] != r || owner[size_t(b->second)] != r + 1 || int64_t(b->first) >= nextLo + plane)
+                return bad(r);
+            int32_t x = find(a->second), y = find(b->second);
+            if (x == y) continue;
+            if (id[size_t(x)] > id[size_t(y)]) std::swap(x, y);
+            parent[size_t(y)] = x;  // (the root keeps the smaller id: a set's root is its minimum)
+        }
+    }
+    std::vector<uint8_t> setOpen(id.size(), 0);
+    for (size_t q = 0; q < id.size(); ++q) setOpen[size_t(find(int32_t(q)))] |= open[q];
+    std::vector<std::pair<int32_t, int32_t>> roots;  // (minimum id, candidate) of the enclosed sets
+    for (size_t q = 0; q < id.size(); ++q)
+        if (find(int32_t(q)) == int32_t(q) && !setOpen[q]) roots.emplace_back(id[q], int32_t(q));
+    std::sort(roots.begin(), roots.end());
+    std::vector<int32_t> rankOf(id.size(), -1);
+    for (size_t k = 0; k < roots.size(); ++k) rankOf[size_t(roots[k].second)] = int32_t(k);
+    // per rank: m, then the global rank (or -1) of each of its candidates
+    answer.clear();
+    counts.assign(size_t(P), 0);
+    displs.assign(size_t(P), 0);
+    size_t q = 0;
+    for (int r = 0; r < P; ++r) {
+        displs[size_t(r)] = answer.size() * sizeof(int32_t);
+        answer.push_back(int32_t(roots.size()));
+        for (int64_t t = 0; t < nc[size_t(r)]; ++t, ++q) answer.push_back(rankOf[size_t(find(int32_t(q)))]);
+        counts[size_t(r)] = answer.size() * sizeof(int32_t) - displs[size_t(r)];
+    }
+    return MGPS_OK;
+}
+
+int setupEnclosedSlab(mgps_solver *h, StageClock &sclock)
+{
+    if (h->opt.enclosed_liquid != 1) return MGPS_OK;
+    const int P = h->comm.size, rank = h->comm.rank;
+    const bool lo = rank > 0, hi = rank < P - 1;
+    const DevLevel &F = h->lv[0];
+    const Dims d = F.d;
+    const size_t plane = size_t(d.nx) * d.ny;
+    EncSlab st;
+    st.d = d;
+    st.base = int32_t(size_t(h->splits[size_t(rank)]) * plane);  // (createSlabImpl refused grids of more than 2^31 - 1 cells)
+    struct Release {
+        EncSlab &s;
+        ~Release() { encSlabRelease(s); }
+    } release{st};
+    DevScratch tmp;
+    const uint8_t *labLo = lo ? F.g.lab - plane : nullptr, *labHi = hi ? F.g.lab + d.cells() : nullptr;  // (the label planes next to the cuts)
+    auto hipFail = [&](int e, const char *what) { return failH(h, MGPS_ERR_HIP, std::string("enclosed-liquid labelling (") + what + "): " + hipGetErrorString(hipError_t(e))); };
+    // ---- local labelling, the roots of plane 0 to the rank below, pairs and candidates
+    int status = [&]() -> int {
+        MGPS_HIP(h, hipDeviceSynchronize());  // (the set-up kernels ran on the null stream)
+        const int e = encSlabLabel(h->stream, st, F.g.lab, h->w[0], h->w[1], h->w[2], labLo, labHi);
+        return e ? hipFail(e, "local") : MGPS_OK;
+    }();
+    MGPS_TRY(agreeSlab(h, status));
+    const size_t pb = plane * sizeof(int32_t);
+    if (P > 1 && h->comm.exchange(h->comm.user, lo ? st.sendRoots : nullptr, lo ? pb : 0, nullptr, 0, nullptr, 0, hi ? st.recvRoots : nullptr, hi ? pb : 0, h->stream) != 0)
+        return failH(h, MGPS_ERR_COMM, "enclosed-liquid labelling: exchange failed");
+    int32_t *cntDev = nullptr, *allCnt = nullptr;
+    status = [&]() -> int {
+        MGPS_HIP(h, hipStreamSynchronize(h->stream));
+        int badIds = 0;
+        const int e = encSlabCandidates(h->stream, st, F.g.lab, labHi, h->w[2], int32_t(size_t(h->splits[size_t(rank) + 1]) * plane), &badIds);
+        if (e) return hipFail(e, "candidates");
+        if (badIds) return failH(h, MGPS_ERR_COMM, "enclosed-liquid labelling: the rank above sent component ids that do not match its planes");
+        const int32_t c2[2] = {int32_t(st.ncand), int32_t(st.npairs)};
+        MGPS_TRY(tmp.get(h, &cntDev, 2));
+        MGPS_TRY(tmp.get(h, &allCnt, size_t(2 * P)));
+        MGPS_HIP(h, hipMemcpy(cntDev, c2, sizeof(c2), hipMemcpyHostToDevice));
+        return MGPS_OK;
+    }();
+    sclock.lap("slab: enclosed local labelling");
+    MGPS_TRY(agreeSlab(h, status));
+    // ---- rank 0: every rank's candidates and pairs, merged
+    if (h->comm.gather(h->comm.user, cntDev, rank == 0 ? allCnt : nullptr, 2 * sizeof(int32_t), 0, h->stream) != 0)
+        return failH(h, MGPS_ERR_COMM, "enclosed-liquid merge: gather failed");
+    std::vector<int64_t> nc(size_t(P), 0), np(size_t(P), 0);
+    std::vector<size_t> counts(size_t(P), 0), displs(size_t(P), 0);
+    int32_t *all = nullptr;
+    size_t total = 0;
+    status = [&]() -> int {
+        if (rank != 0) return MGPS_OK;
+        std::vector<int32_t> c(size_t(2 * P));
+        MGPS_HIP(h, hipStreamSynchronize(h->stream));
+        MGPS_HIP(h, hipMemcpy(c.data(), allCnt, c.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int r = 0; r < P; ++r) {
+            const int64_t owned = int64_t(h->splits[size_t(r) + 1] - h->splits[size_t(r)]) * int64_t(plane);
+            nc[size_t(r)] = c[size_t(2 * r)];
+            np[size_t(r)] = c[size_t(2 * r + 1)];
+            if (nc[size_t(r)] < 0 || nc[size_t(r)] > owned || np[size_t(r)] < 0 || np[size_t(r)] > int64_t(plane))
+                return failH(h, MGPS_ERR_COMM, "enclosed-liquid merge: rank " + std::to_string(r) + " sent impossible counts");
+            displs[size_t(r)] = total * sizeof(int32_t);
+            counts[size_t(r)] = size_t(2 * nc[size_t(r)] + 2 * np[size_t(r)]) * sizeof(int32_t);
+            total += size_t(2 * nc[size_t(r)] + 2 * np[size_t(r)]);
+        }
+        return tmp.get(h, &all, total);
+    }();
+    MGPS_TRY(agreeSlab(h, status));
+    if (h->comm.gatherv(h->comm.user, st.payload, size_t(2 * st.ncand + 2 * st.npairs) * sizeof(int32_t), rank == 0 ? all : nullptr, counts.data(), displs.data(), 0,
+                        h->stream) != 0)
+        return failH(h, MGPS_ERR_COMM, "enclosed-liquid merge: gatherv failed");
+    std::vector<int32_t> answer;
+    std::vector<size_t> acounts, adispls;
+    int32_t *answerDev = nullptr, *mine = nullptr;
+    status = [&]() -> int {
+        if (rank == 0) {
+            std::vector<int32_t> payload(total);
+            MGPS_HIP(h, hipStreamSynchronize(h->stream));
+            if (total) MGPS_HIP(h, hipMemcpy(payload.data(), all, total * sizeof(int32_t), hipMemcpyDeviceToHost));
+            MGPS_TRY(mergeEnclosedPieces(h, payload, nc, np, answer, acounts, adispls));
+            MGPS_TRY(devUpload(h, &answerDev, answer));
+            tmp.ptrs.push_back(answerDev);
+        }
+        return tmp.get(h, &mine, size_t(st.ncand) + 1);
+    }();
+    MGPS_TRY(agreeSlab(h, status));
+    if (h->comm.scatterv(h->comm.user, answerDev, acounts.data(), adispls.data(), mine, (size_t(st.ncand) + 1) * sizeof(int32_t), 0, h->stream) != 0)
+        return failH(h, MGPS_ERR_COMM, "enclosed-liquid merge: scatterv failed");
+    // ---- the rank's lists, grouped by the global ranks
+    int64_t m = 0, localCells = 0;
+    std::vector<int32_t> offsets;
+    status = [&]() -> int {
+        std::vector<int32_t> got(size_t(st.ncand) + 1);
+        MGPS_HIP(h, hipStreamSynchronize(h->stream));
+        MGPS_HIP(h, hipMemcpy(got.data(), mine, got.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        m = got[0];
+        bool ok = m >= 0 && m <= int64_t(INT32_MAX);
+        for (size_t t = 1; t < got.size() && ok; ++t) ok = got[t] >= -1 && got[t] < m;
+        if (!ok) return failH(h, MGPS_ERR_COMM, "enclosed-liquid merge: rank 0 sent component ranks out of range");
+        if (m == 0) return MGPS_OK;  // (no enclosed component anywhere: nothing persists)
+        const int e = encSlabLists(h->stream, st, mine + 1, m, &h->encCellList, &h->encOffsets, &localCells);
+        if (e) return hipFail(e, "lists");
+        offsets.resize(size_t(m) + 1);
+        MGPS_HIP(h, hipMemcpy(offsets.data(), h->encOffsets, offsets.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return MGPS_OK;
+    }();
+    MGPS_TRY(agreeSlab(h, status));
+    sclock.lap("slab: enclosed merge");
+    if (m == 0) return MGPS_OK;  // (m came from rank 0: the same on every rank)
+    // ---- the components' cell counts over all ranks (and the total): one all-reduce
+    std::vector<double> cnt(size_t(m) + 1, 0.0);
+    for (int64_t r = 0; r < m; ++r) cnt[size_t(r)] = double(offsets[size_t(r) + 1] - offsets[size_t(r)]);
+    cnt[size_t(m)] = double(localCells);
+    if (h->comm.allreduce(h->comm.user, cnt.data(), int(cnt.size()), 0) != 0) return failH(h, MGPS_ERR_COMM, "enclosed-liquid counts: all-reduce failed");
+    h->encM = m;
+    h->encCells = int64_t(cnt[size_t(m)]);
+    std::vector<int32_t> global(static_cast<size_t>(m));
+    for (int64_t r = 0; r < m; ++r) global[size_t(r)] = int32_t(cnt[size_t(r)]);
+    status = enclosedChunks(h, offsets, global);
+    return agreeSlab(h, status);
+}
+
 int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t *labels_global_host, const float *wx_slab, const float *wy_slab,
                        const float *wz_slab, bool weightsOnDevice, int mgLevels, bool useGS, const mgps_options &o, const mgps_comm *comm, const int *splits, int device)
 {
@@ -3952,6 +4183,7 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         const int rcLight = hierarchyLight(&h->hier, nx, ny, nzg, levels, nullptr, o, false);
         if (rcLight != MGPS_OK) return bail(failH(h, rcLight, lastGlobalError()));
     }
+    if (int rc = setupEnclosedSlab(h, sclock); rc != MGPS_OK) return bail(rc);  // (options.enclosed_liquid; every rank returns the same verdict)
     *out = h;
     return MGPS_OK;
 }
@@ -3968,8 +4200,14 @@ int createSlabImpl(mgps_solver **out, int nx, int ny, int nz_global, const uint8
     *out = nullptr;
     if (!labels_global_host || !wx_slab || !wy_slab || !wz_slab || !comm || !splits)
         return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: labels, the slab weights, a comm and the cuts are required");
-    if (opt && opt->struct_size == int(sizeof(mgps_options)) && opt->enclosed_liquid != 0)
-        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: options.enclosed_liquid is for single-device solvers only");
+    // options.enclosed_liquid: rank 0 merges the ranks' components through gatherv / scatterv (a struct_size that ends before them
+    // lacks them), and the component ids are int32 global cell indices
+    if (opt && opt->struct_size == int(sizeof(mgps_options)) && opt->enclosed_liquid != 0) {
+        if (comm->struct_size < int(offsetof(mgps_comm, scatterv) + sizeof(comm->scatterv)) || !comm->gatherv || !comm->scatterv)
+            return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: options.enclosed_liquid needs a transport with gatherv and scatterv");
+        if (size_t(nx) * size_t(ny) * size_t(nz_global) > size_t(INT32_MAX))
+            return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: options.enclosed_liquid: more than 2^31 - 1 cells");
+    }
     // (a transport built against the header before `allreduce_device` was appended is accepted: the missing tail reads as NULL)
     if (comm->struct_size < int(offsetof(mgps_comm, allreduce_device)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange || !comm->allreduce ||
         !comm->gather || !comm->scatter || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
@@ -4122,6 +4360,7 @@ int createSlabImpl(mgps_solver **out, int nx, int ny, int nz_global, const uint8
         if (tailRc == MGPS_OK) failH(h, int(failed), "the collapsed tail could not be built on rank 0 (status " + std::to_string(int(failed)) + ")");
         return bail(tailRc != MGPS_OK ? tailRc : int(failed));
     }
+    if (int rc2 = setupEnclosedSlab(h, sclock); rc2 != MGPS_OK) return bail(rc2);  // (options.enclosed_liquid: the same labelling and merge)
     *out = h;
     return MGPS_OK;
 }
@@ -4225,7 +4464,7 @@ try {
     case 12: src = L.bandBoxes.list, n = L.bandBoxes.listCount; break;
     case 13: src = L.bandBoxes.general, n = L.bandBoxes.generalInts; break;
     case 14: {  // (made here from the component lists: the solver keeps no per-cell array)
-        if (level != 0 || h->opt.enclosed_liquid != 1 || h->dist)
+        if (level != 0 || h->opt.enclosed_liquid != 1)
             return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_level_array: array 14 exists on level 0 with options.enclosed_liquid only");
         *count = int64_t(L.d.cells());
         if (!out) return MGPS_OK;
@@ -4592,11 +4831,11 @@ try {
     if (!hasEnclosed(h)) return MGPS_OK;
     MGPS_TRY(projectEnclosed(h, v_dev));
     if (max_abs_mean_removed) {
-        std::vector<double> mean(size_t(h->encM));
-        MGPS_HIP(h, hipMemcpyAsync(mean.data(), h->encMean, mean.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        std::vector<double> sum(size_t(h->encM));  // (a slab rank: the sums over all ranks, the same on every rank)
+        MGPS_HIP(h, hipMemcpyAsync(sum.data(), h->encSum, sum.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         MGPS_HIP(h, hipStreamSynchronize(h->stream));
         double mx = 0.0;
-        for (double v : mean) mx = std::max(mx, std::fabs(v));
+        for (size_t r = 0; r < sum.size(); ++r) mx = std::max(mx, std::fabs(sum[r] / double(h->encCountHost[r])));  // (the subtract pass's mean)
         *max_abs_mean_removed = mx;
     }
     return MGPS_OK;

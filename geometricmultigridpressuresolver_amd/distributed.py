@@ -294,7 +294,11 @@ class SlabSolver(GeometricMultigridPoissonSolver):
     labels: the WHOLE solver grid (nz, ny, nx) uint8; weights: this rank's slab only -- wx, wy with
     nz/size planes, wz with nz/size + 1.  Grids of this solver hold the rank's owned planes; they
     come from new_grid()/to_device(), which surround them with the two ghost planes the exchange
-    writes into."""
+    writes into.
+
+    options.enclosed_liquid: enclosed_components() returns the whole grid's numbers on every rank; enclosed_ranks() and
+    project_enclosed() act on the rank's owned planes and are collectives (every rank calls them together).  The transport
+    needs gatherv and scatterv."""
 
     def __init__(self, labels, slab_weights, mg_levels, use_gauss_seidel, comm, device=None, options=None, splits=None):
         """splits: the cuts (slab_partition); None = nz / size planes per rank.

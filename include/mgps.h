@@ -146,15 +146,18 @@ typedef struct mgps_options {
     /* 1: liquid that touches no air is solved too.  Every connected body of active cells needs a DIRICHLET contact for the
        system to be non-singular; a tank filled to its lid, liquid trapped under a solid or a region cut off by closed faces
        (weight 0) gives a graph Laplacian whose null space is the constant on that region, and the reference's coarse Cholesky
-       only asserts (MG.cpp:409-411).  With this option a single-device solver labels the components of the fine level's
-       active cells at set-up (two active cells are coupled when either is INTERIOR, two BOUNDARY cells when their face weight
+       only asserts (MG.cpp:409-411).  With this option the solver labels the components of the fine level's active cells at
+       set-up (a slab solver: each rank labels its owned planes and rank 0 merges the pieces across the cuts, so every rank
+       sees the whole grid's components; two active cells are coupled when either is INTERIOR, two BOUNDARY cells when their face weight
        is > 0) and calls a component "enclosed" when none of its BOUNDARY cells has a DIRICHLET neighbour behind a face of
        weight > 0.  With P = "subtract the mean over each enclosed component", mgps_solve_pcg solves A x = P b (rhs norm,
        residuals and early-outs refer to P b; the preconditioner output is projected; the returned x has mean 0 on every
        enclosed component) and mgps_apply_vcycle returns P V(P b).  The coarsest level pins the minimum-index cell of each of
        its own components without a DIRICHLET neighbour (the pinned unknown is 0).  Domains without an enclosed component give
-       the results of 0 bit for bit (the labelling is the only extra work).  0 (default): today's behaviour.  Refused on slab
-       solvers and with precision = 1 */
+       the results of 0 bit for bit (the labelling is the only extra work).  0 (default): today's behaviour.  Refused with
+       precision = 1, on slab solvers whose transport lacks gatherv or scatterv, and for grids of more than 2^31 - 1 cells.
+       On a slab rank every projection sums the components over the ranks: one all-reduce of m doubles, through
+       allreduce_device when the transport has it */
     int enclosed_liquid;
 } mgps_options;
 
@@ -179,7 +182,8 @@ int mgps_device_count(int *count);
  * 8 / 9 mixed tiles even / odd (i32), 10 per-tile start of the general BOUNDARY cells (i32), 11..13 the boxes of the fused
  * band stage: info (i32, 16 per group, in launch order), list entries (u32), general entries (i32, 2 per entry), 14 (level 0,
  * options.enclosed_liquid only) the rank of a cell's enclosed component (i32, nx*ny*nz; -1 on every other cell; components
- * ranked by their minimum linear cell index).
+ * ranked by their minimum linear cell index; a slab rank: its owned cells, holding the ranks of the whole grid's components,
+ * ranked by their minimum global index (k_global * ny + j) * nx + i).
  * *count = number of elements; out == NULL asks for the count only. */
 int mgps_level_array(mgps_solver *h, int level, int which, void *out, int64_t *count);
 
@@ -351,11 +355,13 @@ int mgps_solve_pcg(mgps_solver *h, float *x_dev, const float *b_dev, double tole
 
 /* ---- enclosed liquid (options.enclosed_liquid; the reference has no counterpart, MG.cpp:409-411 only asserts) ------------
  * *components: the enclosed components of the fine level, *cells: the cells they hold (either may be NULL); 0 / 0 when the
- * option is off. */
+ * option is off.  A slab rank returns the whole grid's numbers, the same on every rank. */
 int mgps_enclosed_components(const mgps_solver *h, int64_t *components, int64_t *cells);
 /* v = P v on a level-0 grid: the mean over each enclosed component is subtracted from its cells, every other cell is left
  * as it is, bit for bit.  Sums in fp64 in a fixed order (same input, same bits).  max_abs_mean_removed (may be NULL): the
- * largest |mean| removed (0 without enclosed components); synchronises the stream when it is asked for. */
+ * largest |mean| removed (0 without enclosed components); synchronises the stream when it is asked for.  On slab ranks a
+ * collective (every rank calls it): v is the rank's owned planes, the means are the whole grid's and max_abs_mean_removed is
+ * the same on every rank. */
 int mgps_project_enclosed(mgps_solver *h, float *v_dev, double *max_abs_mean_removed);
 
 /* ---- multi-GPU: Z-slab partition of the fine grid -------------------------------------------

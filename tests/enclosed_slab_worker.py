@@ -1,0 +1,362 @@
+"""Worker of tests/test_enclosed_slabs.py: run under torch.distributed.run with 2 or 4 ranks sharing the one GPU over
+TorchDistComm/gloo.  options.enclosed_liquid on slab solvers against the single-device solver on the whole grid.
+
+modes: "ranks" (labels and merge on many domains), "solve" (MG-PCG parity), "cycle" (V-cycle and P), "m0" (a domain without
+pockets: the option adds nothing), "refuse" (a transport without gatherv).  Prints "WORKER_OK <rank>" on success.
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import geometricmultigridpressuresolver_amd as G  # noqa: E402
+from geometricmultigridpressuresolver_amd import domains as D  # noqa: E402
+from geometricmultigridpressuresolver_amd.distributed import SlabSolver, TorchDistComm, slab_partition  # noqa: E402
+
+N, LEV, S = 64, 4, 8  # the domains below: 64^3, 4 levels, an EXTERIOR shell of 8 cells; z is the cut axis
+
+
+def rel_l2(a, b):
+    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-300))
+
+
+def options(enclosed=1, **kw):
+    o = G.default_options()
+    o.enclosed_liquid = enclosed
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def slab_weights(w, splits, rank):
+    z0, z1 = splits[rank], splits[rank + 1]
+    return [w[0][z0:z1], w[1][z0:z1], w[2][z0:z1 + 1]]
+
+
+def even_splits(nz, size):
+    return [nz // size * r for r in range(size + 1)]
+
+
+def make_slab(lab, w, levels, gs, splits=None, **kw):
+    splits = splits or even_splits(lab.shape[0], dist.get_world_size())
+    return SlabSolver(lab, slab_weights(w, splits, dist.get_rank()), levels, gs, TorchDistComm(), device=0, options=options(**kw), splits=splits)
+
+
+def whole_solver(lab, w, levels, gs, **kw):
+    return G.GeometricMultigridPoissonSolver(lab, w, levels, gs, device=0, options=options(**kw))
+
+
+def all_ranks(value):
+    seen = [None] * dist.get_world_size()
+    dist.all_gather_object(seen, value)
+    return seen
+
+
+def gather_ranks(slab):
+    """the ranks' enclosed_ranks() concatenated in z, on every rank"""
+    return np.concatenate(all_ranks(slab.enclosed_ranks()))
+
+
+# ---- domains ----------------------------------------------------------------------------------------------------------
+def unit_weights():
+    return [np.ones(D.face_shape(N, N, N, a), dtype=np.float32) for a in range(3)]
+
+
+def finish(lab, w):
+    D.set_boundary_labels(lab, w)
+    return lab, w
+
+
+def zero_weight_seal(zface):
+    """an open tank (DIRICHLET top layer) whose z faces at plane `zface` are closed: the liquid below them is sealed"""
+    from test_enclosed_liquid import tank
+
+    lab, w = tank(N, LEV, open_top=True)
+    w[2][zface, S:N - S, S:N - S] = 0.0
+    return finish(lab, w)
+
+
+def serpentine():
+    """INTERIOR columns at five x positions joined by bars alternately at the bottom (z 12..15) and the top (z 48..51): one sealed
+    component that crosses every cut of 2 and 4 ranks several times; with 2 ranks the two arms of each bottom U meet on the upper
+    rank only through the rank below"""
+    lab = np.full((N, N, N), D.EXTERIOR, dtype=np.uint8)
+    xs = [10, 20, 30, 40, 50]
+    for x in xs:
+        lab[12:52, 20:24, x:x + 4] = D.INTERIOR
+    for q in range(4):
+        z = slice(12, 16) if q % 2 == 0 else slice(48, 52)
+        lab[z, 20:24, xs[q]:xs[q + 1] + 4] = D.INTERIOR
+    return finish(lab, unit_weights())
+
+
+def far_contact():
+    """most of a component on rank 0 (z 8..27), its only DIRICHLET contact at the top of a thin column on the last rank: open; and
+    a sealed bubble on the upper ranks"""
+    lab = np.full((N, N, N), D.EXTERIOR, dtype=np.uint8)
+    lab[8:28, 8:56, 8:56] = D.INTERIOR
+    lab[28:55, 30:34, 30:34] = D.INTERIOR
+    lab[55, 30:34, 30:34] = D.DIRICHLET
+    lab[40:44, 10:14, 10:14] = D.INTERIOR
+    return finish(lab, unit_weights())
+
+
+def dirichlet_across_cut(weight):
+    """a block on z 20..31 whose only DIRICHLET neighbours lie across the cut at z = 32: open when the faces on the cut have weight
+    > 0, enclosed when they are closed"""
+    lab = np.full((N, N, N), D.EXTERIOR, dtype=np.uint8)
+    lab[20:32, 16:48, 16:48] = D.INTERIOR
+    lab[32, 16:48, 16:48] = D.DIRICHLET
+    w = unit_weights()
+    w[2][32, 16:48, 16:48] = weight
+    return finish(lab, w)
+
+
+def bubbles(seed=7):
+    """>= 100 2^3 bubbles on z layers 10, 15, 20, 27, 31, 36 (15 and 31 straddle the cuts at 16 and 32; with 4 ranks the last one
+    holds none), one in ten opened by a DIRICHLET cell"""
+    rng = np.random.default_rng(seed)
+    lab = np.full((N, N, N), D.EXTERIOR, dtype=np.uint8)
+    count = 0
+    for z in (10, 15, 20, 27, 31, 36):
+        for y in range(8, 54, 4):
+            for x in range(8, 54, 4):
+                if rng.random() < 0.2:
+                    lab[z:z + 2, y:y + 2, x:x + 2] = D.INTERIOR
+                    if rng.random() < 0.1:
+                        lab[z, y, x] = D.DIRICHLET
+                    count += 1
+    assert count >= 100
+    return finish(lab, unit_weights())
+
+
+def rank_domains(size):
+    from test_device_setup import random_domain
+    from test_enclosed_liquid import tank
+
+    yield "tank", tank(N, LEV), LEV, None, {}
+    yield "seal_on_cut", zero_weight_seal(N // 2), LEV, None, {}
+    yield "seal_off_cut", zero_weight_seal(N // 2 + 1), LEV, None, {}
+    yield "serpentine", serpentine(), LEV, None, {"min_cells_per_rank": 0}
+    yield "far_contact", far_contact(), LEV, None, {}
+    yield "dirichlet_cut_open", dirichlet_across_cut(1.0), LEV, None, {}
+    yield "dirichlet_cut_closed", dirichlet_across_cut(0.0), LEV, None, {"min_cells_per_rank": 0}
+    yield "bubbles", bubbles(), LEV, None, {"min_cells_per_rank": 0}
+    for seed in (1, 2):  # (two seeds of test_enclosed_liquid.py::test_random_domain_ranks_match, closed faces on)
+        yield f"random{seed}", random_domain((64, 64, 96), 3, seed), 3, None, {"min_cells_per_rank": 0}
+    lab, w = bubbles(11)
+    yield "bubbles_uneven", (lab, w), LEV, [0, 24, 64] if size == 2 else slab_partition(lab, LEV, size, False), {}
+    yield "serpentine_host", serpentine(), LEV, None, {"host_setup": 1}
+
+
+EXPECT = {"tank": 1, "seal_on_cut": 1, "seal_off_cut": 1, "serpentine": 1, "far_contact": 1, "dirichlet_cut_open": 0, "dirichlet_cut_closed": 1}
+
+
+def ranks_mode():
+    for name, (lab, w), levels, splits, kw in rank_domains(dist.get_world_size()):
+        whole = whole_solver(lab, w, levels, False)
+        try:
+            mw = whole.enclosed_components()
+            rw = whole.enclosed_ranks()
+        finally:
+            whole.close()
+        slab = make_slab(lab, w, levels, False, splits=splits, **kw)
+        try:
+            ms = slab.enclosed_components()
+            assert all(v == mw for v in all_ranks(ms)), (name, all_ranks(ms), mw)
+            rs = gather_ranks(slab)
+            assert np.array_equal(rs, rw), (name, int((rs != rw).sum()), mw)
+            if kw.get("host_setup"):  # (the host builder's slab ranks against the device set-up's)
+                dev = make_slab(lab, w, levels, False, splits=splits)
+                try:
+                    assert np.array_equal(gather_ranks(dev), rs) and dev.enclosed_components() == ms, name
+                finally:
+                    dev.close()
+            if dist.get_rank() == 0:
+                print(f"{name}: m = {ms[0]}, cells = {ms[1]}, cuts {slab.splits}, distributed levels {slab.distributed_levels}", flush=True)
+        finally:
+            slab.close()
+        if name in EXPECT:
+            assert mw[0] == EXPECT[name], (name, mw)
+        if name.startswith("bubbles"):
+            assert mw[0] >= 90, (name, mw)
+
+
+def solve_mode():
+    from test_enclosed_liquid import assemble, projected, reference_ranks, rounding_floor, tank, three_pockets
+
+    rank = dist.get_rank()
+    for name, (lab, w) in (("tank", tank(N, LEV)), ("pockets", three_pockets())):
+        ranks = reference_ranks(lab, w)
+        act = np.flatnonzero(D.active_mask(lab).ravel())
+        A = assemble(lab, w)[0].tocsr() if rank == 0 else None
+        b = D.random_rhs(lab, 1.0 / N)
+        cases = [(gs, mode, True) for gs in (False, True) for mode in (0, 1, 2)] + [(False, 2, False)]
+        for gs, mode, mg in cases:
+            whole = whole_solver(lab, w, LEV, gs, pcg_fp64_vectors=mode)
+            try:
+                xw = whole.new_grid()
+                stw = whole.solveGeometricConjugateGradient(xw, whole.to_device(b), 1e-6, 400, mg)
+                xw = xw.cpu().numpy()
+            finally:
+                whole.close()
+            slab = make_slab(lab, w, LEV, gs, pcg_fp64_vectors=mode, min_cells_per_rank=0)
+            try:
+                z0, z1 = slab.splits[rank], slab.splits[rank + 1]
+                xs = slab.new_grid()
+                st = slab.solveGeometricConjugateGradient(xs, slab.to_device(b[z0:z1]), 1e-6, 400, mg)
+                x = slab.gather_global(xs)
+            finally:
+                slab.close()
+            what = (name, gs, mode, mg, st["iterations"], stw["iterations"])
+            assert st["outcome"] == "converged" and abs(st["iterations"] - stw["iterations"]) <= 1, what
+            err = rel_l2(x, xw)
+            assert err < (1e-4 if mode == 0 else 1e-5), (what, err)
+            xf = x.ravel().astype(np.float64)
+            for r in range(ranks.max() + 1):
+                assert abs(xf[ranks == r].mean()) <= 1e-6 * np.abs(xf).max(), (what, r)
+            if rank == 0:  # (the bounds of test_enclosed_liquid.py::check_solve)
+                pb = projected(b, ranks)[act]
+                res = np.linalg.norm(pb - A @ xf[act]) / np.linalg.norm(pb)
+                bound = 2e-6 if mode else 2e-3
+                if name == "pockets" and mode:
+                    bound = max(bound, 1.2 * rounding_floor(A, pb, ranks[act]))
+                assert res <= bound, (what, res, bound)
+                print(f"{name} gs={gs} mode={mode} mg={mg}: {st['iterations']} it (single device {stw['iterations']}), rel_l2 {err:.1e}, "
+                      f"true residual {res:.1e}", flush=True)
+
+
+def cycle_mode():
+    from test_enclosed_liquid import reference_ranks, three_pockets
+
+    rank = dist.get_rank()
+    lab, w = three_pockets()
+    ranks = reference_ranks(lab, w)
+    rng = np.random.default_rng(4)
+    v = np.where(D.active_mask(lab), rng.standard_normal(lab.shape), 0).astype(np.float32)
+    b = D.random_rhs(lab, 1.0 / N)
+    for gs in (False, True):
+        whole = whole_solver(lab, w, LEV, gs)
+        try:
+            xw = whole.new_grid()
+            whole.applyVCycle(xw, whole.to_device(b), False)
+            vw = whole.to_device(v)
+            mxw = whole.project_enclosed(vw)
+            xw, vw = xw.cpu().numpy(), vw.cpu().numpy()
+        finally:
+            whole.close()
+        slab = make_slab(lab, w, LEV, gs, min_cells_per_rank=0)
+        try:
+            z0, z1 = slab.splits[rank], slab.splits[rank + 1]
+            xs = slab.new_grid()
+            slab.applyVCycle(xs, slab.to_device(b[z0:z1]), False)
+            x = slab.gather_global(xs)
+            assert rel_l2(x, xw) < 1e-5, (gs, rel_l2(x, xw))
+            outs, mxs = [], []
+            for _ in range(2):  # (same input, same bits)
+                vs = slab.to_device(v[z0:z1])
+                mxs.append(slab.project_enclosed(vs))
+                outs.append(vs.clone())
+            assert torch.equal(outs[0], outs[1]) and mxs[0] == mxs[1]
+            assert all(m == mxs[0] for m in all_ranks(mxs[0]))  # (the whole grid's value on every rank)
+            assert abs(mxs[0] - mxw) <= 1e-12 * mxw, (mxs[0], mxw)
+            p = slab.gather_global(outs[0])
+            assert np.abs(p - vw).max() <= 1e-6 * np.abs(vw).max(), np.abs(p - vw).max()
+            assert np.array_equal(p.ravel()[ranks < 0], v.ravel()[ranks < 0])
+            if rank == 0:
+                print(f"cycle gs={gs}: rel_l2 {rel_l2(x, xw):.1e}, P max diff {np.abs(p - vw).max():.1e}, max |mean| {mxs[0]:.6e}", flush=True)
+        finally:
+            slab.close()
+
+
+def m0_mode():
+    """dist_worker's free-surface box (no pocket): the option on gives the bits, the exchanges and the device all-reduces of the
+    option off; with pockets, each iteration adds the device all-reduces DESIGN.md §12 names"""
+    from conftest import make_domain
+    from test_enclosed_liquid import three_pockets
+
+    rank = dist.get_rank()
+    lab, w, off, lev, dx = make_domain("simple", 40 if dist.get_world_size() == 2 else 48, 4, (64, 64, 64))
+    b = D.random_rhs(lab, dx)
+    for gs in (False, True):
+        outs = []
+        for enclosed in (0, 1):
+            slab = make_slab(lab, w, lev, gs, enclosed=enclosed, min_cells_per_rank=0)
+            try:
+                assert slab.enclosed_components() == (0, 0)
+                z0, z1 = slab.splits[rank], slab.splits[rank + 1]
+                bd, xv, xp = slab.to_device(b[z0:z1]), slab.new_grid(), slab.new_grid()
+                e0, a0 = slab.exchange_count, slab.comm.device_allreduces
+                slab.applyVCycle(xv, bd, False)
+                e1 = slab.exchange_count
+                st = slab.solveGeometricConjugateGradient(xp, bd, 1e-6, 200, True)
+                e2, a2 = slab.exchange_count, slab.comm.device_allreduces
+                st.pop("solve_ms")
+                outs.append((xv.clone(), xp.clone(), st, e1 - e0, e2 - e1, a2 - a0))
+            finally:
+                slab.close()
+        off_, on_ = outs
+        assert torch.equal(off_[0], on_[0]) and torch.equal(off_[1], on_[1]), gs
+        assert off_[2] == on_[2] and off_[3:] == on_[3:], (gs, off_[2:], on_[2:])
+        if rank == 0:
+            print(f"m = 0 gs={gs}: {on_[2]['iterations']} it, exchanges {on_[3]} + {on_[4]}, device all-reduces {on_[5]}", flush=True)
+
+    def rate(lab_, w_, mode):  # device all-reduces per iteration: the difference of two solves stopped after 3 and 6 iterations
+        slab = make_slab(lab_, w_, LEV, False, pcg_fp64_vectors=mode, min_cells_per_rank=0)
+        try:
+            z0, z1 = slab.splits[rank], slab.splits[rank + 1]
+            bd = slab.to_device(D.random_rhs(lab_, 1.0 / N)[z0:z1])
+            got = []
+            for its in (3, 6):
+                a0 = slab.comm.device_allreduces
+                st = slab.solveGeometricConjugateGradient(slab.new_grid(), bd, 1e-30, its, True)
+                assert st["iterations"] == its, st
+                got.append(slab.comm.device_allreduces - a0)
+            return (got[1] - got[0]) / 3
+        finally:
+            slab.close()
+
+    lab_p, w_p = three_pockets()
+    for mode, added in ((0, 2), (1, 1), (2, 2)):  # (z and A p projected in the fp32 loops, z in the fp64 one)
+        base, with_pockets = rate(lab, w, mode), rate(lab_p, w_p, mode)
+        assert with_pockets - base == added, (mode, base, with_pockets)
+        if rank == 0:
+            print(f"mode {mode}: device all-reduces per iteration {base:g} without pockets, {with_pockets:g} with", flush=True)
+
+
+def refuse_mode():
+    from test_enclosed_liquid import tank
+
+    lab, w = tank(N, LEV)
+    comm = TorchDistComm()
+    comm.struct.gatherv = type(comm.struct.gatherv)()  # (NULL)
+    splits = even_splits(N, dist.get_world_size())
+    try:
+        SlabSolver(lab, slab_weights(w, splits, dist.get_rank()), LEV, False, comm, device=0, options=options(), splits=splits)
+    except G.MgpsError as e:
+        assert e.status == 1 and "options.enclosed_liquid" in str(e), str(e)
+    else:
+        raise AssertionError("a transport without gatherv was accepted")
+
+
+def main():
+    mode = sys.argv[1]
+    dist.init_process_group("gloo")
+    torch.cuda.set_device(0)
+    try:
+        {"ranks": ranks_mode, "solve": solve_mode, "cycle": cycle_mode, "m0": m0_mode, "refuse": refuse_mode}[mode]()
+        torch.cuda.synchronize()
+        dist.barrier()
+        print(f"WORKER_OK {dist.get_rank()}", flush=True)
+    finally:
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()
