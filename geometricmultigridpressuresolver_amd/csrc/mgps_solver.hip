@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <string>
 #include <atomic>
@@ -1491,6 +1492,42 @@ int projectedRhs(mgps_solver *h, const float *b, const float **out)
     return MGPS_OK;
 }
 
+// The one way out of pcg() and pcg64() (include/mgps.h at mgps_solve_pcg).  handBack(project) leaves in the caller's x the iterate
+// the updates applied so far add up to (project: mean 0 on every enclosed component first); each loop supplies its own, as it
+// alone knows where the iterate sits (x itself; x64; x64 + the pending updates in x).  finish() is the ordinary exit.  stopHere()
+// is the interrupted one: outcome MAX_ITERATIONS, iterations = the loop counter, rel_residual = the loop's residual of the iterate
+// handed back.  A return that took neither -- an interrupt polled inside the preconditioning V-cycle, a failed launch or exchange
+// -- takes stopHere() from the destructor, so that no MGPS_TRY inside a loop leaves x as the scratch grid the loop made of it.
+// (A slab rank comes through the destructor only on a failure of its own, which the other ranks do not share: no collective
+// there, hence no projection.  Single devices project without one.)
+struct PcgExit {
+    mgps_solver *h;
+    mgps_pcg_stats *st;
+    SolveClock &clock;
+    const int &it;
+    const double &res2, &rhs2;
+    std::function<int(bool)> handBack;
+    bool left = false;
+    int finish(int outcome, bool project = true)
+    {
+        const int rc = handBack(project);
+        st->outcome = outcome;
+        st->solve_ms = clock.stop();
+        left = true;
+        return rc;
+    }
+    void stopHere(bool project = true)
+    {
+        finish(MGPS_PCG_MAX_ITERATIONS, project);
+        st->iterations = it;
+        if (rhs2 > 0) st->rel_residual = std::sqrt(res2 / rhs2);
+    }
+    ~PcgExit()
+    {
+        if (!left) stopHere(!h->dist);
+    }
+};
+
 // MG-PCG with the CG vectors in fp64 (options.pcg_fp64_vectors): CG.h:18-207 step by step like pcg() below; the
 // preconditioner is the same fp32 V-cycle (or diagonal) applied to float(r), x and b are fp32 at the boundary
 int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool useMG, mgps_pcg_stats *st)
@@ -1510,13 +1547,17 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     SolveClock clock(h);  // (destroys its events and resets h->dotTarget on every way out)
     if (!clock.ok) return failH(h, MGPS_ERR_HIP, "hipEventCreate failed");
     const bool enc = hasEnclosed(h);  // options.enclosed_liquid: A x = P b, z = P M r (<z, r> then taken on the projected z)
-    bool narrowed = false;             // (the end of the loop projects x64 before narrowing it into x)
-    auto finish = [&](int outcome) {
-        if (enc && !narrowed) (void)projectEnclosed(h, x);
-        st->outcome = outcome;
-        st->solve_ms = clock.stop();
-        return MGPS_OK;
-    };
+    bool widened = false;              // (the loop is under way: the iterate is x64, projected there and narrowed into x on the way out)
+    int it = 0;
+    double rhs2 = 0, res2 = 0;
+    PcgExit ex{h, st, clock, it, res2, rhs2, [&](bool project) -> int {
+                   if (widened) {
+                       if (enc && project) MGPS_TRY(projectEnclosed64(h, x64));  // (mean 0 on every enclosed component, before the narrowing)
+                       MGPS_LAUNCH(h, launchNarrow(h->stream, x, x64, n));
+                   } else if (enc && project)
+                       MGPS_TRY(projectEnclosed(h, x));
+                   return MGPS_OK;
+               }};
     bool gathered = false;  // options.enclosed_liquid: A x = P b, z = P M r (<z, r> then taken on the projected z)
     auto precondition = [&]() -> int {  // z = M float(r)
         gathered = false;
@@ -1534,34 +1575,29 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
         if (gathered) return fetchReduction(h, 0, out);
         return reduceToHost(h, 0, 0, z, r32, out);
     };
-    double rhs2 = 0;
     MGPS_TRY(reduceToHost(h, 1, 0, b, nullptr, &rhs2));  // CG.h:35
     st->rhs_norm2 = rhs2;
-    if (rhs2 == 0) return finish(MGPS_PCG_RHS_ZERO);  // CG.h:36-40
+    if (rhs2 == 0) return ex.finish(MGPS_PCG_RHS_ZERO);  // CG.h:36-40
     MGPS_LAUNCH(h, launchWiden(h->stream, x64, x, n));
-    double res2 = 0;
     MGPS_TRY(exchangeGhosts64(h, x64));
     MGPS_LAUNCH(h, launchStencil64(h->stream, 1, F.g, r64, x64, b, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:50-57
     MGPS_TRY(fetchReduction(h, 1, &res2));
     const double threshold = tol * tol * rhs2;  // CG.h:58
     if (res2 < threshold) {                     // CG.h:60-64
         st->rel_residual = st->rel_residual_recomputed = std::sqrt(res2 / rhs2);
-        return finish(MGPS_PCG_ALREADY_CONVERGED);
+        return ex.finish(MGPS_PCG_ALREADY_CONVERGED);
     }
+    widened = true;
     MGPS_TRY(precondition());                                              // CG.h:75
     MGPS_LAUNCH(h, launchXpay64(h->stream, F.g, p64, z, 0.0, 1));          // p = z
     double absNew = 0;
     MGPS_TRY(zDotR(&absNew));                                              // CG.h:86
-    int it = 0;
     bool converged = false;
     for (; it < maxIt; ++it) {
         bool stop = false;
         MGPS_TRY(interruptRequested(h, &stop));
         if (stop) {
-            (void)launchNarrow(h->stream, x, x64, n);  // what the iterations reached so far, as the fp32 loop leaves it
-            narrowed = true;
-            finish(MGPS_PCG_MAX_ITERATIONS);
-            st->iterations = it;
+            ex.stopHere();  // what the iterations reached so far, as the fp32 loop leaves it
             return failH(h, MGPS_ERR_INTERRUPTED, "mgps_solve_pcg: interrupted");
         }
         double pAp = 0;
@@ -1576,15 +1612,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
             converged = true;
             break;
         }
-        if (const int prc = precondition()) {  // CG.h:168
-            if (prc == MGPS_ERR_INTERRUPTED) {  // (polled inside the V-cycle): hand back what the iterations reached
-                (void)launchNarrow(h->stream, x, x64, n);
-                narrowed = true;
-                finish(MGPS_PCG_MAX_ITERATIONS);
-                st->iterations = it;
-            }
-            return prc;
-        }
+        MGPS_TRY(precondition());  // CG.h:168 (interrupted inside the V-cycle: PcgExit hands back what the iterations reached)
         const double absOld = absNew;
         MGPS_TRY(zDotR(&absNew));  // CG.h:180
         MGPS_LAUNCH(h, launchXpay64(h->stream, F.g, p64, z, absNew / absOld, 0));  // CG.h:191
@@ -1596,10 +1624,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     MGPS_LAUNCH(h, launchStencil64(h->stream, 1, F.g, r64, x64, b, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:203-205, in fp64
     MGPS_TRY(fetchReduction(h, 1, &rec2));
     st->rel_residual_recomputed = std::sqrt(rec2 / rhs2);
-    if (enc) MGPS_TRY(projectEnclosed64(h, x64));  // (mean 0 on every enclosed component, before the narrowing)
-    MGPS_LAUNCH(h, launchNarrow(h->stream, x, x64, n));
-    narrowed = true;
-    return finish(converged ? MGPS_PCG_CONVERGED : MGPS_PCG_MAX_ITERATIONS);
+    return ex.finish(converged ? MGPS_PCG_CONVERGED : MGPS_PCG_MAX_ITERATIONS);
 }
 
 // options.interrupt, polled once per CG iteration; in a slab run the ranks agree (max over ranks) so that nobody is left
@@ -1656,19 +1681,22 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
     if (!clock.ok) return failH(h, MGPS_ERR_HIP, "hipEventCreate failed");
     bool widened = false;  // (x64 holds the caller's iterate: from then on x is the sum of the pending updates)
     const bool enc = hasEnclosed(h);  // options.enclosed_liquid with an enclosed component: see precondition below
-    auto finish = [&](int outcome) {
-        if (wideX && widened && enc) {  // mean 0 on every enclosed component, taken on the fp64 iterate (+ the pending updates) before the narrowing
-            if (grouped > 0) (void)launchWidenAdd(h->stream, x64, x, F.d.cells());
-            (void)projectEnclosed64(h, x64);
-            (void)launchNarrowSum(h->stream, F.g, x, x64, false);
+    int it = 0;
+    double rhs2 = 0, res2 = 0;
+    PcgExit ex{h, st, clock, it, res2, rhs2, [&](bool project) -> int {
+        if (wideX && widened && enc && project) {  // mean 0 on every enclosed component, taken on the fp64 iterate (+ the pending updates) before the narrowing
+            if (grouped > 0) {
+                MGPS_LAUNCH(h, launchWidenAdd(h->stream, x64, x, F.d.cells()));
+                grouped = 0;
+            }
+            MGPS_TRY(projectEnclosed64(h, x64));
+            MGPS_LAUNCH(h, launchNarrowSum(h->stream, F.g, x, x64, false));
         } else if (wideX && widened)
-            (void)launchNarrowSum(h->stream, F.g, x, x64, grouped > 0);  // (what the iterations reached, rounded once)
-        else if (enc)
-            (void)projectEnclosed(h, x);  // mean 0 on every enclosed component
-        st->outcome = outcome;
-        st->solve_ms = clock.stop();
+            MGPS_LAUNCH(h, launchNarrowSum(h->stream, F.g, x, x64, grouped > 0));  // (what the iterations reached, rounded once)
+        else if (enc && project)
+            MGPS_TRY(projectEnclosed(h, x));  // mean 0 on every enclosed component
         return MGPS_OK;
-    };
+    }};
     // r = float(b - A x) from the wide iterate x64 (+ the pending updates in x, which are flushed on the way): it leaves float(r) in r
     // and |r|^2 on the device
     auto wideResidual = [&](double *res2) -> int {
@@ -1719,11 +1747,9 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
         return MGPS_OK;
     };
 
-    double rhs2 = 0;
     MGPS_TRY(reduceToHost(h, 1, 0, b, nullptr, &rhs2));  // CG.h:35
     st->rhs_norm2 = rhs2;
-    if (rhs2 == 0) return finish(MGPS_PCG_RHS_ZERO);  // CG.h:36-40
-    double res2 = 0;
+    if (rhs2 == 0) return ex.finish(MGPS_PCG_RHS_ZERO);  // CG.h:36-40
     if (wideX) {
         MGPS_LAUNCH(h, launchWiden(h->stream, x64, x, F.d.cells()));
         // (the second fp64 grid: zero since its allocation wherever no pass writes -- inactive cells, which read as 0 in every grid)
@@ -1736,7 +1762,7 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
     const double threshold = tol * tol * rhs2;           // CG.h:58
     if (res2 < threshold) {                              // CG.h:60-64
         st->rel_residual = st->rel_residual_recomputed = std::sqrt(res2 / rhs2);
-        return finish(MGPS_PCG_ALREADY_CONVERGED);
+        return ex.finish(MGPS_PCG_ALREADY_CONVERGED);
     }
     // Single-device runs keep alpha and beta on the device (launchCgScalars): the reductions leave <p, A p> and
     // <z, r> there, the update and xpay kernels read them, and only |r|^2 -- the convergence test of CG.h:161 -- is
@@ -1766,7 +1792,6 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
         MGPS_TRY(dotWithResidual(p, &absNew));  // CG.h:86
     MGPS_LAUNCH(h, launchZero(h->stream, z, F.d.cells()));
     MGPS_LAUNCH(h, launchZero(h->stream, t, F.d.cells()));
-    int it = 0;
     bool converged = false, rFresh = false;
     double groupStart2 = res2;  // |r|^2 (true) where the current group of fp32 updates began
     constexpr int wideReplaceEvery = 8;  // iterations between two residual replacements (every 4: +2 % time; every 16: one more iteration -- LABNOTES R4)
@@ -1774,8 +1799,7 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
         bool stop = false;
         MGPS_TRY(interruptRequested(h, &stop));
         if (stop) {
-            finish(MGPS_PCG_MAX_ITERATIONS);
-            st->iterations = it;
+            ex.stopHere();
             return failH(h, MGPS_ERR_INTERRUPTED, "mgps_solve_pcg: interrupted");
         }
         // t = A p (CG.h:110) and <p, A p> (CG.h:121) in one pass over p
@@ -1871,7 +1895,7 @@ int pcg(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool us
         MGPS_TRY(reduceToHost(h, 1, 0, r, nullptr, &rec2));
     }
     st->rel_residual_recomputed = std::sqrt(rec2 / rhs2);  // CG.h:205
-    return finish(converged ? MGPS_PCG_CONVERGED : MGPS_PCG_MAX_ITERATIONS);
+    return ex.finish(converged ? MGPS_PCG_CONVERGED : MGPS_PCG_MAX_ITERATIONS);
 }
 
 // ---- construction --------------------------------------------------------------------------------
@@ -4924,8 +4948,10 @@ try {
 }
 MGPS_API_CATCH(h)
 
+// iterateOnInterrupt (the PCG forms): a body that returns MGPS_ERR_INTERRUPTED has left an iterate in x (mgps_solve_pcg), and
+// x_host receives it like the device form's x does; the status stays MGPS_ERR_INTERRUPTED
 static int withHostGrids(mgps_solver *h, float *x_host, const float *b_host, bool uploadX,
-                         int (*body)(mgps_solver *, float *, const float *, void *), void *ctx)
+                         int (*body)(mgps_solver *, float *, const float *, void *), void *ctx, bool iterateOnInterrupt = false)
 {
     if (!x_host || !b_host) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "host form: NULL pointer");
     float *xd = nullptr, *bd = nullptr;
@@ -4935,6 +4961,11 @@ static int withHostGrids(mgps_solver *h, float *x_host, const float *b_host, boo
     if (rc == MGPS_OK && uploadX) rc = mgps_grid_upload(h, 0, xd, x_host);
     if (rc == MGPS_OK) rc = body(h, xd, bd, ctx);
     if (rc == MGPS_OK) rc = mgps_grid_download(h, 0, x_host, xd);
+    else if (rc == MGPS_ERR_INTERRUPTED && iterateOnInterrupt) {
+        const std::string said = h->lastError;
+        if (const int drc = mgps_grid_download(h, 0, x_host, xd)) rc = drc;
+        else h->lastError = said;
+    }
     const std::string keep = h->lastError;
     if (bd) mgps_grid_free(h, bd);
     mgps_grid_free(h, xd);
@@ -4970,7 +5001,7 @@ try {
             auto *p = static_cast<PcgHostCtx *>(c);
             return mgps_solve_pcg(hh, xd, bd, p->tol, p->maxIt, p->useMG, p->stats);
         },
-        &ctx);
+        &ctx, true);
 }
 MGPS_API_CATCH(h)
 
@@ -4979,7 +5010,7 @@ MGPS_API_CATCH(h)
 namespace {
 // double host grids: upload, narrow on the device, run `body` on fp32 device grids, widen, download
 template <class Body>
-int withHostGrids64(mgps_solver *h, double *x_host, const double *b_host, bool uploadX, Body body)
+int withHostGrids64(mgps_solver *h, double *x_host, const double *b_host, bool uploadX, Body body, bool iterateOnInterrupt = false)
 {
     if (!x_host || !b_host) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "host form: NULL pointer");
     const size_t n = h->lv[0].d.cells();
@@ -4997,13 +5028,16 @@ int withHostGrids64(mgps_solver *h, double *x_host, const double *b_host, bool u
     if (rc == MGPS_OK) rc = up(bd, b_host);
     if (rc == MGPS_OK && uploadX) rc = up(xd, x_host);
     if (rc == MGPS_OK) rc = body(xd, bd);
-    if (rc == MGPS_OK) {
-        rc = [&]() -> int {
+    if (rc == MGPS_OK || (rc == MGPS_ERR_INTERRUPTED && iterateOnInterrupt)) {  // (interrupted: the iterate, see withHostGrids)
+        const std::string said = h->lastError;
+        const int drc = [&]() -> int {
             MGPS_LAUNCH(h, launchWiden(h->stream, stage, xd, n));
             MGPS_HIP(h, hipMemcpyAsync(x_host, stage, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
             MGPS_HIP(h, hipStreamSynchronize(h->stream));
             return MGPS_OK;
         }();
+        if (drc != MGPS_OK) rc = drc;
+        else h->lastError = said;
     }
     const std::string keep = h->lastError;
     (void)cacheFree(stage);
@@ -5030,7 +5064,7 @@ try {
     MGPS_TRY(checkLevel(h, 0, "mgps_solve_pcg_host_f64"));
     return withHostGrids64(h, x_host, b_host, true, [&](float *xd, const float *bd) {
         return mgps_solve_pcg(h, xd, bd, tolerance, max_iterations, use_mg_preconditioner, stats);
-    });
+    }, true);
 }
 MGPS_API_CATCH(h)
 

@@ -207,7 +207,7 @@ def project_free_surface(liquid_phi, solid_phi, cut_weights, velocity, pressure,
     pr.tolerance, pr.max_iterations, pr.power_of_two = float(tolerance), int(max_iterations), int(power_of_two)
     pr.surface_tension, pr.dt, pr.dx, pr.density = float(surface_tension), float(dt), float(dx), float(density)
     pr.surface_pressure = chk(surface_pressure, shape) if surface_pressure is not None else None
-    check(lib().mgps_project_free_surface(C.byref(pr), C.byref(options) if options is not None else None))
+    status = lib().mgps_project_free_surface(C.byref(pr), C.byref(options) if options is not None else None)
     info = {
         "iterations": pr.stats.iterations, "outcome": pr.stats.outcome, "rel_residual": pr.stats.rel_residual,
         "rel_residual_recomputed": pr.stats.rel_residual_recomputed, "mg_levels": pr.mg_levels, "offset": pr.offset,
@@ -217,4 +217,9 @@ def project_free_surface(liquid_phi, solid_phi, cut_weights, velocity, pressure,
         "enclosed_components": pr.enclosed_components, "rhs_mean_removed_max": pr.rhs_mean_removed_max,
         "surface_pressure_max": pr.surface_pressure_max,
     }
+    try:
+        check(status)
+    except _lib.MgpsError as e:  # (interrupted: pressure and velocity hold what the iterate reached gives, include/mgps_fields.h)
+        e.info, e.valid_faces = info, valid
+        raise
     return valid, info

@@ -25,6 +25,27 @@ from ._lib import Options, PcgStats, check, lib
 PCG_OUTCOMES = {0: "converged", 1: "rhs_zero", 2: "already_converged", 3: "max_iterations"}
 
 
+def _pcg_stats(st):
+    return {
+        "outcome": PCG_OUTCOMES.get(st.outcome, st.outcome),
+        "iterations": st.iterations,
+        "rel_residual": st.rel_residual,
+        "rel_residual_recomputed": st.rel_residual_recomputed,
+        "rhs_norm2": st.rhs_norm2,
+        "solve_ms": st.solve_ms,
+    }
+
+
+def _check_pcg(status, handle, st):
+    """check() for the PCG calls: a failed call raises MgpsError with the stats the library filled in as `.stats`
+    (after MGPS_ERR_INTERRUPTED: which iterate the call left in x, see include/mgps.h)."""
+    try:
+        check(status, handle)
+    except _lib.MgpsError as e:
+        e.stats = _pcg_stats(st)
+        raise
+
+
 def default_options():
     o = Options()
     lib().mgps_default_options(C.byref(o))
@@ -356,20 +377,14 @@ class GeometricMultigridPoissonSolver:
     # -- CG.h ------------------------------------------------------------------------------------
     def solveGeometricConjugateGradient(self, solution, rhs, tolerance=1e-5, max_iterations=2500, use_mg_preconditioner=True):
         st = PcgStats()
-        check(
+        _check_pcg(
             lib().mgps_solve_pcg(
                 self.h, self._g(solution), self._g(rhs), C.c_double(tolerance), int(max_iterations), int(bool(use_mg_preconditioner)), C.byref(st)
             ),
             self.h,
+            st,
         )
-        return {
-            "outcome": PCG_OUTCOMES.get(st.outcome, st.outcome),
-            "iterations": st.iterations,
-            "rel_residual": st.rel_residual,
-            "rel_residual_recomputed": st.rel_residual_recomputed,
-            "rhs_norm2": st.rhs_norm2,
-            "solve_ms": st.solve_ms,
-        }
+        return _pcg_stats(st)
 
     # -- enclosed liquid (options.enclosed_liquid) ------------------------------------------------------
     def enclosed_components(self):
@@ -452,20 +467,22 @@ class GeometricMultigridPoissonSolver:
         return x
 
     def solvePcgHost(self, solution, rhs, tolerance=1e-5, max_iterations=2500, use_mg_preconditioner=True):
+        """A failed call raises MgpsError with `.stats` and `.solution` (the host buffer as the call left it: after
+        MGPS_ERR_INTERRUPTED the iterate, like the device form's x)."""
+
+        def run(fn, x, b):
+            st = PcgStats()
+            try:
+                _check_pcg(fn(self.h, _p(x), _p(b), C.c_double(tolerance), int(max_iterations), int(bool(use_mg_preconditioner)), C.byref(st)), self.h, st)
+            except _lib.MgpsError as e:
+                e.solution = x
+                raise
+            return x, {"outcome": PCG_OUTCOMES.get(st.outcome, st.outcome), "iterations": st.iterations, "rel_residual": st.rel_residual}
+
         if np.asarray(solution).dtype == np.float64:  # the reference's StoreReal: narrowed / widened on the device
             x = np.ascontiguousarray(solution, dtype=np.float64)
             b = np.ascontiguousarray(rhs, dtype=np.float64)
-            st = PcgStats()
-            check(lib().mgps_solve_pcg_host_f64(self.h, _p(x), _p(b), C.c_double(tolerance), int(max_iterations), int(bool(use_mg_preconditioner)),
-                                                C.byref(st)), self.h)
-            return x, {"outcome": PCG_OUTCOMES.get(st.outcome, st.outcome), "iterations": st.iterations, "rel_residual": st.rel_residual}
+            return run(lib().mgps_solve_pcg_host_f64, x, b)
         x = _np_f32(solution)
         b = _np_f32(rhs)
-        st = PcgStats()
-        check(
-            lib().mgps_solve_pcg_host(
-                self.h, _p(x), _p(b), C.c_double(tolerance), int(max_iterations), int(bool(use_mg_preconditioner)), C.byref(st)
-            ),
-            self.h,
-        )
-        return x, {"outcome": PCG_OUTCOMES.get(st.outcome, st.outcome), "iterations": st.iterations, "rel_residual": st.rel_residual}
+        return run(lib().mgps_solve_pcg_host, x, b)

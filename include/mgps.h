@@ -108,9 +108,16 @@ typedef struct mgps_options {
                                direction (p = z).  +1.5..3 % solve time at 512^3, 16 B per fine cell of memory.  Not with
                                precision = 1 (falls back to 0) */
     int (*interrupt)(void *user); /* non-zero stops the call with MGPS_ERR_INTERRUPTED (UT_Interrupt::opInterrupt, which the
-                                     reference polls in every operator loop, e.g. Ops.h:319).  Polled before every PCG
-                                     iteration and, on single-device solvers, before every level of both strokes of a
-                                     V-cycle (host side: the device runs at most one cycle behind) */
+                                     reference polls in every operator loop, e.g. Ops.h:319).  Polled at the top of every PCG
+                                     iteration and, on single-device solvers, inside the fp32 V-cycle: going down before
+                                     every level but the fine one and the bottom (L - 2 polls with L levels), coming up
+                                     before every level above the bottom (L - 1 polls).  The first poll of a solve is
+                                     inside the first preconditioner application, before the first iteration; a solve of
+                                     K iterations polls (2 L - 3) (K + 1) + K times.  The binary16 cycle (precision = 1)
+                                     and slab solvers poll at the top of an iteration only (slab ranks agree on the answer
+                                     there: a non-zero answer on any rank stops all of them in the same iteration).
+                                     Nothing is launched after a non-zero answer but what hands back the iterate (see
+                                     mgps_solve_pcg); host side: the device runs at most one cycle behind */
     void *interrupt_user;
     /* full-domain smoother sweeps per stroke.  The reference hard-wires one (MG.cpp:466-486 down, 740-757 up): one
        damped-Jacobi sweep, or the two tile colours of Gauss-Seidel once each.  pre_sweeps applies to the down-stroke of
@@ -163,7 +170,7 @@ typedef struct mgps_options {
 
 typedef struct mgps_pcg_stats {
     int outcome;                   /* MGPS_PCG_* */
-    int iterations;                /* value of `iteration` printed at CG.h:198 */
+    int iterations;                /* value of `iteration` printed at CG.h:198 (after MGPS_ERR_INTERRUPTED: see mgps_solve_pcg) */
     double rel_residual;           /* "Drifted relative L2 Error", CG.h:199-200 */
     double rel_residual_recomputed;/* "Recomputed relative L2 Error", CG.h:203-206 */
     double rhs_norm2;
@@ -349,7 +356,18 @@ int mgps_zero_inactive(mgps_solver *h, int level, float *grid_dev);
 
 /* solveGeometricConjugateGradient (CG.h:18-207) with A = applyPoissonMatrix and
  * M^-1 = applyVCycle (use_mg_preconditioner != 0; Plug.cpp:461-484) or the diagonal
- * preconditioner (0; Plug.cpp:485-618).  x_dev holds the initial guess and receives the solution. */
+ * preconditioner (0; Plug.cpp:485-618).  x_dev holds the initial guess and receives the solution.
+ *
+ * After MGPS_ERR_INTERRUPTED (options.interrupt) x_dev holds an iterate of the loop, never a scratch state of it: the sum of the
+ * initial guess and the updates alpha p applied before the poll that stopped the solve, rounded to fp32 once -- bit for bit
+ * (pcg_fp64_vectors = 0) or to the last place (1, 2) what the same call returns with max_iterations = that number of
+ * updates; the initial guess itself when the poll came before the first update.  With options.enclosed_liquid it has mean zero
+ * on every enclosed component, like the result of every other exit.  The stats say which iterate: outcome =
+ * MGPS_PCG_MAX_ITERATIONS, iterations = the loop counter at the stop, rel_residual = the loop's residual of the iterate handed
+ * back (rel_residual_recomputed is not evaluated: 0), rhs_norm2 and solve_ms as usual.  A poll at the top of iteration i stops
+ * with i updates applied; a poll inside the V-cycle of iteration i comes after that iteration's update: i + 1 updates, iterations
+ * = i.  The same holds on a best-effort basis after any other failure inside the loop (MGPS_ERR_HIP, MGPS_ERR_COMM); slab
+ * ranks then skip the enclosed-liquid projection, which needs the other ranks. */
 int mgps_solve_pcg(mgps_solver *h, float *x_dev, const float *b_dev, double tolerance,
                    int max_iterations, int use_mg_preconditioner, mgps_pcg_stats *stats);
 
@@ -545,7 +563,11 @@ int mgps_swept_cells(const mgps_solver *h, int level, long long *stencil_cells, 
  * decide): 1 = the cache-served quad kernel, 2 = the plane-marching kernel, 3 = the scalar kernel (nx % 4 != 0). */
 int mgps_stencil_kernel(const mgps_solver *h, int level, int *kernel);
 
-/* Host-buffer convenience forms: what the Houdini shim calls (upload, run, download). */
+/* Host-buffer convenience forms: what the Houdini shim calls (upload, run, download).  A call that fails leaves x_host as it was
+ * passed in, with one exception: the two mgps_solve_pcg_host forms return MGPS_ERR_INTERRUPTED with the iterate in x_host and
+ * the stats filled in, exactly as mgps_solve_pcg leaves its x_dev (the one-call projection publishes that iterate, and the
+ * reference's UT_Interrupt exits leave whatever its loops reached).  An interrupted mgps_apply_vcycle_host has no iterate to
+ * hand back and downloads nothing. */
 int mgps_apply_vcycle_host(mgps_solver *h, float *x_host, const float *b_host, int use_initial_guess);
 int mgps_solve_pcg_host(mgps_solver *h, float *x_host, const float *b_host, double tolerance,
                         int max_iterations, int use_mg_preconditioner, mgps_pcg_stats *stats);

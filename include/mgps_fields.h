@@ -131,7 +131,10 @@ typedef struct mgps_projection {
     double surface_pressure_max;       /* result: the largest |p_G| applied (pressure units); 0 when off */
 } mgps_projection;
 /* status MGPS_ERR_HIERARCHY with outcome MGPS_PCG_RHS_ZERO-like early outs are reported through stats.outcome; a domain
- * without liquid returns MGPS_OK with liquid_cells = 0 and leaves velocity and pressure untouched */
+ * without liquid returns MGPS_OK with liquid_cells = 0 and leaves velocity and pressure untouched.
+ * MGPS_ERR_INTERRUPTED (opt->interrupt): the call still publishes -- pressure and velocity are those of the iterate
+ * mgps_solve_pcg hands back (include/mgps.h), i.e. of the same call with max_iterations = the updates applied before the stop;
+ * stats says which (outcome MGPS_PCG_MAX_ITERATIONS, iterations), residual_inf / residual_l2 are not evaluated (0) */
 int mgps_project_free_surface(mgps_projection *p, const mgps_options *opt);
 
 #ifdef __cplusplus

@@ -376,6 +376,64 @@ def violation_mode():
             print(f"  violation on rank {bad_rank}, host_setup={host_setup}, device weights={on_device}: rank 0 got '{msg[:90]}'", flush=True)
 
 
+def interrupt_mode():
+    """options.interrupt on slab solvers: the callback answers 1 on rank 1 alone, at its 4th poll.  Slab runs poll at the top of
+    every CG iteration only and agree on the answer through an all-reduce (max over the ranks), so every rank must come back
+    with MGPS_ERR_INTERRUPTED from the top of iteration 3, after the same number of polls, and the gathered x must be the
+    whole-grid solver's solve capped at three iterations (to the bound gpu_mode puts on slab against whole MG-PCG, 1e-4)."""
+    import ctypes as C
+
+    import geometricmultigridpressuresolver_amd as G
+    from conftest import make_domain
+    from geometricmultigridpressuresolver_amd import domains as D
+    from geometricmultigridpressuresolver_amd.distributed import SlabSolver, TorchDistComm
+
+    rank, size = dist.get_rank(), dist.get_world_size()
+    torch.cuda.set_device(0)
+    lab, w, off, lev, dx = make_domain("simple", 40 if size == 2 else 48, 4, (64, 64, 64))
+    nz = lab.shape[0]
+    nzl = nz // size
+    z0, z1 = rank * nzl, (rank + 1) * nzl
+    slab_w = [w[0][z0:z1], w[1][z0:z1], w[2][z0 : z1 + 1]]
+    b = D.random_rhs(lab, dx)
+    polls = []
+
+    def poll(user):
+        polls.append(1)
+        return int(rank == 1 and len(polls) >= 4)
+
+    cb = C.CFUNCTYPE(C.c_int, C.c_void_p)(poll)
+    for use_gs in (False, True):
+        del polls[:]
+        opt = G.default_options()
+        opt.min_cells_per_rank = 0
+        opt.interrupt = C.cast(cb, C.c_void_p)
+        slab = SlabSolver(lab, slab_w, lev, use_gs, TorchDistComm(), device=0, options=opt)
+        whole = G.GeometricMultigridPoissonSolver(lab, w, lev, use_gs, device=0)
+        xs = slab.new_grid()
+        try:
+            slab.solveGeometricConjugateGradient(xs, slab.to_device(b[z0:z1]), 1e-12, 200, True)
+        except G.MgpsError as e:
+            status, stats = e.status, e.stats
+        else:
+            raise AssertionError(f"rank {rank}: the solve was not interrupted")
+        assert status == 9 and len(polls) == 4, (rank, status, len(polls))
+        assert stats["outcome"] == "max_iterations" and stats["iterations"] == 3, (rank, stats)
+        seen = [None] * size
+        dist.all_gather_object(seen, (status, stats["iterations"], len(polls)))
+        assert all(v == seen[0] for v in seen), seen
+        xw = whole.new_grid()
+        sw = whole.solveGeometricConjugateGradient(xw, whole.to_device(b), 1e-12, 3, True)
+        assert sw["outcome"] == "max_iterations" and sw["iterations"] == 3
+        err = rel_l2(slab.gather_global(xs), xw.cpu().numpy())
+        assert float(xw.abs().max()) > 0 and err < 1e-4, (use_gs, err)
+        if rank == 0:
+            print(f"  interrupt on rank 1 of {size}, gs={use_gs}: every rank left iteration 3, x {err:.1e} from the whole grid's third iterate", flush=True)
+        slab.close()
+        whole.close()
+        dist.barrier()
+
+
 def cpu_mode():
     """Slab emulation on the CPU (no GPU involved): tests/slab_emulation.py over gloo vs the
     whole-grid oracle."""
@@ -476,6 +534,8 @@ if __name__ == "__main__":
         rccl_single_rank_mode()
     elif mode == "violation":
         violation_mode()
+    elif mode == "interrupt":
+        interrupt_mode()
     elif mode == "cpu":
         cpu_mode()
     else:

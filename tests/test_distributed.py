@@ -95,6 +95,14 @@ def test_slab_setup_failure_on_one_rank_reaches_every_rank(nproc):
 
 
 @pytest.mark.gpu
+def test_slab_interrupt_on_one_rank_stops_every_rank():
+    """options.interrupt fires on rank 1 only: the ranks agree through the all-reduce of interruptRequested, every one returns
+    MGPS_ERR_INTERRUPTED from the same iteration, and the gathered x is the whole grid's iterate of that iteration."""
+    out = run_workers("interrupt", 2, 300)
+    print(out[-600:])
+
+
+@pytest.mark.gpu
 def test_rccl_transport_single_rank():
     """The production transport (librccl through dlopen) with a world of one."""
     run_workers("rccl1", 1, 300)

@@ -379,10 +379,10 @@ def test_pcg_fp64_vectors(kind, g, use_mg, use_gs, domain_factory, oracle, torch
     assert rel_l2(x64, x_ref) < (2e-5 if use_mg else 2e-3)
 
 
-@pytest.mark.parametrize("fp64", [0, 1])
+@pytest.mark.parametrize("fp64", [0, 1, 2])
 def test_pcg_interrupt_callback(fp64, domain_factory, torch_cuda):
-    """options.interrupt (the reference polls UT_Interrupt::opInterrupt in every loop, e.g. Ops.h:319): polled before
-    every CG iteration and before every level of both strokes of the preconditioning V-cycle; a non-zero answer stops
+    """options.interrupt (the reference polls UT_Interrupt::opInterrupt in every loop, e.g. Ops.h:319): polled at the top of
+    every CG iteration and inside the preconditioning V-cycle (2 L - 3 polls per cycle: tests/test_pcg_exits.py); a non-zero answer stops
     the solve with MGPS_ERR_INTERRUPTED and leaves the iterate reached so far in x.  A callback that never fires changes
     nothing."""
     import ctypes as C
