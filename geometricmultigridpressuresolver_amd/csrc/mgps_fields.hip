@@ -251,6 +251,29 @@ __device__ __forceinline__ bool isInterfaceCell(const Box &g, const int32_t *__r
 }
 inline dim3 cellGrid(int gx, int gy, int gz) { return dim3(unsigned((gx + 255) / 256), unsigned(gy), unsigned(gz)); }
 
+// scale * clamp(kappa, -1, 1) of the cell (i, j, k): the 19-point curvature from `at(x, y, z)`, the neighbour indices already
+// clamped into the grid.  Shared by the whole-grid pass and the slab pass, which differ in how `at` finds a plane.
+template <class At>
+__device__ __forceinline__ float surfacePressureAt(At at, double scale, int i, int im, int ip, int j, int jm, int jp, int k, int km, int kp)
+{
+    const double p0 = at(i, j, k);
+    const double pxm = at(im, j, k), pxp = at(ip, j, k), pym = at(i, jm, k), pyp = at(i, jp, k), pzm = at(i, j, km), pzp = at(i, j, kp);
+    const double fx = 0.5 * (pxp - pxm), fy = 0.5 * (pyp - pym), fz = 0.5 * (pzp - pzm);
+    const double fxx = pxp - 2.0 * p0 + pxm, fyy = pyp - 2.0 * p0 + pym, fzz = pzp - 2.0 * p0 + pzm;
+    const double fxy = 0.25 * (at(ip, jp, k) - at(ip, jm, k) - at(im, jp, k) + at(im, jm, k));
+    const double fxz = 0.25 * (at(ip, j, kp) - at(ip, j, km) - at(im, j, kp) + at(im, j, km));
+    const double fyz = 0.25 * (at(i, jp, kp) - at(i, jp, km) - at(i, jm, kp) + at(i, jm, km));
+    const double gx2 = fx * fx, gy2 = fy * fy, gz2 = fz * fz, g2 = gx2 + gy2 + gz2;
+    double kappa = 0.0;
+    if (g2 >= 1e-30) {
+        const double num = fxx * (gy2 + gz2) + fyy * (gx2 + gz2) + fzz * (gx2 + gy2) - 2.0 * fx * fy * fxy - 2.0 * fx * fz * fxz -
+                           2.0 * fy * fz * fyz;
+        kappa = num / (g2 * sqrt(g2));
+    }
+    kappa = fmin(fmax(kappa, -1.0), 1.0);
+    return float(scale * kappa);
+}
+
 // sp = scale * clamp(kappa, -1, 1) at every LIQUID or AIR cell with a 6-neighbour of the other kind, 0 elsewhere.  kappa is the
 // mean curvature div(grad phi / |grad phi|) from unit-spacing central differences (19 points, indices clamped into the grid),
 // evaluated in double: only interface cells do it, and they are a thin shell.
@@ -265,22 +288,7 @@ __global__ __launch_bounds__(256) void surfacePressureKernel(Box g, float *__res
         const int im = max(i - 1, 0), ip = min(i + 1, g.gx - 1), jm = max(j - 1, 0), jp = min(j + 1, g.gy - 1), km = max(k - 1, 0),
                   kp = min(k + 1, g.gz - 1);
         auto at = [&](int x, int y, int z) { return double(phi[cellAt(g, x, y, z)]); };
-        const double p0 = at(i, j, k);
-        const double pxm = at(im, j, k), pxp = at(ip, j, k), pym = at(i, jm, k), pyp = at(i, jp, k), pzm = at(i, j, km), pzp = at(i, j, kp);
-        const double fx = 0.5 * (pxp - pxm), fy = 0.5 * (pyp - pym), fz = 0.5 * (pzp - pzm);
-        const double fxx = pxp - 2.0 * p0 + pxm, fyy = pyp - 2.0 * p0 + pym, fzz = pzp - 2.0 * p0 + pzm;
-        const double fxy = 0.25 * (at(ip, jp, k) - at(ip, jm, k) - at(im, jp, k) + at(im, jm, k));
-        const double fxz = 0.25 * (at(ip, j, kp) - at(ip, j, km) - at(im, j, kp) + at(im, j, km));
-        const double fyz = 0.25 * (at(i, jp, kp) - at(i, jp, km) - at(i, jm, kp) + at(i, jm, km));
-        const double gx2 = fx * fx, gy2 = fy * fy, gz2 = fz * fz, g2 = gx2 + gy2 + gz2;
-        double kappa = 0.0;
-        if (g2 >= 1e-30) {
-            const double num = fxx * (gy2 + gz2) + fyy * (gx2 + gz2) + fzz * (gx2 + gy2) - 2.0 * fx * fy * fxy - 2.0 * fx * fz * fxz -
-                               2.0 * fy * fz * fyz;
-            kappa = num / (g2 * sqrt(g2));
-        }
-        kappa = fmin(fmax(kappa, -1.0), 1.0);
-        out = float(scale * kappa);
+        out = surfacePressureAt(at, scale, i, im, ip, j, jm, jp, k, km, kp);
     }
     sp[c] = out;
 }
@@ -904,6 +912,933 @@ try {
     p->solve_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
     p->total_ms = std::chrono::duration<double, std::milli>(t3 - t0).count();
     if (solveRc != MGPS_OK) setLastGlobalError("mgps_project_free_surface: interrupted");
+    return solveRc;
+}
+MGPS_API_CATCH(nullptr)
+
+}  // extern "C"
+
+// ---- the fields layer on Z-slabs (include/mgps_fields.h) ---------------------------------------------------
+// Kernels for a z-window of the grid: one thread per cell (or per face triple) of a (ceil(nx / 256), ny, planes) launch, so the
+// index costs no 64-bit division.  What a pass reads of a neighbour rank's planes arrives in halo planes; a neighbour outside the
+// WHOLE grid is ignored, as the whole-grid kernels ignore it.  The per-cell arithmetic is that of the kernels above (ghostFluidTheta,
+// cellDivergence, surfacePressureAt, interfacePressure).
+namespace {
+struct Slab {
+    int gx, gy, gz, c0, c1, ex, ey, ez, off, e0, e1;
+    __host__ __device__ Box base() const { return Box{gx, gy, c1 - c0}; }    // the window of the base grid
+    __host__ __device__ Box window() const { return Box{ex, ey, e1 - e0}; }  // the window of the expanded grid
+};
+// a window of a base cell grid with the neighbours' planes next to it
+template <class T>
+struct Planes {
+    const T *own, *lo, *hi;
+};
+// value at base cell (i, j, kg), kg a plane of the whole grid in [c0 - 1, c1] (callers never ask for a plane outside the grid)
+template <class T>
+__device__ __forceinline__ T zAt(const Slab &s, const Planes<T> &p, int i, int j, int kg)
+{
+    const size_t ij = size_t(j) * s.gx + i;
+    if (kg < s.c0) return p.lo[ij];
+    if (kg >= s.c1) return p.hi[ij];
+    return p.own[size_t(kg - s.c0) * s.gy * s.gx + ij];
+}
+__device__ __forceinline__ void threadCell(int &i, int &j, int &k)
+{
+    i = int(blockIdx.x * blockDim.x + threadIdx.x);
+    j = int(blockIdx.y);
+    k = int(blockIdx.z);
+}
+
+__global__ __launch_bounds__(256) void materialLabelsSlabKernel(Slab s, int32_t *__restrict__ material, Planes<float> phi,
+                                                                const float *__restrict__ solidPhi, const float *__restrict__ cwx,
+                                                                const float *__restrict__ cwy, const float *__restrict__ cwz)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i >= s.gx) return;
+    const Box g = s.base();
+    const float *cw[3] = {cwx, cwy, cwz};
+    const int ext[3] = {s.gx, s.gy, s.gz};
+    const int kg = s.c0 + k;
+    const size_t c = cellAt(g, i, j, k);
+    bool open[3][2], inFluid = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            open[a][d] = cw[a][cellFace(g, a, d, i, j, k)] > 0.f;
+            inFluid = inFluid || open[a][d];
+        }
+    int label = kSolid;
+    if (inFluid) {
+        bool liquid = phi.own[c] <= 0.f;
+        if (!liquid && solidPhi[c] >= 0.f) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int d = 0; d < 2; ++d) {
+                    int n[3] = {i, j, kg};
+                    n[a] += d ? 1 : -1;
+                    if (open[a][d] && n[a] >= 0 && n[a] < ext[a] && zAt(s, phi, n[0], n[1], n[2]) <= 0.f) liquid = true;
+                }
+        }
+        label = liquid ? kLiquid : kAir;
+    }
+    material[c] = label;
+}
+
+// valid flag and expanded weight of the base face of `axis` in front of base cell (bi, bj, bkg): validFacesKernel +
+// boundaryWeightsKernel on one face
+__device__ __forceinline__ float faceWeight(const Slab &s, int axis, int bi, int bj, int bkg, float cwf, const Planes<int32_t> &mat,
+                                            const Planes<float> &phi, uint8_t &valid)
+{
+    const int ext[3] = {s.gx, s.gy, s.gz};
+    int b[3] = {bi, bj, bkg}, f[3] = {bi, bj, bkg};
+    b[axis] -= 1;
+    valid = 0;
+    float w = 0.f;
+    if (cwf > 0.f && b[axis] >= 0 && f[axis] < ext[axis]) {
+        const int mb = zAt(s, mat, b[0], b[1], b[2]), mf = zAt(s, mat, f[0], f[1], f[2]);
+        valid = mb == kLiquid || mf == kLiquid;
+        if (valid) {
+            w = cwf;
+            if ((mb == kLiquid && mf == kAir) || (mb == kAir && mf == kLiquid))
+                w /= ghostFluidTheta(zAt(s, phi, b[0], b[1], b[2]), zAt(s, phi, f[0], f[1], f[2]));
+        }
+    }
+    return w;
+}
+
+// One thread per (i, j, k) of the window's expanded face grids, (ex + 1) x (ey + 1) x (planes + 1): the x-, y- and z-face in front
+// of expanded cell (i, j, e0 + k).  Writes the three expanded weights everywhere (0 outside the base box) and the valid flags.
+__global__ __launch_bounds__(256) void facesSlabKernel(Slab s, uint8_t *__restrict__ vx, uint8_t *__restrict__ vy, uint8_t *__restrict__ vz,
+                                                       float *__restrict__ wx, float *__restrict__ wy, float *__restrict__ wz,
+                                                       Planes<int32_t> mat, Planes<float> phi, const float *__restrict__ cwx,
+                                                       const float *__restrict__ cwy, const float *__restrict__ cwz)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i > s.ex) return;
+    const Box g = s.base(), e = s.window();
+    const int bi = i - s.off, bj = j - s.off, bkg = s.e0 + k - s.off, bk = bkg - s.c0;
+    const bool inX = bi >= 0 && bi < s.gx, inY = bj >= 0 && bj < s.gy, inZ = bkg >= s.c0 && bkg < s.c1;
+    uint8_t v;
+    if (j < s.ey && k < e.gz) {  // x-face
+        float w = 0.f;
+        if (bi >= 0 && bi <= s.gx && inY && inZ) {
+            const size_t f = faceAt(g, 0, bi, bj, bk);
+            w = faceWeight(s, 0, bi, bj, bkg, cwx[f], mat, phi, v);
+            vx[f] = v;
+        }
+        wx[faceAt(e, 0, i, j, k)] = w;
+    }
+    if (i < s.ex && k < e.gz) {  // y-face
+        float w = 0.f;
+        if (inX && bj >= 0 && bj <= s.gy && inZ) {
+            const size_t f = faceAt(g, 1, bi, bj, bk);
+            w = faceWeight(s, 1, bi, bj, bkg, cwy[f], mat, phi, v);
+            vy[f] = v;
+        }
+        wy[faceAt(e, 1, i, j, k)] = w;
+    }
+    if (i < s.ex && j < s.ey) {  // z-face (the window holds the faces c0 .. c1)
+        float w = 0.f;
+        if (inX && inY && bkg >= s.c0 && bkg <= s.c1) {
+            const size_t f = faceAt(g, 2, bi, bj, bk);
+            w = faceWeight(s, 2, bi, bj, bkg, cwz[f], mat, phi, v);
+            vz[f] = v;
+        }
+        wz[faceAt(e, 2, i, j, k)] = w;
+    }
+}
+
+// domain label of base cell (bi, bj, bkg): EXTERIOR outside the base box (domainLabelsKernel + its fill)
+__device__ __forceinline__ int domainLabelAt(const Slab &s, const Planes<int32_t> &mat, int bi, int bj, int bkg)
+{
+    if (bi < 0 || bi >= s.gx || bj < 0 || bj >= s.gy || bkg < 0 || bkg >= s.gz) return MGPS_EXTERIOR_CELL;
+    const int m = zAt(s, mat, bi, bj, bkg);
+    return m == kLiquid ? MGPS_INTERIOR_CELL : m == kAir ? MGPS_DIRICHLET_CELL : MGPS_EXTERIOR_CELL;
+}
+
+// domainLabelsKernel + setBoundaryLabelsKernel on the window: the neighbours' labels come from the material labels, so nothing
+// is updated in place
+__global__ __launch_bounds__(256) void labelsSlabKernel(Slab s, uint8_t *__restrict__ lab, Planes<int32_t> mat, const float *__restrict__ wx,
+                                                        const float *__restrict__ wy, const float *__restrict__ wz)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i >= s.ex) return;
+    const Box e = s.window();
+    const int bi = i - s.off, bj = j - s.off, bkg = s.e0 + k - s.off;
+    int label = domainLabelAt(s, mat, bi, bj, bkg);
+    if (label == MGPS_INTERIOR_CELL) {
+        const float *w[3] = {wx, wy, wz};
+        bool bnd = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                int n[3] = {bi, bj, bkg};
+                n[a] += d ? 1 : -1;
+                const int nl = domainLabelAt(s, mat, n[0], n[1], n[2]);
+                bnd = bnd || nl == MGPS_DIRICHLET_CELL || nl == MGPS_EXTERIOR_CELL || w[a][cellFace(e, a, d, i, j, k)] != 1.f;
+            }
+        if (bnd) label = MGPS_BOUNDARY_CELL;
+    }
+    lab[cellAt(e, i, j, k)] = uint8_t(label);
+}
+
+// rhsKernel / pressureToSolutionKernel on the window's expanded planes, written everywhere
+__global__ __launch_bounds__(256) void rhsSlabKernel(Slab s, float *__restrict__ rhs, const int32_t *__restrict__ material, const float *vx,
+                                                     const float *vy, const float *vz, const float *svx, const float *svy, const float *svz,
+                                                     const float *cwx, const float *cwy, const float *cwz)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i >= s.ex) return;
+    const Box g = s.base(), e = s.window();
+    const int bi = i - s.off, bj = j - s.off, bk = s.e0 + k - s.off - s.c0;
+    float out = 0.f;
+    if (bi >= 0 && bi < g.gx && bj >= 0 && bj < g.gy && bk >= 0 && bk < g.gz && material[cellAt(g, bi, bj, bk)] == kLiquid) {
+        const float *v[3] = {vx, vy, vz}, *sv[3] = {svx, svy, svz}, *cw[3] = {cwx, cwy, cwz};
+        out = cellDivergence(g, bi, bj, bk, 1.f, v, sv, cw);
+    }
+    rhs[cellAt(e, i, j, k)] = out;
+}
+
+__global__ __launch_bounds__(256) void pressureToSolutionSlabKernel(Slab s, float *__restrict__ x, const float *__restrict__ pressure,
+                                                                    const int32_t *__restrict__ material)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i >= s.ex) return;
+    const Box g = s.base(), e = s.window();
+    const int bi = i - s.off, bj = j - s.off, bk = s.e0 + k - s.off - s.c0;
+    float out = 0.f;
+    if (bi >= 0 && bi < g.gx && bj >= 0 && bj < g.gy && bk >= 0 && bk < g.gz) {
+        const size_t c = cellAt(g, bi, bj, bk);
+        if (material[c] == kLiquid) out = pressure[c];
+    }
+    x[cellAt(e, i, j, k)] = out;
+}
+
+__global__ __launch_bounds__(256) void solutionToPressureSlabKernel(Slab s, float *__restrict__ pressure, const float *__restrict__ x,
+                                                                    const int32_t *__restrict__ material, int clearOthers)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i >= s.gx) return;
+    const Box g = s.base(), e = s.window();
+    const size_t c = cellAt(g, i, j, k);
+    if (material[c] == kLiquid) pressure[c] = x[cellAt(e, i + s.off, j + s.off, s.c0 + k + s.off - s.e0)];
+    else if (clearOthers) pressure[c] = 0.f;
+}
+
+// pressureGradientKernel (sp.own == NULL) / pressureGradientSurfaceKernel on the face of `axis` in front of base cell (bi, bj, bkg)
+__device__ __forceinline__ float faceGradient(const Slab &s, int axis, int bi, int bj, int bkg, const Planes<float> &phi,
+                                              const Planes<float> &pr, const Planes<float> &sp, const Planes<int32_t> &mat)
+{
+    int b[3] = {bi, bj, bkg};
+    b[axis] -= 1;
+    const bool lb = zAt(s, mat, b[0], b[1], b[2]) == kLiquid, lf = zAt(s, mat, bi, bj, bkg) == kLiquid;
+    float pb = zAt(s, pr, b[0], b[1], b[2]), pf = zAt(s, pr, bi, bj, bkg);
+    if (!sp.own) {
+        float grad = pf - pb;
+        if (!lb || !lf) grad /= ghostFluidTheta(zAt(s, phi, b[0], b[1], b[2]), zAt(s, phi, bi, bj, bkg));
+        return grad;
+    }
+    if (lb && lf) return pf - pb;
+    const float theta = ghostFluidTheta(zAt(s, phi, b[0], b[1], b[2]), zAt(s, phi, bi, bj, bkg));
+    const float pg = interfacePressure(theta, lb, zAt(s, sp, b[0], b[1], b[2]), zAt(s, sp, bi, bj, bkg));
+    if (lb) pf = pg;
+    else pb = pg;
+    return (pf - pb) / theta;
+}
+
+// One thread per (i, j, k) of the window's base face grids, (gx + 1) x (gy + 1) x (planes + 1): the three faces in front of base
+// cell (i, j, c0 + k).  A valid face has both cells inside the whole grid, so no halo is read past it.
+__global__ __launch_bounds__(256) void pressureGradientSlabKernel(Slab s, float *__restrict__ velx, float *__restrict__ vely,
+                                                                  float *__restrict__ velz, Planes<float> phi, Planes<float> pr,
+                                                                  Planes<float> sp, const uint8_t *__restrict__ vx,
+                                                                  const uint8_t *__restrict__ vy, const uint8_t *__restrict__ vz,
+                                                                  Planes<int32_t> mat)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i > s.gx) return;
+    const Box g = s.base();
+    const int kg = s.c0 + k;
+    if (j < s.gy && k < g.gz) {
+        const size_t f = faceAt(g, 0, i, j, k);
+        if (vx[f]) velx[f] -= faceGradient(s, 0, i, j, kg, phi, pr, sp, mat);
+    }
+    if (i < s.gx && k < g.gz) {
+        const size_t f = faceAt(g, 1, i, j, k);
+        if (vy[f]) vely[f] -= faceGradient(s, 1, i, j, kg, phi, pr, sp, mat);
+    }
+    if (i < s.gx && j < s.gy) {
+        const size_t f = faceAt(g, 2, i, j, k);
+        if (vz[f]) velz[f] -= faceGradient(s, 2, i, j, kg, phi, pr, sp, mat);
+    }
+}
+
+// isInterfaceCell with the z-neighbours through the halo planes
+__device__ __forceinline__ bool isInterfaceCellSlab(const Slab &s, const Planes<int32_t> &mat, int i, int j, int kg, int m)
+{
+    const int n[6] = {zAt(s, mat, i > 0 ? i - 1 : i, j, kg),       zAt(s, mat, i + 1 < s.gx ? i + 1 : i, j, kg),
+                      zAt(s, mat, i, j > 0 ? j - 1 : j, kg),       zAt(s, mat, i, j + 1 < s.gy ? j + 1 : j, kg),
+                      zAt(s, mat, i, j, kg > 0 ? kg - 1 : kg),     zAt(s, mat, i, j, kg + 1 < s.gz ? kg + 1 : kg)};
+    const int other = m == kLiquid ? kAir : kLiquid;
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) any |= n[q] == other;
+    return (m == kLiquid || m == kAir) && any;
+}
+
+__global__ __launch_bounds__(256) void surfacePressureSlabKernel(Slab s, float *__restrict__ sp, Planes<float> phi, Planes<int32_t> mat,
+                                                                 double scale)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i >= s.gx) return;
+    const Box g = s.base();
+    const int kg = s.c0 + k;
+    const size_t c = cellAt(g, i, j, k);
+    float out = 0.f;
+    if (isInterfaceCellSlab(s, mat, i, j, kg, mat.own[c])) {
+        const int im = max(i - 1, 0), ip = min(i + 1, s.gx - 1), jm = max(j - 1, 0), jp = min(j + 1, s.gy - 1), km = max(kg - 1, 0),
+                  kp = min(kg + 1, s.gz - 1);
+        auto at = [&](int x, int y, int z) { return double(zAt(s, phi, x, y, z)); };
+        out = surfacePressureAt(at, scale, i, im, ip, j, jm, jp, kg, km, kp);
+    }
+    sp[c] = out;
+}
+
+// rhsSurfaceKernel on the window: the expanded weights are the window's (what facesSlabKernel wrote)
+__global__ __launch_bounds__(256) void rhsSurfaceSlabKernel(Slab s, float *__restrict__ rhs, const float *wx, const float *wy, const float *wz,
+                                                            Planes<float> phi, Planes<int32_t> mat, Planes<float> sp,
+                                                            unsigned *__restrict__ pGammaMax)
+{
+    int bi, bj, bk;
+    threadCell(bi, bj, bk);
+    float amax = 0.f;
+    // (no early return: every lane reaches the wave reduction below)
+    const bool inside = bi < s.gx;
+    const Box g = s.base(), e = s.window();
+    const int kg = s.c0 + bk;
+    const size_t c = inside ? cellAt(g, bi, bj, bk) : 0;
+    const int m = inside ? mat.own[c] : kSolid;
+    if (inside && isInterfaceCellSlab(s, mat, bi, bj, kg, m) && m == kLiquid) {
+        const float *w[3] = {wx, wy, wz};
+        const int ext[3] = {s.gx, s.gy, s.gz};
+        const int ei = bi + s.off, ej = bj + s.off, ek = kg + s.off - s.e0;
+        const size_t ec = cellAt(e, ei, ej, ek);
+        float acc = rhs[ec];
+        bool touched = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                int n[3] = {bi, bj, kg};
+                n[a] += d ? 1 : -1;
+                if (n[a] < 0 || n[a] >= ext[a]) continue;
+                if (zAt(s, mat, n[0], n[1], n[2]) != kAir) continue;
+                const float wf = w[a][cellFace(e, a, d, ei, ej, ek)];
+                if (wf == 0.f) continue;  // not a valid face
+                const float phc = phi.own[c], phn = zAt(s, phi, n[0], n[1], n[2]);
+                const float spc = sp.own[c], spn = zAt(s, sp, n[0], n[1], n[2]);
+                const float theta = d ? ghostFluidTheta(phc, phn) : ghostFluidTheta(phn, phc);
+                const float pg = interfacePressure(theta, d == 1, d ? spc : spn, d ? spn : spc);
+                acc += wf * pg;
+                amax = fmaxf(amax, fabsf(pg));
+                touched = true;
+            }
+        if (touched) rhs[ec] = acc;
+    }
+    if (!pGammaMax) return;
+    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+    if ((threadIdx.x & 63) == 0 && amax > 0.f) atomicMax(pGammaMax, __float_as_uint(amax));
+}
+
+inline int clampInt(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+// the descriptor as the kernels take it; false with a message when it is not a window of a layout
+bool readSlab(const mgps_fields_slab *d, Slab &s, const char *what)
+{
+    bool ok = d && d->struct_size == int(sizeof(mgps_fields_slab));
+    if (ok) {
+        s = Slab{d->gx, d->gy, d->gz, d->c0, d->c1, d->ex, d->ey, d->ez, d->offset, d->e0, d->e1};
+        ok = okBox(s.gx, s.gy, s.gz) && okExpanded(s.gx, s.gy, s.gz, s.ex, s.ey, s.ez, s.off) && s.e0 >= 0 && s.e0 < s.e1 && s.e1 <= s.ez &&
+             s.c0 == clampInt(s.e0 - s.off, 0, s.gz) && s.c1 == clampInt(s.e1 - s.off, 0, s.gz) && s.c0 < s.c1 &&
+             s.ey + 1 <= 65535 && s.e1 - s.e0 + 1 <= 65535;  // (y and z extents are launch-grid dimensions)
+    }
+    if (!ok) setLastGlobalError(std::string(what) + ": not a slab window (struct_size, extents, c0 < c1 = the base planes of [e0, e1))");
+    return ok;
+}
+inline dim3 rowGrid(int nx, int ny, int nz) { return dim3(unsigned((nx + 255) / 256), unsigned(ny), unsigned(nz)); }
+// halo planes: present exactly where the whole grid goes on
+template <class T>
+bool okHalo(const Slab &s, const T *own, const T *lo, const T *hi)
+{
+    return own && (s.c0 == 0 || lo) && (s.c1 == s.gz || hi);
+}
+}  // namespace
+
+extern "C" {
+
+int mgps_fields_slab_describe(mgps_fields_slab *out, int gx, int gy, int gz, int power_of_two, const int *splits, int size, int rank)
+try {
+    if (!out || !splits || size < 1 || rank < 0 || rank >= size) return bad("mgps_fields_slab_describe");
+    int dims[3], offset = 0, levels = 0;
+    if (int rc = mgps_expanded_layout(gx, gy, gz, 0, power_of_two, dims, &offset, &levels); rc != MGPS_OK) return rc;
+    bool ok = splits[0] == 0 && splits[size] == dims[2];
+    for (int r = 0; r < size && ok; ++r) ok = splits[r + 1] > splits[r];
+    if (!ok) {
+        setLastGlobalError("mgps_fields_slab_describe: the cuts must run from 0 to the expanded nz (" + std::to_string(dims[2]) + "), increasing");
+        return MGPS_ERR_INVALID_ARGUMENT;
+    }
+    for (int r = 0; r < size; ++r)
+        if (clampInt(splits[r] - offset, 0, gz) >= clampInt(splits[r + 1] - offset, 0, gz)) {
+            setLastGlobalError("mgps_fields_slab_describe: rank " + std::to_string(r) + " owns no plane of the base grid (expanded planes " +
+                               std::to_string(splits[r]) + " .. " + std::to_string(splits[r + 1]) + ", base planes at " + std::to_string(offset) +
+                               " .. " + std::to_string(offset + gz) + "): see mgps_projection_slab_layout");
+            return MGPS_ERR_INVALID_ARGUMENT;
+        }
+    *out = mgps_fields_slab{int(sizeof(mgps_fields_slab)), gx, gy, gz, clampInt(splits[rank] - offset, 0, gz), clampInt(splits[rank + 1] - offset, 0, gz),
+                            dims[0], dims[1], dims[2], offset, splits[rank], splits[rank + 1]};
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_projection_slab_layout(int gx, int gy, int gz, int power_of_two, int size, int use_gauss_seidel, int out_expanded[3],
+                                int *out_offset, int *out_levels, int *out_splits)
+try {
+    if (!out_expanded || !out_offset || !out_levels || !out_splits || size < 1) return bad("mgps_projection_slab_layout");
+    if (int rc = mgps_expanded_layout(gx, gy, gz, 0, power_of_two, out_expanded, out_offset, out_levels); rc != MGPS_OK) return rc;
+    const int ez = out_expanded[2], off = *out_offset, unit = use_gauss_seidel ? 16 : 2, minPlanes = 16;
+    auto refuse = [&](const std::string &why) {
+        setLastGlobalError("mgps_projection_slab_layout: " + std::to_string(gz) + " base planes in " + std::to_string(ez) + " expanded planes cannot be cut for " +
+                           std::to_string(size) + " ranks: " + why);
+        return int(MGPS_ERR_INVALID_ARGUMENT);
+    };
+    if (ez % unit != 0) return refuse("the expanded grid is not a multiple of the cut granule " + std::to_string(unit));
+    // Cuts on multiples of `unit`, every rank >= 16 planes and >= 1 base plane, minimising the sum of the squared base-plane counts
+    // (the most even division the granule allows): a dynamic programme over the n = ez / unit cut positions.
+    const int n = ez / unit;
+    auto basePlanes = [&](int a, int b) { return clampInt(b * unit - off, 0, gz) - clampInt(a * unit - off, 0, gz); };
+    const double kInf = 1e300;
+    std::vector<std::vector<double>> best(size_t(size) + 1, std::vector<double>(size_t(n) + 1, kInf));
+    std::vector<std::vector<int>> from(size_t(size) + 1, std::vector<int>(size_t(n) + 1, -1));
+    best[0][0] = 0.0;
+    for (int r = 1; r <= size; ++r)
+        for (int b = 1; b <= n; ++b) {
+            if (r == size && b != n) continue;
+            for (int a = 0; a < b; ++a) {
+                if (best[size_t(r) - 1][size_t(a)] >= kInf || (b - a) * unit < minPlanes) continue;
+                const int planes = basePlanes(a, b);
+                if (planes < 1) continue;
+                const double cost = best[size_t(r) - 1][size_t(a)] + double(planes) * planes;
+                if (cost < best[size_t(r)][size_t(b)]) {
+                    best[size_t(r)][size_t(b)] = cost;
+                    from[size_t(r)][size_t(b)] = a;
+                }
+            }
+        }
+    if (best[size_t(size)][size_t(n)] >= kInf)
+        return refuse("every rank needs at least 16 expanded planes and one base plane, on cuts that are multiples of " + std::to_string(unit));
+    for (int r = size, b = n; r > 0; --r) {
+        out_splits[r] = b * unit;
+        b = from[size_t(r)][size_t(b)];
+    }
+    out_splits[0] = 0;
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_material_labels(const mgps_fields_slab *d, int32_t *material, const float *liquid_phi, const float *phi_lo,
+                                     const float *phi_hi, const float *solid_phi, const float *cwx, const float *cwy, const float *cwz,
+                                     void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_material_labels")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!material || !okHalo(s, liquid_phi, phi_lo, phi_hi) || !solid_phi || !cwx || !cwy || !cwz) return bad("mgps_fields_slab_material_labels");
+    materialLabelsSlabKernel<<<rowGrid(s.gx, s.gy, s.c1 - s.c0), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        s, material, Planes<float>{liquid_phi, phi_lo, phi_hi}, solid_phi, cwx, cwy, cwz);
+    return done("mgps_fields_slab_material_labels");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_faces(const mgps_fields_slab *d, uint8_t *const valid[3], float *const expanded_weights[3], const int32_t *material,
+                           const int32_t *material_lo, const int32_t *material_hi, const float *liquid_phi, const float *phi_lo,
+                           const float *phi_hi, const float *const cut_weights[3], void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_faces")) return MGPS_ERR_INVALID_ARGUMENT;
+    bool ok = valid && expanded_weights && cut_weights && okHalo(s, material, material_lo, material_hi) && okHalo(s, liquid_phi, phi_lo, phi_hi);
+    for (int a = 0; a < 3 && ok; ++a) ok = valid[a] && expanded_weights[a] && cut_weights[a];
+    if (!ok) return bad("mgps_fields_slab_faces");
+    facesSlabKernel<<<rowGrid(s.ex + 1, s.ey + 1, s.e1 - s.e0 + 1), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        s, valid[0], valid[1], valid[2], expanded_weights[0], expanded_weights[1], expanded_weights[2],
+        Planes<int32_t>{material, material_lo, material_hi}, Planes<float>{liquid_phi, phi_lo, phi_hi}, cut_weights[0], cut_weights[1], cut_weights[2]);
+    return done("mgps_fields_slab_faces");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_labels(const mgps_fields_slab *d, uint8_t *expanded_labels, const int32_t *material, const int32_t *material_lo,
+                            const int32_t *material_hi, const float *const expanded_weights[3], void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_labels")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!expanded_labels || !okHalo(s, material, material_lo, material_hi) || !expanded_weights || !expanded_weights[0] || !expanded_weights[1] ||
+        !expanded_weights[2])
+        return bad("mgps_fields_slab_labels");
+    labelsSlabKernel<<<rowGrid(s.ex, s.ey, s.e1 - s.e0), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        s, expanded_labels, Planes<int32_t>{material, material_lo, material_hi}, expanded_weights[0], expanded_weights[1], expanded_weights[2]);
+    return done("mgps_fields_slab_labels");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_rhs(const mgps_fields_slab *d, float *expanded_rhs, const int32_t *material, const float *const velocity[3],
+                         const float *const solid_velocity[3], const float *const cut_weights[3], void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_rhs")) return MGPS_ERR_INVALID_ARGUMENT;
+    const float *sv[3] = {solid_velocity ? solid_velocity[0] : nullptr, solid_velocity ? solid_velocity[1] : nullptr, solid_velocity ? solid_velocity[2] : nullptr};
+    bool ok = expanded_rhs && material && velocity && cut_weights && (!(sv[0] || sv[1] || sv[2]) || (sv[0] && sv[1] && sv[2]));
+    for (int a = 0; a < 3 && ok; ++a) ok = velocity[a] && cut_weights[a];
+    if (!ok) return bad("mgps_fields_slab_rhs");
+    rhsSlabKernel<<<rowGrid(s.ex, s.ey, s.e1 - s.e0), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        s, expanded_rhs, material, velocity[0], velocity[1], velocity[2], sv[0], sv[1], sv[2], cut_weights[0], cut_weights[1], cut_weights[2]);
+    return done("mgps_fields_slab_rhs");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_pressure_to_solution(const mgps_fields_slab *d, float *expanded_x, const float *pressure, const int32_t *material,
+                                          void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_pressure_to_solution")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!expanded_x || !pressure || !material) return bad("mgps_fields_slab_pressure_to_solution");
+    pressureToSolutionSlabKernel<<<rowGrid(s.ex, s.ey, s.e1 - s.e0), 256, 0, static_cast<hipStream_t>(stream)>>>(s, expanded_x, pressure, material);
+    return done("mgps_fields_slab_pressure_to_solution");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_solution_to_pressure(const mgps_fields_slab *d, float *pressure, const float *expanded_x, const int32_t *material,
+                                          int clear_others, void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_solution_to_pressure")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!pressure || !expanded_x || !material) return bad("mgps_fields_slab_solution_to_pressure");
+    solutionToPressureSlabKernel<<<rowGrid(s.gx, s.gy, s.c1 - s.c0), 256, 0, static_cast<hipStream_t>(stream)>>>(s, pressure, expanded_x, material,
+                                                                                                                 clear_others);
+    return done("mgps_fields_slab_solution_to_pressure");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_pressure_gradient(const mgps_fields_slab *d, float *const velocity[3], const float *liquid_phi, const float *phi_lo,
+                                       const float *phi_hi, const float *pressure, const float *pressure_lo, const float *pressure_hi,
+                                       const float *sp, const float *sp_lo, const float *sp_hi, const uint8_t *const valid[3],
+                                       const int32_t *material, const int32_t *material_lo, const int32_t *material_hi, void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_pressure_gradient")) return MGPS_ERR_INVALID_ARGUMENT;
+    bool ok = velocity && valid && okHalo(s, liquid_phi, phi_lo, phi_hi) && okHalo(s, pressure, pressure_lo, pressure_hi) &&
+              okHalo(s, material, material_lo, material_hi) && (!sp || okHalo(s, sp, sp_lo, sp_hi));
+    for (int a = 0; a < 3 && ok; ++a) ok = velocity[a] && valid[a];
+    if (!ok) return bad("mgps_fields_slab_pressure_gradient");
+    pressureGradientSlabKernel<<<rowGrid(s.gx + 1, s.gy + 1, s.c1 - s.c0 + 1), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        s, velocity[0], velocity[1], velocity[2], Planes<float>{liquid_phi, phi_lo, phi_hi}, Planes<float>{pressure, pressure_lo, pressure_hi},
+        Planes<float>{sp, sp_lo, sp_hi}, valid[0], valid[1], valid[2], Planes<int32_t>{material, material_lo, material_hi});
+    return done("mgps_fields_slab_pressure_gradient");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_surface_pressure(const mgps_fields_slab *d, float *sp, const float *liquid_phi, const float *phi_lo,
+                                      const float *phi_hi, const int32_t *material, const int32_t *material_lo, const int32_t *material_hi,
+                                      double scale, void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_surface_pressure")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!sp || !okHalo(s, liquid_phi, phi_lo, phi_hi) || !okHalo(s, material, material_lo, material_hi)) return bad("mgps_fields_slab_surface_pressure");
+    surfacePressureSlabKernel<<<rowGrid(s.gx, s.gy, s.c1 - s.c0), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        s, sp, Planes<float>{liquid_phi, phi_lo, phi_hi}, Planes<int32_t>{material, material_lo, material_hi}, scale);
+    return done("mgps_fields_slab_surface_pressure");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_rhs_surface(const mgps_fields_slab *d, float *expanded_rhs, const float *const expanded_weights[3],
+                                 const float *liquid_phi, const float *phi_lo, const float *phi_hi, const int32_t *material,
+                                 const int32_t *material_lo, const int32_t *material_hi, const float *sp, const float *sp_lo,
+                                 const float *sp_hi, float *p_gamma_max, void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_rhs_surface")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!expanded_rhs || !expanded_weights || !expanded_weights[0] || !expanded_weights[1] || !expanded_weights[2] ||
+        !okHalo(s, liquid_phi, phi_lo, phi_hi) || !okHalo(s, material, material_lo, material_hi) || !okHalo(s, sp, sp_lo, sp_hi))
+        return bad("mgps_fields_slab_rhs_surface");
+    rhsSurfaceSlabKernel<<<rowGrid(s.gx, s.gy, s.c1 - s.c0), 256, 0, static_cast<hipStream_t>(stream)>>>(
+        s, expanded_rhs, expanded_weights[0], expanded_weights[1], expanded_weights[2], Planes<float>{liquid_phi, phi_lo, phi_hi},
+        Planes<int32_t>{material, material_lo, material_hi}, Planes<float>{sp, sp_lo, sp_hi}, reinterpret_cast<unsigned *>(p_gamma_max));
+    return done("mgps_fields_slab_rhs_surface");
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_divergence(const mgps_fields_slab *d, double out_host[3], const int32_t *material, const float *const velocity[3],
+                                const float *const solid_velocity[3], const float *const cut_weights[3], void *stream)
+try {
+    Slab s;
+    if (!readSlab(d, s, "mgps_fields_slab_divergence")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!velocity || !cut_weights) return bad("mgps_fields_slab_divergence");
+    // every face of an owned cell is in the window (the z-face grid closes with plane c1): the window is a box of its own here
+    return mgps_fields_divergence(out_host, material, velocity[0], velocity[1], velocity[2], solid_velocity ? solid_velocity[0] : nullptr,
+                                  solid_velocity ? solid_velocity[1] : nullptr, solid_velocity ? solid_velocity[2] : nullptr, cut_weights[0],
+                                  cut_weights[1], cut_weights[2], s.gx, s.gy, s.c1 - s.c0, stream);
+}
+MGPS_API_CATCH(nullptr)
+
+}  // extern "C"
+
+// ---- one-call projection on slab ranks (mgps_project_free_surface_slab) -----------------------------------------------------------
+namespace {
+// What the ranks agree on between two steps: one sum all-reduce that carries `sums`, the largest of each entry of `maxes` (every
+// rank fills its own slot of a size-wide row, so a sum is a max) and the ranks' statuses the same way.  Every rank calls it at
+// the same places; it returns this rank's failure, or the first other rank's, or MGPS_OK on every rank together.
+int agreeRanks(const mgps_comm *comm, int status, const char *where, double *sums = nullptr, int nsums = 0, double *maxes = nullptr, int nmaxes = 0)
+{
+    const int P = comm->size, rank = comm->rank;
+    std::vector<double> v(size_t(nsums) + size_t(nmaxes + 1) * size_t(P), 0.0);
+    for (int q = 0; q < nsums; ++q) v[size_t(q)] = sums[q];
+    for (int q = 0; q < nmaxes; ++q) v[size_t(nsums) + size_t(q) * P + rank] = maxes[q];
+    v[size_t(nsums) + size_t(nmaxes) * P + rank] = double(status);
+    if (comm->allreduce(comm->user, v.data(), int(v.size()), 0) != 0) {
+        setLastGlobalError(std::string("mgps_project_free_surface_slab: all-reduce failed (") + where + ")");
+        return MGPS_ERR_COMM;
+    }
+    for (int q = 0; q < nsums; ++q) sums[q] = v[size_t(q)];
+    for (int q = 0; q < nmaxes; ++q) {
+        const double *row = v.data() + size_t(nsums) + size_t(q) * P;
+        maxes[q] = *std::max_element(row, row + P);
+    }
+    if (status != MGPS_OK) return status;
+    const double *st = v.data() + size_t(nsums) + size_t(nmaxes) * P;
+    for (int r = 0; r < P; ++r)
+        if (int(st[r]) != MGPS_OK) {
+            setLastGlobalError(std::string("mgps_project_free_surface_slab: rank ") + std::to_string(r) + " failed (" + where + ", status " +
+                               std::to_string(int(st[r])) + ")");
+            return int(st[r]);
+        }
+    return MGPS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mgps_project_free_surface_slab(mgps_projection_slab *p, const mgps_options *opt, const mgps_comm *comm, const int *splits, void *stream)
+try {
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    auto invalid = [](const std::string &what) {
+        setLastGlobalError("mgps_project_free_surface_slab: " + what);
+        return int(MGPS_ERR_INVALID_ARGUMENT);
+    };
+    // ---- what every rank shares: a refusal here is every rank's, before any collective
+    if (!p || p->struct_size != int(sizeof(mgps_projection_slab))) return invalid("NULL or struct_size mismatch");
+    if (!comm || !splits || comm->struct_size < int(offsetof(mgps_comm, gatherv)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange ||
+        !comm->allreduce || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
+        return invalid("a complete mgps_comm and the cuts are required");
+    mgps_comm cm{};
+    std::memcpy(&cm, comm, size_t(comm->struct_size));  // (struct_size bytes are the caller's; the rest reads as NULL)
+    cm.struct_size = int(sizeof(mgps_comm));
+    const int P = cm.size, rank = cm.rank;
+    if (P > 1 && (!cm.gatherv || !cm.scatterv)) return invalid("the whole grid's labels reach every rank through gatherv and scatterv: the transport has none");
+    mgps_options o;
+    mgps_default_options(&o);
+    if (opt) {
+        if (opt->struct_size != int(sizeof(mgps_options))) return invalid("mgps_options.struct_size mismatch: call mgps_default_options first");
+        o = *opt;
+    }
+    mgps_fields_slab desc;
+    if (int rc = mgps_fields_slab_describe(&desc, p->gx, p->gy, p->gz, p->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
+    Slab s;
+    if (!readSlab(&desc, s, "mgps_project_free_surface_slab")) return MGPS_ERR_INVALID_ARGUMENT;
+    int levels = 0;
+    {
+        int dims[3], off;
+        (void)mgps_expanded_layout(p->gx, p->gy, p->gz, 0, p->power_of_two, dims, &off, &levels);
+    }
+    const int gx = s.gx, gy = s.gy, nzl = s.c1 - s.c0, ex = s.ex, ey = s.ey, ez = s.ez, nze = s.e1 - s.e0;
+    const bool lo = s.c0 > 0, hi = s.c1 < s.gz;  // a neighbour with base planes on that side (every rank has some)
+    const size_t plane = size_t(gx) * gy, cells = plane * size_t(nzl), eplane = size_t(ex) * ey, ecells = eplane * size_t(ez);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    p->mg_levels = levels;
+    p->offset = s.off;
+    p->expanded[0] = ex;
+    p->expanded[1] = ey;
+    p->expanded[2] = ez;
+    p->liquid_cells = 0;
+    std::memset(&p->stats, 0, sizeof(p->stats));
+    p->residual_inf = p->residual_l2 = p->divergence_sum = p->divergence_max = 0;
+    p->enclosed_components = 0;
+    p->rhs_mean_removed_max = p->surface_pressure_max = 0;
+    p->setup_ms = p->solve_ms = p->total_ms = 0;
+    std::fill(p->stage_ms, p->stage_ms + 8, 0.0);
+
+    // ---- this rank's own arguments and buffers: a failure is carried by the first all-reduce
+    const double sigma = p->surface_tension;
+    const bool surface = sigma > 0 || p->surface_pressure;
+    const bool haveSolidVel = p->solid_velocity[0] && p->solid_velocity[1] && p->solid_velocity[2];
+    DevPool pool;
+    int32_t *material = nullptr;  // [lo plane | owned planes | hi plane]
+    float *phiHalo = nullptr, *prHalo = nullptr, *spHalo = nullptr, *spOwn = nullptr, *w[3] = {nullptr, nullptr, nullptr}, *pGammaMax = nullptr;
+    uint8_t *valid[3] = {nullptr, nullptr, nullptr}, *labelsAll = nullptr;
+    unsigned long long *count = nullptr;
+    void *labelsHost = nullptr;
+    struct HostBlock {
+        void *&p;
+        ~HostBlock() { mgps_host_free(p); }
+    } hostBlock{labelsHost};
+    int status = [&]() -> int {
+        bool ok = p->liquid_phi && p->solid_phi && p->pressure;
+        for (int a = 0; a < 3; ++a) ok = ok && p->cut_weights[a] && p->velocity[a];
+        if (!ok || (!haveSolidVel && (p->solid_velocity[0] || p->solid_velocity[1] || p->solid_velocity[2])))
+            return invalid("missing field (solid velocities: all three or none)");
+        if (!std::isfinite(sigma) || sigma < 0) return invalid("surface_tension must be finite and >= 0");
+        if (sigma > 0) {
+            const char *what = !(std::isfinite(p->dt) && p->dt > 0) ? "dt" : !(std::isfinite(p->dx) && p->dx > 0) ? "dx"
+                             : !(std::isfinite(p->density) && p->density > 0) ? "density" : nullptr;
+            if (what) return invalid(std::string("surface_tension > 0 needs a finite ") + what + " > 0");
+            if (p->surface_pressure) return invalid("surface_tension and surface_pressure are both set (pass one of them)");
+        }
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+            setLastGlobalError("no HIP device is visible (this library has no CPU path)");
+            return MGPS_ERR_NO_DEVICE;
+        }
+        if (o.device >= 0 && hipSetDevice(o.device) != hipSuccess) {
+            setLastGlobalError("hipSetDevice failed");
+            return MGPS_ERR_NO_DEVICE;
+        }
+        try {
+            material = pool.get<int32_t>(cells + 2 * plane);
+            phiHalo = pool.get<float>(2 * plane);
+            prHalo = pool.get<float>(2 * plane);
+            if (surface) spHalo = pool.get<float>(2 * plane);
+            if (sigma > 0) spOwn = pool.get<float>(cells);
+            if (surface) pGammaMax = pool.get<float>(1);
+            for (int a = 0; a < 3; ++a) {
+                valid[a] = p->valid_faces[a] ? p->valid_faces[a] : pool.get<uint8_t>(faceCount(gx, gy, nzl, a));
+                w[a] = pool.get<float>(faceCount(ex, ey, nze, a));
+            }
+            labelsAll = pool.get<uint8_t>(ecells);  // the whole grid's labels; this rank's pass writes its window in place
+            count = pool.get<unsigned long long>(1);
+        } catch (const std::bad_alloc &) {
+            setLastGlobalError("mgps_project_free_surface_slab: device allocation failed");
+            return MGPS_ERR_ALLOC;
+        }
+        labelsHost = mgps_host_alloc(ecells);
+        if (!labelsHost) {
+            setLastGlobalError("mgps_project_free_surface_slab: host allocation of the whole grid's labels failed");
+            return MGPS_ERR_ALLOC;
+        }
+        return MGPS_OK;
+    }();
+    {
+        double flags[2] = {surface ? 1.0 : 0.0, surface ? 0.0 : 1.0};  // (both set on some rank: the ranks disagree)
+        if (int rc = agreeRanks(&cm, status, "arguments", nullptr, 0, flags, 2); rc != MGPS_OK) return rc;
+        if (flags[0] != 0 && flags[1] != 0) return invalid("surface tension / surface_pressure is set on some ranks only");
+    }
+    // (from here on the buffers exist on every rank: a failing rank still takes part in every exchange, with whatever its buffers
+    //  hold, and the next all-reduce carries its status)
+    double exchangeMs = 0;
+    auto hipStep = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && status == MGPS_OK) {
+            setLastGlobalError(std::string("mgps_project_free_surface_slab: ") + what + ": " + hipGetErrorString(e));
+            status = MGPS_ERR_HIP;
+        }
+    };
+    auto step = [&](int rc) {
+        if (status == MGPS_OK) status = rc;
+    };
+    // trade one plane with each neighbour: own first plane down, own last plane up; what arrives lands in halo[0] / halo[1]
+    auto tradePlane = [&](const void *own, void *haloLo, void *haloHi, size_t elem, const char *what) -> int {
+        if (P == 1) return MGPS_OK;
+        const auto a = clock::now();
+        const size_t bytes = plane * elem;
+        const char *first = static_cast<const char *>(own), *last = first + size_t(nzl - 1) * bytes;
+        const int rc = cm.exchange(cm.user, lo ? first : nullptr, lo ? bytes : 0, lo ? haloLo : nullptr, lo ? bytes : 0, hi ? last : nullptr, hi ? bytes : 0,
+                                   hi ? haloHi : nullptr, hi ? bytes : 0, st);
+        exchangeMs += ms(a, clock::now());
+        if (rc != 0) {
+            setLastGlobalError(std::string("mgps_project_free_surface_slab: exchange failed (") + what + ")");
+            return MGPS_ERR_COMM;
+        }
+        return MGPS_OK;
+    };
+#define SLAB_COMM(call)                 \
+    do {                                \
+        const int rc_ = (call);         \
+        if (rc_ != MGPS_OK) return rc_; \
+    } while (0)
+    const float *cw[3] = {p->cut_weights[0], p->cut_weights[1], p->cut_weights[2]};
+    const float *svel[3] = {haveSolidVel ? p->solid_velocity[0] : nullptr, haveSolidVel ? p->solid_velocity[1] : nullptr,
+                            haveSolidVel ? p->solid_velocity[2] : nullptr};
+    int32_t *matOwn = material + plane, *matLo = lo ? material : nullptr, *matHi = hi ? matOwn + cells : nullptr;
+    float *phiLo = lo ? phiHalo : nullptr, *phiHi = hi ? phiHalo + plane : nullptr;
+    // ---- 1. phi plane, material labels, material plane, the faces pass and the labels pass (Plug.cpp:270-362)
+    SLAB_COMM(tradePlane(p->liquid_phi, phiHalo, phiHalo + plane, sizeof(float), "liquid_phi"));
+    if (status == MGPS_OK) step(mgps_fields_slab_material_labels(&desc, matOwn, p->liquid_phi, phiLo, phiHi, p->solid_phi, cw[0], cw[1], cw[2], st));
+    SLAB_COMM(tradePlane(matOwn, material, matOwn + cells, sizeof(int32_t), "material labels"));
+    uint8_t *labelsWin = labelsAll + size_t(s.e0) * eplane;
+    if (status == MGPS_OK) step(mgps_fields_slab_faces(&desc, valid, w, matOwn, matLo, matHi, p->liquid_phi, phiLo, phiHi, cw, st));
+    if (status == MGPS_OK) step(mgps_fields_slab_labels(&desc, labelsWin, matOwn, matLo, matHi, w, st));
+    // ---- 2. liquid cells over all ranks; a domain without liquid has nothing to solve (the single-device rule)
+    double liquid = 0;
+    if (status == MGPS_OK) {
+        unsigned long long mine = 0;
+        hipStep(hipMemsetAsync(count, 0, sizeof(unsigned long long), st), "liquid cell count");
+        if (status == MGPS_OK) {
+            countLiquidKernel<<<unsigned(std::min<size_t>((cells + 255) / 256, 4096)), 256, 0, st>>>(matOwn, cells, count);
+            hipStep(hipMemcpyAsync(&mine, count, sizeof(mine), hipMemcpyDeviceToHost, st), "liquid cell count");
+            hipStep(hipStreamSynchronize(st), "field passes");
+        }
+        liquid = double(mine);
+    }
+    SLAB_COMM(agreeRanks(&cm, status, "field passes", &liquid, 1));
+    p->liquid_cells = liquid;
+    const auto t1 = clock::now();
+    p->stage_ms[0] = ms(t0, t1);
+    if (liquid == 0) {
+        hipStep(hipMemsetAsync(p->pressure, 0, cells * sizeof(float), st), "pressure clear");
+        hipStep(hipStreamSynchronize(st), "pressure clear");
+        SLAB_COMM(agreeRanks(&cm, status, "pressure clear"));
+        p->stage_ms[6] = exchangeMs;
+        p->setup_ms = p->total_ms = ms(t0, clock::now());
+        p->stats.outcome = MGPS_PCG_RHS_ZERO;
+        return MGPS_OK;
+    }
+    // ---- 3. the whole grid's labels on every rank's host: gatherv to rank 0 (every window already sits at its place of the
+    //         rank's whole-grid buffer), then scatterv with every other rank's range set to the whole buffer -- a broadcast
+    if (P > 1) {
+        std::vector<size_t> counts(static_cast<size_t>(P), 0), displs(static_cast<size_t>(P), 0);
+        for (int r = 0; r < P; ++r) {
+            counts[size_t(r)] = r == 0 ? 0 : size_t(splits[r + 1] - splits[r]) * eplane;  // (rank 0's window is in place)
+            displs[size_t(r)] = size_t(splits[r]) * eplane;
+        }
+        if (cm.gatherv(cm.user, labelsWin, rank == 0 ? 0 : size_t(nze) * eplane, rank == 0 ? labelsAll : nullptr, counts.data(), displs.data(), 0, st) != 0) {
+            setLastGlobalError("mgps_project_free_surface_slab: gatherv of the labels failed");
+            return MGPS_ERR_COMM;
+        }
+        for (int r = 0; r < P; ++r) {
+            counts[size_t(r)] = r == 0 ? 0 : ecells;
+            displs[size_t(r)] = 0;
+        }
+        if (cm.scatterv(cm.user, rank == 0 ? labelsAll : nullptr, counts.data(), displs.data(), labelsAll, rank == 0 ? 0 : ecells, 0, st) != 0) {
+            setLastGlobalError("mgps_project_free_surface_slab: scatterv of the labels failed");
+            return MGPS_ERR_COMM;
+        }
+    }
+    hipStep(hipMemcpyAsync(labelsHost, labelsAll, ecells, hipMemcpyDeviceToHost, st), "labels to the host");
+    hipStep(hipStreamSynchronize(st), "labels to the host");
+    SLAB_COMM(agreeRanks(&cm, status, "labels to the host"));
+    const auto t2 = clock::now();
+    p->stage_ms[1] = ms(t1, t2);
+    // ---- 4. the slab solver on the rank's expanded weights (borrowed: the pool outlives the solver), rhs, warm start, surface
+    //         term, enclosed-liquid projection, MG-PCG (Plug.cpp:386-629)
+    mgps_solver *mg = nullptr;
+    o.borrow_device_weights = 1;
+    if (int rc = mgps_create_slab_device_weights(&mg, ex, ey, ez, static_cast<const uint8_t *>(labelsHost), w[0], w[1], w[2], levels, p->use_gauss_seidel,
+                                                 &o, &cm, splits);
+        rc != MGPS_OK)
+        return rc;  // (a collective with one verdict)
+    struct Guard {
+        mgps_solver *h;
+        ~Guard() { mgps_destroy(h); }
+    } guard{mg};
+    const auto t3 = clock::now();
+    p->stage_ms[2] = ms(t2, t3);
+    float *rhs = nullptr, *x = nullptr, *res = nullptr;
+    const float *sp = p->surface_pressure ? p->surface_pressure : spOwn;
+    float *spLo = surface && lo ? spHalo : nullptr, *spHi = surface && hi ? spHalo + plane : nullptr;
+    const float *velIn[3] = {p->velocity[0], p->velocity[1], p->velocity[2]};
+    auto solverStep = [&](int rc) {
+        if (rc != MGPS_OK && status == MGPS_OK) {
+            setLastGlobalError(mgps_last_error(mg));
+            status = rc;
+        }
+    };
+    solverStep(mgps_set_stream(mg, stream));
+    if (status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &rhs));
+    if (status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &x));  // zero-filled
+    if (status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &res));
+    if (status == MGPS_OK) step(mgps_fields_slab_rhs(&desc, rhs, matOwn, velIn, svel, cw, st));
+    if (status == MGPS_OK && p->use_old_pressure) step(mgps_fields_slab_pressure_to_solution(&desc, x, p->pressure, matOwn, st));
+    if (surface) {  // b_L += w_f p_G: before the enclosed-liquid projection and the solve, which then see the system actually solved
+        if (status == MGPS_OK && sigma > 0)
+            step(mgps_fields_slab_surface_pressure(&desc, spOwn, p->liquid_phi, phiLo, phiHi, matOwn, matLo, matHi, sigma * p->dt / (p->density * p->dx * p->dx), st));
+        SLAB_COMM(tradePlane(sp, spHalo, spHalo + plane, sizeof(float), "surface pressure"));
+        if (status == MGPS_OK) hipStep(hipMemsetAsync(pGammaMax, 0, sizeof(float), st), "surface pressure");
+        if (status == MGPS_OK) step(mgps_fields_slab_rhs_surface(&desc, rhs, w, p->liquid_phi, phiLo, phiHi, matOwn, matLo, matHi, sp, spLo, spHi, pGammaMax, st));
+    }
+    SLAB_COMM(agreeRanks(&cm, status, "right-hand side"));
+    if (o.enclosed_liquid) {  // the rhs as the solve sees it (P b); both calls return one verdict on every rank
+        int64_t m = 0;
+        int rc = mgps_enclosed_components(mg, &m, nullptr);
+        p->enclosed_components = int(m);
+        if (rc == MGPS_OK && m > 0) rc = mgps_project_enclosed(mg, rhs, &p->rhs_mean_removed_max);
+        if (rc != MGPS_OK) {
+            setLastGlobalError(mgps_last_error(mg));
+            return rc;
+        }
+    }
+    (void)hipStreamSynchronize(st);
+    const auto t4 = clock::now();
+    p->stage_ms[3] = ms(t3, t4);
+    int rc = mgps_solve_pcg(mg, x, rhs, p->tolerance, p->max_iterations, p->use_mg_preconditioner, &p->stats);
+    if (rc == MGPS_OK) rc = mgps_residual(mg, 0, res, x, rhs);  // Plug.cpp:625-628
+    if (rc == MGPS_OK) rc = mgps_inf_norm(mg, 0, res, 1, &p->residual_inf);
+    if (rc == MGPS_OK) rc = mgps_l2_norm(mg, 0, res, &p->residual_l2);
+    if (rc != MGPS_OK && rc != MGPS_ERR_INTERRUPTED) {
+        setLastGlobalError(mgps_last_error(mg));
+        return rc;
+    }
+    const int solveRc = rc;
+    (void)hipStreamSynchronize(st);
+    const auto t5 = clock::now();
+    p->stage_ms[4] = ms(t4, t5);
+    // ---- 5. pressure (0 outside LIQUID cells, Plug.cpp:641), its plane to the neighbours, the gradient on the owned faces -- the
+    //         rank's copy of a cut's z-face plane included -- and the divergence report (Plug.cpp:637-707)
+    step(mgps_fields_slab_solution_to_pressure(&desc, p->pressure, x, matOwn, 1, st));
+    SLAB_COMM(tradePlane(p->pressure, prHalo, prHalo + plane, sizeof(float), "pressure"));
+    if (status == MGPS_OK)
+        step(mgps_fields_slab_pressure_gradient(&desc, p->velocity, p->liquid_phi, phiLo, phiHi, p->pressure, lo ? prHalo : nullptr, hi ? prHalo + plane : nullptr,
+                                                surface ? sp : nullptr, spLo, spHi, valid, matOwn, matLo, matHi, st));
+    double div[3] = {0, 0, 0}, maxes[2] = {0, 0};
+    if (status == MGPS_OK) step(mgps_fields_slab_divergence(&desc, div, matOwn, velIn, svel, cw, st));
+    if (status == MGPS_OK && surface) {
+        float m = 0;
+        hipStep(hipMemcpy(&m, pGammaMax, sizeof(m), hipMemcpyDeviceToHost), "surface pressure");
+        maxes[1] = m;
+    }
+    maxes[0] = div[1];
+    double sums[2] = {div[0], div[2]};
+    SLAB_COMM(agreeRanks(&cm, status, "write-back", sums, 2, maxes, 2));
+#undef SLAB_COMM
+    p->divergence_sum = sums[0];
+    p->divergence_max = maxes[0];
+    p->surface_pressure_max = maxes[1];
+    const auto t6 = clock::now();
+    p->stage_ms[5] = ms(t5, t6);
+    p->stage_ms[6] = exchangeMs;
+    p->setup_ms = ms(t0, t4);
+    p->solve_ms = ms(t4, t5);
+    p->total_ms = ms(t0, t6);
+    if (setupTimingOn())
+        std::printf("projection slab rank %d: passes %.2f ms, labels to hosts %.2f ms, solver set-up %.2f ms, rhs %.2f ms, solve %.2f ms, write-back %.2f ms "
+                    "(plane exchanges %.2f ms)\n",
+                    rank, p->stage_ms[0], p->stage_ms[1], p->stage_ms[2], p->stage_ms[3], p->stage_ms[4], p->stage_ms[5], exchangeMs);
+    if (solveRc != MGPS_OK) setLastGlobalError("mgps_project_free_surface_slab: interrupted");
     return solveRc;
 }
 MGPS_API_CATCH(nullptr)

@@ -223,3 +223,226 @@ def project_free_surface(liquid_phi, solid_phi, cut_weights, velocity, pressure,
         e.info, e.valid_faces = info, valid
         raise
     return valid, info
+
+
+# ---- the fields layer on Z-slabs (include/mgps_fields.h) --------------------------------------------------
+class FieldsSlab(C.Structure):
+    """mgps_fields_slab: one rank's window of a slab projection."""
+
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "gx", "gy", "gz", "c0", "c1", "ex", "ey", "ez", "offset", "e0", "e1")]
+
+    @property
+    def base_shape(self):
+        """the window's cell grid (nz, ny, nx)"""
+        return (self.c1 - self.c0, self.gy, self.gx)
+
+    @property
+    def expanded_shape(self):
+        """the window's expanded cell grid (nz, ny, nx)"""
+        return (self.e1 - self.e0, self.ey, self.ex)
+
+
+def projection_slab_layout(shape, power_of_two, size, use_gauss_seidel):
+    """mgps_projection_slab_layout (host only): the expanded layout of the WHOLE grid `shape` = (gz, gy, gx) and cuts for `size`
+    ranks that divide the base planes evenly.  Returns {"expanded": (ez, ey, ex), "offset", "levels", "splits": [size + 1]}."""
+    gz, gy, gx = shape
+    dims, off, lev, cuts = (C.c_int * 3)(), C.c_int(), C.c_int(), (C.c_int * (int(size) + 1))()
+    check(lib().mgps_projection_slab_layout(gx, gy, gz, int(bool(power_of_two)), int(size), int(bool(use_gauss_seidel)), dims, C.byref(off),
+                                            C.byref(lev), cuts))
+    return {"expanded": (dims[2], dims[1], dims[0]), "offset": off.value, "levels": lev.value, "splits": [int(v) for v in cuts]}
+
+
+def slab_window(global_shape, power_of_two, splits, rank):
+    """mgps_fields_slab_describe: the window of rank `rank` for the cuts `splits` of the expanded grid."""
+    gz, gy, gx = global_shape
+    d = FieldsSlab()
+    cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
+    check(lib().mgps_fields_slab_describe(C.byref(d), gx, gy, gz, int(bool(power_of_two)), cuts, len(splits) - 1, int(rank)))
+    return d
+
+
+def _face3(shape):
+    return [_face_shape(shape, a) for a in range(3)]
+
+
+def _arr3(ts):
+    return (C.c_void_p * 3)(*[t.data_ptr() if t is not None else None for t in ts])
+
+
+def _halo(d, halo, dtype):
+    """(lo, hi) plane tensors -> two pointers; None where the grid ends"""
+    lo, hi = halo if halo is not None else (None, None)
+    for t in (lo, hi):
+        if t is not None:
+            _chk(t, (d.gy, d.gx), dtype)
+    assert (lo is not None) == (d.c0 > 0) and (hi is not None) == (d.c1 < d.gz), "halo planes: exactly where the grid goes on"
+    return _p(lo), _p(hi)
+
+
+def buildMaterialCellLabelsSlab(d, liquid_surface, phi_halo, solid_surface, cut_cell_weights):
+    """buildMaterialCellLabels on the window `d`; phi_halo = (plane c0 - 1 or None, plane c1 or None)."""
+    shape = d.base_shape
+    cw = [_chk(cut_cell_weights[a], fs, torch.float32) for a, fs in enumerate(_face3(shape))]
+    out = torch.empty(shape, dtype=torch.int32, device=liquid_surface.device)
+    check(lib().mgps_fields_slab_material_labels(C.byref(d), _p(out), _p(_chk(liquid_surface, shape, torch.float32)), *_halo(d, phi_halo, torch.float32),
+                                                 _p(_chk(solid_surface, shape, torch.float32)), _p(cw[0]), _p(cw[1]), _p(cw[2]), _stream()))
+    return out
+
+
+def buildFacesSlab(d, material, material_halo, liquid_surface, phi_halo, cut_cell_weights):
+    """buildValidFaces + buildMGBoundaryWeights of all three axes in one pass: (valid[3] uint8 base face grids of the window,
+    weights[3] float32 expanded face grids of the window, zeros outside the base box included)."""
+    shape, eshape, dev = d.base_shape, d.expanded_shape, material.device
+    valid = [torch.empty(fs, dtype=torch.uint8, device=dev) for fs in _face3(shape)]
+    weights = [torch.empty(fs, dtype=torch.float32, device=dev) for fs in _face3(eshape)]
+    cw = [_chk(cut_cell_weights[a], fs, torch.float32) for a, fs in enumerate(_face3(shape))]
+    check(lib().mgps_fields_slab_faces(C.byref(d), _arr3(valid), _arr3(weights), _p(_chk(material, shape, torch.int32)), *_halo(d, material_halo, torch.int32),
+                                       _p(_chk(liquid_surface, shape, torch.float32)), *_halo(d, phi_halo, torch.float32), _arr3(cw), _stream()))
+    return valid, weights
+
+
+def buildLabelsSlab(d, material, material_halo, weights):
+    """buildMGDomainLabels + setBoundaryCellLabels on the window's expanded planes (EXTERIOR outside the base box)."""
+    eshape = d.expanded_shape
+    w = [_chk(weights[a], fs, torch.float32) for a, fs in enumerate(_face3(eshape))]
+    labels = torch.empty(eshape, dtype=torch.uint8, device=material.device)
+    check(lib().mgps_fields_slab_labels(C.byref(d), _p(labels), _p(_chk(material, d.base_shape, torch.int32)), *_halo(d, material_halo, torch.int32),
+                                        _arr3(w), _stream()))
+    return labels
+
+
+def buildRHSSlab(d, material, velocity, cut_cell_weights, solid_velocity=None, out=None):
+    """buildRHS on the window's expanded planes (`out`: a grid of a slab solver, or None for a new tensor)."""
+    shape = d.base_shape
+    rhs = out if out is not None else torch.empty(d.expanded_shape, dtype=torch.float32, device=material.device)
+    v = [_chk(velocity[a], fs, torch.float32) for a, fs in enumerate(_face3(shape))]
+    check(lib().mgps_fields_slab_rhs(C.byref(d), _p(_chk(rhs, d.expanded_shape, torch.float32)), _p(_chk(material, shape, torch.int32)), _arr3(v),
+                                     _arr3(solid_velocity) if solid_velocity is not None else None, _arr3(cut_cell_weights), _stream()))
+    return rhs
+
+
+def applyOldPressureSlab(d, pressure, material, out=None):
+    x = out if out is not None else torch.empty(d.expanded_shape, dtype=torch.float32, device=material.device)
+    check(lib().mgps_fields_slab_pressure_to_solution(C.byref(d), _p(_chk(x, d.expanded_shape, torch.float32)), _p(_chk(pressure, d.base_shape, torch.float32)),
+                                                      _p(_chk(material, d.base_shape, torch.int32)), _stream()))
+    return x
+
+
+def applySolutionToPressureSlab(d, pressure, solution, material, clear_others=False):
+    check(lib().mgps_fields_slab_solution_to_pressure(C.byref(d), _p(_chk(pressure, d.base_shape, torch.float32)), _p(_chk(solution, d.expanded_shape, torch.float32)),
+                                                      _p(_chk(material, d.base_shape, torch.int32)), int(bool(clear_others)), _stream()))
+    return pressure
+
+
+def applyPressureGradientSlab(d, velocity, liquid_surface, phi_halo, pressure, pressure_halo, valid_faces, material, material_halo,
+                              surface_pressure=None, surface_pressure_halo=None):
+    """applyPressureGradient of all three axes on the window (in place); with `surface_pressure` the surface-tension form."""
+    shape = d.base_shape
+    v = [_chk(velocity[a], fs, torch.float32) for a, fs in enumerate(_face3(shape))]
+    sp = (_p(_chk(surface_pressure, shape, torch.float32)), *_halo(d, surface_pressure_halo, torch.float32)) if surface_pressure is not None else (None, None, None)
+    check(lib().mgps_fields_slab_pressure_gradient(C.byref(d), _arr3(v), _p(_chk(liquid_surface, shape, torch.float32)), *_halo(d, phi_halo, torch.float32),
+                                                   _p(_chk(pressure, shape, torch.float32)), *_halo(d, pressure_halo, torch.float32), *sp,
+                                                   _arr3([_chk(valid_faces[a], fs, torch.uint8) for a, fs in enumerate(_face3(shape))]),
+                                                   _p(_chk(material, shape, torch.int32)), *_halo(d, material_halo, torch.int32), _stream()))
+    return velocity
+
+
+def buildSurfacePressureSlab(d, liquid_surface, phi_halo, material, material_halo, scale):
+    shape = d.base_shape
+    sp = torch.empty(shape, dtype=torch.float32, device=material.device)
+    check(lib().mgps_fields_slab_surface_pressure(C.byref(d), _p(sp), _p(_chk(liquid_surface, shape, torch.float32)), *_halo(d, phi_halo, torch.float32),
+                                                  _p(_chk(material, shape, torch.int32)), *_halo(d, material_halo, torch.int32), C.c_double(scale), _stream()))
+    return sp
+
+
+def addSurfacePressureToRHSSlab(d, rhs, weights, liquid_surface, phi_halo, material, material_halo, surface_pressure, surface_pressure_halo,
+                                p_gamma_max=None):
+    shape, eshape = d.base_shape, d.expanded_shape
+    w = [_chk(weights[a], fs, torch.float32) for a, fs in enumerate(_face3(eshape))]
+    check(lib().mgps_fields_slab_rhs_surface(C.byref(d), _p(_chk(rhs, eshape, torch.float32)), _arr3(w), _p(_chk(liquid_surface, shape, torch.float32)),
+                                             *_halo(d, phi_halo, torch.float32), _p(_chk(material, shape, torch.int32)), *_halo(d, material_halo, torch.int32),
+                                             _p(_chk(surface_pressure, shape, torch.float32)), *_halo(d, surface_pressure_halo, torch.float32),
+                                             _p(p_gamma_max), _stream()))
+    return rhs
+
+
+def computeResultingDivergenceSlab(d, material, velocity, cut_cell_weights, solid_velocity=None):
+    """this rank's (sum, max, liquid cell count); the caller reduces over the ranks"""
+    out = (C.c_double * 3)()
+    check(lib().mgps_fields_slab_divergence(C.byref(d), out, _p(_chk(material, d.base_shape, torch.int32)), _arr3(velocity),
+                                            _arr3(solid_velocity) if solid_velocity is not None else None, _arr3(cut_cell_weights), _stream()))
+    return out[0], out[1], out[2]
+
+
+class ProjectionSlab(C.Structure):
+    """mgps_projection_slab (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int),
+        ("liquid_phi", C.c_void_p), ("solid_phi", C.c_void_p), ("cut_weights", C.c_void_p * 3), ("velocity", C.c_void_p * 3),
+        ("solid_velocity", C.c_void_p * 3), ("pressure", C.c_void_p), ("valid_faces", C.c_void_p * 3),
+        ("use_old_pressure", C.c_int), ("use_mg_preconditioner", C.c_int), ("use_gauss_seidel", C.c_int),
+        ("tolerance", C.c_double), ("max_iterations", C.c_int), ("power_of_two", C.c_int),
+        ("stats", _lib.PcgStats), ("mg_levels", C.c_int), ("offset", C.c_int), ("expanded", C.c_int * 3),
+        ("liquid_cells", C.c_double), ("residual_inf", C.c_double), ("residual_l2", C.c_double),
+        ("divergence_sum", C.c_double), ("divergence_max", C.c_double),
+        ("setup_ms", C.c_double), ("solve_ms", C.c_double), ("total_ms", C.c_double),
+        ("enclosed_components", C.c_int), ("rhs_mean_removed_max", C.c_double),
+        ("surface_tension", C.c_double), ("dt", C.c_double), ("dx", C.c_double), ("density", C.c_double),
+        ("surface_pressure", C.c_void_p), ("surface_pressure_max", C.c_double), ("stage_ms", C.c_double * 8),
+    ]
+
+
+STAGES_SLAB = ("passes", "labels_to_hosts", "solver_setup", "rhs", "solve", "write_back", "plane_exchanges")
+
+
+def project_free_surface_slab(comm, splits, global_shape, liquid_phi, solid_phi, cut_weights, velocity, pressure, solid_velocity=None,
+                              use_old_pressure=True, use_mg_preconditioner=True, use_gauss_seidel=True, tolerance=1e-5, max_iterations=2500,
+                              power_of_two=True, options=None, surface_tension=0.0, dt=0.0, dx=0.0, density=0.0, surface_pressure=None):
+    """mgps_project_free_surface_slab: solveGasSubclass on the float32 CUDA tensors of this rank's window of the grid `global_shape`
+    = (gz, gy, gx), a collective over the transport `comm` (RcclComm / TorchDistComm; a world of one is the device-resident
+    projection on one GPU).  `splits`: the cuts of the expanded grid (projection_slab_layout, or the caller's own).  Cell, x-face
+    and y-face grids hold the rank's base planes [c0, c1) (slab_window), z-face grids the faces c0 .. c1.  `velocity` and
+    `pressure` are updated in place; returns (valid_faces[3] uint8 CUDA tensors, info dict of the whole grid's numbers)."""
+    d = slab_window(global_shape, power_of_two, splits, comm.rank)
+    shape = d.base_shape
+    faces = _face3(shape)
+    dev = liquid_phi.device
+    pr = ProjectionSlab()
+    pr.struct_size = C.sizeof(ProjectionSlab)
+    pr.gz, pr.gy, pr.gx = global_shape
+
+    def ptr(t, sh):
+        return _chk(t, sh, torch.float32).data_ptr()
+
+    pr.liquid_phi, pr.solid_phi, pr.pressure = ptr(liquid_phi, shape), ptr(solid_phi, shape), ptr(pressure, shape)
+    valid = []
+    for a in range(3):
+        pr.cut_weights[a] = ptr(cut_weights[a], faces[a])
+        pr.velocity[a] = ptr(velocity[a], faces[a])
+        # (a missing entry stays NULL: the library refuses "some but not all" on every rank together)
+        pr.solid_velocity[a] = ptr(solid_velocity[a], faces[a]) if solid_velocity is not None and solid_velocity[a] is not None else None
+        valid.append(torch.zeros(faces[a], dtype=torch.uint8, device=dev))
+        pr.valid_faces[a] = valid[a].data_ptr()
+    pr.use_old_pressure, pr.use_mg_preconditioner, pr.use_gauss_seidel = int(use_old_pressure), int(use_mg_preconditioner), int(use_gauss_seidel)
+    pr.tolerance, pr.max_iterations, pr.power_of_two = float(tolerance), int(max_iterations), int(bool(power_of_two))
+    pr.surface_tension, pr.dt, pr.dx, pr.density = float(surface_tension), float(dt), float(dx), float(density)
+    pr.surface_pressure = ptr(surface_pressure, shape) if surface_pressure is not None else None
+    cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
+    status = lib().mgps_project_free_surface_slab(C.byref(pr), C.byref(options) if options is not None else None, C.byref(comm.struct), cuts, _stream())
+    info = {
+        "iterations": pr.stats.iterations, "outcome": pr.stats.outcome, "rel_residual": pr.stats.rel_residual,
+        "rel_residual_recomputed": pr.stats.rel_residual_recomputed, "mg_levels": pr.mg_levels, "offset": pr.offset,
+        "expanded": (pr.expanded[2], pr.expanded[1], pr.expanded[0]), "liquid_cells": pr.liquid_cells,
+        "residual_inf": pr.residual_inf, "residual_l2": pr.residual_l2, "divergence_sum": pr.divergence_sum,
+        "divergence_max": pr.divergence_max, "setup_ms": pr.setup_ms, "solve_ms": pr.solve_ms, "total_ms": pr.total_ms,
+        "enclosed_components": pr.enclosed_components, "rhs_mean_removed_max": pr.rhs_mean_removed_max,
+        "surface_pressure_max": pr.surface_pressure_max, "window": (d.c0, d.c1),
+        "stage_ms": {n: pr.stage_ms[q] for q, n in enumerate(STAGES_SLAB)},
+    }
+    try:
+        check(status)
+    except _lib.MgpsError as e:  # (interrupted: pressure and velocity hold what the iterate reached gives)
+        e.info, e.valid_faces = info, valid
+        raise
+    return valid, info

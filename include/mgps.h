@@ -491,7 +491,7 @@ int mgps_slab_partition(int nx, int ny, int nz, const uint8_t *labels_global_hos
 int mgps_create_slab_ranges(mgps_solver **out, int nx, int ny, int nz_global, const uint8_t *labels_global_host,
                             const float *wx_slab, const float *wy_slab, const float *wz_slab, int mg_levels,
                             int use_gauss_seidel, const mgps_options *opt, const mgps_comm *comm, const int *splits);
-/* The same with the slab's face weights already on the rank's DEVICE (what mgps_fields_build_* leave there): no weight
+/* The same with the slab's face weights already on the rank's DEVICE (what mgps_fields_slab_faces leaves there): no weight
  * crosses PCIe -- at 1024^3 on 8 ranks the 1.6 GB of a slab's weights arriving from pageable host memory were 300 of the
  * 470 ms a rank's set-up took -- and the rows of the slab's BOUNDARY cells are evaluated on the device (Ops.h:208-256, as
  * mgps_create_device_weights does for a whole grid).  The arrays are copied unless options.borrow_device_weights is set

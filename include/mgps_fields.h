@@ -137,6 +137,123 @@ typedef struct mgps_projection {
  * stats says which (outcome MGPS_PCG_MAX_ITERATIONS, iterations), residual_inf / residual_l2 are not evaluated (0) */
 int mgps_project_free_surface(mgps_projection *p, const mgps_options *opt);
 
+/* ---- the fields layer on Z-slabs -----------------------------------------------------------------------
+ * One rank of a slab run (include/mgps.h, "multi-GPU") holds a z-window of every field.  With the cuts splits[0..size] of the
+ * EXPANDED grid (the cuts mgps_create_slab_ranges takes), rank r owns the expanded planes [e0, e1) = [splits[r], splits[r + 1])
+ * and the base planes [c0, c1), c0 = clamp(e0 - offset, 0, gz), c1 = clamp(e1 - offset, 0, gz).  Cell grids, x-face grids and
+ * y-face grids hold the rank's c1 - c0 planes; z-face grids hold c1 - c0 + 1 planes, the faces c0 .. c1 (the convention of
+ * wz_slab): the face plane on a cut exists on both neighbours, with the same input values, and each rank updates its own copy.
+ * Expanded grids hold the e1 - e0 planes of the window (the expanded z-face grid e1 - e0 + 1).  A rank without base planes has
+ * no window: c0 < c1 is required.
+ * The passes do no communication.  What a pass reads of a neighbour's planes arrives as halo-plane pointers, one plane of gx * gy
+ * entries each: `*_lo` is base plane c0 - 1, `*_hi` base plane c1; NULL at the ends of the grid (c0 = 0, c1 = gz), where the
+ * passes behave as the whole-grid passes do at the grid boundary.  Results equal those of the whole-grid passes on the rank's
+ * planes: labels and flags exactly, floats to the last place. */
+typedef struct mgps_fields_slab {
+    int struct_size; /* sizeof(mgps_fields_slab) */
+    int gx, gy, gz;  /* the whole base grid */
+    int c0, c1;      /* owned base planes */
+    int ex, ey, ez;  /* the whole expanded grid */
+    int offset;
+    int e0, e1;      /* owned expanded planes */
+} mgps_fields_slab;
+/* The layout of a slab projection, on the host (no device needed): mgps_expanded_layout(gx, gy, gz, 0, power_of_two) and cuts
+ * out_splits[0 .. size] that mgps_create_slab_ranges accepts (every cut even, a multiple of 16 with Gauss-Seidel, at least 16
+ * planes per rank) and that divide the BASE planes as evenly as that granularity allows (an even cut of the expanded grid would
+ * leave the end ranks with EXTERIOR padding only); every rank owns at least one base plane.  MGPS_ERR_INVALID_ARGUMENT with a
+ * message where no such cuts exist.  Callers may pass cuts of their own to the calls below (mgps_slab_partition on the labels
+ * of the previous sub-step, say). */
+int mgps_projection_slab_layout(int gx, int gy, int gz, int power_of_two, int size, int use_gauss_seidel, int out_expanded[3],
+                                int *out_offset, int *out_levels, int *out_splits);
+/* fills `out` for rank `rank` of the cuts `splits` (size + 1 entries); MGPS_ERR_INVALID_ARGUMENT when the cuts do not run from 0
+ * to ez increasing or when ANY rank owns no base plane (the verdict depends on the shared arguments only) */
+int mgps_fields_slab_describe(mgps_fields_slab *out, int gx, int gy, int gz, int power_of_two, const int *splits, int size, int rank);
+/* mgps_fields_material_labels on the window.  material: c1 - c0 planes */
+int mgps_fields_slab_material_labels(const mgps_fields_slab *d, int32_t *material, const float *liquid_phi, const float *phi_lo,
+                                     const float *phi_hi, const float *solid_phi, const float *cwx, const float *cwy, const float *cwz,
+                                     void *stream);
+/* One faces pass: mgps_fields_valid_faces and mgps_fields_boundary_weights of all three axes.  valid[3]: the window's base face
+ * grids; expanded_weights[3]: the window's expanded face grids, written everywhere (0 outside the base box: no fill first) */
+int mgps_fields_slab_faces(const mgps_fields_slab *d, uint8_t *const valid[3], float *const expanded_weights[3], const int32_t *material,
+                           const int32_t *material_lo, const int32_t *material_hi, const float *liquid_phi, const float *phi_lo,
+                           const float *phi_hi, const float *const cut_weights[3], void *stream);
+/* One labels pass: mgps_fields_domain_labels and mgps_fields_set_boundary_labels on the window's e1 - e0 expanded planes, written
+ * everywhere (EXTERIOR outside the base box).  The domain label is a function of the material label, so the material halo is
+ * the label halo BOUNDARY marking needs.  expanded_weights: what mgps_fields_slab_faces wrote */
+int mgps_fields_slab_labels(const mgps_fields_slab *d, uint8_t *expanded_labels, const int32_t *material, const int32_t *material_lo,
+                            const int32_t *material_hi, const float *const expanded_weights[3], void *stream);
+/* mgps_fields_rhs / mgps_fields_pressure_to_solution on the window's expanded planes, written everywhere (0 outside LIQUID cells) */
+int mgps_fields_slab_rhs(const mgps_fields_slab *d, float *expanded_rhs, const int32_t *material, const float *const velocity[3],
+                         const float *const solid_velocity[3], const float *const cut_weights[3], void *stream);
+int mgps_fields_slab_pressure_to_solution(const mgps_fields_slab *d, float *expanded_x, const float *pressure, const int32_t *material,
+                                          void *stream);
+/* mgps_fields_solution_to_pressure; clear_others != 0 writes 0 to every cell that is not LIQUID instead of leaving it */
+int mgps_fields_slab_solution_to_pressure(const mgps_fields_slab *d, float *pressure, const float *expanded_x, const int32_t *material,
+                                          int clear_others, void *stream);
+/* mgps_fields_pressure_gradient of all three axes in one pass (sp != NULL: mgps_fields_pressure_gradient_surface) */
+int mgps_fields_slab_pressure_gradient(const mgps_fields_slab *d, float *const velocity[3], const float *liquid_phi, const float *phi_lo,
+                                       const float *phi_hi, const float *pressure, const float *pressure_lo, const float *pressure_hi,
+                                       const float *sp, const float *sp_lo, const float *sp_hi, const uint8_t *const valid[3],
+                                       const int32_t *material, const int32_t *material_lo, const int32_t *material_hi, void *stream);
+/* mgps_fields_surface_pressure / mgps_fields_rhs_surface on the window (curvature indices clamped to the whole grid) */
+int mgps_fields_slab_surface_pressure(const mgps_fields_slab *d, float *sp, const float *liquid_phi, const float *phi_lo,
+                                      const float *phi_hi, const int32_t *material, const int32_t *material_lo, const int32_t *material_hi,
+                                      double scale, void *stream);
+int mgps_fields_slab_rhs_surface(const mgps_fields_slab *d, float *expanded_rhs, const float *const expanded_weights[3],
+                                 const float *liquid_phi, const float *phi_lo, const float *phi_hi, const int32_t *material,
+                                 const int32_t *material_lo, const int32_t *material_hi, const float *sp, const float *sp_lo,
+                                 const float *sp_hi, float *p_gamma_max, void *stream);
+/* the rank's part of mgps_fields_divergence: out_host[3] = {sum, max (from 0), LIQUID cell count} over the window's cells (every
+ * face of an owned cell is in the window); the caller sums / maximises over the ranks.  Synchronises the stream */
+int mgps_fields_slab_divergence(const mgps_fields_slab *d, double out_host[3], const int32_t *material, const float *const velocity[3],
+                                const float *const solid_velocity[3], const float *const cut_weights[3], void *stream);
+
+/* mgps_project_free_surface on the DEVICE fields of one slab rank; a collective over `comm`: every rank calls it with the same
+ * gx, gy, gz (the WHOLE grid), options, cuts and switches.  Every array is a device float32 array of the rank's window as defined
+ * above; valid_faces are device uint8 outputs (each may be NULL).  With comm->size = 1 it is the device-resident projection on
+ * one GPU.  Steps, in the order of mgps_project_free_surface: liquid_phi plane exchange, material labels, material plane
+ * exchange, the faces pass and the labels pass; liquid cell count (all-reduce; no liquid anywhere: valid faces and zero pressure
+ * are published, outcome MGPS_PCG_RHS_ZERO); the whole grid's labels to every rank's host (gatherv to rank 0, scatterv with every
+ * rank's range set to the whole buffer: ex * ey * ez bytes per rank, 1 GiB at 1024^3) for mgps_create_slab_device_weights on the
+ * rank's weights (borrowed); rhs, warm start, surface term (after an exchange of the sp plane), enclosed-liquid projection,
+ * mgps_solve_pcg, residual norms; pressure write-back, pressure plane exchange, gradient on the owned faces (both copies of a
+ * cut's z-face plane get the same bits), divergence report and surface_pressure_max from one all-reduce.  Every rank-local failure
+ * is folded into the next all-reduce: all ranks return the same status.  The exception is the transport itself: a rank whose
+ * exchange, all-reduce, gatherv or scatterv call fails returns MGPS_ERR_COMM at once and alone (nothing can carry its status; the
+ * other ranks are left in a collective of a broken transport, as on the slab solvers).  A transport without gatherv / scatterv is refused when
+ * size > 1, before any device work.  MGPS_ERR_INTERRUPTED: as mgps_project_free_surface. */
+typedef struct mgps_projection_slab {
+    int struct_size;                /* sizeof(mgps_projection_slab) */
+    int gx, gy, gz;                 /* the WHOLE simulation grid */
+    const float *liquid_phi, *solid_phi;
+    const float *cut_weights[3];
+    float *velocity[3];             /* in: velocity, out: projected velocity */
+    const float *solid_velocity[3]; /* or all NULL */
+    float *pressure;
+    uint8_t *valid_faces[3];        /* out (each may be NULL: not wanted) */
+    int use_old_pressure, use_mg_preconditioner, use_gauss_seidel;
+    double tolerance;
+    int max_iterations, power_of_two;
+    /* results: the whole grid's numbers, the same on every rank */
+    mgps_pcg_stats stats;
+    int mg_levels, offset, expanded[3];
+    double liquid_cells;
+    double residual_inf, residual_l2;
+    double divergence_sum, divergence_max;
+    double setup_ms, solve_ms, total_ms; /* this rank's host wall clock */
+    int enclosed_components;
+    double rhs_mean_removed_max;
+    double surface_tension, dt, dx, density;
+    const float *surface_pressure;  /* cell grid of the window, or NULL */
+    double surface_pressure_max;
+    /* this rank's host wall clock per stage, ms: [0] plane exchanges + material, faces and labels passes + liquid count,
+       [1] labels to every rank's host, [2] solver set-up, [3] rhs, warm start, surface term, enclosed projection, [4] solve +
+       residual norms, [5] write-back, gradient, divergence report, [6] of all that: inside the plane exchanges, [7] reserved */
+    double stage_ms[8];
+} mgps_projection_slab;
+int mgps_project_free_surface_slab(mgps_projection_slab *p, const mgps_options *opt, const mgps_comm *comm, const int *splits,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif
