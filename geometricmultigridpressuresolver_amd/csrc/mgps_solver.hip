@@ -598,6 +598,19 @@ bool levelHasBoxes(const mgps_solver *h, int l)
     if (h->lv[l].boxForm) return true;
     return h->lv[l].bandBoxes.ngroups > 0 && h->lv[l].bandBoxes.depth == h->opt.band_iterations;
 }
+// A level whose boxes the builder could not form runs its band stage pass by pass: halved down to a single cell, a box's region
+// still held more than kBoxMaxGeneral general band cells -- (2 depth + 1)^3 cells lie within reach, 343 at depth 3 and 729 at
+// depth 4, so only band_iterations = 4 on a level crowded with general cells gets here (slab ranks: createSlabOnDevice agrees on
+// the same per level).  The binary16 fine level has no pass-by-pass stage: refused.
+int boxesUnavailable(mgps_solver *h, int l)
+{
+    if (l == 0 && h->opt.precision == 1)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT,
+                     "options.precision = 1 (mixed precision) needs the fused band stage on the fine level: with band_iterations = 4 a band "
+                     "box of this domain holds more than " + std::to_string(kBoxMaxGeneral) + " general cells (use band_iterations <= 3)");
+    if (h->opt.print_stats) std::printf("  level %d: band boxes exceed %d general cells per group; band stage pass by pass\n", l, kBoxMaxGeneral);
+    return MGPS_OK;
+}
 // the level as the band boxes see it (a cut level: operator rows of the whole label buffer)
 const GridP &boxGrid(const mgps_solver *h, int l) { return h->lv[l].boxForm ? h->lv[l].gBox : h->lv[l].g; }
 
@@ -2016,16 +2029,19 @@ int uploadLevel(mgps_solver *h, DevLevel &L, const HostLevel &HL, int z0, int z1
         BandBoxes bx;
         buildBandBoxes(HL, h->opt.band_iterations, bx);
         gclock.lap("  (band boxes alone)");
-        if (bx.groups() == 0) return failH(h, MGPS_ERR_INTERNAL, "band boxes: the builder failed on level of " + std::to_string(L.d.nx) + " cells in x");
-        L.bandBoxes.depth = bx.depth;
-        L.bandBoxes.ngroups = int(bx.groups());
-        L.bandBoxes.listCount = bx.list.size();
-        L.bandBoxes.generalInts = bx.general.size();
-        L.bandBoxes.anyGeneral = !bx.general.empty();
-        MGPS_TRY(devUpload(h, &L.bandBoxes.info, bx.info));
-        MGPS_TRY(devUpload(h, &L.bandBoxes.list, bx.list));
-        MGPS_TRY(devUpload(h, &L.bandBoxes.general, bx.general));
-        MGPS_TRY(finishBandBoxes(h, L, h->stream));
+        if (bx.groups() == 0) {  // (a non-empty band always has a group: the builder gave up, see boxesUnavailable)
+            MGPS_TRY(boxesUnavailable(h, int(&L - h->lv.data())));
+        } else {
+            L.bandBoxes.depth = bx.depth;
+            L.bandBoxes.ngroups = int(bx.groups());
+            L.bandBoxes.listCount = bx.list.size();
+            L.bandBoxes.generalInts = bx.general.size();
+            L.bandBoxes.anyGeneral = !bx.general.empty();
+            MGPS_TRY(devUpload(h, &L.bandBoxes.info, bx.info));
+            MGPS_TRY(devUpload(h, &L.bandBoxes.list, bx.list));
+            MGPS_TRY(devUpload(h, &L.bandBoxes.general, bx.general));
+            MGPS_TRY(finishBandBoxes(h, L, h->stream));
+        }
     }
     if (xbGrids) {
         MGPS_TRY(gridAlloc(h, &L.x, L.d));
@@ -3148,7 +3164,11 @@ int createWholeOnDevice(mgps_solver **out, int nx, int ny, int nz, const uint8_t
             int *broken = flags + 2 * mgLevels + 2 + l;
             int tot[3] = {0, 0, 0}, brokenL = 0;
             MGPS_TRY(boxTotals(h, T[size_t(l)], broken, tot, &brokenL));
-            if (brokenL || tot[0] == 0) return failH(h, MGPS_ERR_INTERNAL, "band boxes: the builder failed on level " + std::to_string(l));
+            if (brokenL) {  // this level keeps no boxes (boxesUnavailable): pass by pass
+                MGPS_TRY(boxesUnavailable(h, l));
+                continue;
+            }
+            if (tot[0] == 0) return failH(h, MGPS_ERR_INTERNAL, "band boxes: the builder failed on level " + std::to_string(l));
             MGPS_TRY(boxFill(h, T[size_t(l)], h->lv[size_t(l)], o.band_iterations, tot, broken));
         }
         MGPS_HIP(h, hipDeviceSynchronize());

@@ -65,9 +65,15 @@ typedef struct mgps_hierarchy mgps_hierarchy; /* host-only multigrid hierarchy (
  * defaults: band width 3 / band iterations 3 (MG.cpp:141-142), omega = 2/3 (Ops.h:291, 554). */
 typedef struct mgps_options {
     int struct_size;        /* sizeof(mgps_options), set by mgps_default_options */
-    int band_width;         /* 3 */
-    int band_iterations;    /* 3 */
-    float jacobi_weight;    /* 2/3 */
+    int band_width;         /* 3; >= 1, the device-side set-up takes up to 8 */
+    int band_iterations;    /* 3; >= 0.  1 .. 4 run as one launch per stage (fuse_band_passes), 0 runs no band stage, 5 and more
+                               run pass by pass.  At 4 a level crowded with general BOUNDARY cells (face weights other than 0 / 1)
+                               runs pass by pass too: a band box keeps the rows of the general cells within band_iterations cells
+                               of it in LDS, 384 at most, and (2 * 4 + 1)^3 = 729 cells lie that close (343 at 3: never).
+                               mgps_band_stage_form tells which form a level took; the numbers are the same either way.
+                               options.precision = 1 has no pass-by-pass stage on its binary16 fine level and returns
+                               MGPS_ERR_INVALID_ARGUMENT for such a domain */
+    float jacobi_weight;    /* 2/3: the damping of the Jacobi sweeps and of every band pass */
     int device;             /* HIP device ordinal; -1 = current device */
     int print_stats;        /* doPrintStats of MG.h:24: per-stage timings on stdout */
     int max_coarse_unknowns;/* direct-solve cap, default 32768 (a 32^3 coarsest level); above 8192 unknowns -- or where the

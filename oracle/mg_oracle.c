@@ -137,8 +137,8 @@ static inline void pack_w(const real *wx, const real *wy, const real *wz, const 
 
 /* jacobiPoissonSmoother (Ops.h:262-367): x <- x + 2/3 (b - A xcopy)/diag on active cells.
  * `scratch` (n cells) holds the whole-grid copy the reference takes at Ops.h:289. */
-void mgo_jacobi(real *x, const real *b, const int32_t *lab, const real *wx, const real *wy,
-                const real *wz, int nx, int ny, int nz, real *scratch)
+void mgo_jacobi_weighted(real *x, const real *b, const int32_t *lab, const real *wx, const real *wy,
+                         const real *wz, int nx, int ny, int nz, real *scratch, double weight)
 {
     const dims_t d = {nx, ny, nz};
     const real *w[3];
@@ -153,7 +153,7 @@ void mgo_jacobi(real *x, const real *b, const int32_t *lab, const real *wx, cons
 #pragma omp parallel for schedule(static)
     for (int k = 0; k < nz; ++k)
         memcpy(scratch + (size_t)k * nx * ny, x + (size_t)k * nx * ny, (size_t)nx * ny * sizeof(real));
-    const real damped = 2. / 3.; /* Ops.h:291 */
+    const real damped = weight; /* Ops.h:291 hard-wires 2. / 3. */
 #pragma omp parallel for collapse(2) schedule(static)
     for (int k = 0; k < nz; ++k)
         for (int j = 0; j < ny; ++j)
@@ -167,6 +167,11 @@ void mgo_jacobi(real *x, const real *b, const int32_t *lab, const real *wx, cons
                 x[c] = x[c] + damped * res; /* Ops.h:356-361 */
             }
     if (own) free(scratch);
+}
+void mgo_jacobi(real *x, const real *b, const int32_t *lab, const real *wx, const real *wy,
+                const real *wz, int nx, int ny, int nz, real *scratch)
+{
+    mgo_jacobi_weighted(x, b, lab, wx, wy, wz, nx, ny, nz, scratch, 2. / 3.);
 }
 
 /* tiledGaussSeidelPoissonSmoother (Ops.h:369-520): undamped in-place GS over the 16^3 tiles whose
@@ -215,15 +220,15 @@ void mgo_tiled_gs(real *x, const real *b, const int32_t *lab, const real *wx, co
 
 /* boundaryJacobiPoissonSmoother (Ops.h:524-619): damped Jacobi on the band list; compute into a
  * temp list, then scatter.  cells = ncells x (i,j,k) int32 triples. */
-void mgo_boundary_jacobi(real *x, const real *b, const int32_t *lab, const int32_t *cells,
-                         int64_t ncells, const real *wx, const real *wy, const real *wz, int nx,
-                         int ny, int nz)
+void mgo_boundary_jacobi_weighted(real *x, const real *b, const int32_t *lab, const int32_t *cells,
+                                  int64_t ncells, const real *wx, const real *wy, const real *wz, int nx,
+                                  int ny, int nz, double weight)
 {
     const dims_t d = {nx, ny, nz};
     const real *w[3];
     pack_w(wx, wy, wz, w);
     const real *const *wp = wx ? w : NULL;
-    const real damped = 2. / 3.; /* Ops.h:554 */
+    const real damped = weight; /* Ops.h:554 hard-wires 2. / 3. */
     real *tmp = (real *)malloc((size_t)(ncells > 0 ? ncells : 1) * sizeof(real));
 #pragma omp parallel for schedule(static)
     for (int64_t n = 0; n < ncells; ++n) {
@@ -239,6 +244,12 @@ void mgo_boundary_jacobi(real *x, const real *b, const int32_t *lab, const int32
     for (int64_t n = 0; n < ncells; ++n) /* Ops.h:604-618 */
         x[cidx(&d, cells[3 * n], cells[3 * n + 1], cells[3 * n + 2])] = tmp[n];
     free(tmp);
+}
+void mgo_boundary_jacobi(real *x, const real *b, const int32_t *lab, const int32_t *cells,
+                         int64_t ncells, const real *wx, const real *wy, const real *wz, int nx,
+                         int ny, int nz)
+{
+    mgo_boundary_jacobi_weighted(x, b, lab, cells, ncells, wx, wy, wz, nx, ny, nz, 2. / 3.);
 }
 
 /* applyPoissonMatrix (Ops.h:621-714): y = A x on active cells, other cells untouched. */
@@ -711,6 +722,7 @@ double mgo_ghost_fluid_weight(double phi0, double phi1)
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
     int levels, alloc_levels, use_gs, band_width, band_iters;
+    double omega; /* damping of the Jacobi and band sweeps; the reference hard-wires 2. / 3. (Ops.h:291, 554) */
     int pre_sweeps, post_sweeps; /* full-domain smoother sweeps per stroke; the reference hard-wires 1 (MG.cpp:466-486, 740-757) */
     dims_t *dims;
     int32_t **lab;
@@ -862,6 +874,7 @@ mgo_solver *mgo_solver_create(const int32_t *labels, const real *wx, const real 
     s->use_gs = use_gs;
     s->band_width = 3; /* MG.cpp:141 */
     s->band_iters = 3; /* MG.cpp:142 */
+    s->omega = 2. / 3.;
     s->pre_sweeps = s->post_sweeps = 1;
     s->dims = (dims_t *)calloc((size_t)mg_levels, sizeof(dims_t));
     s->lab = (int32_t **)calloc((size_t)mg_levels, sizeof(void *));
@@ -960,12 +973,33 @@ void mgo_solver_set_sweeps(mgo_solver *s, int pre, int post)
     s->post_sweeps = post > 0 ? post : 1;
 }
 
+/* The three smoothing options the reference hard-wires (MG.cpp:141-142, Ops.h:291, 554), per solver: the band lists of
+ * every level are rebuilt at `band_width`, the band stage runs `band_iters` passes (0: none) and every damped sweep uses
+ * `omega`.  Returns -1 (and changes nothing) for band_width < 1, band_iters < 0 or a non-positive omega. */
+int mgo_solver_set_band_options(mgo_solver *s, int band_width, int band_iters, double omega)
+{
+    if (band_width < 1 || band_iters < 0 || !(omega > 0)) return -1;
+    if (band_width != s->band_width) {
+        fast_free(s); /* its band rows follow the lists */
+        for (int l = 0; l < s->levels; ++l) {
+            const dims_t d = s->dims[l];
+            free(s->band[l]);
+            s->band[l] = NULL;
+            s->band_n[l] = mgo_build_boundary_cells(s->lab[l], d.nx, d.ny, d.nz, band_width, &s->band[l]);
+        }
+        s->band_width = band_width;
+    }
+    s->band_iters = band_iters;
+    s->omega = omega;
+    return 0;
+}
+
 static void smooth_stroke(mgo_solver *s, int l, real *x, const real *b, int down)
 {
     const dims_t d = s->dims[l];
     const real *wx = l == 0 ? s->w[0] : NULL, *wy = l == 0 ? s->w[1] : NULL, *wz = l == 0 ? s->w[2] : NULL;
     for (int it = 0; it < s->band_iters; ++it)
-        mgo_boundary_jacobi(x, b, s->lab[l], s->band[l], s->band_n[l], wx, wy, wz, d.nx, d.ny, d.nz);
+        mgo_boundary_jacobi_weighted(x, b, s->lab[l], s->band[l], s->band_n[l], wx, wy, wz, d.nx, d.ny, d.nz, s->omega);
     for (int rep = 0; rep < (down ? s->pre_sweeps : s->post_sweeps); ++rep) {
         if (s->use_gs) {
             if (down) { /* MG.cpp:466-479: odd fwd, even fwd */
@@ -976,10 +1010,10 @@ static void smooth_stroke(mgo_solver *s, int l, real *x, const real *b, int down
                 mgo_tiled_gs(x, b, s->lab[l], wx, wy, wz, d.nx, d.ny, d.nz, 1, 0);
             }
         } else
-            mgo_jacobi(x, b, s->lab[l], wx, wy, wz, d.nx, d.ny, d.nz, s->scratch);
+            mgo_jacobi_weighted(x, b, s->lab[l], wx, wy, wz, d.nx, d.ny, d.nz, s->scratch, s->omega);
     }
     for (int it = 0; it < s->band_iters; ++it)
-        mgo_boundary_jacobi(x, b, s->lab[l], s->band[l], s->band_n[l], wx, wy, wz, d.nx, d.ny, d.nz);
+        mgo_boundary_jacobi_weighted(x, b, s->lab[l], s->band[l], s->band_n[l], wx, wy, wz, d.nx, d.ny, d.nz, s->omega);
 }
 
 /* applyVCycle (MG.cpp:420-881). */
@@ -1123,7 +1157,7 @@ static void fast_pass(mgo_solver *s, int l, int mode, real *out, const real *x, 
     const real *w[3] = {s->w[0], s->w[1], s->w[2]};
     const real *const *wp = l == 0 ? w : NULL;
     const ptrdiff_t sy = d.nx, sz = (ptrdiff_t)d.nx * d.ny;
-    const real damped = 2. / 3., sixth = (real)6;
+    const real damped = s->omega, sixth = (real)6;
 #pragma omp parallel for collapse(2) schedule(static)
     for (int k = 0; k < d.nz; ++k)
         for (int j = 0; j < d.ny; ++j) {
@@ -1165,7 +1199,7 @@ static void fast_band(mgo_solver *s, int l, real *x, const real *b)
     const real *row = f->brow[l];
     real *tmp = f->btmp[l];
     const ptrdiff_t sy = d.nx, sz = (ptrdiff_t)d.nx * d.ny;
-    const real damped = 2. / 3.;
+    const real damped = s->omega;
     for (int it = 0; it < s->band_iters; ++it) {
 #pragma omp parallel for schedule(static)
         for (int64_t t = 0; t < nb; ++t) {

@@ -105,21 +105,30 @@ class Oracle:
         return ws, tuple(_ptr(a) for a in ws)
 
     # -- operators (in place on x / outputs) ---------------------------------------------------
-    def jacobi(self, x, b, lab, w=None):
+    def jacobi(self, x, b, lab, w=None, weight=None):
+        """weight: the damping factor (None: the reference's 2/3)."""
         nz, ny, nx = lab.shape
         keep, wp = self._wp(w)
-        self.lib.mgo_jacobi(_ptr(x), _ptr(b), _ptr(lab), *wp, nx, ny, nz, None)
+        if weight is None:
+            self.lib.mgo_jacobi(_ptr(x), _ptr(b), _ptr(lab), *wp, nx, ny, nz, None)
+        else:
+            self.lib.mgo_jacobi_weighted(_ptr(x), _ptr(b), _ptr(lab), *wp, nx, ny, nz, None, C.c_double(weight))
 
     def tiled_gs(self, x, b, lab, odd, forward, w=None):
         nz, ny, nx = lab.shape
         keep, wp = self._wp(w)
         self.lib.mgo_tiled_gs(_ptr(x), _ptr(b), _ptr(lab), *wp, nx, ny, nz, int(odd), int(forward))
 
-    def boundary_jacobi(self, x, b, lab, cells, w=None):
+    def boundary_jacobi(self, x, b, lab, cells, w=None, weight=None):
         nz, ny, nx = lab.shape
         keep, wp = self._wp(w)
         cells = np.ascontiguousarray(cells, dtype=np.int32)
-        self.lib.mgo_boundary_jacobi(_ptr(x), _ptr(b), _ptr(lab), _ptr(cells), C.c_int64(len(cells)), *wp, nx, ny, nz)
+        if weight is None:
+            self.lib.mgo_boundary_jacobi(_ptr(x), _ptr(b), _ptr(lab), _ptr(cells), C.c_int64(len(cells)), *wp, nx, ny, nz)
+        else:
+            self.lib.mgo_boundary_jacobi_weighted(
+                _ptr(x), _ptr(b), _ptr(lab), _ptr(cells), C.c_int64(len(cells)), *wp, nx, ny, nz, C.c_double(weight)
+            )
 
     def apply_poisson(self, y, x, lab, w=None):
         nz, ny, nx = lab.shape
@@ -225,14 +234,16 @@ class Oracle:
     def ghost_fluid_weight(self, phi0, phi1):
         return self.lib.mgo_ghost_fluid_weight(C.c_double(phi0), C.c_double(phi1))
 
-    def solver(self, lab, w, levels, use_gs, pre_sweeps=1, post_sweeps=1):
-        return OracleSolver(self, lab, w, levels, use_gs, pre_sweeps, post_sweeps)
+    def solver(self, lab, w, levels, use_gs, pre_sweeps=1, post_sweeps=1, band_width=3, band_iterations=3, jacobi_weight=2 / 3):
+        """band_width / band_iterations / jacobi_weight: the smoothing options the reference hard-wires at
+        3 / 3 / 2/3.  To compare with a float32 implementation pass jacobi_weight as float(np.float32(w))."""
+        return OracleSolver(self, lab, w, levels, use_gs, pre_sweeps, post_sweeps, band_width, band_iterations, jacobi_weight)
 
 
 class OracleSolver:
     """GeometricMultigridPoissonSolver (MG.h:10-53) on flat arrays."""
 
-    def __init__(self, orc, lab, w, levels, use_gs, pre_sweeps=1, post_sweeps=1):
+    def __init__(self, orc, lab, w, levels, use_gs, pre_sweeps=1, post_sweeps=1, band_width=3, band_iterations=3, jacobi_weight=2 / 3):
         self.o = orc
         self.labels = orc.lab(lab)
         self.w = [orc.arr(a) for a in w]
@@ -245,6 +256,11 @@ class OracleSolver:
         self.h = C.c_void_p(self.h)
         if (pre_sweeps, post_sweeps) != (1, 1):  # benchmark variant; the reference's schedule is 1 / 1
             orc.lib.mgo_solver_set_sweeps(self.h, int(pre_sweeps), int(post_sweeps))
+        self.band_width, self.band_iterations, self.jacobi_weight = int(band_width), int(band_iterations), float(jacobi_weight)
+        if (self.band_width, self.band_iterations, self.jacobi_weight) != (3, 3, 2 / 3):
+            if orc.lib.mgo_solver_set_band_options(self.h, self.band_width, self.band_iterations, C.c_double(self.jacobi_weight)) != 0:
+                self.close()
+                raise ValueError("oracle: band_width >= 1, band_iterations >= 0 and jacobi_weight > 0 are required")
 
     def close(self):
         if self.h:

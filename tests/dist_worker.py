@@ -193,6 +193,81 @@ def gpu_mode():
         assert counts[(False, 1)] < 0.6 * counts[(False, 0)] and counts[(True, 1)] < 0.7 * counts[(True, 0)], counts
 
 
+def band_options_mode():
+    """options.band_width / band_iterations / jacobi_weight away from 3 / 3 / 2/3 on cut levels, random-label domain of gpu_mode
+    (general cells in every group across the cuts): (4, 4, 0.5) -- depth 4 fills the 5 ghost planes of the grids, a box region
+    reaches depth + 1 planes past its owned box (on level 1; the fine level cannot form depth-4 boxes among its general cells and
+    runs pass by pass on every rank) -- and (1, 1, 0.8), box form (deep_band_halo = 1) and an exchange per pass (0),
+    both smoothers, against the whole-grid solver at the same options (which tests/test_band_options.py holds to the oracle), to
+    gpu_mode's bounds.  Then (8, 4, 2/3): the widest label reach the options allow, (8 - 1) + (4 + 2) + 1 = 14 of 16 planes."""
+    import ctypes as C
+
+    import geometricmultigridpressuresolver_amd as G
+    from geometricmultigridpressuresolver_amd import domains as D
+    from geometricmultigridpressuresolver_amd.distributed import SlabSolver, TorchDistComm
+    from test_device_setup import random_domain
+
+    rank, size = dist.get_rank(), dist.get_world_size()
+    torch.cuda.set_device(0)
+    shape, lev = (64, 64, 96), 3
+    lab, w = random_domain(shape, lev, 4, closed_faces=False)
+    dx = 1.0 / shape[2]
+    nz = lab.shape[0]
+    nzl = nz // size
+    z0, z1 = rank * nzl, (rank + 1) * nzl
+    assert any(D.active_mask(lab[c - 1 : c + 1]).any() for c in range(nzl, nz, nzl))
+    slab_w = [w[0][z0:z1], w[1][z0:z1], w[2][z0 : z1 + 1]]
+    b_glob, b_pcg = D.random_rhs(lab, dx), D.random_rhs(lab, dx, seed=9)
+
+    def options(bw, bi, om, slab_run, deep=1):
+        o = G.default_options()
+        o.band_width, o.band_iterations, o.jacobi_weight = bw, bi, om
+        if slab_run:
+            o.min_cells_per_rank, o.deep_band_halo = 0, deep
+        return o
+
+    for bw, bi, om in ((4, 4, 0.5), (1, 1, 0.8), (8, 4, 2.0 / 3.0)):
+        widest = bw == 8
+        for use_gs, deep in ((False, 1),) if widest else ((False, 1), (False, 0), (True, 1), (True, 0)):
+            opt = options(bw, bi, om, True, deep)
+            comm = TorchDistComm()
+            slab = SlabSolver(lab, slab_w, lev, use_gs, comm, device=0, options=opt)
+            whole = G.GeometricMultigridPoissonSolver(lab, w, lev, use_gs, device=0, options=options(bw, bi, om, False))
+            assert slab.slab_range(0) == (z0, z1) and 1 <= slab.distributed_levels < slab.getMGLevels() == whole.getMGLevels()
+            # the form of a cut level: the whole-grid solver's -- boxes, but for the fine level at depth 4: among this domain's general
+            # cells a box of one cell still holds more than kBoxMaxGeneral of them (tests/test_band_options.py: _boxes_expected), and
+            # the ranks agree on pass by pass there; level 1 (unit weights) takes the depth-4 boxes with their 5 ghost planes
+            wform = C.c_int(-1)
+            for l in range(slab.distributed_levels):
+                G.lib().mgps_band_stage_form(whole.h, l, C.byref(wform))
+                assert wform.value == (0 if bi == 4 and l == 0 else 1), (bw, bi, l, wform.value)
+                assert slab.band_stage_form(l) == ("boxes" if deep == 1 and wform.value == 1 else "passes"), (bw, bi, l, deep)
+            assert slab.ghost_planes == 5 and (bi != 4 or slab.distributed_levels >= 2)
+            boxed = deep == 1 and any(slab.band_stage_form(l) == "boxes" for l in range(slab.distributed_levels))
+            bw_, bs = whole.to_device(b_glob), slab.to_device(b_glob[z0:z1])
+            xw, xs = whole.new_grid(), slab.new_grid()
+            for it in range(2):
+                whole.applyVCycle(xw, bw_, it > 0)
+                slab.applyVCycle(xs, bs, it > 0)
+                err = rel_l2(slab.gather_global(xs), xw.cpu().numpy())
+                assert float(xw.abs().max()) > 0 and err < 1e-6, (bw, bi, om, use_gs, deep, it, err)
+            assert (comm.segmented_exchanges > 0) == boxed, (deep, comm.segmented_exchanges)
+            if not widest:
+                xw, xs = whole.new_grid(), slab.new_grid()
+                sw = whole.solveGeometricConjugateGradient(xw, whole.to_device(b_pcg), 1e-5, 200, True)
+                ss = slab.solveGeometricConjugateGradient(xs, slab.to_device(b_pcg[z0:z1]), 1e-5, 200, True)
+                assert sw["outcome"] == ss["outcome"] == "converged" and abs(ss["iterations"] - sw["iterations"]) <= 1, (ss, sw)
+                assert rel_l2(slab.gather_global(xs), xw.cpu().numpy()) < 1e-4
+            if deep == 1 and not use_gs:
+                compare_with_host_builder(slab, lab, slab_w, lev, use_gs, opt, ("random", size, bw, bi))
+            if rank == 0:
+                print(f"  band options ({bw}, {bi}, {om:.2f}) gs={use_gs} deep={deep}: D={slab.distributed_levels} exchanges={comm.exchanges}"
+                      + ("" if widest else f" pcg it {ss['iterations']} (whole grid {sw['iterations']})"), flush=True)
+            slab.close()
+            whole.close()
+            dist.barrier()
+
+
 def plane_mode():
     """The plane-marching sweep (stencilPlaneKernel, the 1024^3 kernel) on cut slabs: its ghostLo / ghostHi reads of the
     plane below the first and above the last owned plane.  options.stencil_path = 2 forces it onto a 264 x 40 x 32 (two ranks) or 272 x 72 x 64 (four ranks, four levels)
@@ -528,6 +603,8 @@ if __name__ == "__main__":
         gpu_mode()
     elif mode == "plane":
         plane_mode()
+    elif mode == "bandopts":
+        band_options_mode()
     elif mode == "balanced":
         balanced_mode()
     elif mode == "rccl1":

@@ -57,6 +57,15 @@ def test_four_slabs_match_single_gpu():
 
 
 @pytest.mark.gpu
+def test_two_slabs_band_options():
+    """options.band_width / band_iterations / jacobi_weight on cut levels: (4, 4, 0.5) -- the depth limit of the 5 ghost planes --
+    and (1, 1, 0.8), box form and pass by pass, both smoothers, against the whole-grid solver at the same options; (8, 4, 2/3), the
+    widest label reach the options allow, is accepted and agrees too."""
+    out = run_workers("bandopts", 2, 420)
+    print(out[-1500:])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("nproc", [2, 4])
 def test_slabs_plane_marching_sweep(nproc):
     """stencilPlaneKernel -- the sweep a 1024^3 slab run executes -- on cut slabs (ghost planes below / above): forced

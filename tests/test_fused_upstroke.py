@@ -22,6 +22,11 @@ from geometricmultigridpressuresolver_amd import domains as D
 from oracle.mg_oracle import Oracle
 
 case, fused, out = sys.argv[1], sys.argv[2] == '1', sys.argv[3]
+# optional: band_width,band_iterations,jacobi_weight for the solver and the oracle (default: the options' defaults)
+band = None
+if len(sys.argv) > 4:
+    bw, bi, om = sys.argv[4].split(',')
+    band = (int(bw), int(bi), float(om))
 
 
 def boxed(shape, fill):
@@ -63,11 +68,16 @@ else:  # random labels: liquid with DIRICHLET cells scattered through it (every 
         bl[1:-1, 1:-1, 1:-1] = np.where(np.random.default_rng(3).random((22, 30, 246)) < 0.95, D.INTERIOR, D.DIRICHLET)
     bl, bw = boxed((24, 32, 248), speckled)
     lab, w, off, lev = D.expand_domain(bl, bw, levels=3, solver_shape=(32, 40, 264))
-s = G.GeometricMultigridPoissonSolver(lab, w, lev, False)
+opt = G.default_options()
+okw = {}
+if band:
+    opt.band_width, opt.band_iterations, opt.jacobi_weight = band
+    okw = dict(band_width=band[0], band_iterations=band[1], jacobi_weight=float(np.float32(band[2])))
+s = G.GeometricMultigridPoissonSolver(lab, w, lev, False, options=opt)
 flags = [s.up_stroke_fused(l) for l in range(s.getMGLevels())]
 assert s.stencil_kernel(0) == 'plane' and flags[0] == fused, (s.stencil_kernel(0), flags)
 assert not any(flags[1:]), flags  # (level 1 is too narrow for plane blocks: the MG-PCG arm, whose level 0 gathers <z, r>, never fuses)
-if fused:  # where it must not run: Gauss-Seidel, binary16 fine level, 2 + 2 sweeps
+if fused and not band:  # where it must not run: Gauss-Seidel, binary16 fine level, 2 + 2 sweeps
     assert not G.GeometricMultigridPoissonSolver(lab, w, lev, True).up_stroke_fused(0)
     for name, value in (('precision', 1), ('post_sweeps', 2)):
         o = G.default_options()
@@ -89,7 +99,7 @@ for _ in range(3):
     s.applyVCycle(x, bd, True)
 x6 = x.cpu().numpy()
 assert np.all(x6[~act] == 0.0) and np.all(x3[~act] == 0.0)
-ref = Oracle().solver(lab.astype(np.int32), [a.astype(np.float64) for a in w], lev, False)
+ref = Oracle().solver(lab.astype(np.int32), [a.astype(np.float64) for a in w], lev, False, **okw)
 xr = np.zeros(lab.shape)
 ref.apply_vcycle(xr, b.astype(np.float64), False)
 err = np.linalg.norm(x1 - xr) / np.linalg.norm(xr)
@@ -101,9 +111,10 @@ print('FUSED_UP_OK', json.dumps({'err': err, 'iterations': st['iterations'], 'ou
 """
 
 
-def _run(case, fused, path):
+def _run(case, fused, path, band=None):
     env = dict(os.environ, MGPS_FUSE_UP=fused, MGPS_STENCIL="plane")
-    res = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}, case, fused, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+    args = [case, fused, path] + ([band] if band else [])
+    res = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}] + args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                          text=True, timeout=600, env=env)
     assert res.returncode == 0 and "FUSED_UP_OK" in res.stdout, res.stdout[-3000:]
     return json.loads(res.stdout.split("FUSED_UP_OK", 1)[1].strip().splitlines()[0])
@@ -121,6 +132,22 @@ def test_fused_upstroke_equals_separate_prolongation(case):
     with tempfile.TemporaryDirectory() as tmp:
         runs = {f: (_run(case, f, os.path.join(tmp, f"r{f}.npz")), np.load(os.path.join(tmp, f"r{f}.npz"))) for f in ("1", "0")}
         (m1, a1), (m0, a0) = runs["1"], runs["0"]
+        for key in ("x3", "x6", "xp"):
+            assert np.array_equal(a1[key], a0[key]), (key, np.abs(a1[key] - a0[key]).max())
+        assert m1["iterations"] == m0["iterations"] and m1["outcome"] == m0["outcome"] == "converged", (m1, m0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("band", ["2,2,0.8", "4,4,0.5"])
+@pytest.mark.parametrize("case", ["wsolid", "random"])
+def test_fused_upstroke_at_band_options(case, band):
+    """The same at band_width, band_iterations, jacobi_weight = 2, 2, 0.8 and 4, 4, 0.5 (the closure launch of the fused up-stroke
+    runs depth + 1 passes over the prolonged input and the sweep damps by the option's weight): bit for bit with and without the
+    fusion, and the first cycle within 1e-5 of the oracle's at the same options (asserted in the child)."""
+    with tempfile.TemporaryDirectory() as tmp:
+        runs = {f: (_run(case, f, os.path.join(tmp, f"r{f}.npz"), band), np.load(os.path.join(tmp, f"r{f}.npz"))) for f in ("1", "0")}
+        (m1, a1), (m0, a0) = runs["1"], runs["0"]
+        assert m1["flags"][0] and not m0["flags"][0], (m1, m0)
         for key in ("x3", "x6", "xp"):
             assert np.array_equal(a1[key], a0[key]), (key, np.abs(a1[key] - a0[key]).max())
         assert m1["iterations"] == m0["iterations"] and m1["outcome"] == m0["outcome"] == "converged", (m1, m0)

@@ -389,3 +389,88 @@ def test_optimised_cpu_cycle_equals_the_faithful_one(kind, oracle):
     gs = oracle.solver(lab.astype(np.int32), w, lev, True)
     with pytest.raises(ValueError):
         gs.apply_vcycle_fast(x_fast, b, False)
+
+
+# band_width / band_iterations / jacobi_weight: the reference hard-wires 3 / 3 / 2/3 (MG.cpp:141-142, Ops.h:291, 554); the
+# oracle takes them per solver so that the HIP library's options of the same names have something to be compared with
+OPTION_SETS = [(1, 1, 2 / 3), (4, 4, 0.5), (3, 0, 2 / 3)]
+
+
+@pytest.mark.parametrize("use_gs", [False, True])
+@pytest.mark.parametrize("bw,bi,omega", OPTION_SETS)
+def test_symmetry_vcycle_with_band_options(bw, bi, omega, use_gs, oracle):
+    """<M a, b> = <M b, a> (Test.cpp:1808-1875, 1e-10) does not depend on the three options: the band stage runs the same
+    passes before and after the sweep, and a damped Jacobi pass is symmetric for any weight."""
+    lab, w, off, lev, dx = dom64("solid", 24)
+    a, b = rand_pair(lab, dx, 2)
+    s = oracle.solver(lab, w, lev, use_gs, band_width=bw, band_iterations=bi, jacobi_weight=omega)
+
+    def four_cycles(rhs):
+        x = np.zeros_like(rhs)
+        for it in range(4):
+            s.apply_vcycle(x, rhs, it > 0)
+        assert (x[~D.active_mask(lab)] == 0).all()
+        return x
+
+    sym_check(oracle, lab, four_cycles, a, b)
+    # the options are in effect: the cycle is not the default one
+    d = oracle.solver(lab, w, lev, use_gs)
+    xo, xd = np.zeros_like(a), np.zeros_like(a)
+    s.apply_vcycle(xo, a, False)
+    d.apply_vcycle(xd, a, False)
+    assert np.linalg.norm(xo - xd) > 1e-3 * np.linalg.norm(xd)
+
+
+@pytest.mark.parametrize("width", [1, 2, 4, 5, 8])
+def test_solver_band_follows_band_width(width, oracle):
+    lab, w, off, lev, dx = dom64("solid", 24)
+    s = oracle.solver(lab, w, lev, False, band_width=width, band_iterations=2)
+    d = oracle.solver(lab, w, lev, False)
+    for l in range(s.levels):
+        ll = s.level_labels(l)
+        assert np.array_equal(s.band(l), oracle.build_boundary_cells(ll, width)), l
+        assert np.array_equal(d.band(l), oracle.build_boundary_cells(ll, 3)), l
+    assert len(s.band(0)) != len(d.band(0))
+    with pytest.raises(ValueError):
+        oracle.solver(lab, w, lev, False, band_width=0)
+    with pytest.raises(ValueError):
+        oracle.solver(lab, w, lev, False, band_iterations=-1)
+
+
+def test_operator_weights(oracle):
+    """jacobi / boundary_jacobi with weight=: the update is linear in the weight, x0 + omega (D^-1 (b - A x0)); the default
+    call is weight 2/3 bit for bit."""
+    lab, w, off, lev, dx = dom64("solid", 24)
+    a, b = rand_pair(lab, dx, 5)
+    band = oracle.build_boundary_cells(lab, 2)
+    for op in (lambda x, **kw: oracle.jacobi(x, b, lab, w, **kw), lambda x, **kw: oracle.boundary_jacobi(x, b, lab, band, w, **kw)):
+        x1, xd, xt = a.copy(), a.copy(), a.copy()
+        op(x1, weight=1.0)
+        op(xd)
+        op(xt, weight=2 / 3)
+        assert np.array_equal(xd, xt)
+        for omega in (0.5, 0.8):
+            xo = a.copy()
+            op(xo, weight=omega)
+            assert np.abs(xo - (a + omega * (x1 - a))).max() <= 1e-14 * np.abs(x1).max()
+            assert np.abs(xo - xd).max() > 1e-3 * np.abs(xd).max()
+
+
+@pytest.mark.parametrize("bw,bi,omega", [(4, 4, 0.5), (1, 1, 0.8), (3, 0, 2 / 3)])
+def test_optimised_cpu_cycle_honours_band_options(bw, bi, omega, oracle):
+    """mgo_solver_apply_vcycle_fast reads the solver's width, depth and weight: equal to the faithful cycle to the round-off
+    bound of test_optimised_cpu_cycle_equals_the_faithful_one, and different from the default-option cycle."""
+    lev = 3
+    lab, w, h = D.free_surface_pool(64, lev)
+    w = [a.astype(np.float64) for a in w]
+    s = oracle.solver(lab.astype(np.int32), w, lev, False, band_width=bw, band_iterations=bi, jacobi_weight=omega)
+    d = oracle.solver(lab.astype(np.int32), w, lev, False)
+    b = D.random_rhs(lab, h, dtype=np.float64)
+    x_ref, x_fast, x_def = np.zeros_like(b), np.zeros_like(b), np.zeros_like(b)
+    d.apply_vcycle_fast(x_def, b, False)  # the default solver's cached rows must not leak into another solver's
+    for it in range(3):
+        s.apply_vcycle(x_ref, b, it > 0)
+        s.apply_vcycle_fast(x_fast, b, it > 0)
+        assert np.abs(x_ref).max() > 0 and np.abs(x_ref - x_fast).max() <= 1e-12 * np.abs(x_ref).max(), it
+    s.apply_vcycle_fast(x_fast, b, False)
+    assert np.linalg.norm(x_fast - x_def) > 1e-3 * np.linalg.norm(x_def)
