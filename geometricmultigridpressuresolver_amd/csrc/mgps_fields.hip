@@ -1552,7 +1552,8 @@ try {
     std::memcpy(&cm, comm, size_t(comm->struct_size));  // (struct_size bytes are the caller's; the rest reads as NULL)
     cm.struct_size = int(sizeof(mgps_comm));
     const int P = cm.size, rank = cm.rank;
-    if (P > 1 && (!cm.gatherv || !cm.scatterv)) return invalid("the whole grid's labels reach every rank through gatherv and scatterv: the transport has none");
+    if (P > 1 && (!cm.gatherv || !cm.scatterv))
+        return invalid("the collapse of uneven cuts and the enclosed-liquid merge go through gatherv and scatterv (and, with host_setup, the whole grid's labels): the transport has none");
     mgps_options o;
     mgps_default_options(&o);
     if (opt) {
@@ -1571,6 +1572,9 @@ try {
     const int gx = s.gx, gy = s.gy, nzl = s.c1 - s.c0, ex = s.ex, ey = s.ey, ez = s.ez, nze = s.e1 - s.e0;
     const bool lo = s.c0 > 0, hi = s.c1 < s.gz;  // a neighbour with base planes on that side (every rank has some)
     const size_t plane = size_t(gx) * gy, cells = plane * size_t(nzl), eplane = size_t(ex) * ey, ecells = eplane * size_t(ez);
+    // the solver is built from the rank's own label planes (mgps_create_slab_device_labels).  The host builder needs the whole
+    // grid's labels on every rank's host: with it they are gathered and broadcast as before (options and environment are everybody's)
+    const bool labelsToHosts = hostSetupRequested(o);
     hipStream_t st = static_cast<hipStream_t>(stream);
     p->mg_levels = levels;
     p->offset = s.off;
@@ -1631,14 +1635,15 @@ try {
                 valid[a] = p->valid_faces[a] ? p->valid_faces[a] : pool.get<uint8_t>(faceCount(gx, gy, nzl, a));
                 w[a] = pool.get<float>(faceCount(ex, ey, nze, a));
             }
-            labelsAll = pool.get<uint8_t>(ecells);  // the whole grid's labels; this rank's pass writes its window in place
+            // the labels pass writes the rank's window: a buffer of its own, or (host set-up) in place in the whole grid's labels
+            labelsAll = pool.get<uint8_t>(labelsToHosts ? ecells : size_t(nze) * eplane);
             count = pool.get<unsigned long long>(1);
         } catch (const std::bad_alloc &) {
             setLastGlobalError("mgps_project_free_surface_slab: device allocation failed");
             return MGPS_ERR_ALLOC;
         }
-        labelsHost = mgps_host_alloc(ecells);
-        if (!labelsHost) {
+        if (labelsToHosts) labelsHost = mgps_host_alloc(ecells);
+        if (labelsToHosts && !labelsHost) {
             setLastGlobalError("mgps_project_free_surface_slab: host allocation of the whole grid's labels failed");
             return MGPS_ERR_ALLOC;
         }
@@ -1690,7 +1695,7 @@ try {
     SLAB_COMM(tradePlane(p->liquid_phi, phiHalo, phiHalo + plane, sizeof(float), "liquid_phi"));
     if (status == MGPS_OK) step(mgps_fields_slab_material_labels(&desc, matOwn, p->liquid_phi, phiLo, phiHi, p->solid_phi, cw[0], cw[1], cw[2], st));
     SLAB_COMM(tradePlane(matOwn, material, matOwn + cells, sizeof(int32_t), "material labels"));
-    uint8_t *labelsWin = labelsAll + size_t(s.e0) * eplane;
+    uint8_t *labelsWin = labelsToHosts ? labelsAll + size_t(s.e0) * eplane : labelsAll;
     if (status == MGPS_OK) step(mgps_fields_slab_faces(&desc, valid, w, matOwn, matLo, matHi, p->liquid_phi, phiLo, phiHi, cw, st));
     if (status == MGPS_OK) step(mgps_fields_slab_labels(&desc, labelsWin, matOwn, matLo, matHi, w, st));
     // ---- 2. liquid cells over all ranks; a domain without liquid has nothing to solve (the single-device rule)
@@ -1718,9 +1723,10 @@ try {
         p->stats.outcome = MGPS_PCG_RHS_ZERO;
         return MGPS_OK;
     }
-    // ---- 3. the whole grid's labels on every rank's host: gatherv to rank 0 (every window already sits at its place of the
-    //         rank's whole-grid buffer), then scatterv with every other rank's range set to the whole buffer -- a broadcast
-    if (P > 1) {
+    // ---- 3. the ranks agree that the passes went through (the constructor is a collective).  Host set-up only: the whole grid's
+    //         labels on every rank's host -- gatherv to rank 0 (every window already sits at its place of the rank's whole-grid
+    //         buffer), then scatterv with every other rank's range set to the whole buffer, a broadcast
+    if (labelsToHosts && P > 1) {
         std::vector<size_t> counts(static_cast<size_t>(P), 0), displs(static_cast<size_t>(P), 0);
         for (int r = 0; r < P; ++r) {
             counts[size_t(r)] = r == 0 ? 0 : size_t(splits[r + 1] - splits[r]) * eplane;  // (rank 0's window is in place)
@@ -1739,17 +1745,20 @@ try {
             return MGPS_ERR_COMM;
         }
     }
-    hipStep(hipMemcpyAsync(labelsHost, labelsAll, ecells, hipMemcpyDeviceToHost, st), "labels to the host");
-    hipStep(hipStreamSynchronize(st), "labels to the host");
-    SLAB_COMM(agreeRanks(&cm, status, "labels to the host"));
+    if (labelsToHosts) {
+        hipStep(hipMemcpyAsync(labelsHost, labelsAll, ecells, hipMemcpyDeviceToHost, st), "labels to the host");
+        hipStep(hipStreamSynchronize(st), "labels to the host");
+    }
+    SLAB_COMM(agreeRanks(&cm, status, labelsToHosts ? "labels to the host" : "labels"));
     const auto t2 = clock::now();
     p->stage_ms[1] = ms(t1, t2);
     // ---- 4. the slab solver on the rank's expanded weights (borrowed: the pool outlives the solver), rhs, warm start, surface
     //         term, enclosed-liquid projection, MG-PCG (Plug.cpp:386-629)
     mgps_solver *mg = nullptr;
     o.borrow_device_weights = 1;
-    if (int rc = mgps_create_slab_device_weights(&mg, ex, ey, ez, static_cast<const uint8_t *>(labelsHost), w[0], w[1], w[2], levels, p->use_gauss_seidel,
-                                                 &o, &cm, splits);
+    if (int rc = labelsToHosts ? mgps_create_slab_device_weights(&mg, ex, ey, ez, static_cast<const uint8_t *>(labelsHost), w[0], w[1], w[2], levels,
+                                                                 p->use_gauss_seidel, &o, &cm, splits)
+                               : mgps_create_slab_device_labels(&mg, ex, ey, ez, labelsWin, w[0], w[1], w[2], levels, p->use_gauss_seidel, &o, &cm, splits);
         rc != MGPS_OK)
         return rc;  // (a collective with one verdict)
     struct Guard {
@@ -1835,7 +1844,7 @@ try {
     p->solve_ms = ms(t4, t5);
     p->total_ms = ms(t0, t6);
     if (setupTimingOn())
-        std::printf("projection slab rank %d: passes %.2f ms, labels to hosts %.2f ms, solver set-up %.2f ms, rhs %.2f ms, solve %.2f ms, write-back %.2f ms "
+        std::printf("projection slab rank %d: passes %.2f ms, agreement (host set-up: labels to hosts) %.2f ms, solver set-up %.2f ms, rhs %.2f ms, solve %.2f ms, write-back %.2f ms "
                     "(plane exchanges %.2f ms)\n",
                     rank, p->stage_ms[0], p->stage_ms[1], p->stage_ms[2], p->stage_ms[3], p->stage_ms[4], p->stage_ms[5], exchangeMs);
     if (solveRc != MGPS_OK) setLastGlobalError("mgps_project_free_surface_slab: interrupted");

@@ -299,6 +299,7 @@ size_t stencilSweptCells(const GridP &g);
 int stencilKernelOf(const GridP &g);
 int forcedStencilPath();  // MGPS_STENCIL=quad|plane (A/B switch of launchStencil): 0 none, 1 quad, 2 plane
 bool setupTimingOn();     // MGPS_SETUP_TIMING=1: stage times of the set-up on stdout / stderr (mgps_host.cpp)
+bool hostSetupRequested(const mgps_options &o);  // options.host_setup, or MGPS_HOST_SETUP=1 in the environment (mgps_solver.hip)
 int launchStencil(void *stream, StencilOp op, const GridP &g, float *out, const float *x, const float *b, float omega,
                   bool skipInactive);
 // out = A x and *resultDev = <x, A x> over the active cells of level g in one pass (the CG loop's A.p and its dot);
@@ -452,6 +453,10 @@ struct WeightView {
 };
 int launchCoarsenLabels(void *stream, const Dims &fine, const uint8_t *fineLab, uint8_t *coarseLab, int *activeFlag);
 int launchAnyActive(void *stream, const Dims &d, const uint8_t *lab, int *activeFlag);
+// per x-y plane of `planes` planes of `plane` labels each: counts[2 k] = active cells, counts[2 k + 1] = BOUNDARY cells of plane k (the load
+// model of the slab cuts, mgps_slab_partition_device).  partials: planeCountScratch(plane, planes) uint32
+size_t planeCountScratch(size_t plane, int planes);
+int launchPlaneCounts(void *stream, const uint8_t *lab, size_t plane, int planes, uint32_t *partials, uint32_t *counts);
 int launchShellCheck(void *stream, const Dims &d, const uint8_t *lab, int *badFlag);
 int launchMarkBoundary(void *stream, const Dims &d, uint8_t *lab);
 size_t scanScratchInts(size_t n);

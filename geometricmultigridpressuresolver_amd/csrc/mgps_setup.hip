@@ -67,6 +67,78 @@ __global__ __launch_bounds__(256) void anyActiveKernel(const uint32_t *__restric
     if (__any(any) && (threadIdx.x & 63) == 0) flags[0] = 1;
 }
 
+// ---- active and BOUNDARY cells per x-y plane (mgps_slab_partition_device: the load model of the slab cuts) -------------------
+// The caller's labels, the reference's values only: active = INTERIOR or BOUNDARY, as mgps_slab_partition counts them on the host.
+// One byte per cell, read once: a streaming read.  perPlane workgroups share a plane; the plane's bytes from its first 16-byte
+// boundary on are read 16 per lane (a plane of nx * ny bytes starts wherever the planes before it end), the few bytes in front of
+// and behind them one at a time by the plane's first workgroup.  Integer counts: a wave's by shuffles, the four waves' through
+// LDS, the workgroups' by planeCountFoldKernel in index order -- no atomics, the same numbers on every run.
+constexpr int kCountThreads = 256;
+constexpr size_t kCountBlockBytes = size_t(64) << 10;  // 16 loads of 16 B per lane
+constexpr unsigned kCountMaxPerPlane = 64;
+
+__device__ __forceinline__ size_t minSize(size_t a, size_t b) { return a < b ? a : b; }
+// how many of the four bytes of w equal the byte that v4 repeats
+__device__ __forceinline__ unsigned bytesEqual(uint32_t w, uint32_t v4)
+{
+    const uint32_t x = w ^ v4;
+    return __popc(~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu));  // (0x80 is left in every byte of x that is 0)
+}
+
+__global__ __launch_bounds__(kCountThreads) void planeCountKernel(const uint8_t *__restrict__ lab, size_t plane, unsigned perPlane, uint32_t *__restrict__ partials)
+{
+    constexpr uint32_t kInterior4 = 0x01010101u * MGPS_INTERIOR_CELL, kBoundary4 = 0x01010101u * MGPS_BOUNDARY_CELL;
+    const unsigned k = blockIdx.x / perPlane, part = blockIdx.x % perPlane;
+    const uint8_t *p = lab + size_t(k) * plane;
+    const size_t head = minSize(plane, size_t(0 - reinterpret_cast<uintptr_t>(p)) & 15), nv = (plane - head) / 16;
+    const size_t per = (nv + perPlane - 1) / perPlane, v0 = minSize(nv, size_t(part) * per), v1 = minSize(nv, v0 + per);
+    const uint4 *q = reinterpret_cast<const uint4 *>(p + head);
+    unsigned act = 0, bnd = 0;
+#pragma unroll 4
+    for (size_t v = v0 + threadIdx.x; v < v1; v += kCountThreads) {
+        const uint4 w = q[v];
+        const unsigned b = bytesEqual(w.x, kBoundary4) + bytesEqual(w.y, kBoundary4) + bytesEqual(w.z, kBoundary4) + bytesEqual(w.w, kBoundary4);
+        act += b + bytesEqual(w.x, kInterior4) + bytesEqual(w.y, kInterior4) + bytesEqual(w.z, kInterior4) + bytesEqual(w.w, kInterior4);
+        bnd += b;
+    }
+    if (part == 0) {  // the bytes in front of the first and behind the last 16-byte load: fewer than 16 each
+        const size_t tail = head + 16 * nv;
+        for (size_t c = threadIdx.x; c < head + (plane - tail); c += kCountThreads) {
+            const unsigned l = p[c < head ? c : tail + (c - head)];
+            act += l == MGPS_INTERIOR_CELL || l == MGPS_BOUNDARY_CELL;
+            bnd += l == MGPS_BOUNDARY_CELL;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        act += __shfl_down(act, off);
+        bnd += __shfl_down(bnd, off);
+    }
+    __shared__ unsigned waveSum[2][kCountThreads / 64];
+    if ((threadIdx.x & 63) == 0) {
+        waveSum[0][threadIdx.x >> 6] = act;
+        waveSum[1][threadIdx.x >> 6] = bnd;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        unsigned s = 0;
+#pragma unroll
+        for (int w = 0; w < kCountThreads / 64; ++w) s += waveSum[threadIdx.x][w];
+        partials[2 * size_t(blockIdx.x) + threadIdx.x] = s;
+    }
+}
+
+// counts[2 k + t] = the sum of plane k's partials, in workgroup order
+__global__ __launch_bounds__(256) void planeCountFoldKernel(const uint32_t *__restrict__ partials, unsigned perPlane, int planes, uint32_t *__restrict__ counts)
+{
+    const int t = int(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t >= 2 * planes) return;
+    const uint32_t *p = partials + 2 * size_t(t >> 1) * perPlane + (t & 1);
+    uint32_t s = 0;
+    for (unsigned q = 0; q < perPlane; ++q) s += p[2 * q];
+    counts[t] = s;
+}
+
 // flags[0] = 1 when a cell of the outermost layer is not EXTERIOR (unitTestExteriorCells, MG.cpp:235, 252)
 __global__ __launch_bounds__(256) void shellCheckKernel(Dims d, const uint8_t *__restrict__ lab, int *__restrict__ flags)
 {
@@ -1025,6 +1097,18 @@ int launchAnyActive(void *stream, const Dims &d, const uint8_t *lab, int *active
 {
     const size_t nq = d.cells() / 4;  // extents are even: cells() is a multiple of 8
     anyActiveKernel<<<unsigned(std::min<size_t>(blocksFor(nq, 256), 8192)), 256, 0, S(stream)>>>(reinterpret_cast<const uint32_t *>(lab), nq, activeFlag);
+    return int(hipGetLastError());
+}
+namespace {
+unsigned planeCountBlocks(size_t plane) { return unsigned(std::min<size_t>(kCountMaxPerPlane, std::max<size_t>(1, (plane + kCountBlockBytes - 1) / kCountBlockBytes))); }
+}  // namespace
+size_t planeCountScratch(size_t plane, int planes) { return 2 * size_t(std::max(planes, 0)) * planeCountBlocks(plane); }
+int launchPlaneCounts(void *stream, const uint8_t *lab, size_t plane, int planes, uint32_t *partials, uint32_t *counts)
+{
+    if (planes < 1) return int(hipSuccess);
+    const unsigned perPlane = planeCountBlocks(plane);
+    planeCountKernel<<<unsigned(planes) * perPlane, kCountThreads, 0, S(stream)>>>(lab, plane, perPlane, partials);
+    planeCountFoldKernel<<<blocksFor(2 * size_t(planes), 256), 256, 0, S(stream)>>>(partials, perPlane, planes, counts);
     return int(hipGetLastError());
 }
 int launchShellCheck(void *stream, const Dims &d, const uint8_t *lab, int *badFlag)

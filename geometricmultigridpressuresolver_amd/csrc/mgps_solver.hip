@@ -3396,30 +3396,38 @@ int distributedLevelsFor(const int *splits, int size, int nx, int ny, int levels
     }
     return D;
 }
-}  // namespace
 
-extern "C" {
-
-int mgps_slab_partition(int nx, int ny, int nz, const uint8_t *labels, int mg_levels, int size, int use_gauss_seidel,
-                        const mgps_options *opt, int *out_splits)
-try {
-    if (!labels || !out_splits || size < 1 || nx < 1 || ny < 1 || nz < 1 || mg_levels < 1)
-        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_slab_partition: bad arguments");
-    mgps_options o;
-    MGPS_TRY(readOptions(opt, &o));
-    auto uniform = [&] {
-        for (int r = 0; r <= size; ++r) out_splits[r] = int(int64_t(nz) * r / size);
-    };
-    uniform();
-    if (size == 1 || nz % size != 0) return MGPS_OK;  // (a grid that does not divide is refused by the constructor)
+// ---- the cuts of a slab run: what mgps_slab_partition (labels on the host) and mgps_slab_partition_device (label windows on the
+// ranks' devices) share.  Both count active and BOUNDARY cells per plane in their own way; everything else is here.
+struct PartitionPlan {
+    int unit = 0;  // the cuts fall on multiples of `unit` fine planes; 0: the even cut stands, nothing to count
+    int D = 0, minUnits = 0;
+};
+// fills out_splits with the even cut and says whether (and on which granule) balanced cuts are worth looking for
+PartitionPlan partitionPlan(int nx, int ny, int nz, int mg_levels, int size, bool useGS, const mgps_options &o, int *out_splits)
+{
+    PartitionPlan plan;
+    for (int r = 0; r <= size; ++r) out_splits[r] = int(int64_t(nz) * r / size);
+    if (size == 1 || nz % size != 0) return plan;  // (a grid that does not divide is refused by the constructor)
     // depth of the distributed part as the even cut gives it; the balanced cuts keep it
-    const int D = distributedLevelsFor(out_splits, size, nx, ny, mg_levels, use_gauss_seidel != 0, o);
-    if (D < 1 || use_gauss_seidel) return MGPS_OK;  // Gauss-Seidel: cuts on multiples of 16 planes of EVERY distributed level -- the even cut
-    const int unit = 1 << D;                         // Jacobi: whole planes of the collapse level (round 5: the device-side set-up takes cuts that are not
-                                                     // multiples of 16 planes; at 1024^3 / 8 ranks the unit of 8 planes is what lets the middle ranks shed load)
-    if (nz % unit != 0) return MGPS_OK;
+    const int D = distributedLevelsFor(out_splits, size, nx, ny, mg_levels, useGS, o);
+    if (D < 1 || useGS) return plan;  // Gauss-Seidel: cuts on multiples of 16 planes of EVERY distributed level -- the even cut
+    const int unit = 1 << D;          // Jacobi: whole planes of the collapse level (round 5: the device-side set-up takes cuts that are not
+                                      // multiples of 16 planes; at 1024^3 / 8 ranks the unit of 8 planes is what lets the middle ranks shed load)
+    if (nz % unit != 0) return plan;
     const int units = nz / unit, minUnits = std::max(1, ((kTile << (D - 1)) + unit - 1) / unit);  // (every rank: 16 planes of the coarsest distributed level)
-    if (units < size * minUnits) return MGPS_OK;
+    if (units < size * minUnits) return plan;
+    plan.unit = unit;
+    plan.D = D;
+    plan.minUnits = minUnits;
+    return plan;
+}
+// active / boundary: the counts of each of the nz / plan.unit units of planes (integers; plan.unit > 0); out_splits holds the even cut
+// and keeps it unless balanced cuts gain something
+void partitionFromCounts(const PartitionPlan &plan, int nx, int ny, int nz, int mg_levels, int size, const mgps_options &o, const double *active,
+                         const double *boundary, int *out_splits)
+{
+    const int unit = plan.unit, units = nz / unit, minUnits = plan.minUnits, D = plan.D;
     // Load of a unit of planes: active cells + w x BOUNDARY cells.  The weights are measured (tools/slab_compute_bound.py, 1024^3,
     // one rank at a time with a null transport, round 5: P = 1, 2, 4, 8 fitted by cycle = c x active planes + F x faces + T on
     // rank 0 + a constant): c = 10.8 us per 1024^2 plane of liquid, F = 60 us for a z face of 894^2 BOUNDARY cells (the box form
@@ -3429,27 +3437,13 @@ try {
     const double kBoundaryWeight = (o.fuse_band_passes && o.deep_band_halo && o.band_iterations >= 1 && o.band_iterations <= kBandMaxDepth) ? 6.0 : 30.0;
     constexpr double kTailShare = 0.032;  // (2.3 % by the fit; rank 0 also pays for the EXTERIOR planes in front of the liquid: measured, 3.2 % levels rank 0 with the middle ranks at 1024^3 / 8)
     std::vector<double> load(size_t(units), 0.0);
-    const size_t plane = size_t(nx) * ny;
-    {
-        std::vector<std::thread> pool;
-        const int nt = std::max(1, std::min(units, int(std::thread::hardware_concurrency() ? std::thread::hardware_concurrency() : 4)));
-        for (int t = 0; t < nt; ++t)
-            pool.emplace_back([&, t] {
-                for (int u = t; u < units; u += nt) {
-                    const uint8_t *p = labels + size_t(u) * unit * plane;
-                    size_t n = 0, nb = 0;
-                    for (size_t c = 0; c < size_t(unit) * plane; ++c) {
-                        n += isActive(p[c]);
-                        nb += p[c] == MGPS_BOUNDARY_CELL;
-                    }
-                    load[size_t(u)] = double(n) + kBoundaryWeight * double(nb);
-                }
-            });
-        for (auto &th : pool) th.join();
-    }
+    for (int u = 0; u < units; ++u) load[size_t(u)] = active[u] + kBoundaryWeight * boundary[u];
+    auto uniform = [&] {
+        for (int r = 0; r <= size; ++r) out_splits[r] = int(int64_t(nz) * r / size);
+    };
     double total = 0;
     for (double v : load) total += v;
-    if (total == 0) return MGPS_OK;
+    if (total == 0) return;
     const double kTailLoad = kTailShare * total;
     // the cuts that minimise the largest per-rank load (dynamic programme over unit boundaries: units <= nz / 16, ranks <= 8),
     // every rank at least minUnits; ties go to the more even plane counts
@@ -3471,17 +3465,144 @@ try {
                     from[size_t(r)][size_t(u)] = v;
                 }
             }
-    if (best[size_t(size)][size_t(units)] >= kInf) return MGPS_OK;
+    if (best[size_t(size)][size_t(units)] >= kInf) return;
     double evenWorst = 0.0;  // what the even cut costs
     for (int r = 0; r < size; ++r)
         evenWorst = std::max(evenWorst, prefix[size_t(out_splits[r + 1] / unit)] - prefix[size_t(out_splits[r] / unit)] + (r == 0 ? kTailLoad : 0.0));
-    if (best[size_t(size)][size_t(units)] >= 0.98 * evenWorst) return MGPS_OK;  // nothing to gain: keep the even cut
+    if (best[size_t(size)][size_t(units)] >= 0.98 * evenWorst) return;  // nothing to gain: keep the even cut
     for (int r = size, u = units; r > 0; --r) {
         out_splits[r] = u * unit;
         u = from[size_t(r)][size_t(u)];
     }
     out_splits[0] = 0;
     if (distributedLevelsFor(out_splits, size, nx, ny, mg_levels, false, o) != D) uniform();  // (never observed; the even cut always stands)
+}
+// counts[2 k] = active, counts[2 k + 1] = BOUNDARY cells of plane k of `planes` planes of device labels (launchPlaneCounts), on the host
+int countPlanes(const uint8_t *labels_dev, size_t plane, int planes, uint32_t *counts_host)
+{
+    uint32_t *partials = nullptr, *counts = nullptr;
+    hipError_t e = cacheMalloc(reinterpret_cast<void **>(&partials), std::max<size_t>(1, planeCountScratch(plane, planes)) * sizeof(uint32_t));
+    if (e == hipSuccess) e = cacheMalloc(reinterpret_cast<void **>(&counts), 2 * size_t(planes) * sizeof(uint32_t));
+    const bool alloc = e != hipSuccess;
+    if (e == hipSuccess) e = hipError_t(launchPlaneCounts(nullptr, labels_dev, plane, planes, partials, counts));
+    if (e == hipSuccess) e = hipMemcpy(counts_host, counts, 2 * size_t(planes) * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (partials) (void)cacheFree(partials);
+    if (counts) (void)cacheFree(counts);
+    if (e == hipSuccess) return MGPS_OK;
+    return failH(nullptr, alloc ? MGPS_ERR_ALLOC : MGPS_ERR_HIP, std::string("counting the label planes: ") + hipGetErrorString(e));
+}
+}  // namespace
+namespace mgps {
+bool hostSetupRequested(const mgps_options &o) { return hostSetup(o); }
+}  // namespace mgps
+
+extern "C" {
+
+int mgps_slab_partition(int nx, int ny, int nz, const uint8_t *labels, int mg_levels, int size, int use_gauss_seidel,
+                        const mgps_options *opt, int *out_splits)
+try {
+    if (!labels || !out_splits || size < 1 || nx < 1 || ny < 1 || nz < 1 || mg_levels < 1)
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_slab_partition: bad arguments");
+    mgps_options o;
+    MGPS_TRY(readOptions(opt, &o));
+    const PartitionPlan plan = partitionPlan(nx, ny, nz, mg_levels, size, use_gauss_seidel != 0, o, out_splits);
+    if (plan.unit == 0) return MGPS_OK;
+    // active and BOUNDARY cells per unit of planes, by a pool of threads
+    const int unit = plan.unit, units = nz / unit;
+    std::vector<double> active(size_t(units), 0.0), boundary(size_t(units), 0.0);
+    const size_t plane = size_t(nx) * ny;
+    {
+        std::vector<std::thread> pool;
+        const int nt = std::max(1, std::min(units, int(std::thread::hardware_concurrency() ? std::thread::hardware_concurrency() : 4)));
+        for (int t = 0; t < nt; ++t)
+            pool.emplace_back([&, t] {
+                for (int u = t; u < units; u += nt) {
+                    const uint8_t *p = labels + size_t(u) * unit * plane;
+                    size_t n = 0, nb = 0;
+                    for (size_t c = 0; c < size_t(unit) * plane; ++c) {
+                        n += isActive(p[c]);
+                        nb += p[c] == MGPS_BOUNDARY_CELL;
+                    }
+                    active[size_t(u)] = double(n);
+                    boundary[size_t(u)] = double(nb);
+                }
+            });
+        for (auto &th : pool) th.join();
+    }
+    partitionFromCounts(plan, nx, ny, nz, mg_levels, size, o, active.data(), boundary.data(), out_splits);
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_label_plane_counts(int nx, int ny, int planes, const uint8_t *labels_dev, int64_t *active, int64_t *boundary)
+try {
+    if (!labels_dev || !active || !boundary || nx < 1 || ny < 1 || planes < 1 || size_t(nx) * size_t(ny) > size_t(INT32_MAX))
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_label_plane_counts: bad arguments");
+    std::vector<uint32_t> counts(2 * size_t(planes), 0);
+    MGPS_TRY(countPlanes(labels_dev, size_t(nx) * ny, planes, counts.data()));
+    for (int k = 0; k < planes; ++k) {
+        active[k] = int64_t(counts[2 * size_t(k)]);
+        boundary[k] = int64_t(counts[2 * size_t(k) + 1]);
+    }
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_slab_partition_device(int nx, int ny, int nz_global, const uint8_t *labels_slab_dev, const int *splits_now, int mg_levels, int use_gauss_seidel,
+                               const mgps_options *opt, const mgps_comm *comm, int *out_splits)
+try {
+    // ---- what every rank shares: a refusal here is every rank's, before the all-reduce
+    if (!labels_slab_dev || !splits_now || !out_splits || !comm || nx < 1 || ny < 1 || nz_global < 1 || mg_levels < 1)
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_slab_partition_device: the rank's label planes, its cuts, a comm and a place for the new cuts are required");
+    if (comm->struct_size < int(offsetof(mgps_comm, allreduce) + sizeof(comm->allreduce)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->allreduce ||
+        comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_slab_partition_device: incomplete mgps_comm (allreduce is what it takes)");
+    const int P = comm->size, rank = comm->rank;
+    bool cutsOk = splits_now[0] == 0 && splits_now[P] == nz_global;
+    for (int r = 0; r < P && cutsOk; ++r) cutsOk = splits_now[r + 1] > splits_now[r];
+    if (!cutsOk) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_slab_partition_device: the present cuts must run from 0 to nz, increasing");
+    const size_t plane = size_t(nx) * ny;
+    if (plane > size_t(INT32_MAX)) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_slab_partition_device: more than 2^31 - 1 cells per plane");
+    mgps_options o;
+    MGPS_TRY(readOptions(opt, &o));
+    const PartitionPlan plan = partitionPlan(nx, ny, nz_global, mg_levels, P, use_gauss_seidel != 0, o, out_splits);
+    if (plan.unit == 0) return MGPS_OK;  // (the even cut, by the shared arguments alone: no rank counts anything)
+    // ---- this rank's planes, counted on its device; a failure travels with the counts
+    const int z0 = splits_now[rank], nzl = splits_now[rank + 1] - z0;
+    std::vector<uint32_t> mine(2 * size_t(nzl), 0);
+    std::string why;
+    const int status = [&]() -> int {
+        int device = 0;
+        int rc = pickDevice(o, &device);
+        if (rc == MGPS_OK) rc = countPlanes(labels_slab_dev, plane, nzl, mine.data());
+        if (rc != MGPS_OK) why = lastGlobalError();
+        return rc;
+    }();
+    // ---- one all-reduce (sum): 2 nz integer-valued doubles below 2^53, and one slot for the ranks' statuses -- a digit per status
+    // wide enough to count every rank, so that the sum names the smallest status any rank brought (with more than 31 ranks the
+    // digits of the last statuses share one, reported as MGPS_ERR_INTERNAL)
+    int bits = 1;
+    while ((1 << bits) <= P) ++bits;
+    const int digits = std::min(int(MGPS_ERR_INTERNAL), 52 / bits);
+    std::vector<double> v(2 * size_t(nz_global) + 1, 0.0);
+    if (status == MGPS_OK)
+        for (size_t q = 0; q < mine.size(); ++q) v[2 * size_t(z0) + q] = double(mine[q]);
+    else
+        v.back() = std::ldexp(1.0, bits * (std::min(status, digits) - 1));
+    if (comm->allreduce(comm->user, v.data(), int(v.size()), 0) != 0) return failH(nullptr, MGPS_ERR_COMM, "mgps_slab_partition_device: all-reduce failed");
+    if (v.back() != 0.0) {
+        int worst = 1;
+        for (uint64_t s = uint64_t(v.back()); (s & ((uint64_t(1) << bits) - 1)) == 0; s >>= bits) ++worst;
+        if (worst == digits && digits < int(MGPS_ERR_INTERNAL)) worst = MGPS_ERR_INTERNAL;
+        return failH(nullptr, worst, status == worst ? why : "mgps_slab_partition_device: counting the planes failed on another rank" + (status != MGPS_OK ? " (here: " + why + ")" : std::string()));
+    }
+    const int unit = plan.unit, units = nz_global / unit;
+    std::vector<double> active(size_t(units), 0.0), boundary(size_t(units), 0.0);
+    for (int z = 0; z < nz_global; ++z) {
+        active[size_t(z / unit)] += v[2 * size_t(z)];
+        boundary[size_t(z / unit)] += v[2 * size_t(z) + 1];
+    }
+    partitionFromCounts(plan, nx, ny, nz_global, mg_levels, P, o, active.data(), boundary.data(), out_splits);
     return MGPS_OK;
 }
 MGPS_API_CATCH(nullptr)
@@ -3752,8 +3873,11 @@ int setupEnclosedSlab(mgps_solver *h, StageClock &sclock)
     return agreeSlab(h, status);
 }
 
-int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t *labels_global_host, const float *wx_slab, const float *wy_slab,
-                       const float *wz_slab, bool weightsOnDevice, int mgLevels, bool useGS, const mgps_options &o, const mgps_comm *comm, const int *splits, int device)
+// The fine labels come from the whole grid's on the host (labels_global_host: the rank's window of them goes up) or, labels_slab_dev set,
+// from the rank's owned planes on its device: those are copied into the buffer and the real0 planes on either side come from
+// the neighbours in one exchange (every rank owns at least 16 << (Dmax - 1) planes, distributedLevelsFor, and real0 is no more).
+int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t *labels_global_host, const uint8_t *labels_slab_dev, const float *wx_slab,
+                       const float *wy_slab, const float *wz_slab, bool weightsOnDevice, int mgLevels, bool useGS, const mgps_options &o, const mgps_comm *comm, const int *splits, int device)
 {
     MGPS_TRY(checkSetupArgs("mgps_create_slab", 2, nx, ny, nzg, mgLevels, o, "band_width 1 .. 8, band_iterations >= 0"));
     const int P = comm->size, rank = comm->rank;
@@ -3813,6 +3937,9 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
     for (int l = Dmax - 2; l >= 0; --l) B[size_t(l)].real = 2 * B[size_t(l) + 1].real + 2;
     for (int l = 0; l <= Dmax; ++l)
         if (B[size_t(l)].real > B[size_t(l)].elo) return bail(failH(h, MGPS_ERR_INTERNAL, "slab set-up: label window past its buffer"));
+    // label windows: a neighbour serves the whole halo from its owned planes (the cuts are everybody's: every rank decides alike)
+    for (int r = 0; r < P && labels_slab_dev && P > 1; ++r)
+        if (B[0].real > splits[r + 1] - splits[r]) return bail(failH(h, MGPS_ERR_INTERNAL, "slab set-up: the label halo is deeper than a neighbour's slab"));
     // (a failure from here on is carried by the first all-reduce: no rank leaves alone)
     int status = [&]() -> int {
         for (Buf &b : B) {
@@ -3824,9 +3951,26 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
         const Buf &b = B[0];
         const int a = std::max(0, z0 - b.real), e = std::min(nzg, z1 + b.real);
         const size_t plane = size_t(nx) * ny;
+        if (labels_slab_dev) {  // the owned planes; the halo follows below
+            MGPS_HIP(h, hipMemcpyAsync(b.owned(), labels_slab_dev, size_t(z1 - z0) * plane, hipMemcpyDeviceToDevice, nullptr));
+            MGPS_HIP(h, hipStreamSynchronize(nullptr));
+            return MGPS_OK;
+        }
         return uploadPageable(h, b.owned() + ptrdiff_t(a - z0) * ptrdiff_t(plane), labels_global_host + size_t(a) * plane, size_t(e - a) * plane, device);
     }();
-    sclock.lap("slab: label window upload");
+    if (labels_slab_dev) {
+        // the real0 planes on either side: the first owned planes go down, the last go up, straight from buffer to buffer (planes are
+        // contiguous); beyond the global grid the EXTERIOR fill stays.  A rank that failed above must not leave its neighbours waiting
+        if (int rc = agreeSlab(h, status); rc != MGPS_OK) return bail(rc);
+        const Buf &b = B[0];
+        const size_t bytes = size_t(b.real) * size_t(nx) * ny, owned = size_t(z1 - z0) * size_t(nx) * ny;
+        if (P > 1 && h->comm.exchange(h->comm.user, lo ? b.owned() : nullptr, lo ? bytes : 0, lo ? b.owned() - bytes : nullptr, lo ? bytes : 0,
+                                      hi ? b.owned() + owned - bytes : nullptr, hi ? bytes : 0, hi ? b.owned() + owned : nullptr, hi ? bytes : 0, nullptr) != 0)
+            return bail(failH(h, MGPS_ERR_COMM, "label halo: exchange failed"));
+        if (hipStreamSynchronize(nullptr) != hipSuccess) status = failH(h, MGPS_ERR_HIP, "label halo: synchronize failed");
+        sclock.lap("slab: label window exchange");
+    } else
+        sclock.lap("slab: label window upload");
     // flags: per level l [2 l] shell broken, [2 l + 1] holds an active cell; then interior rule, weight rule, boxes broken per level
     const size_t nflags = size_t(2 * (mgLevels + 1) + 2 + mgLevels);
     int *flags = nullptr;
@@ -4236,13 +4380,15 @@ int createSlabOnDevice(mgps_solver **out, int nx, int ny, int nzg, const uint8_t
 // their 12 B per cell crosses PCIe -- at 1024^3 / 8 ranks the 1.6 GB of a slab's weights coming from pageable host memory were
 // 300 of the 470 ms a rank's set-up took -- and the operator rows of the slab's BOUNDARY cells are evaluated by
 // launchBoundaryRows like mgps_create_device_weights does for a whole grid
+// labels_slab_dev (mgps_create_slab_device_labels): the rank's owned planes of the labels on its device instead of the whole grid's on
+// the host -- the same argument checks, the device-side set-up only
 int createSlabImpl(mgps_solver **out, int nx, int ny, int nz_global, const uint8_t *labels_global_host, const float *wx_slab,
                    const float *wy_slab, const float *wz_slab, int mg_levels, int use_gauss_seidel, const mgps_options *opt,
-                   const mgps_comm *comm, const int *splits, bool weightsOnDevice)
+                   const mgps_comm *comm, const int *splits, bool weightsOnDevice, const uint8_t *labels_slab_dev = nullptr)
 {
     if (!out) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: out is NULL");
     *out = nullptr;
-    if (!labels_global_host || !wx_slab || !wy_slab || !wz_slab || !comm || !splits)
+    if ((!labels_global_host && !labels_slab_dev) || !wx_slab || !wy_slab || !wz_slab || !comm || !splits)
         return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: labels, the slab weights, a comm and the cuts are required");
     // options.enclosed_liquid: rank 0 merges the ranks' components through gatherv / scatterv (a struct_size that ends before them
     // lacks them), and the component ids are int32 global cell indices
@@ -4268,12 +4414,17 @@ int createSlabImpl(mgps_solver **out, int nx, int ny, int nz_global, const uint8
     mgps_options o;
     MGPS_TRY(readOptions(opt, &o));
     if (o.precision != 0) return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab: options.precision = 1 is for single-device solvers");
+    // (options and environment are everybody's: every rank refuses, before any collective)
+    if (labels_slab_dev && hostSetup(o))
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT,
+                     "mgps_create_slab_device_labels: host_setup (options.host_setup or MGPS_HOST_SETUP=1) builds from the whole grid's labels on the host; "
+                     "pass them to mgps_create_slab_device_weights");
     int device = 0;
     MGPS_TRY(pickDevice(o, &device));
     // the default since round 5: everything on the device, from the rank's window of the labels (createSlabOnDevice).  What follows is
     // the host builder (options.host_setup = 1): the checker of the device arrays, with the band stage pass by pass on cut levels
     if (!hostSetup(o))
-        return createSlabOnDevice(out, nx, ny, nz_global, labels_global_host, wx_slab, wy_slab, wz_slab, weightsOnDevice, mg_levels, use_gauss_seidel != 0, o, comm, splits, device);
+        return createSlabOnDevice(out, nx, ny, nz_global, labels_global_host, labels_slab_dev, wx_slab, wy_slab, wz_slab, weightsOnDevice, mg_levels, use_gauss_seidel != 0, o, comm, splits, device);
     StageClock sclock(setupTimingOn());
     mgps_hierarchy *hier = nullptr;
     {  // the rank's window of the hierarchy: labels of every level, band lists around its slab only
@@ -4422,6 +4573,17 @@ int mgps_create_slab_device_weights(mgps_solver **out, int nx, int ny, int nz_gl
                                     const mgps_comm *comm, const int *splits)
 try {
     return createSlabImpl(out, nx, ny, nz_global, labels_global_host, wx_slab_dev, wy_slab_dev, wz_slab_dev, mg_levels, use_gauss_seidel, opt, comm, splits, true);
+}
+MGPS_API_CATCH(nullptr)
+int mgps_create_slab_device_labels(mgps_solver **out, int nx, int ny, int nz_global, const uint8_t *labels_slab_dev, const float *wx_slab_dev,
+                                   const float *wy_slab_dev, const float *wz_slab_dev, int mg_levels, int use_gauss_seidel, const mgps_options *opt,
+                                   const mgps_comm *comm, const int *splits)
+try {
+    if (!labels_slab_dev) {
+        if (out) *out = nullptr;
+        return failH(nullptr, MGPS_ERR_INVALID_ARGUMENT, "mgps_create_slab_device_labels: the rank's label planes are required");
+    }
+    return createSlabImpl(out, nx, ny, nz_global, nullptr, wx_slab_dev, wy_slab_dev, wz_slab_dev, mg_levels, use_gauss_seidel, opt, comm, splits, true, labels_slab_dev);
 }
 MGPS_API_CATCH(nullptr)
 

@@ -288,6 +288,23 @@ def slab_partition(labels, mg_levels, size, use_gauss_seidel, options=None):
     return [int(v) for v in cuts]
 
 
+def slab_partition_device(labels_window, splits_now, mg_levels, use_gauss_seidel, comm, options=None):
+    """mgps_slab_partition_device: slab_partition for labels that live as windows on the ranks' devices.  A collective: rank r passes
+    its planes [splits_now[r], splits_now[r + 1]) as a uint8 CUDA tensor (nzl, ny, nx); every rank gets the cuts slab_partition
+    returns on the assembled labels, for comm.size ranks."""
+    assert isinstance(labels_window, torch.Tensor) and labels_window.is_cuda and labels_window.dtype == torch.uint8 and labels_window.is_contiguous()
+    assert len(splits_now) == comm.size + 1
+    nzl, ny, nx = labels_window.shape
+    assert nzl == splits_now[comm.rank + 1] - splits_now[comm.rank], "labels_window must hold the rank's planes of splits_now"
+    now = (C.c_int * (comm.size + 1))(*[int(v) for v in splits_now])
+    cuts = (C.c_int * (comm.size + 1))()
+    opt = options if options is not None else default_options()
+    torch.cuda.synchronize()  # (the library counts on its own stream)
+    check(lib().mgps_slab_partition_device(nx, ny, int(splits_now[-1]), C.c_void_p(labels_window.data_ptr()), now, int(mg_levels),
+                                           int(bool(use_gauss_seidel)), C.byref(opt), C.byref(comm.struct), cuts))
+    return [int(v) for v in cuts]
+
+
 class SlabSolver(GeometricMultigridPoissonSolver):
     """GeometricMultigridPoissonSolver on one Z-slab per rank (mgps_create_slab).
 
@@ -341,12 +358,49 @@ class SlabSolver(GeometricMultigridPoissonSolver):
                     int(bool(use_gauss_seidel)), C.byref(opt), C.byref(comm.struct), cuts,
                 )
             )
-        self.shape = (nzl, ny, nx)
-        self.global_shape = (nz, ny, nx)
+        self._finish(nzl, (nz, ny, nx), use_gauss_seidel, opt)
+
+    def _finish(self, nzl, global_shape, use_gauss_seidel, opt):
+        self.shape = (nzl,) + tuple(global_shape[1:])
+        self.global_shape = tuple(global_shape)
         self.use_gauss_seidel = bool(use_gauss_seidel)
         dev_index = opt.device if opt.device >= 0 else torch.cuda.current_device()
         self.device = torch.device("cuda", dev_index)
         self.use_torch_stream()
+
+    @classmethod
+    def from_device_labels(cls, labels_window, slab_weights, global_nz, mg_levels, use_gauss_seidel, comm, device=None, options=None, splits=None):
+        """mgps_create_slab_device_labels: the same solver from the rank's own planes of the labels, on the device -- a uint8 CUDA
+        tensor (nzl, ny, nx) holding planes [splits[rank], splits[rank + 1]) -- and float32 CUDA weights.  No rank holds the whole
+        grid's labels; the label planes the set-up reads across a cut come from the neighbours in one exchange.  Device-side
+        set-up only (options.host_setup = 1 is refused)."""
+        assert isinstance(labels_window, torch.Tensor) and labels_window.is_cuda and labels_window.dtype == torch.uint8 and labels_window.is_contiguous()
+        w = list(slab_weights)
+        assert all(isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32 and a.is_contiguous() for a in w)
+        nz = int(global_nz)
+        nzl, ny, nx = labels_window.shape
+        if splits is None:
+            assert nz % comm.size == 0, "nz must divide evenly over the ranks"
+            splits = [nz // comm.size * r for r in range(comm.size + 1)]
+        assert len(splits) == comm.size + 1 and nzl == splits[comm.rank + 1] - splits[comm.rank]
+        assert tuple(w[0].shape) == (nzl, ny, nx + 1) and tuple(w[1].shape) == (nzl, ny + 1, nx) and tuple(w[2].shape) == (nzl + 1, ny, nx)
+        self = cls.__new__(cls)
+        self.splits = [int(v) for v in splits]
+        opt = options if options is not None else default_options()
+        if device is not None:
+            opt.device = torch.device(device).index if not isinstance(device, int) else device
+        self.comm = comm
+        self.h = C.c_void_p()
+        cuts = (C.c_int * (comm.size + 1))(*self.splits)
+        torch.cuda.synchronize()  # (the library reads the tensors on its own stream)
+        check(
+            lib().mgps_create_slab_device_labels(
+                C.byref(self.h), nx, ny, nz, C.c_void_p(labels_window.data_ptr()), C.c_void_p(w[0].data_ptr()), C.c_void_p(w[1].data_ptr()),
+                C.c_void_p(w[2].data_ptr()), int(mg_levels), int(bool(use_gauss_seidel)), C.byref(opt), C.byref(comm.struct), cuts,
+            )
+        )
+        self._finish(nzl, (nz, ny, nx), use_gauss_seidel, opt)
+        return self
 
     @property
     def distributed_levels(self):

@@ -505,6 +505,27 @@ int mgps_create_slab_ranges(mgps_solver **out, int nx, int ny, int nz_global, co
 int mgps_create_slab_device_weights(mgps_solver **out, int nx, int ny, int nz_global, const uint8_t *labels_global_host,
                                     const float *wx_slab_dev, const float *wy_slab_dev, const float *wz_slab_dev, int mg_levels,
                                     int use_gauss_seidel, const mgps_options *opt, const mgps_comm *comm, const int *splits);
+/* The same from the rank's own planes of the labels, on its DEVICE (what mgps_fields_slab_labels leaves there): labels_slab_dev holds
+ * the owned planes [splits[rank], splits[rank + 1]), nx * ny bytes each, and is read during the call only.  Nothing of the size of the
+ * grid is held, sent or uploaded: the few label planes of the neighbours that the set-up reads next to a cut (8, 18, 38 for 1, 2, 3
+ * distributed levels at the default band options; never more than a neighbour owns) arrive in one comm->exchange per neighbour.
+ * Device-side set-up only: options.host_setup = 1 (or MGPS_HOST_SETUP=1), whose builder reads the whole grid, is refused with
+ * MGPS_ERR_INVALID_ARGUMENT on every rank.  Otherwise the checks, the collectives' verdicts and the solver are those of
+ * mgps_create_slab_device_weights on the assembled labels, bit for bit. */
+int mgps_create_slab_device_labels(mgps_solver **out, int nx, int ny, int nz_global, const uint8_t *labels_slab_dev,
+                                   const float *wx_slab_dev, const float *wy_slab_dev, const float *wz_slab_dev, int mg_levels,
+                                   int use_gauss_seidel, const mgps_options *opt, const mgps_comm *comm, const int *splits);
+/* mgps_slab_partition for callers whose labels live as windows on the ranks' devices (the cuts of the next sub-step from the labels
+ * of this one).  A collective: rank r passes its planes [splits_now[r], splits_now[r + 1]) -- any increasing cuts from 0 to
+ * nz_global -- and every rank gets the cuts for comm->size ranks that mgps_slab_partition returns on the assembled labels.  Active
+ * and BOUNDARY cells are counted per plane on the device; one comm->allreduce carries the 2 * nz_global counts and the ranks'
+ * statuses, so a failure on one rank is every rank's return value.  Where the shared arguments alone settle on the even cut
+ * (Gauss-Seidel, one rank, a grid too thin) nothing is counted and nothing sent. */
+int mgps_slab_partition_device(int nx, int ny, int nz_global, const uint8_t *labels_slab_dev, const int *splits_now, int mg_levels,
+                               int use_gauss_seidel, const mgps_options *opt, const mgps_comm *comm, int *out_splits);
+/* the counts behind it (tests / tools): active[k] = INTERIOR + BOUNDARY cells, boundary[k] = BOUNDARY cells of plane k of `planes`
+ * x-y planes of device labels, nx * ny bytes each (host outputs); runs on the current device and synchronises */
+int mgps_label_plane_counts(int nx, int ny, int planes, const uint8_t *labels_dev, int64_t *active, int64_t *boundary);
 /* owned plane range [z0, z1) of `level` on this rank (levels past the distributed ones: the range
  * of the collapse level) and the number of distributed levels */
 int mgps_slab_range(const mgps_solver *h, int level, int *z0, int *z1);

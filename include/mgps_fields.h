@@ -213,15 +213,17 @@ int mgps_fields_slab_divergence(const mgps_fields_slab *d, double out_host[3], c
  * above; valid_faces are device uint8 outputs (each may be NULL).  With comm->size = 1 it is the device-resident projection on
  * one GPU.  Steps, in the order of mgps_project_free_surface: liquid_phi plane exchange, material labels, material plane
  * exchange, the faces pass and the labels pass; liquid cell count (all-reduce; no liquid anywhere: valid faces and zero pressure
- * are published, outcome MGPS_PCG_RHS_ZERO); the whole grid's labels to every rank's host (gatherv to rank 0, scatterv with every
- * rank's range set to the whole buffer: ex * ey * ez bytes per rank, 1 GiB at 1024^3) for mgps_create_slab_device_weights on the
- * rank's weights (borrowed); rhs, warm start, surface term (after an exchange of the sp plane), enclosed-liquid projection,
+ * are published, outcome MGPS_PCG_RHS_ZERO); mgps_create_slab_device_labels on the rank's own label planes and weights (borrowed:
+ * the labels never leave the device, the constructor fetches its label halo from the neighbours; with options.host_setup or
+ * MGPS_HOST_SETUP=1 the whole grid's labels go to every rank's host first -- gatherv to rank 0, scatterv with every rank's range
+ * set to the whole buffer: ex * ey * ez bytes per rank, 1 GiB at 1024^3 -- for mgps_create_slab_device_weights); rhs, warm start, surface term (after an exchange of the sp plane), enclosed-liquid projection,
  * mgps_solve_pcg, residual norms; pressure write-back, pressure plane exchange, gradient on the owned faces (both copies of a
  * cut's z-face plane get the same bits), divergence report and surface_pressure_max from one all-reduce.  Every rank-local failure
  * is folded into the next all-reduce: all ranks return the same status.  The exception is the transport itself: a rank whose
  * exchange, all-reduce, gatherv or scatterv call fails returns MGPS_ERR_COMM at once and alone (nothing can carry its status; the
  * other ranks are left in a collective of a broken transport, as on the slab solvers).  A transport without gatherv / scatterv is refused when
- * size > 1, before any device work.  MGPS_ERR_INTERRUPTED: as mgps_project_free_surface. */
+ * size > 1, before any device work (the collapse of uneven cuts, the enclosed-liquid merge and the host set-up's labels use them).
+ * The cuts are the caller's (mgps_projection_slab_layout, or mgps_slab_partition_device on the labels of an earlier sub-step).  MGPS_ERR_INTERRUPTED: as mgps_project_free_surface. */
 typedef struct mgps_projection_slab {
     int struct_size;                /* sizeof(mgps_projection_slab) */
     int gx, gy, gz;                 /* the WHOLE simulation grid */
@@ -247,7 +249,7 @@ typedef struct mgps_projection_slab {
     const float *surface_pressure;  /* cell grid of the window, or NULL */
     double surface_pressure_max;
     /* this rank's host wall clock per stage, ms: [0] plane exchanges + material, faces and labels passes + liquid count,
-       [1] labels to every rank's host, [2] solver set-up, [3] rhs, warm start, surface term, enclosed projection, [4] solve +
+       [1] the ranks' agreement in front of the constructor (host set-up: with the whole grid's labels to every rank's host), [2] solver set-up, [3] rhs, warm start, surface term, enclosed projection, [4] solve +
        residual norms, [5] write-back, gradient, divergence report, [6] of all that: inside the plane exchanges, [7] reserved */
     double stage_ms[8];
 } mgps_projection_slab;

@@ -12,7 +12,11 @@ is written once to --scratch (a temporary directory by default) and every measur
      fills they issue; rhs; gradient x3) against the slab passes of this build on the one-rank window (material, faces, labels; rhs;
      gradient), HIP events, mean of 10 launches.
  (c) 2 and 4 ranks sharing the GPU over TorchDistComm/gloo, surface tension on (four plane exchanges): every rank's stages.  Host
-     staging on one device: this says nothing about RCCL between GPUs."""
+     staging on one device: this says nothing about RCCL between GPUs.
+ With --parent-lib, (a)'s slab call and (c) also run on the parent's library, in turn with this build's ("slab_parent",
+ "c_gloo_shared_gpu_parent"): what a change of the slab call itself gains, stage by stage, against the parent's own spread.
+ (d) --part count: mgps_label_plane_counts (the counting kernel of mgps_slab_partition_device) over the expanded grid's labels, ten
+     calls; the kernel's own time comes from running this part under `rocprofv3 --kernel-trace --stats -- python tools/... --part count`."""
 import argparse
 import json
 import os
@@ -196,6 +200,31 @@ def part_ranks(a):
     dist.destroy_process_group()
 
 
+def part_count(a):
+    """the plane counts of the expanded grid's labels (random labels: the kernel's time does not depend on them)"""
+    import ctypes as C
+    import time
+
+    import torch
+
+    import geometricmultigridpressuresolver_amd as G
+    from geometricmultigridpressuresolver_amd._lib import check
+
+    n = a.size
+    (ez, ey, ex), _, _ = G.expanded_layout((n, n, n), 0, power_of_two=False)
+    lab = torch.randint(0, 4, (ez, ey, ex), dtype=torch.uint8, device="cuda")
+    act, bnd = (C.c_int64 * ez)(), (C.c_int64 * ez)()
+    times = []
+    for _ in range(11):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        check(G.lib().mgps_label_plane_counts(ex, ey, ez, C.c_void_p(lab.data_ptr()), act, bnd))
+        times.append((time.perf_counter() - t0) * 1e3)
+    assert sum(act) == int(((lab == 0) | (lab == 3)).sum().item()) and sum(bnd) == int((lab == 3).sum().item())
+    print("RESULT " + json.dumps({"expanded": [ez, ey, ex], "bytes": ez * ey * ex, "call_ms_min": round(min(times[1:]), 4),
+                                  "call_ms_median": round(float(np.median(times[1:])), 4)}), flush=True)
+
+
 def child(args, lib=None, nproc=0, timeout=900):
     env = dict(os.environ)
     if lib:
@@ -216,11 +245,12 @@ def main():
     ap.add_argument("--parent-lib", default="", help="the library of the commit to compare with (default: this build, whose whole-grid entry points are the parent's)")
     ap.add_argument("--scratch", default="", help="where the scene is written (default: a fresh temporary directory, removed at the end)")
     ap.add_argument("--ranks", default="2,4")
+    ap.add_argument("--skip-whole", action="store_true", help="leave (a)'s host-array call and (b) out (a change that does not touch them)")
     ap.add_argument("--out", default="")
     ap.add_argument("--part", default="")
     a = ap.parse_args()
     if a.part:
-        return {"whole": part_whole, "slab": part_slab, "ranks": part_ranks}[a.part](a)
+        return {"whole": part_whole, "slab": part_slab, "ranks": part_ranks, "count": part_count}[a.part](a)
     import torch
 
     own_scratch = None
@@ -230,24 +260,36 @@ def main():
     write_scene(a.size, a.scratch)
     common = ["--size", str(a.size), "--scratch", a.scratch]
     out = {"size": a.size, "device": torch.cuda.get_device_name(0), "power_of_two": False, "rounds": a.rounds,
-           "parent_library": "given" if a.parent_lib else "this build", "whole": [], "slab": []}
-    for r in range(a.rounds):  # the two sides in turn
-        out["whole"].append(child(common + ["--part", "whole"], lib=a.parent_lib))
-        print("whole", json.dumps(out["whole"][-1]), flush=True)
+           "parent_library": "given" if a.parent_lib else "this build", "whole": [], "slab": [], "slab_parent": []}
+    for r in range(a.rounds):  # the sides in turn
+        if not a.skip_whole:
+            out["whole"].append(child(common + ["--part", "whole"], lib=a.parent_lib))
+            print("whole", json.dumps(out["whole"][-1]), flush=True)
+        if a.parent_lib:
+            out["slab_parent"].append(child(common + ["--part", "slab"], lib=a.parent_lib))
+            print("slab_parent", json.dumps(out["slab_parent"][-1]), flush=True)
         out["slab"].append(child(common + ["--part", "slab"]))
         print("slab", json.dumps(out["slab"][-1]), flush=True)
     med = lambda side, f: round(float(np.median([f(r) for r in out[side]])), 3)  # noqa: E731
-    out["median"] = {
-        "a_total_ms": {s: med(s, lambda r: r["timed"]["total_ms"]) for s in ("whole", "slab")},
-        "a_outside_solve_ms": {s: med(s, lambda r: r["timed"]["outside_solve_ms"]) for s in ("whole", "slab")},
-        "a_solve_ms": {s: med(s, lambda r: r["timed"]["solve_ms"]) for s in ("whole", "slab")},
-        "a_slab_stage_ms": {k: med("slab", lambda r, k=k: r["timed"]["stage_ms"][k]) for k in out["slab"][0]["timed"]["stage_ms"]},
-        "b_passes_ms": {k: {s: med(s, lambda r, k=k: r["passes_ms"][k]) for s in ("whole", "slab")} for k in ("front_end", "rhs", "gradient_x3")},
+    sides = [s for s in ("whole", "slab_parent", "slab") if out[s]] if out["slab"] else []
+    spread = lambda side, f: [round(float(min(f(r) for r in out[side])), 3), round(float(max(f(r) for r in out[side])), 3)]  # noqa: E731
+    out["median"] = {} if not sides else {
+        "a_total_ms": {s: med(s, lambda r: r["timed"]["total_ms"]) for s in sides},
+        "a_outside_solve_ms": {s: med(s, lambda r: r["timed"]["outside_solve_ms"]) for s in sides},
+        "a_outside_solve_ms_min_max": {s: spread(s, lambda r: r["timed"]["outside_solve_ms"]) for s in sides},
+        "a_solve_ms": {s: med(s, lambda r: r["timed"]["solve_ms"]) for s in sides},
+        "a_slab_stage_ms": {s: {k: med(s, lambda r, k=k: r["timed"]["stage_ms"][k]) for k in out[s][0]["timed"]["stage_ms"]} for s in sides if s != "whole"},
+        "a_slab_stage_1_plus_2_ms_min_max": {s: spread(s, lambda r: sum(list(r["timed"]["stage_ms"].values())[1:3])) for s in sides if s != "whole"},
+        "b_passes_ms": {k: {s: med(s, lambda r, k=k: r["passes_ms"][k]) for s in sides} for k in ("front_end", "rhs", "gradient_x3")},
     }
-    out["c_gloo_shared_gpu"] = {}
+    out["c_gloo_shared_gpu"], out["c_gloo_shared_gpu_parent"] = {}, {}
     for nproc in [int(v) for v in a.ranks.split(",") if v]:
+        if a.parent_lib:
+            out["c_gloo_shared_gpu_parent"][str(nproc)] = child(common + ["--part", "ranks"], lib=a.parent_lib, nproc=nproc, timeout=1500)
+            print(nproc, "ranks, parent", json.dumps(out["c_gloo_shared_gpu_parent"][str(nproc)]), flush=True)
         out["c_gloo_shared_gpu"][str(nproc)] = child(common + ["--part", "ranks"], nproc=nproc, timeout=1500)
         print(nproc, "ranks", json.dumps(out["c_gloo_shared_gpu"][str(nproc)]), flush=True)
+    out["d_plane_counts"] = child(common + ["--part", "count"])
     text = json.dumps(out, indent=1)
     print(text)
     if a.out:
