@@ -364,7 +364,13 @@ int launchRestrict(void *stream, const GridP &coarse, float *coarseOut, const fl
 bool residualRestrictFits(const GridP &fine, const GridP &coarse);
 std::vector<int32_t> planeBlockEdges(const GridP &g, const std::vector<uint8_t> &flags);
 // rEdge (cut levels): the level's residual grid, whose ghost planes hold the neighbours' r on the planes next to the slab
-int launchResidualZ(void *stream, const GridP &fine, float *rz, const float *x, const float *b, const int32_t *edges, int nedges, const float *rEdge = nullptr);
+// xfold (residualRestrictXFolds: levels without general BOUNDARY cells): rz also folded along x where it is stored, rzxFloats floats
+// (a grid of nx / 2 x ny x nz / 2 and the seam entries of the tile boundaries behind it); launchRestrictY restricts it along y
+bool residualRestrictXFolds(const GridP &fine);
+size_t rzxFloats(const GridP &fine);
+int launchResidualZ(void *stream, const GridP &fine, float *rz, const float *x, const float *b, const int32_t *edges, int nedges, const float *rEdge = nullptr,
+                    bool xfold = false);
+int launchRestrictY(void *stream, const GridP &coarse, float *coarseOut, const float *rzx, const GridP &fine);
 int launchResidualEdgePlanes(void *stream, const GridP &g, float *r, const float *x, const float *b);
 int launchRestrictXY(void *stream, const GridP &coarse, float *coarseOut, const float *rz);
 // ---- mixed precision (options.precision = 1): binary16 grids of the fine level, passed as void* -----------------------

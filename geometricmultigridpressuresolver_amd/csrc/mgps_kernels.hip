@@ -335,6 +335,14 @@ constexpr int kPlanePitch = 256 + 8;  // 4 floats of halo on each side keep the 
 // one lerp of prolongAddKernel: round 6 moved the last bits of the prolongation there) -- so that the kernels that interpolate the
 // same values in different places (prolongJacobiPlaneKernel, the closure launch's coarse input) round them alike
 __device__ __forceinline__ float lerpRef(float a, float b, float f) { return __builtin_fmaf(1.f - f, a, f * b); }
+// One axis of the full weighting (Ops.h:734-835), w0 r0 + w1 r1 + w2 r2 + w3 r3 with w = (1, 3, 3, 1) / 8, the contraction pinned like
+// lerpRef's: the x fold is formed in three places (restrictXYKernel's row sum, the march's stores of the x-folded layout, the
+// seam columns of restrictYKernel) and the y fold in two, and every one of them rounds alike -- the two layouts of the z-folded
+// residual give the same bits.
+__device__ __forceinline__ float foldX4(float r0, float r1, float r2, float r3)
+{
+    return __builtin_fmaf(0.125f, r3, __builtin_fmaf(0.375f, r2, __builtin_fmaf(0.375f, r1, 0.125f * r0)));
+}
 
 // A wave-uniform pointer pinned to a scalar register pair, its derivation hidden from the optimiser (an empty asm): in the
 // plane-marching kernels below the loop optimiser otherwise folds "plane base + lane offset" into one 64-bit vector induction
@@ -376,6 +384,23 @@ __device__ __forceinline__ void gStore4(float *base, unsigned cell, float4 v) { 
 __device__ __forceinline__ void gStore4nt(float *base, unsigned cell, float4 v)
 {
     __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, (MGPS_GLOBAL_AS v4f *)((MGPS_GLOBAL_AS char *)base + cell * 4u));
+}
+typedef float v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void gStore2(float *base, unsigned cell, float2 v) { *(MGPS_GLOBAL_AS v2f *)((MGPS_GLOBAL_AS char *)base + cell * 4u) = v2f{v.x, v.y}; }
+__device__ __forceinline__ void gStore2nt(float *base, unsigned cell, float2 v)
+{
+    __builtin_nontemporal_store(v2f{v.x, v.y}, (MGPS_GLOBAL_AS v2f *)((MGPS_GLOBAL_AS char *)base + cell * 4u));
+}
+
+// The value the lane to the left / to the right of this one holds, 0 at the wave's first / last lane: one DPP move over the whole
+// wave (wave_shr:1 / wave_shl:1 of the GCN3-CDNA encodings; an unwritten lane keeps `old` = 0) -- no LDS crossbar, no address register.
+__device__ __forceinline__ float fromLeftLane(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, false)); }
+__device__ __forceinline__ float fromRightLane(float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, false)); }
+typedef float v4fu __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ float4 gLoad4u(const float *base, unsigned cell)  // (four floats at any cell, not a quad's)
+{
+    const v4fu v = *(const MGPS_GLOBAL_AS v4fu *)((const MGPS_GLOBAL_AS char *)base + cell * 4u);
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 
 // v where `keep`, else 0 -- component by component with the literal (a float4 of zeros as the other operand of the selects was a
@@ -725,9 +750,20 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
 // ghost plane, and r there comes complete from the neighbour in the ghost planes of `rEdge` (the level's residual grid: the ranks
 // exchange r on their boundary planes, as the separate restriction does): w0 r(-1) opens coarse plane 0, w3 r(nz) closes the last
 // one, in the order of the planes like everywhere else.
+// XF (round 8): `rz` also folded along x where it is stored -- rzx(I, j, K) on a grid of nx / 2 x ny x nz / 2, half the bytes out and
+// half the bytes restrictYKernel reads back, no x halo there.  The thread of fine 4 t .. 4 t + 3 holds three of the four terms of
+// both of its coarse columns: I = 2 t from (left lane's .w, .x, .y, .z), I = 2 t + 1 from (.y, .z, .w, right lane's .x) -- two lane
+// shuffles and foldX4 per store, the order of the sum stays z, x, y.  Lanes without a quad of their own (outside the active x range
+// or the grid) hold another quad's values and pass 0; a lane next to the range stores too (its columns take a term from the live
+// neighbour, as they do in the full-resolution layout).  A tile is a wave wide: the columns that straddle a tile boundary
+// (I = 128 s - 1 and 128 s, fine 256 s - 3 .. 256 s + 2) are not formed here -- lane 63 and lane 0 on either side also store their
+// z-folded quads into `seam` (8 floats per interior boundary s, row and coarse plane: [K][j][s - 1][8]), restrictYKernel folds
+// those two columns from there with the same foldX4 and never reads their rzx entries.
+template <bool XF>
 __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, float *__restrict__ rz, const float *__restrict__ x,
                                                                      const float *__restrict__ b, unsigned nbx, unsigned nby, int zc,
-                                                                     const int32_t *__restrict__ blocks, const float *__restrict__ rEdge)
+                                                                     const int32_t *__restrict__ blocks, const float *__restrict__ rEdge,
+                                                                     float *__restrict__ seam)
 {
     __shared__ float plane[2][(kPlaneRows + 2) * kPlanePitch];
     unsigned bid = remapBlock(blockIdx.x, gridDim.x);
@@ -777,6 +813,25 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
     constexpr float w0 = 0.125f, w1 = 0.375f, w2 = 0.375f, w3 = 0.125f;
     // coarse plane (k - 1) / 2 with its first terms (accPrev) and the one after it (accCur), see the fold below
     float accPrev[4] = {0.f, 0.f, 0.f, 0.f}, accCur[4] = {0.f, 0.f, 0.f, 0.f};
+    // XF: where this lane's two coarse columns go, who stores them, and the seam entry of a tile's first / last lane
+    // (offsets formed at the store from a scalar row base -- the row is the wave's -- and the lane: no register held across the march)
+    const unsigned rowS = __builtin_amdgcn_readfirstlane(unsigned(jc));
+    const unsigned rowX = rowS * (unsigned(g.nx) >> 1) + bx * 128u, rowSeam = (rowS * (nbx - 1u) + bx) * 8u;
+    const bool storeX = i < g.nx && j < g.ny && ic >= g.xlo - 4 && ic < g.xhi + 4;
+    const bool seamL = colL && bx > 0, seamR = colR && i + 4 < g.nx;  // (the boundary at fine x = 256 bx / 256 (bx + 1) is inside the grid)
+    const bool seamW = valid && (seamL || seamR);
+    auto storeFolded = [&](int K, bool nt) {  // (every lane of the wave comes here: the shuffles)
+        const float4 v = keepIf(make_float4(accPrev[0], accPrev[1], accPrev[2], accPrev[3]), valid);
+        const float2 o = make_float2(foldX4(fromLeftLane(v.w), v.x, v.y, v.z), foldX4(v.y, v.z, v.w, fromRightLane(v.x)));
+        float *const px = scalarBase(rz + size_t(K) * (sz >> 1));
+        if (storeX) {
+            const unsigned offX = rowX + 2u * unsigned(lane);
+            if (nt) gStore2nt(px, offX, o);
+            else gStore2(px, offX, o);
+        }
+        // (lane 63: the first quad of boundary bx + 1's entry, lane 0: the second quad of boundary bx's)
+        if (seamW) gStore4(scalarBase(seam + size_t(K) * size_t(g.ny) * size_t(nbx - 1u) * 8u), colL ? rowSeam - 4u : rowSeam, v);
+    };
     if (rEdge && k0 == 0 && g.ghostLo) {  // the neighbour's r on the plane below the slab: the first term of coarse plane 0 (wave-uniform branch)
         const float4 e = gLoad4(scalarBase(rEdge - ptrdiff_t(sz)), offL);
         accCur[0] = w0 * e.x;
@@ -836,7 +891,11 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
                 accPrev[e] += w3 * res[e];
                 accCur[e] += w1 * res[e];
             }
-            if (valid && k >= k0 + 2) gStore4nt(scalarBase(rz + size_t((k >> 1) - 1) * sz), offL, make_float4(accPrev[0], accPrev[1], accPrev[2], accPrev[3]));
+            if (XF) {
+                if (k >= k0 + 2) storeFolded((k >> 1) - 1, true);
+            } else if (valid && k >= k0 + 2) {
+                gStore4nt(scalarBase(rz + size_t((k >> 1) - 1) * sz), offL, make_float4(accPrev[0], accPrev[1], accPrev[2], accPrev[3]));
+            }
         }
         xc = xp;
         xp = xq;
@@ -846,15 +905,16 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
     }
     // the top block of the grid: plane nz does not exist, the last coarse plane is complete with three terms -- or, on a cut, its
     // fourth term is the neighbour's r on the plane above the slab
-    if (valid && k1 == g.nz) {
-        if (rEdge && g.ghostHi) {
+    if (k1 == g.nz) {  // (wave-uniform)
+        if (valid && rEdge && g.ghostHi) {
             const float4 e = gLoad4(scalarBase(rEdge + ptrdiff_t(g.nz) * ptrdiff_t(sz)), offL);
             accPrev[0] += w3 * e.x;
             accPrev[1] += w3 * e.y;
             accPrev[2] += w3 * e.z;
             accPrev[3] += w3 * e.w;
         }
-        gStore4(rz + size_t((g.nz >> 1) - 1) * sz, offL, make_float4(accPrev[0], accPrev[1], accPrev[2], accPrev[3]));
+        if (XF) storeFolded((g.nz >> 1) - 1, false);
+        else if (valid) gStore4(rz + size_t((g.nz >> 1) - 1) * sz, offL, make_float4(accPrev[0], accPrev[1], accPrev[2], accPrev[3]));
     }
 }
 
@@ -864,8 +924,12 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
 // workgroup per such block and side (a list made once, planeBlockEdges); every other entry of a block off the activity list is
 // 0, which is what rz holds there since it was made.
 // One plane, no march: the quad kernel's way of gathering the neighbours (x by lane shuffle, y and z from the caches).
+// XF: the x-folded layout and its seam entries, see residualZKernel -- every lane of a row stays to the end (the fold's shuffles), a
+// lane without a quad of its own loads nothing and passes 0.
+template <bool XF>
 __global__ __launch_bounds__(64 * kPlaneRows) void residualZEdgeKernel(GridP g, float *__restrict__ rz, const float *__restrict__ x, const float *__restrict__ b,
-                                                                      unsigned nbx, unsigned nby, int zc, const int32_t *__restrict__ edges)
+                                                                      unsigned nbx, unsigned nby, int zc, const int32_t *__restrict__ edges,
+                                                                      float *__restrict__ seam)
 {
     // edges[w] = 2 * block + side: the blocks without active cells whose neighbour below (side 0) / above (side 1) has some
     const unsigned bid = unsigned(edges[blockIdx.x]) >> 1, side = unsigned(edges[blockIdx.x]) & 1u;
@@ -876,8 +940,9 @@ __global__ __launch_bounds__(64 * kPlaneRows) void residualZEdgeKernel(GridP g, 
     if (k < 0 || k >= g.nz) return;
     const int lane = threadIdx.x & (kWave - 1), ty = threadIdx.x / kWave;
     const int i = int(bx) * 256 + lane * 4, j = int(by) * kPlaneRows + ty;
-    if (i >= g.nx || j >= g.ny) return;  // (whole wavefront rows leave together only when j is past the grid; lanes past nx: no shuffle partner needs them)
-    const bool live = i >= g.xlo && i < g.xhi;
+    if (j >= g.ny) return;                 // (a whole wavefront row)
+    if (!XF && i >= g.nx) return;          // (lanes past nx: no shuffle partner needs them)
+    const bool live = i < g.nx && i >= g.xlo && i < g.xhi;
     const size_t sy = size_t(g.nx), sz = size_t(g.nx) * g.ny;
     const size_t c = size_t(k) * sz + size_t(j) * sy + i;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -891,7 +956,7 @@ __global__ __launch_bounds__(64 * kPlaneRows) void residualZEdgeKernel(GridP g, 
     float left = __shfl_up(xc.w, 1), right = __shfl_down(xc.x, 1);
     if (lane == 0) left = (live && i > 0) ? x[c - 1] : 0.f;
     if (lane == kWave - 1 || i + 4 >= g.nx) right = (live && i + 4 < g.nx) ? x[c + 4] : 0.f;
-    if (!live) return;
+    if (!XF && !live) return;
     const float xs[6] = {left, xc.x, xc.y, xc.z, xc.w, right};
     const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
     const float zms[4] = {zm.x, zm.y, zm.z, zm.w}, zps[4] = {zp.x, zp.y, zp.z, zp.w};
@@ -905,7 +970,16 @@ __global__ __launch_bounds__(64 * kPlaneRows) void residualZEdgeKernel(GridP g, 
         const float r = simpleCell(ls[e]) ? epilogueRcp<OP_RESIDUAL>(xs[e + 1], bs[e], lap, simpleRcp(diag), 0.f) : inactiveValue<OP_RESIDUAL>(xs[e + 1]);
         res[e] = wz * r;
     }
-    *reinterpret_cast<float4 *>(rz + size_t(K) * sz + size_t(j) * sy + i) = make_float4(res[0], res[1], res[2], res[3]);
+    if (!XF) {
+        *reinterpret_cast<float4 *>(rz + size_t(K) * sz + size_t(j) * sy + i) = make_float4(res[0], res[1], res[2], res[3]);
+        return;
+    }
+    const float4 v = keepIf(make_float4(res[0], res[1], res[2], res[3]), live);
+    const float2 o = make_float2(foldX4(fromLeftLane(v.w), v.x, v.y, v.z), foldX4(v.y, v.z, v.w, fromRightLane(v.x)));
+    if (i < g.nx && i >= g.xlo - 4 && i < g.xhi + 4) *reinterpret_cast<float2 *>(rz + size_t(K) * (sz >> 1) + size_t(j) * (sy >> 1) + size_t(i >> 1)) = o;
+    const bool seamL = lane == 0 && bx > 0, seamR = lane == kWave - 1 && i + 4 < g.nx;
+    if (live && (seamL || seamR))
+        *reinterpret_cast<float4 *>(seam + ((size_t(K) * g.ny + size_t(j)) * (nbx - 1u) + (seamL ? bx - 1u : bx)) * 8u + (seamL ? 4u : 0u)) = v;
 }
 
 // Scalar fallback for levels whose nx is not a multiple of 4 (only the tiniest coarse levels).
@@ -1061,6 +1135,13 @@ __device__ __forceinline__ void bandBoxBody(const GridP &g, const TX *__restrict
     __shared__ float grow[7][kGenRows];
     __shared__ float gbv[kGenRows];
     __shared__ uint16_t gnode[kGenRows], gring[kGenRows];  // region cell and ring
+    // PRO without general cells (round 8): the coarse cells the region's corrections interpolate from -- bi .. bi + 1 over the
+    // region's cells per axis, at most (rx / 2 + 2)(ry / 2 + 2)(rz / 2 + 2) words -- staged once per group by dense loads that
+    // leave with the first batch, instead of eight scattered loads per listed cell one slot at a time behind it.  72 KB with
+    // `val`: still two workgroups per CU (GEN levels carry 18 KB of rows more and keep the loads from global memory).
+    constexpr bool kStaged = PRO && !GEN;
+    constexpr int kCoarseBoxWords = 2048, kCoarseSlots = kCoarseBoxWords / kBoxThreads;
+    __shared__ float cbox[kStaged ? kCoarseBoxWords : 1];
     // the group's description is wave-uniform: scalar registers (addresses below: scalar base + one 32-bit vector offset)
     const int32_t *gip = info + kBoxInfoInts * size_t(group);
     int gi[kBoxInfoInts];
@@ -1091,9 +1172,35 @@ __device__ __forceinline__ void bandBoxBody(const GridP &g, const TX *__restrict
     auto rd = [&](const TX *base, unsigned c) { return Cell<TX>::load1(reinterpret_cast<const TX *>(reinterpret_cast<const char *>(base) + c * unsigned(sizeof(TX)))); };
     auto rdf = [&](const float *base, unsigned c) { return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + c * 4u); };
     auto wr = [&](TX *base, unsigned c, float v) { Cell<TX>::store1(reinterpret_cast<TX *>(reinterpret_cast<char *>(base) + c * unsigned(sizeof(TX))), v); };
+    // the coarse box of the region (wave-uniform): [blo, blo + bn) per axis, with prolongAddKernel's clamp at both ends -- every cell's
+    // bi lies in [blo, blo + bn - 2], and the box lies inside the coarse grid
+    int cbLo[3] = {0, 0, 0}, cbN[3] = {1, 1, 1};
+    bool staged = false;
+    if (kStaged) {
+        const int o3[3] = {int(origin % g.nx), int((origin / g.nx) % g.ny), int(origin / sz)};
+        const int r3[3] = {rx, ry, (gi[1] >> 16) & 255}, cn3[3] = {g.nx >> 1, g.ny >> 1, g.nz >> 1};
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            cbLo[a] = min(max((o3[a] - 1) >> 1, 0), cn3[a] - 2);
+            cbN[a] = min(max((o3[a] + r3[a] - 2) >> 1, 0), cn3[a] - 2) + 2 - cbLo[a];
+        }
+        staged = cbN[0] * cbN[1] * cbN[2] <= kCoarseBoxWords;  // (else: the loads from global memory below)
+    }
     uint32_t ue[kBoxSlots];
     float bv[kBoxSlots];
     {
+        float cv[kCoarseSlots];
+        if (kStaged && staged) {  // unconditional loads, dense rows of the coarse grid (a thread past the box re-reads its first word)
+            const unsigned csy = unsigned(g.nx >> 1), csz = csy * unsigned(g.ny >> 1);
+            const unsigned nxy = unsigned(cbN[0] * cbN[1]), nbox = nxy * unsigned(cbN[2]);
+            const float *cb = scalarBase(coarse + (size_t(cbLo[2]) * csz + size_t(cbLo[1]) * csy + size_t(cbLo[0])));
+#pragma unroll
+            for (int m = 0; m < kCoarseSlots; ++m) {
+                const unsigned q = unsigned(tid) + unsigned(m) * kBoxThreads, qq = q < nbox ? q : 0u;
+                const unsigned z = qq / nxy, rem = qq - z * nxy, y = rem / unsigned(cbN[0]), x = rem - y * unsigned(cbN[0]);
+                cv[m] = gLoad1(cb, z * csz + y * csy + x);
+            }
+        }
         // first batch of loads: every list entry of this thread (and its general entry); second batch: every value
 #pragma unroll
         for (int m = 0; m < kBoxSlots; ++m) {
@@ -1132,6 +1239,10 @@ __device__ __forceinline__ void bandBoxBody(const GridP &g, const TX *__restrict
                 z1[q] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
+        if (kStaged && staged) {
+#pragma unroll
+            for (int m = 0; m < kCoarseSlots; ++m) cbox[tid + m * kBoxThreads] = cv[m];  // (read behind the two barriers below)
+        }
         __syncthreads();
         if (GEN && tid < ngen) {
             const uint32_t e = ge;
@@ -1160,6 +1271,26 @@ __device__ __forceinline__ void bandBoxBody(const GridP &g, const TX *__restrict
         const int cnx = g.nx >> 1, cny = g.ny >> 1, cnz = g.nz >> 1;
         const unsigned csy = unsigned(cnx), csz = unsigned(cnx) * unsigned(cny);
         const float *cb = scalarBase(coarse);
+        if (kStaged && staged) {  // the same eight values out of the staged box, the same lerps in the same order
+            const int bsy = cbN[0], bsz = cbN[0] * cbN[1];
+#pragma unroll
+            for (int m = 0; m < kBoxSlots; ++m) {
+                const uint32_t e = ue[m];
+                const unsigned cls = (e >> 16) & 15u;
+                if (tid + m * kBoxThreads < nList && cls != kBoxSkip && cls != kBoxZero) {
+                    const int ci = ox + int(e & 31u), cj = oy + int((e >> 5) & 31u), ck = oz + int((e >> 10) & 31u);
+                    const int bi = min(max((ci - 1) >> 1, 0), cnx - 2), bj = min(max((cj - 1) >> 1, 0), cny - 2), bk = min(max((ck - 1) >> 1, 0), cnz - 2);
+                    const float fx = (ci & 1) ? 0.25f : 0.75f, fy = (cj & 1) ? 0.25f : 0.75f, fz = (ck & 1) ? 0.25f : 0.75f;
+                    const float *c0 = cbox + ((bk - cbLo[2]) * bsz + (bj - cbLo[1]) * bsy + (bi - cbLo[0]));
+                    const float v00 = lerpRef(c0[0], c0[1], fx), v10 = lerpRef(c0[bsy], c0[bsy + 1], fx);
+                    const float v01 = lerpRef(c0[bsz], c0[bsz + 1], fx), v11 = lerpRef(c0[bsz + bsy], c0[bsz + bsy + 1], fx);
+                    const int n = nodeOf(e);
+                    const float v = val[0][n] + 4.f * lerpRef(lerpRef(v00, v10, fy), lerpRef(v01, v11, fy), fz);
+                    val[0][n] = v;
+                    val[1][n] = v;
+                }
+            }
+        } else
 #pragma unroll
         for (int m = 0; m < kBoxSlots; ++m) {
             if (m > 0) asm volatile("" ::: "memory");
@@ -1901,7 +2032,6 @@ __global__ __launch_bounds__(256) void restrictXYKernel(GridP cg, float *__restr
 #pragma unroll
         for (int m = 0; m < kRtLoads; ++m) v[m] = ok[m] ? *reinterpret_cast<const float4 *>(p + off[m]) : make_float4(0.f, 0.f, 0.f, 0.f);
     };
-    const float w[4] = {0.125f, 0.375f, 0.375f, 0.125f};
     float4 nextv[kRtLoads];
     loadPlane(K0, nextv);
     for (int K = K0; K < K1; ++K) {
@@ -1920,13 +2050,104 @@ __global__ __launch_bounds__(256) void restrictXYKernel(GridP cg, float *__restr
         for (int yo = 0; yo < 6; ++yo) {
             const float *r = p + yo * kRtStride;
             const float2 mid = *reinterpret_cast<const float2 *>(r + 1);
-            rs[yo] = w[0] * r[0] + w[1] * mid.x + w[2] * mid.y + w[3] * r[3];
+            rs[yo] = foldX4(r[0], mid.x, mid.y, r[3]);
         }
         if (inGrid && any) {
             const size_t c = size_t(K) * cplane + col;
-            const float va = w[0] * rs[0] + w[1] * rs[1] + w[2] * rs[2] + w[3] * rs[3], vb = w[0] * rs[2] + w[1] * rs[3] + w[2] * rs[4] + w[3] * rs[5];
+            const float va = foldX4(rs[0], rs[1], rs[2], rs[3]), vb = foldX4(rs[2], rs[3], rs[4], rs[5]);  // (the same weights along y)
             coarse[c] = activeLabel(cg.lab[c]) ? va : 0.f;
             if (second) coarse[c + cg.nx] = activeLabel(cg.lab[c + cg.nx]) ? vb : 0.f;
+        }
+    }
+}
+
+// The y half of the restriction for a residual that residualZKernel<true> folded along z and x already: `rzx` has the coarse
+// level's columns and planes and the fine level's rows; coarse(I, J, K) = sum_b w_b rzx(I, 2J-1+b, K), restrictXYKernel's sum
+// along y.  A thread owns two neighbouring coarse columns and kRyJ coarse rows: 2 kRyJ + 2 rows of float2 in, no x halo, no
+// LDS, a wave reads 512 contiguous bytes of a row; one plane in, one plane out.  A wave is one of the march's tiles wide, so the
+// columns that straddle a tile boundary (I = 128 s, 128 s - 1) are its first lane's first column and its last lane's second one:
+// they take their rows from `seam` -- the two z-folded quads on either side of the boundary, folded with the march's foldX4.  The
+// wave fetches them together, row yo of the left boundary by lane yo, of the right boundary by lane 32 + yo (one load per lane,
+// no branch per row), and hands them over through readlane.  Rows and ranges as in restrictXYKernel: rows clamped at the grid's
+// faces (the coarse cells there are masked by their labels), entries nothing ever wrote are 0.
+constexpr int kRyJ = 8, kRyI = 512, kRyRows = 2 * kRyJ + 2;
+__global__ __launch_bounds__(256, 8) void restrictYKernel(GridP cg, float *__restrict__ coarse, const float *__restrict__ rzx, const float *__restrict__ seam, int kc,
+                                                         unsigned nbx, unsigned nby)
+{
+    __shared__ int anyActiveCol;
+    const unsigned bid = remapBlock(blockIdx.x, gridDim.x);
+    const unsigned bx = bid % nbx, by = (bid / nbx) % nby, bz = bid / (nbx * nby);
+    const int I = int(bx) * kRyI + 2 * int(threadIdx.x), J0 = int(by) * kRyJ;  // (cg.nx, cg.xlo and cg.xhi are even: a pair is inside or outside whole)
+    const int K0 = int(bz) * kc, K1 = min(K0 + kc, cg.nz);
+    const size_t cplane = size_t(cg.nx) * cg.ny;
+    const bool inGrid = I < cg.nx && I >= cg.xlo && I < cg.xhi;
+    const int nJ = min(kRyJ, cg.ny - J0);
+    bool any = false;
+    if (inGrid)
+        for (int K = K0; K < K1; ++K)
+            for (int jj = 0; jj < nJ; ++jj) {
+                const uchar2 l = *reinterpret_cast<const uchar2 *>(cg.lab + size_t(K) * cplane + size_t(J0 + jj) * cg.nx + I);
+                any = any || activeLabel(l.x) || activeLabel(l.y);
+            }
+    if (threadIdx.x == 0) anyActiveCol = 0;
+    __syncthreads();
+    if (any) anyActiveCol = 1;
+    __syncthreads();
+    if (!anyActiveCol) return;  // (the destination holds 0 there already)
+    const bool mine = inGrid && any;  // (a thread without columns stays for the wave's seam loads; its own loads aim at the row's last pair)
+    const int fny = 2 * cg.ny;
+    const int nseam = (2 * cg.nx + 255) / 256 - 1;
+    const int lane = int(threadIdx.x) & (kWave - 1);
+    // the boundaries at the wave's first column (sL, fine x = 256 sL) and behind its last one (sL + 1), where they lie inside the grid
+    const int sL = __builtin_amdgcn_readfirstlane(int(bx) * (kRyI / 128) + int(threadIdx.x >> 6));
+    const bool hasL = sL >= 1 && sL <= nseam, hasR = sL + 1 <= nseam;
+    const int seamRow = lane & 31, seamSide = lane >> 5;
+    const bool seamLoad = seamRow < kRyRows && (seamSide ? hasR : hasL);
+    // the entry: fine 256 s - 4 .. 256 s + 3; column 128 s folds 256 s - 1 .. 256 s + 2, column 128 s - 1 folds 256 s - 3 .. 256 s
+    const unsigned seamOff = (unsigned(min(max(2 * J0 - 1 + seamRow, 0), fny - 1)) * unsigned(nseam) + unsigned(sL + seamSide - 1)) * 8u + (seamSide ? 1u : 3u);
+    const bool takeL = hasL && lane == 0, takeR = hasR && lane == kWave - 1;
+    const unsigned Ic = unsigned(min(I, cg.nx - 2));
+    auto opq = [](unsigned v) {
+        asm volatile("" : "+v"(v));
+        return v;
+    };
+    for (int K = K0; K < K1; ++K) {
+        // (a plane of each array as a scalar base, 32-bit offsets inside it formed where they are used: through `opq` the row offsets
+        // are not loop invariants the optimiser could keep in a register each across the planes)
+        const float *p = scalarBase(rzx + size_t(K) * size_t(fny) * cg.nx);
+        const unsigned col = opq(Ic);
+        float sf = 0.f;
+        if (seamLoad) {
+            const float4 v = gLoad4u(scalarBase(seam + size_t(K) * size_t(fny) * size_t(nseam) * 8u), seamOff);
+            sf = foldX4(v.x, v.y, v.z, v.w);
+        }
+        float2 r[kRyRows];
+#pragma unroll
+        for (int yo = 0; yo < kRyRows; ++yo) {
+            const int fy = min(max(2 * J0 - 1 + yo, 0), fny - 1);  // (rows clamped: results masked)
+            r[yo] = gLoad2(p, unsigned(fy) * unsigned(cg.nx) + col);
+        }
+        if (hasL || hasR) {  // (wave-uniform)
+#pragma unroll
+            for (int yo = 0; yo < kRyRows; ++yo) {
+                const float fl = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sf), yo));
+                const float fr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sf), 32 + yo));
+                r[yo].x = takeL ? fl : r[yo].x;
+                r[yo].y = takeR ? fr : r[yo].y;
+            }
+        }
+        if (!mine) continue;
+        const uint8_t *labK = scalarBase(cg.lab + size_t(K) * cplane);
+        float *outK = scalarBase(coarse + size_t(K) * cplane);
+#pragma unroll
+        for (int jj = 0; jj < kRyJ; ++jj) {
+            if (jj >= nJ) break;
+            const unsigned cell = unsigned(J0 + jj) * unsigned(cg.nx) + col;  // (mine: Ic = I)
+            typedef uint8_t v2b __attribute__((ext_vector_type(2)));
+            const v2b l = *(const MGPS_GLOBAL_AS v2b *)((const MGPS_GLOBAL_AS uint8_t *)labK + cell);
+            const float va = foldX4(r[2 * jj].x, r[2 * jj + 1].x, r[2 * jj + 2].x, r[2 * jj + 3].x);
+            const float vb = foldX4(r[2 * jj].y, r[2 * jj + 1].y, r[2 * jj + 2].y, r[2 * jj + 3].y);
+            gStore2(outK, cell, make_float2(activeLabel(l.x) ? va : 0.f, activeLabel(l.y) ? vb : 0.f));
         }
     }
 }
@@ -2987,15 +3208,33 @@ int launchResidualEdgePlanes(void *stream, const GridP &g, float *r, const float
     }
     return int(hipGetLastError());
 }
-int launchResidualZ(void *stream, const GridP &fine, float *rz, const float *x, const float *b, const int32_t *edges, int nedges, const float *rEdge)
+// The x-folded layout of rz (residualZKernel<true>): levels without general BOUNDARY cells -- residualZGeneralKernel adds into
+// full-resolution entries in an order fixed by k mod 4 and keeps the layout it was written for.  rzxFloats: the grid of
+// nx / 2 x ny x nz / 2 (rounded up to whole quads) with the seam array behind it.
+bool residualRestrictXFolds(const GridP &fine) { return fine.nbnd == 0; }
+static size_t rzxGridFloats(const GridP &fine) { return (size_t(fine.nx) * fine.ny * fine.nz / 4 + 3) & ~size_t(3); }
+size_t rzxFloats(const GridP &fine) { return rzxGridFloats(fine) + size_t(fine.nz / 2) * fine.ny * size_t((fine.nx + 255) / 256 - 1) * 8; }
+int launchResidualZ(void *stream, const GridP &fine, float *rz, const float *x, const float *b, const int32_t *edges, int nedges, const float *rEdge, bool xfold)
 {
+    if (xfold) {
+        if (fine.nbnd > 0) return int(hipErrorInvalidValue);
+        const int zc = fine.planeZc;
+        const unsigned nbx = (fine.nx + 255) / 256, nby = (fine.ny + kPlaneRows - 1) / kPlaneRows, nbz = (fine.nz + zc - 1) / zc;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        const bool list = fine.planeBlocks != nullptr;
+        const unsigned nb = list ? unsigned(fine.nplaneBlocks) : nbx * nby * nbz;
+        float *seam = rz + rzxGridFloats(fine);
+        if (nb > 0) residualZKernel<true><<<nb, 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, list ? fine.planeBlocks : nullptr, rEdge, seam);
+        if (list && nedges > 0) residualZEdgeKernel<true><<<unsigned(nedges), 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, edges, seam);
+        return int(hipGetLastError());
+    }
     const int zc = fine.planeZc;
     const unsigned nbx = (fine.nx + 255) / 256, nby = (fine.ny + kPlaneRows - 1) / kPlaneRows, nbz = (fine.nz + zc - 1) / zc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool list = fine.planeBlocks != nullptr;
     const unsigned nb = list ? unsigned(fine.nplaneBlocks) : nbx * nby * nbz;
-    if (nb > 0) residualZKernel<<<nb, 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, list ? fine.planeBlocks : nullptr, rEdge);
-    if (list && nedges > 0) residualZEdgeKernel<<<unsigned(nedges), 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, edges);
+    if (nb > 0) residualZKernel<false><<<nb, 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, list ? fine.planeBlocks : nullptr, rEdge, nullptr);
+    if (list && nedges > 0) residualZEdgeKernel<false><<<unsigned(nedges), 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, edges, nullptr);
     if (fine.nbnd > 0)  // the general BOUNDARY cells' part (their entries lie in blocks the launches above have just written)
         for (int phase = 0; phase < 4; ++phase) residualZGeneralKernel<<<blocksFor(size_t(fine.nbnd), 256), 256, 0, s>>>(fine, rz, x, b, phase);
     return int(hipGetLastError());
@@ -3007,6 +3246,17 @@ int launchRestrictXY(void *stream, const GridP &coarse, float *coarseOut, const 
     while (kc > 1 && size_t(nbx) * nby * ((coarse.nz + kc - 1) / kc) < 8192) kc >>= 1;
     const unsigned nbz = (coarse.nz + kc - 1) / kc;
     restrictXYKernel<<<nbx * nby * nbz, 256, 0, static_cast<hipStream_t>(stream)>>>(coarse, coarseOut, rz, kc, nbx, nby);
+    return int(hipGetLastError());
+}
+
+// fine: the level `rzx` was folded from (its seam array lies behind the grid, rzxFloats)
+int launchRestrictY(void *stream, const GridP &coarse, float *coarseOut, const float *rzx, const GridP &fine)
+{
+    int kc = 16;  // (as launchRestrictXY)
+    const unsigned nbx = (coarse.nx + kRyI - 1) / kRyI, nby = (coarse.ny + kRyJ - 1) / kRyJ;
+    while (kc > 1 && size_t(nbx) * nby * ((coarse.nz + kc - 1) / kc) < 8192) kc >>= 1;
+    const unsigned nbz = (coarse.nz + kc - 1) / kc;
+    restrictYKernel<<<nbx * nby * nbz, 256, 0, static_cast<hipStream_t>(stream)>>>(coarse, coarseOut, rzx, rzx + rzxGridFloats(fine), kc, nbx, nby);
     return int(hipGetLastError());
 }
 

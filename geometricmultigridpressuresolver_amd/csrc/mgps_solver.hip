@@ -856,12 +856,25 @@ bool residualRestrictFuses(const mgps_solver *h, int l)
     if (mode < 0 && size_t(F.nx) * F.ny * sizeof(float) < kPlaneSweepMinPlaneBytes) return false;
     return residualRestrictFits(F, h->lv[l + 1].g);
 }
+// The form of the pair on a level that takes it (round 8): rz folded along x as well where the march stores it (residualZKernel<true>
+// + restrictYKernel: half the bytes handed over, 1024^3 fine level: see DESIGN 3.2) unless the level has general BOUNDARY cells,
+// whose patch launches add into the full-resolution layout.  MGPS_RZ_XFOLD=0: the full-resolution layout everywhere (A/B; the two
+// give the same bits, foldX4).
+bool residualRestrictXFolded(const mgps_solver *h, int l)
+{
+    static const bool allowed = [] {
+        const char *e = getenv("MGPS_RZ_XFOLD");
+        return !(e && e[0] == '0');
+    }();
+    return allowed && residualRestrictFuses(h, l) && residualRestrictXFolds(h->lv[l].g);
+}
 // out (optional): where the coarse rhs goes instead of the coarse level's own rhs grid (mgps_residual_downsample)
 int residualRestrict(mgps_solver *h, int l, const float *x, const float *rhs, float *out = nullptr)
 {
     DevLevel &F = h->lv[l], &C = h->lv[l + 1];
+    const bool xfold = residualRestrictXFolded(h, l);  // (the same answer at every call: the level's rz keeps its layout)
     if (!F.rz) {
-        MGPS_TRY(devAlloc(h, &F.rz, F.d.cells() / 2, true));
+        MGPS_TRY(devAlloc(h, &F.rz, xfold ? rzxFloats(F.g) : F.d.cells() / 2, true));
         if (F.g.planeBlocks) {  // once: which blocks off the activity list sit below / above a listed one
             if (!F.planeFlags) {
                 MGPS_TRY(devAlloc(h, &F.planeFlags, planeBlockCount(F.g), true));
@@ -883,10 +896,11 @@ int residualRestrict(mgps_solver *h, int l, const float *x, const float *rhs, fl
             MGPS_LAUNCH(h, launchResidualEdgePlanes(h->stream, F.g, F.r, x, rhs));
             MGPS_TRY(exchangeGhosts(h, l, F.r, GHOST_FULL));
         }
-        MGPS_LAUNCH(h, launchResidualZ(h->stream, F.g, F.rz, x, rhs, F.rzEdges, F.nrzEdges, cut ? F.r : nullptr));
+        MGPS_LAUNCH(h, launchResidualZ(h->stream, F.g, F.rz, x, rhs, F.rzEdges, F.nrzEdges, cut ? F.r : nullptr, xfold));
     }
     StageScope scope(h, ST_RESTRICT, l);
-    MGPS_LAUNCH(h, launchRestrictXY(h->stream, C.g, out ? out : C.b, F.rz));
+    if (xfold) MGPS_LAUNCH(h, launchRestrictY(h->stream, C.g, out ? out : C.b, F.rz, F.g));
+    else MGPS_LAUNCH(h, launchRestrictXY(h->stream, C.g, out ? out : C.b, F.rz));
     return MGPS_OK;
 }
 
@@ -4700,6 +4714,13 @@ int mgps_residual_restrict_fused(const mgps_solver *h, int level, int *fused)
 try {
     if (!h || !fused || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
     *fused = residualRestrictFuses(h, level) ? 1 : 0;
+    return MGPS_OK;
+}
+MGPS_API_CATCH(h)
+int mgps_residual_restrict_xfolded(const mgps_solver *h, int level, int *xfolded)
+try {
+    if (!h || !xfolded || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
+    *xfolded = residualRestrictXFolded(h, level) ? 1 : 0;
     return MGPS_OK;
 }
 MGPS_API_CATCH(h)

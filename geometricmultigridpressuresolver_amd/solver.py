@@ -442,6 +442,12 @@ class GeometricMultigridPoissonSolver:
         check(lib().mgps_residual_restrict_fused(self.h, int(level), C.byref(f)), self.h)
         return bool(f.value)
 
+    def residual_restrict_xfolded(self, level=0):
+        """mgps_residual_restrict_xfolded: does that pair hand the residual over folded along x as well (restrictYKernel)?"""
+        f = C.c_int()
+        check(lib().mgps_residual_restrict_xfolded(self.h, int(level), C.byref(f)), self.h)
+        return bool(f.value)
+
     def up_stroke_fused(self, level=0):
         """mgps_up_stroke_fused: does an up-stroke of this level run the prolongation inside its Jacobi sweep?"""
         f = C.c_int()

@@ -544,6 +544,11 @@ int mgps_band_stage_form(const mgps_solver *h, int level, int *form);
  * the residual grid.  By size (x-y planes >= 4 MiB) on levels whose shape the pair takes; MGPS_FUSE_RR=0 / 1 forces it off /
  * onto every level that fits (tests).  The same products either way, added along z first instead of last. */
 int mgps_residual_restrict_fused(const mgps_solver *h, int level, int *fused);
+/* *xfolded = 1 when that pair hands the residual over folded along x as well (half the bytes between its two launches: "residual
+ * folded along z and x as it is formed + y restriction"), 0 when the level runs the pair on the full-resolution layout or not at
+ * all.  Levels without general BOUNDARY cells; MGPS_RZ_XFOLD=0 keeps the full-resolution layout everywhere (A/B).  The same bits
+ * either way. */
+int mgps_residual_restrict_xfolded(const mgps_solver *h, int level, int *xfolded);
 /* *fused = 1 when an up-stroke of level `level` runs its prolongation inside the Jacobi sweep (prolongJacobiPlaneKernel, and the
  * closure launch reading x + 4 P e; no prolongation pass), 0 when the prolongation is a pass of its own.  By size (x-y planes
  * >= 4 MiB) on single-device fp32 Jacobi levels with band boxes and plane blocks, one post-sweep; MGPS_FUSE_UP=0 / 1 forces it
