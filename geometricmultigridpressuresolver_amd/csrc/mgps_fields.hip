@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -1849,6 +1850,474 @@ try {
                     rank, p->stage_ms[0], p->stage_ms[1], p->stage_ms[2], p->stage_ms[3], p->stage_ms[4], p->stage_ms[5], exchangeMs);
     if (solveRc != MGPS_OK) setLastGlobalError("mgps_project_free_surface_slab: interrupted");
     return solveRc;
+}
+MGPS_API_CATCH(nullptr)
+
+}  // extern "C"
+
+// ---- velocity extrapolation into the air band (include/mgps_fields.h) ---------------------------------------
+// One launch per layer over the three face grids (blockIdx.y = axis).  A layer touches a thin shell of faces, so the pass is a sweep
+// of the `layer` bytes: a thread reads one aligned dword -- 4 faces that follow each other in the flat x-fastest grid, whatever the
+// row length -- and a wave none of whose 256 faces is still open (255) leaves at once.  Only an open face looks at its 6 neighbours'
+// bytes, and only a known neighbour's velocity is fetched.  In place: a layer reads values of layers < l and writes faces of layer
+// 255, so a neighbour byte that another thread turns from 255 to l meanwhile reads as "not known" either way.
+namespace {
+struct ExAxis {
+    float *vel;
+    uint8_t *layer;
+    const uint8_t *valid;               // read by the l == 0 pass only
+    const float *cw;                    // or NULL
+    const float *velLo, *velHi;         // the face planes in front of / behind the window, or NULL
+    const uint8_t *layLo, *layHi;
+    int nx, ny, nz;                     // the face grid of the window
+};
+struct ExArgs {
+    ExAxis a[3];
+    int l;
+};
+
+// flat face index -> (i, j, k)
+__device__ __forceinline__ void exUnflatten(const ExAxis &A, long long n, long long idx, int &i, int &j, int &k)
+{
+    if (n <= 0xffffffffll) {
+        const unsigned u = unsigned(idx), row = u / unsigned(A.nx);
+        i = int(u - row * unsigned(A.nx));
+        k = int(row / unsigned(A.ny));
+        j = int(row - unsigned(k) * unsigned(A.ny));
+    } else {
+        const long long row = idx / A.nx;
+        i = int(idx - row * A.nx);
+        k = int(row / A.ny);
+        j = int(row - (long long)k * A.ny);
+    }
+}
+
+// the 4 faces [first, first + 4) of the grid that share the aligned dword at layer + first (first may be < 0 and first + 4 > n when
+// the grid does not start or end on a dword: those bytes are fetched one by one and the missing ones read as 0, "not open")
+__device__ __forceinline__ unsigned exLoad4(const uint8_t *p, long long first, long long n)
+{
+    if (first >= 0 && first + 4 <= n) return *reinterpret_cast<const unsigned *>(p + first);
+    unsigned w = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (first + q >= 0 && first + q < n) w |= unsigned(p[first + q]) << (8 * q);
+    return w;
+}
+// does a byte of w equal 255?  (exact: ~w has a zero byte)
+__device__ __forceinline__ bool exAnyOpen(unsigned w) { return ((~w - 0x01010101u) & w & 0x80808080u) != 0; }
+
+__device__ __forceinline__ void extrapolateAxis(const ExAxis &A, unsigned l)
+{
+    const long long n = (long long)A.nx * A.ny * A.nz;
+    const long long first = 4 * ((long long)blockIdx.x * blockDim.x + threadIdx.x) - (long long)(reinterpret_cast<uintptr_t>(A.layer) & 3u);
+    const unsigned w = first < n ? exLoad4(A.layer, first, n) : 0u;
+    if (!__any(exAnyOpen(w))) return;  // (wave-uniform: the common case)
+    if (exAnyOpen(w)) {
+        const long long plane = (long long)A.nx * A.ny;
+        const long long base = first < 0 ? 0 : first;
+        int i0, j0, k0;
+        exUnflatten(A, n, base, i0, j0, k0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (((w >> (8 * q)) & 0xffu) != 255u) continue;
+            const long long idx = first + q;
+            int i = i0 + int(idx - base), j = j0, k = k0;
+            while (i >= A.nx) {
+                i -= A.nx;
+                if (++j == A.ny) j = 0, ++k;
+            }
+            float sum = 0.f;
+            int known = 0;
+            // -x, +x: inside the dword where they are
+            if (i > 0 && (q > 0 ? (w >> (8 * (q - 1))) & 0xffu : unsigned(A.layer[idx - 1])) < l) sum += A.vel[idx - 1], ++known;
+            if (i + 1 < A.nx && (q < 3 ? (w >> (8 * (q + 1))) & 0xffu : unsigned(A.layer[idx + 1])) < l) sum += A.vel[idx + 1], ++known;
+            if (j > 0 && A.layer[idx - A.nx] < l) sum += A.vel[idx - A.nx], ++known;
+            if (j + 1 < A.ny && A.layer[idx + A.nx] < l) sum += A.vel[idx + A.nx], ++known;
+            const long long ij = (long long)j * A.nx + i;
+            if (k > 0) {
+                if (A.layer[idx - plane] < l) sum += A.vel[idx - plane], ++known;
+            } else if (A.layLo) {
+                if (A.layLo[ij] < l) sum += A.velLo[ij], ++known;
+            }
+            if (k + 1 < A.nz) {
+                if (A.layer[idx + plane] < l) sum += A.vel[idx + plane], ++known;
+            } else if (A.layHi) {
+                if (A.layHi[ij] < l) sum += A.velHi[ij], ++known;
+            }
+            if (known == 0 || (A.cw && !(A.cw[idx] > 0.f))) continue;
+            A.vel[idx] = sum / float(known);
+            A.layer[idx] = uint8_t(l);
+        }
+    }
+}
+
+// layer l of up to three face grids; blocks past the end of a shorter grid leave at once
+__global__ __launch_bounds__(256) void extrapolateLayerKernel(ExArgs p)
+{
+    // (constant indices: a dynamically indexed by-value argument would be copied to scratch)
+    if (blockIdx.y == 0) extrapolateAxis(p.a[0], unsigned(p.l));
+    else if (blockIdx.y == 1) extrapolateAxis(p.a[1], unsigned(p.l));
+    else extrapolateAxis(p.a[2], unsigned(p.l));
+}
+
+// filled[axis] += the faces [0, n[axis]) whose layer lies in [lo, hi].  A pass of its own over the layer bytes, behind the layers:
+// counting where the faces are filled costs one atomic per wave of the shell on three addresses, which took longer than the layer
+// itself.  Here a block sums its share in registers and LDS and adds once: kCountBlocks adds per axis
+constexpr int kCountBlocks = 1024;
+struct ExCount {
+    const uint8_t *layer[3];
+    long long n[3];
+    unsigned lo, hi;
+    unsigned long long *filled;
+};
+__global__ __launch_bounds__(256) void extrapolateCountKernel(ExCount p)
+{
+    const int axis = int(blockIdx.y);
+    const uint8_t *layer = axis == 0 ? p.layer[0] : axis == 1 ? p.layer[1] : p.layer[2];
+    const long long n = axis == 0 ? p.n[0] : axis == 1 ? p.n[1] : p.n[2];
+    const long long mis = (long long)(reinterpret_cast<uintptr_t>(layer) & 3u);
+    unsigned mine = 0;  // (at most 4 faces per step of 2^20 faces: no overflow below 2^50 faces)
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; 4 * c - mis < n; c += (long long)gridDim.x * blockDim.x) {
+        const unsigned w = exLoad4(layer, 4 * c - mis, n);  // (a missing byte reads 0: lo >= 1)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned b = (w >> (8 * q)) & 0xffu;
+            mine += b >= p.lo && b <= p.hi;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+    __shared__ unsigned part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned total = part[0] + part[1] + part[2] + part[3];
+        if (total) atomicAdd(p.filled + axis, (unsigned long long)total);
+    }
+}
+
+// layer = valid ? 0 : 255, 4 faces per thread (dword-wide where both grids allow it)
+__device__ __forceinline__ void extrapolateInitAxis(const ExAxis &A)
+{
+    const long long n = (long long)A.nx * A.ny * A.nz;
+    const long long first = 4 * ((long long)blockIdx.x * blockDim.x + threadIdx.x) - (long long)(reinterpret_cast<uintptr_t>(A.layer) & 3u);
+    if (first >= n) return;
+    if (first >= 0 && first + 4 <= n && ((reinterpret_cast<uintptr_t>(A.valid) ^ reinterpret_cast<uintptr_t>(A.layer)) & 3u) == 0) {
+        const unsigned v = *reinterpret_cast<const unsigned *>(A.valid + first);
+        unsigned out = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) out |= (((v >> (8 * q)) & 0xffu) == 1u ? 0u : 255u) << (8 * q);
+        *reinterpret_cast<unsigned *>(A.layer + first) = out;
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (first + q >= 0 && first + q < n) A.layer[first + q] = A.valid[first + q] == 1 ? 0 : 255;
+}
+__global__ __launch_bounds__(256) void extrapolateInitKernel(ExArgs p)
+{
+    if (blockIdx.y == 0) extrapolateInitAxis(p.a[0]);
+    else if (blockIdx.y == 1) extrapolateInitAxis(p.a[1]);
+    else extrapolateInitAxis(p.a[2]);
+}
+
+// the planes a slab rank sends to its neighbours before a layer, packed: [x-face | y-face | z-face velocity planes (float) | the same
+// three layer planes (uint8)].  To the rank below: plane 0 of every window (of the z-faces plane 1: plane 0 is the cut's, the
+// neighbour has its own copy); to the rank above: the last plane (of the z-faces the last but one)
+struct ExPack {
+    const float *vel[3];
+    const uint8_t *lay[3];
+    int count[3];  // entries of one plane per axis
+    long long lo[3], hi[3];  // first entry of the plane sent down / up (-1: no neighbour)
+    float *outLo, *outHi;
+};
+__global__ __launch_bounds__(256) void extrapolatePackKernel(ExPack p)
+{
+    const int total = p.count[0] + p.count[1] + p.count[2];
+    int t = int(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t >= total) return;
+    const int slot = t;
+    const int a = t < p.count[0] ? 0 : t < p.count[0] + p.count[1] ? 1 : 2;
+    t -= a == 0 ? 0 : a == 1 ? p.count[0] : p.count[0] + p.count[1];
+    const float *vel = a == 0 ? p.vel[0] : a == 1 ? p.vel[1] : p.vel[2];
+    const uint8_t *lay = a == 0 ? p.lay[0] : a == 1 ? p.lay[1] : p.lay[2];
+    const long long lo = a == 0 ? p.lo[0] : a == 1 ? p.lo[1] : p.lo[2], hi = a == 0 ? p.hi[0] : a == 1 ? p.hi[1] : p.hi[2];
+    if (lo >= 0) {
+        p.outLo[slot] = vel[lo + t];
+        reinterpret_cast<uint8_t *>(p.outLo + total)[slot] = lay[lo + t];
+    }
+    if (hi >= 0) {
+        p.outHi[slot] = vel[hi + t];
+        reinterpret_cast<uint8_t *>(p.outHi + total)[slot] = lay[hi + t];
+    }
+}
+
+int exRefuse(const char *fn, const std::string &what)
+{
+    setLastGlobalError(std::string(fn) + ": " + what);
+    return MGPS_ERR_INVALID_ARGUMENT;
+}
+// the checks every extrapolation entry shares, on the host, before any HIP call
+int exCheckLayers(const char *fn, int layers)
+{
+    if (layers < 1 || layers > 254) return exRefuse(fn, "layers = " + std::to_string(layers) + " is outside 1 .. 254 (layer is a uint8 grid, 255 = not reached)");
+    return MGPS_OK;
+}
+int exCheckExtents(const char *fn, int gx, int gy, int gz)
+{
+    if (!okBox(gx, gy, gz)) return exRefuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(gx) + ", " + std::to_string(gy) + ", " + std::to_string(gz) + ")");
+    return MGPS_OK;
+}
+// cut_weights: NULL, or all three
+int exCheckCutWeights(const char *fn, const float *const cw[3])
+{
+    if (cw && !(cw[0] && cw[1] && cw[2]) && (cw[0] || cw[1] || cw[2])) return exRefuse(fn, "cut_weights: all three grids, or none");
+    return MGPS_OK;
+}
+inline dim3 exGrid(const ExArgs &p, int naxes)
+{
+    long long n = 0;
+    for (int a = 0; a < naxes; ++a) n = std::max(n, (long long)p.a[a].nx * p.a[a].ny * p.a[a].nz);
+    return dim3(unsigned((n + 3 + 4 * 256 - 1) / (4 * 256)), unsigned(naxes));  // (+3: a grid that starts inside a dword)
+}
+int exLaunchLayer(const ExArgs &p, int naxes, hipStream_t st, const char *fn)
+{
+    if (p.l == 0) extrapolateInitKernel<<<exGrid(p, naxes), 256, 0, st>>>(p);
+    else extrapolateLayerKernel<<<exGrid(p, naxes), 256, 0, st>>>(p);
+    return done(fn);
+}
+// filled[a] += the faces of the planes [0, countNz[a]) of the three grids of p whose layer lies in [lo, hi]
+int exLaunchCount(const ExArgs &p, const int countNz[3], unsigned lo, unsigned hi, unsigned long long *filled, hipStream_t st, const char *fn)
+{
+    ExCount c{};
+    long long most = 0;
+    for (int a = 0; a < 3; ++a) {
+        c.layer[a] = p.a[a].layer;
+        c.n[a] = (long long)p.a[a].nx * p.a[a].ny * countNz[a];
+        most = std::max(most, c.n[a]);
+    }
+    c.lo = lo;
+    c.hi = hi;
+    c.filled = filled;
+    const long long want = (most + 3 + 4 * 256 - 1) / (4 * 256);
+    extrapolateCountKernel<<<dim3(unsigned(std::min<long long>(std::max<long long>(want, 1), kCountBlocks)), 3), 256, 0, st>>>(c);
+    return done(fn);
+}
+}  // namespace
+
+extern "C" {
+
+int mgps_fields_extrapolate(int axis, float *velocity, uint8_t *layer, const uint8_t *valid, const float *cut_weights, int layers, int gx,
+                            int gy, int gz, void *stream)
+try {
+    const char *fn = "mgps_fields_extrapolate";
+    if (axis < 0 || axis > 2) return exRefuse(fn, "axis = " + std::to_string(axis) + " is outside 0 .. 2");
+    if (int rc = exCheckLayers(fn, layers); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
+    if (!velocity) return exRefuse(fn, "velocity is NULL");
+    if (!layer) return exRefuse(fn, "layer is NULL");
+    if (!valid) return exRefuse(fn, "valid is NULL");
+    ExArgs p{};
+    p.a[0] = ExAxis{velocity, layer, valid, cut_weights, nullptr, nullptr, nullptr, nullptr, gx + (axis == 0), gy + (axis == 1), gz + (axis == 2)};
+    for (p.l = 0; p.l <= layers; ++p.l)
+        if (int rc = exLaunchLayer(p, 1, static_cast<hipStream_t>(stream), fn); rc != MGPS_OK) return rc;
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_extrapolate3(float *const velocity[3], uint8_t *const layer[3], const uint8_t *const valid[3], const float *const cut_weights[3],
+                             int layers, int gx, int gy, int gz, unsigned long long *filled_dev, void *stream)
+try {
+    const char *fn = "mgps_fields_extrapolate3";
+    if (int rc = exCheckLayers(fn, layers); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
+    if (!velocity || !velocity[0] || !velocity[1] || !velocity[2]) return exRefuse(fn, "velocity: three grids are required");
+    if (!layer || !layer[0] || !layer[1] || !layer[2]) return exRefuse(fn, "layer: three grids are required");
+    if (!valid || !valid[0] || !valid[1] || !valid[2]) return exRefuse(fn, "valid: three grids are required");
+    if (int rc = exCheckCutWeights(fn, cut_weights); rc != MGPS_OK) return rc;
+    const bool closed = cut_weights && cut_weights[0];
+    ExArgs p{};
+    for (int a = 0; a < 3; ++a)
+        p.a[a] = ExAxis{velocity[a], layer[a], valid[a], closed ? cut_weights[a] : nullptr, nullptr, nullptr, nullptr, nullptr, gx + (a == 0), gy + (a == 1),
+                        gz + (a == 2)};
+    for (p.l = 0; p.l <= layers; ++p.l)
+        if (int rc = exLaunchLayer(p, 3, static_cast<hipStream_t>(stream), fn); rc != MGPS_OK) return rc;
+    if (!filled_dev) return MGPS_OK;
+    const int countNz[3] = {gz, gz, gz + 1};
+    return exLaunchCount(p, countNz, 1, 254, filled_dev, static_cast<hipStream_t>(stream), fn);
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_extrapolate_layer(const mgps_fields_slab *d, int l, float *const velocity[3], uint8_t *const layer[3],
+                                       const uint8_t *const valid[3], const float *const velocity_lo[3], const float *const velocity_hi[3],
+                                       const uint8_t *const layer_lo[3], const uint8_t *const layer_hi[3], const float *const cut_weights[3],
+                                       unsigned long long *filled_dev, void *stream)
+try {
+    const char *fn = "mgps_fields_slab_extrapolate_layer";
+    Slab s;
+    if (!readSlab(d, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    if (l < 0 || l > 254) return exRefuse(fn, "l = " + std::to_string(l) + " is outside 0 .. 254 (0 initialises layer from valid)");
+    if (!velocity || !velocity[0] || !velocity[1] || !velocity[2]) return exRefuse(fn, "velocity: three grids are required");
+    if (!layer || !layer[0] || !layer[1] || !layer[2]) return exRefuse(fn, "layer: three grids are required");
+    if (l == 0 && (!valid || !valid[0] || !valid[1] || !valid[2])) return exRefuse(fn, "valid: three grids are required with l = 0");
+    if (int rc = exCheckCutWeights(fn, cut_weights); rc != MGPS_OK) return rc;
+    const bool lo = l > 0 && s.c0 > 0, hi = l > 0 && s.c1 < s.gz;
+    for (int a = 0; a < 3; ++a) {
+        if (lo && !(velocity_lo && layer_lo && velocity_lo[a] && layer_lo[a])) return exRefuse(fn, "velocity_lo / layer_lo: the planes below the window are required (c0 > 0)");
+        if (hi && !(velocity_hi && layer_hi && velocity_hi[a] && layer_hi[a])) return exRefuse(fn, "velocity_hi / layer_hi: the planes above the window are required (c1 < gz)");
+    }
+    const bool closed = cut_weights && cut_weights[0];
+    const int nzl = s.c1 - s.c0;
+    ExArgs p{};
+    for (int a = 0; a < 3; ++a)
+        p.a[a] = ExAxis{velocity[a], layer[a], l == 0 ? valid[a] : nullptr, closed ? cut_weights[a] : nullptr, lo ? velocity_lo[a] : nullptr,
+                        hi ? velocity_hi[a] : nullptr, lo ? layer_lo[a] : nullptr, hi ? layer_hi[a] : nullptr, s.gx + (a == 0), s.gy + (a == 1), nzl + (a == 2)};
+    p.l = l;
+    if (int rc = exLaunchLayer(p, 3, static_cast<hipStream_t>(stream), fn); rc != MGPS_OK || !filled_dev || l == 0) return rc;
+    const int countNz[3] = {nzl, nzl, s.c1 < s.gz ? nzl : nzl + 1};  // (the cut's z-face plane is counted by the rank above it)
+    return exLaunchCount(p, countNz, unsigned(l), unsigned(l), filled_dev, static_cast<hipStream_t>(stream), fn);
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_extrapolate_velocity_slab(mgps_extrapolation_slab *e, const mgps_comm *comm, const int *splits, void *stream)
+try {
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const char *fn = "mgps_extrapolate_velocity_slab";
+    // ---- what every rank shares: a refusal here is every rank's, before any collective and any HIP call
+    if (!e || e->struct_size != int(sizeof(mgps_extrapolation_slab))) return exRefuse(fn, "NULL or struct_size mismatch (mgps_extrapolation_slab)");
+    if (!comm || !splits || comm->struct_size < int(offsetof(mgps_comm, gather)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange ||
+        !comm->allreduce || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
+        return exRefuse(fn, "comm / splits: a mgps_comm with exchange and allreduce and the cuts are required");
+    if (int rc = exCheckLayers(fn, e->layers); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, e->gx, e->gy, e->gz); rc != MGPS_OK) return rc;
+    const int P = comm->size, rank = comm->rank, L = e->layers;
+    mgps_fields_slab desc;
+    if (int rc = mgps_fields_slab_describe(&desc, e->gx, e->gy, e->gz, e->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
+    Slab s;
+    if (!readSlab(&desc, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    e->filled[0] = e->filled[1] = e->filled[2] = 0;
+    e->total_ms = e->exchange_ms = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int gx = s.gx, gy = s.gy, nzl = s.c1 - s.c0;
+    const bool lo = s.c0 > 0, hi = s.c1 < s.gz;
+    const int count[3] = {(gx + 1) * gy, gx * (gy + 1), gx * gy};
+    const size_t entries = size_t(count[0]) + size_t(count[1]) + size_t(count[2]), message = entries * (sizeof(float) + 1);
+    // the ranks' verdicts through one sum all-reduce (every rank fills its own slot); a world of one asks nobody
+    auto agree = [&](int status, const char *where, double *sums, int nsums) -> int {
+        if (P == 1) return status;
+        std::vector<double> v(size_t(nsums) + size_t(P), 0.0);
+        for (int q = 0; q < nsums; ++q) v[size_t(q)] = sums[q];
+        v[size_t(nsums) + size_t(rank)] = double(status);
+        if (comm->allreduce(comm->user, v.data(), int(v.size()), 0) != 0) {
+            setLastGlobalError(std::string(fn) + ": all-reduce failed (" + where + ")");
+            return MGPS_ERR_COMM;
+        }
+        for (int q = 0; q < nsums; ++q) sums[q] = v[size_t(q)];
+        if (status != MGPS_OK) return status;
+        for (int r = 0; r < P; ++r)
+            if (int(v[size_t(nsums) + size_t(r)]) != MGPS_OK) {
+                setLastGlobalError(std::string(fn) + ": rank " + std::to_string(r) + " failed (" + where + ", status " +
+                                   std::to_string(int(v[size_t(nsums) + size_t(r)])) + ")");
+                return int(v[size_t(nsums) + size_t(r)]);
+            }
+        return MGPS_OK;
+    };
+    // ---- this rank's own arguments and buffers: a failure is carried by the all-reduce in front of the first exchange
+    std::unique_ptr<DevPool> pool;  // (made after the argument checks: a refusal makes no HIP call)
+    uint8_t *layer[3] = {nullptr, nullptr, nullptr};
+    float *sendLo = nullptr, *sendHi = nullptr, *recvLo = nullptr, *recvHi = nullptr;
+    unsigned long long *filled = nullptr;
+    int status = [&]() -> int {
+        for (int a = 0; a < 3; ++a) {
+            if (!e->velocity[a]) return exRefuse(fn, "velocity: three grids are required");
+            if (!e->valid_faces[a]) return exRefuse(fn, "valid_faces: three grids are required");
+        }
+        if (int rc = exCheckCutWeights(fn, e->cut_weights); rc != MGPS_OK) return rc;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+            setLastGlobalError("no HIP device is visible (this library has no CPU path)");
+            return MGPS_ERR_NO_DEVICE;
+        }
+        try {
+            pool.reset(new DevPool);
+            for (int a = 0; a < 3; ++a) layer[a] = e->layer[a] ? e->layer[a] : pool->get<uint8_t>(faceCount(gx, gy, nzl, a));
+            // (a message is floats first: every block of the cache is aligned for them)
+            if (lo) sendLo = pool->get<float>((message + 3) / 4), recvLo = pool->get<float>((message + 3) / 4);
+            if (hi) sendHi = pool->get<float>((message + 3) / 4), recvHi = pool->get<float>((message + 3) / 4);
+            filled = pool->get<unsigned long long>(3);
+        } catch (const std::bad_alloc &) {
+            setLastGlobalError(std::string(fn) + ": device allocation failed");
+            return MGPS_ERR_ALLOC;
+        }
+        if (hipMemsetAsync(filled, 0, 3 * sizeof(unsigned long long), st) != hipSuccess) {
+            setLastGlobalError(std::string(fn) + ": hipMemsetAsync failed");
+            return MGPS_ERR_HIP;
+        }
+        return MGPS_OK;
+    }();
+    if (int rc = agree(status, "arguments", nullptr, 0); rc != MGPS_OK) return rc;
+    // (from here on the buffers exist on every rank: a failing rank still takes part in every exchange and the last all-reduce
+    //  carries its status)
+    auto step = [&](int rc) {
+        if (status == MGPS_OK) status = rc;
+    };
+    const float *cw[3] = {e->cut_weights[0], e->cut_weights[1], e->cut_weights[2]};
+    const float *velLo[3], *velHi[3];
+    const uint8_t *layLo[3], *layHi[3];
+    ExPack pack{};
+    {
+        size_t at = 0;
+        for (int a = 0; a < 3; ++a) {
+            velLo[a] = lo ? recvLo + at : nullptr;
+            velHi[a] = hi ? recvHi + at : nullptr;
+            layLo[a] = lo ? reinterpret_cast<const uint8_t *>(recvLo + entries) + at : nullptr;
+            layHi[a] = hi ? reinterpret_cast<const uint8_t *>(recvHi + entries) + at : nullptr;
+            at += size_t(count[a]);
+            pack.vel[a] = e->velocity[a];
+            pack.lay[a] = layer[a];
+            pack.count[a] = count[a];
+            // the z-face window holds the faces c0 .. c1: the neighbours have the end planes themselves
+            pack.lo[a] = lo ? (long long)(a == 2 ? 1 : 0) * count[a] : -1;
+            pack.hi[a] = hi ? (long long)(a == 2 ? nzl - 1 : nzl - 1) * count[a] : -1;
+        }
+        pack.outLo = sendLo;
+        pack.outHi = sendHi;
+    }
+    double exchangeMs = 0;
+    step(mgps_fields_slab_extrapolate_layer(&desc, 0, e->velocity, layer, e->valid_faces, nullptr, nullptr, nullptr, nullptr, cw[0] ? cw : nullptr, nullptr, st));
+    for (int l = 1; l <= L; ++l) {
+        if (P > 1) {
+            extrapolatePackKernel<<<blocks(entries), 256, 0, st>>>(pack);
+            step(done(fn));
+            const auto a = clock::now();
+            const int rc = comm->exchange(comm->user, sendLo, lo ? message : 0, recvLo, lo ? message : 0, sendHi, hi ? message : 0, recvHi, hi ? message : 0, st);
+            exchangeMs += ms(a, clock::now());
+            if (rc != 0) {
+                setLastGlobalError(std::string(fn) + ": exchange failed (layer " + std::to_string(l) + ")");
+                return MGPS_ERR_COMM;
+            }
+        }
+        if (status == MGPS_OK)
+            step(mgps_fields_slab_extrapolate_layer(&desc, l, e->velocity, layer, nullptr, velLo, velHi, layLo, layHi, cw[0] ? cw : nullptr, nullptr, st));
+    }
+    if (status == MGPS_OK) {  // the faces filled, counted once behind the layers (the cut's z-face plane by the rank above it)
+        ExArgs grids{};
+        for (int a = 0; a < 3; ++a) grids.a[a] = ExAxis{nullptr, layer[a], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gx + (a == 0), gy + (a == 1), nzl + (a == 2)};
+        const int countNz[3] = {nzl, nzl, hi ? nzl : nzl + 1};
+        step(exLaunchCount(grids, countNz, 1, 254, filled, st, fn));
+    }
+    unsigned long long mine[3] = {0, 0, 0};
+    if (status == MGPS_OK && (hipMemcpyAsync(mine, filled, sizeof(mine), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+        setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(hipGetLastError()));
+        status = MGPS_ERR_HIP;
+    }
+    double sums[3] = {double(mine[0]), double(mine[1]), double(mine[2])};
+    const int rc = agree(status, "layers", sums, 3);
+    for (int a = 0; a < 3; ++a) e->filled[a] = (unsigned long long)(sums[a]);
+    e->exchange_ms = exchangeMs;
+    e->total_ms = ms(t0, clock::now());
+    return rc;
 }
 MGPS_API_CATCH(nullptr)
 

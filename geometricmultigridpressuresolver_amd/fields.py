@@ -446,3 +446,94 @@ def project_free_surface_slab(comm, splits, global_shape, liquid_phi, solid_phi,
         e.info, e.valid_faces = info, valid
         raise
     return valid, info
+
+
+# ---- velocity extrapolation into the air band (include/mgps_fields.h) ------------------------------------------
+def _cw3(cut_cell_weights, faces):
+    """None, or the three cut-cell weight grids (a missing one stays NULL: the library refuses "some but not all")"""
+    if cut_cell_weights is None:
+        return None
+    return [_chk(c, fs, torch.float32) if c is not None else None for c, fs in zip(cut_cell_weights, faces)]
+
+
+def extrapolateVelocity(velocity, valid_faces, layers, cut_cell_weights=None):
+    """mgps_fields_extrapolate3: carries the velocity of the valid faces `layers` faces out, breadth first, in place on the three
+    face grids; with `cut_cell_weights` closed faces (weight <= 0) are left out.  Returns (layer_grids, filled): three uint8 face
+    grids (0 valid, l = filled by layer l, 255 not reached) and the number of faces filled per axis."""
+    shape = list(velocity[0].shape)
+    shape[2] -= 1
+    faces = _face3(tuple(shape))
+    v = [_chk(velocity[a], faces[a], torch.float32) for a in range(3)]
+    valid = [_chk(valid_faces[a], faces[a], torch.uint8) for a in range(3)]
+    cw = _cw3(cut_cell_weights, faces)
+    layer = [torch.empty(fs, dtype=torch.uint8, device=v[0].device) for fs in faces]
+    filled = torch.zeros(3, dtype=torch.int64, device=v[0].device)
+    check(lib().mgps_fields_extrapolate3(_arr3(v), _arr3(layer), _arr3(valid), _arr3(cw) if cw is not None else None, int(layers), *_g(shape),
+                                         _p(filled), _stream()))
+    return layer, [int(c) for c in filled.tolist()]
+
+
+def _halo3(d, halo, dtype):
+    """halo = ((lo planes[3] or None), (hi planes[3] or None)) of the three face grids -> two pointer arrays; None where the grid ends"""
+    lo, hi = halo if halo is not None else (None, None)
+    plane = [(d.gy, d.gx + 1), (d.gy + 1, d.gx), (d.gy, d.gx)]
+    for side in (lo, hi):
+        if side is not None:
+            for a in range(3):
+                _chk(side[a], plane[a], dtype)
+    assert (lo is not None) == (d.c0 > 0) and (hi is not None) == (d.c1 < d.gz), "halo planes: exactly where the grid goes on"
+    return (_arr3(lo) if lo is not None else None), (_arr3(hi) if hi is not None else None)
+
+
+def extrapolateVelocityLayerSlab(d, l, velocity, layer, valid_faces=None, velocity_halo=None, layer_halo=None, cut_cell_weights=None, filled=None):
+    """mgps_fields_slab_extrapolate_layer: layer `l` on the window `d`, in place on `velocity` and `layer` (the window's face grids);
+    l = 0 writes `layer` from `valid_faces`.  velocity_halo / layer_halo = (planes below[3] or None, planes above[3] or None): base
+    planes c0 - 1 and c1 of the x-face and y-face grids, face planes c0 - 1 and c1 + 1 of the z-face grid.  `filled`: an int64 CUDA
+    tensor of 3 counts that the pass raises, or None."""
+    faces = _face3(d.base_shape)
+    v = [_chk(velocity[a], faces[a], torch.float32) for a in range(3)]
+    lay = [_chk(layer[a], faces[a], torch.uint8) for a in range(3)]
+    valid = [_chk(valid_faces[a], faces[a], torch.uint8) for a in range(3)] if valid_faces is not None else None
+    cw = _cw3(cut_cell_weights, faces)
+    if int(l) > 0:
+        vlo, vhi = _halo3(d, velocity_halo, torch.float32)
+        llo, lhi = _halo3(d, layer_halo, torch.uint8)
+    else:
+        vlo = vhi = llo = lhi = None
+    check(lib().mgps_fields_slab_extrapolate_layer(C.byref(d), int(l), _arr3(v), _arr3(lay), _arr3(valid) if valid is not None else None, vlo, vhi, llo, lhi,
+                                                   _arr3(cw) if cw is not None else None, _p(filled), _stream()))
+    return layer
+
+
+class ExtrapolationSlab(C.Structure):
+    """mgps_extrapolation_slab (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("power_of_two", C.c_int), ("layers", C.c_int),
+        ("velocity", C.c_void_p * 3), ("valid_faces", C.c_void_p * 3), ("cut_weights", C.c_void_p * 3), ("layer", C.c_void_p * 3),
+        ("filled", C.c_ulonglong * 3), ("total_ms", C.c_double), ("exchange_ms", C.c_double),
+    ]
+
+
+def extrapolate_velocity_slab(comm, splits, global_shape, velocity, valid_faces, layers, cut_weights=None, power_of_two=True, layer=None):
+    """mgps_extrapolate_velocity_slab: the extrapolation on the CUDA tensors of this rank's window of the grid `global_shape` =
+    (gz, gy, gx), a collective over the transport `comm`; meant for the velocity and the valid_faces project_free_surface_slab
+    returned, with the same `splits`.  `velocity` is updated in place.  `layer`: three uint8 face grids of the window to write, or
+    None for new ones.  Returns {"filled": the whole grid's counts per axis, "total_ms", "exchange_ms", "layer"}."""
+    d = slab_window(global_shape, power_of_two, splits, comm.rank)
+    faces = _face3(d.base_shape)
+    ex = ExtrapolationSlab()
+    ex.struct_size = C.sizeof(ExtrapolationSlab)
+    ex.gz, ex.gy, ex.gx = global_shape
+    ex.power_of_two, ex.layers = int(bool(power_of_two)), int(layers)
+    if layer is None:
+        layer = [torch.empty(fs, dtype=torch.uint8, device=velocity[0].device) for fs in faces]
+    for a in range(3):
+        ex.velocity[a] = _chk(velocity[a], faces[a], torch.float32).data_ptr()
+        ex.valid_faces[a] = _chk(valid_faces[a], faces[a], torch.uint8).data_ptr()
+        ex.layer[a] = _chk(layer[a], faces[a], torch.uint8).data_ptr()
+        # (a missing entry stays NULL: the library refuses "some but not all" on every rank together)
+        ex.cut_weights[a] = _chk(cut_weights[a], faces[a], torch.float32).data_ptr() if cut_weights is not None and cut_weights[a] is not None else None
+    cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
+    check(lib().mgps_extrapolate_velocity_slab(C.byref(ex), C.byref(comm.struct), cuts, _stream()))
+    return {"filled": [int(ex.filled[a]) for a in range(3)], "total_ms": ex.total_ms, "exchange_ms": ex.exchange_ms, "layer": layer}

@@ -256,6 +256,59 @@ typedef struct mgps_projection_slab {
 int mgps_project_free_surface_slab(mgps_projection_slab *p, const mgps_options *opt, const mgps_comm *comm, const int *splits,
                                    void *stream);
 
+/* ---- velocity extrapolation into the air band ------------------------------------------------------------
+ * The projection leaves a velocity that is defined on valid faces only; advection needs it a few cells further out.  The passes
+ * below carry it there breadth first, layer by layer, on one face grid of axis a.  No counterpart in the reference, which hands
+ * its validFaces field to a downstream extrapolation (Plug.cpp:155-166, 711); the definition here is the contract.
+ *   layer (uint8 face grid, out): 0 where valid == 1, 255 elsewhere, written by every call (no continuation state).
+ *   For l = 1 .. layers (1 <= layers <= 254): every face f with layer[f] == 255 -- and cut_weights[f] > 0 when cut_weights is
+ *   given -- that has a KNOWN neighbour gets the mean of its known neighbours' velocities and layer[f] = l.  The neighbours are
+ *   the 6 faces -x, +x, -y, +y, -z, +z of the same face grid (one outside the grid does not exist); n is known when layer[n] < l.
+ *   The mean is a float32 sum over the known neighbours in that order, divided by their count.
+ * Every other face keeps its velocity bit for bit: valid faces, faces never reached, closed faces (never written, never known).
+ * A layer reads values of layers < l only and writes faces of layer 255 only: it runs in place, without a second velocity grid
+ * and without atomics on values, and the same inputs give the same bits whatever the order of execution. */
+int mgps_fields_extrapolate(int axis, float *velocity, uint8_t *layer, const uint8_t *valid, const float *cut_weights /* or NULL */,
+                            int layers, int gx, int gy, int gz, void *stream);
+/* the three axes with one launch per layer: the bits of three mgps_fields_extrapolate calls.  cut_weights: NULL, or all three.
+ * filled_dev (device, [3], may be NULL): the faces given a value per axis, ADDED to what the array holds (initialise it) */
+int mgps_fields_extrapolate3(float *const velocity[3], uint8_t *const layer[3], const uint8_t *const valid[3],
+                             const float *const cut_weights[3] /* or NULL */, int layers, int gx, int gy, int gz,
+                             unsigned long long *filled_dev, void *stream);
+/* One layer on a slab window, without communication.  l == 0 writes `layer` from `valid` (valid is read then, and only then);
+ * 1 <= l <= 254 computes layer l.  velocity / layer / valid / cut_weights: the window's face grids.  Halo planes as everywhere in
+ * this header for the x-face and y-face grids (base planes c0 - 1 and c1); the z-face window holds the faces c0 .. c1, so its
+ * halos are the face planes c0 - 1 and c1 + 1.  All halos of a side are NULL where the grid ends, and unused with l == 0.  The
+ * two copies of a cut's z-face plane see the same neighbours and come out with the same bits.  filled_dev (device, [3], may be
+ * NULL) is raised by the faces filled; of the z-faces the planes c0 .. c1 - 1 count, on the last rank also plane gz, so that a sum
+ * over the ranks counts every face once */
+int mgps_fields_slab_extrapolate_layer(const mgps_fields_slab *d, int l, float *const velocity[3], uint8_t *const layer[3],
+                                       const uint8_t *const valid[3], const float *const velocity_lo[3], const float *const velocity_hi[3],
+                                       const uint8_t *const layer_lo[3], const uint8_t *const layer_hi[3],
+                                       const float *const cut_weights[3] /* or NULL */, unsigned long long *filled_dev, void *stream);
+/* The extrapolation on the DEVICE fields of one slab rank, a collective over `comm`: every rank calls it with the same gx, gy,
+ * gz (the WHOLE grid), power_of_two, layers and cuts -- those of mgps_project_free_surface_slab, on whose velocity and valid_faces
+ * it is meant to run.  Per layer one `exchange` message per neighbour carries the velocity planes and the layer planes of the
+ * three axes, packed; one launch follows.  With comm->size = 1 it is the device-resident extrapolation on one GPU: no exchange and
+ * no all-reduce; gatherv / scatterv are never used.  What every rank shares (struct_size, extents, layers, the cuts) is refused at
+ * once; a rank-local failure (a missing array, an allocation) is carried by an all-reduce in front of the first exchange, a later
+ * one by the all-reduce at the end that sums `filled`: all ranks return the same status.  A rank whose transport call fails
+ * returns MGPS_ERR_COMM at once and alone, as in mgps_project_free_surface_slab. */
+typedef struct mgps_extrapolation_slab {
+    int struct_size;               /* sizeof(mgps_extrapolation_slab) */
+    int gx, gy, gz;                /* the WHOLE simulation grid */
+    int power_of_two;              /* the expansion the cuts refer to */
+    int layers;                    /* 1 .. 254 */
+    float *velocity[3];            /* the window's face grids, in/out */
+    const uint8_t *valid_faces[3]; /* what mgps_project_free_surface_slab published */
+    const float *cut_weights[3];   /* all three, or all NULL */
+    uint8_t *layer[3];             /* out; each may be NULL: not wanted */
+    /* results */
+    unsigned long long filled[3];  /* faces given a value per axis, of the whole grid: the same on every rank */
+    double total_ms, exchange_ms;  /* this rank's host wall clock: the call / inside the exchanges */
+} mgps_extrapolation_slab;
+int mgps_extrapolate_velocity_slab(mgps_extrapolation_slab *e, const mgps_comm *comm, const int *splits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
