@@ -54,15 +54,48 @@ __device__ __forceinline__ bool unflatten(int nx, int ny, int nz, int &i, int &j
     k = int(t / (size_t(nx) * ny));
     return true;
 }
-
-__global__ void materialLabelsKernel(Box g, int32_t *__restrict__ material, const float *__restrict__ phi,
-                                     const float *__restrict__ solidPhi, const float *__restrict__ cwx,
-                                     const float *__restrict__ cwy, const float *__restrict__ cwz)
+// (i, j, k) of this thread in a rowGrid(nx, ny, nz) launch: no 64-bit division for the index; i may lie past the row's end
+__device__ __forceinline__ void threadCell(int &i, int &j, int &k)
 {
-    int i, j, k;
-    if (!unflatten(g.gx, g.gy, g.gz, i, j, k)) return;
-    const float *cw[3] = {cwx, cwy, cwz};
-    const int ext[3] = {g.gx, g.gy, g.gz};
+    i = int(blockIdx.x * blockDim.x + threadIdx.x);
+    j = int(blockIdx.y);
+    k = int(blockIdx.z);
+}
+inline dim3 rowGrid(int nx, int ny, int nz) { return dim3(unsigned((nx + 255) / 256), unsigned(ny), unsigned(nz)); }
+
+// ---- the per-cell rules, each stated once for the whole-grid kernels and the slab kernels ----------
+// A rule is templated on how the value of a cell other than the thread's own is reached: `at(i, j, k)`, (i, j, k) a cell of the
+// WHOLE grid G.  The whole-grid kernels pass GridAt, which indexes the array; the slab kernels pass SlabAt (below), which goes
+// through the window and its halo planes.  A rule asks only for cells inside G, and only on the branch where it needs the value:
+// nothing is fetched that the kernel would not have fetched with the rule written out in it.
+template <class T>
+struct GridAt {
+    const Box &g;
+    const T *a;
+    __device__ __forceinline__ T operator()(int i, int j, int k) const { return a[cellAt(g, i, j, k)]; }
+};
+// the same for cells next to the thread's own cell (ci, cj, ck) = c: the index is c plus strides, no product per cell asked for
+template <class T>
+struct GridNear {
+    const Box &g;
+    const T *a;
+    size_t c;
+    int ci, cj, ck;
+    __device__ __forceinline__ T operator()(int i, int j, int k) const
+    {
+        return a[ptrdiff_t(c) + (i - ci) + ptrdiff_t(j - cj) * g.gx + ptrdiff_t(k - ck) * (ptrdiff_t(g.gx) * g.gy)];
+    }
+};
+
+// Material label of cell (i, j, k) of the box g its own arrays (phi, solidPhi, the cut weights) are indexed in -- the grid G or a
+// window of its planes -- which is cell (i, j, kg) of G.  phiAt reaches the 6-neighbours' liquid phi.  (The own arrays as pointers
+// and the face loop in here: with the cut weights and the own values handed in through a functor and references the slab kernel
+// measured 7 % slower, LABNOTES R10.)
+template <class PhiAt>
+__device__ __forceinline__ int materialLabel(const Box &G, const Box &g, int i, int j, int k, int kg, const float *phi,
+                                             const float *solidPhi, const float *const cw[3], PhiAt phiAt)
+{
+    const int ext[3] = {G.gx, G.gy, G.gz};
     const size_t c = cellAt(g, i, j, k);
     bool open[3][2], inFluid = false;
 #pragma unroll
@@ -72,94 +105,189 @@ __global__ void materialLabelsKernel(Box g, int32_t *__restrict__ material, cons
             open[a][d] = cw[a][cellFace(g, a, d, i, j, k)] > 0.f;
             inFluid = inFluid || open[a][d];
         }
-    int label = kSolid;
-    if (inFluid) {
-        bool liquid = phi[c] <= 0.f;
-        if (!liquid && solidPhi[c] >= 0.f) {
+    if (!inFluid) return kSolid;
+    bool liquid = phi[c] <= 0.f;
+    if (!liquid && solidPhi[c] >= 0.f) {
 #pragma unroll
-            for (int a = 0; a < 3; ++a)
+        for (int a = 0; a < 3; ++a)
 #pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    int n[3] = {i, j, k};
-                    n[a] += d ? 1 : -1;
-                    if (open[a][d] && n[a] >= 0 && n[a] < ext[a] && phi[cellAt(g, n[0], n[1], n[2])] <= 0.f) liquid = true;
-                }
-        }
-        label = liquid ? kLiquid : kAir;
+            for (int d = 0; d < 2; ++d) {
+                int n[3] = {i, j, kg};
+                n[a] += d ? 1 : -1;
+                if (open[a][d] && n[a] >= 0 && n[a] < ext[a] && phiAt(n[0], n[1], n[2]) <= 0.f) liquid = true;
+            }
     }
-    material[c] = label;
+    return liquid ? kLiquid : kAir;
 }
 
-__global__ void validFacesKernel(Box g, int axis, uint8_t *__restrict__ valid, const int32_t *__restrict__ material,
-                                 const float *__restrict__ cw)
+// The face of `axis` in front of cell (i, j, k) of G, cut weight cwf, is valid when it is open, has both cells in G and one is
+// LIQUID.  mb / mf: the labels of the cell behind and in front, loaded when the face is open and both cells are in G.
+template <class MatAt>
+__device__ __forceinline__ bool isValidFace(const Box &G, int axis, int i, int j, int k, float cwf, MatAt mat, int &mb, int &mf)
 {
-    int i, j, k;
-    if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), i, j, k)) return;
-    const size_t f = faceAt(g, axis, i, j, k);
-    const int ext[3] = {g.gx, g.gy, g.gz};
+    const int ext[3] = {G.gx, G.gy, G.gz};
     int b[3] = {i, j, k}, fw[3] = {i, j, k};
     b[axis] -= 1;
-    uint8_t v = 0;
-    if (cw[f] > 0.f && b[axis] >= 0 && fw[axis] < ext[axis])
-        v = material[cellAt(g, b[0], b[1], b[2])] == kLiquid || material[cellAt(g, fw[0], fw[1], fw[2])] == kLiquid;
-    valid[f] = v;
+    if (!(cwf > 0.f && b[axis] >= 0 && fw[axis] < ext[axis])) return false;
+    mb = mat(b[0], b[1], b[2]), mf = mat(fw[0], fw[1], fw[2]);
+    return mb == kLiquid || mf == kLiquid;
+}
+// Expanded weight of that face, known to be valid: the cut weight, over theta on a liquid/air face.
+template <class PhiAt>
+__device__ __forceinline__ float expandedWeight(int axis, int i, int j, int k, float cwf, int mb, int mf, PhiAt phi)
+{
+    int b[3] = {i, j, k};
+    b[axis] -= 1;
+    float w = cwf;
+    if ((mb == kLiquid && mf == kAir) || (mb == kAir && mf == kLiquid)) w /= ghostFluidTheta(phi(b[0], b[1], b[2]), phi(i, j, k));
+    return w;
 }
 
-__global__ void domainLabelsKernel(Box g, Box e, int offset, uint8_t *__restrict__ expanded, const int32_t *__restrict__ material)
+// material label -> domain label
+__device__ __forceinline__ int domainLabel(int m)
 {
-    int bi, bj, bk;  // (the base box only: the launcher has filled the expanded grid with EXTERIOR)
-    if (!unflatten(g.gx, g.gy, g.gz, bi, bj, bk)) return;
-    const int m = material[cellAt(g, bi, bj, bk)];
-    expanded[cellAt(e, bi + offset, bj + offset, bk + offset)] =
-        m == kLiquid ? MGPS_INTERIOR_CELL : m == kAir ? MGPS_DIRICHLET_CELL : MGPS_EXTERIOR_CELL;
+    return m == kLiquid ? MGPS_INTERIOR_CELL : m == kAir ? MGPS_DIRICHLET_CELL : MGPS_EXTERIOR_CELL;
 }
-
-__global__ void boundaryWeightsKernel(Box g, Box e, int offset, int axis, float *__restrict__ expanded, const float *__restrict__ cw,
-                                      const float *__restrict__ phi, const uint8_t *__restrict__ valid,
-                                      const int32_t *__restrict__ material)
+// An INTERIOR cell, (i, j, k) of the expanded box e, becomes BOUNDARY next to a DIRICHLET or EXTERIOR cell or at a face whose
+// expanded weight is not 1.  labelAcross(a, d) is the domain label of the 6-neighbour across face (a, d).
+template <class LabelAcross>
+__device__ __forceinline__ bool isBoundaryCell(const Box &e, int i, int j, int k, const float *const w[3], LabelAcross labelAcross)
 {
-    int bi, bj, bk;  // (the faces of the base box only: the launcher has zeroed the expanded face grid)
-    if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), bi, bj, bk)) return;
-    const int i = bi + offset, j = bj + offset, k = bk + offset;
-    float w = 0.f;
-    {
-        const size_t f = faceAt(g, axis, bi, bj, bk);
-        if (valid[f]) {  // a valid face has both cells inside the grid
-            int b[3] = {bi, bj, bk};
-            b[axis] -= 1;
-            const size_t cb = cellAt(g, b[0], b[1], b[2]), cf = cellAt(g, bi, bj, bk);
-            const int mb = material[cb], mf = material[cf];
-            w = cw[f];
-            if ((mb == kLiquid && mf == kAir) || (mb == kAir && mf == kLiquid)) w /= ghostFluidTheta(phi[cb], phi[cf]);
-        }
-    }
-    expanded[faceAt(e, axis, i, j, k)] = w;
-}
-
-__global__ void setBoundaryLabelsKernel(Box e, uint8_t *__restrict__ lab, const float *__restrict__ wx,
-                                        const float *__restrict__ wy, const float *__restrict__ wz)
-{
-    int i, j, k;
-    if (!unflatten(e.gx, e.gy, e.gz, i, j, k)) return;
-    const size_t c = cellAt(e, i, j, k);
-    // INTERIOR cells have all six neighbours inside the grid (the EXTERIOR shell); BOUNDARY written by another
-    // thread reads as "not DIRICHLET / EXTERIOR" just like INTERIOR, so the in-place update is race-free
-    if (lab[c] != MGPS_INTERIOR_CELL) return;
-    const float *w[3] = {wx, wy, wz};
-    const ptrdiff_t stride[3] = {1, e.gx, ptrdiff_t(e.gx) * e.gy};
     bool bnd = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
-            const uint8_t nl = lab[ptrdiff_t(c) + (d ? stride[a] : -stride[a])];
+            const int nl = labelAcross(a, d);
             bnd = bnd || nl == MGPS_DIRICHLET_CELL || nl == MGPS_EXTERIOR_CELL || w[a][cellFace(e, a, d, i, j, k)] != 1.f;
         }
-    if (bnd) lab[c] = MGPS_BOUNDARY_CELL;
+    return bnd;
+}
+
+// Cell (i, j, k) of G with label m is an interface cell: LIQUID or AIR with a 6-neighbour of the other kind (the six labels are
+// loaded together, not one after the other; an out-of-grid neighbour reads the cell itself: never `other`)
+template <class MatAt>
+__device__ __forceinline__ bool isInterfaceCell(const Box &G, int i, int j, int k, int m, MatAt mat)
+{
+    const int n[6] = {mat(i > 0 ? i - 1 : i, j, k), mat(i + 1 < G.gx ? i + 1 : i, j, k), mat(i, j > 0 ? j - 1 : j, k),
+                      mat(i, j + 1 < G.gy ? j + 1 : j, k), mat(i, j, k > 0 ? k - 1 : k), mat(i, j, k + 1 < G.gz ? k + 1 : k)};
+    const int other = m == kLiquid ? kAir : kLiquid;
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) any |= n[q] == other;
+    return (m == kLiquid || m == kAir) && any;
+}
+
+// ---- surface tension: a non-zero interface pressure p_G on liquid/air faces (DESIGN.md section 13) ------------------------
+// p_G of the liquid/air face between cells b (behind) and c (front): sp interpolated to the interface, theta measured from
+// the liquid cell.  liquidBehind tells which of the two cells is the liquid one.
+__device__ __forceinline__ float interfacePressure(float theta, bool liquidBehind, float spb, float spc)
+{
+    const float spL = liquidBehind ? spb : spc, spA = liquidBehind ? spc : spb;
+    return (1.f - theta) * spL + theta * spA;
+}
+
+// rhsC += w_f * p_G over the liquid/air faces of the LIQUID cell (i, j, k) of G, in face order a = 0..2, d = 0..1.  rhsC is the
+// cell's entry of the expanded rhs, phiC and spC its own phi and sp (references: touched only at a liquid/air face), wAcross(a, d)
+// the expanded weight of its face (a, d) (cw / theta; 0 on an invalid face).  Returns the largest |p_G| met.
+template <class WAcross, class MatAt, class RealAt>
+__device__ __forceinline__ float addSurfaceRhs(const Box &G, int i, int j, int k, const float &phiC, const float &spC, float &rhsC,
+                                               WAcross wAcross, MatAt matAt, RealAt phiAt, RealAt spAt)
+{
+    const int ext[3] = {G.gx, G.gy, G.gz};
+    float acc = rhsC, amax = 0.f;
+    bool touched = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            int n[3] = {i, j, k};
+            n[a] += d ? 1 : -1;
+            if (n[a] < 0 || n[a] >= ext[a]) continue;
+            if (matAt(n[0], n[1], n[2]) != kAir) continue;
+            const float wf = wAcross(a, d);
+            if (wf == 0.f) continue;  // not a valid face
+            const float phc = phiC, phn = phiAt(n[0], n[1], n[2]);
+            const float spc = spC, spn = spAt(n[0], n[1], n[2]);
+            // b / c of the face: the neighbour is behind for d = 0
+            const float theta = d ? ghostFluidTheta(phc, phn) : ghostFluidTheta(phn, phc);
+            const float pg = interfacePressure(theta, d == 1, d ? spc : spn, d ? spn : spc);
+            acc += wf * pg;
+            amax = fmaxf(amax, fabsf(pg));
+            touched = true;
+        }
+    if (touched) rhsC = acc;
+    return amax;
+}
+// pGammaMax (may be NULL) is raised to the largest amax of the wave, as float bits: non-negative floats order like their bits.
+// Every lane of the wave calls it.
+__device__ __forceinline__ void raisePGammaMax(unsigned *pGammaMax, float amax)
+{
+    if (!pGammaMax) return;
+    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
+    if ((threadIdx.x & 63) == 0 && amax > 0.f) atomicMax(pGammaMax, __float_as_uint(amax));
+}
+
+// Pressure gradient across the valid face of `axis` in front of cell (i, j, k) of G (a valid face has both cells in G): the
+// difference, over theta unless the face is liquid/liquid (Plug.cpp:1086-1087).  With `surface` the air cell's value on a
+// liquid/air face is p_G first.  phi and sp are fetched only on a face that is not liquid/liquid.
+template <class MatAt, class RealAt>
+__device__ __forceinline__ float faceGradient(int axis, int i, int j, int k, bool surface, MatAt mat, RealAt pr, RealAt phi, RealAt sp)
+{
+    int b[3] = {i, j, k};
+    b[axis] -= 1;
+    const bool lb = mat(b[0], b[1], b[2]) == kLiquid, lf = mat(i, j, k) == kLiquid;
+    float pb = pr(b[0], b[1], b[2]), pf = pr(i, j, k);
+    float grad;
+    if (lb && lf) grad = pf - pb;
+    else {  // a valid face that is not liquid/liquid is liquid/air
+        const float theta = ghostFluidTheta(phi(b[0], b[1], b[2]), phi(i, j, k));
+        if (surface) {
+            const float pg = interfacePressure(theta, lb, sp(b[0], b[1], b[2]), sp(i, j, k));
+            if (lb) pf = pg;
+            else pb = pg;
+        }
+        grad = (pf - pb) / theta;
+    }
+    return grad;
+}
+
+// scale * clamp(kappa, -1, 1) of the cell (i, j, k): the 19-point curvature from `at(x, y, z)`, the neighbour indices already
+// clamped into the grid.
+template <class At>
+__device__ __forceinline__ float surfacePressureAt(At at, double scale, int i, int im, int ip, int j, int jm, int jp, int k, int km, int kp)
+{
+    const double p0 = at(i, j, k);
+    const double pxm = at(im, j, k), pxp = at(ip, j, k), pym = at(i, jm, k), pyp = at(i, jp, k), pzm = at(i, j, km), pzp = at(i, j, kp);
+    const double fx = 0.5 * (pxp - pxm), fy = 0.5 * (pyp - pym), fz = 0.5 * (pzp - pzm);
+    const double fxx = pxp - 2.0 * p0 + pxm, fyy = pyp - 2.0 * p0 + pym, fzz = pzp - 2.0 * p0 + pzm;
+    const double fxy = 0.25 * (at(ip, jp, k) - at(ip, jm, k) - at(im, jp, k) + at(im, jm, k));
+    const double fxz = 0.25 * (at(ip, j, kp) - at(ip, j, km) - at(im, j, kp) + at(im, j, km));
+    const double fyz = 0.25 * (at(i, jp, kp) - at(i, jp, km) - at(i, jm, kp) + at(i, jm, km));
+    const double gx2 = fx * fx, gy2 = fy * fy, gz2 = fz * fz, g2 = gx2 + gy2 + gz2;
+    double kappa = 0.0;
+    if (g2 >= 1e-30) {
+        const double num = fxx * (gy2 + gz2) + fyy * (gx2 + gz2) + fzz * (gx2 + gy2) - 2.0 * fx * fy * fxy - 2.0 * fx * fz * fxz -
+                           2.0 * fy * fz * fyz;
+        kappa = num / (g2 * sqrt(g2));
+    }
+    kappa = fmin(fmax(kappa, -1.0), 1.0);
+    return float(scale * kappa);
+}
+// sp of cell (i, j, k) of G with label m: scale * clamp(kappa, -1, 1) at an interface cell, 0 elsewhere.  kappa is the mean
+// curvature div(grad phi / |grad phi|) from unit-spacing central differences (19 points, indices clamped into the grid),
+// evaluated in double: only interface cells do it, and they are a thin shell.
+template <class MatAt, class PhiAt>
+__device__ __forceinline__ float surfacePressure(const Box &G, int i, int j, int k, int m, double scale, MatAt mat, PhiAt phi)
+{
+    if (!isInterfaceCell(G, i, j, k, m, mat)) return 0.f;
+    const int im = max(i - 1, 0), ip = min(i + 1, G.gx - 1), jm = max(j - 1, 0), jp = min(j + 1, G.gy - 1), km = max(k - 1, 0),
+              kp = min(k + 1, G.gz - 1);
+    return surfacePressureAt([&](int x, int y, int z) { return double(phi(x, y, z)); }, scale, i, im, ip, j, jm, jp, k, km, kp);
 }
 
 // weighted divergence of a LIQUID cell; signBackward = +1 gives the right-hand side (Plug.cpp:912), -1 the
-// divergence report (Plug.cpp:1180)
+// divergence report (Plug.cpp:1180).  It reads the cell's own faces only, so a window is a box of its own here.
 __device__ __forceinline__ float cellDivergence(const Box &g, int i, int j, int k, float signBackward, const float *const v[3],
                                                 const float *const sv[3], const float *const cw[3])
 {
@@ -174,6 +302,66 @@ __device__ __forceinline__ float cellDivergence(const Box &g, int i, int j, int 
             if (sv[a] && w < 1.f) div += sign * (1.f - w) * sv[a][f];
         }
     return div;
+}
+
+// ---- the whole-grid passes --------------------------------------------------------------------------------------------
+__global__ void materialLabelsKernel(Box g, int32_t *__restrict__ material, const float *__restrict__ phi,
+                                     const float *__restrict__ solidPhi, const float *__restrict__ cwx,
+                                     const float *__restrict__ cwy, const float *__restrict__ cwz)
+{
+    int i, j, k;
+    if (!unflatten(g.gx, g.gy, g.gz, i, j, k)) return;
+    const float *cw[3] = {cwx, cwy, cwz};
+    material[cellAt(g, i, j, k)] = materialLabel(g, g, i, j, k, k, phi, solidPhi, cw, GridAt<float>{g, phi});
+}
+
+__global__ void validFacesKernel(Box g, int axis, uint8_t *__restrict__ valid, const int32_t *__restrict__ material,
+                                 const float *__restrict__ cw)
+{
+    int i, j, k;
+    if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), i, j, k)) return;
+    const size_t f = faceAt(g, axis, i, j, k);
+    int mb, mf;
+    valid[f] = isValidFace(g, axis, i, j, k, cw[f], GridAt<int32_t>{g, material}, mb, mf);
+}
+
+__global__ void domainLabelsKernel(Box g, Box e, int offset, uint8_t *__restrict__ expanded, const int32_t *__restrict__ material)
+{
+    int bi, bj, bk;  // (the base box only: the launcher has filled the expanded grid with EXTERIOR)
+    if (!unflatten(g.gx, g.gy, g.gz, bi, bj, bk)) return;
+    expanded[cellAt(e, bi + offset, bj + offset, bk + offset)] = domainLabel(material[cellAt(g, bi, bj, bk)]);
+}
+
+__global__ void boundaryWeightsKernel(Box g, Box e, int offset, int axis, float *__restrict__ expanded, const float *__restrict__ cw,
+                                      const float *__restrict__ phi, const uint8_t *__restrict__ valid,
+                                      const int32_t *__restrict__ material)
+{
+    int bi, bj, bk;  // (the faces of the base box only: the launcher has zeroed the expanded face grid)
+    if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), bi, bj, bk)) return;
+    const size_t f = faceAt(g, axis, bi, bj, bk);
+    float w = 0.f;
+    if (valid[f]) {  // a valid face has both cells inside the grid
+        const GridAt<int32_t> mat{g, material};
+        int b[3] = {bi, bj, bk};
+        b[axis] -= 1;
+        w = expandedWeight(axis, bi, bj, bk, cw[f], mat(b[0], b[1], b[2]), mat(bi, bj, bk), GridAt<float>{g, phi});
+    }
+    expanded[faceAt(e, axis, bi + offset, bj + offset, bk + offset)] = w;
+}
+
+__global__ void setBoundaryLabelsKernel(Box e, uint8_t *__restrict__ lab, const float *__restrict__ wx,
+                                        const float *__restrict__ wy, const float *__restrict__ wz)
+{
+    int i, j, k;
+    if (!unflatten(e.gx, e.gy, e.gz, i, j, k)) return;
+    const size_t c = cellAt(e, i, j, k);
+    // INTERIOR cells have all six neighbours inside the grid (the EXTERIOR shell); BOUNDARY written by another
+    // thread reads as "not DIRICHLET / EXTERIOR" just like INTERIOR, so the in-place update is race-free
+    if (lab[c] != MGPS_INTERIOR_CELL) return;
+    const float *w[3] = {wx, wy, wz};
+    const ptrdiff_t stride[3] = {1, e.gx, ptrdiff_t(e.gx) * e.gy};
+    if (isBoundaryCell(e, i, j, k, w, [&](int a, int d) { return int(lab[ptrdiff_t(c) + (d ? stride[a] : -stride[a])]); }))
+        lab[c] = MGPS_BOUNDARY_CELL;
 }
 
 __global__ void rhsKernel(Box g, Box e, int offset, float *__restrict__ rhs, const int32_t *__restrict__ material, const float *vx,
@@ -205,6 +393,7 @@ __global__ void solutionToPressureKernel(Box g, Box e, int offset, float *__rest
     if (material[c] == kLiquid) pressure[c] = x[cellAt(e, i + offset, j + offset, k + offset)];
 }
 
+// velocity -= the pressure gradient on the valid faces of `axis`
 __global__ void pressureGradientKernel(Box g, int axis, float *__restrict__ velocity, const float *__restrict__ phi,
                                        const float *__restrict__ pressure, const uint8_t *__restrict__ valid,
                                        const int32_t *__restrict__ material)
@@ -212,135 +401,12 @@ __global__ void pressureGradientKernel(Box g, int axis, float *__restrict__ velo
     int i, j, k;
     if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), i, j, k)) return;
     const size_t f = faceAt(g, axis, i, j, k);
-    if (!valid[f]) return;  // valid faces have both cells inside the grid (Plug.cpp:1086-1087 never skips one)
-    int b[3] = {i, j, k};
-    b[axis] -= 1;
-    const size_t cb = cellAt(g, b[0], b[1], b[2]), cf = cellAt(g, i, j, k);
-    float grad = pressure[cf] - pressure[cb];
-    if (material[cb] != kLiquid || material[cf] != kLiquid) grad /= ghostFluidTheta(phi[cb], phi[cf]);
-    velocity[f] -= grad;
+    if (!valid[f]) return;
+    velocity[f] -= faceGradient(axis, i, j, k, false, GridAt<int32_t>{g, material}, GridAt<float>{g, pressure}, GridAt<float>{g, phi},
+                                GridAt<float>{g, nullptr});
 }
-
-// ---- surface tension: a non-zero interface pressure p_G on liquid/air faces (DESIGN.md section 13) ------------------------
-// p_G of the liquid/air face between cells b (behind) and c (front): sp interpolated to the interface, theta measured from
-// the liquid cell.  liquidBehind tells which of the two cells is the liquid one.
-__device__ __forceinline__ float interfacePressure(float theta, bool liquidBehind, float spb, float spc)
-{
-    const float spL = liquidBehind ? spb : spc, spA = liquidBehind ? spc : spb;
-    return (1.f - theta) * spL + theta * spA;
-}
-
-// (i, j, k) of this thread in a (ceil(gx / 256), gy, gz) launch: no 64-bit division for the index; false past the row's end
-__device__ __forceinline__ bool cellOfThread(const Box &g, int &i, int &j, int &k)
-{
-    i = int(blockIdx.x * blockDim.x + threadIdx.x);
-    j = int(blockIdx.y);
-    k = int(blockIdx.z);
-    return i < g.gx;
-}
-// LIQUID or AIR cell with a 6-neighbour of the other kind (the six labels are loaded together, not one after the other)
-__device__ __forceinline__ bool isInterfaceCell(const Box &g, const int32_t *__restrict__ material, int i, int j, int k, int m)
-{
-    const size_t c = cellAt(g, i, j, k), sy = size_t(g.gx), sz = size_t(g.gx) * g.gy;
-    const int n[6] = {material[i > 0 ? c - 1 : c], material[i + 1 < g.gx ? c + 1 : c], material[j > 0 ? c - sy : c],
-                      material[j + 1 < g.gy ? c + sy : c], material[k > 0 ? c - sz : c], material[k + 1 < g.gz ? c + sz : c]};
-    const int other = m == kLiquid ? kAir : kLiquid;
-    bool any = false;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) any |= n[q] == other;  // (an out-of-grid neighbour reads the cell itself: never `other`)
-    return (m == kLiquid || m == kAir) && any;
-}
-inline dim3 cellGrid(int gx, int gy, int gz) { return dim3(unsigned((gx + 255) / 256), unsigned(gy), unsigned(gz)); }
-
-// scale * clamp(kappa, -1, 1) of the cell (i, j, k): the 19-point curvature from `at(x, y, z)`, the neighbour indices already
-// clamped into the grid.  Shared by the whole-grid pass and the slab pass, which differ in how `at` finds a plane.
-template <class At>
-__device__ __forceinline__ float surfacePressureAt(At at, double scale, int i, int im, int ip, int j, int jm, int jp, int k, int km, int kp)
-{
-    const double p0 = at(i, j, k);
-    const double pxm = at(im, j, k), pxp = at(ip, j, k), pym = at(i, jm, k), pyp = at(i, jp, k), pzm = at(i, j, km), pzp = at(i, j, kp);
-    const double fx = 0.5 * (pxp - pxm), fy = 0.5 * (pyp - pym), fz = 0.5 * (pzp - pzm);
-    const double fxx = pxp - 2.0 * p0 + pxm, fyy = pyp - 2.0 * p0 + pym, fzz = pzp - 2.0 * p0 + pzm;
-    const double fxy = 0.25 * (at(ip, jp, k) - at(ip, jm, k) - at(im, jp, k) + at(im, jm, k));
-    const double fxz = 0.25 * (at(ip, j, kp) - at(ip, j, km) - at(im, j, kp) + at(im, j, km));
-    const double fyz = 0.25 * (at(i, jp, kp) - at(i, jp, km) - at(i, jm, kp) + at(i, jm, km));
-    const double gx2 = fx * fx, gy2 = fy * fy, gz2 = fz * fz, g2 = gx2 + gy2 + gz2;
-    double kappa = 0.0;
-    if (g2 >= 1e-30) {
-        const double num = fxx * (gy2 + gz2) + fyy * (gx2 + gz2) + fzz * (gx2 + gy2) - 2.0 * fx * fy * fxy - 2.0 * fx * fz * fxz -
-                           2.0 * fy * fz * fyz;
-        kappa = num / (g2 * sqrt(g2));
-    }
-    kappa = fmin(fmax(kappa, -1.0), 1.0);
-    return float(scale * kappa);
-}
-
-// sp = scale * clamp(kappa, -1, 1) at every LIQUID or AIR cell with a 6-neighbour of the other kind, 0 elsewhere.  kappa is the
-// mean curvature div(grad phi / |grad phi|) from unit-spacing central differences (19 points, indices clamped into the grid),
-// evaluated in double: only interface cells do it, and they are a thin shell.
-__global__ __launch_bounds__(256) void surfacePressureKernel(Box g, float *__restrict__ sp, const float *__restrict__ phi,
-                                                             const int32_t *__restrict__ material, double scale)
-{
-    int i, j, k;
-    if (!cellOfThread(g, i, j, k)) return;
-    const size_t c = cellAt(g, i, j, k);
-    float out = 0.f;
-    if (isInterfaceCell(g, material, i, j, k, material[c])) {
-        const int im = max(i - 1, 0), ip = min(i + 1, g.gx - 1), jm = max(j - 1, 0), jp = min(j + 1, g.gy - 1), km = max(k - 1, 0),
-                  kp = min(k + 1, g.gz - 1);
-        auto at = [&](int x, int y, int z) { return double(phi[cellAt(g, x, y, z)]); };
-        out = surfacePressureAt(at, scale, i, im, ip, j, jm, jp, k, km, kp);
-    }
-    sp[c] = out;
-}
-
-// rhs[L] += w_f * p_G over the liquid/air faces of every LIQUID cell L, in face order a = 0..2, d = 0..1, on top of the rhs
-// already in the expanded grid.  w_f is the expanded weight boundaryWeightsKernel wrote (cw / theta; 0 on an invalid face).
-// pGammaMax (may be NULL) is raised to the largest |p_G| met, as float bits: non-negative floats order like their bits.
-__global__ __launch_bounds__(256) void rhsSurfaceKernel(Box g, Box e, int offset, float *__restrict__ rhs, const float *wx,
-                                                        const float *wy, const float *wz, const float *__restrict__ phi,
-                                                        const int32_t *__restrict__ material, const float *__restrict__ sp,
-                                                        unsigned *__restrict__ pGammaMax)
-{
-    int bi, bj, bk;
-    float amax = 0.f;
-    // (no early return: every lane reaches the wave reduction below)
-    const bool inside = cellOfThread(g, bi, bj, bk);
-    const size_t c = inside ? cellAt(g, bi, bj, bk) : 0;
-    const int m = inside ? material[c] : kSolid;
-    if (inside && isInterfaceCell(g, material, bi, bj, bk, m) && m == kLiquid) {  // (the seven labels load together)
-        const float *w[3] = {wx, wy, wz};
-        const int ext[3] = {g.gx, g.gy, g.gz};
-        const int ei = bi + offset, ej = bj + offset, ek = bk + offset;
-        const size_t ec = cellAt(e, ei, ej, ek);
-        float acc = rhs[ec];
-        bool touched = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                int n[3] = {bi, bj, bk};
-                n[a] += d ? 1 : -1;
-                if (n[a] < 0 || n[a] >= ext[a]) continue;
-                const size_t cn = cellAt(g, n[0], n[1], n[2]);
-                if (material[cn] != kAir) continue;
-                const float wf = w[a][cellFace(e, a, d, ei, ej, ek)];
-                if (wf == 0.f) continue;  // not a valid face
-                // b / c of the face: the neighbour is behind for d = 0
-                const float theta = d ? ghostFluidTheta(phi[c], phi[cn]) : ghostFluidTheta(phi[cn], phi[c]);
-                const float pg = interfacePressure(theta, d == 1, d ? sp[c] : sp[cn], d ? sp[cn] : sp[c]);
-                acc += wf * pg;
-                amax = fmaxf(amax, fabsf(pg));
-                touched = true;
-            }
-        if (touched) rhs[ec] = acc;
-    }
-    if (!pGammaMax) return;
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if ((threadIdx.x & 63) == 0 && amax > 0.f) atomicMax(pGammaMax, __float_as_uint(amax));
-}
-
-// pressureGradientKernel with the air cell's value on a liquid/air face replaced by p_G
+// ... with the air cell's value on a liquid/air face replaced by p_G.  faceGradient's rule written out: through the shared
+// function this pass measured 0.4-0.5 % slower than before at 480^3, twice, beyond the run's noise (LABNOTES R10)
 __global__ __launch_bounds__(256) void pressureGradientSurfaceKernel(Box g, int axis, float *__restrict__ velocity,
                                                                      const float *__restrict__ phi, const float *__restrict__ pressure,
                                                                      const float *__restrict__ sp, const uint8_t *__restrict__ valid,
@@ -364,6 +430,39 @@ __global__ __launch_bounds__(256) void pressureGradientSurfaceKernel(Box g, int 
         grad = (pf - pb) / theta;
     }
     velocity[f] -= grad;
+}
+
+__global__ __launch_bounds__(256) void surfacePressureKernel(Box g, float *__restrict__ sp, const float *__restrict__ phi,
+                                                             const int32_t *__restrict__ material, double scale)
+{
+    int i, j, k;
+    threadCell(i, j, k);
+    if (i >= g.gx) return;
+    const size_t c = cellAt(g, i, j, k);
+    sp[c] = surfacePressure(g, i, j, k, material[c], scale, GridNear<int32_t>{g, material, c, i, j, k}, GridAt<float>{g, phi});
+}
+
+// the surface term on top of the rhs already in the expanded grid (addSurfaceRhs), with the weights boundaryWeightsKernel wrote
+__global__ __launch_bounds__(256) void rhsSurfaceKernel(Box g, Box e, int offset, float *__restrict__ rhs, const float *wx,
+                                                        const float *wy, const float *wz, const float *__restrict__ phi,
+                                                        const int32_t *__restrict__ material, const float *__restrict__ sp,
+                                                        unsigned *__restrict__ pGammaMax)
+{
+    int bi, bj, bk;
+    threadCell(bi, bj, bk);
+    float amax = 0.f;
+    // (no early return: every lane reaches the wave reduction below)
+    const bool inside = bi < g.gx;
+    const size_t c = inside ? cellAt(g, bi, bj, bk) : 0;
+    const int m = inside ? material[c] : kSolid;
+    if (inside && isInterfaceCell(g, bi, bj, bk, m, GridNear<int32_t>{g, material, c, bi, bj, bk}) && m == kLiquid) {  // (the seven labels load together)
+        const float *w[3] = {wx, wy, wz};
+        const int ei = bi + offset, ej = bj + offset, ek = bk + offset;
+        auto wAcross = [&](int a, int d) { return w[a][cellFace(e, a, d, ei, ej, ek)]; };
+        amax = addSurfaceRhs(g, bi, bj, bk, phi[c], sp[c], rhs[cellAt(e, ei, ej, ek)], wAcross, GridAt<int32_t>{g, material}, GridAt<float>{g, phi},
+                             GridAt<float>{g, sp});
+    }
+    raisePGammaMax(pGammaMax, amax);
 }
 
 constexpr int kDivBlocks = 1024;
@@ -417,7 +516,7 @@ int done(const char *what)
 }
 inline unsigned blocks(size_t n) { return unsigned((n + 255) / 256); }
 inline bool okBox(int x, int y, int z) { return x > 0 && y > 0 && z > 0; }
-inline bool okCellGrid(int y, int z) { return y <= 65535 && z <= 65535; }  // cellGrid: y and z extents are launch-grid dimensions
+inline bool okCellGrid(int y, int z) { return y <= 65535 && z <= 65535; }  // rowGrid: y and z extents are launch-grid dimensions
 inline bool okExpanded(int gx, int gy, int gz, int ex, int ey, int ez, int off)
 {
     return okBox(ex, ey, ez) && off >= 0 && gx + off <= ex && gy + off <= ey && gz + off <= ez;
@@ -544,7 +643,7 @@ int mgps_fields_surface_pressure(float *sp, const float *liquid_phi, const int32
 try {
     if (!sp || !liquid_phi || !material || !okBox(gx, gy, gz) || !okCellGrid(gy, gz)) return bad("mgps_fields_surface_pressure");
     const Box g{gx, gy, gz};
-    surfacePressureKernel<<<cellGrid(gx, gy, gz), 256, 0, static_cast<hipStream_t>(stream)>>>(g, sp, liquid_phi, material, scale);
+    surfacePressureKernel<<<rowGrid(gx, gy, gz), 256, 0, static_cast<hipStream_t>(stream)>>>(g, sp, liquid_phi, material, scale);
     return done("mgps_fields_surface_pressure");
 }
 MGPS_API_CATCH(nullptr)
@@ -557,7 +656,7 @@ try {
         !okExpanded(gx, gy, gz, ex, ey, ez, offset))
         return bad("mgps_fields_rhs_surface");
     const Box g{gx, gy, gz}, e{ex, ey, ez};
-    rhsSurfaceKernel<<<cellGrid(gx, gy, gz), 256, 0, static_cast<hipStream_t>(stream)>>>(g, e, offset, expanded_rhs, wx, wy, wz, liquid_phi,
+    rhsSurfaceKernel<<<rowGrid(gx, gy, gz), 256, 0, static_cast<hipStream_t>(stream)>>>(g, e, offset, expanded_rhs, wx, wy, wz, liquid_phi,
                                                                                        material, sp, reinterpret_cast<unsigned *>(p_gamma_max));
     return done("mgps_fields_rhs_surface");
 }
@@ -654,6 +753,67 @@ struct DevPool {
     }
 };
 size_t faceCount(int gx, int gy, int gz, int axis) { return size_t(gx + (axis == 0)) * (gy + (axis == 1)) * (gz + (axis == 2)); }
+
+// ---- what mgps_project_free_surface and mgps_project_free_surface_slab check and prepare alike (P: their structs) ------------
+// The caller's fields and the surface-tension block, before any device is touched.  `fn` is the entry point's name, the prefix of its
+// messages; `shapeOk` and `missing` carry what only one of the two has to check about extents.
+template <class P>
+int checkProjectionFields(const P *p, const char *fn, bool shapeOk, const char *missing)
+{
+    auto refuse = [fn](const std::string &what) {
+        setLastGlobalError(std::string(fn) + ": " + what);
+        return int(MGPS_ERR_INVALID_ARGUMENT);
+    };
+    bool ok = shapeOk && p->liquid_phi && p->solid_phi && p->pressure;
+    for (int a = 0; a < 3; ++a) ok = ok && p->cut_weights[a] && p->velocity[a];
+    const bool haveSolidVel = p->solid_velocity[0] && p->solid_velocity[1] && p->solid_velocity[2];
+    if (!ok || (!haveSolidVel && (p->solid_velocity[0] || p->solid_velocity[1] || p->solid_velocity[2])))
+        return refuse(std::string(missing) + " (solid velocities: all three or none)");
+    // surface tension: dt, dx and density are read only with surface_tension > 0
+    const double sigma = p->surface_tension;
+    if (!std::isfinite(sigma) || sigma < 0) return refuse("surface_tension must be finite and >= 0");
+    if (sigma > 0) {
+        const char *what = !(std::isfinite(p->dt) && p->dt > 0) ? "dt" : !(std::isfinite(p->dx) && p->dx > 0) ? "dx"
+                         : !(std::isfinite(p->density) && p->density > 0) ? "density" : nullptr;
+        if (what) return refuse(std::string("surface_tension > 0 needs a finite ") + what + " > 0");
+        if (p->surface_pressure) return refuse("surface_tension and surface_pressure are both set (pass one of them)");
+    }
+    return MGPS_OK;
+}
+// o = the caller's options, or the defaults; `prefix` goes in front of the refusal
+int readOptions(const mgps_options *opt, mgps_options &o, const char *prefix)
+{
+    mgps_default_options(&o);
+    if (!opt) return MGPS_OK;
+    if (opt->struct_size != int(sizeof(mgps_options))) {
+        setLastGlobalError(std::string(prefix) + "mgps_options.struct_size mismatch: call mgps_default_options first");
+        return MGPS_ERR_INVALID_ARGUMENT;
+    }
+    o = *opt;
+    return MGPS_OK;
+}
+int selectDevice(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        setLastGlobalError("no HIP device is visible (this library has no CPU path)");
+        return MGPS_ERR_NO_DEVICE;
+    }
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) {
+        setLastGlobalError("hipSetDevice failed");
+        return MGPS_ERR_NO_DEVICE;
+    }
+    return MGPS_OK;
+}
+// what a call reports about its solve, before there is one
+template <class P>
+void clearReport(P *p)
+{
+    std::memset(&p->stats, 0, sizeof(p->stats));
+    p->residual_inf = p->residual_l2 = p->divergence_sum = p->divergence_max = 0;
+    p->enclosed_components = 0;
+    p->rhs_mean_removed_max = p->surface_pressure_max = 0;
+}
 }  // namespace
 
 extern "C" {
@@ -667,50 +827,16 @@ try {
         return MGPS_ERR_INVALID_ARGUMENT;
     }
     const int gx = p->gx, gy = p->gy, gz = p->gz;
-    bool ok = gx > 0 && gy > 0 && gz > 0 && (p->real_bytes == 4 || p->real_bytes == 8) && p->liquid_phi && p->solid_phi && p->pressure;
-    for (int a = 0; a < 3; ++a) ok = ok && p->cut_weights[a] && p->velocity[a];
-    const bool haveSolidVel = p->solid_velocity[0] && p->solid_velocity[1] && p->solid_velocity[2];
-    if (!ok || (!haveSolidVel && (p->solid_velocity[0] || p->solid_velocity[1] || p->solid_velocity[2]))) {
-        setLastGlobalError("mgps_project_free_surface: missing field or bad extents (solid velocities: all three or none)");
-        return MGPS_ERR_INVALID_ARGUMENT;
-    }
-    // surface tension: dt, dx and density are read only with surface_tension > 0
+    if (int rc = checkProjectionFields(p, "mgps_project_free_surface", gx > 0 && gy > 0 && gz > 0 && (p->real_bytes == 4 || p->real_bytes == 8),
+                                       "missing field or bad extents");
+        rc != MGPS_OK)
+        return rc;
+    const bool haveSolidVel = p->solid_velocity[0] != nullptr;  // (all three or none)
     const double sigma = p->surface_tension;
-    if (!std::isfinite(sigma) || sigma < 0) {
-        setLastGlobalError("mgps_project_free_surface: surface_tension must be finite and >= 0");
-        return MGPS_ERR_INVALID_ARGUMENT;
-    }
-    if (sigma > 0) {
-        const char *what = !(std::isfinite(p->dt) && p->dt > 0) ? "dt" : !(std::isfinite(p->dx) && p->dx > 0) ? "dx"
-                         : !(std::isfinite(p->density) && p->density > 0) ? "density" : nullptr;
-        if (what) {
-            setLastGlobalError(std::string("mgps_project_free_surface: surface_tension > 0 needs a finite ") + what + " > 0");
-            return MGPS_ERR_INVALID_ARGUMENT;
-        }
-        if (p->surface_pressure) {
-            setLastGlobalError("mgps_project_free_surface: surface_tension and surface_pressure are both set (pass one of them)");
-            return MGPS_ERR_INVALID_ARGUMENT;
-        }
-    }
     const bool surface = sigma > 0 || p->surface_pressure;
     mgps_options o;
-    mgps_default_options(&o);
-    if (opt) {
-        if (opt->struct_size != int(sizeof(mgps_options))) {
-            setLastGlobalError("mgps_options.struct_size mismatch: call mgps_default_options first");
-            return MGPS_ERR_INVALID_ARGUMENT;
-        }
-        o = *opt;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        setLastGlobalError("no HIP device is visible (this library has no CPU path)");
-        return MGPS_ERR_NO_DEVICE;
-    }
-    if (o.device >= 0 && hipSetDevice(o.device) != hipSuccess) {
-        setLastGlobalError("hipSetDevice failed");
-        return MGPS_ERR_NO_DEVICE;
-    }
+    if (int rc = readOptions(opt, o, ""); rc != MGPS_OK) return rc;
+    if (int rc = selectDevice(o.device); rc != MGPS_OK) return rc;
     hipStream_t s = nullptr;
     DevPool pool;
     const size_t cells = size_t(gx) * gy * gz;
@@ -820,11 +946,7 @@ try {
         div[2] = double(liquid);
     }
     p->liquid_cells = div[2];
-    std::memset(&p->stats, 0, sizeof(p->stats));
-    p->residual_inf = p->residual_l2 = p->divergence_sum = p->divergence_max = 0;
-    p->enclosed_components = 0;
-    p->rhs_mean_removed_max = 0;
-    p->surface_pressure_max = 0;
+    clearReport(p);
     if (div[2] == 0) {
         if (copy.s && (he = hipStreamSynchronize(copy.s)) != hipSuccess) return failHip("upload", he);
         if ((he = hipMemsetAsync(pressure, 0, cells * sizeof(float), s)) != hipSuccess) return failHip("pressure clear", he);
@@ -927,6 +1049,7 @@ MGPS_API_CATCH(nullptr)
 namespace {
 struct Slab {
     int gx, gy, gz, c0, c1, ex, ey, ez, off, e0, e1;
+    __host__ __device__ Box whole() const { return Box{gx, gy, gz}; }        // the base grid
     __host__ __device__ Box base() const { return Box{gx, gy, c1 - c0}; }    // the window of the base grid
     __host__ __device__ Box window() const { return Box{ex, ey, e1 - e0}; }  // the window of the expanded grid
 };
@@ -944,12 +1067,13 @@ __device__ __forceinline__ T zAt(const Slab &s, const Planes<T> &p, int i, int j
     if (kg >= s.c1) return p.hi[ij];
     return p.own[size_t(kg - s.c0) * s.gy * s.gx + ij];
 }
-__device__ __forceinline__ void threadCell(int &i, int &j, int &k)
-{
-    i = int(blockIdx.x * blockDim.x + threadIdx.x);
-    j = int(blockIdx.y);
-    k = int(blockIdx.z);
-}
+// how the slab kernels hand a grid to a rule (GridAt's counterpart)
+template <class T>
+struct SlabAt {
+    const Slab &s;
+    const Planes<T> &p;
+    __device__ __forceinline__ T operator()(int i, int j, int kg) const { return zAt(s, p, i, j, kg); }
+};
 
 __global__ __launch_bounds__(256) void materialLabelsSlabKernel(Slab s, int32_t *__restrict__ material, Planes<float> phi,
                                                                 const float *__restrict__ solidPhi, const float *__restrict__ cwx,
@@ -960,59 +1084,20 @@ __global__ __launch_bounds__(256) void materialLabelsSlabKernel(Slab s, int32_t 
     if (i >= s.gx) return;
     const Box g = s.base();
     const float *cw[3] = {cwx, cwy, cwz};
-    const int ext[3] = {s.gx, s.gy, s.gz};
-    const int kg = s.c0 + k;
-    const size_t c = cellAt(g, i, j, k);
-    bool open[3][2], inFluid = false;
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            open[a][d] = cw[a][cellFace(g, a, d, i, j, k)] > 0.f;
-            inFluid = inFluid || open[a][d];
-        }
-    int label = kSolid;
-    if (inFluid) {
-        bool liquid = phi.own[c] <= 0.f;
-        if (!liquid && solidPhi[c] >= 0.f) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    int n[3] = {i, j, kg};
-                    n[a] += d ? 1 : -1;
-                    if (open[a][d] && n[a] >= 0 && n[a] < ext[a] && zAt(s, phi, n[0], n[1], n[2]) <= 0.f) liquid = true;
-                }
-        }
-        label = liquid ? kLiquid : kAir;
-    }
-    material[c] = label;
+    material[cellAt(g, i, j, k)] = materialLabel(s.whole(), g, i, j, k, s.c0 + k, phi.own, solidPhi, cw, SlabAt<float>{s, phi});
 }
 
-// valid flag and expanded weight of the base face of `axis` in front of base cell (bi, bj, bkg): validFacesKernel +
-// boundaryWeightsKernel on one face
+// valid flag and expanded weight of the base face of `axis` in front of base cell (bi, bj, bkg)
 __device__ __forceinline__ float faceWeight(const Slab &s, int axis, int bi, int bj, int bkg, float cwf, const Planes<int32_t> &mat,
                                             const Planes<float> &phi, uint8_t &valid)
 {
-    const int ext[3] = {s.gx, s.gy, s.gz};
-    int b[3] = {bi, bj, bkg}, f[3] = {bi, bj, bkg};
-    b[axis] -= 1;
-    valid = 0;
-    float w = 0.f;
-    if (cwf > 0.f && b[axis] >= 0 && f[axis] < ext[axis]) {
-        const int mb = zAt(s, mat, b[0], b[1], b[2]), mf = zAt(s, mat, f[0], f[1], f[2]);
-        valid = mb == kLiquid || mf == kLiquid;
-        if (valid) {
-            w = cwf;
-            if ((mb == kLiquid && mf == kAir) || (mb == kAir && mf == kLiquid))
-                w /= ghostFluidTheta(zAt(s, phi, b[0], b[1], b[2]), zAt(s, phi, f[0], f[1], f[2]));
-        }
-    }
-    return w;
+    int mb, mf;
+    valid = isValidFace(s.whole(), axis, bi, bj, bkg, cwf, SlabAt<int32_t>{s, mat}, mb, mf);
+    return valid ? expandedWeight(axis, bi, bj, bkg, cwf, mb, mf, SlabAt<float>{s, phi}) : 0.f;
 }
 
-// One thread per (i, j, k) of the window's expanded face grids, (ex + 1) x (ey + 1) x (planes + 1): the x-, y- and z-face in front
-// of expanded cell (i, j, e0 + k).  Writes the three expanded weights everywhere (0 outside the base box) and the valid flags.
+// One thread per (i, j, k) of the window's expanded face grids, (ex + 1) x (ey + 1) x (planes + 1): the x-, y- and z-face in front of
+// expanded cell (i, j, e0 + k).  Writes the three expanded weights everywhere (0 outside the base box) and the valid flags.
 __global__ __launch_bounds__(256) void facesSlabKernel(Slab s, uint8_t *__restrict__ vx, uint8_t *__restrict__ vy, uint8_t *__restrict__ vz,
                                                        float *__restrict__ wx, float *__restrict__ wy, float *__restrict__ wz,
                                                        Planes<int32_t> mat, Planes<float> phi, const float *__restrict__ cwx,
@@ -1058,8 +1143,7 @@ __global__ __launch_bounds__(256) void facesSlabKernel(Slab s, uint8_t *__restri
 __device__ __forceinline__ int domainLabelAt(const Slab &s, const Planes<int32_t> &mat, int bi, int bj, int bkg)
 {
     if (bi < 0 || bi >= s.gx || bj < 0 || bj >= s.gy || bkg < 0 || bkg >= s.gz) return MGPS_EXTERIOR_CELL;
-    const int m = zAt(s, mat, bi, bj, bkg);
-    return m == kLiquid ? MGPS_INTERIOR_CELL : m == kAir ? MGPS_DIRICHLET_CELL : MGPS_EXTERIOR_CELL;
+    return domainLabel(zAt(s, mat, bi, bj, bkg));
 }
 
 // domainLabelsKernel + setBoundaryLabelsKernel on the window: the neighbours' labels come from the material labels, so nothing
@@ -1075,17 +1159,12 @@ __global__ __launch_bounds__(256) void labelsSlabKernel(Slab s, uint8_t *__restr
     int label = domainLabelAt(s, mat, bi, bj, bkg);
     if (label == MGPS_INTERIOR_CELL) {
         const float *w[3] = {wx, wy, wz};
-        bool bnd = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                int n[3] = {bi, bj, bkg};
-                n[a] += d ? 1 : -1;
-                const int nl = domainLabelAt(s, mat, n[0], n[1], n[2]);
-                bnd = bnd || nl == MGPS_DIRICHLET_CELL || nl == MGPS_EXTERIOR_CELL || w[a][cellFace(e, a, d, i, j, k)] != 1.f;
-            }
-        if (bnd) label = MGPS_BOUNDARY_CELL;
+        auto labelAcross = [&](int a, int d) {
+            int n[3] = {bi, bj, bkg};
+            n[a] += d ? 1 : -1;
+            return domainLabelAt(s, mat, n[0], n[1], n[2]);
+        };
+        if (isBoundaryCell(e, i, j, k, w, labelAcross)) label = MGPS_BOUNDARY_CELL;
     }
     lab[cellAt(e, i, j, k)] = uint8_t(label);
 }
@@ -1136,29 +1215,9 @@ __global__ __launch_bounds__(256) void solutionToPressureSlabKernel(Slab s, floa
     else if (clearOthers) pressure[c] = 0.f;
 }
 
-// pressureGradientKernel (sp.own == NULL) / pressureGradientSurfaceKernel on the face of `axis` in front of base cell (bi, bj, bkg)
-__device__ __forceinline__ float faceGradient(const Slab &s, int axis, int bi, int bj, int bkg, const Planes<float> &phi,
-                                              const Planes<float> &pr, const Planes<float> &sp, const Planes<int32_t> &mat)
-{
-    int b[3] = {bi, bj, bkg};
-    b[axis] -= 1;
-    const bool lb = zAt(s, mat, b[0], b[1], b[2]) == kLiquid, lf = zAt(s, mat, bi, bj, bkg) == kLiquid;
-    float pb = zAt(s, pr, b[0], b[1], b[2]), pf = zAt(s, pr, bi, bj, bkg);
-    if (!sp.own) {
-        float grad = pf - pb;
-        if (!lb || !lf) grad /= ghostFluidTheta(zAt(s, phi, b[0], b[1], b[2]), zAt(s, phi, bi, bj, bkg));
-        return grad;
-    }
-    if (lb && lf) return pf - pb;
-    const float theta = ghostFluidTheta(zAt(s, phi, b[0], b[1], b[2]), zAt(s, phi, bi, bj, bkg));
-    const float pg = interfacePressure(theta, lb, zAt(s, sp, b[0], b[1], b[2]), zAt(s, sp, bi, bj, bkg));
-    if (lb) pf = pg;
-    else pb = pg;
-    return (pf - pb) / theta;
-}
-
 // One thread per (i, j, k) of the window's base face grids, (gx + 1) x (gy + 1) x (planes + 1): the three faces in front of base
-// cell (i, j, c0 + k).  A valid face has both cells inside the whole grid, so no halo is read past it.
+// cell (i, j, c0 + k).  A valid face has both cells inside the whole grid, so no halo is read past it.  sp.own == NULL gives the
+// plain gradient.
 __global__ __launch_bounds__(256) void pressureGradientSlabKernel(Slab s, float *__restrict__ velx, float *__restrict__ vely,
                                                                   float *__restrict__ velz, Planes<float> phi, Planes<float> pr,
                                                                   Planes<float> sp, const uint8_t *__restrict__ vx,
@@ -1170,31 +1229,21 @@ __global__ __launch_bounds__(256) void pressureGradientSlabKernel(Slab s, float 
     if (i > s.gx) return;
     const Box g = s.base();
     const int kg = s.c0 + k;
+    const bool surface = sp.own != nullptr;
+    const SlabAt<int32_t> matAt{s, mat};
+    const SlabAt<float> prAt{s, pr}, phiAt{s, phi}, spAt{s, sp};
     if (j < s.gy && k < g.gz) {
         const size_t f = faceAt(g, 0, i, j, k);
-        if (vx[f]) velx[f] -= faceGradient(s, 0, i, j, kg, phi, pr, sp, mat);
+        if (vx[f]) velx[f] -= faceGradient(0, i, j, kg, surface, matAt, prAt, phiAt, spAt);
     }
     if (i < s.gx && k < g.gz) {
         const size_t f = faceAt(g, 1, i, j, k);
-        if (vy[f]) vely[f] -= faceGradient(s, 1, i, j, kg, phi, pr, sp, mat);
+        if (vy[f]) vely[f] -= faceGradient(1, i, j, kg, surface, matAt, prAt, phiAt, spAt);
     }
     if (i < s.gx && j < s.gy) {
         const size_t f = faceAt(g, 2, i, j, k);
-        if (vz[f]) velz[f] -= faceGradient(s, 2, i, j, kg, phi, pr, sp, mat);
+        if (vz[f]) velz[f] -= faceGradient(2, i, j, kg, surface, matAt, prAt, phiAt, spAt);
     }
-}
-
-// isInterfaceCell with the z-neighbours through the halo planes
-__device__ __forceinline__ bool isInterfaceCellSlab(const Slab &s, const Planes<int32_t> &mat, int i, int j, int kg, int m)
-{
-    const int n[6] = {zAt(s, mat, i > 0 ? i - 1 : i, j, kg),       zAt(s, mat, i + 1 < s.gx ? i + 1 : i, j, kg),
-                      zAt(s, mat, i, j > 0 ? j - 1 : j, kg),       zAt(s, mat, i, j + 1 < s.gy ? j + 1 : j, kg),
-                      zAt(s, mat, i, j, kg > 0 ? kg - 1 : kg),     zAt(s, mat, i, j, kg + 1 < s.gz ? kg + 1 : kg)};
-    const int other = m == kLiquid ? kAir : kLiquid;
-    bool any = false;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) any |= n[q] == other;
-    return (m == kLiquid || m == kAir) && any;
 }
 
 __global__ __launch_bounds__(256) void surfacePressureSlabKernel(Slab s, float *__restrict__ sp, Planes<float> phi, Planes<int32_t> mat,
@@ -1203,17 +1252,8 @@ __global__ __launch_bounds__(256) void surfacePressureSlabKernel(Slab s, float *
     int i, j, k;
     threadCell(i, j, k);
     if (i >= s.gx) return;
-    const Box g = s.base();
-    const int kg = s.c0 + k;
-    const size_t c = cellAt(g, i, j, k);
-    float out = 0.f;
-    if (isInterfaceCellSlab(s, mat, i, j, kg, mat.own[c])) {
-        const int im = max(i - 1, 0), ip = min(i + 1, s.gx - 1), jm = max(j - 1, 0), jp = min(j + 1, s.gy - 1), km = max(kg - 1, 0),
-                  kp = min(kg + 1, s.gz - 1);
-        auto at = [&](int x, int y, int z) { return double(zAt(s, phi, x, y, z)); };
-        out = surfacePressureAt(at, scale, i, im, ip, j, jm, jp, kg, km, kp);
-    }
-    sp[c] = out;
+    const size_t c = cellAt(s.base(), i, j, k);
+    sp[c] = surfacePressure(s.whole(), i, j, s.c0 + k, mat.own[c], scale, SlabAt<int32_t>{s, mat}, SlabAt<float>{s, phi});
 }
 
 // rhsSurfaceKernel on the window: the expanded weights are the window's (what facesSlabKernel wrote)
@@ -1226,40 +1266,20 @@ __global__ __launch_bounds__(256) void rhsSurfaceSlabKernel(Slab s, float *__res
     float amax = 0.f;
     // (no early return: every lane reaches the wave reduction below)
     const bool inside = bi < s.gx;
-    const Box g = s.base(), e = s.window();
+    const Box G = s.whole();
     const int kg = s.c0 + bk;
-    const size_t c = inside ? cellAt(g, bi, bj, bk) : 0;
+    const size_t c = inside ? cellAt(s.base(), bi, bj, bk) : 0;
     const int m = inside ? mat.own[c] : kSolid;
-    if (inside && isInterfaceCellSlab(s, mat, bi, bj, kg, m) && m == kLiquid) {
+    const SlabAt<int32_t> matAt{s, mat};
+    if (inside && isInterfaceCell(G, bi, bj, kg, m, matAt) && m == kLiquid) {
         const float *w[3] = {wx, wy, wz};
-        const int ext[3] = {s.gx, s.gy, s.gz};
+        const Box e = s.window();
         const int ei = bi + s.off, ej = bj + s.off, ek = kg + s.off - s.e0;
-        const size_t ec = cellAt(e, ei, ej, ek);
-        float acc = rhs[ec];
-        bool touched = false;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                int n[3] = {bi, bj, kg};
-                n[a] += d ? 1 : -1;
-                if (n[a] < 0 || n[a] >= ext[a]) continue;
-                if (zAt(s, mat, n[0], n[1], n[2]) != kAir) continue;
-                const float wf = w[a][cellFace(e, a, d, ei, ej, ek)];
-                if (wf == 0.f) continue;  // not a valid face
-                const float phc = phi.own[c], phn = zAt(s, phi, n[0], n[1], n[2]);
-                const float spc = sp.own[c], spn = zAt(s, sp, n[0], n[1], n[2]);
-                const float theta = d ? ghostFluidTheta(phc, phn) : ghostFluidTheta(phn, phc);
-                const float pg = interfacePressure(theta, d == 1, d ? spc : spn, d ? spn : spc);
-                acc += wf * pg;
-                amax = fmaxf(amax, fabsf(pg));
-                touched = true;
-            }
-        if (touched) rhs[ec] = acc;
+        auto wAcross = [&](int a, int d) { return w[a][cellFace(e, a, d, ei, ej, ek)]; };
+        amax = addSurfaceRhs(G, bi, bj, kg, phi.own[c], sp.own[c], rhs[cellAt(e, ei, ej, ek)], wAcross, matAt, SlabAt<float>{s, phi},
+                             SlabAt<float>{s, sp});
     }
-    if (!pGammaMax) return;
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    if ((threadIdx.x & 63) == 0 && amax > 0.f) atomicMax(pGammaMax, __float_as_uint(amax));
+    raisePGammaMax(pGammaMax, amax);
 }
 
 inline int clampInt(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
@@ -1276,7 +1296,6 @@ bool readSlab(const mgps_fields_slab *d, Slab &s, const char *what)
     if (!ok) setLastGlobalError(std::string(what) + ": not a slab window (struct_size, extents, c0 < c1 = the base planes of [e0, e1))");
     return ok;
 }
-inline dim3 rowGrid(int nx, int ny, int nz) { return dim3(unsigned((nx + 255) / 256), unsigned(ny), unsigned(nz)); }
 // halo planes: present exactly where the whole grid goes on
 template <class T>
 bool okHalo(const Slab &s, const T *own, const T *lo, const T *hi)
@@ -1556,11 +1575,7 @@ try {
     if (P > 1 && (!cm.gatherv || !cm.scatterv))
         return invalid("the collapse of uneven cuts and the enclosed-liquid merge go through gatherv and scatterv (and, with host_setup, the whole grid's labels): the transport has none");
     mgps_options o;
-    mgps_default_options(&o);
-    if (opt) {
-        if (opt->struct_size != int(sizeof(mgps_options))) return invalid("mgps_options.struct_size mismatch: call mgps_default_options first");
-        o = *opt;
-    }
+    if (int rc = readOptions(opt, o, "mgps_project_free_surface_slab: "); rc != MGPS_OK) return rc;
     mgps_fields_slab desc;
     if (int rc = mgps_fields_slab_describe(&desc, p->gx, p->gy, p->gz, p->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
     Slab s;
@@ -1583,10 +1598,7 @@ try {
     p->expanded[1] = ey;
     p->expanded[2] = ez;
     p->liquid_cells = 0;
-    std::memset(&p->stats, 0, sizeof(p->stats));
-    p->residual_inf = p->residual_l2 = p->divergence_sum = p->divergence_max = 0;
-    p->enclosed_components = 0;
-    p->rhs_mean_removed_max = p->surface_pressure_max = 0;
+    clearReport(p);
     p->setup_ms = p->solve_ms = p->total_ms = 0;
     std::fill(p->stage_ms, p->stage_ms + 8, 0.0);
 
@@ -1605,26 +1617,8 @@ try {
         ~HostBlock() { mgps_host_free(p); }
     } hostBlock{labelsHost};
     int status = [&]() -> int {
-        bool ok = p->liquid_phi && p->solid_phi && p->pressure;
-        for (int a = 0; a < 3; ++a) ok = ok && p->cut_weights[a] && p->velocity[a];
-        if (!ok || (!haveSolidVel && (p->solid_velocity[0] || p->solid_velocity[1] || p->solid_velocity[2])))
-            return invalid("missing field (solid velocities: all three or none)");
-        if (!std::isfinite(sigma) || sigma < 0) return invalid("surface_tension must be finite and >= 0");
-        if (sigma > 0) {
-            const char *what = !(std::isfinite(p->dt) && p->dt > 0) ? "dt" : !(std::isfinite(p->dx) && p->dx > 0) ? "dx"
-                             : !(std::isfinite(p->density) && p->density > 0) ? "density" : nullptr;
-            if (what) return invalid(std::string("surface_tension > 0 needs a finite ") + what + " > 0");
-            if (p->surface_pressure) return invalid("surface_tension and surface_pressure are both set (pass one of them)");
-        }
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-            setLastGlobalError("no HIP device is visible (this library has no CPU path)");
-            return MGPS_ERR_NO_DEVICE;
-        }
-        if (o.device >= 0 && hipSetDevice(o.device) != hipSuccess) {
-            setLastGlobalError("hipSetDevice failed");
-            return MGPS_ERR_NO_DEVICE;
-        }
+        if (int rc = checkProjectionFields(p, "mgps_project_free_surface_slab", true, "missing field"); rc != MGPS_OK) return rc;
+        if (int rc = selectDevice(o.device); rc != MGPS_OK) return rc;
         try {
             material = pool.get<int32_t>(cells + 2 * plane);
             phiHalo = pool.get<float>(2 * plane);

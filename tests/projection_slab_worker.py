@@ -22,14 +22,11 @@ import geometricmultigridpressuresolver_amd as G  # noqa: E402
 from geometricmultigridpressuresolver_amd import domains as D  # noqa: E402
 from geometricmultigridpressuresolver_amd import fields as F  # noqa: E402
 from geometricmultigridpressuresolver_amd.distributed import RcclComm, TorchDistComm  # noqa: E402
+from slab_slices import cell, dev, faces, halo, zface  # noqa: E402
 
 SHAPE = (96, 64, 64)  # (gz, gy, gx): 5 levels, offset 16, 128 expanded planes with either expansion
 CUTS = {1: [0, 128], 2: [0, 64, 128], 4: [0, 32, 64, 96, 128]}  # every rank owns base planes; valid for both smoothers
 LIQUID, AIR = 1, 2
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def h(a):
@@ -44,23 +41,6 @@ def all_ranks(value):
     seen = [None] * dist.get_world_size()
     dist.all_gather_object(seen, value)
     return seen
-
-
-def cell(a, d):
-    return a[d.c0:d.c1]
-
-
-def zface(a, d):
-    return a[d.c0:d.c1 + 1]
-
-
-def faces(arrs, d):
-    return [cell(arrs[0], d), cell(arrs[1], d), zface(arrs[2], d)]
-
-
-def halo(a, d):
-    """the planes next to the window, as an exchange would deliver them; None where the grid ends"""
-    return (dev(a[d.c0 - 1]) if d.c0 > 0 else None, dev(a[d.c1]) if d.c1 < d.gz else None)
 
 
 def cut_faces(material, cw, splits, offset):
@@ -178,6 +158,8 @@ def passes_mode():
             print(f"passes {name}: {la} liquid-air and {frac} fractional z-faces on the cuts {splits[1:-1]}", flush=True)
     assert seen_la >= 1 and seen_frac >= 1, (seen_la, seen_frac)
     print(f"rank {rank}: bit-equal float arrays {bit_equal}", flush=True)
+    # one definition per rule: the two kernel families round alike, not only within the bounds above
+    assert len(bit_equal) == 6 and all(bit_equal.values()), bit_equal
 
 
 # ---- 3. the one call against the single-device call -------------------------------------------------------------------------------
