@@ -263,7 +263,21 @@ struct GridP {
     // expansion pads every row with 2^(L-1) EXTERIOR cells per side (an eighth of a 1024-cell row at L = 7): activity-skipping
     // sweeps leave the quads outside the range alone -- nothing loaded, nothing stored, like the runs / blocks without active cells
     int xlo, xhi;
+    // Plain quads: one bit per quad (four cells along x, nx % 4 == 0), set where all four codes are MGPS_INTERIOR_CELL -- in the
+    // liquid nearly every quad.  The plane marches (stencilPlaneKernel, residualZKernel, prolongJacobiPlaneKernel) take the codes of
+    // such a quad as 0 and do not load them.  nullptr = every code is loaded (levels without plane blocks, slab ranks,
+    // MGPS_PLAIN_QUADS=0).
+    //   plainQ  the canonical layout: bit q & 31 of word q >> 5, q = flat cell index / 4 (an even number of words is allocated:
+    //           the builder's waves store the ballot of 64 consecutive quads as a pair); no kernel reads it but the one that cuts
+    //   plainT  from it -- the plane marches' copy: one 64-bit word per (plane, row, 256-cell tile), bit = lane (the quad at x = 256 tile +
+    //           4 lane), bits past the end of a row 0 -- word (k ny + j) nbx + tile, nbx = (nx + 255) / 256
+    const uint32_t *plainQ;
+    const unsigned long long *plainT;
 };
+// plainQ / plainT of a level from its cell codes (one streaming pass over the codes; plainT is cut from plainQ); plainQ holds
+// plainQuadWords(cells) words, plainT ny nz nbx
+inline size_t plainQuadWords(size_t cells) { return ((cells / 4 + 63) / 64) * 2; }
+int launchPlainQuads(void *stream, const uint8_t *lab, int nx, int ny, int nz, uint32_t *plainQ, unsigned long long *plainT);
 // xlo / xhi of a level from its cell codes (range[0] = min x, range[1] = max x over the active cells; range preset to {nx, -1})
 int launchActiveXRange(void *stream, const uint8_t *lab, int nx, size_t cells, int *range);
 

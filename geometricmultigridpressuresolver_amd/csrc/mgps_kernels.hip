@@ -210,6 +210,16 @@ __device__ __forceinline__ bool listQuad(const int32_t *__restrict__ chunks, int
 // lanes whose x-neighbour quad lives in another lane's registers: all but the ends of a run
 __device__ __forceinline__ int listRunMask(const int32_t *chunks, int chunkCells) { return (chunks && chunkCells < kWaveChunkCells) ? (chunkCells >> 2) - 1 : kWave - 1; }
 
+// Plain quads (GridP::plainT): the words come through the constant address space, so that a wave-uniform index makes the
+// fetch a scalar load whatever the optimiser knows about the stores around it.  (Tried and taken out again, LABNOTES R11: the same
+// look-up on GridP::plainQ in stencilQuadBody -- 0.56 GB less read per 1024^3 sweep and no time gained, a loss on the levels that
+// live in the caches)
+#define MGPS_CONST_AS __attribute__((address_space(4)))
+__device__ __forceinline__ unsigned long long plainWord64(const void *base, size_t idx) { return *((const MGPS_CONST_AS unsigned long long *)base + idx); }
+// a wave's word of GridP::plainT as a predicate: bit = lane.  The word is wave-uniform (scalar registers) and becomes the execution
+// mask of the branch as it is -- no vector register, no shift per lane
+__device__ __forceinline__ bool plainLane(unsigned long long w) { return __builtin_amdgcn_inverse_ballot_w64(w); }
+
 // XZERO: the iterate is known to be zero everywhere (the first sweep of a stroke that starts from the cleared grid, MG.cpp:439-440 /
 // 566): nothing of x is loaded and nobody had to clear it
 // The body serves two kernels: stencilQuadKernel (a 256-thread workgroup = one share `vblock` of the launch) and strokeFrontKernel
@@ -379,6 +389,19 @@ __device__ __forceinline__ uchar4 gLoadCodes4nt(const uint8_t *base, unsigned ce
     const v4b v = __builtin_nontemporal_load((const MGPS_GLOBAL_AS v4b *)((const MGPS_GLOBAL_AS char *)base + cell));
     return make_uchar4(v.x, v.y, v.z, v.w);
 }
+// (the same four codes as one word: what a branch round the load merges with "no codes", a word of zeros, in one register)
+__device__ __forceinline__ unsigned gLoadCodesWnt(const uint8_t *base, unsigned cell) { return __builtin_nontemporal_load((const MGPS_GLOBAL_AS unsigned *)((const MGPS_GLOBAL_AS char *)base + cell)); }
+__device__ __forceinline__ uchar4 codes4(unsigned w) { return make_uchar4(w & 255u, (w >> 8) & 255u, (w >> 16) & 255u, w >> 24); }
+// the lane's index formed where it is used (the zero is opaque: nothing is hoisted or kept in a register across a march).
+// What it prevents: residualZKernel<true> holding threadIdx.x & 63 across its march for the last x-folded store -- 64 VGPRs and
+// 8 B of scratch with the plain-quad branch in the loop, 62 and none with this.  If tools/kres.py shows no scratch there with
+// `lane` in its place, this helper can go.
+__device__ __forceinline__ unsigned laneHere()
+{
+    unsigned z = 0u;
+    asm volatile("" : "+s"(z));
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+}
 __device__ __forceinline__ unsigned gLoadCode1(const uint8_t *base, unsigned cell) { return *((const MGPS_GLOBAL_AS uint8_t *)base + cell); }
 __device__ __forceinline__ void gStore4(float *base, unsigned cell, float4 v) { *(MGPS_GLOBAL_AS v4f *)((MGPS_GLOBAL_AS char *)base + cell * 4u) = v4f{v.x, v.y, v.z, v.w}; }
 __device__ __forceinline__ void gStore4nt(float *base, unsigned cell, float4 v)
@@ -446,7 +469,13 @@ GridP g, float *__restrict__ out,
     const unsigned offHx = !useHx ? off : (colL ? off - 1u : off + 4u);
 
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const uchar4 ext4 = make_uchar4(MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL);
+    constexpr unsigned extW = 0x01010101u * unsigned(MGPS_EXTERIOR_CELL);
+    // plain quads (GridP::plainT): the 64 bits of this wave's row and tile in a plane are one word at a wave-uniform index (the row
+    // through readfirstlane) -- a scalar load, requested a step before the code load it gates; bit = lane.  A lane whose bit is set
+    // takes its codes as 0; a wave of such lanes branches round the load.
+    const unsigned long long *const pt = g.plainT;
+    const size_t wRow = size_t(__builtin_amdgcn_readfirstlane(unsigned(jc))) * nbx + bx, wPlane = size_t(g.ny) * nbx;
+    unsigned long long pw = pt ? plainWord64(pt, size_t(k0) * wPlane + wRow) : 0ull;
     // Two planes of a thread's own x quad are in flight at any time: plane k + 2 is requested while plane k is computed, so the
     // plane k + 1 a step needs (its z + 1 neighbours) was requested a whole step earlier; the halo is requested one plane ahead,
     // the rhs and the codes of a plane at the top of its own step (in flight across the barrier).  The z - 1 values of a step are
@@ -474,11 +503,13 @@ GridP g, float *__restrict__ out,
         if (colL) me[-1] = useHx ? hx : 0.f;
         if (colR) me[4] = useHx ? hx : 0.f;
         float4 bc = zero4;
-        uchar4 lc = ext4;
+        unsigned lcw = extW;
         if (live) {
             if (OP != OP_APPLY) bc = gLoad4nt(scalarBase(b + ptrdiff_t(k) * sz), off);
-            lc = gLoadCodes4nt(scalarBase(g.lab + ptrdiff_t(k) * sz), off);
+            lcw = 0u;
+            if (!plainLane(pw)) lcw = gLoadCodesWnt(scalarBase(g.lab + ptrdiff_t(k) * sz), off);
         }
+        if (pt) pw = plainWord64(pt, size_t(min(k + 1, g.nz - 1)) * wPlane + wRow);  // (the next step's)
         // the plane after the next one (own quad); the next plane's halo
         float4 xq = zero4, hyn = hy;
         float hxn = hx;
@@ -497,6 +528,7 @@ GridP g, float *__restrict__ out,
         const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
         const float zms[4] = {xm.x, xm.y, xm.z, xm.w}, zps[4] = {xp.x, xp.y, xp.z, xp.w};
         const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
+        const uchar4 lc = codes4(lcw);
         const unsigned ls[4] = {lc.x, lc.y, lc.z, lc.w};
         float res[4];
 #pragma unroll
@@ -583,7 +615,6 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
         return v;
     };
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const uchar4 ext4 = make_uchar4(MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL, MGPS_EXTERIOR_CELL);
 
     // this thread's share of a coarse plane: quad sq of staged row sr (clamped indices: they bite for the EXTERIOR shell and
     // for columns / rows past the grid only, whose values nobody keeps; prolongAddBlockKernel clamps the same way)
@@ -617,7 +648,8 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
     };
     auto trilerp = [](float a0, float a1, float b0, float b1, float fy, float fz) { return lerpRef(lerpRef(a0, a1, fy), lerpRef(b0, b1, fy), fz); };
     // x + 4 t on a quad; `act`: only where the codes say active (else every component)
-    auto corr4 = [&](int kk, int jj, float4 v, uchar4 lc, bool act) {
+    auto corr4 = [&](int kk, int jj, float4 v, unsigned lcw, bool act) {
+        const uchar4 lc = codes4(lcw);
         const float *pa, *pb;
         float fy, fz;
         rowsAt(kk, jj, 4 + lane * 4, pa, pb, fy, fz);
@@ -654,9 +686,17 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
     const float *xk = planeOf(x, k0);
     float4 xc = live ? gLoad4(xk, off) : zero4;
     float4 xp = live ? gLoad4(planeOf(x, k0 + 1), off) : zero4;
+    // plain quads (GridP::plainT, see stencilPlaneKernel).  The codes are requested two planes ahead, their words three
+    const unsigned long long *const pt = g.plainT;
+    const size_t wRow = size_t(__builtin_amdgcn_readfirstlane(unsigned(jc))) * nbx + bx, wPlane = size_t(g.ny) * nbx;
+    auto plainAt = [&](int kk) { return pt ? plainWord64(pt, size_t(min(kk, g.nz - 1)) * wPlane + wRow) : 0ull; };
+    const unsigned long long pw0 = plainAt(k0), pw1 = plainAt(k0 + 1);
+    unsigned long long pw = plainAt(k0 + 2);  // (of the plane whose codes the step requests)
+    constexpr unsigned extW = 0x01010101u * unsigned(MGPS_EXTERIOR_CELL);
     const uint8_t *lab0 = scalarBase(g.lab + ptrdiff_t(k0) * sz);
-    uchar4 lc = live ? gLoadCodes4nt(lab0, off) : ext4;                                           // codes of the step's plane
-    uchar4 lcn = live ? gLoadCodes4nt(scalarBase(g.lab + ptrdiff_t(k0 + 1) * sz), off) : ext4;    // ... and of the next one
+    unsigned lc = live ? 0u : extW, lcn = lc;  // codes of the step's plane and of the next one, four to a word
+    if (live && !plainLane(pw0)) lc = gLoadCodesWnt(lab0, off);
+    if (live && !plainLane(pw1)) lcn = gLoadCodesWnt(scalarBase(g.lab + ptrdiff_t(k0 + 1) * sz), off);
     float4 hy = zero4;
     if (live && rowTop) hy = gLoad4(xk, offYm);
     if (live && rowBot) hy = gLoad4(xk, offYp);
@@ -686,13 +726,17 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
         if (colL) me[-1] = useHx ? hx : 0.f;
         if (colR) me[4] = useHx ? hx : 0.f;
         float4 bc = zero4;
-        uchar4 lcq = ext4;  // codes of plane k + 2
+        unsigned lcq = extW;  // codes of plane k + 2
         const float *bk = scalarBase(b + ptrdiff_t(k) * sz);
         const uint8_t *labq = scalarBase(g.lab + ptrdiff_t(min(k + 2, g.nz - 1)) * sz);
         if (live) {
             bc = gLoad4nt(bk, opq(off));
-            if (k + 2 < k1) lcq = gLoadCodes4nt(labq, opq(off));
+            if (k + 2 < k1) {
+                lcq = 0u;
+                if (!plainLane(pw)) lcq = gLoadCodesWnt(labq, opq(off));
+            }
         }
+        pw = plainAt(k + 3);  // (the next step's)
         float4 xq = zero4, hyn = hy;
         float hxn = hx;
         if (k + 1 < k1 && live) {
@@ -715,7 +759,8 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
         const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
         const float zms[4] = {xm.x, xm.y, xm.z, xm.w}, zps[4] = {xp.x, xp.y, xp.z, xp.w};
         const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
-        const unsigned ls[4] = {lc.x, lc.y, lc.z, lc.w};
+        const uchar4 lc4 = codes4(lc);
+        const unsigned ls[4] = {lc4.x, lc4.y, lc4.z, lc4.w};
         float res[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -779,11 +824,14 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
     const int k0 = int(bz) * zc, k1 = min(k0 + zc, g.nz);  // both even
     const int ks = max(k0 - 1, 0), ke = min(k1, g.nz - 1);   // planes outside the grid: r = 0, nothing to add
     // addresses: the plane's base (wave-uniform: scalar registers) + one 32-bit offset inside the plane per thread
-    // Round 5: every load of the march is UNCONDITIONAL.  A lane outside the active x range (`live`) aims at the nearest quad of
-    // the range in its row -- a line the wave fetches anyway -- and what arrives is dropped where it is used; the wave of a middle
-    // row re-reads its own quad as its "y halo".  With no branch around a load the compiler can count them: the wait behind the
-    // barrier becomes vmcnt(3) -- this plane's rhs and codes -- and the three loads for the next planes stay in flight across the
-    // arithmetic (round 4: a branch per load left it no choice but vmcnt(0) there, a memory round trip per plane).
+    // Round 5: the loads of x and of the rhs are UNCONDITIONAL.  A lane outside the active x range (`live`) aims at the nearest quad
+    // of the range in its row -- a line the wave fetches anyway -- and what arrives is dropped where it is used; the wave of a middle
+    // row re-reads its own quad as its "y halo".  With no lane-dependent branch around them the compiler can count them (round 4: a
+    // branch per load left it no choice but vmcnt(0) behind the barrier, a memory round trip per plane).
+    // Round 11: one load does sit behind a lane-dependent branch, the codes (plain quads, below).  It is the step's FIRST request, so
+    // the count still works: behind the barrier the codes are waited for with vmcnt(3) and the rhs with vmcnt(2) -- the two or three
+    // loads for the next planes (x halo, the y halo on the tile's first / last wave, the quad two planes ahead) stay in flight
+    // across the arithmetic, as before.
     // (a live lane's own quad IS that quad: offL serves its stores as well)
     const unsigned offL = unsigned(jc) * unsigned(g.nx) + unsigned(min(max(ic, g.xlo), max(g.xhi - 4, g.xlo)));
     const bool rowTop = ty == 0, rowBot = ty == kPlaneRows - 1, colL = lane == 0, colR = lane == kWave - 1;
@@ -825,7 +873,7 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
         const float2 o = make_float2(foldX4(fromLeftLane(v.w), v.x, v.y, v.z), foldX4(v.y, v.z, v.w, fromRightLane(v.x)));
         float *const px = scalarBase(rz + size_t(K) * (sz >> 1));
         if (storeX) {
-            const unsigned offX = rowX + 2u * unsigned(lane);
+            const unsigned offX = rowX + 2u * laneHere();  // (a wave is a row of the tile)
             if (nt) gStore2nt(px, offX, o);
             else gStore2(px, offX, o);
         }
@@ -839,6 +887,11 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
         accCur[2] = w0 * e.z;
         accCur[3] = w0 * e.w;
     }
+    // plain quads (GridP::plainT, see stencilPlaneKernel): the lane's own bit.  A lane outside the active x range or the grid has
+    // none set (EXTERIOR cells, or past the end of the row) and loads the codes offL aims at as before; nothing of them is kept
+    const unsigned long long *const pt = g.plainT;
+    const size_t wRow = size_t(rowS) * nbx + bx, wPlane = size_t(g.ny) * nbx;
+    unsigned long long pw = pt ? plainWord64(pt, size_t(ks) * wPlane + wRow) : 0ull;
     int buf = 0;
     for (int k = ks; k <= ke; ++k) {
         float *me = mine0 + buf * kBufFloats;
@@ -852,9 +905,12 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
         const float *bk = planeOf(b, k);
         const uint8_t *lk = scalarBase(g.lab + size_t(k) * sz);
         const float *xn = planeOf(x, k + 1), *xq2 = planeOf(x, k + 2);
-        // (unconditional, this plane's first: see offL; past the last plane the bases are clamped, what arrives is never used)
+        // (the codes first: the one branch round a load -- a wave of plain quads issues none -- and the other loads stay in one block;
+        // then the rhs, unconditional: see offL.  Past the last plane the bases are clamped, what arrives is never used)
+        unsigned lcw = 0u;
+        if (!plainLane(pw)) lcw = gLoadCodesWnt(lk, offL);
+        if (pt) pw = plainWord64(pt, size_t(min(k + 1, g.nz - 1)) * wPlane + wRow);  // (the next step's)
         const float4 bc = gLoad4nt(bk, offL);
-        const uchar4 lc = gLoadCodes4nt(lk, offL);
         // (in the order of their use: the halo of the next plane is staged at the top of the next step, the quad two planes ahead is
         // needed behind the next barrier -- requested last, it is the one left in flight across the top of the loop)
         const float hxn = gLoad1(xn, offHx);
@@ -869,6 +925,7 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
         const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
         const float zms[4] = {xm.x, xm.y, xm.z, xm.w}, zps[4] = {xp.x, xp.y, xp.z, xp.w};
         const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
+        const uchar4 lc = codes4(lcw);
         const unsigned ls[4] = {lc.x, lc.y, lc.z, lc.w};
         float res[4];
 #pragma unroll
@@ -2742,6 +2799,50 @@ int launchActiveXRange(void *stream, const uint8_t *lab, int nx, size_t cells, i
     return int(hipGetLastError());
 }
 
+// GridP::plainQ from the cell codes: a wave takes 64 consecutive quads (one code word per lane, coalesced) and stores their
+// ballot as two words; quads past the end of the grid are not plain
+__global__ __launch_bounds__(256) void plainQuadsKernel(const uint8_t *__restrict__ lab, size_t quads, uint32_t *__restrict__ plainQ)
+{
+    const unsigned *w = reinterpret_cast<const unsigned *>(lab);
+    const size_t groups = (quads + kWave - 1) / kWave, waves = size_t(gridDim.x) * (blockDim.x / kWave);
+    const unsigned lane = threadIdx.x & (kWave - 1);
+    for (size_t grp = size_t(blockIdx.x) * (blockDim.x / kWave) + threadIdx.x / kWave; grp < groups; grp += waves) {
+        const size_t q = grp * kWave + lane;
+        const unsigned v = q < quads ? __builtin_nontemporal_load(w + q) : 0x01010101u * unsigned(MGPS_EXTERIOR_CELL);
+        const unsigned long long plain = __ballot(v == 0u);  // (MGPS_INTERIOR_CELL four times)
+        if (lane < 2) plainQ[2 * grp + lane] = unsigned(plain >> (32 * lane));
+    }
+}
+// GridP::plainT cut from plainQ: a thread per (plane, row, tile) takes the 64 bits that start at the tile's first quad
+__global__ __launch_bounds__(256) void plainTilesKernel(const uint32_t *__restrict__ plainQ, size_t words, unsigned nq, unsigned nbx, size_t rows,
+                                                        unsigned long long *__restrict__ plainT)
+{
+    const size_t t = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= rows * nbx) return;
+    const size_t row = t / nbx;
+    const unsigned tile = unsigned(t - row * nbx), left = nq - tile * 64u;  // (quads of the row from this tile on)
+    const size_t q0 = row * nq + size_t(tile) * 64u, w0 = q0 >> 5;
+    const unsigned sh = unsigned(q0) & 31u;
+    const unsigned long long a = plainQ[w0], b = w0 + 1 < words ? plainQ[w0 + 1] : 0u, c = w0 + 2 < words ? plainQ[w0 + 2] : 0u;
+    unsigned long long v = ((a | (b << 32)) >> sh) | (sh ? c << (64u - sh) : 0ull);
+    if (left < 64u) v &= (1ull << left) - 1ull;
+    plainT[t] = v;
+}
+int launchPlainQuads(void *stream, const uint8_t *lab, int nx, int ny, int nz, uint32_t *plainQ, unsigned long long *plainT)
+{
+    const size_t cells = size_t(nx) * ny * nz, quads = cells >> 2;
+    if (cells == 0 || (nx & 3) != 0) return int(hipErrorInvalidValue);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t groups = (quads + kWave - 1) / kWave;
+    plainQuadsKernel<<<unsigned(std::min<size_t>((groups + 3) / 4, 256 * 64)), 256, 0, s>>>(lab, quads, plainQ);
+    if (plainT) {
+        const unsigned nbx = unsigned(nx + 255) / 256u;
+        const size_t rows = size_t(ny) * nz;
+        plainTilesKernel<<<blocksFor(rows * nbx, 256), 256, 0, s>>>(plainQ, plainQuadWords(cells), unsigned(nx) >> 2, nbx, rows, plainT);
+    }
+    return int(hipGetLastError());
+}
+
 // blocks of the main launch of a sweep over level g (same choice of kernel as launchStencil)
 static unsigned sweepBlocks(const GridP &g, bool skipInactive, int *path)
 {
@@ -3189,6 +3290,8 @@ int launchResidualEdgePlanes(void *stream, const GridP &g, float *r, const float
         GridP p = g;  // the plane as a grid of its own: its neighbours below and above are its "ghost planes"
         p.nz = 1;
         p.lab = g.lab + size_t(k) * sz;
+        p.plainQ = nullptr;  // (the bits are indexed by the whole grid's cells)
+        p.plainT = nullptr;
         p.ghostLo = (k > 0 || g.ghostLo) ? 1 : 0;
         p.ghostHi = (k < g.nz - 1 || g.ghostHi) ? 1 : 0;
         p.chunks = nullptr;

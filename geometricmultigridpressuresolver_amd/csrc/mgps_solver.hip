@@ -84,6 +84,8 @@ struct DevLevel {
     bool hasBandPlanes = false;  // host-built slab levels: packed band cells of the planes at the cuts (GHOST_BAND exchanges)
     GridP gBox{};              // the level as the box launches of a cut level see it: rows of the general cells of the whole label buffer
     float *extRows = nullptr;
+    uint32_t *plainQ = nullptr;            // GridP::plainQ / plainT (commonDeviceState)
+    unsigned long long *plainT = nullptr;
     int elo = 0;               // label ghost planes below owned plane 0 in the level's label buffer (codes allocation: spare plane | buffer | spare plane)
 };
 
@@ -458,6 +460,8 @@ void freeAll(mgps_solver *h)
         (void)cacheFree(L.rz);
         (void)cacheFree(L.rzEdges);
         (void)cacheFree(L.bandBoxes.general);
+        (void)cacheFree(L.plainQ);
+        (void)cacheFree(L.plainT);
     }
     for (int a = 0; a < 3 && !h->weightsBorrowed; ++a) (void)cacheFree(h->w[a]);
     if (!h->cinvShared) (void)cacheFree(h->cinv);  // (a device-built inverse belongs to its shared holder)
@@ -2311,6 +2315,24 @@ int commonDeviceState(mgps_solver *h, bool needCoarseSolver)
             if (g.lab && (g.nx & 3) == 0) MGPS_LAUNCH(h, launchActiveXRange(nullptr, g.lab, g.nx, size_t(g.nx) * g.ny * g.nz, rangeDev + 2 * l));
         }
         MGPS_HIP(h, hipMemcpyAsync(range.data(), rangeDev, range.size() * sizeof(int), hipMemcpyDeviceToHost, nullptr));
+    }
+    // the plain quads (GridP::plainQ / plainT) of the levels whose sweeps can be plane marches (plane blocks kept: g.planeZc) -- the
+    // marches are their one consumer: one more pass over the codes, which stay as they are for the solver's life.  Whole grids only;
+    // slab ranks load every code as before.  MGPS_PLAIN_QUADS=0: no level has them (A/B runs and tests: the same bits either way)
+    static const bool plainQuads = [] {
+        const char *e = getenv("MGPS_PLAIN_QUADS");
+        return !(e && e[0] == '0');
+    }();
+    for (size_t l = 0; l < nlv && plainQuads && !h->dist; ++l) {
+        DevLevel &L = h->lv[l];
+        const GridP &g = L.g;
+        if (!g.lab || (g.nx & 3) != 0 || g.ghostLo || g.ghostHi || g.planeZc <= 0 || L.plainQ) continue;
+        const size_t cells = size_t(g.nx) * g.ny * g.nz;
+        MGPS_TRY(devAlloc(h, &L.plainQ, plainQuadWords(cells), false));
+        MGPS_TRY(devAlloc(h, &L.plainT, size_t(g.ny) * g.nz * size_t((g.nx + 255) / 256), false));
+        MGPS_LAUNCH(h, launchPlainQuads(nullptr, g.lab, g.nx, g.ny, g.nz, L.plainQ, L.plainT));  // (the null stream: see above)
+        L.g.plainQ = L.plainQ;
+        L.g.plainT = L.plainT;
     }
     MGPS_HIP(h, hipDeviceSynchronize());
     if (rangeDev) {
@@ -4698,6 +4720,8 @@ try {
         (void)cacheFree(rank);
         return rc;
     }
+    case 15: src = L.g.plainQ, n = L.g.plainQ ? (L.d.cells() / 4 + 31) / 32 : 0; break;  // (the canonical layout; empty: every code is loaded)
+    case 16: src = L.g.plainT, n = L.g.plainT ? size_t(L.d.ny) * L.d.nz * size_t((L.d.nx + 255) / 256) : 0, elem = 8; break;  // (the marches' copy)
     default: return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_level_array: unknown array");
     }
     *count = int64_t(n);

@@ -196,7 +196,11 @@ int mgps_device_count(int *count);
  * band stage: info (i32, 16 per group, in launch order), list entries (u32), general entries (i32, 2 per entry), 14 (level 0,
  * options.enclosed_liquid only) the rank of a cell's enclosed component (i32, nx*ny*nz; -1 on every other cell; components
  * ranked by their minimum linear cell index; a slab rank: its owned cells, holding the ranks of the whole grid's components,
- * ranked by their minimum global index (k_global * ny + j) * nx + i).
+ * ranked by their minimum global index (k_global * ny + j) * nx + i), 15 the plain quads (u32 words, bit q & 31 of word q >> 5
+ * set where the four codes of quad q = flat cell index / 4 are all INTERIOR; empty on levels whose sweeps load every code: levels
+ * without plane blocks, slab ranks, MGPS_PLAIN_QUADS=0), 16 the copy of those bits the plane marches read (u64 words, one per
+ * (plane k, row j, 256-cell tile t) at (k ny + j) nbx + t, nbx = (nx + 255) / 256; bit l = the quad at x = 256 t + 4 l, 0 past the
+ * end of the row; empty where 15 is).
  * *count = number of elements; out == NULL asks for the count only. */
 int mgps_level_array(mgps_solver *h, int level, int which, void *out, int64_t *count);
 
