@@ -486,11 +486,10 @@ void edgeFirst(HostLevel &L)
         L.chunks.insert(L.chunks.end(), rest.begin(), rest.end());
     }
     if (L.planeZc) {
-        const int nbx = (d.nx + 255) / 256, nby = (d.ny + kPlaneRows - 1) / kPlaneRows, nbz = (d.nz + L.planeZc - 1) / L.planeZc;
+        const size_t layer = planeTiles(d.nx, d.ny, d.nz, L.planeZc).layer();
         std::vector<int32_t> edge, rest;
         for (int32_t b : L.planeBlocks) {
-            const int bz = b / (nbx * nby), k0 = bz * L.planeZc, k1 = std::min(d.nz, k0 + L.planeZc) - 1;
-            (void)nbz;
+            const int bz = int(size_t(b) / layer), k0 = bz * L.planeZc, k1 = std::min(d.nz, k0 + L.planeZc) - 1;
             (k0 < E || k1 >= d.nz - E ? edge : rest).push_back(b);
         }
         L.edgePlaneBlocks = int32_t(edge.size());
@@ -550,17 +549,18 @@ void buildSlabLevel(const HostLevel &G, int z0, int z1, const float *wx, const f
             L.planeBlocks.clear();
             L.planeZc = planeSweepZc(d.nx, d.ny, d.nz);
             if (L.planeZc) {
-                const int nbx = (d.nx + 255) / 256, nby = (d.ny + kPlaneRows - 1) / kPlaneRows, nbz = (d.nz + L.planeZc - 1) / L.planeZc;
-                std::vector<uint8_t> act(size_t(nbx) * nby * nbz, 0);
+                const PlaneTiles pt = planeTiles(d.nx, d.ny, d.nz, L.planeZc);
+                const int nbx = int(pt.nbx), nbz = int(pt.nbz);
+                std::vector<uint8_t> act(pt.count(), 0);
                 const int zc = L.planeZc;
                 parallelFor(nbz, [&](int64_t b0, int64_t b1) {
                     for (int k = int(b0) * zc; k < std::min(d.nz, int(b1) * zc); ++k)
                         for (int j = 0; j < d.ny; ++j) {
                             const uint8_t *row = labels + d.idx(0, j, k);
                             for (int bx = 0; bx < nbx; ++bx) {
-                                uint8_t &a = act[(size_t(k / zc) * nby + j / kPlaneRows) * nbx + bx];
+                                uint8_t &a = act[pt.index(bx, j / kPlaneRows, k / zc)];
                                 if (a) continue;
-                                for (int i = bx * 256; i < std::min(d.nx, bx * 256 + 256); ++i)
+                                for (int i = bx * kPlaneCols; i < std::min(d.nx, (bx + 1) * kPlaneCols); ++i)
                                     if (isActive(row[i])) {
                                         a = 1;
                                         break;

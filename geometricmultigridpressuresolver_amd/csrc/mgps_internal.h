@@ -270,7 +270,7 @@ struct GridP {
     //   plainQ  the canonical layout: bit q & 31 of word q >> 5, q = flat cell index / 4 (an even number of words is allocated:
     //           the builder's waves store the ballot of 64 consecutive quads as a pair); no kernel reads it but the one that cuts
     //   plainT  from it -- the plane marches' copy: one 64-bit word per (plane, row, 256-cell tile), bit = lane (the quad at x = 256 tile +
-    //           4 lane), bits past the end of a row 0 -- word (k ny + j) nbx + tile, nbx = (nx + 255) / 256
+    //           4 lane), bits past the end of a row 0 -- word (k ny + j) nbx + tile, nbx = planeTiles(..).nbx
     const uint32_t *plainQ;
     const unsigned long long *plainT;
 };
@@ -290,18 +290,40 @@ struct MixScale {
     float c1 = 1.f, c2 = 1.f;
 };
 
-constexpr int kPlaneRows = 16;  // y extent of a plane-marching block (x extent 256)
+constexpr int kPlaneCols = 256;  // x extent of a plane-marching block: one wavefront of quads
+constexpr int kPlaneRows = 16;   // its y extent
 constexpr size_t kPlaneSweepMinPlaneBytes = size_t(4) << 20;  // levels whose x-y planes are larger take the plane-marching sweep by size (launchStencil)
 constexpr int kSlabEdgePlanes = kBandMaxDepth + 1;  // planes at either end of a slab whose sweep goes first: the band closure a stage message carries reaches band_iterations planes in, its face neighbours one more
+// The tiles of the plane marches: blocks of kPlaneCols x kPlaneRows x zc cells, block (bx, by, bz) at index (bz nby + by) nbx + bx.
+// The one statement of the decomposition: the kernels take their block from it, the builders' block lists and flags index it,
+// plainT holds a word per (plane, row, bx).
+struct PlaneTiles {
+    unsigned nbx, nby, nbz;
+    constexpr size_t layer() const { return size_t(nbx) * nby; }
+    constexpr size_t count() const { return layer() * nbz; }
+    constexpr size_t index(int bx, int by, int bz) const { return (size_t(bz) * nby + size_t(by)) * nbx + size_t(bx); }
+};
+constexpr PlaneTiles planeTiles(int nx, int ny, int nz, int zc)
+{
+    return PlaneTiles{unsigned((nx + kPlaneCols - 1) / kPlaneCols), unsigned((ny + kPlaneRows - 1) / kPlaneRows), zc > 0 ? unsigned((nz + zc - 1) / zc) : 0u};
+}
 // does the plane-marching sweep apply to a level of this shape, and with how many planes per block
 inline int planeSweepZc(int nx, int ny, int nz)
 {
-    if ((nx & 3) != 0 || nx < 256 || ny < kPlaneRows) return 0;
-    const size_t nbx = (nx + 255) / 256, nby = (ny + kPlaneRows - 1) / kPlaneRows;
+    if ((nx & 3) != 0 || nx < kPlaneCols || ny < kPlaneRows) return 0;
     int zc = 32;  // fewer planes per workgroup on small grids so that the launch still fills 256 CUs
-    while (zc > 4 && nbx * nby * size_t((nz + zc - 1) / zc) < 1024) zc >>= 1;
+    while (zc > 4 && planeTiles(nx, ny, nz, zc).count() < 1024) zc >>= 1;
     return zc;
 }
+// The seam array of the x-folded residual (residualZKernel<true>): for every coarse plane K, fine row j and tile boundary s
+// (fine x = kPlaneCols s, s = 1 .. nseam) the two z-folded quads on either side of the boundary -- side 0: fine x 256 s - 4 ..
+// 256 s - 1, side 1: 256 s .. 256 s + 3 -- eight floats, [K][j][s - 1][8].  The marches write it, restrictYKernel reads it.
+struct SeamLayout {
+    unsigned ny, nseam;
+    constexpr size_t planeFloats() const { return size_t(ny) * nseam * 8u; }
+    constexpr unsigned entry(unsigned j, unsigned s, unsigned side) const { return (j * nseam + (s - 1u)) * 8u + side * 4u; }  // (inside plane K)
+};
+constexpr SeamLayout seamLayout(int nx, int ny) { return SeamLayout{unsigned(ny), planeTiles(nx, ny, 0, 0).nbx - 1u}; }
 
 enum StencilOp { OP_JACOBI = 0, OP_RESIDUAL = 1, OP_APPLY = 2 };
 

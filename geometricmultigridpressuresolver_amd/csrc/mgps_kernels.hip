@@ -150,6 +150,40 @@ __device__ __forceinline__ double dotTerm(float xc, float bc, float res)
 {
     return OP == OP_JACOBI ? double(res) * double(bc) : double(xc) * double(res);
 }
+// The sweeps' arithmetic on a quad, stated once: INTERIOR and simple BOUNDARY cells take the 7-point row their code spells
+// (simpleDiag), every other cell inactiveValue -- general BOUNDARY cells are patched by a list kernel after the launch.
+// xs: the quad (xs[1 .. 4]) between its x neighbours -- or xl, xc, xr, which the second form puts together; ym .. zp: the neighbour
+// quads along y and z; codes: four to a word.
+// The epilogue is epilogueRcp, or epilogueMix with the scales of the binary16 grids.
+struct PlainEpilogue {
+    template <int OP>
+    __device__ __forceinline__ float at(float xc, float bc, float lap, float rdiag, float omega) const { return epilogueRcp<OP>(xc, bc, lap, rdiag, omega); }
+};
+struct MixEpilogue {
+    float bm, c2;
+    template <int OP>
+    __device__ __forceinline__ float at(float xc, float bc, float lap, float rdiag, float omega) const { return epilogueMix<OP>(xc, bc, lap, rdiag, omega, bm, c2); }
+};
+__device__ __forceinline__ float comp(float4 v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }  // (e: an unrolled loop's constant)
+template <int OP, class E = PlainEpilogue>
+__device__ __forceinline__ void simpleQuad(const float (&xs)[6], float4 ym, float4 yp, float4 zm, float4 zp, float4 bc, unsigned codes, float omega,
+                                           float (&res)[4], E epi = E{})
+{
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const unsigned l = (codes >> (8 * e)) & 255u;
+        const float diag = simpleDiag(l);
+        const float lap = diag * xs[e + 1] - (xs[e] + xs[e + 2] + comp(ym, e) + comp(yp, e) + comp(zm, e) + comp(zp, e));
+        res[e] = simpleCell(l) ? epi.template at<OP>(xs[e + 1], comp(bc, e), lap, simpleRcp(diag), omega) : inactiveValue<OP>(xs[e + 1]);
+    }
+}
+template <int OP>
+__device__ __forceinline__ void simpleQuad(float xl, float4 xc, float xr, float4 ym, float4 yp, float4 zm, float4 zp, float4 bc, unsigned codes, float omega,
+                                           float (&res)[4])
+{
+    const float xs[6] = {xl, xc.x, xc.y, xc.z, xc.w, xr};
+    simpleQuad<OP>(xs, ym, yp, zm, zp, bc, codes, omega, res);
+}
 
 // Sum of `acc` over the workgroup (up to 1024 threads), left in partials[slot] by thread 0: the A.p launches of the
 // CG loop also deliver their share of <p, A p> (CG.h:110-121) instead of a second pass over p and A p.
@@ -284,22 +318,11 @@ __device__ __forceinline__ void stencilQuadBody(const GridP &g, TX *__restrict__
         if (lane == runMask || i + 4 >= g.nx || t + 1 >= totalQuads) right = (i + 4 < g.nx) ? Cell<TX>::load1(x + c + 4) : 0.f;
     }
 
-    const float xs[6] = {left, xc.x, xc.y, xc.z, xc.w, right};
-    const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
-    const float zms[4] = {zm.x, zm.y, zm.z, zm.w}, zps[4] = {zp.x, zp.y, zp.z, zp.w};
-    const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
-    const unsigned ls[4] = {labw & 255u, (labw >> 8) & 255u, (labw >> 16) & 255u, labw >> 24};
-    const float bm = kMixed ? mixRhsScale(ms) : 1.f;
+    const float xs[6] = {left, xc.x, xc.y, xc.z, xc.w, right};  // (kept here: the DOT sum below reads it)
     float res[4];
-    // INTERIOR and simple BOUNDARY cells; general BOUNDARY cells are patched by boundaryOpKernel
-    // right after this launch
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float diag = simpleDiag(ls[e]);
-        const float lap = diag * xs[e + 1] - (xs[e] + xs[e + 2] + yms[e] + yps[e] + zms[e] + zps[e]);
-        if (kMixed) res[e] = simpleCell(ls[e]) ? epilogueMix<OP>(xs[e + 1], bs[e], lap, simpleRcp(diag), omega, bm, ms.c2) : inactiveValue<OP>(xs[e + 1]);
-        else res[e] = simpleCell(ls[e]) ? epilogueRcp<OP>(xs[e + 1], bs[e], lap, simpleRcp(diag), omega) : inactiveValue<OP>(xs[e + 1]);
-    }
+    // (general BOUNDARY cells are patched by boundaryOpKernel right after this launch)
+    if (kMixed) simpleQuad<OP>(xs, ym, yp, zm, zp, bc, labw, omega, res, MixEpilogue{mixRhsScale(ms), ms.c2});
+    else simpleQuad<OP>(xs, ym, yp, zm, zp, bc, labw, omega, res);
     unsigned skip = 0;  // cells of this quad the launch leaves alone
     if (KEEP && valid) skip = (keep[c >> 5] >> (c & 31)) & 15u;
     if (valid && !skip) {
@@ -314,7 +337,7 @@ __device__ __forceinline__ void stencilQuadBody(const GridP &g, TX *__restrict__
         double acc = 0.0;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-            if (valid && simpleCell(ls[e])) acc += dotTerm<OP>(xs[e + 1], bs[e], kMixed ? __half2float(toHalfSat(res[e])) : res[e]);  // (the value as stored)
+            if (valid && simpleCell((labw >> (8 * e)) & 255u)) acc += dotTerm<OP>(xs[e + 1], comp(bc, e), kMixed ? __half2float(toHalfSat(res[e])) : res[e]);  // (the value as stored)
         blockDotStore(acc, dotPartials, vblock);
     }
 }
@@ -394,8 +417,7 @@ __device__ __forceinline__ unsigned gLoadCodesWnt(const uint8_t *base, unsigned 
 __device__ __forceinline__ uchar4 codes4(unsigned w) { return make_uchar4(w & 255u, (w >> 8) & 255u, (w >> 16) & 255u, w >> 24); }
 // the lane's index formed where it is used (the zero is opaque: nothing is hoisted or kept in a register across a march).
 // What it prevents: residualZKernel<true> holding threadIdx.x & 63 across its march for the last x-folded store -- 64 VGPRs and
-// 8 B of scratch with the plain-quad branch in the loop, 62 and none with this.  If tools/kres.py shows no scratch there with
-// `lane` in its place, this helper can go.
+// 8 B of scratch with PlaneTile::lane in its place, 62 and none with this (tools/kres.py).
 __device__ __forceinline__ unsigned laneHere()
 {
     unsigned z = 0u;
@@ -430,52 +452,132 @@ __device__ __forceinline__ float4 gLoad4u(const float *base, unsigned cell)  // 
 // register quad the compiler spilled)
 __device__ __forceinline__ float4 keepIf(float4 v, bool keep) { return make_float4(keep ? v.x : 0.f, keep ? v.y : 0.f, keep ? v.z : 0.f, keep ? v.w : 0.f); }
 
+// What a plane march is made of (stencilPlaneKernel, prolongJacobiPlaneKernel, residualZKernel): a tile's coordinates and
+// address rules (PlaneTile), the LDS traffic of a step (stagePlane before the barrier, readStaged behind it) and the arithmetic
+// on the quad (simpleQuad).  What a march keeps to itself is its schedule of global loads -- which are unconditional, their
+// order within a step, how far ahead the codes and the plain words are requested -- and what it does with the result.
+// PlaneCoords: the thread's place in block `bid` of the decomposition (planeTiles).  A workgroup of 64 x kPlaneRows threads owns a
+// tile of kPlaneCols x kPlaneRows cells and the planes [k0, k1); a wave is a row of the tile (ty), a lane a quad of the row; (i, j):
+// the quad's first cell and its row in the grid (past the grid's edge on a ragged tile).
+struct PlaneCoords {
+    unsigned bx, by, bz;
+    int lane, ty, i, j, k0, k1;
+};
+__device__ __forceinline__ void planeCoords(PlaneCoords &t, const GridP &g, unsigned bid, unsigned nbx, unsigned nby, int zc)
+{
+    t.bx = bid % nbx, t.by = (bid / nbx) % nby, t.bz = bid / (nbx * nby);
+    t.lane = threadIdx.x & (kWave - 1), t.ty = threadIdx.x / kWave;
+    t.i = int(t.bx) * kPlaneCols + t.lane * 4, t.j = int(t.by) * kPlaneRows + t.ty;
+    t.k0 = int(t.bz) * zc, t.k1 = min(t.k0 + zc, g.nz);
+}
+struct PlaneTile : PlaneCoords {
+    // threads past the grid edge shadow the last quad / row (ic, jc): their loads stay in bounds, they take part in the barriers,
+    // they do not store.  live: the quad column lies in the level's active x range (GridP::xlo) -- outside it every grid is zero,
+    // staged as zeros, nothing stored; valid: a quad of the grid that is live
+    int ic, jc;
+    bool live, valid;
+    bool rowTop, rowBot, colL, colR;  // the tile's first / last row (they stage the y halo) and lane (the x halo)
+    int nx, ny;
+    ptrdiff_t sz;  // cells of a plane
+    // planes are clamped to what exists: the ghost planes of a slab, else the first / last plane (EXTERIOR shell there: results 0
+    // whatever the neighbours hold)
+    int kLo, kHi;
+    // plain quads (GridP::plainT): the 64 bits of this wave's row and tile in plane k are the word k wPlane + wRow, a wave-uniform
+    // index (the row through readfirstlane: rowS) -- a scalar load; bit = lane
+    unsigned rowS;
+    size_t wRow, wPlane;
+
+    // addresses: the plane's base (scalarBase) + one 32-bit offset inside the plane per thread
+    template <class T>
+    __device__ __forceinline__ T *planeOf(T *p, int k) const { return scalarBase(p + ptrdiff_t(min(max(k, kLo), kHi)) * sz); }
+    __device__ __forceinline__ unsigned off() const { return unsigned(jc) * unsigned(nx) + unsigned(ic); }
+    __device__ __forceinline__ unsigned offYm(unsigned o) const { return jc > 0 ? o - unsigned(nx) : o; }
+    __device__ __forceinline__ unsigned offYp(unsigned o) const { return jc < ny - 1 ? o + unsigned(nx) : o; }
+    // the x-halo cell of the first / last lane (where the grid continues on that side): one unconditional load per wave, the other
+    // lanes re-read their own cell `o` and drop it -- a branch per side made every wave wait for all its loads in flight
+    __device__ __forceinline__ bool hasHx() const { return (colL && ic > 0) || (colR && ic + 4 < nx); }
+    __device__ __forceinline__ unsigned offHx(bool use, unsigned o) const { return !use ? o : (colL ? o - 1u : o + 4u); }
+    __device__ __forceinline__ size_t plainIdx(int k) const { return size_t(k) * wPlane + wRow; }
+};
+__device__ __forceinline__ PlaneTile planeTile(const GridP &g, unsigned nbx, unsigned nby, int zc, const int32_t *__restrict__ blocks)
+{
+    PlaneTile t;
+    unsigned bid = remapBlock(blockIdx.x, gridDim.x);
+    if (blocks) bid = unsigned(blocks[bid]);     // only blocks that hold active cells
+    bid = __builtin_amdgcn_readfirstlane(bid);  // (the plane bases: scalar registers)
+    planeCoords(t, g, bid, nbx, nby, zc);
+    t.nx = g.nx, t.ny = g.ny;
+    t.ic = min(t.i, g.nx - 4), t.jc = min(t.j, g.ny - 1);
+    t.live = t.ic >= g.xlo && t.ic < g.xhi;
+    t.valid = t.i < g.nx && t.j < g.ny && t.live;
+    t.rowTop = t.ty == 0, t.rowBot = t.ty == kPlaneRows - 1, t.colL = t.lane == 0, t.colR = t.lane == kWave - 1;
+    t.sz = ptrdiff_t(g.nx) * g.ny;
+    t.kLo = g.ghostLo ? -1 : 0, t.kHi = g.ghostHi ? g.nz : g.nz - 1;
+    t.rowS = __builtin_amdgcn_readfirstlane(unsigned(t.jc));
+    t.wRow = size_t(t.rowS) * nbx + t.bx, t.wPlane = size_t(g.ny) * nbx;
+    return t;
+}
+// A step's LDS traffic.  `me`: the thread's quad in the step's buffer of the double-buffered tile (one-cell halo, rows of
+// kPlanePitch floats).  Before the barrier a thread stores its quad, the tile's first / last row the y-halo row `hy`, its first /
+// last lane the x-halo cell `hx` (0 where there is none); behind it everybody reads the neighbours back, and from the other
+// buffer (`prev`) its own quad of the step before: the z - 1 values.
+constexpr int kPlaneBufFloats = (kPlaneRows + 2) * kPlanePitch;
+__device__ __forceinline__ void stagePlane(float *me, const PlaneTile &t, float4 xc, float4 hy, float hx, bool useHx)
+{
+    *reinterpret_cast<float4 *>(me) = xc;
+    if (t.rowTop) *reinterpret_cast<float4 *>(me - kPlanePitch) = hy;
+    if (t.rowBot) *reinterpret_cast<float4 *>(me + kPlanePitch) = hy;
+    if (t.colL) me[-1] = useHx ? hx : 0.f;
+    if (t.colR) me[4] = useHx ? hx : 0.f;
+}
+struct StagedPlane {
+    float4 ym, yp, zm;
+    float xl, xr;
+};
+__device__ __forceinline__ StagedPlane readStaged(const float *me, const float *prev)
+{
+    StagedPlane s;
+    s.ym = *reinterpret_cast<const float4 *>(me - kPlanePitch);
+    s.yp = *reinterpret_cast<const float4 *>(me + kPlanePitch);
+    s.zm = *reinterpret_cast<const float4 *>(prev);
+    s.xl = me[-1];
+    s.xr = me[4];
+    return s;
+}
+// A z-folded quad `v` (0 in lanes that own none) folded along x into the lane's two coarse columns and stored in the x-folded
+// layout (XF, below); every lane of the wave comes here (the shuffles).  rzK / seamK: coarse plane K of the grid and of the seam
+// array, offX / seamOff the entries inside it; seamW: a tile's first / last lane at a boundary inside the grid also stores `v`.
+__device__ __forceinline__ void storeXFolded(float4 v, float *rzK, unsigned offX, bool storeX, bool nt, float *seamK, unsigned seamOff, bool seamW)
+{
+    const float2 o = make_float2(foldX4(fromLeftLane(v.w), v.x, v.y, v.z), foldX4(v.y, v.z, v.w, fromRightLane(v.x)));
+    if (storeX) {
+        if (nt) gStore2nt(rzK, offX, o);
+        else gStore2(rzK, offX, o);
+    }
+    if (seamW) gStore4(seamK, seamOff, v);
+}
+
 template <int OP, bool DOT = false, bool XZERO = false>  // XZERO: see stencilQuadKernel
 __global__ __launch_bounds__(64 * kPlaneRows, 8) void stencilPlaneKernel(  // (8 waves per SIMD = two workgroups per CU: at most 64 registers)
-GridP g, float *__restrict__ out,
-                                                                      const float *__restrict__ x,
-                                                                      const float *__restrict__ b, float omega,
-                                                                      unsigned nbx, unsigned nby, unsigned nbz, int zc,
-                                                                      const int32_t *__restrict__ blocks,
-                                                                      double *__restrict__ dotPartials = nullptr)
+    GridP g, float *__restrict__ out, const float *__restrict__ x, const float *__restrict__ b, float omega, unsigned nbx, unsigned nby, unsigned nbz, int zc,
+    const int32_t *__restrict__ blocks, double *__restrict__ dotPartials = nullptr)
 {
     double dotAcc = 0.0;
-    __shared__ float plane[2][(kPlaneRows + 2) * kPlanePitch];
-    unsigned bid = remapBlock(blockIdx.x, gridDim.x);
-    if (blocks) bid = unsigned(blocks[bid]);  // only blocks that hold active cells
-    bid = __builtin_amdgcn_readfirstlane(bid);
-    const unsigned bx = bid % nbx, by = (bid / nbx) % nby, bz = bid / (nbx * nby);
-    const int lane = threadIdx.x & (kWave - 1), ty = threadIdx.x / kWave;
-    const int i = int(bx) * 256 + lane * 4, j = int(by) * kPlaneRows + ty;
-    // threads past the grid edge shadow the last quad / row: their loads stay in bounds, they take
-    // part in the barriers, they do not store
-    const int ic = min(i, g.nx - 4), jc = min(j, g.ny - 1);
-    // quad columns outside the level's active x range (GridP::xlo): zero in every grid, staged as zeros, nothing loaded or stored
-    const bool live = ic >= g.xlo && ic < g.xhi;
-    const bool valid = i < g.nx && j < g.ny && live;
+    __shared__ float plane[2][kPlaneBufFloats];
+    const PlaneTile t = planeTile(g, nbx, nby, zc, blocks);
+    const int k0 = t.k0, k1 = t.k1;
+    const bool live = t.live, valid = t.valid, rowTop = t.rowTop, rowBot = t.rowBot;
     const bool ld = live && !XZERO;
-    const ptrdiff_t sz = ptrdiff_t(g.nx) * g.ny;
-    const int k0 = int(bz) * zc, k1 = min(k0 + zc, g.nz);
-    // addresses: the plane's base (scalarBase) + one 32-bit offset inside the plane per thread.  Planes are clamped to what exists:
-    // the ghost planes of a slab, else the first / last plane (EXTERIOR shell there: results 0 whatever the neighbours hold)
-    const int kLo = g.ghostLo ? -1 : 0, kHi = g.ghostHi ? g.nz : g.nz - 1;
-    const unsigned off = unsigned(jc) * unsigned(g.nx) + unsigned(ic);
-    const unsigned offYm = jc > 0 ? off - unsigned(g.nx) : off, offYp = jc < g.ny - 1 ? off + unsigned(g.nx) : off;
-    auto planeOf = [&](const float *p, int k) { return scalarBase(p + ptrdiff_t(min(max(k, kLo), kHi)) * sz); };
-    const bool rowTop = ty == 0, rowBot = ty == kPlaneRows - 1, colL = lane == 0, colR = lane == kWave - 1;
-    // the x-halo cell of the first / last lane: one unconditional load per wave (the other lanes re-read their own cell and drop
-    // it) -- a branch per side made every wave wait for all its loads in flight before each of the two
-    const bool useHx = ld && ((colL && ic > 0) || (colR && ic + 4 < g.nx));
-    const unsigned offHx = !useHx ? off : (colL ? off - 1u : off + 4u);
+    const unsigned off = t.off(), offYm = t.offYm(off), offYp = t.offYp(off);
+    const bool useHx = ld && t.hasHx();
+    const unsigned offHx = t.offHx(useHx, off);
 
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     constexpr unsigned extW = 0x01010101u * unsigned(MGPS_EXTERIOR_CELL);
-    // plain quads (GridP::plainT): the 64 bits of this wave's row and tile in a plane are one word at a wave-uniform index (the row
-    // through readfirstlane) -- a scalar load, requested a step before the code load it gates; bit = lane.  A lane whose bit is set
-    // takes its codes as 0; a wave of such lanes branches round the load.
+    // plain quads (PlaneTile): the word is requested a step before the code load it gates.  A lane whose bit is set takes its
+    // codes as 0; a wave of such lanes branches round the load.
     const unsigned long long *const pt = g.plainT;
-    const size_t wRow = size_t(__builtin_amdgcn_readfirstlane(unsigned(jc))) * nbx + bx, wPlane = size_t(g.ny) * nbx;
-    unsigned long long pw = pt ? plainWord64(pt, size_t(k0) * wPlane + wRow) : 0ull;
+    unsigned long long pw = pt ? plainWord64(pt, t.plainIdx(k0)) : 0ull;
     // Two planes of a thread's own x quad are in flight at any time: plane k + 2 is requested while plane k is computed, so the
     // plane k + 1 a step needs (its z + 1 neighbours) was requested a whole step earlier; the halo is requested one plane ahead,
     // the rhs and the codes of a plane at the top of its own step (in flight across the barrier).  The z - 1 values of a step are
@@ -483,12 +585,11 @@ GridP g, float *__restrict__ out,
     // (Tried on top and dropped: the four planes in a ring of named registers with the march unrolled four times, every load
     // unconditional and ordered by first use: 1024^3 cycle 10.32 -> 12.22 ms.  Round 4: plane bases in scalar registers, the
     // z - 1 quad out of LDS, no rhs / code look-ahead, the branch-free x-halo load -- no spills left: see residualZKernel.)
-    float *const mine0 = plane[0] + (ty + 1) * kPlanePitch + 4 + lane * 4;
-    constexpr int kBufFloats = (kPlaneRows + 2) * kPlanePitch;
-    *reinterpret_cast<float4 *>(mine0 + kBufFloats) = ld ? gLoad4(planeOf(x, k0 - 1), off) : zero4;
-    const float *xk = XZERO ? x : planeOf(x, k0);
+    float *const mine0 = plane[0] + (t.ty + 1) * kPlanePitch + 4 + t.lane * 4;
+    *reinterpret_cast<float4 *>(mine0 + kPlaneBufFloats) = ld ? gLoad4(t.planeOf(x, k0 - 1), off) : zero4;
+    const float *xk = XZERO ? x : t.planeOf(x, k0);
     float4 xc = ld ? gLoad4(xk, off) : zero4;
-    float4 xp = ld ? gLoad4(planeOf(x, k0 + 1), off) : zero4;
+    float4 xp = ld ? gLoad4(t.planeOf(x, k0 + 1), off) : zero4;
     float4 hy = zero4;  // y-halo row this thread stages (top / bottom rows only)
     if (ld && rowTop) hy = gLoad4(xk, offYm);
     if (ld && rowBot) hy = gLoad4(xk, offYp);
@@ -496,53 +597,36 @@ GridP g, float *__restrict__ out,
 
     int buf = 0;
     for (int k = k0; k < k1; ++k) {
-        float *me = mine0 + buf * kBufFloats;
-        *reinterpret_cast<float4 *>(me) = xc;
-        if (rowTop) *reinterpret_cast<float4 *>(me - kPlanePitch) = hy;
-        if (rowBot) *reinterpret_cast<float4 *>(me + kPlanePitch) = hy;
-        if (colL) me[-1] = useHx ? hx : 0.f;
-        if (colR) me[4] = useHx ? hx : 0.f;
+        float *me = mine0 + buf * kPlaneBufFloats;
+        stagePlane(me, t, xc, hy, hx, useHx);
         float4 bc = zero4;
         unsigned lcw = extW;
         if (live) {
-            if (OP != OP_APPLY) bc = gLoad4nt(scalarBase(b + ptrdiff_t(k) * sz), off);
+            if (OP != OP_APPLY) bc = gLoad4nt(scalarBase(b + ptrdiff_t(k) * t.sz), off);
             lcw = 0u;
-            if (!plainLane(pw)) lcw = gLoadCodesWnt(scalarBase(g.lab + ptrdiff_t(k) * sz), off);
+            if (!plainLane(pw)) lcw = gLoadCodesWnt(scalarBase(g.lab + ptrdiff_t(k) * t.sz), off);
         }
-        if (pt) pw = plainWord64(pt, size_t(min(k + 1, g.nz - 1)) * wPlane + wRow);  // (the next step's)
+        if (pt) pw = plainWord64(pt, t.plainIdx(min(k + 1, g.nz - 1)));  // (the next step's)
         // the plane after the next one (own quad); the next plane's halo
         float4 xq = zero4, hyn = hy;
         float hxn = hx;
         if (k + 1 < k1 && ld) {  // (the last step's z + 1 plane is already here: xp)
-            const float *xn = planeOf(x, k + 1);
-            xq = gLoad4(planeOf(x, k + 2), off);
+            const float *xn = t.planeOf(x, k + 1);
+            xq = gLoad4(t.planeOf(x, k + 2), off);
             if (rowTop) hyn = gLoad4(xn, offYm);
             if (rowBot) hyn = gLoad4(xn, offYp);
             hxn = gLoad1(xn, offHx);
         }
         __syncthreads();
-        const float4 ym = *reinterpret_cast<const float4 *>(me - kPlanePitch);
-        const float4 yp = *reinterpret_cast<const float4 *>(me + kPlanePitch);
-        const float4 xm = *reinterpret_cast<const float4 *>(mine0 + (buf ^ 1) * kBufFloats);
-        const float xs[6] = {me[-1], xc.x, xc.y, xc.z, xc.w, me[4]};
-        const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
-        const float zms[4] = {xm.x, xm.y, xm.z, xm.w}, zps[4] = {xp.x, xp.y, xp.z, xp.w};
-        const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
-        const uchar4 lc = codes4(lcw);
-        const unsigned ls[4] = {lc.x, lc.y, lc.z, lc.w};
+        const StagedPlane n = readStaged(me, mine0 + (buf ^ 1) * kPlaneBufFloats);
         float res[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float diag = simpleDiag(ls[e]);
-            const float lap = diag * xs[e + 1] - (xs[e] + xs[e + 2] + yms[e] + yps[e] + zms[e] + zps[e]);
-            res[e] = simpleCell(ls[e]) ? epilogueRcp<OP>(xs[e + 1], bs[e], lap, simpleRcp(diag), omega) : inactiveValue<OP>(xs[e + 1]);
-        }
+        simpleQuad<OP>(n.xl, xc, n.xr, n.ym, n.yp, n.zm, xp, bc, lcw, omega, res);
         if (valid)  // streamed out: nothing re-reads the sweep's output before it has left the caches (+5 % at 1024^3)
-            gStore4nt(scalarBase(out + ptrdiff_t(k) * sz), off, make_float4(res[0], res[1], res[2], res[3]));
+            gStore4nt(scalarBase(out + ptrdiff_t(k) * t.sz), off, make_float4(res[0], res[1], res[2], res[3]));
         if (DOT) {
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (valid && simpleCell(ls[e])) dotAcc += dotTerm<OP>(xs[e + 1], bs[e], res[e]);
+                if (valid && simpleCell((lcw >> (8 * e)) & 255u)) dotAcc += dotTerm<OP>(comp(xc, e), comp(bc, e), res[e]);
         }
         xc = xp;
         xp = xq;
@@ -575,8 +659,8 @@ GridP g, float *__restrict__ out,
 //     with an inactive face neighbour can read a wrong halo value, and no such cell keeps this launch's result -- it is either
 //     inactive (its own value is written) or a BOUNDARY cell, and every BOUNDARY cell lies in the band closure, which the plain
 //     band launch after this one rewrites (the same invariant lets the sweep run with nbnd = 0; LABNOTES R5).
-// Bits: the lerps are lerpRef's (pinned fma), in the order of prolongAddBlockKernel (x, y, z, then x + 4 t), the epilogue is
-// stencilPlaneKernel's: the output equals "launchProlongAdd, then launchStencil(OP_JACOBI)" bit for bit.
+// Bits: the lerps are lerpRef's (pinned fma), in the order of prolongAddBlockKernel (x, y, z, then x + 4 t), tile, staging and
+// arithmetic are stencilPlaneKernel's (PlaneTile, stagePlane / readStaged, simpleQuad): the output equals "launchProlongAdd, then launchStencil(OP_JACOBI)" bit for bit.
 // Needs an even march depth (zc) and even extents; no slab ghost planes (prolongJacobiPlaneFits).  Resources: 63 VGPRs at 8 waves
 // per SIMD, no scratch, 69 696 B of LDS (two workgroups per CU).
 // ---------------------------------------------------------------------------------------------
@@ -589,25 +673,15 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
                                                                               const float *__restrict__ b, const float *__restrict__ coarse, float omega,
                                                                               unsigned nbx, unsigned nby, int zc, const int32_t *__restrict__ blocks)
 {
-    __shared__ float plane[2][(kPlaneRows + 2) * kPlanePitch];
+    __shared__ float plane[2][kPlaneBufFloats];
     __shared__ float crow[kUpRing][kUpRows * kPlanePitch];  // coarse rows lerped along x; fine column i at 4 + i - i0, as in `plane`
-    unsigned bid = remapBlock(blockIdx.x, gridDim.x);
-    if (blocks) bid = unsigned(blocks[bid]);
-    bid = __builtin_amdgcn_readfirstlane(bid);
-    const unsigned bx = bid % nbx, by = (bid / nbx) % nby, bz = bid / (nbx * nby);
-    const int lane = threadIdx.x & (kWave - 1), ty = threadIdx.x / kWave;
-    const int i = int(bx) * 256 + lane * 4, j = int(by) * kPlaneRows + ty;
-    const int ic = min(i, g.nx - 4), jc = min(j, g.ny - 1);
-    const bool live = ic >= g.xlo && ic < g.xhi;
-    const bool valid = i < g.nx && j < g.ny && live;
-    const ptrdiff_t sz = ptrdiff_t(g.nx) * g.ny;
-    const int k0 = int(bz) * zc, k1 = min(k0 + zc, g.nz);
-    const unsigned off = unsigned(jc) * unsigned(g.nx) + unsigned(ic);
-    const unsigned offYm = jc > 0 ? off - unsigned(g.nx) : off, offYp = jc < g.ny - 1 ? off + unsigned(g.nx) : off;
-    auto planeOf = [&](const float *p, int k) { return scalarBase(p + ptrdiff_t(min(max(k, 0), g.nz - 1)) * sz); };
-    const bool rowTop = ty == 0, rowBot = ty == kPlaneRows - 1, colL = lane == 0, colR = lane == kWave - 1;
-    const bool useHx = live && ((colL && ic > 0) || (colR && ic + 4 < g.nx));
-    const unsigned offHx = !useHx ? off : (colL ? off - 1u : off + 4u);
+    const PlaneTile t = planeTile(g, nbx, nby, zc, blocks);  // (no ghost planes here: kLo = 0, kHi = nz - 1)
+    const unsigned bx = t.bx, by = t.by;
+    const int lane = t.lane, j = t.j, k0 = t.k0, k1 = t.k1;
+    const bool live = t.live, valid = t.valid, rowTop = t.rowTop, rowBot = t.rowBot, colL = t.colL;
+    const unsigned off = t.off(), offYm = t.offYm(off), offYp = t.offYp(off);
+    const bool useHx = live && t.hasHx();
+    const unsigned offHx = t.offHx(useHx, off);
     // (every 32-bit offset goes through `opq` where a load uses it: otherwise the loop optimiser hoists its 64-bit zero extension
     // out of the march -- two registers per offset, and the saddr + voffset form of the loads is lost; that alone spilled 16 VGPRs)
     auto opq = [](unsigned v) {
@@ -680,23 +754,21 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
             stageC((k0 >> 1) + 1, c2);
         }
     }
-    float *const mine0 = plane[0] + (ty + 1) * kPlanePitch + 4 + lane * 4;
-    constexpr int kBufFloats = (kPlaneRows + 2) * kPlanePitch;
-    float4 xm0 = live ? gLoad4(planeOf(x, k0 - 1), off) : zero4;
-    const float *xk = planeOf(x, k0);
+    float *const mine0 = plane[0] + (t.ty + 1) * kPlanePitch + 4 + lane * 4;
+    float4 xm0 = live ? gLoad4(t.planeOf(x, k0 - 1), off) : zero4;
+    const float *xk = t.planeOf(x, k0);
     float4 xc = live ? gLoad4(xk, off) : zero4;
-    float4 xp = live ? gLoad4(planeOf(x, k0 + 1), off) : zero4;
+    float4 xp = live ? gLoad4(t.planeOf(x, k0 + 1), off) : zero4;
     // plain quads (GridP::plainT, see stencilPlaneKernel).  The codes are requested two planes ahead, their words three
     const unsigned long long *const pt = g.plainT;
-    const size_t wRow = size_t(__builtin_amdgcn_readfirstlane(unsigned(jc))) * nbx + bx, wPlane = size_t(g.ny) * nbx;
-    auto plainAt = [&](int kk) { return pt ? plainWord64(pt, size_t(min(kk, g.nz - 1)) * wPlane + wRow) : 0ull; };
+    auto plainAt = [&](int kk) { return pt ? plainWord64(pt, t.plainIdx(min(kk, g.nz - 1))) : 0ull; };
     const unsigned long long pw0 = plainAt(k0), pw1 = plainAt(k0 + 1);
     unsigned long long pw = plainAt(k0 + 2);  // (of the plane whose codes the step requests)
     constexpr unsigned extW = 0x01010101u * unsigned(MGPS_EXTERIOR_CELL);
-    const uint8_t *lab0 = scalarBase(g.lab + ptrdiff_t(k0) * sz);
+    const uint8_t *lab0 = scalarBase(g.lab + ptrdiff_t(k0) * t.sz);
     unsigned lc = live ? 0u : extW, lcn = lc;  // codes of the step's plane and of the next one, four to a word
     if (live && !plainLane(pw0)) lc = gLoadCodesWnt(lab0, off);
-    if (live && !plainLane(pw1)) lcn = gLoadCodesWnt(scalarBase(g.lab + ptrdiff_t(k0 + 1) * sz), off);
+    if (live && !plainLane(pw1)) lcn = gLoadCodesWnt(scalarBase(g.lab + ptrdiff_t(k0 + 1) * t.sz), off);
     float4 hy = zero4;
     if (live && rowTop) hy = gLoad4(xk, offYm);
     if (live && rowBot) hy = gLoad4(xk, offYp);
@@ -706,29 +778,25 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
         xm0 = corr4(k0 - 1, j, xm0, lc, false);
         xc = corr4(k0, j, xc, lc, true);
     }
-    *reinterpret_cast<float4 *>(mine0 + kBufFloats) = xm0;
+    *reinterpret_cast<float4 *>(mine0 + kPlaneBufFloats) = xm0;
 
     // Step k: before the barrier the halo of plane k and the own quad of plane k + 1 take their corrections (from coarse planes
     // (k - 1) >> 1 .. (k >> 1) + 1, staged before the previous barrier); an even step requests coarse plane k/2 + 2 and stages
     // it right after its barrier, into the slot whose last reader was this step's halo.
     int buf = 0;
     for (int k = k0; k < k1; ++k) {
-        float *me = mine0 + buf * kBufFloats;
+        float *me = mine0 + buf * kPlaneBufFloats;
         if (live) {
             if (rowTop) hy = corr4(k, j - 1, hy, lc, false);
             if (rowBot) hy = corr4(k, j + 1, hy, lc, false);
             if (useHx) hx = corr1(k, j, hx);
             xp = corr4(k + 1, j, xp, lcn, k + 1 < k1);  // (plane k1 is this block's z + 1 neighbour only)
         }
-        *reinterpret_cast<float4 *>(me) = xc;
-        if (rowTop) *reinterpret_cast<float4 *>(me - kPlanePitch) = hy;
-        if (rowBot) *reinterpret_cast<float4 *>(me + kPlanePitch) = hy;
-        if (colL) me[-1] = useHx ? hx : 0.f;
-        if (colR) me[4] = useHx ? hx : 0.f;
+        stagePlane(me, t, xc, hy, hx, useHx);
         float4 bc = zero4;
         unsigned lcq = extW;  // codes of plane k + 2
-        const float *bk = scalarBase(b + ptrdiff_t(k) * sz);
-        const uint8_t *labq = scalarBase(g.lab + ptrdiff_t(min(k + 2, g.nz - 1)) * sz);
+        const float *bk = scalarBase(b + ptrdiff_t(k) * t.sz);
+        const uint8_t *labq = scalarBase(g.lab + ptrdiff_t(min(k + 2, g.nz - 1)) * t.sz);
         if (live) {
             bc = gLoad4nt(bk, opq(off));
             if (k + 2 < k1) {
@@ -740,8 +808,8 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
         float4 xq = zero4, hyn = hy;
         float hxn = hx;
         if (k + 1 < k1 && live) {
-            const float *xn = planeOf(x, k + 1);
-            xq = gLoad4(planeOf(x, k + 2), opq(off));
+            const float *xn = t.planeOf(x, k + 1);
+            xq = gLoad4(t.planeOf(x, k + 2), opq(off));
             if (rowTop) hyn = gLoad4(xn, opq(offYm));
             if (rowBot) hyn = gLoad4(xn, opq(offYp));
             hxn = gLoad1(xn, opq(offHx));
@@ -752,23 +820,10 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
         if (stageNext && stager) cnext = loadC(pn);
         __syncthreads();
         if (stageNext && stager) stageC((k >> 1) + 2, cnext);
-        const float4 ym = *reinterpret_cast<const float4 *>(me - kPlanePitch);
-        const float4 yp = *reinterpret_cast<const float4 *>(me + kPlanePitch);
-        const float4 xm = *reinterpret_cast<const float4 *>(mine0 + (buf ^ 1) * kBufFloats);
-        const float xs[6] = {me[-1], xc.x, xc.y, xc.z, xc.w, me[4]};
-        const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
-        const float zms[4] = {xm.x, xm.y, xm.z, xm.w}, zps[4] = {xp.x, xp.y, xp.z, xp.w};
-        const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
-        const uchar4 lc4 = codes4(lc);
-        const unsigned ls[4] = {lc4.x, lc4.y, lc4.z, lc4.w};
+        const StagedPlane n = readStaged(me, mine0 + (buf ^ 1) * kPlaneBufFloats);
         float res[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float diag = simpleDiag(ls[e]);
-            const float lap = diag * xs[e + 1] - (xs[e] + xs[e + 2] + yms[e] + yps[e] + zms[e] + zps[e]);
-            res[e] = simpleCell(ls[e]) ? epilogueRcp<OP_JACOBI>(xs[e + 1], bs[e], lap, simpleRcp(diag), omega) : inactiveValue<OP_JACOBI>(xs[e + 1]);
-        }
-        if (valid) gStore4nt(scalarBase(out + ptrdiff_t(k) * sz), opq(off), make_float4(res[0], res[1], res[2], res[3]));
+        simpleQuad<OP_JACOBI>(n.xl, xc, n.xr, n.ym, n.yp, n.zm, xp, bc, lc, omega, res);
+        if (valid) gStore4nt(scalarBase(out + ptrdiff_t(k) * t.sz), opq(off), make_float4(res[0], res[1], res[2], res[3]));
         xc = xp;
         xp = xq;
         hy = hyn;
@@ -802,7 +857,7 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void prolongJacobiPlaneKernel(G
 // or the grid) hold another quad's values and pass 0; a lane next to the range stores too (its columns take a term from the live
 // neighbour, as they do in the full-resolution layout).  A tile is a wave wide: the columns that straddle a tile boundary
 // (I = 128 s - 1 and 128 s, fine 256 s - 3 .. 256 s + 2) are not formed here -- lane 63 and lane 0 on either side also store their
-// z-folded quads into `seam` (8 floats per interior boundary s, row and coarse plane: [K][j][s - 1][8]), restrictYKernel folds
+// z-folded quads into `seam` (8 floats per interior boundary s, row and coarse plane: SeamLayout), restrictYKernel folds
 // those two columns from there with the same foldX4 and never reads their rzx entries.
 template <bool XF>
 __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, float *__restrict__ rz, const float *__restrict__ x,
@@ -810,20 +865,12 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
                                                                      const int32_t *__restrict__ blocks, const float *__restrict__ rEdge,
                                                                      float *__restrict__ seam)
 {
-    __shared__ float plane[2][(kPlaneRows + 2) * kPlanePitch];
-    unsigned bid = remapBlock(blockIdx.x, gridDim.x);
-    if (blocks) bid = unsigned(blocks[bid]);  // (blocks without active cells: residualZEdgeKernel writes what they owe rz)
-    bid = __builtin_amdgcn_readfirstlane(bid);  // (the plane bases below: scalar registers)
-    const unsigned bx = bid % nbx, by = (bid / nbx) % nby, bz = bid / (nbx * nby);
-    const int lane = threadIdx.x & (kWave - 1), ty = threadIdx.x / kWave;
-    const int i = int(bx) * 256 + lane * 4, j = int(by) * kPlaneRows + ty;
-    const int ic = min(i, g.nx - 4), jc = min(j, g.ny - 1);
-    const bool live = ic >= g.xlo && ic < g.xhi;
-    const bool valid = i < g.nx && j < g.ny && live;
-    const size_t sz = size_t(g.nx) * g.ny;
-    const int k0 = int(bz) * zc, k1 = min(k0 + zc, g.nz);  // both even
+    __shared__ float plane[2][kPlaneBufFloats];
+    const PlaneTile t = planeTile(g, nbx, nby, zc, blocks);  // (blocks without active cells: residualZEdgeKernel writes what they owe rz)
+    const bool live = t.live, valid = t.valid, rowTop = t.rowTop, rowBot = t.rowBot, colL = t.colL, colR = t.colR;
+    const size_t sz = size_t(t.sz);
+    const int k0 = t.k0, k1 = t.k1;  // both even
     const int ks = max(k0 - 1, 0), ke = min(k1, g.nz - 1);   // planes outside the grid: r = 0, nothing to add
-    // addresses: the plane's base (wave-uniform: scalar registers) + one 32-bit offset inside the plane per thread
     // Round 5: the loads of x and of the rhs are UNCONDITIONAL.  A lane outside the active x range (`live`) aims at the nearest quad
     // of the range in its row -- a line the wave fetches anyway -- and what arrives is dropped where it is used; the wave of a middle
     // row re-reads its own quad as its "y halo".  With no lane-dependent branch around them the compiler can count them (round 4: a
@@ -833,29 +880,20 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
     // loads for the next planes (x halo, the y halo on the tile's first / last wave, the quad two planes ahead) stay in flight
     // across the arithmetic, as before.
     // (a live lane's own quad IS that quad: offL serves its stores as well)
-    const unsigned offL = unsigned(jc) * unsigned(g.nx) + unsigned(min(max(ic, g.xlo), max(g.xhi - 4, g.xlo)));
-    const bool rowTop = ty == 0, rowBot = ty == kPlaneRows - 1, colL = lane == 0, colR = lane == kWave - 1;
-    const bool hasL = ic > 0, hasR = ic + 4 < g.nx;  // (the grid continues on that side)
-    // (planes clamped to what exists -- the ghost planes of a slab, else the grid: the first and the last plane of a whole-grid level
-    // are EXTERIOR shell, whose results are 0 whatever their neighbours hold -- the assumption stencilPlaneKernel makes at the faces)
-    const int kLo = g.ghostLo ? -1 : 0, kHi = g.ghostHi ? g.nz : g.nz - 1;
-    auto planeOf = [&](const float *p, int k) { return scalarBase(p + ptrdiff_t(min(max(k, kLo), kHi)) * ptrdiff_t(sz)); };
-    float *const mine0 = plane[0] + (ty + 1) * kPlanePitch + 4 + lane * 4;
-    constexpr int kBufFloats = (kPlaneRows + 2) * kPlanePitch;
+    const unsigned offL = unsigned(t.jc) * unsigned(g.nx) + unsigned(min(max(t.ic, g.xlo), max(g.xhi - 4, g.xlo)));
+    float *const mine0 = plane[0] + (t.ty + 1) * kPlanePitch + 4 + t.lane * 4;
     // the y-halo row a wave stages: the row above the tile (its first wave), below it (its last), else its own quad again
-    const unsigned offHy = (rowTop && jc > 0) ? offL - unsigned(g.nx) : (rowBot && jc < g.ny - 1) ? offL + unsigned(g.nx) : offL;
+    const unsigned offHy = (rowTop && t.jc > 0) ? offL - unsigned(g.nx) : (rowBot && t.jc < g.ny - 1) ? offL + unsigned(g.nx) : offL;
     {  // plane ks - 1 of the thread's own quad: the z - 1 values of a step are read back from the LDS buffer of the step before
-        const float4 xm = gLoad4(planeOf(x, ks - 1), offL);
-        *reinterpret_cast<float4 *>(mine0 + kBufFloats) = keepIf(xm, live);
+        const float4 xm = gLoad4(t.planeOf(x, ks - 1), offL);
+        *reinterpret_cast<float4 *>(mine0 + kPlaneBufFloats) = keepIf(xm, live);
     }
-    const float *xk = planeOf(x, ks);
+    const float *xk = t.planeOf(x, ks);
     float4 xc = gLoad4(xk, offL);
-    float4 xp = gLoad4(planeOf(x, ks + 1), offL);
+    float4 xp = gLoad4(t.planeOf(x, ks + 1), offL);
     float4 hy = gLoad4(xk, offHy);
-    // the x-halo cell of the first / last lane: one unconditional load per wave (the other lanes re-read their own cell and drop it)
-    // -- a branch per side made every wave wait for all its loads in flight before each of the two
-    const bool useHx = live && ((colL && hasL) || (colR && hasR));
-    const unsigned offHx = !useHx ? offL : colL ? offL - 1u : offL + 4u;
+    const bool useHx = live && t.hasHx();
+    const unsigned offHx = t.offHx(useHx, offL);
     float hx = gLoad1(xk, offHx);  // (lanes without such a cell: whatever arrives is dropped where hx is staged -- a select here
                                                 // would wait for the load, the last one requested, and with it for every load in flight)
     constexpr float w0 = 0.125f, w1 = 0.375f, w2 = 0.375f, w3 = 0.125f;
@@ -863,22 +901,16 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
     float accPrev[4] = {0.f, 0.f, 0.f, 0.f}, accCur[4] = {0.f, 0.f, 0.f, 0.f};
     // XF: where this lane's two coarse columns go, who stores them, and the seam entry of a tile's first / last lane
     // (offsets formed at the store from a scalar row base -- the row is the wave's -- and the lane: no register held across the march)
-    const unsigned rowS = __builtin_amdgcn_readfirstlane(unsigned(jc));
-    const unsigned rowX = rowS * (unsigned(g.nx) >> 1) + bx * 128u, rowSeam = (rowS * (nbx - 1u) + bx) * 8u;
-    const bool storeX = i < g.nx && j < g.ny && ic >= g.xlo - 4 && ic < g.xhi + 4;
-    const bool seamL = colL && bx > 0, seamR = colR && i + 4 < g.nx;  // (the boundary at fine x = 256 bx / 256 (bx + 1) is inside the grid)
+    const unsigned rowX = t.rowS * (unsigned(g.nx) >> 1) + t.bx * 128u;
+    const bool storeX = t.i < g.nx && t.j < g.ny && t.ic >= g.xlo - 4 && t.ic < g.xhi + 4;
+    const bool seamL = colL && t.bx > 0, seamR = colR && t.i + 4 < g.nx;  // (the boundary at fine x = 256 bx / 256 (bx + 1) is inside the grid)
     const bool seamW = valid && (seamL || seamR);
-    auto storeFolded = [&](int K, bool nt) {  // (every lane of the wave comes here: the shuffles)
+    const SeamLayout sl = seamLayout(g.nx, g.ny);
+    auto storeFolded = [&](int K, bool nt) {  // (every lane of the wave comes here)
         const float4 v = keepIf(make_float4(accPrev[0], accPrev[1], accPrev[2], accPrev[3]), valid);
-        const float2 o = make_float2(foldX4(fromLeftLane(v.w), v.x, v.y, v.z), foldX4(v.y, v.z, v.w, fromRightLane(v.x)));
-        float *const px = scalarBase(rz + size_t(K) * (sz >> 1));
-        if (storeX) {
-            const unsigned offX = rowX + 2u * laneHere();  // (a wave is a row of the tile)
-            if (nt) gStore2nt(px, offX, o);
-            else gStore2(px, offX, o);
-        }
-        // (lane 63: the first quad of boundary bx + 1's entry, lane 0: the second quad of boundary bx's)
-        if (seamW) gStore4(scalarBase(seam + size_t(K) * size_t(g.ny) * size_t(nbx - 1u) * 8u), colL ? rowSeam - 4u : rowSeam, v);
+        // (a wave is a row of the tile.  Lane 63: side 0 of boundary bx + 1, lane 0: side 1 of boundary bx)
+        storeXFolded(v, scalarBase(rz + size_t(K) * (sz >> 1)), rowX + 2u * laneHere(), storeX, nt, scalarBase(seam + size_t(K) * sl.planeFloats()),
+                     colL ? sl.entry(t.rowS, t.bx, 1u) : sl.entry(t.rowS, t.bx + 1u, 0u), seamW);
     };
     if (rEdge && k0 == 0 && g.ghostLo) {  // the neighbour's r on the plane below the slab: the first term of coarse plane 0 (wave-uniform branch)
         const float4 e = gLoad4(scalarBase(rEdge - ptrdiff_t(sz)), offL);
@@ -890,26 +922,21 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
     // plain quads (GridP::plainT, see stencilPlaneKernel): the lane's own bit.  A lane outside the active x range or the grid has
     // none set (EXTERIOR cells, or past the end of the row) and loads the codes offL aims at as before; nothing of them is kept
     const unsigned long long *const pt = g.plainT;
-    const size_t wRow = size_t(rowS) * nbx + bx, wPlane = size_t(g.ny) * nbx;
-    unsigned long long pw = pt ? plainWord64(pt, size_t(ks) * wPlane + wRow) : 0ull;
+    unsigned long long pw = pt ? plainWord64(pt, t.plainIdx(ks)) : 0ull;
     int buf = 0;
     for (int k = ks; k <= ke; ++k) {
-        float *me = mine0 + buf * kBufFloats;
+        float *me = mine0 + buf * kPlaneBufFloats;
         xc = keepIf(xc, live);  // (what the neighbours read of a quad outside the range is 0; its own results are never stored)
-        *reinterpret_cast<float4 *>(me) = xc;
-        if (rowTop) *reinterpret_cast<float4 *>(me - kPlanePitch) = keepIf(hy, live);
-        if (rowBot) *reinterpret_cast<float4 *>(me + kPlanePitch) = keepIf(hy, live);
-        if (colL) me[-1] = useHx ? hx : 0.f;
-        if (colR) me[4] = useHx ? hx : 0.f;
+        stagePlane(me, t, xc, keepIf(hy, live), hx, useHx);
         // this plane's rhs and codes (in flight across the barrier), the own quad two planes ahead, the next plane's halo
-        const float *bk = planeOf(b, k);
+        const float *bk = t.planeOf(b, k);
         const uint8_t *lk = scalarBase(g.lab + size_t(k) * sz);
-        const float *xn = planeOf(x, k + 1), *xq2 = planeOf(x, k + 2);
+        const float *xn = t.planeOf(x, k + 1), *xq2 = t.planeOf(x, k + 2);
         // (the codes first: the one branch round a load -- a wave of plain quads issues none -- and the other loads stay in one block;
         // then the rhs, unconditional: see offL.  Past the last plane the bases are clamped, what arrives is never used)
         unsigned lcw = 0u;
         if (!plainLane(pw)) lcw = gLoadCodesWnt(lk, offL);
-        if (pt) pw = plainWord64(pt, size_t(min(k + 1, g.nz - 1)) * wPlane + wRow);  // (the next step's)
+        if (pt) pw = plainWord64(pt, t.plainIdx(min(k + 1, g.nz - 1)));  // (the next step's)
         const float4 bc = gLoad4nt(bk, offL);
         // (in the order of their use: the halo of the next plane is staged at the top of the next step, the quad two planes ahead is
         // needed behind the next barrier -- requested last, it is the one left in flight across the top of the loop)
@@ -918,22 +945,9 @@ __global__ __launch_bounds__(64 * kPlaneRows, 8) void residualZKernel(GridP g, f
         if (rowTop || rowBot) hyn = gLoad4(xn, offHy);  // (wave-uniform: the tile's first and last wave only)
         const float4 xq = gLoad4(xq2, offL);
         __syncthreads();
-        const float4 ym = *reinterpret_cast<const float4 *>(me - kPlanePitch);
-        const float4 yp = *reinterpret_cast<const float4 *>(me + kPlanePitch);
-        const float4 xm = *reinterpret_cast<const float4 *>(mine0 + (buf ^ 1) * kBufFloats);  // (this thread's own store of the last step)
-        const float xs[6] = {me[-1], xc.x, xc.y, xc.z, xc.w, me[4]};
-        const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
-        const float zms[4] = {xm.x, xm.y, xm.z, xm.w}, zps[4] = {xp.x, xp.y, xp.z, xp.w};
-        const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
-        const uchar4 lc = codes4(lcw);
-        const unsigned ls[4] = {lc.x, lc.y, lc.z, lc.w};
+        const StagedPlane n = readStaged(me, mine0 + (buf ^ 1) * kPlaneBufFloats);
         float res[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {  // the arithmetic of stencilPlaneKernel<OP_RESIDUAL>
-            const float diag = simpleDiag(ls[e]);
-            const float lap = diag * xs[e + 1] - (xs[e] + xs[e + 2] + yms[e] + yps[e] + zms[e] + zps[e]);
-            res[e] = simpleCell(ls[e]) ? epilogueRcp<OP_RESIDUAL>(xs[e + 1], bs[e], lap, simpleRcp(diag), 0.f) : inactiveValue<OP_RESIDUAL>(xs[e + 1]);
-        }
+        simpleQuad<OP_RESIDUAL>(n.xl, xc, n.xr, n.ym, n.yp, n.zm, xp, bc, lcw, 0.f, res);
         // the fold along z, terms in the order of the planes: plane 2 m + 1 is the third term of coarse plane m and the first of
         // m + 1, plane 2 m the second term of m and the last of m - 1
         if (k & 1) {
@@ -989,14 +1003,13 @@ __global__ __launch_bounds__(64 * kPlaneRows) void residualZEdgeKernel(GridP g, 
                                                                       float *__restrict__ seam)
 {
     // edges[w] = 2 * block + side: the blocks without active cells whose neighbour below (side 0) / above (side 1) has some
-    const unsigned bid = unsigned(edges[blockIdx.x]) >> 1, side = unsigned(edges[blockIdx.x]) & 1u;
-    const unsigned bx = bid % nbx, by = (bid / nbx) % nby, bz = bid / (nbx * nby);
-    const int k0 = int(bz) * zc, k1 = min(k0 + zc, g.nz);
-    const int k = side == 0 ? k0 - 1 : k1, K = side == 0 ? (k0 >> 1) : (k1 >> 1) - 1;
+    const unsigned side = unsigned(edges[blockIdx.x]) & 1u;
+    PlaneCoords t;
+    planeCoords(t, g, unsigned(edges[blockIdx.x]) >> 1, nbx, nby, zc);
+    const int lane = t.lane, i = t.i, j = t.j;
+    const int k = side == 0 ? t.k0 - 1 : t.k1, K = side == 0 ? (t.k0 >> 1) : (t.k1 >> 1) - 1;
     const float wz = 0.125f;  // w0 = w3
     if (k < 0 || k >= g.nz) return;
-    const int lane = threadIdx.x & (kWave - 1), ty = threadIdx.x / kWave;
-    const int i = int(bx) * 256 + lane * 4, j = int(by) * kPlaneRows + ty;
     if (j >= g.ny) return;                 // (a whole wavefront row)
     if (!XF && i >= g.nx) return;          // (lanes past nx: no shuffle partner needs them)
     const bool live = i < g.nx && i >= g.xlo && i < g.xhi;
@@ -1014,29 +1027,19 @@ __global__ __launch_bounds__(64 * kPlaneRows) void residualZEdgeKernel(GridP g, 
     if (lane == 0) left = (live && i > 0) ? x[c - 1] : 0.f;
     if (lane == kWave - 1 || i + 4 >= g.nx) right = (live && i + 4 < g.nx) ? x[c + 4] : 0.f;
     if (!XF && !live) return;
-    const float xs[6] = {left, xc.x, xc.y, xc.z, xc.w, right};
-    const float yms[4] = {ym.x, ym.y, ym.z, ym.w}, yps[4] = {yp.x, yp.y, yp.z, yp.w};
-    const float zms[4] = {zm.x, zm.y, zm.z, zm.w}, zps[4] = {zp.x, zp.y, zp.z, zp.w};
-    const float bs[4] = {bc.x, bc.y, bc.z, bc.w};
-    const unsigned ls[4] = {labw & 255u, (labw >> 8) & 255u, (labw >> 16) & 255u, labw >> 24};
     float res[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {  // the arithmetic of stencil...Kernel<OP_RESIDUAL>, then the one z weight
-        const float diag = simpleDiag(ls[e]);
-        const float lap = diag * xs[e + 1] - (xs[e] + xs[e + 2] + yms[e] + yps[e] + zms[e] + zps[e]);
-        const float r = simpleCell(ls[e]) ? epilogueRcp<OP_RESIDUAL>(xs[e + 1], bs[e], lap, simpleRcp(diag), 0.f) : inactiveValue<OP_RESIDUAL>(xs[e + 1]);
-        res[e] = wz * r;
-    }
+    simpleQuad<OP_RESIDUAL>(left, xc, right, ym, yp, zm, zp, bc, labw, 0.f, res);
+    const float4 wr = make_float4(wz * res[0], wz * res[1], wz * res[2], wz * res[3]);  // (the one z weight)
     if (!XF) {
-        *reinterpret_cast<float4 *>(rz + size_t(K) * sz + size_t(j) * sy + i) = make_float4(res[0], res[1], res[2], res[3]);
+        *reinterpret_cast<float4 *>(rz + size_t(K) * sz + size_t(j) * sy + i) = wr;
         return;
     }
-    const float4 v = keepIf(make_float4(res[0], res[1], res[2], res[3]), live);
-    const float2 o = make_float2(foldX4(fromLeftLane(v.w), v.x, v.y, v.z), foldX4(v.y, v.z, v.w, fromRightLane(v.x)));
-    if (i < g.nx && i >= g.xlo - 4 && i < g.xhi + 4) *reinterpret_cast<float2 *>(rz + size_t(K) * (sz >> 1) + size_t(j) * (sy >> 1) + size_t(i >> 1)) = o;
-    const bool seamL = lane == 0 && bx > 0, seamR = lane == kWave - 1 && i + 4 < g.nx;
-    if (live && (seamL || seamR))
-        *reinterpret_cast<float4 *>(seam + ((size_t(K) * g.ny + size_t(j)) * (nbx - 1u) + (seamL ? bx - 1u : bx)) * 8u + (seamL ? 4u : 0u)) = v;
+    const bool seamL = lane == 0 && t.bx > 0, seamR = lane == kWave - 1 && i + 4 < g.nx;
+    const SeamLayout sl = seamLayout(g.nx, g.ny);
+    const unsigned offX = unsigned(j) * (unsigned(g.nx) >> 1) + (unsigned(i) >> 1);
+    const unsigned seamOff = seamL ? sl.entry(unsigned(j), t.bx, 1u) : sl.entry(unsigned(j), t.bx + 1u, 0u);
+    const bool storeX = i < g.nx && i >= g.xlo - 4 && i < g.xhi + 4, seamW = live && (seamL || seamR);
+    storeXFolded(keepIf(wr, live), rz + size_t(K) * (sz >> 1), offX, storeX, false, seam + size_t(K) * sl.planeFloats(), seamOff, seamW);
 }
 
 // Scalar fallback for levels whose nx is not a multiple of 4 (only the tiniest coarse levels).
@@ -2153,15 +2156,15 @@ __global__ __launch_bounds__(256, 8) void restrictYKernel(GridP cg, float *__res
     if (!anyActiveCol) return;  // (the destination holds 0 there already)
     const bool mine = inGrid && any;  // (a thread without columns stays for the wave's seam loads; its own loads aim at the row's last pair)
     const int fny = 2 * cg.ny;
-    const int nseam = (2 * cg.nx + 255) / 256 - 1;
+    const SeamLayout sl = seamLayout(2 * cg.nx, fny);
     const int lane = int(threadIdx.x) & (kWave - 1);
     // the boundaries at the wave's first column (sL, fine x = 256 sL) and behind its last one (sL + 1), where they lie inside the grid
     const int sL = __builtin_amdgcn_readfirstlane(int(bx) * (kRyI / 128) + int(threadIdx.x >> 6));
-    const bool hasL = sL >= 1 && sL <= nseam, hasR = sL + 1 <= nseam;
+    const bool hasL = sL >= 1 && sL <= int(sl.nseam), hasR = sL + 1 <= int(sl.nseam);
     const int seamRow = lane & 31, seamSide = lane >> 5;
     const bool seamLoad = seamRow < kRyRows && (seamSide ? hasR : hasL);
     // the entry: fine 256 s - 4 .. 256 s + 3; column 128 s folds 256 s - 1 .. 256 s + 2, column 128 s - 1 folds 256 s - 3 .. 256 s
-    const unsigned seamOff = (unsigned(min(max(2 * J0 - 1 + seamRow, 0), fny - 1)) * unsigned(nseam) + unsigned(sL + seamSide - 1)) * 8u + (seamSide ? 1u : 3u);
+    const unsigned seamOff = sl.entry(unsigned(min(max(2 * J0 - 1 + seamRow, 0), fny - 1)), unsigned(sL + seamSide), 0u) + (seamSide ? 1u : 3u);
     const bool takeL = hasL && lane == 0, takeR = hasR && lane == kWave - 1;
     const unsigned Ic = unsigned(min(I, cg.nx - 2));
     auto opq = [](unsigned v) {
@@ -2175,7 +2178,7 @@ __global__ __launch_bounds__(256, 8) void restrictYKernel(GridP cg, float *__res
         const unsigned col = opq(Ic);
         float sf = 0.f;
         if (seamLoad) {
-            const float4 v = gLoad4u(scalarBase(seam + size_t(K) * size_t(fny) * size_t(nseam) * 8u), seamOff);
+            const float4 v = gLoad4u(scalarBase(seam + size_t(K) * sl.planeFloats()), seamOff);
             sf = foldX4(v.x, v.y, v.z, v.w);
         }
         float2 r[kRyRows];
@@ -2664,9 +2667,9 @@ size_t stencilSweptCells(const GridP &g)
     const int kind = stencilKernelOf(g);
     if (kind == 3) return n;
     const bool plane = kind == 2;
-    const unsigned nbx = (g.nx + 255) / 256, nby = (g.ny + kPlaneRows - 1) / kPlaneRows, nbz = plane ? (g.nz + g.planeZc - 1) / g.planeZc : 0;
+    const PlaneTiles pt = planeTiles(g.nx, g.ny, g.nz, plane ? g.planeZc : 0);
     const int32_t *list = plane ? g.planeBlocks : g.chunks;
-    const size_t entries = plane ? (list ? size_t(g.nplaneBlocks) : size_t(nbx) * nby * nbz) : (list ? size_t(g.nchunks) : size_t(g.ny) * g.nz);
+    const size_t entries = plane ? (list ? size_t(g.nplaneBlocks) : pt.count()) : (list ? size_t(g.nchunks) : size_t(g.ny) * g.nz);
     unsigned long long *dev = nullptr, host = 0;
     if (entries == 0) return 0;
     if (hipMalloc(reinterpret_cast<void **>(&dev), sizeof(host)) != hipSuccess || hipMemset(dev, 0, sizeof(host)) != hipSuccess) {
@@ -2674,7 +2677,7 @@ size_t stencilSweptCells(const GridP &g)
         if (dev) (void)hipFree(dev);
         return n;
     }
-    sweptCountKernel<<<unsigned(std::min<size_t>((entries + 255) / 256, 4096)), 256>>>(g, plane ? 1 : 0, nbx, list, entries, dev);
+    sweptCountKernel<<<unsigned(std::min<size_t>((entries + 255) / 256, 4096)), 256>>>(g, plane ? 1 : 0, pt.nbx, list, entries, dev);
     const bool ok = hipMemcpy(&host, dev, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess;
     (void)hipFree(dev);
     if (!ok) {
@@ -2708,10 +2711,10 @@ int launchStencil(void *stream, StencilOp op, const GridP &g, float *out, const 
     // MGPS_STENCIL=plane send to it
     const bool planeWins = size_t(g.nx) * g.ny * sizeof(float) > kPlaneSweepMinPlaneBytes;
     if (zc && (forced == 2 || (forced == 0 && planeWins))) {
-        const unsigned nbx = (g.nx + 255) / 256, nby = (g.ny + kPlaneRows - 1) / kPlaneRows;
-        const unsigned nbz = (g.nz + zc - 1) / zc;
+        const PlaneTiles pt = planeTiles(g.nx, g.ny, g.nz, zc);
+        const unsigned nbx = pt.nbx, nby = pt.nby, nbz = pt.nbz;
         const bool list = skipInactive && g.planeBlocks != nullptr;
-        const unsigned nb = list ? unsigned(g.nplaneBlocks) : nbx * nby * nbz;
+        const unsigned nb = list ? unsigned(g.nplaneBlocks) : unsigned(pt.count());
         const int32_t *blocks = list ? g.planeBlocks : nullptr;
         if (nb > 0) switch (op) {
                 case OP_JACOBI:
@@ -2836,7 +2839,7 @@ int launchPlainQuads(void *stream, const uint8_t *lab, int nx, int ny, int nz, u
     const size_t groups = (quads + kWave - 1) / kWave;
     plainQuadsKernel<<<unsigned(std::min<size_t>((groups + 3) / 4, 256 * 64)), 256, 0, s>>>(lab, quads, plainQ);
     if (plainT) {
-        const unsigned nbx = unsigned(nx + 255) / 256u;
+        const unsigned nbx = planeTiles(nx, ny, nz, 0).nbx;
         const size_t rows = size_t(ny) * nz;
         plainTilesKernel<<<blocksFor(rows * nbx, 256), 256, 0, s>>>(plainQ, plainQuadWords(cells), unsigned(nx) >> 2, nbx, rows, plainT);
     }
@@ -2852,8 +2855,7 @@ static unsigned sweepBlocks(const GridP &g, bool skipInactive, int *path)
     const bool planeWins = size_t(g.nx) * g.ny * sizeof(float) > kPlaneSweepMinPlaneBytes;
     if (zc && (forced == 2 || (forced == 0 && planeWins))) {
         *path = 0;
-        const unsigned nbx = (g.nx + 255) / 256, nby = (g.ny + kPlaneRows - 1) / kPlaneRows, nbz = (g.nz + zc - 1) / zc;
-        return (skipInactive && g.planeBlocks) ? unsigned(g.nplaneBlocks) : nbx * nby * nbz;
+        return (skipInactive && g.planeBlocks) ? unsigned(g.nplaneBlocks) : unsigned(planeTiles(g.nx, g.ny, g.nz, zc).count());
     }
     if ((g.nx & 3) == 0) {
         *path = 1;
@@ -2898,10 +2900,10 @@ int launchStencilDot(void *stream, StencilOp op, const GridP &g, float *out, con
     const bool jac = op == OP_JACOBI;
     if (path == 0) {
         const int zc = g.planeZc;
-        const unsigned nbx = (g.nx + 255) / 256, nby = (g.ny + kPlaneRows - 1) / kPlaneRows, nbz = (g.nz + zc - 1) / zc;
+        const PlaneTiles pt = planeTiles(g.nx, g.ny, g.nz, zc);
         if (nb > 0) {
-            if (jac) stencilPlaneKernel<OP_JACOBI, true><<<nb, 64 * kPlaneRows, 0, s>>>(g, out, x, b, omega, nbx, nby, nbz, zc, g.planeBlocks, partials);
-            else stencilPlaneKernel<OP_APPLY, true><<<nb, 64 * kPlaneRows, 0, s>>>(g, out, x, nullptr, 0.f, nbx, nby, nbz, zc, g.planeBlocks, partials);
+            if (jac) stencilPlaneKernel<OP_JACOBI, true><<<nb, 64 * kPlaneRows, 0, s>>>(g, out, x, b, omega, pt.nbx, pt.nby, pt.nbz, zc, g.planeBlocks, partials);
+            else stencilPlaneKernel<OP_APPLY, true><<<nb, 64 * kPlaneRows, 0, s>>>(g, out, x, nullptr, 0.f, pt.nbx, pt.nby, pt.nbz, zc, g.planeBlocks, partials);
         }
     } else if (path == 1) {
         if (nb > 0) {
@@ -3269,7 +3271,8 @@ bool residualRestrictFits(const GridP &fine, const GridP &coarse)
 std::vector<int32_t> planeBlockEdges(const GridP &g, const std::vector<uint8_t> &flags)
 {
     const int zc = g.planeZc > 0 ? g.planeZc : 1;
-    const size_t layer = size_t((g.nx + 255) / 256) * size_t((g.ny + kPlaneRows - 1) / kPlaneRows), nbz = size_t((g.nz + zc - 1) / zc);
+    const PlaneTiles pt = planeTiles(g.nx, g.ny, g.nz, zc);
+    const size_t layer = pt.layer(), nbz = pt.nbz;
     std::vector<int32_t> edges;
     for (size_t bid = 0; bid < flags.size() && bid < layer * nbz; ++bid) {
         if (flags[bid]) continue;
@@ -3316,26 +3319,22 @@ int launchResidualEdgePlanes(void *stream, const GridP &g, float *r, const float
 // nx / 2 x ny x nz / 2 (rounded up to whole quads) with the seam array behind it.
 bool residualRestrictXFolds(const GridP &fine) { return fine.nbnd == 0; }
 static size_t rzxGridFloats(const GridP &fine) { return (size_t(fine.nx) * fine.ny * fine.nz / 4 + 3) & ~size_t(3); }
-size_t rzxFloats(const GridP &fine) { return rzxGridFloats(fine) + size_t(fine.nz / 2) * fine.ny * size_t((fine.nx + 255) / 256 - 1) * 8; }
+size_t rzxFloats(const GridP &fine) { return rzxGridFloats(fine) + size_t(fine.nz / 2) * seamLayout(fine.nx, fine.ny).planeFloats(); }
 int launchResidualZ(void *stream, const GridP &fine, float *rz, const float *x, const float *b, const int32_t *edges, int nedges, const float *rEdge, bool xfold)
 {
+    if (xfold && fine.nbnd > 0) return int(hipErrorInvalidValue);
+    const int zc = fine.planeZc;
+    const PlaneTiles pt = planeTiles(fine.nx, fine.ny, fine.nz, zc);
+    const unsigned nbx = pt.nbx, nby = pt.nby;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool list = fine.planeBlocks != nullptr;
+    const unsigned nb = list ? unsigned(fine.nplaneBlocks) : unsigned(pt.count());
     if (xfold) {
-        if (fine.nbnd > 0) return int(hipErrorInvalidValue);
-        const int zc = fine.planeZc;
-        const unsigned nbx = (fine.nx + 255) / 256, nby = (fine.ny + kPlaneRows - 1) / kPlaneRows, nbz = (fine.nz + zc - 1) / zc;
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        const bool list = fine.planeBlocks != nullptr;
-        const unsigned nb = list ? unsigned(fine.nplaneBlocks) : nbx * nby * nbz;
         float *seam = rz + rzxGridFloats(fine);
         if (nb > 0) residualZKernel<true><<<nb, 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, list ? fine.planeBlocks : nullptr, rEdge, seam);
         if (list && nedges > 0) residualZEdgeKernel<true><<<unsigned(nedges), 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, edges, seam);
         return int(hipGetLastError());
     }
-    const int zc = fine.planeZc;
-    const unsigned nbx = (fine.nx + 255) / 256, nby = (fine.ny + kPlaneRows - 1) / kPlaneRows, nbz = (fine.nz + zc - 1) / zc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool list = fine.planeBlocks != nullptr;
-    const unsigned nb = list ? unsigned(fine.nplaneBlocks) : nbx * nby * nbz;
     if (nb > 0) residualZKernel<false><<<nb, 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, list ? fine.planeBlocks : nullptr, rEdge, nullptr);
     if (list && nedges > 0) residualZEdgeKernel<false><<<unsigned(nedges), 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, edges, nullptr);
     if (fine.nbnd > 0)  // the general BOUNDARY cells' part (their entries lie in blocks the launches above have just written)
@@ -3430,9 +3429,9 @@ int launchProlongJacobi(void *stream, const GridP &g, float *out, const float *x
 {
     if (!prolongJacobiPlaneFits(g) || !out || !x || !coarse || out == x || g.nbnd > 0) return int(hipErrorInvalidValue);
     const int zc = g.planeZc;
-    const unsigned nbx = (g.nx + 255) / 256, nby = (g.ny + kPlaneRows - 1) / kPlaneRows, nbz = (g.nz + zc - 1) / zc;
-    const unsigned nb = g.planeBlocks ? unsigned(g.nplaneBlocks) : nbx * nby * nbz;
-    if (nb > 0) prolongJacobiPlaneKernel<<<nb, 64 * kPlaneRows, 0, static_cast<hipStream_t>(stream)>>>(g, out, x, b, coarse, omega, nbx, nby, zc, g.planeBlocks);
+    const PlaneTiles pt = planeTiles(g.nx, g.ny, g.nz, zc);
+    const unsigned nb = g.planeBlocks ? unsigned(g.nplaneBlocks) : unsigned(pt.count());
+    if (nb > 0) prolongJacobiPlaneKernel<<<nb, 64 * kPlaneRows, 0, static_cast<hipStream_t>(stream)>>>(g, out, x, b, coarse, omega, pt.nbx, pt.nby, zc, g.planeBlocks);
     return int(hipGetLastError());
 }
 
@@ -3444,8 +3443,7 @@ __global__ __launch_bounds__(256) void planeBlockFlagsKernel(const int32_t *__re
 }
 size_t planeBlockCount(const GridP &g)
 {
-    const int zc = g.planeZc > 0 ? g.planeZc : 1;
-    return size_t((g.nx + 255) / 256) * size_t((g.ny + kPlaneRows - 1) / kPlaneRows) * size_t((g.nz + zc - 1) / zc);
+    return planeTiles(g.nx, g.ny, g.nz, g.planeZc > 0 ? g.planeZc : 1).count();
 }
 int launchPlaneBlockFlags(void *stream, const GridP &g, uint8_t *flags)
 {

@@ -636,7 +636,7 @@ __global__ __launch_bounds__(256) void byteFlagKernel(const uint8_t *__restrict_
 // chunkFlags[q] = the q-th run of kSegCells = 32 cells holds an active cell (8 lanes per run); planeFlags (optional, nx % 4 == 0):
 // per block of the plane-marching sweep (256 cells in x, kPlaneRows rows, zc planes)
 __global__ __launch_bounds__(256) void activityFlagsKernel(Dims d, const uint32_t *__restrict__ lab4, size_t nq, uint8_t *__restrict__ chunkFlags,
-                                                           uint8_t *__restrict__ planeFlags, int zc, int nbx, int nby)
+                                                           uint8_t *__restrict__ planeFlags, int zc, PlaneTiles pt)
 {
     const size_t q = blockIdx.x * size_t(blockDim.x) + threadIdx.x;
     bool any = false;
@@ -646,7 +646,7 @@ __global__ __launch_bounds__(256) void activityFlagsKernel(Dims d, const uint32_
         if (any && planeFlags) {
             const size_t c = q * 4;
             const int i = int(c % d.nx), j = int((c / d.nx) % d.ny), k = int(c / (size_t(d.nx) * d.ny));
-            planeFlags[(size_t(k / zc) * nby + j / kPlaneRows) * nbx + i / 256] = 1;
+            planeFlags[pt.index(i / kPlaneCols, j / kPlaneRows, k / zc)] = 1;
         }
     }
     const unsigned long long votes = __ballot(any);
@@ -1205,9 +1205,8 @@ int launchGather(void *stream, const int32_t *rank, const int32_t *start, int n,
 int launchActivityFlags(void *stream, const Dims &d, const uint8_t *lab, uint8_t *chunkFlags, uint8_t *planeFlags, int zc)
 {
     const size_t nq = d.cells() / 4;
-    const int nbx = (d.nx + 255) / 256, nby = (d.ny + kPlaneRows - 1) / kPlaneRows;
     activityFlagsKernel<<<blocksFor(nq, 256), 256, 0, S(stream)>>>(d, reinterpret_cast<const uint32_t *>(lab), nq, chunkFlags, zc ? planeFlags : nullptr, zc ? zc : 1,
-                                                                 nbx, nby);
+                                                                 planeTiles(d.nx, d.ny, d.nz, zc));
     return int(hipGetLastError());
 }
 
@@ -1619,7 +1618,7 @@ __global__ __launch_bounds__(256) void checkIndexKernel(const int32_t *__restric
 }
 // a byte per block of the plane-marching sweep (256 x kPlaneRows x zc): set where plane k of the grid (a ghost plane: -1 or nz, clamped
 // into the first / last layer of blocks) holds an active cell -- the residual + restriction pair of a cut level visits such blocks too
-__global__ __launch_bounds__(256) void ghostPlaneBlockFlagsKernel(Dims d, const uint8_t *__restrict__ lab, int k, int zc, int nbx, int nby, uint8_t *__restrict__ flags)
+__global__ __launch_bounds__(256) void ghostPlaneBlockFlagsKernel(Dims d, const uint8_t *__restrict__ lab, int k, int zc, PlaneTiles pt, uint8_t *__restrict__ flags)
 {
     const size_t q = blockIdx.x * size_t(blockDim.x) + threadIdx.x, nq = size_t(d.nx) * d.ny / 4;
     if (q >= nq) return;
@@ -1628,7 +1627,7 @@ __global__ __launch_bounds__(256) void ghostPlaneBlockFlagsKernel(Dims d, const 
     if (!(activeCode(v & 0xffu) || activeCode((v >> 8) & 0xffu) || activeCode((v >> 16) & 0xffu) || activeCode(v >> 24))) return;
     const size_t c = q * 4;
     const int i = int(c % d.nx), j = int(c / d.nx), kb = min(max(k, 0), d.nz - 1) / zc;
-    flags[(size_t(kb) * nby + j / kPlaneRows) * nbx + i / 256] = 1;
+    flags[pt.index(i / kPlaneCols, j / kPlaneRows, kb)] = 1;
 }
 
 }  // namespace
@@ -1674,8 +1673,7 @@ int launchCheckIndex(void *stream, const int32_t *idx, int n, int32_t limit, int
 int launchGhostPlaneBlockFlags(void *stream, const Dims &d, const uint8_t *lab, int k, int zc, uint8_t *flags)
 {
     if ((d.nx & 3) != 0 || zc <= 0) return 0;
-    const int nbx = (d.nx + 255) / 256, nby = (d.ny + kPlaneRows - 1) / kPlaneRows;
-    ghostPlaneBlockFlagsKernel<<<blocksFor(size_t(d.nx) * d.ny / 4, 256), 256, 0, S(stream)>>>(d, lab, k, zc, nbx, nby, flags);
+    ghostPlaneBlockFlagsKernel<<<blocksFor(size_t(d.nx) * d.ny / 4, 256), 256, 0, S(stream)>>>(d, lab, k, zc, planeTiles(d.nx, d.ny, d.nz, zc), flags);
     return int(hipGetLastError());
 }
 

@@ -2329,7 +2329,7 @@ int commonDeviceState(mgps_solver *h, bool needCoarseSolver)
         if (!g.lab || (g.nx & 3) != 0 || g.ghostLo || g.ghostHi || g.planeZc <= 0 || L.plainQ) continue;
         const size_t cells = size_t(g.nx) * g.ny * g.nz;
         MGPS_TRY(devAlloc(h, &L.plainQ, plainQuadWords(cells), false));
-        MGPS_TRY(devAlloc(h, &L.plainT, size_t(g.ny) * g.nz * size_t((g.nx + 255) / 256), false));
+        MGPS_TRY(devAlloc(h, &L.plainT, size_t(g.ny) * g.nz * planeTiles(g.nx, g.ny, g.nz, 0).nbx, false));
         MGPS_LAUNCH(h, launchPlainQuads(nullptr, g.lab, g.nx, g.ny, g.nz, L.plainQ, L.plainT));  // (the null stream: see above)
         L.g.plainQ = L.plainQ;
         L.g.plainT = L.plainT;
@@ -2854,7 +2854,7 @@ int activity(mgps_solver *h, DevScratch &tmp, LevelBuild &t, bool ghostLo, bool 
     t.planeZc = planeSweepZc(t.own.nx, t.own.ny, t.own.nz);
     MGPS_TRY(tmp.get(h, &t.chunkFlags, t.nfine));
     if (t.planeZc) {
-        t.nplane = size_t((t.own.nx + 255) / 256) * size_t((t.own.ny + kPlaneRows - 1) / kPlaneRows) * size_t((t.own.nz + t.planeZc - 1) / t.planeZc);
+        t.nplane = planeTiles(t.own.nx, t.own.ny, t.own.nz, t.planeZc).count();
         MGPS_TRY(tmp.get(h, &t.planeFlags, t.nplane));
         MGPS_HIP(h, hipMemsetAsync(t.planeFlags, 0, t.nplane, nullptr));
     }
@@ -4721,7 +4721,7 @@ try {
         return rc;
     }
     case 15: src = L.g.plainQ, n = L.g.plainQ ? (L.d.cells() / 4 + 31) / 32 : 0; break;  // (the canonical layout; empty: every code is loaded)
-    case 16: src = L.g.plainT, n = L.g.plainT ? size_t(L.d.ny) * L.d.nz * size_t((L.d.nx + 255) / 256) : 0, elem = 8; break;  // (the marches' copy)
+    case 16: src = L.g.plainT, n = L.g.plainT ? size_t(L.d.ny) * L.d.nz * planeTiles(L.d.nx, L.d.ny, L.d.nz, 0).nbx : 0, elem = 8; break;  // (the marches' copy)
     default: return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_level_array: unknown array");
     }
     *count = int64_t(n);

@@ -60,6 +60,29 @@ def build_simple_domain(grid_size, dirichlet_band=1, dtype=np.float64):
     return lab, weights, 1.0 / g
 
 
+def dirichlet_box(shape, fill, dtype=np.float32):
+    """A (nz, ny, nx) box of DIRICHLET cells in which `fill(labels)` marks the liquid INTERIOR; unit weights on the faces that
+    touch an INTERIOR cell.  Returns (labels, weights): a base domain for expand_domain."""
+    lab = np.full(shape, DIRICHLET, dtype=np.uint8)
+    fill(lab)
+    weights = []
+    for axis in range(3):
+        w = np.zeros(face_shape(*shape, axis), dtype=dtype)
+        back, fwd = _shift_pair(lab, axis)
+        w[_inner_faces(w, axis)] = np.where((back == INTERIOR) | (fwd == INTERIOR), 1.0, 0.0)
+        weights.append(w)
+    return lab, weights
+
+
+def rag264():
+    """A 248 x 44 x 20 box of liquid in a 264 x 52 x 28 solver grid, three levels: the last tile of the plane marches is ragged on
+    every axis (256 + 8 columns, 3 x 16 + 4 rows), the active x range lies strictly inside the grid, no general BOUNDARY cells.
+    Returns (labels, weights, offset, levels) as expand_domain does."""
+    def inner(lab):
+        lab[1:-1, 1:-1, 1:-1] = INTERIOR
+    return expand_domain(*dirichlet_box((20, 44, 248), inner), levels=3, solver_shape=(28, 52, 264))
+
+
 def ghost_fluid_theta(phi0, phi1):
     """Util.h:25-42, vectorised."""
     theta = np.zeros_like(phi0)
