@@ -2316,3 +2316,417 @@ try {
 MGPS_API_CATCH(nullptr)
 
 }  // extern "C"
+
+// ---- pressure feedback: force and torque of the pressure on solid bodies (include/mgps_fields.h) ------------
+// One launch over the cells of the grid (or of a window): a thread handles the three backward faces of its cell and, at the far end
+// of an axis, the end face.  Almost every face is open: the cut weight is loaded first and body, material and pressure only where
+// w < 1, so far from solids the pass streams the three weight grids (12 bytes per cell).  Contributions are summed per row (body) in
+// fp64 without atomics: lanes of a wave that hold the same row are reduced by shuffles, lane 0 adds the sum into the wave's own
+// table in LDS, the waves' tables are added in wave order into one table per workgroup, and a second kernel adds the workgroups'
+// tables in index order.  The launch is a fixed number of workgroups walking the cells with a fixed stride: every sum has one order.
+namespace {
+constexpr int kForceBlocks = 1024, kForceThreads = 256, kForceWaves = kForceThreads / 64, kForceCols = 8;
+constexpr int kForceSlices = 16;  // the second kernel: 16 threads share the workgroups of one table entry
+static_assert(kForceBlocks % kForceSlices == 0, "the slices divide the workgroups evenly");
+
+// The rule of one face: the face of `axis` behind cell (i, j, k) of G (its forward cell; k a plane of the whole grid) with cut weight
+// w.  False unless the face is wet; then, and only then, s is set to its closed fraction, phi to the push along +axis and row to the
+// table row.  mat / pr reach
+// material and pressure of a cell of G, bodyOf() loads the face's body id; all three are touched on a closed or cut face only.
+template <class MatAt, class PrAt, class BodyOf>
+__device__ __forceinline__ bool solidFaceTerm(const Box &G, int axis, int i, int j, int k, float w, int bodies, MatAt mat, PrAt pr,
+                                              BodyOf bodyOf, int &row, float &s, double &phi)
+{
+    if (!(w < 1.f)) return false;
+    const int ext[3] = {G.gx, G.gy, G.gz};
+    int b[3] = {i, j, k}, f[3] = {i, j, k};
+    b[axis] -= 1;
+    const bool lb = b[axis] >= 0 && mat(b[0], b[1], b[2]) == kLiquid, lf = f[axis] < ext[axis] && mat(i, j, k) == kLiquid;
+    if (!(lb || lf)) return false;
+    const float pb = lb ? pr(b[0], b[1], b[2]) : 0.f, pf = lf ? pr(i, j, k) : 0.f;
+    s = 1.f - w;  // (w < 1: s > 0)
+    phi = double(s) * (double(pb) - double(pf));
+    const int id = bodyOf();
+    row = id >= 1 && id <= bodies ? id : 0;
+    return true;
+}
+
+__device__ __forceinline__ double waveSum(double v)  // every lane gets the sum, in one fixed order
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// Adds the wave's terms of one face slot of axis A into the wave's table: while terms are pending, the row of the first pending lane
+// is taken, the lanes of that row are reduced and lane 0 adds once.  (x, y, z): the face centre.  Every lane of the wave calls it.
+template <int A>
+__device__ __forceinline__ void addFaceTerms(double *table, const double *__restrict__ centres, bool has, int row, float s, double phi,
+                                             double x, double y, double z)
+{
+    unsigned long long todo = __ballot(has);
+    if (!todo) return;
+    constexpr int U = (A + 1) % 3, V = (A + 2) % 3;
+    double tu = 0.0, tv = 0.0;  // (d x phi e_A)_U = d_V phi, (d x phi e_A)_V = -d_U phi, d = the arm from the row's centre
+    if (has) {
+        const double pos[3] = {x, y, z};
+        tu = (pos[V] - centres[3 * row + V]) * phi;
+        tv = -(pos[U] - centres[3 * row + U]) * phi;
+    }
+    while (todo) {
+        const int r0 = __builtin_amdgcn_readlane(row, __ffsll(todo) - 1);
+        const bool mine = has && row == r0;
+        const unsigned long long m = __ballot(mine);
+        const double f = waveSum(mine ? phi : 0.0), su = waveSum(mine ? tu : 0.0), sv = waveSum(mine ? tv : 0.0),
+                     area = waveSum(mine ? double(s) : 0.0);
+        if ((threadIdx.x & 63) == 0) {
+            double *t = table + size_t(r0) * kForceCols;
+            t[A] += f;
+            t[3 + U] += su;
+            t[3 + V] += sv;
+            t[6] += area;
+            t[7] += double(__popcll(m));
+        }
+        todo &= ~m;
+    }
+}
+
+struct ForceArgs {
+    Box G;                 // the whole grid
+    Box g;                 // the box the face grids are indexed in: G, or the window's planes
+    int k0;                // the whole grid's plane of the box's plane 0
+    int topCounts;         // the z end face of the box's last plane counts (the whole grid's plane gz)
+    int bodies;
+    int di, dj, dk;        // the stride of the walk, kForceBlocks * kForceThreads cells, as steps of (i, j, k)
+    const float *cw[3];
+    const int32_t *body[3];
+    const double *centres; // device, (bodies + 1) * 3
+    double *partials;      // device, kForceBlocks tables of (bodies + 1) * 8
+};
+
+// the walk and the sums; mat / pr: GridAt of the whole grid, or SlabAt of the window with its lower halo
+template <class MatAt, class PrAt>
+__device__ __forceinline__ void solidForcesWalk(const ForceArgs &p, MatAt mat, PrAt pr, double *lds)
+{
+    const int entries = (p.bodies + 1) * kForceCols;
+    for (int e = int(threadIdx.x); e < kForceWaves * entries; e += kForceThreads) lds[e] = 0.0;
+    __syncthreads();
+    double *table = lds + size_t(threadIdx.x >> 6) * entries;
+    const Box g = p.g;
+    const size_t n = g.cells(), plane = size_t(g.gx) * g.gy, stride = size_t(kForceBlocks) * kForceThreads;
+    size_t base = size_t(blockIdx.x) * kForceThreads, t = base + threadIdx.x;
+    int i = int(t % g.gx), j = int((t / g.gx) % g.gy), k = int(min(t / plane, size_t(g.gz)));  // (past the end: k = gz and stays there)
+    bool active = t < n;
+    // the cut weights of the cell's backward faces: x-face c + (k gy + j), y-face c + k gx, z-face c (c = the cell's index)
+    auto loadW = [&](float w[3]) {
+        w[0] = w[1] = w[2] = 1.f;
+        if (active) {
+            w[0] = p.cw[0][t + size_t(k) * g.gy + j];
+            w[1] = p.cw[1][t + size_t(k) * g.gx];
+            w[2] = p.cw[2][t];
+        }
+    };
+    float w[3];
+    loadW(w);
+    for (; base < n; base += stride) {  // (a wave-uniform bound: every lane stays for the ballots and shuffles)
+        const size_t tc = t;
+        const int ci = i, cj = j, ck = k;
+        const bool cur = active;
+        const float wc[3] = {w[0], w[1], w[2]};
+        // the next cell of the walk, and its weights on their way while this one is worked on
+        t += stride;
+        i += p.di;
+        if (i >= g.gx) i -= g.gx, ++j;
+        j += p.dj;
+        if (j >= g.gy) j -= g.gy, ++k;
+        k = min(k + p.dk, g.gz);
+        active = t < n;
+        loadW(w);
+        const int kg = p.k0 + ck;
+        const size_t fx = tc + size_t(ck) * g.gy + cj, fy = tc + size_t(ck) * g.gx, fz = tc;
+        int row = 0;
+        float s = 0.f;
+        double phi = 0.0;
+        bool has;
+        has = cur && solidFaceTerm(p.G, 0, ci, cj, kg, wc[0], p.bodies, mat, pr, [&] { return p.body[0][fx]; }, row, s, phi);
+        addFaceTerms<0>(table, p.centres, has, row, s, phi, double(ci), cj + 0.5, kg + 0.5);
+        has = cur && solidFaceTerm(p.G, 1, ci, cj, kg, wc[1], p.bodies, mat, pr, [&] { return p.body[1][fy]; }, row, s, phi);
+        addFaceTerms<1>(table, p.centres, has, row, s, phi, ci + 0.5, double(cj), kg + 0.5);
+        has = cur && solidFaceTerm(p.G, 2, ci, cj, kg, wc[2], p.bodies, mat, pr, [&] { return p.body[2][fz]; }, row, s, phi);
+        addFaceTerms<2>(table, p.centres, has, row, s, phi, ci + 0.5, cj + 0.5, double(kg));
+        // the end faces: in front of the last cell of an axis
+        const bool endX = cur && ci == g.gx - 1, endY = cur && cj == g.gy - 1, endZ = cur && ck == g.gz - 1 && p.topCounts;
+        if (__ballot(endX)) {
+            has = endX && solidFaceTerm(p.G, 0, ci + 1, cj, kg, endX ? p.cw[0][fx + 1] : 1.f, p.bodies, mat, pr, [&] { return p.body[0][fx + 1]; }, row, s, phi);
+            addFaceTerms<0>(table, p.centres, has, row, s, phi, double(ci + 1), cj + 0.5, kg + 0.5);
+        }
+        if (__ballot(endY)) {
+            has = endY && solidFaceTerm(p.G, 1, ci, cj + 1, kg, endY ? p.cw[1][fy + g.gx] : 1.f, p.bodies, mat, pr, [&] { return p.body[1][fy + g.gx]; }, row, s, phi);
+            addFaceTerms<1>(table, p.centres, has, row, s, phi, ci + 0.5, double(cj + 1), kg + 0.5);
+        }
+        if (__ballot(endZ)) {
+            has = endZ && solidFaceTerm(p.G, 2, ci, cj, kg + 1, endZ ? p.cw[2][fz + plane] : 1.f, p.bodies, mat, pr, [&] { return p.body[2][fz + plane]; }, row, s, phi);
+            addFaceTerms<2>(table, p.centres, has, row, s, phi, ci + 0.5, cj + 0.5, double(kg + 1));
+        }
+    }
+    __syncthreads();
+    double *out = p.partials + size_t(blockIdx.x) * entries;
+    for (int e = int(threadIdx.x); e < entries; e += kForceThreads) {
+        double sum = lds[e];
+#pragma unroll
+        for (int wv = 1; wv < kForceWaves; ++wv) sum += lds[size_t(wv) * entries + e];  // wave order
+        out[e] = sum;
+    }
+}
+
+__global__ __launch_bounds__(kForceThreads) void solidForcesKernel(ForceArgs p, const int32_t *__restrict__ material,
+                                                                   const float *__restrict__ pressure)
+{
+    extern __shared__ double forceTables[];
+    solidForcesWalk(p, GridAt<int32_t>{p.G, material}, GridAt<float>{p.G, pressure}, forceTables);
+}
+__global__ __launch_bounds__(kForceThreads) void solidForcesSlabKernel(ForceArgs p, Slab s, Planes<int32_t> mat, Planes<float> pr)
+{
+    extern __shared__ double forceTables[];
+    solidForcesWalk(p, SlabAt<int32_t>{s, mat}, SlabAt<float>{s, pr}, forceTables);
+}
+
+// out[e] = the workgroups' tables added in index order, force and torque columns times scale.  16 entries x 16 slices per block: a
+// slice adds its 64 workgroups in order, thread 0 of the entry adds the slices in order.
+__global__ __launch_bounds__(kForceSlices * 16) void solidForcesSumKernel(double *__restrict__ out, const double *__restrict__ partials,
+                                                                          int entries, double scale)
+{
+    __shared__ double part[kForceSlices][16];
+    const int lane = int(threadIdx.x) & 15, slice = int(threadIdx.x) >> 4, e = int(blockIdx.x) * 16 + lane;
+    constexpr int per = kForceBlocks / kForceSlices;
+    double sum = 0.0;
+    if (e < entries)
+        for (int b = slice * per; b < (slice + 1) * per; ++b) sum += partials[size_t(b) * entries + e];
+    part[slice][lane] = sum;
+    __syncthreads();
+    if (slice == 0 && e < entries) {
+        double total = part[0][lane];
+        for (int q = 1; q < kForceSlices; ++q) total += part[q][lane];
+        out[e] = e % kForceCols < 6 ? scale * total : total;
+    }
+}
+
+int forceCheckBodies(const char *fn, int bodies)
+{
+    if (bodies < 1 || bodies > 255) return exRefuse(fn, "bodies = " + std::to_string(bodies) + " is outside 1 .. 255");
+    return MGPS_OK;
+}
+
+// The launches of one call and the rows' way to the host.  `slab`: the window and its lower halo, or NULL for the whole grid G.
+// Synchronises the stream.
+int runSolidForces(const char *fn, double *outHost, const Box &G, const Slab *slab, const float *pressure, const float *pressureLo,
+                   const int32_t *material, const int32_t *materialLo, const float *const cw[3], const int32_t *const body[3],
+                   const double *centresHost, int bodies, double scale, hipStream_t st)
+{
+    ForceArgs p{};
+    p.G = G;
+    p.g = slab ? slab->base() : G;
+    p.k0 = slab ? slab->c0 : 0;
+    p.topCounts = slab ? slab->c1 == slab->gz : 1;
+    p.bodies = bodies;
+    {
+        const size_t stride = size_t(kForceBlocks) * kForceThreads, plane = size_t(p.g.gx) * p.g.gy;
+        p.di = int(stride % size_t(p.g.gx));
+        p.dj = int((stride / size_t(p.g.gx)) % size_t(p.g.gy));
+        p.dk = int(std::min<size_t>(stride / plane, size_t(p.g.gz)));
+    }
+    const size_t entries = size_t(bodies + 1) * kForceCols, centreCount = size_t(bodies + 1) * 3;
+    DevPool pool;
+    double *dev = nullptr;  // [partials | rows | centres]
+    try {
+        dev = pool.get<double>(size_t(kForceBlocks) * entries + entries + centreCount);
+    } catch (const std::bad_alloc &) {
+        setLastGlobalError(std::string(fn) + ": device allocation failed");
+        return MGPS_ERR_ALLOC;
+    }
+    double *rows = dev + size_t(kForceBlocks) * entries, *centres = rows + entries;
+    for (int a = 0; a < 3; ++a) p.cw[a] = cw[a], p.body[a] = body[a];
+    p.centres = centres;
+    p.partials = dev;
+    hipError_t e = hipMemcpyAsync(centres, centresHost, centreCount * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        const size_t lds = size_t(kForceWaves) * entries * sizeof(double);  // 64 KiB at 255 bodies
+        if (slab)
+            solidForcesSlabKernel<<<kForceBlocks, kForceThreads, lds, st>>>(p, *slab, Planes<int32_t>{material, materialLo, nullptr},
+                                                                            Planes<float>{pressure, pressureLo, nullptr});
+        else solidForcesKernel<<<kForceBlocks, kForceThreads, lds, st>>>(p, material, pressure);
+        solidForcesSumKernel<<<unsigned((entries + 15) / 16), kForceSlices * 16, 0, st>>>(rows, dev, int(entries), scale);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(outHost, rows, entries * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(e));
+        return MGPS_ERR_HIP;
+    }
+    return MGPS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mgps_fields_solid_forces(double *out_host, const float *pressure, const int32_t *material, const float *cwx, const float *cwy,
+                             const float *cwz, const int32_t *bx, const int32_t *by, const int32_t *bz, const double *centres_host,
+                             int bodies, double scale, int gx, int gy, int gz, void *stream)
+try {
+    const char *fn = "mgps_fields_solid_forces";
+    if (int rc = forceCheckBodies(fn, bodies); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
+    if (!out_host) return exRefuse(fn, "out_host is NULL");
+    if (!pressure) return exRefuse(fn, "pressure is NULL");
+    if (!material) return exRefuse(fn, "material is NULL");
+    if (!cwx || !cwy || !cwz) return exRefuse(fn, "cut weights: three grids are required");
+    if (!bx || !by || !bz) return exRefuse(fn, "body: three grids are required");
+    if (!centres_host) return exRefuse(fn, "centres_host is NULL");
+    const float *cw[3] = {cwx, cwy, cwz};
+    const int32_t *body[3] = {bx, by, bz};
+    return runSolidForces(fn, out_host, Box{gx, gy, gz}, nullptr, pressure, nullptr, material, nullptr, cw, body, centres_host, bodies, scale,
+                          static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_solid_forces(const mgps_fields_slab *d, double *out_host, const float *pressure, const float *pressure_lo,
+                                  const int32_t *material, const int32_t *material_lo, const float *const cut_weights[3],
+                                  const int32_t *const body[3], const double *centres_host, int bodies, double scale, void *stream)
+try {
+    const char *fn = "mgps_fields_slab_solid_forces";
+    Slab s;
+    if (!readSlab(d, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    if (int rc = forceCheckBodies(fn, bodies); rc != MGPS_OK) return rc;
+    if (!out_host) return exRefuse(fn, "out_host is NULL");
+    if (!pressure) return exRefuse(fn, "pressure is NULL");
+    if (!material) return exRefuse(fn, "material is NULL");
+    if (!cut_weights || !cut_weights[0] || !cut_weights[1] || !cut_weights[2]) return exRefuse(fn, "cut_weights: three grids are required");
+    if (!body || !body[0] || !body[1] || !body[2]) return exRefuse(fn, "body: three grids are required");
+    if (!centres_host) return exRefuse(fn, "centres_host is NULL");
+    if (s.c0 > 0 && !pressure_lo) return exRefuse(fn, "pressure_lo: the plane below the window is required (c0 > 0)");
+    if (s.c0 > 0 && !material_lo) return exRefuse(fn, "material_lo: the plane below the window is required (c0 > 0)");
+    return runSolidForces(fn, out_host, s.whole(), &s, pressure, s.c0 > 0 ? pressure_lo : nullptr, material, s.c0 > 0 ? material_lo : nullptr,
+                          cut_weights, body, centres_host, bodies, scale, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_solid_forces_slab(struct mgps_solid_forces_slab *f, const mgps_comm *comm, const int *splits, void *stream)
+try {
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const char *fn = "mgps_solid_forces_slab";
+    // ---- what every rank shares: a refusal here is every rank's, before any collective and any HIP call
+    if (!f || f->struct_size != int(sizeof(struct mgps_solid_forces_slab))) return exRefuse(fn, "NULL or struct_size mismatch (mgps_solid_forces_slab)");
+    if (!comm || !splits || comm->struct_size < int(offsetof(mgps_comm, gather)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange ||
+        !comm->allreduce || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
+        return exRefuse(fn, "comm / splits: a mgps_comm with exchange and allreduce and the cuts are required");
+    if (int rc = forceCheckBodies(fn, f->bodies); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, f->gx, f->gy, f->gz); rc != MGPS_OK) return rc;
+    const int P = comm->size, rank = comm->rank;
+    mgps_fields_slab desc;
+    if (int rc = mgps_fields_slab_describe(&desc, f->gx, f->gy, f->gz, f->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
+    Slab s;
+    if (!readSlab(&desc, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    f->total_ms = f->exchange_ms = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int nzl = s.c1 - s.c0;
+    const bool lo = s.c0 > 0, hi = s.c1 < s.gz;
+    const size_t plane = size_t(s.gx) * s.gy, cells = plane * size_t(nzl), entries = size_t(f->bodies + 1) * kForceCols;
+    // ---- this rank's own arguments: a failure is carried by the all-reduce at the end, the rank takes part in both exchanges
+    int status = [&]() -> int {
+        if (!f->pressure) return exRefuse(fn, "pressure is NULL");
+        if (!f->liquid_phi || !f->solid_phi) return exRefuse(fn, "liquid_phi / solid_phi: both are required");
+        if (!f->cut_weights[0] || !f->cut_weights[1] || !f->cut_weights[2]) return exRefuse(fn, "cut_weights: three grids are required");
+        if (!f->body[0] || !f->body[1] || !f->body[2]) return exRefuse(fn, "body: three grids are required");
+        if (!f->centres) return exRefuse(fn, "centres is NULL");
+        if (!f->out) return exRefuse(fn, "out is NULL");
+        return MGPS_OK;
+    }();
+    if (P == 1 && status != MGPS_OK) return status;
+    // the buffers the exchanges need: without them the rank cannot take part, and returns at once and alone
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        setLastGlobalError("no HIP device is visible (this library has no CPU path)");
+        return MGPS_ERR_NO_DEVICE;
+    }
+    DevPool pool;
+    int32_t *material = nullptr;
+    float *phiHalo = nullptr, *up = nullptr, *below = nullptr;  // messages: [pressure plane | material plane]
+    try {
+        material = pool.get<int32_t>(cells);
+        phiHalo = pool.get<float>(2 * plane);
+        if (hi) up = pool.get<float>(2 * plane);
+        if (lo) below = pool.get<float>(2 * plane);
+    } catch (const std::bad_alloc &) {
+        setLastGlobalError(std::string(fn) + ": device allocation failed");
+        return MGPS_ERR_ALLOC;
+    }
+    auto step = [&](int rc) {
+        if (status == MGPS_OK) status = rc;
+    };
+    auto hipStep = [&](hipError_t e, const char *what) {
+        if (e != hipSuccess && status == MGPS_OK) {
+            setLastGlobalError(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
+            status = MGPS_ERR_HIP;
+        }
+    };
+    double exchangeMs = 0;
+    const size_t planeBytes = plane * sizeof(float);
+    float *phiLo = lo ? phiHalo : nullptr, *phiHi = hi ? phiHalo + plane : nullptr;
+    if (P > 1) {  // 1. the liquid_phi plane, both ways (a rank without the array sends what its halo buffer holds)
+        const float *first = status == MGPS_OK ? f->liquid_phi : phiHalo, *last = status == MGPS_OK ? f->liquid_phi + size_t(nzl - 1) * plane : phiHalo;
+        const auto a = clock::now();
+        const int rc = comm->exchange(comm->user, lo ? first : nullptr, lo ? planeBytes : 0, phiLo, lo ? planeBytes : 0, hi ? last : nullptr,
+                                      hi ? planeBytes : 0, phiHi, hi ? planeBytes : 0, st);
+        exchangeMs += ms(a, clock::now());
+        if (rc != 0) {
+            setLastGlobalError(std::string(fn) + ": exchange failed (liquid_phi)");
+            return MGPS_ERR_COMM;
+        }
+    }
+    // 2. the projection's labels, made again
+    if (status == MGPS_OK)
+        step(mgps_fields_slab_material_labels(&desc, material, f->liquid_phi, phiLo, phiHi, f->solid_phi, f->cut_weights[0], f->cut_weights[1],
+                                              f->cut_weights[2], st));
+    if (P > 1) {  // 3. the last pressure plane and the last material plane go up in one message; the lower halo arrives from below
+        if (hi && status == MGPS_OK) {
+            hipStep(hipMemcpyAsync(up, f->pressure + size_t(nzl - 1) * plane, planeBytes, hipMemcpyDeviceToDevice, st), "packing the pressure plane");
+            hipStep(hipMemcpyAsync(up + plane, material + size_t(nzl - 1) * plane, planeBytes, hipMemcpyDeviceToDevice, st), "packing the material plane");
+        }
+        const auto a = clock::now();
+        const int rc = comm->exchange(comm->user, nullptr, 0, below, lo ? 2 * planeBytes : 0, up, hi ? 2 * planeBytes : 0, nullptr, 0, st);
+        exchangeMs += ms(a, clock::now());
+        if (rc != 0) {
+            setLastGlobalError(std::string(fn) + ": exchange failed (pressure and material planes)");
+            return MGPS_ERR_COMM;
+        }
+    }
+    // 4. the window pass
+    std::vector<double> rows(entries + size_t(P), 0.0);
+    if (status == MGPS_OK)
+        step(runSolidForces(fn, rows.data(), s.whole(), &s, f->pressure, lo ? below : nullptr, material,
+                            lo ? reinterpret_cast<const int32_t *>(below + plane) : nullptr, f->cut_weights, f->body, f->centres, f->bodies, f->scale, st));
+    // 5. the rows of all ranks, and their statuses (every rank fills its own slot)
+    if (P > 1) {
+        if (status != MGPS_OK) std::fill(rows.begin(), rows.begin() + ptrdiff_t(entries), 0.0);
+        rows[entries + size_t(rank)] = double(status);
+        if (comm->allreduce(comm->user, rows.data(), int(rows.size()), 0) != 0) {
+            setLastGlobalError(std::string(fn) + ": all-reduce failed (rows)");
+            return MGPS_ERR_COMM;
+        }
+        for (int r = 0; r < P && status == MGPS_OK; ++r)
+            if (int(rows[entries + size_t(r)]) != MGPS_OK) {
+                status = int(rows[entries + size_t(r)]);
+                setLastGlobalError(std::string(fn) + ": rank " + std::to_string(r) + " failed (status " + std::to_string(status) + ")");
+            }
+    }
+    if (status == MGPS_OK) std::copy(rows.begin(), rows.begin() + ptrdiff_t(entries), f->out);
+    f->exchange_ms = exchangeMs;
+    f->total_ms = ms(t0, clock::now());
+    return status;
+}
+MGPS_API_CATCH(nullptr)
+
+}  // extern "C"

@@ -537,3 +537,88 @@ def extrapolate_velocity_slab(comm, splits, global_shape, velocity, valid_faces,
     cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
     check(lib().mgps_extrapolate_velocity_slab(C.byref(ex), C.byref(comm.struct), cuts, _stream()))
     return {"filled": [int(ex.filled[a]) for a in range(3)], "total_ms": ex.total_ms, "exchange_ms": ex.exchange_ms, "layer": layer}
+
+
+# ---- pressure feedback: force and torque of the pressure on solid bodies (include/mgps_fields.h) ----------------
+def _centres(centres):
+    """(bodies + 1, 3) float64 host array (row 0: the point the unowned faces' torque refers to) -> (array, bodies)"""
+    import numpy as np
+
+    c = np.ascontiguousarray(centres, dtype=np.float64)
+    assert c.ndim == 2 and c.shape[1] == 3 and c.shape[0] >= 2, c.shape
+    return c, c.shape[0] - 1
+
+
+def solidForces(pressure, material, cut_cell_weights, body, centres, scale=1.0):
+    """mgps_fields_solid_forces: the net force and torque of `pressure` on the closed part of the cut faces, per body.  `body`: three
+    int32 face grids of body ids (1 .. bodies; anything else counts for row 0); `centres`: (bodies + 1, 3) host array of x, y, z in
+    cell units.  Returns a (bodies + 1, 8) float64 numpy array: force[3], torque[3] (both times `scale`), wet closed area, wet faces."""
+    import numpy as np
+
+    shape = tuple(material.shape)
+    faces = _face3(shape)
+    cw = [_chk(cut_cell_weights[a], faces[a], torch.float32) for a in range(3)]
+    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
+    c, bodies = _centres(centres)
+    out = np.zeros((bodies + 1, 8), dtype=np.float64)
+    check(lib().mgps_fields_solid_forces(out.ctypes.data_as(C.c_void_p), _p(_chk(pressure, shape, torch.float32)), _p(_chk(material, shape, torch.int32)),
+                                         _p(cw[0]), _p(cw[1]), _p(cw[2]), _p(ids[0]), _p(ids[1]), _p(ids[2]), c.ctypes.data_as(C.c_void_p),
+                                         int(bodies), C.c_double(scale), *_g(shape), _stream()))
+    return out
+
+
+def solidForcesSlab(d, pressure, pressure_lo, material, material_lo, cut_cell_weights, body, centres, scale=1.0):
+    """mgps_fields_slab_solid_forces: this rank's rows on the window `d` (the caller adds the ranks').  pressure_lo / material_lo: base
+    plane c0 - 1 (None at c0 == 0); cut_cell_weights / body: the window's face grids."""
+    import numpy as np
+
+    shape = d.base_shape
+    faces = _face3(shape)
+    cw = [_chk(cut_cell_weights[a], faces[a], torch.float32) for a in range(3)]
+    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
+    for t, dtype in ((pressure_lo, torch.float32), (material_lo, torch.int32)):
+        if t is not None:
+            _chk(t, (d.gy, d.gx), dtype)
+    c, bodies = _centres(centres)
+    out = np.zeros((bodies + 1, 8), dtype=np.float64)
+    check(lib().mgps_fields_slab_solid_forces(C.byref(d), out.ctypes.data_as(C.c_void_p), _p(_chk(pressure, shape, torch.float32)), _p(pressure_lo),
+                                              _p(_chk(material, shape, torch.int32)), _p(material_lo), _arr3(cw), _arr3(ids),
+                                              c.ctypes.data_as(C.c_void_p), int(bodies), C.c_double(scale), _stream()))
+    return out
+
+
+class SolidForcesSlab(C.Structure):
+    """struct mgps_solid_forces_slab (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("power_of_two", C.c_int), ("bodies", C.c_int),
+        ("pressure", C.c_void_p), ("liquid_phi", C.c_void_p), ("solid_phi", C.c_void_p), ("cut_weights", C.c_void_p * 3), ("body", C.c_void_p * 3),
+        ("centres", C.c_void_p), ("scale", C.c_double), ("out", C.c_void_p), ("total_ms", C.c_double), ("exchange_ms", C.c_double),
+    ]
+
+
+def solid_forces_slab(comm, splits, global_shape, pressure, liquid_phi, solid_phi, cut_weights, body, centres, scale=1.0, power_of_two=True):
+    """mgps_solid_forces_slab: the forces on the CUDA tensors of this rank's window of the grid `global_shape` = (gz, gy, gx), a
+    collective over the transport `comm`; meant for the fields project_free_surface_slab took and the pressure it published, with the
+    same `splits`.  Returns {"rows": (bodies + 1, 8) float64 array of the whole grid's numbers, "total_ms", "exchange_ms"}."""
+    import numpy as np
+
+    d = slab_window(global_shape, power_of_two, splits, comm.rank)
+    shape = d.base_shape
+    faces = _face3(shape)
+    c, bodies = _centres(centres)
+    out = np.zeros((bodies + 1, 8), dtype=np.float64)
+    sf = SolidForcesSlab()
+    sf.struct_size = C.sizeof(SolidForcesSlab)
+    sf.gz, sf.gy, sf.gx = global_shape
+    sf.power_of_two, sf.bodies = int(bool(power_of_two)), int(bodies)
+    sf.pressure = _chk(pressure, shape, torch.float32).data_ptr()
+    sf.liquid_phi, sf.solid_phi = _chk(liquid_phi, shape, torch.float32).data_ptr(), _chk(solid_phi, shape, torch.float32).data_ptr()
+    for a in range(3):
+        sf.cut_weights[a] = _chk(cut_weights[a], faces[a], torch.float32).data_ptr()
+        # (a missing entry stays NULL: the library carries the refusal to every rank)
+        sf.body[a] = _chk(body[a], faces[a], torch.int32).data_ptr() if body[a] is not None else None
+    sf.centres, sf.scale, sf.out = c.ctypes.data, float(scale), out.ctypes.data
+    cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
+    check(lib().mgps_solid_forces_slab(C.byref(sf), C.byref(comm.struct), cuts, _stream()))
+    return {"rows": out, "total_ms": sf.total_ms, "exchange_ms": sf.exchange_ms}

@@ -309,6 +309,74 @@ typedef struct mgps_extrapolation_slab {
 } mgps_extrapolation_slab;
 int mgps_extrapolate_velocity_slab(mgps_extrapolation_slab *e, const mgps_comm *comm, const int *splits, void *stream);
 
+/* ---- pressure feedback: net pressure force and torque on solid bodies -------------------------------------
+ * The projection takes the solid velocity through the closed part 1 - w of every cut face (mgps_fields_rhs); this is the other
+ * half, the operator J^T p: what the pressure pushes back with, summed per body.  No counterpart in the reference; the definition
+ * here is the contract.
+ *   Device inputs on the base grid: pressure (float cell grid), material (int32 cell grid), the three cut-weight face grids and
+ *   body[3], int32 face grids: the id of the body that owns the closed part of a face, sampled by the caller at the face centre
+ *   (as solid_velocity is).  Host inputs: bodies (1 .. 255), centres[(bodies + 1) * 3] doubles (x, y, z in cell units from the
+ *   grid's corner: cell (i, j, k) has its centre at (i + 1/2, j + 1/2, k + 1/2), the x-face (i, j, k) at (i, j + 1/2, k + 1/2)) and
+ *   scale.
+ *   Face f of axis a with backward cell B and forward cell F (a cell outside the grid does not exist):
+ *     w = cut_weights[a][f], closed fraction s = w < 1.f ? 1.f - w : 0.f in float32 (the expressions of the right-hand side);
+ *     pB = pressure[B] if B exists and material[B] == LIQUID, else 0; pF likewise;
+ *     the face is WET when s > 0 and B or F is LIQUID;
+ *     phi = double(s) * (double(pB) - double(pF)): the push of the liquid on the solid along +a;
+ *     row r = body[a][f] if 1 <= body[a][f] <= bodies, else 0.
+ *   Row 0 collects every wet face no body owns (static walls, ids out of range): every wet face lands in exactly one row and the
+ *   sum of the force columns over the rows does not depend on the ids.
+ *   out_host[(bodies + 1) * 8] doubles, one row per r: [0..2] scale * sum of phi e_a (force), [3..5] scale * sum of
+ *   (x_f - centres[r]) x (phi e_a) (torque, arm in cells), [6] sum of s (wet closed area in faces, not scaled), [7] the number of
+ *   wet faces.  Sums are in fp64, in an order that is the implementation's but fixed: the same inputs give the same bits on every
+ *   run (no floating-point atomics; the launch shape depends on the extents and on `bodies` only).
+ * Units: the pressure is in velocity units (velocity -= p_F - p_B), so scale = density dx^3 / dt gives the force in newtons; the
+ * torque then still needs a factor dx.
+ * Limits: an AIR cell contributes 0 -- with surface tension on, the interface pressure p_G is not seen by this pass; 255 bodies
+ * per call; the cell-centred pressure sits half a cell off the face.
+ * Adjoint of the solid term of the right-hand side: with zero fluid velocity and solid velocities sv, the right-hand side is
+ * rhs_c = sum_a (1 - w_back) sv_back - (1 - w_fwd) sv_fwd at LIQUID c, hence sum_c p_c rhs_c = - sum_a sum_f sv_a[f] phi_a[f]; for
+ * a rigid motion sv_a[f] = (U_r + omega_r x (x_f - centres[r]))_a per row that is - sum_r (U_r . F_r + omega_r . T_r) at scale 1.
+ * Every entry refuses, before any device work: a NULL array, bodies outside 1 .. 255, a non-positive extent. */
+/* on whole grids; synchronises the stream */
+int mgps_fields_solid_forces(double *out_host, const float *pressure, const int32_t *material, const float *cwx, const float *cwy,
+                             const float *cwz, const int32_t *bx, const int32_t *by, const int32_t *bz, const double *centres_host,
+                             int bodies, double scale, int gx, int gy, int gz, void *stream);
+/* The rank's part on a slab window, without communication: out_host holds the sums over the window's faces, the caller adds the
+ * ranks' rows.  The x- and y-faces of the owned planes count; of the z-faces the planes c0 .. c1 - 1, on the last rank also plane
+ * gz (the counting rule of filled_dev above): a sum over the ranks counts every face once.  Only the lower halo is read: base
+ * plane c0 - 1 of pressure and material (NULL at c0 == 0, required elsewhere).  cut_weights / body: the window's face grids;
+ * positions use the plane index of the whole grid.  Synchronises the stream */
+int mgps_fields_slab_solid_forces(const mgps_fields_slab *d, double *out_host, const float *pressure, const float *pressure_lo,
+                                  const int32_t *material, const int32_t *material_lo, const float *const cut_weights[3],
+                                  const int32_t *const body[3], const double *centres_host, int bodies, double scale, void *stream);
+/* The forces on the DEVICE fields of one slab rank, a collective over `comm` on what mgps_project_free_surface_slab took
+ * (liquid_phi, solid_phi, cut_weights) and published (pressure), with the same gx, gy, gz (the WHOLE grid), power_of_two and cuts.
+ * Steps: the liquid_phi plane is traded with both neighbours; mgps_fields_slab_material_labels makes the projection's labels
+ * again; one packed message to the upper neighbour -- the rank's last pressure plane and last material plane; nothing goes down,
+ * since only the lower halo is read -- ; the window pass; one all-reduce (sum) of the rows with the ranks' statuses folded in.  With comm->size =
+ * 1 it is the device-resident form: no exchange and no all-reduce; gatherv / scatterv are never used.  What every rank shares
+ * (struct_size, extents, bodies, the cuts, the transport) is refused at once; a rank-local failure (a missing array, a failing
+ * kernel) is carried by the all-reduce, the rank still takes part in both exchanges: all ranks return the same status.  A rank
+ * whose transport call fails returns MGPS_ERR_COMM at once and alone, as in mgps_project_free_surface_slab; so does, with
+ * MGPS_ERR_ALLOC or MGPS_ERR_NO_DEVICE, a rank that cannot get the buffers an exchange needs.
+ * The struct and the call share one name, as stat does: a struct tag, not a typedef (write `struct mgps_solid_forces_slab`). */
+struct mgps_solid_forces_slab {
+    int struct_size;             /* sizeof(struct mgps_solid_forces_slab) */
+    int gx, gy, gz;              /* the WHOLE simulation grid */
+    int power_of_two;            /* the expansion the cuts refer to */
+    int bodies;                  /* 1 .. 255 */
+    const float *pressure;       /* the window's device arrays: what the projection published ... */
+    const float *liquid_phi, *solid_phi; /* ... and took */
+    const float *cut_weights[3];
+    const int32_t *body[3];
+    const double *centres;       /* host, (bodies + 1) * 3 */
+    double scale;
+    double *out;                 /* host, (bodies + 1) * 8: the whole grid's numbers, the same on every rank */
+    double total_ms, exchange_ms; /* this rank's host wall clock: the call / inside the exchanges */
+};
+int mgps_solid_forces_slab(struct mgps_solid_forces_slab *s, const mgps_comm *comm, const int *splits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
