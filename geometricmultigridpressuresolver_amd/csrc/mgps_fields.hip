@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -15,6 +14,7 @@
 
 #include "mgps_fields.h"
 #include "mgps_internal.h"
+#include "mgps_slab_call.h"
 
 using namespace mgps;
 
@@ -760,23 +760,19 @@ size_t faceCount(int gx, int gy, int gz, int axis) { return size_t(gx + (axis ==
 template <class P>
 int checkProjectionFields(const P *p, const char *fn, bool shapeOk, const char *missing)
 {
-    auto refuse = [fn](const std::string &what) {
-        setLastGlobalError(std::string(fn) + ": " + what);
-        return int(MGPS_ERR_INVALID_ARGUMENT);
-    };
     bool ok = shapeOk && p->liquid_phi && p->solid_phi && p->pressure;
     for (int a = 0; a < 3; ++a) ok = ok && p->cut_weights[a] && p->velocity[a];
     const bool haveSolidVel = p->solid_velocity[0] && p->solid_velocity[1] && p->solid_velocity[2];
     if (!ok || (!haveSolidVel && (p->solid_velocity[0] || p->solid_velocity[1] || p->solid_velocity[2])))
-        return refuse(std::string(missing) + " (solid velocities: all three or none)");
+        return refuse(fn, std::string(missing) + " (solid velocities: all three or none)");
     // surface tension: dt, dx and density are read only with surface_tension > 0
     const double sigma = p->surface_tension;
-    if (!std::isfinite(sigma) || sigma < 0) return refuse("surface_tension must be finite and >= 0");
+    if (!std::isfinite(sigma) || sigma < 0) return refuse(fn, "surface_tension must be finite and >= 0");
     if (sigma > 0) {
         const char *what = !(std::isfinite(p->dt) && p->dt > 0) ? "dt" : !(std::isfinite(p->dx) && p->dx > 0) ? "dx"
                          : !(std::isfinite(p->density) && p->density > 0) ? "density" : nullptr;
-        if (what) return refuse(std::string("surface_tension > 0 needs a finite ") + what + " > 0");
-        if (p->surface_pressure) return refuse("surface_tension and surface_pressure are both set (pass one of them)");
+        if (what) return refuse(fn, std::string("surface_tension > 0 needs a finite ") + what + " > 0");
+        if (p->surface_pressure) return refuse(fn, "surface_tension and surface_pressure are both set (pass one of them)");
     }
     return MGPS_OK;
 }
@@ -820,7 +816,7 @@ extern "C" {
 
 int mgps_project_free_surface(mgps_projection *p, const mgps_options *opt)
 try {
-    using clock = std::chrono::steady_clock;
+    using clock = SlabCall::Clock;
     const auto t0 = clock::now();
     if (!p || p->struct_size != int(sizeof(mgps_projection))) {
         setLastGlobalError("mgps_project_free_surface: NULL or struct_size mismatch");
@@ -954,7 +950,7 @@ try {
         for (int a = 0; a < 3; ++a)
             if (p->valid_faces[a] && he == hipSuccess) he = hipMemcpy(p->valid_faces[a], valid[a], faceCount(gx, gy, gz, a), hipMemcpyDeviceToHost);
         if (he != hipSuccess) return failHip("download", he);
-        p->setup_ms = p->total_ms = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+        p->setup_ms = p->total_ms = SlabCall::ms(t0, clock::now());
         p->solve_ms = 0;
         p->stats.outcome = MGPS_PCG_RHS_ZERO;
         return MGPS_OK;
@@ -1031,9 +1027,9 @@ try {
     }
     if (he != hipSuccess) return failHip("download", he);
     const auto t3 = clock::now();
-    p->setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    p->solve_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    p->total_ms = std::chrono::duration<double, std::milli>(t3 - t0).count();
+    p->setup_ms = SlabCall::ms(t0, t1);
+    p->solve_ms = SlabCall::ms(t1, t2);
+    p->total_ms = SlabCall::ms(t0, t3);
     if (solveRc != MGPS_OK) setLastGlobalError("mgps_project_free_surface: interrupted");
     return solveRc;
 }
@@ -1521,34 +1517,10 @@ MGPS_API_CATCH(nullptr)
 
 // ---- one-call projection on slab ranks (mgps_project_free_surface_slab) -----------------------------------------------------------
 namespace {
-// What the ranks agree on between two steps: one sum all-reduce that carries `sums`, the largest of each entry of `maxes` (every
-// rank fills its own slot of a size-wide row, so a sum is a max) and the ranks' statuses the same way.  Every rank calls it at
-// the same places; it returns this rank's failure, or the first other rank's, or MGPS_OK on every rank together.
-int agreeRanks(const mgps_comm *comm, int status, const char *where, double *sums = nullptr, int nsums = 0, double *maxes = nullptr, int nmaxes = 0)
+// a HIP call of a slab one-call (mgps_slab_call.h): its failure is the rank's own and travels in the next agreement
+void hipStep(SlabCall &c, hipError_t e, const char *what)
 {
-    const int P = comm->size, rank = comm->rank;
-    std::vector<double> v(size_t(nsums) + size_t(nmaxes + 1) * size_t(P), 0.0);
-    for (int q = 0; q < nsums; ++q) v[size_t(q)] = sums[q];
-    for (int q = 0; q < nmaxes; ++q) v[size_t(nsums) + size_t(q) * P + rank] = maxes[q];
-    v[size_t(nsums) + size_t(nmaxes) * P + rank] = double(status);
-    if (comm->allreduce(comm->user, v.data(), int(v.size()), 0) != 0) {
-        setLastGlobalError(std::string("mgps_project_free_surface_slab: all-reduce failed (") + where + ")");
-        return MGPS_ERR_COMM;
-    }
-    for (int q = 0; q < nsums; ++q) sums[q] = v[size_t(q)];
-    for (int q = 0; q < nmaxes; ++q) {
-        const double *row = v.data() + size_t(nsums) + size_t(q) * P;
-        maxes[q] = *std::max_element(row, row + P);
-    }
-    if (status != MGPS_OK) return status;
-    const double *st = v.data() + size_t(nsums) + size_t(nmaxes) * P;
-    for (int r = 0; r < P; ++r)
-        if (int(st[r]) != MGPS_OK) {
-            setLastGlobalError(std::string("mgps_project_free_surface_slab: rank ") + std::to_string(r) + " failed (" + where + ", status " +
-                               std::to_string(int(st[r])) + ")");
-            return int(st[r]);
-        }
-    return MGPS_OK;
+    if (e != hipSuccess) c.fail(MGPS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 }  // namespace
 
@@ -1556,30 +1528,23 @@ extern "C" {
 
 int mgps_project_free_surface_slab(mgps_projection_slab *p, const mgps_options *opt, const mgps_comm *comm, const int *splits, void *stream)
 try {
-    using clock = std::chrono::steady_clock;
-    const auto t0 = clock::now();
-    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    auto invalid = [](const std::string &what) {
-        setLastGlobalError("mgps_project_free_surface_slab: " + what);
-        return int(MGPS_ERR_INVALID_ARGUMENT);
-    };
+    using clock = SlabCall::Clock;
+    SlabCall c;
+    const char *fn = "mgps_project_free_surface_slab";
+    const auto t0 = c.t0;
     // ---- what every rank shares: a refusal here is every rank's, before any collective
-    if (!p || p->struct_size != int(sizeof(mgps_projection_slab))) return invalid("NULL or struct_size mismatch");
-    if (!comm || !splits || comm->struct_size < int(offsetof(mgps_comm, gatherv)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange ||
-        !comm->allreduce || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
-        return invalid("a complete mgps_comm and the cuts are required");
-    mgps_comm cm{};
-    std::memcpy(&cm, comm, size_t(comm->struct_size));  // (struct_size bytes are the caller's; the rest reads as NULL)
-    cm.struct_size = int(sizeof(mgps_comm));
-    const int P = cm.size, rank = cm.rank;
+    if (!p || p->struct_size != int(sizeof(mgps_projection_slab))) return refuse(fn, "NULL or struct_size mismatch");
+    if (int rc = c.open(fn, comm, splits, offsetof(mgps_comm, gatherv)); rc != MGPS_OK) return rc;
+    const mgps_comm &cm = c.cm;
+    const int P = c.P, rank = c.rank;
     if (P > 1 && (!cm.gatherv || !cm.scatterv))
-        return invalid("the collapse of uneven cuts and the enclosed-liquid merge go through gatherv and scatterv (and, with host_setup, the whole grid's labels): the transport has none");
+        return refuse(fn, "the collapse of uneven cuts and the enclosed-liquid merge go through gatherv and scatterv (and, with host_setup, the whole grid's labels): the transport has none");
     mgps_options o;
     if (int rc = readOptions(opt, o, "mgps_project_free_surface_slab: "); rc != MGPS_OK) return rc;
     mgps_fields_slab desc;
     if (int rc = mgps_fields_slab_describe(&desc, p->gx, p->gy, p->gz, p->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
     Slab s;
-    if (!readSlab(&desc, s, "mgps_project_free_surface_slab")) return MGPS_ERR_INVALID_ARGUMENT;
+    if (!readSlab(&desc, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
     int levels = 0;
     {
         int dims[3], off;
@@ -1616,8 +1581,8 @@ try {
         void *&p;
         ~HostBlock() { mgps_host_free(p); }
     } hostBlock{labelsHost};
-    int status = [&]() -> int {
-        if (int rc = checkProjectionFields(p, "mgps_project_free_surface_slab", true, "missing field"); rc != MGPS_OK) return rc;
+    c.step([&]() -> int {
+        if (int rc = checkProjectionFields(p, fn, true, "missing field"); rc != MGPS_OK) return rc;
         if (int rc = selectDevice(o.device); rc != MGPS_OK) return rc;
         try {
             material = pool.get<int32_t>(cells + 2 * plane);
@@ -1634,47 +1599,25 @@ try {
             labelsAll = pool.get<uint8_t>(labelsToHosts ? ecells : size_t(nze) * eplane);
             count = pool.get<unsigned long long>(1);
         } catch (const std::bad_alloc &) {
-            setLastGlobalError("mgps_project_free_surface_slab: device allocation failed");
-            return MGPS_ERR_ALLOC;
+            return c.fail(MGPS_ERR_ALLOC, "device allocation failed");
         }
         if (labelsToHosts) labelsHost = mgps_host_alloc(ecells);
-        if (labelsToHosts && !labelsHost) {
-            setLastGlobalError("mgps_project_free_surface_slab: host allocation of the whole grid's labels failed");
-            return MGPS_ERR_ALLOC;
-        }
+        if (labelsToHosts && !labelsHost) return c.fail(MGPS_ERR_ALLOC, "host allocation of the whole grid's labels failed");
         return MGPS_OK;
-    }();
+    }());
     {
         double flags[2] = {surface ? 1.0 : 0.0, surface ? 0.0 : 1.0};  // (both set on some rank: the ranks disagree)
-        if (int rc = agreeRanks(&cm, status, "arguments", nullptr, 0, flags, 2); rc != MGPS_OK) return rc;
-        if (flags[0] != 0 && flags[1] != 0) return invalid("surface tension / surface_pressure is set on some ranks only");
+        if (int rc = c.agree("arguments", nullptr, 0, flags, 2); rc != MGPS_OK) return rc;
+        if (flags[0] != 0 && flags[1] != 0) return refuse(fn, "surface tension / surface_pressure is set on some ranks only");
     }
     // (from here on the buffers exist on every rank: a failing rank still takes part in every exchange, with whatever its buffers
-    //  hold, and the next all-reduce carries its status)
-    double exchangeMs = 0;
-    auto hipStep = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && status == MGPS_OK) {
-            setLastGlobalError(std::string("mgps_project_free_surface_slab: ") + what + ": " + hipGetErrorString(e));
-            status = MGPS_ERR_HIP;
-        }
-    };
-    auto step = [&](int rc) {
-        if (status == MGPS_OK) status = rc;
-    };
+    //  hold, and the next agreement carries its status)
     // trade one plane with each neighbour: own first plane down, own last plane up; what arrives lands in halo[0] / halo[1]
     auto tradePlane = [&](const void *own, void *haloLo, void *haloHi, size_t elem, const char *what) -> int {
-        if (P == 1) return MGPS_OK;
-        const auto a = clock::now();
         const size_t bytes = plane * elem;
         const char *first = static_cast<const char *>(own), *last = first + size_t(nzl - 1) * bytes;
-        const int rc = cm.exchange(cm.user, lo ? first : nullptr, lo ? bytes : 0, lo ? haloLo : nullptr, lo ? bytes : 0, hi ? last : nullptr, hi ? bytes : 0,
-                                   hi ? haloHi : nullptr, hi ? bytes : 0, st);
-        exchangeMs += ms(a, clock::now());
-        if (rc != 0) {
-            setLastGlobalError(std::string("mgps_project_free_surface_slab: exchange failed (") + what + ")");
-            return MGPS_ERR_COMM;
-        }
-        return MGPS_OK;
+        return c.trade(lo ? first : nullptr, lo ? bytes : 0, lo ? haloLo : nullptr, lo ? bytes : 0, hi ? last : nullptr, hi ? bytes : 0,
+                       hi ? haloHi : nullptr, hi ? bytes : 0, st, what);
     };
 #define SLAB_COMM(call)                 \
     do {                                \
@@ -1688,33 +1631,33 @@ try {
     float *phiLo = lo ? phiHalo : nullptr, *phiHi = hi ? phiHalo + plane : nullptr;
     // ---- 1. phi plane, material labels, material plane, the faces pass and the labels pass (Plug.cpp:270-362)
     SLAB_COMM(tradePlane(p->liquid_phi, phiHalo, phiHalo + plane, sizeof(float), "liquid_phi"));
-    if (status == MGPS_OK) step(mgps_fields_slab_material_labels(&desc, matOwn, p->liquid_phi, phiLo, phiHi, p->solid_phi, cw[0], cw[1], cw[2], st));
+    if (c.status == MGPS_OK) c.step(mgps_fields_slab_material_labels(&desc, matOwn, p->liquid_phi, phiLo, phiHi, p->solid_phi, cw[0], cw[1], cw[2], st));
     SLAB_COMM(tradePlane(matOwn, material, matOwn + cells, sizeof(int32_t), "material labels"));
     uint8_t *labelsWin = labelsToHosts ? labelsAll + size_t(s.e0) * eplane : labelsAll;
-    if (status == MGPS_OK) step(mgps_fields_slab_faces(&desc, valid, w, matOwn, matLo, matHi, p->liquid_phi, phiLo, phiHi, cw, st));
-    if (status == MGPS_OK) step(mgps_fields_slab_labels(&desc, labelsWin, matOwn, matLo, matHi, w, st));
+    if (c.status == MGPS_OK) c.step(mgps_fields_slab_faces(&desc, valid, w, matOwn, matLo, matHi, p->liquid_phi, phiLo, phiHi, cw, st));
+    if (c.status == MGPS_OK) c.step(mgps_fields_slab_labels(&desc, labelsWin, matOwn, matLo, matHi, w, st));
     // ---- 2. liquid cells over all ranks; a domain without liquid has nothing to solve (the single-device rule)
     double liquid = 0;
-    if (status == MGPS_OK) {
+    if (c.status == MGPS_OK) {
         unsigned long long mine = 0;
-        hipStep(hipMemsetAsync(count, 0, sizeof(unsigned long long), st), "liquid cell count");
-        if (status == MGPS_OK) {
+        hipStep(c, hipMemsetAsync(count, 0, sizeof(unsigned long long), st), "liquid cell count");
+        if (c.status == MGPS_OK) {
             countLiquidKernel<<<unsigned(std::min<size_t>((cells + 255) / 256, 4096)), 256, 0, st>>>(matOwn, cells, count);
-            hipStep(hipMemcpyAsync(&mine, count, sizeof(mine), hipMemcpyDeviceToHost, st), "liquid cell count");
-            hipStep(hipStreamSynchronize(st), "field passes");
+            hipStep(c, hipMemcpyAsync(&mine, count, sizeof(mine), hipMemcpyDeviceToHost, st), "liquid cell count");
+            hipStep(c, hipStreamSynchronize(st), "field passes");
         }
         liquid = double(mine);
     }
-    SLAB_COMM(agreeRanks(&cm, status, "field passes", &liquid, 1));
+    SLAB_COMM(c.agree("field passes", &liquid, 1));
     p->liquid_cells = liquid;
     const auto t1 = clock::now();
-    p->stage_ms[0] = ms(t0, t1);
+    p->stage_ms[0] = SlabCall::ms(t0, t1);
     if (liquid == 0) {
-        hipStep(hipMemsetAsync(p->pressure, 0, cells * sizeof(float), st), "pressure clear");
-        hipStep(hipStreamSynchronize(st), "pressure clear");
-        SLAB_COMM(agreeRanks(&cm, status, "pressure clear"));
-        p->stage_ms[6] = exchangeMs;
-        p->setup_ms = p->total_ms = ms(t0, clock::now());
+        hipStep(c, hipMemsetAsync(p->pressure, 0, cells * sizeof(float), st), "pressure clear");
+        hipStep(c, hipStreamSynchronize(st), "pressure clear");
+        SLAB_COMM(c.agree("pressure clear"));
+        p->stage_ms[6] = c.exchangeMs;
+        p->setup_ms = p->total_ms = SlabCall::ms(t0, clock::now());
         p->stats.outcome = MGPS_PCG_RHS_ZERO;
         return MGPS_OK;
     }
@@ -1727,26 +1670,22 @@ try {
             counts[size_t(r)] = r == 0 ? 0 : size_t(splits[r + 1] - splits[r]) * eplane;  // (rank 0's window is in place)
             displs[size_t(r)] = size_t(splits[r]) * eplane;
         }
-        if (cm.gatherv(cm.user, labelsWin, rank == 0 ? 0 : size_t(nze) * eplane, rank == 0 ? labelsAll : nullptr, counts.data(), displs.data(), 0, st) != 0) {
-            setLastGlobalError("mgps_project_free_surface_slab: gatherv of the labels failed");
-            return MGPS_ERR_COMM;
-        }
+        if (cm.gatherv(cm.user, labelsWin, rank == 0 ? 0 : size_t(nze) * eplane, rank == 0 ? labelsAll : nullptr, counts.data(), displs.data(), 0, st) != 0)
+            return c.leave(MGPS_ERR_COMM, "gatherv of the labels failed");
         for (int r = 0; r < P; ++r) {
             counts[size_t(r)] = r == 0 ? 0 : ecells;
             displs[size_t(r)] = 0;
         }
-        if (cm.scatterv(cm.user, rank == 0 ? labelsAll : nullptr, counts.data(), displs.data(), labelsAll, rank == 0 ? 0 : ecells, 0, st) != 0) {
-            setLastGlobalError("mgps_project_free_surface_slab: scatterv of the labels failed");
-            return MGPS_ERR_COMM;
-        }
+        if (cm.scatterv(cm.user, rank == 0 ? labelsAll : nullptr, counts.data(), displs.data(), labelsAll, rank == 0 ? 0 : ecells, 0, st) != 0)
+            return c.leave(MGPS_ERR_COMM, "scatterv of the labels failed");
     }
     if (labelsToHosts) {
-        hipStep(hipMemcpyAsync(labelsHost, labelsAll, ecells, hipMemcpyDeviceToHost, st), "labels to the host");
-        hipStep(hipStreamSynchronize(st), "labels to the host");
+        hipStep(c, hipMemcpyAsync(labelsHost, labelsAll, ecells, hipMemcpyDeviceToHost, st), "labels to the host");
+        hipStep(c, hipStreamSynchronize(st), "labels to the host");
     }
-    SLAB_COMM(agreeRanks(&cm, status, labelsToHosts ? "labels to the host" : "labels"));
+    SLAB_COMM(c.agree(labelsToHosts ? "labels to the host" : "labels"));
     const auto t2 = clock::now();
-    p->stage_ms[1] = ms(t1, t2);
+    p->stage_ms[1] = SlabCall::ms(t1, t2);
     // ---- 4. the slab solver on the rank's expanded weights (borrowed: the pool outlives the solver), rhs, warm start, surface
     //         term, enclosed-liquid projection, MG-PCG (Plug.cpp:386-629)
     mgps_solver *mg = nullptr;
@@ -1761,31 +1700,31 @@ try {
         ~Guard() { mgps_destroy(h); }
     } guard{mg};
     const auto t3 = clock::now();
-    p->stage_ms[2] = ms(t2, t3);
+    p->stage_ms[2] = SlabCall::ms(t2, t3);
     float *rhs = nullptr, *x = nullptr, *res = nullptr;
     const float *sp = p->surface_pressure ? p->surface_pressure : spOwn;
     float *spLo = surface && lo ? spHalo : nullptr, *spHi = surface && hi ? spHalo + plane : nullptr;
     const float *velIn[3] = {p->velocity[0], p->velocity[1], p->velocity[2]};
     auto solverStep = [&](int rc) {
-        if (rc != MGPS_OK && status == MGPS_OK) {
+        if (rc != MGPS_OK && c.status == MGPS_OK) {
             setLastGlobalError(mgps_last_error(mg));
-            status = rc;
+            c.status = rc;
         }
     };
     solverStep(mgps_set_stream(mg, stream));
-    if (status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &rhs));
-    if (status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &x));  // zero-filled
-    if (status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &res));
-    if (status == MGPS_OK) step(mgps_fields_slab_rhs(&desc, rhs, matOwn, velIn, svel, cw, st));
-    if (status == MGPS_OK && p->use_old_pressure) step(mgps_fields_slab_pressure_to_solution(&desc, x, p->pressure, matOwn, st));
+    if (c.status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &rhs));
+    if (c.status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &x));  // zero-filled
+    if (c.status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &res));
+    if (c.status == MGPS_OK) c.step(mgps_fields_slab_rhs(&desc, rhs, matOwn, velIn, svel, cw, st));
+    if (c.status == MGPS_OK && p->use_old_pressure) c.step(mgps_fields_slab_pressure_to_solution(&desc, x, p->pressure, matOwn, st));
     if (surface) {  // b_L += w_f p_G: before the enclosed-liquid projection and the solve, which then see the system actually solved
-        if (status == MGPS_OK && sigma > 0)
-            step(mgps_fields_slab_surface_pressure(&desc, spOwn, p->liquid_phi, phiLo, phiHi, matOwn, matLo, matHi, sigma * p->dt / (p->density * p->dx * p->dx), st));
+        if (c.status == MGPS_OK && sigma > 0)
+            c.step(mgps_fields_slab_surface_pressure(&desc, spOwn, p->liquid_phi, phiLo, phiHi, matOwn, matLo, matHi, sigma * p->dt / (p->density * p->dx * p->dx), st));
         SLAB_COMM(tradePlane(sp, spHalo, spHalo + plane, sizeof(float), "surface pressure"));
-        if (status == MGPS_OK) hipStep(hipMemsetAsync(pGammaMax, 0, sizeof(float), st), "surface pressure");
-        if (status == MGPS_OK) step(mgps_fields_slab_rhs_surface(&desc, rhs, w, p->liquid_phi, phiLo, phiHi, matOwn, matLo, matHi, sp, spLo, spHi, pGammaMax, st));
+        if (c.status == MGPS_OK) hipStep(c, hipMemsetAsync(pGammaMax, 0, sizeof(float), st), "surface pressure");
+        if (c.status == MGPS_OK) c.step(mgps_fields_slab_rhs_surface(&desc, rhs, w, p->liquid_phi, phiLo, phiHi, matOwn, matLo, matHi, sp, spLo, spHi, pGammaMax, st));
     }
-    SLAB_COMM(agreeRanks(&cm, status, "right-hand side"));
+    SLAB_COMM(c.agree("right-hand side"));
     if (o.enclosed_liquid) {  // the rhs as the solve sees it (P b); both calls return one verdict on every rank
         int64_t m = 0;
         int rc = mgps_enclosed_components(mg, &m, nullptr);
@@ -1798,7 +1737,7 @@ try {
     }
     (void)hipStreamSynchronize(st);
     const auto t4 = clock::now();
-    p->stage_ms[3] = ms(t3, t4);
+    p->stage_ms[3] = SlabCall::ms(t3, t4);
     int rc = mgps_solve_pcg(mg, x, rhs, p->tolerance, p->max_iterations, p->use_mg_preconditioner, &p->stats);
     if (rc == MGPS_OK) rc = mgps_residual(mg, 0, res, x, rhs);  // Plug.cpp:625-628
     if (rc == MGPS_OK) rc = mgps_inf_norm(mg, 0, res, 1, &p->residual_inf);
@@ -1810,40 +1749,39 @@ try {
     const int solveRc = rc;
     (void)hipStreamSynchronize(st);
     const auto t5 = clock::now();
-    p->stage_ms[4] = ms(t4, t5);
+    p->stage_ms[4] = SlabCall::ms(t4, t5);
     // ---- 5. pressure (0 outside LIQUID cells, Plug.cpp:641), its plane to the neighbours, the gradient on the owned faces -- the
     //         rank's copy of a cut's z-face plane included -- and the divergence report (Plug.cpp:637-707)
-    step(mgps_fields_slab_solution_to_pressure(&desc, p->pressure, x, matOwn, 1, st));
+    c.step(mgps_fields_slab_solution_to_pressure(&desc, p->pressure, x, matOwn, 1, st));
     SLAB_COMM(tradePlane(p->pressure, prHalo, prHalo + plane, sizeof(float), "pressure"));
-    if (status == MGPS_OK)
-        step(mgps_fields_slab_pressure_gradient(&desc, p->velocity, p->liquid_phi, phiLo, phiHi, p->pressure, lo ? prHalo : nullptr, hi ? prHalo + plane : nullptr,
-                                                surface ? sp : nullptr, spLo, spHi, valid, matOwn, matLo, matHi, st));
+    if (c.status == MGPS_OK)
+        c.step(mgps_fields_slab_pressure_gradient(&desc, p->velocity, p->liquid_phi, phiLo, phiHi, p->pressure, lo ? prHalo : nullptr, hi ? prHalo + plane : nullptr,
+                                                  surface ? sp : nullptr, spLo, spHi, valid, matOwn, matLo, matHi, st));
     double div[3] = {0, 0, 0}, maxes[2] = {0, 0};
-    if (status == MGPS_OK) step(mgps_fields_slab_divergence(&desc, div, matOwn, velIn, svel, cw, st));
-    if (status == MGPS_OK && surface) {
+    if (c.status == MGPS_OK) c.step(mgps_fields_slab_divergence(&desc, div, matOwn, velIn, svel, cw, st));
+    if (c.status == MGPS_OK && surface) {
         float m = 0;
-        hipStep(hipMemcpy(&m, pGammaMax, sizeof(m), hipMemcpyDeviceToHost), "surface pressure");
+        hipStep(c, hipMemcpy(&m, pGammaMax, sizeof(m), hipMemcpyDeviceToHost), "surface pressure");
         maxes[1] = m;
     }
     maxes[0] = div[1];
     double sums[2] = {div[0], div[2]};
-    SLAB_COMM(agreeRanks(&cm, status, "write-back", sums, 2, maxes, 2));
+    SLAB_COMM(c.agree("write-back", sums, 2, maxes, 2));
 #undef SLAB_COMM
     p->divergence_sum = sums[0];
     p->divergence_max = maxes[0];
     p->surface_pressure_max = maxes[1];
     const auto t6 = clock::now();
-    p->stage_ms[5] = ms(t5, t6);
-    p->stage_ms[6] = exchangeMs;
-    p->setup_ms = ms(t0, t4);
-    p->solve_ms = ms(t4, t5);
-    p->total_ms = ms(t0, t6);
+    p->stage_ms[5] = SlabCall::ms(t5, t6);
+    p->stage_ms[6] = c.exchangeMs;
+    p->setup_ms = SlabCall::ms(t0, t4);
+    p->solve_ms = SlabCall::ms(t4, t5);
+    p->total_ms = SlabCall::ms(t0, t6);
     if (setupTimingOn())
         std::printf("projection slab rank %d: passes %.2f ms, agreement (host set-up: labels to hosts) %.2f ms, solver set-up %.2f ms, rhs %.2f ms, solve %.2f ms, write-back %.2f ms "
                     "(plane exchanges %.2f ms)\n",
-                    rank, p->stage_ms[0], p->stage_ms[1], p->stage_ms[2], p->stage_ms[3], p->stage_ms[4], p->stage_ms[5], exchangeMs);
-    if (solveRc != MGPS_OK) setLastGlobalError("mgps_project_free_surface_slab: interrupted");
-    return solveRc;
+                    rank, p->stage_ms[0], p->stage_ms[1], p->stage_ms[2], p->stage_ms[3], p->stage_ms[4], p->stage_ms[5], c.exchangeMs);
+    return solveRc != MGPS_OK ? c.leave(solveRc, "interrupted") : MGPS_OK;
 }
 MGPS_API_CATCH(nullptr)
 
@@ -2045,26 +1983,21 @@ __global__ __launch_bounds__(256) void extrapolatePackKernel(ExPack p)
     }
 }
 
-int exRefuse(const char *fn, const std::string &what)
-{
-    setLastGlobalError(std::string(fn) + ": " + what);
-    return MGPS_ERR_INVALID_ARGUMENT;
-}
 // the checks every extrapolation entry shares, on the host, before any HIP call
 int exCheckLayers(const char *fn, int layers)
 {
-    if (layers < 1 || layers > 254) return exRefuse(fn, "layers = " + std::to_string(layers) + " is outside 1 .. 254 (layer is a uint8 grid, 255 = not reached)");
+    if (layers < 1 || layers > 254) return refuse(fn, "layers = " + std::to_string(layers) + " is outside 1 .. 254 (layer is a uint8 grid, 255 = not reached)");
     return MGPS_OK;
 }
 int exCheckExtents(const char *fn, int gx, int gy, int gz)
 {
-    if (!okBox(gx, gy, gz)) return exRefuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(gx) + ", " + std::to_string(gy) + ", " + std::to_string(gz) + ")");
+    if (!okBox(gx, gy, gz)) return refuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(gx) + ", " + std::to_string(gy) + ", " + std::to_string(gz) + ")");
     return MGPS_OK;
 }
 // cut_weights: NULL, or all three
 int exCheckCutWeights(const char *fn, const float *const cw[3])
 {
-    if (cw && !(cw[0] && cw[1] && cw[2]) && (cw[0] || cw[1] || cw[2])) return exRefuse(fn, "cut_weights: all three grids, or none");
+    if (cw && !(cw[0] && cw[1] && cw[2]) && (cw[0] || cw[1] || cw[2])) return refuse(fn, "cut_weights: all three grids, or none");
     return MGPS_OK;
 }
 inline dim3 exGrid(const ExArgs &p, int naxes)
@@ -2104,12 +2037,12 @@ int mgps_fields_extrapolate(int axis, float *velocity, uint8_t *layer, const uin
                             int gy, int gz, void *stream)
 try {
     const char *fn = "mgps_fields_extrapolate";
-    if (axis < 0 || axis > 2) return exRefuse(fn, "axis = " + std::to_string(axis) + " is outside 0 .. 2");
+    if (axis < 0 || axis > 2) return refuse(fn, "axis = " + std::to_string(axis) + " is outside 0 .. 2");
     if (int rc = exCheckLayers(fn, layers); rc != MGPS_OK) return rc;
     if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
-    if (!velocity) return exRefuse(fn, "velocity is NULL");
-    if (!layer) return exRefuse(fn, "layer is NULL");
-    if (!valid) return exRefuse(fn, "valid is NULL");
+    if (!velocity) return refuse(fn, "velocity is NULL");
+    if (!layer) return refuse(fn, "layer is NULL");
+    if (!valid) return refuse(fn, "valid is NULL");
     ExArgs p{};
     p.a[0] = ExAxis{velocity, layer, valid, cut_weights, nullptr, nullptr, nullptr, nullptr, gx + (axis == 0), gy + (axis == 1), gz + (axis == 2)};
     for (p.l = 0; p.l <= layers; ++p.l)
@@ -2124,9 +2057,9 @@ try {
     const char *fn = "mgps_fields_extrapolate3";
     if (int rc = exCheckLayers(fn, layers); rc != MGPS_OK) return rc;
     if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
-    if (!velocity || !velocity[0] || !velocity[1] || !velocity[2]) return exRefuse(fn, "velocity: three grids are required");
-    if (!layer || !layer[0] || !layer[1] || !layer[2]) return exRefuse(fn, "layer: three grids are required");
-    if (!valid || !valid[0] || !valid[1] || !valid[2]) return exRefuse(fn, "valid: three grids are required");
+    if (!velocity || !velocity[0] || !velocity[1] || !velocity[2]) return refuse(fn, "velocity: three grids are required");
+    if (!layer || !layer[0] || !layer[1] || !layer[2]) return refuse(fn, "layer: three grids are required");
+    if (!valid || !valid[0] || !valid[1] || !valid[2]) return refuse(fn, "valid: three grids are required");
     if (int rc = exCheckCutWeights(fn, cut_weights); rc != MGPS_OK) return rc;
     const bool closed = cut_weights && cut_weights[0];
     ExArgs p{};
@@ -2149,15 +2082,15 @@ try {
     const char *fn = "mgps_fields_slab_extrapolate_layer";
     Slab s;
     if (!readSlab(d, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
-    if (l < 0 || l > 254) return exRefuse(fn, "l = " + std::to_string(l) + " is outside 0 .. 254 (0 initialises layer from valid)");
-    if (!velocity || !velocity[0] || !velocity[1] || !velocity[2]) return exRefuse(fn, "velocity: three grids are required");
-    if (!layer || !layer[0] || !layer[1] || !layer[2]) return exRefuse(fn, "layer: three grids are required");
-    if (l == 0 && (!valid || !valid[0] || !valid[1] || !valid[2])) return exRefuse(fn, "valid: three grids are required with l = 0");
+    if (l < 0 || l > 254) return refuse(fn, "l = " + std::to_string(l) + " is outside 0 .. 254 (0 initialises layer from valid)");
+    if (!velocity || !velocity[0] || !velocity[1] || !velocity[2]) return refuse(fn, "velocity: three grids are required");
+    if (!layer || !layer[0] || !layer[1] || !layer[2]) return refuse(fn, "layer: three grids are required");
+    if (l == 0 && (!valid || !valid[0] || !valid[1] || !valid[2])) return refuse(fn, "valid: three grids are required with l = 0");
     if (int rc = exCheckCutWeights(fn, cut_weights); rc != MGPS_OK) return rc;
     const bool lo = l > 0 && s.c0 > 0, hi = l > 0 && s.c1 < s.gz;
     for (int a = 0; a < 3; ++a) {
-        if (lo && !(velocity_lo && layer_lo && velocity_lo[a] && layer_lo[a])) return exRefuse(fn, "velocity_lo / layer_lo: the planes below the window are required (c0 > 0)");
-        if (hi && !(velocity_hi && layer_hi && velocity_hi[a] && layer_hi[a])) return exRefuse(fn, "velocity_hi / layer_hi: the planes above the window are required (c1 < gz)");
+        if (lo && !(velocity_lo && layer_lo && velocity_lo[a] && layer_lo[a])) return refuse(fn, "velocity_lo / layer_lo: the planes below the window are required (c0 > 0)");
+        if (hi && !(velocity_hi && layer_hi && velocity_hi[a] && layer_hi[a])) return refuse(fn, "velocity_hi / layer_hi: the planes above the window are required (c1 < gz)");
     }
     const bool closed = cut_weights && cut_weights[0];
     const int nzl = s.c1 - s.c0;
@@ -2174,18 +2107,14 @@ MGPS_API_CATCH(nullptr)
 
 int mgps_extrapolate_velocity_slab(mgps_extrapolation_slab *e, const mgps_comm *comm, const int *splits, void *stream)
 try {
-    using clock = std::chrono::steady_clock;
-    const auto t0 = clock::now();
-    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    SlabCall c;
     const char *fn = "mgps_extrapolate_velocity_slab";
     // ---- what every rank shares: a refusal here is every rank's, before any collective and any HIP call
-    if (!e || e->struct_size != int(sizeof(mgps_extrapolation_slab))) return exRefuse(fn, "NULL or struct_size mismatch (mgps_extrapolation_slab)");
-    if (!comm || !splits || comm->struct_size < int(offsetof(mgps_comm, gather)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange ||
-        !comm->allreduce || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
-        return exRefuse(fn, "comm / splits: a mgps_comm with exchange and allreduce and the cuts are required");
+    if (!e || e->struct_size != int(sizeof(mgps_extrapolation_slab))) return refuse(fn, "NULL or struct_size mismatch (mgps_extrapolation_slab)");
+    if (int rc = c.open(fn, comm, splits, offsetof(mgps_comm, gather)); rc != MGPS_OK) return rc;
     if (int rc = exCheckLayers(fn, e->layers); rc != MGPS_OK) return rc;
     if (int rc = exCheckExtents(fn, e->gx, e->gy, e->gz); rc != MGPS_OK) return rc;
-    const int P = comm->size, rank = comm->rank, L = e->layers;
+    const int P = c.P, rank = c.rank, L = e->layers;
     mgps_fields_slab desc;
     if (int rc = mgps_fields_slab_describe(&desc, e->gx, e->gy, e->gz, e->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
     Slab s;
@@ -2197,42 +2126,18 @@ try {
     const bool lo = s.c0 > 0, hi = s.c1 < s.gz;
     const int count[3] = {(gx + 1) * gy, gx * (gy + 1), gx * gy};
     const size_t entries = size_t(count[0]) + size_t(count[1]) + size_t(count[2]), message = entries * (sizeof(float) + 1);
-    // the ranks' verdicts through one sum all-reduce (every rank fills its own slot); a world of one asks nobody
-    auto agree = [&](int status, const char *where, double *sums, int nsums) -> int {
-        if (P == 1) return status;
-        std::vector<double> v(size_t(nsums) + size_t(P), 0.0);
-        for (int q = 0; q < nsums; ++q) v[size_t(q)] = sums[q];
-        v[size_t(nsums) + size_t(rank)] = double(status);
-        if (comm->allreduce(comm->user, v.data(), int(v.size()), 0) != 0) {
-            setLastGlobalError(std::string(fn) + ": all-reduce failed (" + where + ")");
-            return MGPS_ERR_COMM;
-        }
-        for (int q = 0; q < nsums; ++q) sums[q] = v[size_t(q)];
-        if (status != MGPS_OK) return status;
-        for (int r = 0; r < P; ++r)
-            if (int(v[size_t(nsums) + size_t(r)]) != MGPS_OK) {
-                setLastGlobalError(std::string(fn) + ": rank " + std::to_string(r) + " failed (" + where + ", status " +
-                                   std::to_string(int(v[size_t(nsums) + size_t(r)])) + ")");
-                return int(v[size_t(nsums) + size_t(r)]);
-            }
-        return MGPS_OK;
-    };
     // ---- this rank's own arguments and buffers: a failure is carried by the all-reduce in front of the first exchange
     std::unique_ptr<DevPool> pool;  // (made after the argument checks: a refusal makes no HIP call)
     uint8_t *layer[3] = {nullptr, nullptr, nullptr};
     float *sendLo = nullptr, *sendHi = nullptr, *recvLo = nullptr, *recvHi = nullptr;
     unsigned long long *filled = nullptr;
-    int status = [&]() -> int {
+    c.step([&]() -> int {
         for (int a = 0; a < 3; ++a) {
-            if (!e->velocity[a]) return exRefuse(fn, "velocity: three grids are required");
-            if (!e->valid_faces[a]) return exRefuse(fn, "valid_faces: three grids are required");
+            if (!e->velocity[a]) return refuse(fn, "velocity: three grids are required");
+            if (!e->valid_faces[a]) return refuse(fn, "valid_faces: three grids are required");
         }
         if (int rc = exCheckCutWeights(fn, e->cut_weights); rc != MGPS_OK) return rc;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-            setLastGlobalError("no HIP device is visible (this library has no CPU path)");
-            return MGPS_ERR_NO_DEVICE;
-        }
+        if (int rc = selectDevice(-1); rc != MGPS_OK) return rc;
         try {
             pool.reset(new DevPool);
             for (int a = 0; a < 3; ++a) layer[a] = e->layer[a] ? e->layer[a] : pool->get<uint8_t>(faceCount(gx, gy, nzl, a));
@@ -2241,21 +2146,14 @@ try {
             if (hi) sendHi = pool->get<float>((message + 3) / 4), recvHi = pool->get<float>((message + 3) / 4);
             filled = pool->get<unsigned long long>(3);
         } catch (const std::bad_alloc &) {
-            setLastGlobalError(std::string(fn) + ": device allocation failed");
-            return MGPS_ERR_ALLOC;
+            return c.fail(MGPS_ERR_ALLOC, "device allocation failed");
         }
-        if (hipMemsetAsync(filled, 0, 3 * sizeof(unsigned long long), st) != hipSuccess) {
-            setLastGlobalError(std::string(fn) + ": hipMemsetAsync failed");
-            return MGPS_ERR_HIP;
-        }
-        return MGPS_OK;
-    }();
-    if (int rc = agree(status, "arguments", nullptr, 0); rc != MGPS_OK) return rc;
-    // (from here on the buffers exist on every rank: a failing rank still takes part in every exchange and the last all-reduce
+        hipStep(c, hipMemsetAsync(filled, 0, 3 * sizeof(unsigned long long), st), "clearing the counts");
+        return c.status;
+    }());
+    if (int rc = c.agree("arguments"); rc != MGPS_OK) return rc;
+    // (from here on the buffers exist on every rank: a failing rank still takes part in every exchange and the last agreement
     //  carries its status)
-    auto step = [&](int rc) {
-        if (status == MGPS_OK) status = rc;
-    };
     const float *cw[3] = {e->cut_weights[0], e->cut_weights[1], e->cut_weights[2]};
     const float *velLo[3], *velHi[3];
     const uint8_t *layLo[3], *layHi[3];
@@ -2278,39 +2176,32 @@ try {
         pack.outLo = sendLo;
         pack.outHi = sendHi;
     }
-    double exchangeMs = 0;
-    step(mgps_fields_slab_extrapolate_layer(&desc, 0, e->velocity, layer, e->valid_faces, nullptr, nullptr, nullptr, nullptr, cw[0] ? cw : nullptr, nullptr, st));
+    c.step(mgps_fields_slab_extrapolate_layer(&desc, 0, e->velocity, layer, e->valid_faces, nullptr, nullptr, nullptr, nullptr, cw[0] ? cw : nullptr, nullptr, st));
     for (int l = 1; l <= L; ++l) {
         if (P > 1) {
             extrapolatePackKernel<<<blocks(entries), 256, 0, st>>>(pack);
-            step(done(fn));
-            const auto a = clock::now();
-            const int rc = comm->exchange(comm->user, sendLo, lo ? message : 0, recvLo, lo ? message : 0, sendHi, hi ? message : 0, recvHi, hi ? message : 0, st);
-            exchangeMs += ms(a, clock::now());
-            if (rc != 0) {
-                setLastGlobalError(std::string(fn) + ": exchange failed (layer " + std::to_string(l) + ")");
-                return MGPS_ERR_COMM;
-            }
+            c.step(done(fn));
+            if (int rc = c.trade(sendLo, lo ? message : 0, recvLo, lo ? message : 0, sendHi, hi ? message : 0, recvHi, hi ? message : 0, st, "layer " + std::to_string(l));
+                rc != MGPS_OK)
+                return rc;
         }
-        if (status == MGPS_OK)
-            step(mgps_fields_slab_extrapolate_layer(&desc, l, e->velocity, layer, nullptr, velLo, velHi, layLo, layHi, cw[0] ? cw : nullptr, nullptr, st));
+        if (c.status == MGPS_OK)
+            c.step(mgps_fields_slab_extrapolate_layer(&desc, l, e->velocity, layer, nullptr, velLo, velHi, layLo, layHi, cw[0] ? cw : nullptr, nullptr, st));
     }
-    if (status == MGPS_OK) {  // the faces filled, counted once behind the layers (the cut's z-face plane by the rank above it)
+    if (c.status == MGPS_OK) {  // the faces filled, counted once behind the layers (the cut's z-face plane by the rank above it)
         ExArgs grids{};
         for (int a = 0; a < 3; ++a) grids.a[a] = ExAxis{nullptr, layer[a], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gx + (a == 0), gy + (a == 1), nzl + (a == 2)};
         const int countNz[3] = {nzl, nzl, hi ? nzl : nzl + 1};
-        step(exLaunchCount(grids, countNz, 1, 254, filled, st, fn));
+        c.step(exLaunchCount(grids, countNz, 1, 254, filled, st, fn));
     }
     unsigned long long mine[3] = {0, 0, 0};
-    if (status == MGPS_OK && (hipMemcpyAsync(mine, filled, sizeof(mine), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
-        setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(hipGetLastError()));
-        status = MGPS_ERR_HIP;
-    }
+    if (c.status == MGPS_OK) hipStep(c, hipMemcpyAsync(mine, filled, sizeof(mine), hipMemcpyDeviceToHost, st), "the counts to the host");
+    if (c.status == MGPS_OK) hipStep(c, hipStreamSynchronize(st), "the counts to the host");
     double sums[3] = {double(mine[0]), double(mine[1]), double(mine[2])};
-    const int rc = agree(status, "layers", sums, 3);
+    const int rc = c.agree("layers", sums, 3);
     for (int a = 0; a < 3; ++a) e->filled[a] = (unsigned long long)(sums[a]);
-    e->exchange_ms = exchangeMs;
-    e->total_ms = ms(t0, clock::now());
+    e->exchange_ms = c.exchangeMs;
+    e->total_ms = SlabCall::ms(c.t0, SlabCall::Clock::now());
     return rc;
 }
 MGPS_API_CATCH(nullptr)
@@ -2513,7 +2404,7 @@ __global__ __launch_bounds__(kForceSlices * 16) void solidForcesSumKernel(double
 
 int forceCheckBodies(const char *fn, int bodies)
 {
-    if (bodies < 1 || bodies > 255) return exRefuse(fn, "bodies = " + std::to_string(bodies) + " is outside 1 .. 255");
+    if (bodies < 1 || bodies > 255) return refuse(fn, "bodies = " + std::to_string(bodies) + " is outside 1 .. 255");
     return MGPS_OK;
 }
 
@@ -2577,12 +2468,12 @@ try {
     const char *fn = "mgps_fields_solid_forces";
     if (int rc = forceCheckBodies(fn, bodies); rc != MGPS_OK) return rc;
     if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
-    if (!out_host) return exRefuse(fn, "out_host is NULL");
-    if (!pressure) return exRefuse(fn, "pressure is NULL");
-    if (!material) return exRefuse(fn, "material is NULL");
-    if (!cwx || !cwy || !cwz) return exRefuse(fn, "cut weights: three grids are required");
-    if (!bx || !by || !bz) return exRefuse(fn, "body: three grids are required");
-    if (!centres_host) return exRefuse(fn, "centres_host is NULL");
+    if (!out_host) return refuse(fn, "out_host is NULL");
+    if (!pressure) return refuse(fn, "pressure is NULL");
+    if (!material) return refuse(fn, "material is NULL");
+    if (!cwx || !cwy || !cwz) return refuse(fn, "cut weights: three grids are required");
+    if (!bx || !by || !bz) return refuse(fn, "body: three grids are required");
+    if (!centres_host) return refuse(fn, "centres_host is NULL");
     const float *cw[3] = {cwx, cwy, cwz};
     const int32_t *body[3] = {bx, by, bz};
     return runSolidForces(fn, out_host, Box{gx, gy, gz}, nullptr, pressure, nullptr, material, nullptr, cw, body, centres_host, bodies, scale,
@@ -2598,14 +2489,14 @@ try {
     Slab s;
     if (!readSlab(d, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
     if (int rc = forceCheckBodies(fn, bodies); rc != MGPS_OK) return rc;
-    if (!out_host) return exRefuse(fn, "out_host is NULL");
-    if (!pressure) return exRefuse(fn, "pressure is NULL");
-    if (!material) return exRefuse(fn, "material is NULL");
-    if (!cut_weights || !cut_weights[0] || !cut_weights[1] || !cut_weights[2]) return exRefuse(fn, "cut_weights: three grids are required");
-    if (!body || !body[0] || !body[1] || !body[2]) return exRefuse(fn, "body: three grids are required");
-    if (!centres_host) return exRefuse(fn, "centres_host is NULL");
-    if (s.c0 > 0 && !pressure_lo) return exRefuse(fn, "pressure_lo: the plane below the window is required (c0 > 0)");
-    if (s.c0 > 0 && !material_lo) return exRefuse(fn, "material_lo: the plane below the window is required (c0 > 0)");
+    if (!out_host) return refuse(fn, "out_host is NULL");
+    if (!pressure) return refuse(fn, "pressure is NULL");
+    if (!material) return refuse(fn, "material is NULL");
+    if (!cut_weights || !cut_weights[0] || !cut_weights[1] || !cut_weights[2]) return refuse(fn, "cut_weights: three grids are required");
+    if (!body || !body[0] || !body[1] || !body[2]) return refuse(fn, "body: three grids are required");
+    if (!centres_host) return refuse(fn, "centres_host is NULL");
+    if (s.c0 > 0 && !pressure_lo) return refuse(fn, "pressure_lo: the plane below the window is required (c0 > 0)");
+    if (s.c0 > 0 && !material_lo) return refuse(fn, "material_lo: the plane below the window is required (c0 > 0)");
     return runSolidForces(fn, out_host, s.whole(), &s, pressure, s.c0 > 0 ? pressure_lo : nullptr, material, s.c0 > 0 ? material_lo : nullptr,
                           cut_weights, body, centres_host, bodies, scale, static_cast<hipStream_t>(stream));
 }
@@ -2613,18 +2504,14 @@ MGPS_API_CATCH(nullptr)
 
 int mgps_solid_forces_slab(struct mgps_solid_forces_slab *f, const mgps_comm *comm, const int *splits, void *stream)
 try {
-    using clock = std::chrono::steady_clock;
-    const auto t0 = clock::now();
-    auto ms = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    SlabCall c;
     const char *fn = "mgps_solid_forces_slab";
     // ---- what every rank shares: a refusal here is every rank's, before any collective and any HIP call
-    if (!f || f->struct_size != int(sizeof(struct mgps_solid_forces_slab))) return exRefuse(fn, "NULL or struct_size mismatch (mgps_solid_forces_slab)");
-    if (!comm || !splits || comm->struct_size < int(offsetof(mgps_comm, gather)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange ||
-        !comm->allreduce || comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
-        return exRefuse(fn, "comm / splits: a mgps_comm with exchange and allreduce and the cuts are required");
+    if (!f || f->struct_size != int(sizeof(struct mgps_solid_forces_slab))) return refuse(fn, "NULL or struct_size mismatch (mgps_solid_forces_slab)");
+    if (int rc = c.open(fn, comm, splits, offsetof(mgps_comm, gather)); rc != MGPS_OK) return rc;
     if (int rc = forceCheckBodies(fn, f->bodies); rc != MGPS_OK) return rc;
     if (int rc = exCheckExtents(fn, f->gx, f->gy, f->gz); rc != MGPS_OK) return rc;
-    const int P = comm->size, rank = comm->rank;
+    const int P = c.P, rank = c.rank;
     mgps_fields_slab desc;
     if (int rc = mgps_fields_slab_describe(&desc, f->gx, f->gy, f->gz, f->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
     Slab s;
@@ -2634,23 +2521,19 @@ try {
     const int nzl = s.c1 - s.c0;
     const bool lo = s.c0 > 0, hi = s.c1 < s.gz;
     const size_t plane = size_t(s.gx) * s.gy, cells = plane * size_t(nzl), entries = size_t(f->bodies + 1) * kForceCols;
-    // ---- this rank's own arguments: a failure is carried by the all-reduce at the end, the rank takes part in both exchanges
-    int status = [&]() -> int {
-        if (!f->pressure) return exRefuse(fn, "pressure is NULL");
-        if (!f->liquid_phi || !f->solid_phi) return exRefuse(fn, "liquid_phi / solid_phi: both are required");
-        if (!f->cut_weights[0] || !f->cut_weights[1] || !f->cut_weights[2]) return exRefuse(fn, "cut_weights: three grids are required");
-        if (!f->body[0] || !f->body[1] || !f->body[2]) return exRefuse(fn, "body: three grids are required");
-        if (!f->centres) return exRefuse(fn, "centres is NULL");
-        if (!f->out) return exRefuse(fn, "out is NULL");
+    // ---- this rank's own arguments: a failure is carried by the agreement at the end, the rank takes part in both exchanges
+    c.step([&]() -> int {
+        if (!f->pressure) return refuse(fn, "pressure is NULL");
+        if (!f->liquid_phi || !f->solid_phi) return refuse(fn, "liquid_phi / solid_phi: both are required");
+        if (!f->cut_weights[0] || !f->cut_weights[1] || !f->cut_weights[2]) return refuse(fn, "cut_weights: three grids are required");
+        if (!f->body[0] || !f->body[1] || !f->body[2]) return refuse(fn, "body: three grids are required");
+        if (!f->centres) return refuse(fn, "centres is NULL");
+        if (!f->out) return refuse(fn, "out is NULL");
         return MGPS_OK;
-    }();
-    if (P == 1 && status != MGPS_OK) return status;
+    }());
+    if (P == 1 && c.status != MGPS_OK) return c.status;
     // the buffers the exchanges need: without them the rank cannot take part, and returns at once and alone
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        setLastGlobalError("no HIP device is visible (this library has no CPU path)");
-        return MGPS_ERR_NO_DEVICE;
-    }
+    if (int rc = selectDevice(-1); rc != MGPS_OK) return rc;
     DevPool pool;
     int32_t *material = nullptr;
     float *phiHalo = nullptr, *up = nullptr, *below = nullptr;  // messages: [pressure plane | material plane]
@@ -2660,72 +2543,41 @@ try {
         if (hi) up = pool.get<float>(2 * plane);
         if (lo) below = pool.get<float>(2 * plane);
     } catch (const std::bad_alloc &) {
-        setLastGlobalError(std::string(fn) + ": device allocation failed");
-        return MGPS_ERR_ALLOC;
+        return c.leave(MGPS_ERR_ALLOC, "device allocation failed");
     }
-    auto step = [&](int rc) {
-        if (status == MGPS_OK) status = rc;
-    };
-    auto hipStep = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && status == MGPS_OK) {
-            setLastGlobalError(std::string(fn) + ": " + what + ": " + hipGetErrorString(e));
-            status = MGPS_ERR_HIP;
-        }
-    };
-    double exchangeMs = 0;
     const size_t planeBytes = plane * sizeof(float);
     float *phiLo = lo ? phiHalo : nullptr, *phiHi = hi ? phiHalo + plane : nullptr;
-    if (P > 1) {  // 1. the liquid_phi plane, both ways (a rank without the array sends what its halo buffer holds)
-        const float *first = status == MGPS_OK ? f->liquid_phi : phiHalo, *last = status == MGPS_OK ? f->liquid_phi + size_t(nzl - 1) * plane : phiHalo;
-        const auto a = clock::now();
-        const int rc = comm->exchange(comm->user, lo ? first : nullptr, lo ? planeBytes : 0, phiLo, lo ? planeBytes : 0, hi ? last : nullptr,
-                                      hi ? planeBytes : 0, phiHi, hi ? planeBytes : 0, st);
-        exchangeMs += ms(a, clock::now());
-        if (rc != 0) {
-            setLastGlobalError(std::string(fn) + ": exchange failed (liquid_phi)");
-            return MGPS_ERR_COMM;
-        }
+    {  // 1. the liquid_phi plane, both ways (a rank without the array sends what its halo buffer holds)
+        const float *first = c.status == MGPS_OK ? f->liquid_phi : phiHalo, *last = c.status == MGPS_OK ? f->liquid_phi + size_t(nzl - 1) * plane : phiHalo;
+        if (int rc = c.trade(lo ? first : nullptr, lo ? planeBytes : 0, phiLo, lo ? planeBytes : 0, hi ? last : nullptr, hi ? planeBytes : 0, phiHi,
+                             hi ? planeBytes : 0, st, "liquid_phi");
+            rc != MGPS_OK)
+            return rc;
     }
     // 2. the projection's labels, made again
-    if (status == MGPS_OK)
-        step(mgps_fields_slab_material_labels(&desc, material, f->liquid_phi, phiLo, phiHi, f->solid_phi, f->cut_weights[0], f->cut_weights[1],
-                                              f->cut_weights[2], st));
+    if (c.status == MGPS_OK)
+        c.step(mgps_fields_slab_material_labels(&desc, material, f->liquid_phi, phiLo, phiHi, f->solid_phi, f->cut_weights[0], f->cut_weights[1],
+                                                f->cut_weights[2], st));
     if (P > 1) {  // 3. the last pressure plane and the last material plane go up in one message; the lower halo arrives from below
-        if (hi && status == MGPS_OK) {
-            hipStep(hipMemcpyAsync(up, f->pressure + size_t(nzl - 1) * plane, planeBytes, hipMemcpyDeviceToDevice, st), "packing the pressure plane");
-            hipStep(hipMemcpyAsync(up + plane, material + size_t(nzl - 1) * plane, planeBytes, hipMemcpyDeviceToDevice, st), "packing the material plane");
+        if (hi && c.status == MGPS_OK) {
+            hipStep(c, hipMemcpyAsync(up, f->pressure + size_t(nzl - 1) * plane, planeBytes, hipMemcpyDeviceToDevice, st), "packing the pressure plane");
+            hipStep(c, hipMemcpyAsync(up + plane, material + size_t(nzl - 1) * plane, planeBytes, hipMemcpyDeviceToDevice, st), "packing the material plane");
         }
-        const auto a = clock::now();
-        const int rc = comm->exchange(comm->user, nullptr, 0, below, lo ? 2 * planeBytes : 0, up, hi ? 2 * planeBytes : 0, nullptr, 0, st);
-        exchangeMs += ms(a, clock::now());
-        if (rc != 0) {
-            setLastGlobalError(std::string(fn) + ": exchange failed (pressure and material planes)");
-            return MGPS_ERR_COMM;
-        }
+        if (int rc = c.trade(nullptr, 0, below, lo ? 2 * planeBytes : 0, up, hi ? 2 * planeBytes : 0, nullptr, 0, st, "pressure and material planes"); rc != MGPS_OK)
+            return rc;
     }
     // 4. the window pass
-    std::vector<double> rows(entries + size_t(P), 0.0);
-    if (status == MGPS_OK)
-        step(runSolidForces(fn, rows.data(), s.whole(), &s, f->pressure, lo ? below : nullptr, material,
-                            lo ? reinterpret_cast<const int32_t *>(below + plane) : nullptr, f->cut_weights, f->body, f->centres, f->bodies, f->scale, st));
-    // 5. the rows of all ranks, and their statuses (every rank fills its own slot)
-    if (P > 1) {
-        if (status != MGPS_OK) std::fill(rows.begin(), rows.begin() + ptrdiff_t(entries), 0.0);
-        rows[entries + size_t(rank)] = double(status);
-        if (comm->allreduce(comm->user, rows.data(), int(rows.size()), 0) != 0) {
-            setLastGlobalError(std::string(fn) + ": all-reduce failed (rows)");
-            return MGPS_ERR_COMM;
-        }
-        for (int r = 0; r < P && status == MGPS_OK; ++r)
-            if (int(rows[entries + size_t(r)]) != MGPS_OK) {
-                status = int(rows[entries + size_t(r)]);
-                setLastGlobalError(std::string(fn) + ": rank " + std::to_string(r) + " failed (status " + std::to_string(status) + ")");
-            }
-    }
-    if (status == MGPS_OK) std::copy(rows.begin(), rows.begin() + ptrdiff_t(entries), f->out);
-    f->exchange_ms = exchangeMs;
-    f->total_ms = ms(t0, clock::now());
-    return status;
+    std::vector<double> rows(entries, 0.0);
+    if (c.status == MGPS_OK)
+        c.step(runSolidForces(fn, rows.data(), s.whole(), &s, f->pressure, lo ? below : nullptr, material,
+                              lo ? reinterpret_cast<const int32_t *>(below + plane) : nullptr, f->cut_weights, f->body, f->centres, f->bodies, f->scale, st));
+    // 5. the rows of all ranks travel as sums with the statuses: the one all-reduce of the call
+    if (c.status != MGPS_OK) std::fill(rows.begin(), rows.end(), 0.0);
+    const int rc = c.agree("rows", rows.data(), int(entries));
+    if (rc == MGPS_OK) std::copy(rows.begin(), rows.end(), f->out);
+    f->exchange_ms = c.exchangeMs;
+    f->total_ms = SlabCall::ms(c.t0, SlabCall::Clock::now());
+    return rc;
 }
 MGPS_API_CATCH(nullptr)
 

@@ -219,7 +219,8 @@ int mgps_fields_slab_divergence(const mgps_fields_slab *d, double out_host[3], c
  * set to the whole buffer: ex * ey * ez bytes per rank, 1 GiB at 1024^3 -- for mgps_create_slab_device_weights); rhs, warm start, surface term (after an exchange of the sp plane), enclosed-liquid projection,
  * mgps_solve_pcg, residual norms; pressure write-back, pressure plane exchange, gradient on the owned faces (both copies of a
  * cut's z-face plane get the same bits), divergence report and surface_pressure_max from one all-reduce.  Every rank-local failure
- * is folded into the next all-reduce: all ranks return the same status.  The exception is the transport itself: a rank whose
+ * is folded into the next all-reduce: all ranks return the same status, the failing rank with its own message, the others with
+ * "rank R failed (<where>, status S)".  With comm->size = 1 no transport entry is called.  The exception is the transport itself: a rank whose
  * exchange, all-reduce, gatherv or scatterv call fails returns MGPS_ERR_COMM at once and alone (nothing can carry its status; the
  * other ranks are left in a collective of a broken transport, as on the slab solvers).  A transport without gatherv / scatterv is refused when
  * size > 1, before any device work (the collapse of uneven cuts, the enclosed-liquid merge and the host set-up's labels use them).
@@ -357,7 +358,8 @@ int mgps_fields_slab_solid_forces(const mgps_fields_slab *d, double *out_host, c
  * since only the lower halo is read -- ; the window pass; one all-reduce (sum) of the rows with the ranks' statuses folded in.  With comm->size =
  * 1 it is the device-resident form: no exchange and no all-reduce; gatherv / scatterv are never used.  What every rank shares
  * (struct_size, extents, bodies, the cuts, the transport) is refused at once; a rank-local failure (a missing array, a failing
- * kernel) is carried by the all-reduce, the rank still takes part in both exchanges: all ranks return the same status.  A rank
+ * kernel) is carried by the all-reduce, the rank still takes part in both exchanges: all ranks return the same status, the failing
+ * rank with its own message, the others with "rank R failed (rows, status S)".  A rank
  * whose transport call fails returns MGPS_ERR_COMM at once and alone, as in mgps_project_free_surface_slab; so does, with
  * MGPS_ERR_ALLOC or MGPS_ERR_NO_DEVICE, a rank that cannot get the buffers an exchange needs.
  * The struct and the call share one name, as stat does: a struct tag, not a typedef (write `struct mgps_solid_forces_slab`). */

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import geometricmultigridpressuresolver_amd as G  # noqa: E402
 from geometricmultigridpressuresolver_amd import domains as D  # noqa: E402
 from geometricmultigridpressuresolver_amd.distributed import SlabSolver, TorchDistComm, slab_partition  # noqa: E402
+from slab_slices import all_ranks, worker_main  # noqa: E402
 
 N, LEV, S = 64, 4, 8  # the domains below: 64^3, 4 levels, an EXTERIOR shell of 8 cells; z is the cut axis
 
@@ -50,12 +51,6 @@ def make_slab(lab, w, levels, gs, splits=None, **kw):
 
 def whole_solver(lab, w, levels, gs, **kw):
     return G.GeometricMultigridPoissonSolver(lab, w, levels, gs, device=0, options=options(**kw))
-
-
-def all_ranks(value):
-    seen = [None] * dist.get_world_size()
-    dist.all_gather_object(seen, value)
-    return seen
 
 
 def gather_ranks(slab):
@@ -345,18 +340,5 @@ def refuse_mode():
         raise AssertionError("a transport without gatherv was accepted")
 
 
-def main():
-    mode = sys.argv[1]
-    dist.init_process_group("gloo")
-    torch.cuda.set_device(0)
-    try:
-        {"ranks": ranks_mode, "solve": solve_mode, "cycle": cycle_mode, "m0": m0_mode, "refuse": refuse_mode}[mode]()
-        torch.cuda.synchronize()
-        dist.barrier()
-        print(f"WORKER_OK {dist.get_rank()}", flush=True)
-    finally:
-        dist.destroy_process_group()
-
-
 if __name__ == "__main__":
-    main()
+    worker_main({"ranks": ranks_mode, "solve": solve_mode, "cycle": cycle_mode, "m0": m0_mode, "refuse": refuse_mode})

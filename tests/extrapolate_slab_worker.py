@@ -3,7 +3,8 @@ extrapolation on Z-slabs (include/mgps_fields.h) against t
 
 modes: "slabs" (mgps_extrapolate_velocity_slab and the slab pass by hand against mgps_fields_extrapolate3, bit for bit), "one"
 (RcclComm with a world of one, behind mgps_project_free_surface_slab, against the numpy restatement), "fail" (a transport whose
-exchange fails on one rank).  Prints "WORKER_OK <rank>" on success.
+exchange fails on one rank), "missing" (one rank without one of its cut-weight grids: the refusal every rank gets, and a complete
+call on the same transport).  Prints "WORKER_OK <rank>" on success.
 """
 import os
 import sys
@@ -21,25 +22,16 @@ import geometricmultigridpressuresolver_amd as G  # noqa: E402
 from geometricmultigridpressuresolver_amd import domains as D  # noqa: E402
 from geometricmultigridpressuresolver_amd import fields as F  # noqa: E402
 from geometricmultigridpressuresolver_amd.distributed import RcclComm, TorchDistComm  # noqa: E402
+from slab_slices import BrokenComm, all_ranks, dev, worker_main  # noqa: E402
 
 SHAPE = (96, 64, 64)  # (gz, gy, gx): offset 16, 128 expanded planes with either expansion
 CUTS = {1: [0, 128], 2: [0, 64, 128], 4: [0, 32, 64, 96, 128]}  # base cuts at 48 / at 16, 48, 80
 LAYERS = 6
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def bits(t):
     a = t.cpu().numpy() if isinstance(t, torch.Tensor) else t
     return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def all_ranks(value):
-    seen = [None] * dist.get_world_size()
-    dist.all_gather_object(seen, value)
-    return seen
 
 
 def window(grids, d):
@@ -156,25 +148,6 @@ def one_mode():
         comm.close()
 
 
-class BrokenComm(TorchDistComm):
-    """a transport that breaks: the `exchange_fails_at`-th exchange of this rank delivers and then reports a failure; from the
-    `allreduce_fails_at`-th on, an all-reduce reports one at once (its peer has left).  0 = never."""
-
-    def __init__(self, exchange_fails_at=0, allreduce_fails_at=0):
-        super().__init__()
-        self.exchange_fails_at, self.allreduce_fails_at, self.allreduces = exchange_fails_at, allreduce_fails_at, 0
-
-    def _exchange(self, *args):
-        rc = super()._exchange(*args)
-        return 1 if self.exchanges == self.exchange_fails_at else rc
-
-    def _allreduce(self, *args):
-        self.allreduces += 1
-        if self.allreduce_fails_at and self.allreduces >= self.allreduce_fails_at:
-            return 1
-        return super()._allreduce(*args)
-
-
 def fail_mode():
     """rank 1's exchange in front of the last layer fails: MGPS_ERR_COMM there, at once.  Rank 0 is left with a transport whose peer
     is gone, as on the slab solvers: its next transport call -- the all-reduce at the end -- fails too"""
@@ -197,18 +170,37 @@ def fail_mode():
     print(f"rank {rank}: MGPS_ERR_COMM after {comm.exchanges} exchanges and {comm.allreduces} all-reduces", flush=True)
 
 
-def main():
-    mode = sys.argv[1]
-    dist.init_process_group("gloo")
-    torch.cuda.set_device(0)
+def missing_mode():
+    """rank 1 comes with two of its three cut-weight grids: its status travels in the agreement on the arguments, before any exchange,
+    and both ranks return MGPS_ERR_INVALID_ARGUMENT -- rank 1 with its own message, rank 0 naming rank 1 and the place.  The same
+    transport then serves a complete call, bit-equal to mgps_fields_extrapolate3: nobody was left behind in a collective"""
+    comm = TorchDistComm()
+    rank = comm.rank
+    assert comm.size == 2
+    splits = CUTS[2]
+    d = F.slab_window(SHAPE, True, splits, rank)
+    sc, cw, vel, valid = device_scene()
+    w_vel, w_valid = [t.clone() for t in window(vel, d)], [t.contiguous() for t in window(valid, d)]
+    w_cw = [t.contiguous() for t in window(cw, d)]
     try:
-        {"slabs": slabs_mode, "one": one_mode, "fail": fail_mode}[mode]()
-        torch.cuda.synchronize()
-        dist.barrier()
-        print(f"WORKER_OK {dist.get_rank()}", flush=True)
-    finally:
-        dist.destroy_process_group()
+        F.extrapolate_velocity_slab(comm, splits, SHAPE, w_vel, w_valid, LAYERS, cut_weights=[w_cw[0], None if rank == 1 else w_cw[1], w_cw[2]])
+    except G.MgpsError as e:
+        assert e.status == 1, (rank, e.status, str(e))
+        assert ("cut_weights: all three grids, or none" if rank == 1 else "rank 1 failed (arguments, status 1)") in str(e), (rank, str(e))
+    else:
+        raise AssertionError(f"rank {rank}: a missing cut-weight grid on rank 1 went unnoticed")
+    assert comm.exchanges == 0, (rank, comm.exchanges)
+    for a in range(3):
+        assert np.array_equal(bits(w_vel[a]), bits(window(vel, d)[a])), a  # (nothing was touched)
+    out = F.extrapolate_velocity_slab(comm, splits, SHAPE, w_vel, w_valid, LAYERS, cut_weights=w_cw)
+    torch.cuda.synchronize()
+    ref_v, ref_layer, ref_filled = whole_grid(vel, valid, LAYERS, cw)
+    for a in range(3):
+        assert np.array_equal(bits(w_vel[a]), bits(window(ref_v, d)[a])), ("velocity", a)
+        assert np.array_equal(bits(out["layer"][a]), bits(window(ref_layer, d)[a])), ("layer", a)
+    assert out["filled"] == ref_filled and comm.exchanges == LAYERS, (out["filled"], ref_filled, comm.exchanges)
+    print(f"rank {rank}: MGPS_ERR_INVALID_ARGUMENT on both ranks before any exchange; the next call is complete, filled {out['filled']}", flush=True)
 
 
 if __name__ == "__main__":
-    main()
+    worker_main({"slabs": slabs_mode, "one": one_mode, "fail": fail_mode, "missing": missing_mode})

@@ -4,7 +4,8 @@ projection of the same scene.
 
 modes: "passes" (every slab pass against the whole-grid pass, sliced), "onecall" (mgps_project_free_surface_slab against
 mgps_project_free_surface), "options" (enclosed liquid, surface tension, a caller's surface pressure), "edges" (no liquid, liquid
-on one rank, a bad argument on one rank, a transport without gatherv), "one" (RcclComm with a world of one).  Prints
+on one rank, a bad argument on one rank, a transport without gatherv), "missing" (one rank without one of its solid velocities: the
+refusal every rank gets, and a complete call on the same transport), "one" (RcclComm with a world of one).  Prints
 "WORKER_OK <rank>" on success.
 """
 import os
@@ -22,7 +23,7 @@ import geometricmultigridpressuresolver_amd as G  # noqa: E402
 from geometricmultigridpressuresolver_amd import domains as D  # noqa: E402
 from geometricmultigridpressuresolver_amd import fields as F  # noqa: E402
 from geometricmultigridpressuresolver_amd.distributed import RcclComm, TorchDistComm  # noqa: E402
-from slab_slices import cell, dev, faces, halo, zface  # noqa: E402
+from slab_slices import all_ranks, cell, dev, faces, halo, worker_main, zface  # noqa: E402
 
 SHAPE = (96, 64, 64)  # (gz, gy, gx): 5 levels, offset 16, 128 expanded planes with either expansion
 CUTS = {1: [0, 128], 2: [0, 64, 128], 4: [0, 32, 64, 96, 128]}  # every rank owns base planes; valid for both smoothers
@@ -35,12 +36,6 @@ def h(a):
 
 def rel_l2(a, b):
     return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-300))
-
-
-def all_ranks(value):
-    seen = [None] * dist.get_world_size()
-    dist.all_gather_object(seen, value)
-    return seen
 
 
 def cut_faces(material, cw, splits, offset):
@@ -378,6 +373,36 @@ def edges_mode():
         raise AssertionError("a rank without base planes was accepted")
 
 
+# ---- 5b. a rank's own refusal travels in the first agreement ----------------------------------------------------------------------
+def missing_mode():
+    """rank 1 comes with two of its three solid velocities: its status travels in the agreement on the arguments, and both ranks return
+    MGPS_ERR_INVALID_ARGUMENT -- rank 1 with its own message, rank 0 naming rank 1 and the place.  The same transport then serves a
+    complete call that agrees with the single-device call: nobody was left behind in a collective"""
+    comm = TorchDistComm()
+    rank = comm.rank
+    assert comm.size == 2
+    splits = CUTS[2]
+    sc = D.projection_scene(SHAPE, with_solid_velocity=True)
+    d = F.slab_window(SHAPE, True, splits, rank)
+    kw = {"use_gauss_seidel": False, "power_of_two": True, "tolerance": 1e-6, "max_iterations": 300}
+    t = window_tensors(sc, d)
+    sv = list(t["solid_velocity"])
+    if rank == 1:
+        sv[1] = None
+    try:
+        F.project_free_surface_slab(comm, splits, SHAPE, t["liquid_phi"], t["solid_phi"], t["cut_weights"], t["velocity"], t["pressure"], sv,
+                                    use_old_pressure=False, **kw)
+    except G.MgpsError as e:
+        assert e.status == 1, (rank, e.status, str(e))
+        assert ("all three or none" if rank == 1 else "rank 1 failed (arguments, status 1)") in str(e), (rank, str(e))
+    else:
+        raise AssertionError(f"rank {rank}: two of three solid velocities on rank 1 went unnoticed")
+    for a, ref in enumerate(faces(sc["velocity"], d)):
+        assert np.array_equal(t["velocity"][a].cpu().numpy(), ref), a  # (nothing was touched)
+    rhs_max, _, _ = scene_rhs_max(sc, SHAPE, True)
+    check_against_single("after a refusal", comm, splits, SHAPE, sc, rhs_max, kw)
+
+
 # ---- 6. one rank over RCCL: the device-resident projection ------------------------------------------------------------------------
 def one_mode():
     comm = RcclComm()
@@ -393,18 +418,5 @@ def one_mode():
         comm.close()
 
 
-def main():
-    mode = sys.argv[1]
-    dist.init_process_group("gloo")
-    torch.cuda.set_device(0)
-    try:
-        {"passes": passes_mode, "onecall": onecall_mode, "options": options_mode, "edges": edges_mode, "one": one_mode}[mode]()
-        torch.cuda.synchronize()
-        dist.barrier()
-        print(f"WORKER_OK {dist.get_rank()}", flush=True)
-    finally:
-        dist.destroy_process_group()
-
-
 if __name__ == "__main__":
-    main()
+    worker_main({"passes": passes_mode, "onecall": onecall_mode, "options": options_mode, "edges": edges_mode, "missing": missing_mode, "one": one_mode})

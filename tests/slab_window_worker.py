@@ -23,18 +23,9 @@ from geometricmultigridpressuresolver_amd import domains as D  # noqa: E402
 from geometricmultigridpressuresolver_amd import fields as F  # noqa: E402
 from geometricmultigridpressuresolver_amd.distributed import (  # noqa: E402
     RcclComm, SlabSolver, TorchDistComm, slab_partition, slab_partition_device)
+from slab_slices import all_ranks, dev, worker_main  # noqa: E402
 
 LEVEL_ARRAYS = sorted(G.GeometricMultigridPoissonSolver.LEVEL_ARRAYS)
-
-
-def dev(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
-
-
-def all_ranks(value):
-    seen = [None] * dist.get_world_size()
-    dist.all_gather_object(seen, value)
-    return seen
 
 
 def copy_options(opt):
@@ -68,8 +59,8 @@ def build_pair(lab, w, lev, gs, opt, cuts, make_comm=TorchDistComm):
     z0, z1 = cuts[rank], cuts[rank + 1]
     slab_w = [w[0][z0:z1], w[1][z0:z1], w[2][z0:z1 + 1]]
     ca, cb = make_comm(), make_comm()
-    ref = SlabSolver(lab, [dev(a) for a in slab_w], lev, gs, ca, device=0, options=copy_options(opt), splits=cuts)
-    win = SlabSolver.from_device_labels(dev(lab[z0:z1], np.uint8), [dev(a) for a in slab_w], lab.shape[0], lev, gs, cb, device=0,
+    ref = SlabSolver(lab, [dev(a, np.float32) for a in slab_w], lev, gs, ca, device=0, options=copy_options(opt), splits=cuts)
+    win = SlabSolver.from_device_labels(dev(lab[z0:z1], np.uint8), [dev(a, np.float32) for a in slab_w], lab.shape[0], lev, gs, cb, device=0,
                                         options=copy_options(opt), splits=cuts)
     return ref, win, ca, cb
 
@@ -189,7 +180,7 @@ def failing_rank_check():
     lab[k + z0b + 2, j, i] = 3
     z0, z1 = rank * nzl, (rank + 1) * nzl
     try:
-        SlabSolver.from_device_labels(dev(lab[z0:z1], np.uint8), [dev(w[0][z0:z1]), dev(w[1][z0:z1]), dev(w[2][z0:z1 + 1])], lab.shape[0], lev, False,
+        SlabSolver.from_device_labels(dev(lab[z0:z1], np.uint8), [dev(a, np.float32) for a in (w[0][z0:z1], w[1][z0:z1], w[2][z0:z1 + 1])], lab.shape[0], lev, False,
                                       TorchDistComm(), device=0, options=options(min_cells_per_rank=0))
     except G.MgpsError as e:
         status, msg = e.status, str(e)
@@ -289,8 +280,8 @@ def one_mode():
             check_against_single(f"one rank gs={gs}", comm, CUTS[1], SHAPE, sc, rhs_max, kw)
         lab, w, off, lev, dx = make_domain("simple", 40, 4, (64, 64, 64))
         opt = options(min_cells_per_rank=0)
-        ref = SlabSolver(lab, [dev(a) for a in w], lev, False, comm, device=0, options=copy_options(opt))
-        win = SlabSolver.from_device_labels(dev(lab, np.uint8), [dev(a) for a in w], lab.shape[0], lev, False, comm, device=0, options=copy_options(opt))
+        ref = SlabSolver(lab, [dev(a, np.float32) for a in w], lev, False, comm, device=0, options=copy_options(opt))
+        win = SlabSolver.from_device_labels(dev(lab, np.uint8), [dev(a, np.float32) for a in w], lab.shape[0], lev, False, comm, device=0, options=copy_options(opt))
         try:
             assert win.distributed_levels == ref.distributed_levels >= 1 and win.getMGLevels() == ref.getMGLevels()
             for l in range(ref.distributed_levels):
@@ -305,18 +296,5 @@ def one_mode():
         comm.close()
 
 
-def main():
-    mode = sys.argv[1]
-    dist.init_process_group("gloo")
-    torch.cuda.set_device(0)
-    try:
-        {"ranks": ranks_mode, "one": one_mode}[mode]()
-        torch.cuda.synchronize()
-        dist.barrier()
-        print(f"WORKER_OK {dist.get_rank()}", flush=True)
-    finally:
-        dist.destroy_process_group()
-
-
 if __name__ == "__main__":
-    main()
+    worker_main({"ranks": ranks_mode, "one": one_mode})

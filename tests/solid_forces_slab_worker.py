@@ -24,20 +24,11 @@ import geometricmultigridpressuresolver_amd as G  # noqa: E402
 from geometricmultigridpressuresolver_amd import domains as D  # noqa: E402
 from geometricmultigridpressuresolver_amd import fields as F  # noqa: E402
 from geometricmultigridpressuresolver_amd.distributed import CommStruct, RcclComm, TorchDistComm  # noqa: E402
+from slab_slices import BrokenComm, all_ranks, dev, worker_main  # noqa: E402
 
 SHAPE = (48, 40, 56)  # (gz, gy, gx): 48 base planes
 BODIES = 3
 SCALE = 0.37
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def all_ranks(value):
-    seen = [None] * dist.get_world_size()
-    dist.all_gather_object(seen, value)
-    return seen
 
 
 def window(grids, d):
@@ -120,25 +111,6 @@ def one_mode():
         comm.close()
 
 
-class BrokenComm(TorchDistComm):
-    """a transport that breaks: the `exchange_fails_at`-th exchange of this rank delivers and then reports a failure; from the
-    `allreduce_fails_at`-th on, an all-reduce reports one at once (its peer has left).  0 = never."""
-
-    def __init__(self, exchange_fails_at=0, allreduce_fails_at=0):
-        super().__init__()
-        self.exchange_fails_at, self.allreduce_fails_at, self.allreduces = exchange_fails_at, allreduce_fails_at, 0
-
-    def _exchange(self, *args):
-        rc = super()._exchange(*args)
-        return 1 if self.exchanges == self.exchange_fails_at else rc
-
-    def _allreduce(self, *args):
-        self.allreduces += 1
-        if self.allreduce_fails_at and self.allreduces >= self.allreduce_fails_at:
-            return 1
-        return super()._allreduce(*args)
-
-
 def fail_mode():
     """rank 1's second exchange (pressure and material planes) fails: MGPS_ERR_COMM there, at once.  Rank 0 is left with a transport
     whose peer is gone: its next transport call -- the all-reduce of the rows -- fails too"""
@@ -178,7 +150,7 @@ def missing_mode():
         F.solid_forces_slab(comm, splits, SHAPE, *fields, [ids[0], None if rank == 1 else ids[1], ids[2]], centres, SCALE)
     except G.MgpsError as e:
         assert e.status == 1, (rank, e.status, str(e))
-        assert ("body: three grids are required" if rank == 1 else "rank 1 failed (status 1)") in str(e), (rank, str(e))
+        assert ("body: three grids are required" if rank == 1 else "rank 1 failed (rows, status 1)") in str(e), (rank, str(e))
     else:
         raise AssertionError(f"rank {rank}: a missing array on rank 1 went unnoticed")
     assert comm.exchanges == 2, (rank, comm.exchanges)
@@ -188,18 +160,5 @@ def missing_mode():
     print(f"rank {rank}: MGPS_ERR_INVALID_ARGUMENT on both ranks after {comm.exchanges} exchanges; the next call is complete", flush=True)
 
 
-def main():
-    mode = sys.argv[1]
-    dist.init_process_group("gloo")
-    torch.cuda.set_device(0)
-    try:
-        {"slabs": slabs_mode, "one": one_mode, "fail": fail_mode, "missing": missing_mode}[mode]()
-        torch.cuda.synchronize()
-        dist.barrier()
-        print(f"WORKER_OK {dist.get_rank()}", flush=True)
-    finally:
-        dist.destroy_process_group()
-
-
 if __name__ == "__main__":
-    main()
+    worker_main({"slabs": slabs_mode, "one": one_mode, "fail": fail_mode, "missing": missing_mode})

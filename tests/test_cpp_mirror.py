@@ -66,6 +66,26 @@ def test_host_setup_under_sanitizers():
     assert res.stdout.count(" ok: ") == 6 and "ERROR" not in res.stdout and "runtime error" not in res.stdout, res.stdout[-4000:]
 
 
+def test_slab_call_scaffold_under_sanitizers():
+    """The collective scaffold of the slab one-calls (csrc/mgps_slab_call.h: the transport check, the carried status, the agreement
+    all-reduce, the timed exchange) compiled with g++ -fsanitize=address,undefined, the ranks as threads over an in-process
+    transport (tests/cpp/slab_call_check.cpp): P = 1, 2, 4, every rank in turn as the failing one, transports that report failure,
+    a world of one that asks nobody, what open() refuses and reads of a short caller struct."""
+    src = os.path.join(ROOT, "tests", "cpp", "slab_call_check.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "build", "slab_call_check")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.check_call([
+        "g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+        "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, os.path.join(CSRC, "mgps_host.cpp"), "-o", out, "-lpthread",
+    ])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
+    env.pop("LD_PRELOAD", None)
+    res = subprocess.run([out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120, env=env)
+    assert res.returncode == 0, res.stdout[-4000:]
+    assert res.stdout.count(" ok: 1") == 3 and "slab call check ok" in res.stdout, res.stdout[-4000:]
+    assert "ERROR" not in res.stdout and "runtime error" not in res.stdout and "FAILED" not in res.stdout, res.stdout[-4000:]
+
+
 def test_flatten_roundtrip_and_cmake_configures_without_houdini(tmp_path):
     """The HDK-free half of the Houdini shim (geometricmultigridpressuresolver_amd/host/): flattenGrid / unflattenGrid
     round-trip on a 16^3-tiled stand-in for UT_VoxelArray (tests/cpp/flatten_roundtrip.cpp), and the top-level

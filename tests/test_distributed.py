@@ -11,35 +11,18 @@
   TorchDistComm/gloo and must reproduce the single-GPU solver on four domains (box, cut-cell solid, free-surface scene,
   random labels).  Only the transport differs from production (RCCL refuses two ranks on one device).
 """
+from functools import partial
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
+from slab_launch import run_workers as launch
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def run_workers(mode, nproc, timeout, extra_env=None):
-    cmd = [
-        sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
-        "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(HERE, "dist_worker.py"), mode,
-    ]
-    env = dict(os.environ, OMP_NUM_THREADS="2")
-    env.update(extra_env or {})
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout, env=env)
-    ok = [f"WORKER_OK {r}" in res.stdout for r in range(nproc)]
-    assert res.returncode == 0 and all(ok), res.stdout[-4000:]
-    return res.stdout
+run_workers = partial(launch, "dist_worker.py")
 
 
 @pytest.mark.gpu

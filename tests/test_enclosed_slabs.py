@@ -5,35 +5,14 @@ open and closed faces, 100+ bubbles, random domains, uneven cuts, the host build
 smoothers and the diagonal preconditioner, the V-cycle and P.  Without pockets the option adds no bit, exchange or device
 all-reduce.  A transport without gatherv / scatterv is refused."""
 import ctypes as C
-import os
-import socket
-import subprocess
-import sys
+from functools import partial
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from slab_launch import run_workers as launch
 
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def run_workers(mode, nproc, timeout):
-    cmd = [
-        sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
-        "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(HERE, "enclosed_slab_worker.py"), mode,
-    ]
-    env = dict(os.environ, OMP_NUM_THREADS="2")
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout, env=env)
-    ok = [f"WORKER_OK {r}" in res.stdout for r in range(nproc)]
-    assert res.returncode == 0 and all(ok), res.stdout[-4000:]
-    return res.stdout
+run_workers = partial(launch, "enclosed_slab_worker.py")
 
 
 @pytest.mark.gpu

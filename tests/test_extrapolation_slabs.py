@@ -2,34 +2,12 @@
 TorchDistComm/gloo (tests/extrapolate_slab_worker.py, one process per rank) and must reproduce mgps_fields_extrapolate3 on their
 planes bit for bit; one rank over RcclComm extrapolates behind the one-call projection; a transport whose exchange fails gives
 MGPS_ERR_COMM.  Every launch has a timeout of its own."""
-import os
-import socket
-import subprocess
-import sys
-
+from functools import partial
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from slab_launch import run_workers as launch
 
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def run_workers(mode, nproc, timeout):
-    cmd = [
-        sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
-        "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(HERE, "extrapolate_slab_worker.py"), mode,
-    ]
-    env = dict(os.environ, OMP_NUM_THREADS="2")
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout, env=env)
-    ok = [f"WORKER_OK {r}" in res.stdout for r in range(nproc)]
-    assert res.returncode == 0 and all(ok), res.stdout[-6000:]
-    return res.stdout
+run_workers = partial(launch, "extrapolate_slab_worker.py")
 
 
 @pytest.mark.gpu
@@ -46,3 +24,8 @@ def test_one_rank_over_rccl_extrapolates_behind_the_projection():
 @pytest.mark.gpu
 def test_failing_exchange_returns_comm_error_without_hanging():
     print(run_workers("fail", 2, 120)[-2000:])
+
+
+@pytest.mark.gpu
+def test_missing_array_on_one_rank_is_refused_on_every_rank():
+    print(run_workers("missing", 2, 120)[-2000:])

@@ -3,34 +3,13 @@
 reproduce the single-device passes on their planes and the single-device one-call projection of the same scene; one rank over
 RcclComm is the device-resident projection.  Several checks run per worker launch to keep the suite short."""
 import ctypes as C
-import os
-import socket
-import subprocess
-import sys
+from functools import partial
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from slab_launch import run_workers as launch
 
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def run_workers(mode, nproc, timeout):
-    cmd = [
-        sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
-        "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(HERE, "projection_slab_worker.py"), mode,
-    ]
-    env = dict(os.environ, OMP_NUM_THREADS="2")
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout, env=env)
-    ok = [f"WORKER_OK {r}" in res.stdout for r in range(nproc)]
-    assert res.returncode == 0 and all(ok), res.stdout[-6000:]
-    return res.stdout
+run_workers = partial(launch, "projection_slab_worker.py")
 
 
 # grids whose ranks get at least 16 base planes each at 4 ranks: the 16-plane minimum of a rank then does not bind and the division of
@@ -139,6 +118,11 @@ def test_slab_projection_options():
 @pytest.mark.gpu
 def test_slab_projection_edges():
     print(run_workers("edges", 2, 300)[-2000:])
+
+
+@pytest.mark.gpu
+def test_missing_array_on_one_rank_is_refused_on_every_rank():
+    print(run_workers("missing", 2, 120)[-2000:])
 
 
 @pytest.mark.gpu

@@ -3,34 +3,12 @@ TorchDistComm/gloo (tests/solid_forces_slab_worker.py, one process per rank) and
 pass on the gathered fields -- within the reordering bound of an fp64 sum, the count exactly, the same bits on all ranks; one rank
 over RcclComm behind the one-call projection equals the whole-grid pass bit for bit and makes no transport call; a transport whose
 exchange fails gives MGPS_ERR_COMM; a rank that comes without one of its arrays makes every rank return the same refusal.  Every launch has a timeout of its own."""
-import os
-import socket
-import subprocess
-import sys
-
+from functools import partial
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from slab_launch import run_workers as launch
 
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
-def run_workers(mode, nproc, timeout):
-    cmd = [
-        sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
-        "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(HERE, "solid_forces_slab_worker.py"), mode,
-    ]
-    env = dict(os.environ, OMP_NUM_THREADS="2")
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout, env=env)
-    ok = [f"WORKER_OK {r}" in res.stdout for r in range(nproc)]
-    assert res.returncode == 0 and all(ok), res.stdout[-6000:]
-    return res.stdout
+run_workers = partial(launch, "solid_forces_slab_worker.py")
 
 
 @pytest.mark.gpu
