@@ -2582,3 +2582,529 @@ try {
 MGPS_API_CATCH(nullptr)
 
 }  // extern "C"
+
+// ---- two-way rigid-body coupling: body velocities solved with the pressure (include/mgps_fields.h) -----------
+// Set-up compacts the COUPLED cells -- LIQUID cells with a wet face some body owns -- into a list in base-cell order: a count per
+// workgroup of 256 consecutive cells, an exclusive scan of the counts, and a fill pass that ranks the cells of a workgroup by
+// ballots.  Both passes take the faces from solidFaceTerm, the rule of the forces pass.  An application of G K G^T is three launches
+// over the list: the gather g = - G^T x sums per row with addFaceTerms (the forces pass's tables: lanes of one row by shuffles, a
+// table per wave, the waves' tables in wave order), one workgroup adds the workgroups' tables in index order and forms W = K g per
+// row (and g^T K g for the loop's <p, A p>), and the scatter gives each coupled cell - (G W)_c: a cell is written by its own thread.
+namespace {
+constexpr int kCoupleThreads = 256, kCoupleWaves = kCoupleThreads / 64, kCoupleBlocksMax = 128, kCoupleSumThreads = 1024;
+constexpr int kCoupleK = 7;  // K of one row: inv_mass, then inv_inertia xx, yy, zz, xy, xz, yz
+
+struct CoupleGrids {
+    Box g, e;
+    int offset, bodies;
+    const int32_t *material;
+    const float *cw[3];
+    const int32_t *body[3];
+};
+
+// The six faces of cell t of the base grid, slot 2 a + d: the backward (d = 0) and forward (d = 1) face of axis a.  False unless t is
+// a LIQUID cell with a wet face of row >= 1; then row[slot] is the face's row (0: not part of G) and sg[slot] its signed closed
+// fraction, + s on a backward and - s on a forward face ((G V)_c = sum of sg * sv over the slots).
+__device__ __forceinline__ bool coupledCell(const CoupleGrids &p, size_t t, int &i, int &j, int &k, int row[6], float sg[6])
+{
+    if (t >= p.g.cells()) return false;
+    if (p.material[t] != kLiquid) return false;
+    i = int(t % p.g.gx), j = int((t / p.g.gx) % p.g.gy), k = int(t / (size_t(p.g.gx) * p.g.gy));
+    const GridAt<int32_t> mat{p.g, p.material};
+    const auto noPressure = [](int, int, int) { return 0.f; };  // (phi is not wanted here)
+    bool any = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            int fc[3] = {i, j, k};  // the face lies behind cell fc
+            fc[a] += d;
+            const size_t f = faceAt(p.g, a, fc[0], fc[1], fc[2]);
+            int r = 0;
+            float s = 0.f;
+            double phi = 0.0;
+            const bool wet = solidFaceTerm(p.g, a, fc[0], fc[1], fc[2], p.cw[a][f], p.bodies, mat, noPressure, [&] { return p.body[a][f]; }, r, s, phi);
+            const bool on = wet && r >= 1;
+            row[2 * a + d] = on ? r : 0;
+            sg[2 * a + d] = on ? (d ? -s : s) : 0.f;
+            any = any || on;
+        }
+    return any;
+}
+
+__global__ __launch_bounds__(kCoupleThreads) void coupleCountKernel(CoupleGrids p, int32_t *__restrict__ blockCount)
+{
+    int i, j, k, row[6];
+    float sg[6];
+    const int n = __syncthreads_count(coupledCell(p, size_t(blockIdx.x) * kCoupleThreads + threadIdx.x, i, j, k, row, sg));
+    if (threadIdx.x == 0) blockCount[blockIdx.x] = n;
+}
+
+// cell[e] = the expanded index, rows[slot * count + e], sg[slot * count + e]: the list, entry e = blockStart + the cell's rank in its workgroup
+__global__ __launch_bounds__(kCoupleThreads) void coupleFillKernel(CoupleGrids p, const int32_t *__restrict__ blockStart, int count,
+                                                                   int32_t *__restrict__ cell, uint8_t *__restrict__ rows, float *__restrict__ sgs)
+{
+    __shared__ int waveCount[kCoupleWaves];
+    int i = 0, j = 0, k = 0, row[6];
+    float sg[6];
+    const bool on = coupledCell(p, size_t(blockIdx.x) * kCoupleThreads + threadIdx.x, i, j, k, row, sg);
+    const unsigned long long mask = __ballot(on);
+    const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
+    if (lane == 0) waveCount[wave] = __popcll(mask);
+    __syncthreads();
+    if (!on) return;
+    int e = blockStart[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) e += waveCount[w];
+    if (e >= count) return;  // (cannot happen: the count pass applied the same rule)
+    cell[e] = int32_t(cellAt(p.e, i + p.offset, j + p.offset, k + p.offset));
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        rows[size_t(s) * count + e] = uint8_t(row[s]);
+        sgs[size_t(s) * count + e] = sg[s];
+    }
+}
+
+struct CoupleList {
+    int count, bodies;
+    int ex, ey, offset;
+    const int32_t *cell;
+    const uint8_t *rows;
+    const float *sg;
+    const double *centres;  // device, (bodies + 1) * 3
+};
+// base coordinates of the list's cell c (an expanded index)
+__device__ __forceinline__ void coupleCoords(const CoupleList &L, int c, int &i, int &j, int &k)
+{
+    i = c % L.ex - L.offset;
+    j = (c / L.ex) % L.ey - L.offset;
+    k = c / (L.ex * L.ey) - L.offset;
+}
+
+// partials[workgroup][(bodies + 1) * kForceCols]: columns 0 .. 5 hold the workgroup's share of g = - G^T x (the layout of the forces
+// pass's tables; columns 6 and 7 are addFaceTerms' area and count, not used here)
+template <class X>
+__global__ __launch_bounds__(kCoupleThreads) void coupleGatherKernel(CoupleList L, const X *__restrict__ x, double *__restrict__ partials)
+{
+    extern __shared__ double coupleTables[];
+    const int entries = (L.bodies + 1) * kForceCols;
+    for (int e = int(threadIdx.x); e < kCoupleWaves * entries; e += kCoupleThreads) coupleTables[e] = 0.0;
+    __syncthreads();
+    double *table = coupleTables + size_t(threadIdx.x >> 6) * entries;
+    const int stride = int(gridDim.x) * kCoupleThreads;
+    for (int base = int(blockIdx.x) * kCoupleThreads; base < L.count; base += stride) {  // (a wave-uniform bound: every lane stays for the ballots)
+        const int e = base + int(threadIdx.x);
+        const bool on = e < L.count;
+        const int c = on ? L.cell[e] : 0;
+        const double xv = on ? double(x[c]) : 0.0;
+        int i, j, k;
+        coupleCoords(L, c, i, j, k);
+        int row[6];
+        float sg[6];
+#pragma unroll
+        for (int s = 0; s < 6; ++s) {
+            row[s] = on ? int(L.rows[size_t(s) * L.count + e]) : 0;
+            sg[s] = row[s] ? L.sg[size_t(s) * L.count + e] : 0.f;
+        }
+        // - sg x: the cell's share of the push on the body along +a (phi of the forces pass, cell by cell)
+        addFaceTerms<0>(table, L.centres, row[0] != 0, row[0], fabsf(sg[0]), -double(sg[0]) * xv, double(i), j + 0.5, k + 0.5);
+        addFaceTerms<0>(table, L.centres, row[1] != 0, row[1], fabsf(sg[1]), -double(sg[1]) * xv, double(i + 1), j + 0.5, k + 0.5);
+        addFaceTerms<1>(table, L.centres, row[2] != 0, row[2], fabsf(sg[2]), -double(sg[2]) * xv, i + 0.5, double(j), k + 0.5);
+        addFaceTerms<1>(table, L.centres, row[3] != 0, row[3], fabsf(sg[3]), -double(sg[3]) * xv, i + 0.5, double(j + 1), k + 0.5);
+        addFaceTerms<2>(table, L.centres, row[4] != 0, row[4], fabsf(sg[4]), -double(sg[4]) * xv, i + 0.5, j + 0.5, double(k));
+        addFaceTerms<2>(table, L.centres, row[5] != 0, row[5], fabsf(sg[5]), -double(sg[5]) * xv, i + 0.5, j + 0.5, double(k + 1));
+    }
+    __syncthreads();
+    double *out = partials + size_t(blockIdx.x) * entries;
+    for (int e = int(threadIdx.x); e < entries; e += kCoupleThreads) {
+        double sum = coupleTables[e];
+#pragma unroll
+        for (int wv = 1; wv < kCoupleWaves; ++wv) sum += coupleTables[size_t(wv) * entries + e];  // wave order
+        out[e] = sum;
+    }
+}
+
+// One workgroup: g[r][0..5] = the workgroups' tables added in index order (sixteen loads in flight per thread: a sum that waits for
+// each load in turn took 32 us at one body and 194 us at 255); W[r] = K[r] g[r] (inv_mass on the force,
+// inv_inertia on the torque); *quad += the sum over the rows of g[r] . W[r], in one fixed order (quad may be NULL)
+__global__ __launch_bounds__(kCoupleSumThreads) void coupleSumKernel(int bodies, int nblocks, const double *__restrict__ partials,
+                                                                     const double *__restrict__ K, double *__restrict__ g, double *__restrict__ W,
+                                                                     double *quad)
+{
+    extern __shared__ double coupleRows[];  // (bodies + 1) * 6, then 256 slots of q
+    const int n6 = (bodies + 1) * 6, entries = (bodies + 1) * kForceCols;
+    for (int e = int(threadIdx.x); e < n6; e += kCoupleSumThreads) {
+        const double *at = partials + (e / 6) * kForceCols + e % 6;
+        double sum = 0.0;
+        for (int b = 0; b < nblocks; b += 16) {
+            double v[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) v[q] = b + q < nblocks ? at[size_t(b + q) * entries] : 0.0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) sum += v[q];
+        }
+        coupleRows[e] = sum;
+        g[e] = sum;
+    }
+    double *q = coupleRows + n6;
+    if (threadIdx.x < 256) q[threadIdx.x] = 0.0;
+    __syncthreads();
+    const int r = int(threadIdx.x);  // (bodies <= 255: a thread per row; row 0 has K = 0)
+    if (r <= bodies) {
+        const double *gr = coupleRows + 6 * r, *k = K + size_t(kCoupleK) * r;
+        const double w[6] = {k[0] * gr[0], k[0] * gr[1], k[0] * gr[2],
+                             k[1] * gr[3] + k[4] * gr[4] + k[5] * gr[5],
+                             k[4] * gr[3] + k[2] * gr[4] + k[6] * gr[5],
+                             k[5] * gr[3] + k[6] * gr[4] + k[3] * gr[5]};
+        double qr = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            W[6 * r + c] = w[c];
+            qr += gr[c] * w[c];
+        }
+        q[r] = qr;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64 && quad) {  // (one wave: four rows per lane in order, then the butterfly)
+        const int l = int(threadIdx.x);
+        const double total = waveSum(((q[l] + q[l + 64]) + q[l + 128]) + q[l + 192]);
+        if (l == 0) *quad += total;
+    }
+}
+
+// target[c] = T(double(target[c]) + sign * (G W)_c) on the list's cells.  (G K G^T x = - G W with W = K g, g = - G^T x: sign = -1 adds
+// the operator, sign = +1 takes it off a residual.)  r32 (may be NULL): the float32 copy of the new value; corr (may be NULL): per
+// workgroup the sum of new^2 - old^2, lanes by the butterfly, waves in wave order
+template <class T>
+__global__ __launch_bounds__(kCoupleThreads) void coupleScatterKernel(CoupleList L, const double *__restrict__ W, double sign, T *__restrict__ target,
+                                                                      float *__restrict__ r32, double *__restrict__ corr)
+{
+    __shared__ double waveDelta[kCoupleWaves];
+    const int e = int(blockIdx.x) * kCoupleThreads + int(threadIdx.x);
+    double delta = 0.0;
+    if (e < L.count) {
+        const int c = L.cell[e];
+        int ijk[3];
+        coupleCoords(L, c, ijk[0], ijk[1], ijk[2]);
+        double v = 0.0;
+#pragma unroll
+        for (int s = 0; s < 6; ++s) {
+            const int r = int(L.rows[size_t(s) * L.count + e]);
+            if (!r) continue;
+            const int a = s >> 1, u = (a + 1) % 3, vv = (a + 2) % 3;
+            double pos[3] = {ijk[0] + 0.5, ijk[1] + 0.5, ijk[2] + 0.5};
+            pos[a] = double(ijk[a] + (s & 1));
+            const double *w = W + 6 * r, *cen = L.centres + 3 * r;
+            // (U + omega x d)_a = U_a + omega_u d_v - omega_v d_u
+            v += double(L.sg[size_t(s) * L.count + e]) * (w[a] + w[3 + u] * (pos[vv] - cen[vv]) - w[3 + vv] * (pos[u] - cen[u]));
+        }
+        const double old = double(target[c]), now = old + sign * v;
+        target[c] = T(now);
+        if (r32) r32[c] = float(now);
+        delta = now * now - old * old;
+    }
+    if (!corr) return;
+    delta = waveSum(delta);
+    if ((threadIdx.x & 63) == 0) waveDelta[threadIdx.x >> 6] = delta;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = waveDelta[0];
+#pragma unroll
+        for (int wv = 1; wv < kCoupleWaves; ++wv) sum += waveDelta[wv];
+        corr[blockIdx.x] = sum;
+    }
+}
+// *out += corr[0 .. n) added in a fixed order: each thread its strided share, then the threads in index order
+__global__ __launch_bounds__(kCoupleThreads) void coupleCorrKernel(int n, const double *__restrict__ corr, double *out)
+{
+    __shared__ double part[kCoupleThreads];
+    double sum = 0.0;
+    for (int b = int(threadIdx.x); b < n; b += kCoupleThreads) sum += corr[b];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        for (int t = 0; t < kCoupleThreads; ++t) total += part[t];
+        *out += total;
+    }
+}
+
+// sv[f] = float((U_r + omega_r x (x_f - centres[r]))_axis) on the faces of row r >= 1 of one axis
+__global__ void rigidVelocityKernel(Box g, int axis, float *__restrict__ sv, const int32_t *__restrict__ body, const double *__restrict__ centres,
+                                    const double *__restrict__ motions, int bodies)
+{
+    int i, j, k;
+    if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), i, j, k)) return;
+    const size_t f = faceAt(g, axis, i, j, k);
+    const int r = body[f];
+    if (r < 1 || r > bodies) return;
+    double pos[3] = {i + 0.5, j + 0.5, k + 0.5};
+    const int ijk[3] = {i, j, k};
+    pos[axis] = double(ijk[axis]);
+    const int u = (axis + 1) % 3, v = (axis + 2) % 3;
+    const double *m = motions + 6 * r, *c = centres + 3 * r;
+    sv[f] = float(m[axis] + m[3 + u] * (pos[v] - c[v]) - m[3 + v] * (pos[u] - c[u]));
+}
+
+template <class T>
+struct CoupleBuf {  // a device block of the library's allocator
+    T *p = nullptr;
+    int get(size_t count) { return mgps::deviceAlloc(reinterpret_cast<void **>(&p), std::max<size_t>(count, 1) * sizeof(T)); }
+    ~CoupleBuf()
+    {
+        if (p) (void)mgps::deviceFree(p);
+    }
+};
+
+// the host tables of the bodies: finite, inv_mass >= 0, the diagonal of inv_inertia >= 0 (rows 1 .. bodies; row 0 is not read)
+int coupleCheckBodies(const char *fn, int bodies, const double *centres, const double *invMass, const double *invInertia)
+{
+    if (!centres) return refuse(fn, "centres is NULL");
+    if (!invMass) return refuse(fn, "inv_mass is NULL");
+    if (!invInertia) return refuse(fn, "inv_inertia is NULL");
+    for (int r = 1; r <= bodies; ++r) {
+        if (!(std::isfinite(invMass[r]) && invMass[r] >= 0)) return refuse(fn, "inv_mass of body " + std::to_string(r) + " is negative or not finite");
+        for (int c = 0; c < 6; ++c)
+            if (!std::isfinite(invInertia[6 * r + c]) || (c < 3 && invInertia[6 * r + c] < 0))
+                return refuse(fn, "inv_inertia of body " + std::to_string(r) + " is not finite or has a negative diagonal entry");
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(centres[3 * r + c])) return refuse(fn, "centre of body " + std::to_string(r) + " is not finite");
+    }
+    return MGPS_OK;
+}
+int coupleHip(const char *fn, hipError_t e)
+{
+    if (e == hipSuccess) return MGPS_OK;
+    setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(e));
+    return MGPS_ERR_HIP;
+}
+}  // namespace
+
+struct mgps_coupling {
+    int bodies = 0, count = 0;
+    int ex = 0, ey = 0, ez = 0, offset = 0;
+    CoupleBuf<int32_t> cell;
+    CoupleBuf<uint8_t> rows;
+    CoupleBuf<float> sg;
+    CoupleBuf<double> tables;    // [centres (b + 1) * 3 | K (b + 1) * 7 | g (b + 1) * 6 | W (b + 1) * 6]
+    CoupleBuf<double> partials;  // gather: kCoupleBlocksMax tables; behind them the scatter's per-workgroup corrections
+    std::vector<double> K;       // host: what the device holds (mgps_coupling_velocities forms K g on the host)
+    int gatherBlocks() const { return std::min(kCoupleBlocksMax, (count + kCoupleThreads - 1) / kCoupleThreads); }
+    int scatterBlocks() const { return (count + kCoupleThreads - 1) / kCoupleThreads; }
+    size_t rows3() const { return size_t(bodies + 1) * 3; }
+    double *centres() const { return tables.p; }
+    double *Kdev() const { return tables.p + rows3(); }
+    double *g() const { return Kdev() + size_t(bodies + 1) * kCoupleK; }
+    double *W() const { return g() + size_t(bodies + 1) * 6; }
+    double *corr() const { return partials.p + size_t(kCoupleBlocksMax) * (bodies + 1) * kForceCols; }
+    CoupleList list() const { return CoupleList{count, bodies, ex, ey, offset, cell.p, rows.p, sg.p, centres()}; }
+};
+
+namespace {
+int coupleUpload(const char *fn, mgps_coupling *c, const double *centres, const double *invMass, const double *invInertia, hipStream_t st)
+{
+    const int n = c->bodies + 1;
+    std::vector<double> host(c->rows3() + size_t(n) * kCoupleK, 0.0);  // (row 0: zeros, never read through a face)
+    for (int r = 1; r < n; ++r) {
+        for (int q = 0; q < 3; ++q) host[size_t(3) * r + q] = centres[3 * r + q];
+        double *k = host.data() + c->rows3() + size_t(kCoupleK) * r;
+        k[0] = invMass[r];
+        for (int q = 0; q < 6; ++q) k[1 + q] = invInertia[6 * r + q];
+    }
+    c->K.assign(host.begin() + ptrdiff_t(c->rows3()), host.end());
+    if (int rc = coupleHip(fn, hipMemcpyAsync(c->tables.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st)); rc != MGPS_OK) return rc;
+    return coupleHip(fn, hipStreamSynchronize(st));  // (`host` leaves scope)
+}
+
+// gather + sum: g and W = K g on the device; *quad += g^T K g (quad may be NULL).  Nothing to do on an empty list (g, W stay 0)
+template <class X>
+int coupleGather(mgps_coupling *c, hipStream_t st, const X *x, double *quad)
+{
+    if (c->count == 0) return 0;
+    const int nb = c->gatherBlocks(), entries = (c->bodies + 1) * kForceCols;
+    coupleGatherKernel<X><<<nb, kCoupleThreads, size_t(kCoupleWaves) * entries * sizeof(double), st>>>(c->list(), x, c->partials.p);
+    coupleSumKernel<<<1, kCoupleSumThreads, (size_t(c->bodies + 1) * 6 + 256) * sizeof(double), st>>>(c->bodies, nb, c->partials.p, c->Kdev(), c->g(), c->W(), quad);
+    return int(hipGetLastError());
+}
+template <class T>
+int coupleScatter(mgps_coupling *c, hipStream_t st, double sign, T *target, float *r32, double *norm2)
+{
+    if (c->count == 0) return 0;
+    const int nb = c->scatterBlocks();
+    coupleScatterKernel<T><<<nb, kCoupleThreads, 0, st>>>(c->list(), c->W(), sign, target, r32, norm2 ? c->corr() : nullptr);
+    if (norm2) coupleCorrKernel<<<1, kCoupleThreads, 0, st>>>(nb, c->corr(), norm2);
+    return int(hipGetLastError());
+}
+}  // namespace
+
+namespace mgps {
+void couplingExtents(const mgps_coupling *c, int e[3]) { e[0] = c->ex, e[1] = c->ey, e[2] = c->ez; }
+int couplingApply64(mgps_coupling *c, void *stream, double *t, const double *p, double *dotDev)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int e = coupleGather(c, st, p, dotDev)) return e;
+    return coupleScatter<double>(c, st, -1.0, t, nullptr, nullptr);
+}
+int couplingResidual64(mgps_coupling *c, void *stream, double *r, const double *x, float *r32, double *norm2Dev)
+{
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int e = coupleGather(c, st, x, static_cast<double *>(nullptr))) return e;
+    return coupleScatter<double>(c, st, 1.0, r, r32, norm2Dev);
+}
+}  // namespace mgps
+
+extern "C" {
+
+int mgps_fields_rigid_velocity(float *svx, float *svy, float *svz, const int32_t *bx, const int32_t *by, const int32_t *bz,
+                               const double *centres_host, const double *motions_host, int bodies, int gx, int gy, int gz, void *stream)
+try {
+    const char *fn = "mgps_fields_rigid_velocity";
+    if (int rc = forceCheckBodies(fn, bodies); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
+    if (!svx || !svy || !svz) return refuse(fn, "solid velocity: three grids are required");
+    if (!bx || !by || !bz) return refuse(fn, "body: three grids are required");
+    if (!centres_host) return refuse(fn, "centres_host is NULL");
+    if (!motions_host) return refuse(fn, "motions_host is NULL");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t nc = size_t(bodies + 1) * 3, nm = size_t(bodies + 1) * 6;
+    DevPool pool;
+    double *dev = nullptr;  // [centres | motions]
+    try {
+        dev = pool.get<double>(nc + nm);
+    } catch (const std::bad_alloc &) {
+        setLastGlobalError(std::string(fn) + ": device allocation failed");
+        return MGPS_ERR_ALLOC;
+    }
+    if (int rc = coupleHip(fn, hipMemcpyAsync(dev, centres_host, nc * sizeof(double), hipMemcpyHostToDevice, st)); rc != MGPS_OK) return rc;
+    if (int rc = coupleHip(fn, hipMemcpyAsync(dev + nc, motions_host, nm * sizeof(double), hipMemcpyHostToDevice, st)); rc != MGPS_OK) return rc;
+    const Box g{gx, gy, gz};
+    float *sv[3] = {svx, svy, svz};
+    const int32_t *body[3] = {bx, by, bz};
+    for (int a = 0; a < 3; ++a) rigidVelocityKernel<<<blocks(faceCount(gx, gy, gz, a)), 256, 0, st>>>(g, a, sv[a], body[a], dev, dev + nc, bodies);
+    return coupleHip(fn, hipGetLastError());
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_coupling_create(mgps_coupling **out, const mgps_coupling_desc *d, void *stream)
+try {
+    const char *fn = "mgps_coupling_create";
+    if (!out) return refuse(fn, "out is NULL");
+    *out = nullptr;
+    if (!d || d->struct_size != int(sizeof(mgps_coupling_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_coupling_desc)");
+    if (int rc = forceCheckBodies(fn, d->bodies); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, d->gx, d->gy, d->gz); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, d->ex, d->ey, d->ez); rc != MGPS_OK) return rc;
+    if (d->offset < 0 || d->gx + d->offset > d->ex || d->gy + d->offset > d->ey || d->gz + d->offset > d->ez)
+        return refuse(fn, "the expanded box does not hold the base grid at this offset");
+    if (size_t(d->ex) * d->ey * d->ez > size_t(0x7fffffff)) return refuse(fn, "more than 2^31 - 1 expanded cells");
+    if (!d->material) return refuse(fn, "material is NULL");
+    if (!d->cut_weights[0] || !d->cut_weights[1] || !d->cut_weights[2]) return refuse(fn, "cut weights: three grids are required");
+    if (!d->body[0] || !d->body[1] || !d->body[2]) return refuse(fn, "body: three grids are required");
+    if (int rc = coupleCheckBodies(fn, d->bodies, d->centres, d->inv_mass, d->inv_inertia); rc != MGPS_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::unique_ptr<mgps_coupling> c(new mgps_coupling);
+    c->bodies = d->bodies;
+    c->ex = d->ex, c->ey = d->ey, c->ez = d->ez, c->offset = d->offset;
+    CoupleGrids p{Box{d->gx, d->gy, d->gz}, Box{d->ex, d->ey, d->ez}, d->offset, d->bodies, d->material, {d->cut_weights[0], d->cut_weights[1], d->cut_weights[2]},
+                  {d->body[0], d->body[1], d->body[2]}};
+    const size_t nblocks = (p.g.cells() + kCoupleThreads - 1) / kCoupleThreads;
+    if (nblocks > size_t(0x7fffffff)) return refuse(fn, "the base grid is too large");
+    const auto noMemory = [&] {
+        setLastGlobalError(std::string(fn) + ": device allocation failed");
+        return MGPS_ERR_ALLOC;
+    };
+    {
+        CoupleBuf<int32_t> blockCount, blockStart, scratch;
+        if (blockCount.get(nblocks) || blockStart.get(nblocks + 1) || scratch.get(scanScratchInts(nblocks))) return noMemory();
+        coupleCountKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockCount.p);
+        if (int rc = coupleHip(fn, hipGetLastError()); rc != MGPS_OK) return rc;
+        if (int e = launchExclusiveScan(st, blockCount.p, blockStart.p, nblocks, scratch.p)) return coupleHip(fn, hipError_t(e));
+        int32_t total = 0;
+        if (int rc = coupleHip(fn, hipMemcpyAsync(&total, blockStart.p + nblocks, sizeof(total), hipMemcpyDeviceToHost, st)); rc != MGPS_OK) return rc;
+        if (int rc = coupleHip(fn, hipStreamSynchronize(st)); rc != MGPS_OK) return rc;
+        c->count = total;
+        const size_t n = size_t(std::max(total, 1)), tab = size_t(d->bodies + 1);
+        if (c->cell.get(n) || c->rows.get(6 * n) || c->sg.get(6 * n) || c->tables.get(tab * (3 + kCoupleK + 6 + 6)) ||
+            c->partials.get(size_t(kCoupleBlocksMax) * tab * kForceCols + size_t(c->scatterBlocks()) + 1))
+            return noMemory();
+        if (total > 0) coupleFillKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockStart.p, total, c->cell.p, c->rows.p, c->sg.p);
+        if (int rc = coupleHip(fn, hipGetLastError()); rc != MGPS_OK) return rc;
+        if (int rc = coupleHip(fn, hipMemsetAsync(c->tables.p, 0, tab * (3 + kCoupleK + 6 + 6) * sizeof(double), st)); rc != MGPS_OK) return rc;
+        if (int rc = coupleHip(fn, hipStreamSynchronize(st)); rc != MGPS_OK) return rc;  // (the scan's buffers leave scope)
+    }
+    if (int rc = coupleUpload(fn, c.get(), d->centres, d->inv_mass, d->inv_inertia, st); rc != MGPS_OK) return rc;
+    *out = c.release();
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+void mgps_coupling_destroy(mgps_coupling *c)
+{
+    if (!c) return;
+    (void)hipDeviceSynchronize();  // (deviceFree does not wait for queued kernels)
+    delete c;
+}
+
+int mgps_coupling_set_bodies(mgps_coupling *c, const double *centres_host, const double *inv_mass_host, const double *inv_inertia_host, void *stream)
+try {
+    const char *fn = "mgps_coupling_set_bodies";
+    if (!c) return refuse(fn, "NULL coupling");
+    if (int rc = coupleCheckBodies(fn, c->bodies, centres_host, inv_mass_host, inv_inertia_host); rc != MGPS_OK) return rc;
+    return coupleUpload(fn, c, centres_host, inv_mass_host, inv_inertia_host, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_coupling_cells(const mgps_coupling *c, int64_t *count)
+{
+    if (!c || !count) return refuse("mgps_coupling_cells", "NULL argument");
+    *count = c->count;
+    return MGPS_OK;
+}
+
+int mgps_coupling_apply(mgps_coupling *c, float *y_dev, const float *x_dev, void *stream)
+try {
+    const char *fn = "mgps_coupling_apply";
+    if (!c) return refuse(fn, "NULL coupling");
+    if (!y_dev || !x_dev) return refuse(fn, "NULL grid");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int e = coupleGather(c, st, x_dev, static_cast<double *>(nullptr))) return coupleHip(fn, hipError_t(e));
+    return coupleHip(fn, hipError_t(coupleScatter<float>(c, st, -1.0, y_dev, nullptr, nullptr)));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_coupling_impulses(mgps_coupling *c, const float *x_dev, double *out_host, void *stream)
+try {
+    const char *fn = "mgps_coupling_impulses";
+    if (!c) return refuse(fn, "NULL coupling");
+    if (!x_dev) return refuse(fn, "x is NULL");
+    if (!out_host) return refuse(fn, "out_host is NULL");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t n = size_t(c->bodies + 1) * 6;
+    std::fill(out_host, out_host + n, 0.0);
+    if (c->count == 0) return coupleHip(fn, hipStreamSynchronize(st));
+    if (int e = coupleGather(c, st, x_dev, static_cast<double *>(nullptr))) return coupleHip(fn, hipError_t(e));
+    if (int rc = coupleHip(fn, hipMemcpyAsync(out_host, c->g(), n * sizeof(double), hipMemcpyDeviceToHost, st)); rc != MGPS_OK) return rc;
+    return coupleHip(fn, hipStreamSynchronize(st));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_coupling_velocities(mgps_coupling *c, const float *x_dev, const double *v_in_host, double *v_out_host, double *impulses_host, void *stream)
+try {
+    const char *fn = "mgps_coupling_velocities";
+    if (!c) return refuse(fn, "NULL coupling");
+    if (!v_in_host || !v_out_host) return refuse(fn, "NULL velocity table");
+    std::vector<double> g(size_t(c->bodies + 1) * 6);
+    if (int rc = mgps_coupling_impulses(c, x_dev, g.data(), stream); rc != MGPS_OK) return rc;
+    for (int r = 0; r <= c->bodies; ++r) {
+        const double *gr = g.data() + 6 * r, *k = c->K.data() + size_t(kCoupleK) * r, *in = v_in_host + 6 * r;
+        double *o = v_out_host + 6 * r;
+        for (int q = 0; q < 3; ++q) o[q] = in[q] + k[0] * gr[q];
+        o[3] = in[3] + (k[1] * gr[3] + k[4] * gr[4] + k[5] * gr[5]);
+        o[4] = in[4] + (k[4] * gr[3] + k[2] * gr[4] + k[6] * gr[5]);
+        o[5] = in[5] + (k[5] * gr[3] + k[6] * gr[4] + k[3] * gr[5]);
+    }
+    if (impulses_host) std::copy(g.begin(), g.end(), impulses_host);
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+}  // extern "C"

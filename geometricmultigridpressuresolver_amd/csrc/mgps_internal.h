@@ -611,6 +611,16 @@ int launchUnpack(void *stream, float *a, const float *buf, const int32_t *idx, i
 
 }  // namespace mgps
 
+// ---- the rigid-body coupling (mgps_fields.hip) as pcg64 sees it: fp64 grids of the expanded extents ----------
+struct mgps_coupling;
+namespace mgps {
+void couplingExtents(const mgps_coupling *c, int e[3]);
+// t += G K G^T p over the coupled cells and *dotDev += g^T K g (g = - G^T p): <p, A p> becomes <p, (A + G K G^T) p>.  Three launches
+int couplingApply64(mgps_coupling *c, void *stream, double *t, const double *p, double *dotDev);
+// r -= G K G^T x, r32 = float(r) on the coupled cells, *norm2Dev += the fp64 sum of new^2 - old^2 over them.  Four launches
+int couplingResidual64(mgps_coupling *c, void *stream, double *r, const double *x, float *r32, double *norm2Dev);
+}  // namespace mgps
+
 namespace mgps {
 constexpr int kHostCoarseMax = 8192;
 constexpr double kHostFactorFlops = 4e9;  // n x bandwidth^2 of the host's banded Cholesky factor (buildCoarseSolver): beyond it the device factorises

@@ -25,6 +25,7 @@
 #include <memory>
 #include <vector>
 
+#include "mgps_fields.h"
 #include "mgps_internal.h"
 
 using namespace mgps;
@@ -111,6 +112,7 @@ struct mgps_solver {
     double *partials = nullptr, *resultDev = nullptr, *resultHost = nullptr;
     double *dotPartials = nullptr;  // per-workgroup shares of <p, A p> from the fused A.p launch of the CG loop
     double *cg64[4] = {nullptr, nullptr, nullptr, nullptr};  // x, r, p, A p in fp64 (options.pcg_fp64_vectors), with ghost planes
+    mgps_coupling *coupling = nullptr;  // mgps_solve_pcg_coupled: the rigid-body coupling pcg64 adds to A, for the length of that call
     // the last stroke of a preconditioning V-cycle also gathers <x, b> (= <z, r>, CG.h:86 / 180) when asked to:
     // the sweep leaves <x', b>, every band scatter after it the correction sum (new - old) b
     bool gatherDot = false;
@@ -1560,7 +1562,9 @@ struct PcgExit {
 };
 
 // MG-PCG with the CG vectors in fp64 (options.pcg_fp64_vectors): CG.h:18-207 step by step like pcg() below; the
-// preconditioner is the same fp32 V-cycle (or diagonal) applied to float(r), x and b are fp32 at the boundary
+// preconditioner is the same fp32 V-cycle (or diagonal) applied to float(r), x and b are fp32 at the boundary.
+// With h->coupling set (mgps_solve_pcg_coupled) the operator is A + G K G^T: the coupling's list kernels follow
+// the stencil pass at the three places marked below, in front of the fetch of its reduction; without it no launch differs.
 int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool useMG, mgps_pcg_stats *st)
 {
     DevLevel &F = h->lv[0];
@@ -1575,6 +1579,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     h->dotTarget = nullptr;  // (the gathered <z, r> goes to resultDev here)
     double *x64 = h->cg64[0], *r64 = h->cg64[1], *p64 = h->cg64[2], *t64 = h->cg64[3];
     float *r32 = h->pcg[0], *z = h->pcg[2];
+    mgps_coupling *const cpl = h->coupling;
     SolveClock clock(h);  // (destroys its events and resets h->dotTarget on every way out)
     if (!clock.ok) return failH(h, MGPS_ERR_HIP, "hipEventCreate failed");
     const bool enc = hasEnclosed(h);  // options.enclosed_liquid: A x = P b, z = P M r (<z, r> then taken on the projected z)
@@ -1612,6 +1617,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     MGPS_LAUNCH(h, launchWiden(h->stream, x64, x, n));
     MGPS_TRY(exchangeGhosts64(h, x64));
     MGPS_LAUNCH(h, launchStencil64(h->stream, 1, F.g, r64, x64, b, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:50-57
+    if (cpl) MGPS_LAUNCH(h, couplingResidual64(cpl, h->stream, r64, x64, r32, h->resultDev));  // r -= G K G^T x
     MGPS_TRY(fetchReduction(h, 1, &res2));
     const double threshold = tol * tol * rhs2;  // CG.h:58
     if (res2 < threshold) {                     // CG.h:60-64
@@ -1634,6 +1640,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
         double pAp = 0;
         MGPS_TRY(exchangeGhosts64(h, p64));
         MGPS_LAUNCH(h, launchStencil64(h->stream, 0, F.g, t64, p64, nullptr, nullptr, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:110-121
+        if (cpl) MGPS_LAUNCH(h, couplingApply64(cpl, h->stream, t64, p64, h->resultDev));  // t += G K G^T p, <p, A p> += g^T K g
         MGPS_TRY(fetchReduction(h, 0, &pAp));
         const double alpha = absNew / pAp;
         MGPS_LAUNCH(h, launchCgUpdate64(h->stream, F.g, x64, p64, r64, t64, alpha, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:132-153
@@ -1653,6 +1660,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     double rec2 = 0;
     MGPS_TRY(exchangeGhosts64(h, x64));
     MGPS_LAUNCH(h, launchStencil64(h->stream, 1, F.g, r64, x64, b, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:203-205, in fp64
+    if (cpl) MGPS_LAUNCH(h, couplingResidual64(cpl, h->stream, r64, x64, r32, h->resultDev));
     MGPS_TRY(fetchReduction(h, 1, &rec2));
     st->rel_residual_recomputed = std::sqrt(rec2 / rhs2);
     return ex.finish(converged ? MGPS_PCG_CONVERGED : MGPS_PCG_MAX_ITERATIONS);
@@ -5063,6 +5071,40 @@ try {
     if (!x_dev || !b_dev || x_dev == b_dev || !(tolerance >= 0) || max_iterations < 0)
         return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_solve_pcg: bad arguments");
     return pcg(h, x_dev, const_cast<float *>(b_dev), tolerance, max_iterations, use_mg_preconditioner != 0, stats);
+}
+MGPS_API_CATCH(h)
+
+int mgps_solve_pcg_coupled(mgps_solver *h, mgps_coupling *coupling, float *x_dev, const float *b_dev, double tolerance, int max_iterations,
+                           int use_mg_preconditioner, mgps_pcg_stats *stats)
+try {
+    const char *fn = "mgps_solve_pcg_coupled";
+    MGPS_TRY(checkLevel(h, 0, fn));
+    if (!coupling) return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL coupling");
+    if (!x_dev || !b_dev || x_dev == b_dev || !(tolerance >= 0) || max_iterations < 0)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    if (h->dist || h->tailOfSlabRun)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": a slab solver cannot take a coupling (the list lives on one device)");
+    if (h->opt.precision == 1)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": not available with options.precision = 1 (mixed precision)");
+    if (hasEnclosed(h))
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT,
+                     std::string(fn) + ": the solver has an enclosed liquid component (options.enclosed_liquid); a moving body changes its null space");
+    int e[3];
+    couplingExtents(coupling, e);
+    const Dims &d = h->lv[0].d;
+    if (e[0] != d.nx || e[1] != d.ny || e[2] != d.nz)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT,
+                     std::string(fn) + ": the coupling's expanded extents " + std::to_string(e[0]) + " x " + std::to_string(e[1]) + " x " + std::to_string(e[2]) +
+                         " differ from the solver's " + std::to_string(d.nx) + " x " + std::to_string(d.ny) + " x " + std::to_string(d.nz));
+    mgps_pcg_stats local{};
+    if (!stats) stats = &local;
+    std::memset(stats, 0, sizeof(*stats));
+    struct Attached {  // (every way out of pcg64 detaches the coupling)
+        mgps_solver *h;
+        ~Attached() { h->coupling = nullptr; }
+    } attached{h};
+    h->coupling = coupling;
+    return pcg64(h, x_dev, const_cast<float *>(b_dev), tolerance, max_iterations, use_mg_preconditioner != 0, stats);
 }
 MGPS_API_CATCH(h)
 

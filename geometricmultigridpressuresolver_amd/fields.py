@@ -622,3 +622,150 @@ def solid_forces_slab(comm, splits, global_shape, pressure, liquid_phi, solid_ph
     cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
     check(lib().mgps_solid_forces_slab(C.byref(sf), C.byref(comm.struct), cuts, _stream()))
     return {"rows": out, "total_ms": sf.total_ms, "exchange_ms": sf.exchange_ms}
+
+
+# ---- two-way rigid-body coupling: body velocities solved with the pressure (include/mgps_fields.h) ------------
+def _table(a, bodies, cols, what):
+    """a host table with one row per body, row 0 included: (bodies + 1, cols) float64"""
+    import numpy as np
+
+    t = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, cols) if cols > 1 else np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    assert t.shape[0] == bodies + 1, (what, t.shape, bodies)
+    return t
+
+
+def rigidVelocity(solid_velocity, body, centres, motions):
+    """mgps_fields_rigid_velocity (in place on the three solid-velocity face grids): (U_r + omega_r x (x_f - centres[r]))_a on the faces
+    whose body id is 1 .. bodies; every other face keeps its value.  `motions`: (bodies + 1, 6) host array, U then omega per row."""
+    shape = list(solid_velocity[2].shape)
+    shape[0] -= 1
+    faces = _face3(tuple(shape))
+    sv = [_chk(solid_velocity[a], faces[a], torch.float32) for a in range(3)]
+    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
+    c, bodies = _centres(centres)
+    m = _table(motions, bodies, 6, "motions")
+    check(lib().mgps_fields_rigid_velocity(_p(sv[0]), _p(sv[1]), _p(sv[2]), _p(ids[0]), _p(ids[1]), _p(ids[2]), c.ctypes.data_as(C.c_void_p),
+                                           m.ctypes.data_as(C.c_void_p), int(bodies), *_g(tuple(shape)), _stream()))
+    return solid_velocity
+
+
+class CouplingDesc(C.Structure):
+    """mgps_coupling_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int),
+        ("ex", C.c_int), ("ey", C.c_int), ("ez", C.c_int), ("offset", C.c_int), ("bodies", C.c_int),
+        ("material", C.c_void_p), ("cut_weights", C.c_void_p * 3), ("body", C.c_void_p * 3),
+        ("centres", C.c_void_p), ("inv_mass", C.c_void_p), ("inv_inertia", C.c_void_p),
+    ]
+
+
+class RigidCoupling:
+    """mgps_coupling: the operator G K G^T of the bodies `body` / `centres` / `inv_mass` (bodies + 1) / `inv_inertia` (bodies + 1, 6:
+    xx, yy, zz, xy, xz, yz) on the coupled cells of the base grids, for expanded grids of `expanded_shape` at `offset`."""
+
+    def __init__(self, material, cut_cell_weights, body, centres, inv_mass, inv_inertia, expanded_shape, offset):
+        shape = tuple(material.shape)
+        faces = _face3(shape)
+        c, bodies = _centres(centres)
+        im, ii = _table(inv_mass, bodies, 1, "inv_mass"), _table(inv_inertia, bodies, 6, "inv_inertia")
+        d = CouplingDesc()
+        d.struct_size = C.sizeof(CouplingDesc)
+        d.gz, d.gy, d.gx = shape
+        d.ez, d.ey, d.ex = expanded_shape
+        d.offset, d.bodies = int(offset), int(bodies)
+        d.material = _chk(material, shape, torch.int32).data_ptr()
+        for a in range(3):
+            d.cut_weights[a] = _chk(cut_cell_weights[a], faces[a], torch.float32).data_ptr()
+            d.body[a] = _chk(body[a], faces[a], torch.int32).data_ptr()
+        d.centres, d.inv_mass, d.inv_inertia = c.ctypes.data, im.ctypes.data, ii.ctypes.data
+        self.h = C.c_void_p()
+        check(lib().mgps_coupling_create(C.byref(self.h), C.byref(d), _stream()))
+        self.bodies, self.expanded_shape, self.offset, self.device = bodies, tuple(expanded_shape), int(offset), material.device
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mgps_coupling_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _x(self, t):
+        return _p(_chk(t, self.expanded_shape, torch.float32))
+
+    def set_bodies(self, centres, inv_mass, inv_inertia):
+        c, bodies = _centres(centres)
+        assert bodies == self.bodies
+        im, ii = _table(inv_mass, bodies, 1, "inv_mass"), _table(inv_inertia, bodies, 6, "inv_inertia")
+        check(lib().mgps_coupling_set_bodies(self.h, c.ctypes.data_as(C.c_void_p), im.ctypes.data_as(C.c_void_p), ii.ctypes.data_as(C.c_void_p), _stream()))
+
+    def cells(self):
+        n = C.c_int64()
+        check(lib().mgps_coupling_cells(self.h, C.byref(n)))
+        return n.value
+
+    def apply(self, y, x):
+        """y += G K G^T x on the coupled cells (expanded float32 grids), in place on y"""
+        check(lib().mgps_coupling_apply(self.h, self._x(y), self._x(x), _stream()))
+        return y
+
+    def impulses(self, x):
+        """(bodies + 1, 6) float64: (F, T) = - G^T x per row at scale 1, row 0 zero"""
+        import numpy as np
+
+        out = np.zeros((self.bodies + 1, 6), dtype=np.float64)
+        check(lib().mgps_coupling_impulses(self.h, self._x(x), out.ctypes.data_as(C.c_void_p), _stream()))
+        return out
+
+    def velocities(self, x, motions):
+        """(V_out, impulses): V_out = motions + K (F, T)(x), both (bodies + 1, 6) float64"""
+        import numpy as np
+
+        m = _table(motions, self.bodies, 6, "motions")
+        out, imp = np.zeros_like(m), np.zeros_like(m)
+        check(lib().mgps_coupling_velocities(self.h, self._x(x), m.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                                             imp.ctypes.data_as(C.c_void_p), _stream()))
+        return out, imp
+
+
+def project_free_surface_rigid(liquid_phi, solid_phi, cut_weights, velocity, pressure, body, centres, inv_mass, inv_inertia, motions,
+                               solid_velocity=None, use_old_pressure=True, use_mg_preconditioner=True, use_gauss_seidel=True, tolerance=1e-5,
+                               max_iterations=2500, power_of_two=True, options=None):
+    """The free-surface projection with rigid bodies the liquid moves, composed from the device passes on CUDA tensors: material
+    labels, valid faces, MG domain, rigidVelocity(V*) + buildRHS, solver from the device labels, the coupled solve (A + G K G^T) p =
+    b_fluid + G V*, pressure write-back and gradient.  `velocity` and `pressure` are updated in place; `solid_velocity` (or zeros)
+    supplies the faces no body owns and is left untouched.  `motions` = V*: (bodies + 1, 6), U then omega per row.
+    Returns {"pressure", "velocity", "motions": V_out = V* + K (F, T)(p), "impulses", "stats", "material", "valid_faces", "solid_velocity":
+    the rigid velocity of V*, "offset", "expanded", "coupled_cells"}."""
+    from . import solver as S
+
+    shape = tuple(liquid_phi.shape)
+    faces = _face3(shape)
+    material = buildMaterialCellLabels(liquid_phi, solid_phi, cut_weights)
+    valid = buildValidFaces(material, cut_weights)
+    eshape, offset, levels = S.expanded_layout(shape, 0, power_of_two)
+    labels, weights = buildMGDomain(material, cut_weights, liquid_phi, valid, eshape, offset)
+    if solid_velocity is not None:
+        sv = [_chk(solid_velocity[a], faces[a], torch.float32).clone() for a in range(3)]
+    else:
+        sv = [torch.zeros(faces[a], dtype=torch.float32, device=material.device) for a in range(3)]
+    rigidVelocity(sv, body, centres, motions)
+    rhs = buildRHS(material, velocity, cut_weights, eshape, offset, sv)
+    x = applyOldPressure(pressure, material, eshape, offset) if use_old_pressure else torch.zeros(eshape, dtype=torch.float32, device=material.device)
+    mg = S.GeometricMultigridPoissonSolver(labels, weights, levels, use_gauss_seidel, options=options)
+    coupling = RigidCoupling(material, cut_weights, body, centres, inv_mass, inv_inertia, eshape, offset)
+    try:
+        stats = mg.solve_pcg_coupled(coupling, x, rhs, tolerance, max_iterations, use_mg_preconditioner)
+        applySolutionToPressure(pressure, x, material, offset)
+        applyPressureGradient(velocity, liquid_phi, pressure, valid, material)
+        v_out, impulses = coupling.velocities(x, motions)
+        cells = coupling.cells()
+    finally:
+        coupling.close()
+        mg.close()
+    return {"pressure": pressure, "velocity": velocity, "motions": v_out, "impulses": impulses, "stats": stats, "material": material,
+            "valid_faces": valid, "solid_velocity": sv, "offset": offset, "expanded": eshape, "coupled_cells": cells}

@@ -386,6 +386,19 @@ class GeometricMultigridPoissonSolver:
         )
         return _pcg_stats(st)
 
+    def solve_pcg_coupled(self, coupling, solution, rhs, tolerance=1e-5, max_iterations=2500, use_mg_preconditioner=True):
+        """mgps_solve_pcg_coupled: (A + G K G^T) solution = rhs with `coupling` (fields.RigidCoupling) attached for the length of the
+        call; the loop of options.pcg_fp64_vectors = 1 (include/mgps_fields.h)"""
+        st = PcgStats()
+        _check_pcg(
+            lib().mgps_solve_pcg_coupled(
+                self.h, coupling.h, self._g(solution), self._g(rhs), C.c_double(tolerance), int(max_iterations), int(bool(use_mg_preconditioner)), C.byref(st)
+            ),
+            self.h,
+            st,
+        )
+        return _pcg_stats(st)
+
     # -- enclosed liquid (options.enclosed_liquid) ------------------------------------------------------
     def enclosed_components(self):
         """(components, cells): the fine level's liquid components without a DIRICHLET contact; (0, 0) with the option off."""

@@ -379,6 +379,79 @@ struct mgps_solid_forces_slab {
 };
 int mgps_solid_forces_slab(struct mgps_solid_forces_slab *s, const mgps_comm *comm, const int *splits, void *stream);
 
+/* ---- two-way rigid-body coupling: body velocities solved with the pressure ---------------------------------
+ * mgps_fields_rhs takes a solid velocity, mgps_fields_solid_forces returns what the pressure pushes back with; the entries below
+ * close the loop for rigid bodies that the liquid moves (Batty, Bertails & Bridson 2007).  No counterpart in the reference; the
+ * definition here is the contract.
+ *   A body r = 1 .. bodies moves with V_r = (U_r, omega_r): sv_a[f] = (U_r + omega_r x (x_f - centres[r]))_a on the faces whose row
+ *   (section "pressure feedback" above: body[a][f] if 1 <= body[a][f] <= bodies, else 0) is r.  G maps the motions to the solid
+ *   part of the right-hand side: (G V)_c = sum_a s_back sv_back - s_fwd sv_fwd at a LIQUID cell c, s the closed fraction
+ *   w < 1.f ? 1.f - w : 0.f of the face; faces of row 0 (walls, scripted solids, ids out of range) are not part of G.  By the
+ *   adjoint identity above the rows of mgps_fields_solid_forces at scale 1 are (F, T) = - G^T p.
+ *   With lengths in cells and the pressure in velocity units a body answers the pressure with V_out = V* + K (F, T)(p), K block
+ *   diagonal per body: inv_mass * I_3 on the force and the symmetric 3 x 3 inv_inertia (world frame, about centres[r]) on the torque,
+ *   inv_mass = density dx^3 / m, inv_inertia = density dx^5 I^-1.  inv_mass = 0 and inv_inertia = 0: a kinematic body, the one-way
+ *   behaviour of mgps_fields_rhs alone.  Substituting V_out into A p = b_fluid + G V_out gives the symmetric positive definite system
+ *   (A + G K G^T) p = b_fluid + G V*, which mgps_solve_pcg_coupled solves; the right-hand side is mgps_fields_rhs with the solid
+ *   velocity mgps_fields_rigid_velocity writes from V*.
+ * Arithmetic: fp64 from the float32 fields and the host tables; every sum over cells has one order, fixed by the extents and the
+ * inputs (wave butterfly, per-workgroup tables, one sum in workgroup order; no floating-point atomics): the same inputs give the
+ * same bits on every run. */
+/* sv_a[f] = float((U_r + omega_r x (x_f - centres[r]))_a), formed in fp64 and rounded once, on every face with row r >= 1; every
+ * other face keeps its value (walls and scripted solids stay the caller's).  motions_host[(bodies + 1) * 6]: U then omega per row
+ * (row 0 is not read); centres_host[(bodies + 1) * 3] as in mgps_fields_solid_forces.  Refuses what that entry refuses. */
+int mgps_fields_rigid_velocity(float *svx, float *svy, float *svz, const int32_t *bx, const int32_t *by, const int32_t *bz,
+                               const double *centres_host, const double *motions_host, int bodies, int gx, int gy, int gz, void *stream);
+
+/* The coupling object: the list of COUPLED cells -- LIQUID cells with at least one face of s > 0 and row >= 1 -- made on the device
+ * (count, scan, compact) from the base grids; per cell its expanded index and, for its six faces, the row and the signed s (+ on
+ * the backward, - on the forward face).  A cell appears once whatever the number of bodies it touches; the list is in base-cell
+ * order.  The kernels of an application run over the list only.  The grids are read by mgps_coupling_create and not kept; the
+ * object owns its device memory and its scratch: one call at a time per object. */
+typedef struct mgps_coupling mgps_coupling;
+typedef struct mgps_coupling_desc {
+    int struct_size;             /* sizeof(mgps_coupling_desc) */
+    int gx, gy, gz;              /* base grid */
+    int ex, ey, ez, offset;      /* the expanded layout (mgps_expanded_layout): base cell c lives at c + offset */
+    int bodies;                  /* 1 .. 255 */
+    const int32_t *material;     /* device, base cell grid */
+    const float *cut_weights[3]; /* device, base face grids */
+    const int32_t *body[3];      /* device, base face grids of body ids */
+    const double *centres;       /* host, (bodies + 1) * 3; row 0 is not read */
+    const double *inv_mass;      /* host, bodies + 1; row 0 is not read */
+    const double *inv_inertia;   /* host, (bodies + 1) * 6 in the order xx, yy, zz, xy, xz, yz; row 0 is not read */
+} mgps_coupling_desc;
+/* Refuses, before any device work: NULL / struct_size mismatch, a NULL array, bodies outside 1 .. 255, a non-positive extent, an
+ * expanded box that does not hold the base grid at `offset` or has 2^31 cells or more, a negative or non-finite inv_mass, a
+ * negative or non-finite diagonal entry of inv_inertia.  Synchronises the stream (the list's length comes to the host). */
+int mgps_coupling_create(mgps_coupling **out, const mgps_coupling_desc *d, void *stream);
+void mgps_coupling_destroy(mgps_coupling *c);
+/* new centres and K for the same list (a sub-step that moves the bodies but not the grids' faces); checks as above */
+int mgps_coupling_set_bodies(mgps_coupling *c, const double *centres_host, const double *inv_mass_host, const double *inv_inertia_host,
+                             void *stream);
+int mgps_coupling_cells(const mgps_coupling *c, int64_t *count);
+/* x, y: expanded float32 grids.  y[c] = float(double(y[c]) + (G K G^T x)_c) on the coupled cells; nothing else is touched.  Three
+ * launches: gather g = - G^T x ((bodies + 1) * 6 doubles, on the device), its sum with W = K g, scatter.  No synchronisation */
+int mgps_coupling_apply(mgps_coupling *c, float *y_dev, const float *x_dev, void *stream);
+/* out_host[(bodies + 1) * 6]: (F, T) = - G^T x per row at scale 1, row 0 zero: columns 0 .. 5 of mgps_fields_solid_forces on the
+ * matching base-grid pressure.  Synchronises the stream */
+int mgps_coupling_impulses(mgps_coupling *c, const float *x_dev, double *out_host, void *stream);
+/* v_out_host = v_in_host + K (F, T)(x) per row ((bodies + 1) * 6: U then omega; row 0 is copied), the product formed on the host in
+ * fp64 from the impulses; impulses_host (may be NULL) receives them.  Synchronises the stream */
+int mgps_coupling_velocities(mgps_coupling *c, const float *x_dev, const double *v_in_host, double *v_out_host, double *impulses_host,
+                             void *stream);
+/* mgps_solve_pcg on (A + G K G^T) x = b with the coupling attached to the solver for the length of the call.  It runs the loop of
+ * options.pcg_fp64_vectors = 1 whatever that option says: after t = A p, t += G K G^T p and <p, A p> gains g^T K g on the device; the
+ * two true residuals lose G K G^T x (the coupled cells' float32 residual is narrowed again and |r|^2 corrected by the fp64 sum of
+ * new^2 - old^2 over them); preconditioner, updates, interrupt and the iterate handed back are those of mgps_solve_pcg.  With K = 0
+ * every coupling term is 0.0 and the iterates are those of mgps_solve_pcg under pcg_fp64_vectors = 1.
+ * The coupled cells must be active cells of the solver (both made from the same material labels).  Refused with a message: a slab
+ * solver, options.precision = 1, a solver with an enclosed component (options.enclosed_liquid: a moving body changes the null
+ * space), a coupling whose expanded extents differ from the solver's.  Coupling inside the one-call entries, on slabs and in the
+ * default grouped fp32 loop: not yet. */
+int mgps_solve_pcg_coupled(mgps_solver *h, mgps_coupling *coupling, float *x_dev, const float *b_dev, double tolerance,
+                           int max_iterations, int use_mg_preconditioner, mgps_pcg_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif
