@@ -2590,13 +2590,15 @@ MGPS_API_CATCH(nullptr)
 // over the list: the gather g = - G^T x sums per row with addFaceTerms (the forces pass's tables: lanes of one row by shuffles, a
 // table per wave, the waves' tables in wave order), one workgroup adds the workgroups' tables in index order and forms W = K g per
 // row (and g^T K g for the loop's <p, A p>), and the scatter gives each coupled cell - (G W)_c: a cell is written by its own thread.
+// On slab ranks (mgps_coupling_create_slab) a rank lists its own cells from its window of the grids, and g is summed over the ranks
+// between the two halves of the sum stage: one all-reduce of (bodies + 1) * 6 doubles per application.
 namespace {
 constexpr int kCoupleThreads = 256, kCoupleWaves = kCoupleThreads / 64, kCoupleBlocksMax = 128, kCoupleSumThreads = 1024;
 constexpr int kCoupleK = 7;  // K of one row: inv_mass, then inv_inertia xx, yy, zz, xy, xz, yz
 
 struct CoupleGrids {
-    Box g, e;
-    int offset, bodies;
+    Box g, e;  // the base cell grid the arrays are indexed in and the expanded grid of the list's indices: whole grids, or a rank's windows
+    int offset, zoff, bodies;  // base cell (i, j, k) of g lives at (i + offset, j + offset, k + zoff) of e; zoff = offset on whole grids
     const int32_t *material;
     const float *cw[3];
     const int32_t *body[3];
@@ -2605,6 +2607,9 @@ struct CoupleGrids {
 // The six faces of cell t of the base grid, slot 2 a + d: the backward (d = 0) and forward (d = 1) face of axis a.  False unless t is
 // a LIQUID cell with a wet face of row >= 1; then row[slot] is the face's row (0: not part of G) and sg[slot] its signed closed
 // fraction, + s on a backward and - s on a forward face ((G V)_c = sum of sg * sv over the slots).
+// Window: g is a rank's window and the cell across a face may lie on another rank.  The cell itself is LIQUID, so solidFaceTerm
+// finds every face of w < 1 wet whatever lies across it: it is handed `LIQUID` for every cell and no label but the cell's own is read.
+template <bool Window>
 __device__ __forceinline__ bool coupledCell(const CoupleGrids &p, size_t t, int &i, int &j, int &k, int row[6], float sg[6])
 {
     if (t >= p.g.cells()) return false;
@@ -2623,7 +2628,10 @@ __device__ __forceinline__ bool coupledCell(const CoupleGrids &p, size_t t, int 
             int r = 0;
             float s = 0.f;
             double phi = 0.0;
-            const bool wet = solidFaceTerm(p.g, a, fc[0], fc[1], fc[2], p.cw[a][f], p.bodies, mat, noPressure, [&] { return p.body[a][f]; }, r, s, phi);
+            const auto bodyOf = [&] { return p.body[a][f]; };
+            bool wet;
+            if constexpr (Window) wet = solidFaceTerm(p.g, a, fc[0], fc[1], fc[2], p.cw[a][f], p.bodies, [](int, int, int) { return kLiquid; }, noPressure, bodyOf, r, s, phi);
+            else wet = solidFaceTerm(p.g, a, fc[0], fc[1], fc[2], p.cw[a][f], p.bodies, mat, noPressure, bodyOf, r, s, phi);
             const bool on = wet && r >= 1;
             row[2 * a + d] = on ? r : 0;
             sg[2 * a + d] = on ? (d ? -s : s) : 0.f;
@@ -2632,22 +2640,26 @@ __device__ __forceinline__ bool coupledCell(const CoupleGrids &p, size_t t, int 
     return any;
 }
 
-__global__ __launch_bounds__(kCoupleThreads) void coupleCountKernel(CoupleGrids p, int32_t *__restrict__ blockCount)
+template <bool Window>
+__device__ __forceinline__ void coupleCount(const CoupleGrids &p, int32_t *__restrict__ blockCount)
 {
     int i, j, k, row[6];
     float sg[6];
-    const int n = __syncthreads_count(coupledCell(p, size_t(blockIdx.x) * kCoupleThreads + threadIdx.x, i, j, k, row, sg));
+    const int n = __syncthreads_count(coupledCell<Window>(p, size_t(blockIdx.x) * kCoupleThreads + threadIdx.x, i, j, k, row, sg));
     if (threadIdx.x == 0) blockCount[blockIdx.x] = n;
 }
+__global__ __launch_bounds__(kCoupleThreads) void coupleCountKernel(CoupleGrids p, int32_t *__restrict__ blockCount) { coupleCount<false>(p, blockCount); }
+__global__ __launch_bounds__(kCoupleThreads) void coupleCountWindowKernel(CoupleGrids p, int32_t *__restrict__ blockCount) { coupleCount<true>(p, blockCount); }
 
 // cell[e] = the expanded index, rows[slot * count + e], sg[slot * count + e]: the list, entry e = blockStart + the cell's rank in its workgroup
-__global__ __launch_bounds__(kCoupleThreads) void coupleFillKernel(CoupleGrids p, const int32_t *__restrict__ blockStart, int count,
-                                                                   int32_t *__restrict__ cell, uint8_t *__restrict__ rows, float *__restrict__ sgs)
+template <bool Window>
+__device__ __forceinline__ void coupleFill(const CoupleGrids &p, const int32_t *__restrict__ blockStart, int count, int32_t *__restrict__ cell,
+                                           uint8_t *__restrict__ rows, float *__restrict__ sgs)
 {
     __shared__ int waveCount[kCoupleWaves];
     int i = 0, j = 0, k = 0, row[6];
     float sg[6];
-    const bool on = coupledCell(p, size_t(blockIdx.x) * kCoupleThreads + threadIdx.x, i, j, k, row, sg);
+    const bool on = coupledCell<Window>(p, size_t(blockIdx.x) * kCoupleThreads + threadIdx.x, i, j, k, row, sg);
     const unsigned long long mask = __ballot(on);
     const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
     if (lane == 0) waveCount[wave] = __popcll(mask);
@@ -2656,28 +2668,39 @@ __global__ __launch_bounds__(kCoupleThreads) void coupleFillKernel(CoupleGrids p
     int e = blockStart[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) e += waveCount[w];
     if (e >= count) return;  // (cannot happen: the count pass applied the same rule)
-    cell[e] = int32_t(cellAt(p.e, i + p.offset, j + p.offset, k + p.offset));
+    cell[e] = int32_t(cellAt(p.e, i + p.offset, j + p.offset, k + p.zoff));
 #pragma unroll
     for (int s = 0; s < 6; ++s) {
         rows[size_t(s) * count + e] = uint8_t(row[s]);
         sgs[size_t(s) * count + e] = sg[s];
     }
 }
+__global__ __launch_bounds__(kCoupleThreads) void coupleFillKernel(CoupleGrids p, const int32_t *__restrict__ blockStart, int count,
+                                                                   int32_t *__restrict__ cell, uint8_t *__restrict__ rows, float *__restrict__ sgs)
+{
+    coupleFill<false>(p, blockStart, count, cell, rows, sgs);
+}
+__global__ __launch_bounds__(kCoupleThreads) void coupleFillWindowKernel(CoupleGrids p, const int32_t *__restrict__ blockStart, int count,
+                                                                         int32_t *__restrict__ cell, uint8_t *__restrict__ rows, float *__restrict__ sgs)
+{
+    coupleFill<true>(p, blockStart, count, cell, rows, sgs);
+}
 
 struct CoupleList {
     int count, bodies;
     int ex, ey, offset;
+    int z0;  // the expanded plane of the whole grid that plane 0 of the list's indices is: 0 on whole grids, e0 on a rank's window
     const int32_t *cell;
     const uint8_t *rows;
     const float *sg;
     const double *centres;  // device, (bodies + 1) * 3
 };
-// base coordinates of the list's cell c (an expanded index)
+// base coordinates, in the whole grid, of the list's cell c (an expanded index)
 __device__ __forceinline__ void coupleCoords(const CoupleList &L, int c, int &i, int &j, int &k)
 {
     i = c % L.ex - L.offset;
     j = (c / L.ex) % L.ey - L.offset;
-    k = c / (L.ex * L.ey) - L.offset;
+    k = c / (L.ex * L.ey) - L.offset + L.z0;
 }
 
 // partials[workgroup][(bodies + 1) * kForceCols]: columns 0 .. 5 hold the workgroup's share of g = - G^T x (the layout of the forces
@@ -2723,9 +2746,49 @@ __global__ __launch_bounds__(kCoupleThreads) void coupleGatherKernel(CoupleList 
     }
 }
 
-// One workgroup: g[r][0..5] = the workgroups' tables added in index order (sixteen loads in flight per thread: a sum that waits for
-// each load in turn took 32 us at one body and 194 us at 255); W[r] = K[r] g[r] (inv_mass on the force,
-// inv_inertia on the torque); *quad += the sum over the rows of g[r] . W[r], in one fixed order (quad may be NULL)
+// The three steps of the sum stage, each stated once: on one device coupleSumKernel takes them in one launch; on slab ranks
+// coupleRankSumKernel and coupleRowsKernel take them on either side of the all-reduce of g.
+// Entry e of g: the workgroups' tables added in index order (sixteen loads in flight per thread: a sum that waits for each load in
+// turn took 32 us at one body and 194 us at 255); 0 without a workgroup
+__device__ __forceinline__ double coupleTableSum(const double *__restrict__ partials, int e, int nblocks, int entries)
+{
+    const double *at = partials + (e / 6) * kForceCols + e % 6;
+    double sum = 0.0;
+    for (int b = 0; b < nblocks; b += 16) {
+        double v[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = b + q < nblocks ? at[size_t(b + q) * entries] : 0.0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) sum += v[q];
+    }
+    return sum;
+}
+// W[r] = K[r] g[r] (inv_mass on the force, inv_inertia on the torque); returns g[r] . W[r]
+__device__ __forceinline__ double coupleRowProduct(const double *gr, const double *__restrict__ k, double *__restrict__ Wr)
+{
+    const double w[6] = {k[0] * gr[0], k[0] * gr[1], k[0] * gr[2],
+                         k[1] * gr[3] + k[4] * gr[4] + k[5] * gr[5],
+                         k[4] * gr[3] + k[2] * gr[4] + k[6] * gr[5],
+                         k[5] * gr[3] + k[6] * gr[4] + k[3] * gr[5]};
+    double qr = 0.0;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        Wr[c] = w[c];
+        qr += gr[c] * w[c];
+    }
+    return qr;
+}
+// *quad += the sum of the 256 slots of q in one fixed order (one wave: four rows per lane in order, then the butterfly)
+__device__ __forceinline__ void coupleQuadSum(const double *q, double *quad)
+{
+    if (threadIdx.x < 64 && quad) {
+        const int l = int(threadIdx.x);
+        const double total = waveSum(((q[l] + q[l + 64]) + q[l + 128]) + q[l + 192]);
+        if (l == 0) *quad += total;
+    }
+}
+
+// One workgroup: g = the workgroups' tables added; W = K g per row; *quad += the sum over the rows of g[r] . W[r] (quad may be NULL)
 __global__ __launch_bounds__(kCoupleSumThreads) void coupleSumKernel(int bodies, int nblocks, const double *__restrict__ partials,
                                                                      const double *__restrict__ K, double *__restrict__ g, double *__restrict__ W,
                                                                      double *quad)
@@ -2733,15 +2796,7 @@ __global__ __launch_bounds__(kCoupleSumThreads) void coupleSumKernel(int bodies,
     extern __shared__ double coupleRows[];  // (bodies + 1) * 6, then 256 slots of q
     const int n6 = (bodies + 1) * 6, entries = (bodies + 1) * kForceCols;
     for (int e = int(threadIdx.x); e < n6; e += kCoupleSumThreads) {
-        const double *at = partials + (e / 6) * kForceCols + e % 6;
-        double sum = 0.0;
-        for (int b = 0; b < nblocks; b += 16) {
-            double v[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = b + q < nblocks ? at[size_t(b + q) * entries] : 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) sum += v[q];
-        }
+        const double sum = coupleTableSum(partials, e, nblocks, entries);
         coupleRows[e] = sum;
         g[e] = sum;
     }
@@ -2749,26 +2804,27 @@ __global__ __launch_bounds__(kCoupleSumThreads) void coupleSumKernel(int bodies,
     if (threadIdx.x < 256) q[threadIdx.x] = 0.0;
     __syncthreads();
     const int r = int(threadIdx.x);  // (bodies <= 255: a thread per row; row 0 has K = 0)
-    if (r <= bodies) {
-        const double *gr = coupleRows + 6 * r, *k = K + size_t(kCoupleK) * r;
-        const double w[6] = {k[0] * gr[0], k[0] * gr[1], k[0] * gr[2],
-                             k[1] * gr[3] + k[4] * gr[4] + k[5] * gr[5],
-                             k[4] * gr[3] + k[2] * gr[4] + k[6] * gr[5],
-                             k[5] * gr[3] + k[6] * gr[4] + k[3] * gr[5]};
-        double qr = 0.0;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) {
-            W[6 * r + c] = w[c];
-            qr += gr[c] * w[c];
-        }
-        q[r] = qr;
-    }
+    if (r <= bodies) q[r] = coupleRowProduct(coupleRows + 6 * r, K + size_t(kCoupleK) * r, W + 6 * r);
     __syncthreads();
-    if (threadIdx.x < 64 && quad) {  // (one wave: four rows per lane in order, then the butterfly)
-        const int l = int(threadIdx.x);
-        const double total = waveSum(((q[l] + q[l + 64]) + q[l + 128]) + q[l + 192]);
-        if (l == 0) *quad += total;
-    }
+    coupleQuadSum(q, quad);
+}
+// Slab ranks, in front of the all-reduce: g = this rank's share, the workgroups' tables added (nblocks = 0, an empty list: zeros)
+__global__ __launch_bounds__(kCoupleSumThreads) void coupleRankSumKernel(int bodies, int nblocks, const double *__restrict__ partials,
+                                                                         double *__restrict__ g)
+{
+    const int n6 = (bodies + 1) * 6, entries = (bodies + 1) * kForceCols;
+    for (int e = int(threadIdx.x); e < n6; e += kCoupleSumThreads) g[e] = coupleTableSum(partials, e, nblocks, entries);
+}
+// Slab ranks, behind it: g is the whole grid's; W = K g per row; *quad += g^T K g (quad: NULL on every rank but one, the solver
+// sums its scalar over the ranks)
+__global__ __launch_bounds__(256) void coupleRowsKernel(int bodies, const double *__restrict__ K, const double *__restrict__ g,
+                                                        double *__restrict__ W, double *quad)
+{
+    __shared__ double q[256];
+    const int r = int(threadIdx.x);
+    q[r] = r <= bodies ? coupleRowProduct(g + 6 * r, K + size_t(kCoupleK) * r, W + 6 * r) : 0.0;
+    __syncthreads();
+    coupleQuadSum(q, quad);
 }
 
 // target[c] = T(double(target[c]) + sign * (G W)_c) on the list's cells.  (G K G^T x = - G W with W = K g, g = - G^T x: sign = -1 adds
@@ -2828,21 +2884,33 @@ __global__ __launch_bounds__(kCoupleThreads) void coupleCorrKernel(int n, const 
     }
 }
 
-// sv[f] = float((U_r + omega_r x (x_f - centres[r]))_axis) on the faces of row r >= 1 of one axis
-__global__ void rigidVelocityKernel(Box g, int axis, float *__restrict__ sv, const int32_t *__restrict__ body, const double *__restrict__ centres,
-                                    const double *__restrict__ motions, int bodies)
+// sv[f] = float((U_r + omega_r x (x_f - centres[r]))_axis) on the faces of row r >= 1 of one axis; g: the box the face grids are
+// indexed in, plane 0 of which is plane k0 of the whole grid
+__device__ __forceinline__ void rigidVelocityFace(const Box &g, int k0, int axis, float *__restrict__ sv, const int32_t *__restrict__ body,
+                                                  const double *__restrict__ centres, const double *__restrict__ motions, int bodies)
 {
     int i, j, k;
     if (!unflatten(g.gx + (axis == 0), g.gy + (axis == 1), g.gz + (axis == 2), i, j, k)) return;
     const size_t f = faceAt(g, axis, i, j, k);
     const int r = body[f];
     if (r < 1 || r > bodies) return;
+    k += k0;
     double pos[3] = {i + 0.5, j + 0.5, k + 0.5};
     const int ijk[3] = {i, j, k};
     pos[axis] = double(ijk[axis]);
     const int u = (axis + 1) % 3, v = (axis + 2) % 3;
     const double *m = motions + 6 * r, *c = centres + 3 * r;
     sv[f] = float(m[axis] + m[3 + u] * (pos[v] - c[v]) - m[3 + v] * (pos[u] - c[u]));
+}
+__global__ void rigidVelocityKernel(Box g, int axis, float *__restrict__ sv, const int32_t *__restrict__ body, const double *__restrict__ centres,
+                                    const double *__restrict__ motions, int bodies)
+{
+    rigidVelocityFace(g, 0, axis, sv, body, centres, motions, bodies);
+}
+__global__ void rigidVelocityWindowKernel(Box g, int k0, int axis, float *__restrict__ sv, const int32_t *__restrict__ body,
+                                          const double *__restrict__ centres, const double *__restrict__ motions, int bodies)
+{
+    rigidVelocityFace(g, k0, axis, sv, body, centres, motions, bodies);
 }
 
 template <class T>
@@ -2888,6 +2956,13 @@ struct mgps_coupling {
     CoupleBuf<double> tables;    // [centres (b + 1) * 3 | K (b + 1) * 7 | g (b + 1) * 6 | W (b + 1) * 6]
     CoupleBuf<double> partials;  // gather: kCoupleBlocksMax tables; behind them the scatter's per-workgroup corrections
     std::vector<double> K;       // host: what the device holds (mgps_coupling_velocities forms K g on the host)
+    // a slab coupling (mgps_coupling_create_slab): the list holds the rank's own cells as indices of its e1 - e0 expanded planes, and
+    // g is summed over the ranks of `cm` in every application
+    bool slab = false;
+    int e0 = 0, e1 = 0;          // the owned expanded planes (ez: the whole grid's)
+    mgps_comm cm{};              // the caller's transport at full size, as SlabCall::open keeps it
+    std::vector<double> gHost;   // (a transport without allreduce_device: g goes through the host)
+    bool collective() const { return slab && cm.size > 1; }
     int gatherBlocks() const { return std::min(kCoupleBlocksMax, (count + kCoupleThreads - 1) / kCoupleThreads); }
     int scatterBlocks() const { return (count + kCoupleThreads - 1) / kCoupleThreads; }
     size_t rows3() const { return size_t(bodies + 1) * 3; }
@@ -2896,7 +2971,7 @@ struct mgps_coupling {
     double *g() const { return Kdev() + size_t(bodies + 1) * kCoupleK; }
     double *W() const { return g() + size_t(bodies + 1) * 6; }
     double *corr() const { return partials.p + size_t(kCoupleBlocksMax) * (bodies + 1) * kForceCols; }
-    CoupleList list() const { return CoupleList{count, bodies, ex, ey, offset, cell.p, rows.p, sg.p, centres()}; }
+    CoupleList list() const { return CoupleList{count, bodies, ex, ey, offset, e0, cell.p, rows.p, sg.p, centres()}; }
 };
 
 namespace {
@@ -2915,14 +2990,41 @@ int coupleUpload(const char *fn, mgps_coupling *c, const double *centres, const 
     return coupleHip(fn, hipStreamSynchronize(st));  // (`host` leaves scope)
 }
 
-// gather + sum: g and W = K g on the device; *quad += g^T K g (quad may be NULL).  Nothing to do on an empty list (g, W stay 0)
+// What a step of an application returns: 0, a hipError_t, or this when a call of the transport failed (MGPS_ERR_COMM to the caller)
+constexpr int kCoupleCommFailed = mgps::kCouplingCommFailed;
+
+// g on the device summed over the ranks, in place: on the stream where the transport can, through the host otherwise (as the
+// solver's encSumOverRanks).  Every rank of a slab coupling comes here once per application, whatever its list holds
+int coupleSumOverRanks(mgps_coupling *c, hipStream_t st)
+{
+    const int n = (c->bodies + 1) * 6;
+    if (c->cm.allreduce_device) return c->cm.allreduce_device(c->cm.user, c->g(), n, 0, st) == 0 ? 0 : kCoupleCommFailed;
+    c->gHost.resize(size_t(n));
+    if (hipError_t e = hipMemcpyAsync(c->gHost.data(), c->g(), size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st); e != hipSuccess) return int(e);
+    if (hipError_t e = hipStreamSynchronize(st); e != hipSuccess) return int(e);
+    if (c->cm.allreduce(c->cm.user, c->gHost.data(), n, 0) != 0) return kCoupleCommFailed;
+    if (hipError_t e = hipMemcpyAsync(c->g(), c->gHost.data(), size_t(n) * sizeof(double), hipMemcpyHostToDevice, st); e != hipSuccess) return int(e);
+    return int(hipStreamSynchronize(st));
+}
+
+// gather + sum: g and W = K g on the device; *quad += g^T K g (quad may be NULL).  One device, or a world of one: nothing to do on
+// an empty list (g, W stay 0).  Slab ranks: the sum stage in two halves around the all-reduce of g, and an empty list still takes
+// part in it; g^T K g, a number of the whole grid, is added on rank 0 only (the solver sums its scalar over the ranks)
 template <class X>
 int coupleGather(mgps_coupling *c, hipStream_t st, const X *x, double *quad)
 {
-    if (c->count == 0) return 0;
     const int nb = c->gatherBlocks(), entries = (c->bodies + 1) * kForceCols;
-    coupleGatherKernel<X><<<nb, kCoupleThreads, size_t(kCoupleWaves) * entries * sizeof(double), st>>>(c->list(), x, c->partials.p);
-    coupleSumKernel<<<1, kCoupleSumThreads, (size_t(c->bodies + 1) * 6 + 256) * sizeof(double), st>>>(c->bodies, nb, c->partials.p, c->Kdev(), c->g(), c->W(), quad);
+    if (!c->collective()) {
+        if (c->count == 0) return 0;
+        coupleGatherKernel<X><<<nb, kCoupleThreads, size_t(kCoupleWaves) * entries * sizeof(double), st>>>(c->list(), x, c->partials.p);
+        coupleSumKernel<<<1, kCoupleSumThreads, (size_t(c->bodies + 1) * 6 + 256) * sizeof(double), st>>>(c->bodies, nb, c->partials.p, c->Kdev(), c->g(), c->W(), quad);
+        return int(hipGetLastError());
+    }
+    if (c->count > 0) coupleGatherKernel<X><<<nb, kCoupleThreads, size_t(kCoupleWaves) * entries * sizeof(double), st>>>(c->list(), x, c->partials.p);
+    coupleRankSumKernel<<<1, kCoupleSumThreads, 0, st>>>(c->bodies, nb, c->partials.p, c->g());
+    if (int e = int(hipGetLastError())) return e;
+    if (int e = coupleSumOverRanks(c, st)) return e;
+    coupleRowsKernel<<<1, 256, 0, st>>>(c->bodies, c->Kdev(), c->g(), c->W(), c->cm.rank == 0 ? quad : nullptr);
     return int(hipGetLastError());
 }
 template <class T>
@@ -2934,10 +3036,117 @@ int coupleScatter(mgps_coupling *c, hipStream_t st, double sign, T *target, floa
     if (norm2) coupleCorrKernel<<<1, kCoupleThreads, 0, st>>>(nb, c->corr(), norm2);
     return int(hipGetLastError());
 }
+// the rigid velocity on the face grids of box g: the whole grid (win NULL), or a rank's window of it
+int runRigidVelocity(const char *fn, const Box &g, const Slab *win, float *const sv[3], const int32_t *const body[3], const double *centresHost,
+                     const double *motionsHost, int bodies, hipStream_t st)
+{
+    if (!sv[0] || !sv[1] || !sv[2]) return refuse(fn, "solid velocity: three grids are required");
+    if (!body[0] || !body[1] || !body[2]) return refuse(fn, "body: three grids are required");
+    if (!centresHost) return refuse(fn, "centres_host is NULL");
+    if (!motionsHost) return refuse(fn, "motions_host is NULL");
+    const size_t nc = size_t(bodies + 1) * 3, nm = size_t(bodies + 1) * 6;
+    DevPool pool;
+    double *dev = nullptr;  // [centres | motions]
+    try {
+        dev = pool.get<double>(nc + nm);
+    } catch (const std::bad_alloc &) {
+        setLastGlobalError(std::string(fn) + ": device allocation failed");
+        return MGPS_ERR_ALLOC;
+    }
+    if (int rc = coupleHip(fn, hipMemcpyAsync(dev, centresHost, nc * sizeof(double), hipMemcpyHostToDevice, st)); rc != MGPS_OK) return rc;
+    if (int rc = coupleHip(fn, hipMemcpyAsync(dev + nc, motionsHost, nm * sizeof(double), hipMemcpyHostToDevice, st)); rc != MGPS_OK) return rc;
+    for (int a = 0; a < 3; ++a) {
+        const unsigned nb = blocks(faceCount(g.gx, g.gy, g.gz, a));
+        if (win) rigidVelocityWindowKernel<<<nb, 256, 0, st>>>(g, win->c0, a, sv[a], body[a], dev, dev + nc, bodies);
+        else rigidVelocityKernel<<<nb, 256, 0, st>>>(g, a, sv[a], body[a], dev, dev + nc, bodies);
+    }
+    return coupleHip(fn, hipGetLastError());
+}
+
+// what both constructors refuse of a desc, before any device work
+int coupleCheckDesc(const char *fn, const mgps_coupling_desc *d, bool wholeGrid)
+{
+    if (!d || d->struct_size != int(sizeof(mgps_coupling_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_coupling_desc)");
+    if (int rc = forceCheckBodies(fn, d->bodies); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, d->gx, d->gy, d->gz); rc != MGPS_OK) return rc;
+    if (int rc = exCheckExtents(fn, d->ex, d->ey, d->ez); rc != MGPS_OK) return rc;
+    if (d->offset < 0 || d->gx + d->offset > d->ex || d->gy + d->offset > d->ey || d->gz + d->offset > d->ez)
+        return refuse(fn, "the expanded box does not hold the base grid at this offset");
+    // (the list's indices are int32: of the whole expanded grid here, of the rank's planes on a slab, checked with the window)
+    if (wholeGrid && size_t(d->ex) * d->ey * d->ez > size_t(0x7fffffff)) return refuse(fn, "more than 2^31 - 1 expanded cells");
+    if (!d->material) return refuse(fn, "material is NULL");
+    if (!d->cut_weights[0] || !d->cut_weights[1] || !d->cut_weights[2]) return refuse(fn, "cut weights: three grids are required");
+    if (!d->body[0] || !d->body[1] || !d->body[2]) return refuse(fn, "body: three grids are required");
+    return coupleCheckBodies(fn, d->bodies, d->centres, d->inv_mass, d->inv_inertia);
+}
+
+// The object from a checked desc: count, scan, fill, tables.  win: NULL for whole grids; else the rank's window -- the desc's grids
+// hold its planes, the list its own cells as indices of its e1 - e0 expanded planes
+int coupleBuild(const char *fn, mgps_coupling **out, const mgps_coupling_desc *d, const Slab *win, hipStream_t st)
+{
+    std::unique_ptr<mgps_coupling> c(new mgps_coupling);
+    c->bodies = d->bodies;
+    c->ex = d->ex, c->ey = d->ey, c->ez = d->ez, c->offset = d->offset;
+    c->e1 = d->ez;
+    CoupleGrids p{Box{d->gx, d->gy, d->gz}, Box{d->ex, d->ey, d->ez}, d->offset, d->offset, d->bodies, d->material, {d->cut_weights[0], d->cut_weights[1], d->cut_weights[2]},
+                  {d->body[0], d->body[1], d->body[2]}};
+    if (win) {
+        c->slab = true;
+        c->e0 = win->e0, c->e1 = win->e1;
+        p.g = win->base(), p.e = win->window();
+        p.zoff = win->c0 + win->off - win->e0;  // (base plane c0 is expanded plane c0 + offset of the whole grid)
+    }
+    const size_t nblocks = (p.g.cells() + kCoupleThreads - 1) / kCoupleThreads;
+    if (nblocks > size_t(0x7fffffff)) return refuse(fn, "the base grid is too large");
+    const auto noMemory = [&] {
+        setLastGlobalError(std::string(fn) + ": device allocation failed");
+        return MGPS_ERR_ALLOC;
+    };
+    {
+        CoupleBuf<int32_t> blockCount, blockStart, scratch;
+        if (blockCount.get(nblocks) || blockStart.get(nblocks + 1) || scratch.get(scanScratchInts(nblocks))) return noMemory();
+        if (win) coupleCountWindowKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockCount.p);
+        else coupleCountKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockCount.p);
+        if (int rc = coupleHip(fn, hipGetLastError()); rc != MGPS_OK) return rc;
+        if (int e = launchExclusiveScan(st, blockCount.p, blockStart.p, nblocks, scratch.p)) return coupleHip(fn, hipError_t(e));
+        int32_t total = 0;
+        if (int rc = coupleHip(fn, hipMemcpyAsync(&total, blockStart.p + nblocks, sizeof(total), hipMemcpyDeviceToHost, st)); rc != MGPS_OK) return rc;
+        if (int rc = coupleHip(fn, hipStreamSynchronize(st)); rc != MGPS_OK) return rc;
+        c->count = total;
+        const size_t n = size_t(std::max(total, 1)), tab = size_t(d->bodies + 1);
+        if (c->cell.get(n) || c->rows.get(6 * n) || c->sg.get(6 * n) || c->tables.get(tab * (3 + kCoupleK + 6 + 6)) ||
+            c->partials.get(size_t(kCoupleBlocksMax) * tab * kForceCols + size_t(c->scatterBlocks()) + 1))
+            return noMemory();
+        if (total > 0) {
+            if (win) coupleFillWindowKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockStart.p, total, c->cell.p, c->rows.p, c->sg.p);
+            else coupleFillKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockStart.p, total, c->cell.p, c->rows.p, c->sg.p);
+        }
+        if (int rc = coupleHip(fn, hipGetLastError()); rc != MGPS_OK) return rc;
+        if (int rc = coupleHip(fn, hipMemsetAsync(c->tables.p, 0, tab * (3 + kCoupleK + 6 + 6) * sizeof(double), st)); rc != MGPS_OK) return rc;
+        if (int rc = coupleHip(fn, hipStreamSynchronize(st)); rc != MGPS_OK) return rc;  // (the scan's buffers leave scope)
+    }
+    if (int rc = coupleUpload(fn, c.get(), d->centres, d->inv_mass, d->inv_inertia, st); rc != MGPS_OK) return rc;
+    *out = c.release();
+    return MGPS_OK;
+}
+
+// the status of a public entry from what a step returned
+int coupleStatus(const char *fn, int e)
+{
+    if (e != kCoupleCommFailed) return coupleHip(fn, hipError_t(e));
+    setLastGlobalError(std::string(fn) + ": all-reduce failed (the impulses g)");
+    return MGPS_ERR_COMM;
+}
 }  // namespace
 
 namespace mgps {
 void couplingExtents(const mgps_coupling *c, int e[3]) { e[0] = c->ex, e[1] = c->ey, e[2] = c->ez; }
+bool couplingOnSlab(const mgps_coupling *c, int planes[2], int *rank, int *size)
+{
+    planes[0] = c->e0, planes[1] = c->e1;
+    *rank = c->cm.rank, *size = c->cm.size;
+    return c->slab;
+}
 int couplingApply64(mgps_coupling *c, void *stream, double *t, const double *p, double *dotDev)
 {
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2960,27 +3169,22 @@ try {
     const char *fn = "mgps_fields_rigid_velocity";
     if (int rc = forceCheckBodies(fn, bodies); rc != MGPS_OK) return rc;
     if (int rc = exCheckExtents(fn, gx, gy, gz); rc != MGPS_OK) return rc;
-    if (!svx || !svy || !svz) return refuse(fn, "solid velocity: three grids are required");
-    if (!bx || !by || !bz) return refuse(fn, "body: three grids are required");
-    if (!centres_host) return refuse(fn, "centres_host is NULL");
-    if (!motions_host) return refuse(fn, "motions_host is NULL");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t nc = size_t(bodies + 1) * 3, nm = size_t(bodies + 1) * 6;
-    DevPool pool;
-    double *dev = nullptr;  // [centres | motions]
-    try {
-        dev = pool.get<double>(nc + nm);
-    } catch (const std::bad_alloc &) {
-        setLastGlobalError(std::string(fn) + ": device allocation failed");
-        return MGPS_ERR_ALLOC;
-    }
-    if (int rc = coupleHip(fn, hipMemcpyAsync(dev, centres_host, nc * sizeof(double), hipMemcpyHostToDevice, st)); rc != MGPS_OK) return rc;
-    if (int rc = coupleHip(fn, hipMemcpyAsync(dev + nc, motions_host, nm * sizeof(double), hipMemcpyHostToDevice, st)); rc != MGPS_OK) return rc;
-    const Box g{gx, gy, gz};
     float *sv[3] = {svx, svy, svz};
     const int32_t *body[3] = {bx, by, bz};
-    for (int a = 0; a < 3; ++a) rigidVelocityKernel<<<blocks(faceCount(gx, gy, gz, a)), 256, 0, st>>>(g, a, sv[a], body[a], dev, dev + nc, bodies);
-    return coupleHip(fn, hipGetLastError());
+    return runRigidVelocity(fn, Box{gx, gy, gz}, nullptr, sv, body, centres_host, motions_host, bodies, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_rigid_velocity(const mgps_fields_slab *d, float *const sv[3], const int32_t *const body[3], const double *centres_host,
+                                    const double *motions_host, int bodies, void *stream)
+try {
+    const char *fn = "mgps_fields_slab_rigid_velocity";
+    Slab s;
+    if (!readSlab(d, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    if (int rc = forceCheckBodies(fn, bodies); rc != MGPS_OK) return rc;
+    if (!sv) return refuse(fn, "solid velocity: three grids are required");
+    if (!body) return refuse(fn, "body: three grids are required");
+    return runRigidVelocity(fn, s.base(), &s, sv, body, centres_host, motions_host, bodies, static_cast<hipStream_t>(stream));
 }
 MGPS_API_CATCH(nullptr)
 
@@ -2989,51 +3193,31 @@ try {
     const char *fn = "mgps_coupling_create";
     if (!out) return refuse(fn, "out is NULL");
     *out = nullptr;
-    if (!d || d->struct_size != int(sizeof(mgps_coupling_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_coupling_desc)");
-    if (int rc = forceCheckBodies(fn, d->bodies); rc != MGPS_OK) return rc;
-    if (int rc = exCheckExtents(fn, d->gx, d->gy, d->gz); rc != MGPS_OK) return rc;
-    if (int rc = exCheckExtents(fn, d->ex, d->ey, d->ez); rc != MGPS_OK) return rc;
-    if (d->offset < 0 || d->gx + d->offset > d->ex || d->gy + d->offset > d->ey || d->gz + d->offset > d->ez)
-        return refuse(fn, "the expanded box does not hold the base grid at this offset");
-    if (size_t(d->ex) * d->ey * d->ez > size_t(0x7fffffff)) return refuse(fn, "more than 2^31 - 1 expanded cells");
-    if (!d->material) return refuse(fn, "material is NULL");
-    if (!d->cut_weights[0] || !d->cut_weights[1] || !d->cut_weights[2]) return refuse(fn, "cut weights: three grids are required");
-    if (!d->body[0] || !d->body[1] || !d->body[2]) return refuse(fn, "body: three grids are required");
-    if (int rc = coupleCheckBodies(fn, d->bodies, d->centres, d->inv_mass, d->inv_inertia); rc != MGPS_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    std::unique_ptr<mgps_coupling> c(new mgps_coupling);
-    c->bodies = d->bodies;
-    c->ex = d->ex, c->ey = d->ey, c->ez = d->ez, c->offset = d->offset;
-    CoupleGrids p{Box{d->gx, d->gy, d->gz}, Box{d->ex, d->ey, d->ez}, d->offset, d->bodies, d->material, {d->cut_weights[0], d->cut_weights[1], d->cut_weights[2]},
-                  {d->body[0], d->body[1], d->body[2]}};
-    const size_t nblocks = (p.g.cells() + kCoupleThreads - 1) / kCoupleThreads;
-    if (nblocks > size_t(0x7fffffff)) return refuse(fn, "the base grid is too large");
-    const auto noMemory = [&] {
-        setLastGlobalError(std::string(fn) + ": device allocation failed");
-        return MGPS_ERR_ALLOC;
-    };
-    {
-        CoupleBuf<int32_t> blockCount, blockStart, scratch;
-        if (blockCount.get(nblocks) || blockStart.get(nblocks + 1) || scratch.get(scanScratchInts(nblocks))) return noMemory();
-        coupleCountKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockCount.p);
-        if (int rc = coupleHip(fn, hipGetLastError()); rc != MGPS_OK) return rc;
-        if (int e = launchExclusiveScan(st, blockCount.p, blockStart.p, nblocks, scratch.p)) return coupleHip(fn, hipError_t(e));
-        int32_t total = 0;
-        if (int rc = coupleHip(fn, hipMemcpyAsync(&total, blockStart.p + nblocks, sizeof(total), hipMemcpyDeviceToHost, st)); rc != MGPS_OK) return rc;
-        if (int rc = coupleHip(fn, hipStreamSynchronize(st)); rc != MGPS_OK) return rc;
-        c->count = total;
-        const size_t n = size_t(std::max(total, 1)), tab = size_t(d->bodies + 1);
-        if (c->cell.get(n) || c->rows.get(6 * n) || c->sg.get(6 * n) || c->tables.get(tab * (3 + kCoupleK + 6 + 6)) ||
-            c->partials.get(size_t(kCoupleBlocksMax) * tab * kForceCols + size_t(c->scatterBlocks()) + 1))
-            return noMemory();
-        if (total > 0) coupleFillKernel<<<unsigned(nblocks), kCoupleThreads, 0, st>>>(p, blockStart.p, total, c->cell.p, c->rows.p, c->sg.p);
-        if (int rc = coupleHip(fn, hipGetLastError()); rc != MGPS_OK) return rc;
-        if (int rc = coupleHip(fn, hipMemsetAsync(c->tables.p, 0, tab * (3 + kCoupleK + 6 + 6) * sizeof(double), st)); rc != MGPS_OK) return rc;
-        if (int rc = coupleHip(fn, hipStreamSynchronize(st)); rc != MGPS_OK) return rc;  // (the scan's buffers leave scope)
-    }
-    if (int rc = coupleUpload(fn, c.get(), d->centres, d->inv_mass, d->inv_inertia, st); rc != MGPS_OK) return rc;
-    *out = c.release();
-    return MGPS_OK;
+    if (int rc = coupleCheckDesc(fn, d, true); rc != MGPS_OK) return rc;
+    return coupleBuild(fn, out, d, nullptr, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_coupling_create_slab(mgps_coupling **out, const mgps_coupling_desc *d, const mgps_fields_slab *window, const mgps_comm *comm, void *stream)
+try {
+    const char *fn = "mgps_coupling_create_slab";
+    if (!out) return refuse(fn, "out is NULL");
+    *out = nullptr;
+    if (int rc = coupleCheckDesc(fn, d, false); rc != MGPS_OK) return rc;
+    Slab s;
+    if (!readSlab(window, s, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    if (s.gx != d->gx || s.gy != d->gy || s.gz != d->gz || s.ex != d->ex || s.ey != d->ey || s.ez != d->ez || s.off != d->offset)
+        return refuse(fn, "the window does not match the desc (gx .. ez and offset are the whole grid's in both)");
+    if (size_t(s.ex) * s.ey * size_t(s.e1 - s.e0) > size_t(0x7fffffff)) return refuse(fn, "more than 2^31 - 1 expanded cells in the window");
+    if (!comm || comm->struct_size < int(offsetof(mgps_comm, gather)) || comm->struct_size > int(sizeof(mgps_comm)) || !comm->exchange || !comm->allreduce ||
+        comm->size < 1 || comm->rank < 0 || comm->rank >= comm->size)
+        return refuse(fn, "comm: a mgps_comm with exchange and allreduce is required");
+    mgps_comm cm{};
+    std::memcpy(&cm, comm, size_t(comm->struct_size));  // (members behind the caller's struct_size read as NULL)
+    cm.struct_size = int(sizeof(mgps_comm));
+    const int rc = coupleBuild(fn, out, d, &s, static_cast<hipStream_t>(stream));
+    if (rc == MGPS_OK) (*out)->cm = cm;
+    return rc;
 }
 MGPS_API_CATCH(nullptr)
 
@@ -3066,7 +3250,7 @@ try {
     if (!c) return refuse(fn, "NULL coupling");
     if (!y_dev || !x_dev) return refuse(fn, "NULL grid");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int e = coupleGather(c, st, x_dev, static_cast<double *>(nullptr))) return coupleHip(fn, hipError_t(e));
+    if (int e = coupleGather(c, st, x_dev, static_cast<double *>(nullptr))) return coupleStatus(fn, e);
     return coupleHip(fn, hipError_t(coupleScatter<float>(c, st, -1.0, y_dev, nullptr, nullptr)));
 }
 MGPS_API_CATCH(nullptr)
@@ -3080,8 +3264,8 @@ try {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t n = size_t(c->bodies + 1) * 6;
     std::fill(out_host, out_host + n, 0.0);
-    if (c->count == 0) return coupleHip(fn, hipStreamSynchronize(st));
-    if (int e = coupleGather(c, st, x_dev, static_cast<double *>(nullptr))) return coupleHip(fn, hipError_t(e));
+    if (c->count == 0 && !c->collective()) return coupleHip(fn, hipStreamSynchronize(st));  // (an empty rank still joins the all-reduce)
+    if (int e = coupleGather(c, st, x_dev, static_cast<double *>(nullptr))) return coupleStatus(fn, e);
     if (int rc = coupleHip(fn, hipMemcpyAsync(out_host, c->g(), n * sizeof(double), hipMemcpyDeviceToHost, st)); rc != MGPS_OK) return rc;
     return coupleHip(fn, hipStreamSynchronize(st));
 }

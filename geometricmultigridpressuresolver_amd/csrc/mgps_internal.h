@@ -614,10 +614,18 @@ int launchUnpack(void *stream, float *a, const float *buf, const int32_t *idx, i
 // ---- the rigid-body coupling (mgps_fields.hip) as pcg64 sees it: fp64 grids of the expanded extents ----------
 struct mgps_coupling;
 namespace mgps {
-void couplingExtents(const mgps_coupling *c, int e[3]);
+void couplingExtents(const mgps_coupling *c, int e[3]);  // the whole expanded grid's
+// true for a slab coupling (mgps_coupling_create_slab); planes: the expanded planes [e0, e1) its list and grids cover, rank / size:
+// its transport's
+bool couplingOnSlab(const mgps_coupling *c, int planes[2], int *rank, int *size);
+// Both return 0, a hipError_t, or kCouplingCommFailed.  A slab coupling over more than one rank makes them collectives: one sum
+// all-reduce of g per call, on every rank whatever its list holds; the grids are then the rank's e1 - e0 planes.
+constexpr int kCouplingCommFailed = -1;
 // t += G K G^T p over the coupled cells and *dotDev += g^T K g (g = - G^T p): <p, A p> becomes <p, (A + G K G^T) p>.  Three launches
+// (slab ranks: four around the all-reduce, and g^T K g is added on rank 0 alone -- the solver sums *dotDev over the ranks)
 int couplingApply64(mgps_coupling *c, void *stream, double *t, const double *p, double *dotDev);
-// r -= G K G^T x, r32 = float(r) on the coupled cells, *norm2Dev += the fp64 sum of new^2 - old^2 over them.  Four launches
+// r -= G K G^T x, r32 = float(r) on the coupled cells, *norm2Dev += the fp64 sum of new^2 - old^2 over them (slab ranks: over the
+// rank's own cells, summed with *norm2Dev over the ranks).  Four launches (slab ranks: five)
 int couplingResidual64(mgps_coupling *c, void *stream, double *r, const double *x, float *r32, double *norm2Dev);
 }  // namespace mgps
 

@@ -222,6 +222,13 @@ int failH(mgps_solver *h, int code, const std::string &msg)
         int s_ = (call);                                                             \
         if (s_ != 0) return failH(h, MGPS_ERR_COMM, std::string(#call) + " failed"); \
     } while (0)
+// a pass of the rigid-body coupling: launches, and on slab ranks the all-reduce of its impulses (mgps_internal.h)
+#define MGPS_COUPLE(h, call)                                                                                                     \
+    do {                                                                                                                         \
+        int e_ = (call);                                                                                                         \
+        if (e_ == mgps::kCouplingCommFailed) return failH(h, MGPS_ERR_COMM, std::string(#call) + ": the all-reduce of g failed"); \
+        if (e_ != 0) return failH(h, MGPS_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(hipError_t(e_)));              \
+    } while (0)
 
 
 // ---- device memory of the library -------------------------------------------------------------------------------------
@@ -1564,7 +1571,9 @@ struct PcgExit {
 // MG-PCG with the CG vectors in fp64 (options.pcg_fp64_vectors): CG.h:18-207 step by step like pcg() below; the
 // preconditioner is the same fp32 V-cycle (or diagonal) applied to float(r), x and b are fp32 at the boundary.
 // With h->coupling set (mgps_solve_pcg_coupled) the operator is A + G K G^T: the coupling's list kernels follow
-// the stencil pass at the three places marked below, in front of the fetch of its reduction; without it no launch differs.
+// the stencil pass at the three places marked below, in front of the fetch of its reduction; without it no launch differs.  A slab
+// coupling makes each of the three a collective (one all-reduce of the impulses g): every rank passes them alike, and what they add
+// to resultDev -- g^T K g on rank 0, each rank's own residual corrections -- is summed over the ranks by the fetch that follows.
 int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool useMG, mgps_pcg_stats *st)
 {
     DevLevel &F = h->lv[0];
@@ -1617,7 +1626,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     MGPS_LAUNCH(h, launchWiden(h->stream, x64, x, n));
     MGPS_TRY(exchangeGhosts64(h, x64));
     MGPS_LAUNCH(h, launchStencil64(h->stream, 1, F.g, r64, x64, b, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:50-57
-    if (cpl) MGPS_LAUNCH(h, couplingResidual64(cpl, h->stream, r64, x64, r32, h->resultDev));  // r -= G K G^T x
+    if (cpl) MGPS_COUPLE(h, couplingResidual64(cpl, h->stream, r64, x64, r32, h->resultDev));  // r -= G K G^T x
     MGPS_TRY(fetchReduction(h, 1, &res2));
     const double threshold = tol * tol * rhs2;  // CG.h:58
     if (res2 < threshold) {                     // CG.h:60-64
@@ -1640,7 +1649,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
         double pAp = 0;
         MGPS_TRY(exchangeGhosts64(h, p64));
         MGPS_LAUNCH(h, launchStencil64(h->stream, 0, F.g, t64, p64, nullptr, nullptr, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:110-121
-        if (cpl) MGPS_LAUNCH(h, couplingApply64(cpl, h->stream, t64, p64, h->resultDev));  // t += G K G^T p, <p, A p> += g^T K g
+        if (cpl) MGPS_COUPLE(h, couplingApply64(cpl, h->stream, t64, p64, h->resultDev));  // t += G K G^T p, <p, A p> += g^T K g
         MGPS_TRY(fetchReduction(h, 0, &pAp));
         const double alpha = absNew / pAp;
         MGPS_LAUNCH(h, launchCgUpdate64(h->stream, F.g, x64, p64, r64, t64, alpha, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:132-153
@@ -1660,7 +1669,7 @@ int pcg64(mgps_solver *h, float *x, const float *b, double tol, int maxIt, bool 
     double rec2 = 0;
     MGPS_TRY(exchangeGhosts64(h, x64));
     MGPS_LAUNCH(h, launchStencil64(h->stream, 1, F.g, r64, x64, b, r32, h->dotPartials, h->dotCapacity, h->resultDev));  // CG.h:203-205, in fp64
-    if (cpl) MGPS_LAUNCH(h, couplingResidual64(cpl, h->stream, r64, x64, r32, h->resultDev));
+    if (cpl) MGPS_COUPLE(h, couplingResidual64(cpl, h->stream, r64, x64, r32, h->resultDev));
     MGPS_TRY(fetchReduction(h, 1, &rec2));
     st->rel_residual_recomputed = std::sqrt(rec2 / rhs2);
     return ex.finish(converged ? MGPS_PCG_CONVERGED : MGPS_PCG_MAX_ITERATIONS);
@@ -5082,20 +5091,32 @@ try {
     if (!coupling) return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL coupling");
     if (!x_dev || !b_dev || x_dev == b_dev || !(tolerance >= 0) || max_iterations < 0)
         return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
-    if (h->dist || h->tailOfSlabRun)
-        return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": a slab solver cannot take a coupling (the list lives on one device)");
     if (h->opt.precision == 1)
         return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": not available with options.precision = 1 (mixed precision)");
+    int planes[2], cplRank = 0, cplSize = 1;
+    const bool slabCoupling = couplingOnSlab(coupling, planes, &cplRank, &cplSize), slabSolver = h->dist || h->tailOfSlabRun;
+    if (slabSolver && !slabCoupling)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT,
+                     std::string(fn) + ": a slab solver cannot take a whole-grid coupling (its list lives on one device); make one with mgps_coupling_create_slab");
+    if (!slabSolver && slabCoupling)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": a slab coupling needs the slab solver of its ranks, this solver holds a whole grid");
+    if (h->tailOfSlabRun) return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": the collapsed tail of a slab run takes no coupling");
     if (hasEnclosed(h))
         return failH(h, MGPS_ERR_INVALID_ARGUMENT,
                      std::string(fn) + ": the solver has an enclosed liquid component (options.enclosed_liquid); a moving body changes its null space");
     int e[3];
     couplingExtents(coupling, e);
     const Dims &d = h->lv[0].d;
-    if (e[0] != d.nx || e[1] != d.ny || e[2] != d.nz)
+    const int nzWhole = slabSolver ? h->splits.back() : d.nz;
+    if (e[0] != d.nx || e[1] != d.ny || e[2] != nzWhole)
         return failH(h, MGPS_ERR_INVALID_ARGUMENT,
                      std::string(fn) + ": the coupling's expanded extents " + std::to_string(e[0]) + " x " + std::to_string(e[1]) + " x " + std::to_string(e[2]) +
-                         " differ from the solver's " + std::to_string(d.nx) + " x " + std::to_string(d.ny) + " x " + std::to_string(d.nz));
+                         " differ from the solver's " + std::to_string(d.nx) + " x " + std::to_string(d.ny) + " x " + std::to_string(nzWhole));
+    if (slabSolver && (planes[0] != h->lv[0].z0 || planes[1] != h->lv[0].z1 || cplRank != h->comm.rank || cplSize != h->comm.size))
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT,
+                     std::string(fn) + ": the coupling's window, expanded planes " + std::to_string(planes[0]) + " .. " + std::to_string(planes[1]) + " of rank " +
+                         std::to_string(cplRank) + " of " + std::to_string(cplSize) + ", is not this slab solver's (planes " + std::to_string(h->lv[0].z0) + " .. " +
+                         std::to_string(h->lv[0].z1) + " of rank " + std::to_string(h->comm.rank) + " of " + std::to_string(h->comm.size) + ")");
     mgps_pcg_stats local{};
     if (!stats) stats = &local;
     std::memset(stats, 0, sizeof(*stats));

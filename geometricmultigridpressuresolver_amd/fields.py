@@ -649,6 +649,19 @@ def rigidVelocity(solid_velocity, body, centres, motions):
     return solid_velocity
 
 
+def rigidVelocitySlab(d, solid_velocity, body, centres, motions):
+    """mgps_fields_slab_rigid_velocity: rigidVelocity on the window `d` (in place on the window's three face grids; positions use the
+    whole grid's plane index): the bits of the whole-grid pass on the rank's planes.  No communication."""
+    faces = _face3(d.base_shape)
+    sv = [_chk(solid_velocity[a], faces[a], torch.float32) for a in range(3)]
+    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
+    c, bodies = _centres(centres)
+    m = _table(motions, bodies, 6, "motions")
+    check(lib().mgps_fields_slab_rigid_velocity(C.byref(d), _arr3(sv), _arr3(ids), c.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p),
+                                                int(bodies), _stream()))
+    return solid_velocity
+
+
 class CouplingDesc(C.Structure):
     """mgps_coupling_desc (include/mgps_fields.h)."""
 
@@ -662,26 +675,50 @@ class CouplingDesc(C.Structure):
 
 class RigidCoupling:
     """mgps_coupling: the operator G K G^T of the bodies `body` / `centres` / `inv_mass` (bodies + 1) / `inv_inertia` (bodies + 1, 6:
-    xx, yy, zz, xy, xz, yz) on the coupled cells of the base grids, for expanded grids of `expanded_shape` at `offset`."""
+    xx, yy, zz, xy, xz, yz) on the coupled cells of the base grids, for expanded grids of `expanded_shape` at `offset`.
+
+    RigidCoupling.on_slab makes the object of one rank of a slab run: its list holds the rank's own coupled cells, its grids are the
+    rank's windows, and apply, impulses and velocities are collectives (every rank calls them together)."""
 
     def __init__(self, material, cut_cell_weights, body, centres, inv_mass, inv_inertia, expanded_shape, offset):
         shape = tuple(material.shape)
-        faces = _face3(shape)
+        d, keep = self._desc(shape, shape, expanded_shape, offset, material, cut_cell_weights, body, centres, inv_mass, inv_inertia)
+        self.h = C.c_void_p()
+        check(lib().mgps_coupling_create(C.byref(self.h), C.byref(d), _stream()))
+        self.bodies, self.expanded_shape, self.offset, self.device = d.bodies, tuple(expanded_shape), int(offset), material.device
+        self.comm = None
+
+    @staticmethod
+    def _desc(grid_shape, array_shape, expanded_shape, offset, material, cut_cell_weights, body, centres, inv_mass, inv_inertia):
+        """the desc of the grid `grid_shape` / `expanded_shape` over arrays of `array_shape` (the grid's, or a window's), and what
+        must stay alive while the library reads it"""
+        faces = _face3(array_shape)
         c, bodies = _centres(centres)
         im, ii = _table(inv_mass, bodies, 1, "inv_mass"), _table(inv_inertia, bodies, 6, "inv_inertia")
         d = CouplingDesc()
         d.struct_size = C.sizeof(CouplingDesc)
-        d.gz, d.gy, d.gx = shape
+        d.gz, d.gy, d.gx = grid_shape
         d.ez, d.ey, d.ex = expanded_shape
         d.offset, d.bodies = int(offset), int(bodies)
-        d.material = _chk(material, shape, torch.int32).data_ptr()
+        d.material = _chk(material, array_shape, torch.int32).data_ptr()
         for a in range(3):
             d.cut_weights[a] = _chk(cut_cell_weights[a], faces[a], torch.float32).data_ptr()
             d.body[a] = _chk(body[a], faces[a], torch.int32).data_ptr()
         d.centres, d.inv_mass, d.inv_inertia = c.ctypes.data, im.ctypes.data, ii.ctypes.data
+        return d, (c, im, ii)
+
+    @classmethod
+    def on_slab(cls, d, comm, material, cut_cell_weights, body, centres, inv_mass, inv_inertia):
+        """mgps_coupling_create_slab: the coupling of the rank whose window is `d` (fields.slab_window) over the transport `comm`;
+        material / cut_cell_weights / body: the window's grids.  No communication here; `comm` is kept alive with the object.  Its
+        expanded grids are the rank's d.expanded_shape planes: the grids of the rank's SlabSolver."""
+        desc, keep = cls._desc((d.gz, d.gy, d.gx), d.base_shape, (d.ez, d.ey, d.ex), d.offset, material, cut_cell_weights, body, centres, inv_mass, inv_inertia)
+        self = cls.__new__(cls)
         self.h = C.c_void_p()
-        check(lib().mgps_coupling_create(C.byref(self.h), C.byref(d), _stream()))
-        self.bodies, self.expanded_shape, self.offset, self.device = bodies, tuple(expanded_shape), int(offset), material.device
+        check(lib().mgps_coupling_create_slab(C.byref(self.h), C.byref(desc), C.byref(d), C.byref(comm.struct), _stream()))
+        self.bodies, self.expanded_shape, self.offset, self.device = desc.bodies, tuple(d.expanded_shape), int(d.offset), material.device
+        self.comm, self.window = comm, d
+        return self
 
     def close(self):
         if getattr(self, "h", None):
@@ -704,17 +741,20 @@ class RigidCoupling:
         check(lib().mgps_coupling_set_bodies(self.h, c.ctypes.data_as(C.c_void_p), im.ctypes.data_as(C.c_void_p), ii.ctypes.data_as(C.c_void_p), _stream()))
 
     def cells(self):
+        """the coupled cells of the list (on a slab: the rank's own)"""
         n = C.c_int64()
         check(lib().mgps_coupling_cells(self.h, C.byref(n)))
         return n.value
 
     def apply(self, y, x):
-        """y += G K G^T x on the coupled cells (expanded float32 grids), in place on y"""
+        """y += G K G^T x on the coupled cells (expanded float32 grids), in place on y.  On a slab coupling a collective: every
+        rank calls it with its window of x and y, and one all-reduce sums the impulses over the ranks"""
         check(lib().mgps_coupling_apply(self.h, self._x(y), self._x(x), _stream()))
         return y
 
     def impulses(self, x):
-        """(bodies + 1, 6) float64: (F, T) = - G^T x per row at scale 1, row 0 zero"""
+        """(bodies + 1, 6) float64: (F, T) = - G^T x per row at scale 1, row 0 zero.  On a slab coupling a collective (one
+        all-reduce): the whole grid's numbers, the same bits on every rank"""
         import numpy as np
 
         out = np.zeros((self.bodies + 1, 6), dtype=np.float64)
@@ -722,7 +762,8 @@ class RigidCoupling:
         return out
 
     def velocities(self, x, motions):
-        """(V_out, impulses): V_out = motions + K (F, T)(x), both (bodies + 1, 6) float64"""
+        """(V_out, impulses): V_out = motions + K (F, T)(x), both (bodies + 1, 6) float64.  On a slab coupling a collective (one
+        all-reduce): the whole grid's numbers, the same bits on every rank"""
         import numpy as np
 
         m = _table(motions, self.bodies, 6, "motions")

@@ -388,7 +388,8 @@ class GeometricMultigridPoissonSolver:
 
     def solve_pcg_coupled(self, coupling, solution, rhs, tolerance=1e-5, max_iterations=2500, use_mg_preconditioner=True):
         """mgps_solve_pcg_coupled: (A + G K G^T) solution = rhs with `coupling` (fields.RigidCoupling) attached for the length of the
-        call; the loop of options.pcg_fp64_vectors = 1 (include/mgps_fields.h)"""
+        call; the loop of options.pcg_fp64_vectors = 1 (include/mgps_fields.h).  A SlabSolver takes the
+        fields.RigidCoupling.on_slab of its own rank; the call is then a collective"""
         st = PcgStats()
         _check_pcg(
             lib().mgps_solve_pcg_coupled(

@@ -402,6 +402,11 @@ int mgps_solid_forces_slab(struct mgps_solid_forces_slab *s, const mgps_comm *co
  * (row 0 is not read); centres_host[(bodies + 1) * 3] as in mgps_fields_solid_forces.  Refuses what that entry refuses. */
 int mgps_fields_rigid_velocity(float *svx, float *svy, float *svz, const int32_t *bx, const int32_t *by, const int32_t *bz,
                                const double *centres_host, const double *motions_host, int bodies, int gx, int gy, int gz, void *stream);
+/* The same on a slab window (no communication): sv / body are the window's face grids, face positions use the plane index of the
+ * whole grid (k + c0).  The bits are those of the whole-grid pass on the rank's planes; both copies of a cut's z-face plane get
+ * the same bits.  Refuses, before any device work: not a slab window, bodies outside 1 .. 255, a NULL array. */
+int mgps_fields_slab_rigid_velocity(const mgps_fields_slab *d, float *const sv[3], const int32_t *const body[3], const double *centres_host,
+                                    const double *motions_host, int bodies, void *stream);
 
 /* The coupling object: the list of COUPLED cells -- LIQUID cells with at least one face of s > 0 and row >= 1 -- made on the device
  * (count, scan, compact) from the base grids; per cell its expanded index and, for its six faces, the row and the signed s (+ on
@@ -425,6 +430,25 @@ typedef struct mgps_coupling_desc {
  * expanded box that does not hold the base grid at `offset` or has 2^31 cells or more, a negative or non-finite inv_mass, a
  * negative or non-finite diagonal entry of inv_inertia.  Synchronises the stream (the list's length comes to the host). */
 int mgps_coupling_create(mgps_coupling **out, const mgps_coupling_desc *d, void *stream);
+/* The coupling of one rank of a slab run ("on slab ranks").  desc->gx .. ez and offset are the WHOLE grid's
+ * and must equal the window's; desc->material, cut_weights and body are the window's device grids (c1 - c0 planes, of the z-faces
+ * c0 .. c1).  The list holds the rank's OWN coupled cells: LIQUID cells of its base planes [c0, c1) with a face of s > 0 and row
+ * >= 1, each with all six faces -- a cell of the last owned plane carries its forward z-face on the cut, whoever holds the cell
+ * across it.  A cell has one owner: the ranks' lists together are the whole grid's list and no face term is counted twice or
+ * dropped.  The stored index is the cell's index in the rank's e1 - e0 expanded planes, the fine level of its slab solver.  No halo
+ * plane is read: the cell is LIQUID, so a face of w < 1 is wet whatever lies across the cut.
+ * Creation does no communication; it copies `comm` (comm->user must outlive the object) for the collectives below.  Refuses, before
+ * any device work: what mgps_coupling_create refuses (the 2^31 limit applies to the window's expanded cells), a window that is not
+ * one or does not match the desc, a comm without exchange and allreduce.
+ * On such an object mgps_coupling_apply, mgps_coupling_impulses and mgps_coupling_velocities are COLLECTIVES: every rank calls them,
+ * with its own window of x (and y), and each makes one sum all-reduce of g, (bodies + 1) * 6 doubles -- on the stream through
+ * comm->allreduce_device where the transport has it, through the host otherwise.  A rank whose list is empty takes part all the
+ * same.  impulses and velocities return the whole grid's numbers, the same bits on every rank; mgps_coupling_cells the rank's own
+ * count; mgps_coupling_set_bodies stays local (every rank passes the same tables).  A failing transport call returns MGPS_ERR_COMM
+ * at once, on that rank.  A world of one asks its transport nothing and computes the bits of the whole-grid object.  Sums stay in
+ * fp64 in one fixed order per rank; for fixed inputs, cuts and transport the bits repeat. */
+int mgps_coupling_create_slab(mgps_coupling **out, const mgps_coupling_desc *desc, const mgps_fields_slab *window, const mgps_comm *comm,
+                              void *stream);
 void mgps_coupling_destroy(mgps_coupling *c);
 /* new centres and K for the same list (a sub-step that moves the bodies but not the grids' faces); checks as above */
 int mgps_coupling_set_bodies(mgps_coupling *c, const double *centres_host, const double *inv_mass_host, const double *inv_inertia_host,
@@ -445,10 +469,17 @@ int mgps_coupling_velocities(mgps_coupling *c, const float *x_dev, const double 
  * two true residuals lose G K G^T x (the coupled cells' float32 residual is narrowed again and |r|^2 corrected by the fp64 sum of
  * new^2 - old^2 over them); preconditioner, updates, interrupt and the iterate handed back are those of mgps_solve_pcg.  With K = 0
  * every coupling term is 0.0 and the iterates are those of mgps_solve_pcg under pcg_fp64_vectors = 1.
- * The coupled cells must be active cells of the solver (both made from the same material labels).  Refused with a message: a slab
- * solver, options.precision = 1, a solver with an enclosed component (options.enclosed_liquid: a moving body changes the null
- * space), a coupling whose expanded extents differ from the solver's.  Coupling inside the one-call entries, on slabs and in the
- * default grouped fp32 loop: not yet. */
+ * The coupled cells must be active cells of the solver (both made from the same material labels).
+ * A slab solver takes the slab coupling of its own rank (mgps_coupling_create_slab: the same extents, owned expanded planes, rank and
+ * size); the call is then a collective like mgps_solve_pcg on a slab solver, with one more all-reduce (g) per application of the
+ * operator: iterations + 3 of them in a converged solve.  g^T K g enters the loop's <p, A p> on rank 0 alone and the residuals'
+ * corrections rank by rank, both summed by the reduction the loop makes anyway.
+ * Refused with a message, on the rank's own arguments and before any device work or collective (what is refused depends on what
+ * the ranks share, so all refuse alike): a slab solver with a whole-grid coupling, a whole-grid solver with a slab coupling, a
+ * window that is not the solver's, options.precision = 1, a solver with an enclosed component (options.enclosed_liquid: a moving body
+ * changes the null space), a coupling whose expanded extents differ from the solver's.  A failing transport call: MGPS_ERR_COMM at
+ * once.  Coupling inside the one-call entries (mgps_project_free_surface_slab included), in the default grouped fp32 loop and with
+ * enclosed_liquid: not yet. */
 int mgps_solve_pcg_coupled(mgps_solver *h, mgps_coupling *coupling, float *x_dev, const float *b_dev, double tolerance,
                            int max_iterations, int use_mg_preconditioner, mgps_pcg_stats *stats);
 
