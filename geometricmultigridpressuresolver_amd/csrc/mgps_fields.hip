@@ -1522,15 +1522,50 @@ void hipStep(SlabCall &c, hipError_t e, const char *what)
 {
     if (e != hipSuccess) c.fail(MGPS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-}  // namespace
+// The transport the slab solver of a world of one gets instead of the caller's, so that the one-call keeps its word -- with
+// comm->size = 1 no entry of the caller's transport is called -- through the constructor and the solve as well: nobody to trade
+// with, reductions over one rank are the identity, a gather or scatter is a device copy that synchronises the stream and blocks.
+int soloCopy(void *dst, const void *src, size_t bytes, void *stream)
+{
+    if (!bytes || dst == src) return 0;
+    if (hipStreamSynchronize(static_cast<hipStream_t>(stream)) != hipSuccess) return 1;
+    return hipMemcpy(dst, src, bytes, hipMemcpyDefault) == hipSuccess ? 0 : 1;
+}
+mgps_comm soloComm()
+{
+    mgps_comm cm{};
+    cm.struct_size = int(sizeof(mgps_comm));
+    cm.rank = 0, cm.size = 1;
+    cm.exchange = [](void *, const void *, size_t, void *, size_t, const void *, size_t, void *, size_t, void *) { return 0; };
+    cm.allreduce = [](void *, double *, int, int) { return 0; };
+    cm.gather = [](void *, const void *send, void *recv, size_t bytes, int, void *stream) { return soloCopy(recv, send, bytes, stream); };
+    cm.scatter = [](void *, const void *send, void *recv, size_t bytes, int, void *stream) { return soloCopy(recv, send, bytes, stream); };
+    cm.gatherv = [](void *, const void *send, size_t bytes, void *recv, const size_t *, const size_t *displs, int, void *stream) {
+        return soloCopy(static_cast<char *>(recv) + (bytes ? displs[0] : 0), send, bytes, stream);
+    };
+    cm.scatterv = [](void *, const void *send, const size_t *, const size_t *displs, void *recv, size_t bytes, int, void *stream) {
+        return soloCopy(recv, static_cast<const char *>(send) + (bytes ? displs[0] : 0), bytes, stream);
+    };
+    cm.allreduce_device = [](void *, double *, int, int, void *) { return 0; };
+    cm.exchange2 = [](void *, const mgps_xfer2 *, const mgps_xfer2 *, const mgps_xfer2 *, const mgps_xfer2 *, void *) { return 0; };
+    return cm;
+}
+// (the checks of the bodies' count and host tables, stated with the pressure feedback and the coupling further down)
+int forceCheckBodies(const char *fn, int bodies);
+int coupleCheckBodies(const char *fn, int bodies, const double *centres, const double *invMass, const double *invInertia);
 
-extern "C" {
-
-int mgps_project_free_surface_slab(mgps_projection_slab *p, const mgps_options *opt, const mgps_comm *comm, const int *splits, void *stream)
-try {
+// The sequence of mgps_project_free_surface_slab and mgps_project_free_surface_rigid_slab, stated once.  r: the rigid block, or NULL
+// for the plain call -- then no launch, transport call, message or result differs from what the sequence was without it.  With r
+// (DESIGN.md section 17.2): the bodies' count travels in the first agreement; after the solver, the rank's coupling object and one
+// more agreement (it carries the coupled cells' count), then what the coupled solve refuses, asked before any output but the valid
+// faces is touched; sv = the base solid velocity with V* on the bodies' faces feeds the right-hand side; the solve is
+// mgps_solve_pcg_coupled and its residual loses G K G^T x; V_out and the impulses come from one more collective and V_out goes over
+// sv in front of the divergence report.
+int projectFreeSurfaceSlab(const char *fn, mgps_projection_slab *p, mgps_projection_rigid_slab *r, const mgps_options *opt, const mgps_comm *comm,
+                           const int *splits, void *stream)
+{
     using clock = SlabCall::Clock;
     SlabCall c;
-    const char *fn = "mgps_project_free_surface_slab";
     const auto t0 = c.t0;
     // ---- what every rank shares: a refusal here is every rank's, before any collective
     if (!p || p->struct_size != int(sizeof(mgps_projection_slab))) return refuse(fn, "NULL or struct_size mismatch");
@@ -1539,8 +1574,18 @@ try {
     const int P = c.P, rank = c.rank;
     if (P > 1 && (!cm.gatherv || !cm.scatterv))
         return refuse(fn, "the collapse of uneven cuts and the enclosed-liquid merge go through gatherv and scatterv (and, with host_setup, the whole grid's labels): the transport has none");
+    const size_t tableDoubles = r ? size_t(r->bodies + 1) * 6 : 0;
+    if (r) {
+        if (int rc = forceCheckBodies(fn, r->bodies); rc != MGPS_OK) return rc;
+        if (int rc = coupleCheckBodies(fn, r->bodies, r->centres, r->inv_mass, r->inv_inertia); rc != MGPS_OK) return rc;
+        if (!r->motions) return refuse(fn, "motions is NULL");
+        if (!r->motions_out) return refuse(fn, "motions_out is NULL");
+        const int given = (r->solid_velocity_out[0] != nullptr) + (r->solid_velocity_out[1] != nullptr) + (r->solid_velocity_out[2] != nullptr);
+        if (given != 0 && given != 3) return refuse(fn, "solid_velocity_out: all three or none");
+        r->coupled_cells = r->coupled_cells_rank = 0;
+    }
     mgps_options o;
-    if (int rc = readOptions(opt, o, "mgps_project_free_surface_slab: "); rc != MGPS_OK) return rc;
+    if (int rc = readOptions(opt, o, (std::string(fn) + ": ").c_str()); rc != MGPS_OK) return rc;
     mgps_fields_slab desc;
     if (int rc = mgps_fields_slab_describe(&desc, p->gx, p->gy, p->gz, p->power_of_two, splits, P, rank); rc != MGPS_OK) return rc;
     Slab s;
@@ -1574,6 +1619,7 @@ try {
     DevPool pool;
     int32_t *material = nullptr;  // [lo plane | owned planes | hi plane]
     float *phiHalo = nullptr, *prHalo = nullptr, *spHalo = nullptr, *spOwn = nullptr, *w[3] = {nullptr, nullptr, nullptr}, *pGammaMax = nullptr;
+    float *sv[3] = {nullptr, nullptr, nullptr};  // rigid: the solid velocity the right-hand side and the report see
     uint8_t *valid[3] = {nullptr, nullptr, nullptr}, *labelsAll = nullptr;
     unsigned long long *count = nullptr;
     void *labelsHost = nullptr;
@@ -1583,6 +1629,7 @@ try {
     } hostBlock{labelsHost};
     c.step([&]() -> int {
         if (int rc = checkProjectionFields(p, fn, true, "missing field"); rc != MGPS_OK) return rc;
+        if (r && !(r->body[0] && r->body[1] && r->body[2])) return refuse(fn, "body: three grids are required");
         if (int rc = selectDevice(o.device); rc != MGPS_OK) return rc;
         try {
             material = pool.get<int32_t>(cells + 2 * plane);
@@ -1594,6 +1641,7 @@ try {
             for (int a = 0; a < 3; ++a) {
                 valid[a] = p->valid_faces[a] ? p->valid_faces[a] : pool.get<uint8_t>(faceCount(gx, gy, nzl, a));
                 w[a] = pool.get<float>(faceCount(ex, ey, nze, a));
+                if (r) sv[a] = r->solid_velocity_out[a] ? r->solid_velocity_out[a] : pool.get<float>(faceCount(gx, gy, nzl, a));
             }
             // the labels pass writes the rank's window: a buffer of its own, or (host set-up) in place in the whole grid's labels
             labelsAll = pool.get<uint8_t>(labelsToHosts ? ecells : size_t(nze) * eplane);
@@ -1606,9 +1654,12 @@ try {
         return MGPS_OK;
     }());
     {
-        double flags[2] = {surface ? 1.0 : 0.0, surface ? 0.0 : 1.0};  // (both set on some rank: the ranks disagree)
-        if (int rc = c.agree("arguments", nullptr, 0, flags, 2); rc != MGPS_OK) return rc;
+        // (both flags set on some rank: the ranks disagree; rigid: the largest and the smallest count of bodies)
+        double flags[4] = {surface ? 1.0 : 0.0, surface ? 0.0 : 1.0, r ? double(r->bodies) : 0.0, r ? -double(r->bodies) : 0.0};
+        if (int rc = c.agree("arguments", nullptr, 0, flags, r ? 4 : 2); rc != MGPS_OK) return rc;
         if (flags[0] != 0 && flags[1] != 0) return refuse(fn, "surface tension / surface_pressure is set on some ranks only");
+        if (flags[2] != -flags[3])
+            return refuse(fn, "bodies differs between the ranks (" + std::to_string(int(-flags[3])) + " .. " + std::to_string(int(flags[2])) + ")");
     }
     // (from here on the buffers exist on every rank: a failing rank still takes part in every exchange, with whatever its buffers
     //  hold, and the next agreement carries its status)
@@ -1625,8 +1676,17 @@ try {
         if (rc_ != MGPS_OK) return rc_; \
     } while (0)
     const float *cw[3] = {p->cut_weights[0], p->cut_weights[1], p->cut_weights[2]};
-    const float *svel[3] = {haveSolidVel ? p->solid_velocity[0] : nullptr, haveSolidVel ? p->solid_velocity[1] : nullptr,
-                            haveSolidVel ? p->solid_velocity[2] : nullptr};
+    const float *svel[3];
+    for (int a = 0; a < 3; ++a) svel[a] = r ? sv[a] : haveSolidVel ? p->solid_velocity[a] : nullptr;
+    // rigid: sv = the caller's solid velocity (or zeros) with `motions` on the faces the bodies own; again: those faces only
+    auto rigidSolidVelocity = [&](const double *motions, bool again) {
+        for (int a = 0; a < 3 && !again && c.status == MGPS_OK; ++a) {
+            const size_t bytes = faceCount(gx, gy, nzl, a) * sizeof(float);
+            if (!haveSolidVel) hipStep(c, hipMemsetAsync(sv[a], 0, bytes, st), "solid velocity");
+            else if (sv[a] != p->solid_velocity[a]) hipStep(c, hipMemcpyAsync(sv[a], p->solid_velocity[a], bytes, hipMemcpyDeviceToDevice, st), "solid velocity");
+        }
+        if (c.status == MGPS_OK) c.step(mgps_fields_slab_rigid_velocity(&desc, sv, r->body, r->centres, motions, r->bodies, st));
+    };
     int32_t *matOwn = material + plane, *matLo = lo ? material : nullptr, *matHi = hi ? matOwn + cells : nullptr;
     float *phiLo = lo ? phiHalo : nullptr, *phiHi = hi ? phiHalo + plane : nullptr;
     // ---- 1. phi plane, material labels, material plane, the faces pass and the labels pass (Plug.cpp:270-362)
@@ -1654,8 +1714,13 @@ try {
     p->stage_ms[0] = SlabCall::ms(t0, t1);
     if (liquid == 0) {
         hipStep(c, hipMemsetAsync(p->pressure, 0, cells * sizeof(float), st), "pressure clear");
+        if (r && r->solid_velocity_out[0]) rigidSolidVelocity(r->motions, false);
         hipStep(c, hipStreamSynchronize(st), "pressure clear");
         SLAB_COMM(c.agree("pressure clear"));
+        if (r) {  // nothing pushes back: V_out = V*
+            std::copy(r->motions, r->motions + tableDoubles, r->motions_out);
+            if (r->impulses) std::fill(r->impulses, r->impulses + tableDoubles, 0.0);
+        }
         p->stage_ms[6] = c.exchangeMs;
         p->setup_ms = p->total_ms = SlabCall::ms(t0, clock::now());
         p->stats.outcome = MGPS_PCG_RHS_ZERO;
@@ -1690,18 +1755,47 @@ try {
     //         term, enclosed-liquid projection, MG-PCG (Plug.cpp:386-629)
     mgps_solver *mg = nullptr;
     o.borrow_device_weights = 1;
+    const mgps_comm solo = soloComm(), *solverComm = P == 1 ? &solo : &cm;  // (the solver copies it)
     if (int rc = labelsToHosts ? mgps_create_slab_device_weights(&mg, ex, ey, ez, static_cast<const uint8_t *>(labelsHost), w[0], w[1], w[2], levels,
-                                                                 p->use_gauss_seidel, &o, &cm, splits)
-                               : mgps_create_slab_device_labels(&mg, ex, ey, ez, labelsWin, w[0], w[1], w[2], levels, p->use_gauss_seidel, &o, &cm, splits);
+                                                                 p->use_gauss_seidel, &o, solverComm, splits)
+                               : mgps_create_slab_device_labels(&mg, ex, ey, ez, labelsWin, w[0], w[1], w[2], levels, p->use_gauss_seidel, &o, solverComm, splits);
         rc != MGPS_OK)
         return rc;  // (a collective with one verdict)
     struct Guard {
         mgps_solver *h;
         ~Guard() { mgps_destroy(h); }
     } guard{mg};
+    // rigid: the rank's coupling object (its failure is the rank's own), the whole grid's count, and what the coupled solve refuses
+    // -- every rank alike -- while pressure, velocity and solid_velocity_out still hold what they held
+    mgps_coupling *cpl = nullptr;
+    struct CouplingGuard {
+        mgps_coupling *&h;
+        ~CouplingGuard() { mgps_coupling_destroy(h); }
+    } couplingGuard{cpl};
+    if (r) {
+        int64_t mine = 0;
+        if (c.status == MGPS_OK) {
+            mgps_coupling_desc cd{};
+            cd.struct_size = int(sizeof(cd));
+            cd.gx = s.gx, cd.gy = s.gy, cd.gz = s.gz, cd.ex = ex, cd.ey = ey, cd.ez = ez, cd.offset = s.off, cd.bodies = r->bodies;
+            cd.material = matOwn;
+            for (int a = 0; a < 3; ++a) cd.cut_weights[a] = cw[a], cd.body[a] = r->body[a];
+            cd.centres = r->centres, cd.inv_mass = r->inv_mass, cd.inv_inertia = r->inv_inertia;
+            c.step(mgps_coupling_create_slab(&cpl, &cd, &desc, &cm, st));
+            if (c.status == MGPS_OK) c.step(mgps_coupling_cells(cpl, &mine));
+        }
+        double all = double(mine);
+        SLAB_COMM(c.agree("coupling", &all, 1));
+        r->coupled_cells = int64_t(all);
+        r->coupled_cells_rank = mine;
+        if (int rc = coupledSolveRefusal(mg, cpl, "mgps_solve_pcg_coupled"); rc != MGPS_OK) {
+            setLastGlobalError(mgps_last_error(mg));
+            return rc;
+        }
+    }
     const auto t3 = clock::now();
     p->stage_ms[2] = SlabCall::ms(t2, t3);
-    float *rhs = nullptr, *x = nullptr, *res = nullptr;
+    float *rhs = nullptr, *x = nullptr, *res = nullptr, *gkg = nullptr;
     const float *sp = p->surface_pressure ? p->surface_pressure : spOwn;
     float *spLo = surface && lo ? spHalo : nullptr, *spHi = surface && hi ? spHalo + plane : nullptr;
     const float *velIn[3] = {p->velocity[0], p->velocity[1], p->velocity[2]};
@@ -1715,6 +1809,8 @@ try {
     if (c.status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &rhs));
     if (c.status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &x));  // zero-filled
     if (c.status == MGPS_OK) solverStep(mgps_grid_alloc(mg, 0, &res));
+    if (c.status == MGPS_OK && r) solverStep(mgps_grid_alloc(mg, 0, &gkg));
+    if (r) rigidSolidVelocity(r->motions, false);
     if (c.status == MGPS_OK) c.step(mgps_fields_slab_rhs(&desc, rhs, matOwn, velIn, svel, cw, st));
     if (c.status == MGPS_OK && p->use_old_pressure) c.step(mgps_fields_slab_pressure_to_solution(&desc, x, p->pressure, matOwn, st));
     if (surface) {  // b_L += w_f p_G: before the enclosed-liquid projection and the solve, which then see the system actually solved
@@ -1738,8 +1834,13 @@ try {
     (void)hipStreamSynchronize(st);
     const auto t4 = clock::now();
     p->stage_ms[3] = SlabCall::ms(t3, t4);
-    int rc = mgps_solve_pcg(mg, x, rhs, p->tolerance, p->max_iterations, p->use_mg_preconditioner, &p->stats);
+    int rc = r ? mgps_solve_pcg_coupled(mg, cpl, x, rhs, p->tolerance, p->max_iterations, p->use_mg_preconditioner, &p->stats)
+               : mgps_solve_pcg(mg, x, rhs, p->tolerance, p->max_iterations, p->use_mg_preconditioner, &p->stats);
     if (rc == MGPS_OK) rc = mgps_residual(mg, 0, res, x, rhs);  // Plug.cpp:625-628
+    if (rc == MGPS_OK && r) {  // the coupled system's: b - (A + G K G^T) x (a collective; its message is the library's already)
+        if (int arc = mgps_coupling_apply(cpl, gkg, x, st); arc != MGPS_OK) return arc;
+        rc = mgps_add_to_vector(mg, 0, res, gkg, -1.0);
+    }
     if (rc == MGPS_OK) rc = mgps_inf_norm(mg, 0, res, 1, &p->residual_inf);
     if (rc == MGPS_OK) rc = mgps_l2_norm(mg, 0, res, &p->residual_l2);
     if (rc != MGPS_OK && rc != MGPS_ERR_INTERRUPTED) {
@@ -1752,6 +1853,12 @@ try {
     p->stage_ms[4] = SlabCall::ms(t4, t5);
     // ---- 5. pressure (0 outside LIQUID cells, Plug.cpp:641), its plane to the neighbours, the gradient on the owned faces -- the
     //         rank's copy of a cut's z-face plane included -- and the divergence report (Plug.cpp:637-707)
+    if (r) {  // V_out and the impulses of the iterate handed back (a collective: every rank, whatever its status), V_out over sv
+        const int vrc = mgps_coupling_velocities(cpl, x, r->motions, r->motions_out, r->impulses, st);
+        if (vrc == MGPS_ERR_COMM) return vrc;
+        c.step(vrc);
+        rigidSolidVelocity(r->motions_out, true);
+    }
     c.step(mgps_fields_slab_solution_to_pressure(&desc, p->pressure, x, matOwn, 1, st));
     SLAB_COMM(tradePlane(p->pressure, prHalo, prHalo + plane, sizeof(float), "pressure"));
     if (c.status == MGPS_OK)
@@ -1782,6 +1889,22 @@ try {
                     "(plane exchanges %.2f ms)\n",
                     rank, p->stage_ms[0], p->stage_ms[1], p->stage_ms[2], p->stage_ms[3], p->stage_ms[4], p->stage_ms[5], c.exchangeMs);
     return solveRc != MGPS_OK ? c.leave(solveRc, "interrupted") : MGPS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mgps_project_free_surface_slab(mgps_projection_slab *p, const mgps_options *opt, const mgps_comm *comm, const int *splits, void *stream)
+try {
+    return projectFreeSurfaceSlab("mgps_project_free_surface_slab", p, nullptr, opt, comm, splits, stream);
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_project_free_surface_rigid_slab(mgps_projection_rigid_slab *r, const mgps_options *opt, const mgps_comm *comm, const int *splits, void *stream)
+try {
+    const char *fn = "mgps_project_free_surface_rigid_slab";
+    if (!r || r->struct_size != int(sizeof(mgps_projection_rigid_slab))) return refuse(fn, "NULL or struct_size mismatch (mgps_projection_rigid_slab)");
+    return projectFreeSurfaceSlab(fn, r->projection, r, opt, comm, splits, stream);
 }
 MGPS_API_CATCH(nullptr)
 

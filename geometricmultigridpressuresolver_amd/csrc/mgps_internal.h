@@ -627,6 +627,9 @@ int couplingApply64(mgps_coupling *c, void *stream, double *t, const double *p, 
 // r -= G K G^T x, r32 = float(r) on the coupled cells, *norm2Dev += the fp64 sum of new^2 - old^2 over them (slab ranks: over the
 // rank's own cells, summed with *norm2Dev over the ranks).  Four launches (slab ranks: five)
 int couplingResidual64(mgps_coupling *c, void *stream, double *r, const double *x, float *r32, double *norm2Dev);
+// What mgps_solve_pcg_coupled refuses of a solver and a coupling (mgps_solver.hip): MGPS_OK, or the status with "<fn>: ..." as the
+// solver's last error.  No device work, no collective
+int coupledSolveRefusal(mgps_solver *h, mgps_coupling *coupling, const char *fn);
 }  // namespace mgps
 
 namespace mgps {

@@ -5083,14 +5083,13 @@ try {
 }
 MGPS_API_CATCH(h)
 
-int mgps_solve_pcg_coupled(mgps_solver *h, mgps_coupling *coupling, float *x_dev, const float *b_dev, double tolerance, int max_iterations,
-                           int use_mg_preconditioner, mgps_pcg_stats *stats)
-try {
-    const char *fn = "mgps_solve_pcg_coupled";
-    MGPS_TRY(checkLevel(h, 0, fn));
-    if (!coupling) return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL coupling");
-    if (!x_dev || !b_dev || x_dev == b_dev || !(tolerance >= 0) || max_iterations < 0)
-        return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+}  // extern "C"
+
+namespace mgps {
+// What mgps_solve_pcg_coupled refuses of a solver and a coupling, on the rank's own arguments and before any device work or
+// collective (every rank refuses alike): stated once for the solve and for the one-call that asks before it touches its outputs
+int coupledSolveRefusal(mgps_solver *h, mgps_coupling *coupling, const char *fn)
+{
     if (h->opt.precision == 1)
         return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": not available with options.precision = 1 (mixed precision)");
     int planes[2], cplRank = 0, cplSize = 1;
@@ -5117,6 +5116,21 @@ try {
                      std::string(fn) + ": the coupling's window, expanded planes " + std::to_string(planes[0]) + " .. " + std::to_string(planes[1]) + " of rank " +
                          std::to_string(cplRank) + " of " + std::to_string(cplSize) + ", is not this slab solver's (planes " + std::to_string(h->lv[0].z0) + " .. " +
                          std::to_string(h->lv[0].z1) + " of rank " + std::to_string(h->comm.rank) + " of " + std::to_string(h->comm.size) + ")");
+    return MGPS_OK;
+}
+}  // namespace mgps
+
+extern "C" {
+
+int mgps_solve_pcg_coupled(mgps_solver *h, mgps_coupling *coupling, float *x_dev, const float *b_dev, double tolerance, int max_iterations,
+                           int use_mg_preconditioner, mgps_pcg_stats *stats)
+try {
+    const char *fn = "mgps_solve_pcg_coupled";
+    MGPS_TRY(checkLevel(h, 0, fn));
+    if (!coupling) return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": NULL coupling");
+    if (!x_dev || !b_dev || x_dev == b_dev || !(tolerance >= 0) || max_iterations < 0)
+        return failH(h, MGPS_ERR_INVALID_ARGUMENT, std::string(fn) + ": bad arguments");
+    MGPS_TRY(mgps::coupledSolveRefusal(h, coupling, fn));
     mgps_pcg_stats local{};
     if (!stats) stats = &local;
     std::memset(stats, 0, sizeof(*stats));

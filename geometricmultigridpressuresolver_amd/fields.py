@@ -396,15 +396,10 @@ class ProjectionSlab(C.Structure):
 STAGES_SLAB = ("passes", "labels_to_hosts", "solver_setup", "rhs", "solve", "write_back", "plane_exchanges")
 
 
-def project_free_surface_slab(comm, splits, global_shape, liquid_phi, solid_phi, cut_weights, velocity, pressure, solid_velocity=None,
-                              use_old_pressure=True, use_mg_preconditioner=True, use_gauss_seidel=True, tolerance=1e-5, max_iterations=2500,
-                              power_of_two=True, options=None, surface_tension=0.0, dt=0.0, dx=0.0, density=0.0, surface_pressure=None):
-    """mgps_project_free_surface_slab: solveGasSubclass on the float32 CUDA tensors of this rank's window of the grid `global_shape`
-    = (gz, gy, gx), a collective over the transport `comm` (RcclComm / TorchDistComm; a world of one is the device-resident
-    projection on one GPU).  `splits`: the cuts of the expanded grid (projection_slab_layout, or the caller's own).  Cell, x-face
-    and y-face grids hold the rank's base planes [c0, c1) (slab_window), z-face grids the faces c0 .. c1.  `velocity` and
-    `pressure` are updated in place; returns (valid_faces[3] uint8 CUDA tensors, info dict of the whole grid's numbers)."""
-    d = slab_window(global_shape, power_of_two, splits, comm.rank)
+def _projection_slab(d, global_shape, liquid_phi, solid_phi, cut_weights, velocity, pressure, solid_velocity, use_old_pressure,
+                     use_mg_preconditioner, use_gauss_seidel, tolerance, max_iterations, power_of_two, surface_tension, dt, dx, density,
+                     surface_pressure):
+    """the ProjectionSlab of one call on the window `d` and the valid-face tensors it writes"""
     shape = d.base_shape
     faces = _face3(shape)
     dev = liquid_phi.device
@@ -428,9 +423,11 @@ def project_free_surface_slab(comm, splits, global_shape, liquid_phi, solid_phi,
     pr.tolerance, pr.max_iterations, pr.power_of_two = float(tolerance), int(max_iterations), int(bool(power_of_two))
     pr.surface_tension, pr.dt, pr.dx, pr.density = float(surface_tension), float(dt), float(dx), float(density)
     pr.surface_pressure = ptr(surface_pressure, shape) if surface_pressure is not None else None
-    cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
-    status = lib().mgps_project_free_surface_slab(C.byref(pr), C.byref(options) if options is not None else None, C.byref(comm.struct), cuts, _stream())
-    info = {
+    return pr, valid
+
+
+def _projection_slab_info(pr, d):
+    return {
         "iterations": pr.stats.iterations, "outcome": pr.stats.outcome, "rel_residual": pr.stats.rel_residual,
         "rel_residual_recomputed": pr.stats.rel_residual_recomputed, "mg_levels": pr.mg_levels, "offset": pr.offset,
         "expanded": (pr.expanded[2], pr.expanded[1], pr.expanded[0]), "liquid_cells": pr.liquid_cells,
@@ -440,6 +437,23 @@ def project_free_surface_slab(comm, splits, global_shape, liquid_phi, solid_phi,
         "surface_pressure_max": pr.surface_pressure_max, "window": (d.c0, d.c1),
         "stage_ms": {n: pr.stage_ms[q] for q, n in enumerate(STAGES_SLAB)},
     }
+
+
+def project_free_surface_slab(comm, splits, global_shape, liquid_phi, solid_phi, cut_weights, velocity, pressure, solid_velocity=None,
+                              use_old_pressure=True, use_mg_preconditioner=True, use_gauss_seidel=True, tolerance=1e-5, max_iterations=2500,
+                              power_of_two=True, options=None, surface_tension=0.0, dt=0.0, dx=0.0, density=0.0, surface_pressure=None):
+    """mgps_project_free_surface_slab: solveGasSubclass on the float32 CUDA tensors of this rank's window of the grid `global_shape`
+    = (gz, gy, gx), a collective over the transport `comm` (RcclComm / TorchDistComm; a world of one is the device-resident
+    projection on one GPU).  `splits`: the cuts of the expanded grid (projection_slab_layout, or the caller's own).  Cell, x-face
+    and y-face grids hold the rank's base planes [c0, c1) (slab_window), z-face grids the faces c0 .. c1.  `velocity` and
+    `pressure` are updated in place; returns (valid_faces[3] uint8 CUDA tensors, info dict of the whole grid's numbers)."""
+    d = slab_window(global_shape, power_of_two, splits, comm.rank)
+    pr, valid = _projection_slab(d, global_shape, liquid_phi, solid_phi, cut_weights, velocity, pressure, solid_velocity, use_old_pressure,
+                                 use_mg_preconditioner, use_gauss_seidel, tolerance, max_iterations, power_of_two, surface_tension, dt, dx, density,
+                                 surface_pressure)
+    cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
+    status = lib().mgps_project_free_surface_slab(C.byref(pr), C.byref(options) if options is not None else None, C.byref(comm.struct), cuts, _stream())
+    info = _projection_slab_info(pr, d)
     try:
         check(status)
     except _lib.MgpsError as e:  # (interrupted: pressure and velocity hold what the iterate reached gives)
@@ -810,3 +824,59 @@ def project_free_surface_rigid(liquid_phi, solid_phi, cut_weights, velocity, pre
         mg.close()
     return {"pressure": pressure, "velocity": velocity, "motions": v_out, "impulses": impulses, "stats": stats, "material": material,
             "valid_faces": valid, "solid_velocity": sv, "offset": offset, "expanded": eshape, "coupled_cells": cells}
+
+
+class ProjectionRigidSlab(C.Structure):
+    """mgps_projection_rigid_slab (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("projection", C.POINTER(ProjectionSlab)), ("bodies", C.c_int), ("body", C.c_void_p * 3),
+        ("centres", C.c_void_p), ("inv_mass", C.c_void_p), ("inv_inertia", C.c_void_p), ("motions", C.c_void_p),
+        ("solid_velocity_out", C.c_void_p * 3), ("motions_out", C.c_void_p), ("impulses", C.c_void_p),
+        ("coupled_cells", C.c_int64), ("coupled_cells_rank", C.c_int64),
+    ]
+
+
+def project_free_surface_rigid_slab(comm, splits, global_shape, liquid_phi, solid_phi, cut_weights, velocity, pressure, body, centres, inv_mass,
+                                    inv_inertia, motions, solid_velocity=None, solid_velocity_out=None, use_old_pressure=True,
+                                    use_mg_preconditioner=True, use_gauss_seidel=True, tolerance=1e-5, max_iterations=2500, power_of_two=True,
+                                    options=None, surface_tension=0.0, dt=0.0, dx=0.0, density=0.0, surface_pressure=None):
+    """mgps_project_free_surface_rigid_slab: project_free_surface_slab with rigid bodies the liquid moves, a collective over `comm` (a
+    world of one is the device-resident coupled projection on one GPU).  The fields are those of project_free_surface_slab; `body`:
+    the window's three int32 face grids of body ids; `centres`, `inv_mass`, `inv_inertia`, `motions` (V*): the host tables of
+    RigidCoupling and rigidVelocity, the same on every rank.  `solid_velocity` (or zeros) supplies the faces no body owns and is left
+    untouched; `solid_velocity_out` (three float32 face grids of the window, or None) receives the solid velocity the projected
+    velocity is divergence free against: `solid_velocity` with V_out on the bodies' faces.  `velocity` and `pressure` are updated in
+    place.  Returns (valid_faces, info): the info of project_free_surface_slab plus "motions" (V_out) and "impulses", (bodies + 1, 6)
+    float64 arrays with the same bits on every rank, "coupled_cells" (the whole grid's) and "coupled_cells_rank"."""
+    import numpy as np
+
+    d = slab_window(global_shape, power_of_two, splits, comm.rank)
+    faces = _face3(d.base_shape)
+    pr, valid = _projection_slab(d, global_shape, liquid_phi, solid_phi, cut_weights, velocity, pressure, solid_velocity, use_old_pressure,
+                                 use_mg_preconditioner, use_gauss_seidel, tolerance, max_iterations, power_of_two, surface_tension, dt, dx, density,
+                                 surface_pressure)
+    c, bodies = _centres(centres)
+    im, ii, m = _table(inv_mass, bodies, 1, "inv_mass"), _table(inv_inertia, bodies, 6, "inv_inertia"), _table(motions, bodies, 6, "motions")
+    v_out, impulses = np.zeros_like(m), np.zeros_like(m)
+    rg = ProjectionRigidSlab()
+    rg.struct_size = C.sizeof(ProjectionRigidSlab)
+    rg.projection = C.pointer(pr)
+    rg.bodies = int(bodies)
+    for a in range(3):
+        # (a missing entry stays NULL: the library carries the refusal to every rank)
+        rg.body[a] = _chk(body[a], faces[a], torch.int32).data_ptr() if body[a] is not None else None
+        rg.solid_velocity_out[a] = _chk(solid_velocity_out[a], faces[a], torch.float32).data_ptr() if solid_velocity_out is not None else None
+    rg.centres, rg.inv_mass, rg.inv_inertia, rg.motions = c.ctypes.data, im.ctypes.data, ii.ctypes.data, m.ctypes.data
+    rg.motions_out, rg.impulses = v_out.ctypes.data, impulses.ctypes.data
+    cuts = (C.c_int * len(splits))(*[int(v) for v in splits])
+    status = lib().mgps_project_free_surface_rigid_slab(C.byref(rg), C.byref(options) if options is not None else None, C.byref(comm.struct), cuts,
+                                                        _stream())
+    info = _projection_slab_info(pr, d)
+    info.update(motions=v_out, impulses=impulses, coupled_cells=rg.coupled_cells, coupled_cells_rank=rg.coupled_cells_rank)
+    try:
+        check(status)
+    except _lib.MgpsError as e:  # (interrupted: pressure, velocity, motions and impulses are those of the iterate handed back)
+        e.info, e.valid_faces = info, valid
+        raise
+    return valid, info

@@ -478,10 +478,53 @@ int mgps_coupling_velocities(mgps_coupling *c, const float *x_dev, const double 
  * the ranks share, so all refuse alike): a slab solver with a whole-grid coupling, a whole-grid solver with a slab coupling, a
  * window that is not the solver's, options.precision = 1, a solver with an enclosed component (options.enclosed_liquid: a moving body
  * changes the null space), a coupling whose expanded extents differ from the solver's.  A failing transport call: MGPS_ERR_COMM at
- * once.  Coupling inside the one-call entries (mgps_project_free_surface_slab included), in the default grouped fp32 loop and with
- * enclosed_liquid: not yet. */
+ * once.  The one-call on device fields is mgps_project_free_surface_rigid_slab below.  Coupling in the host-array entry
+ * mgps_project_free_surface, in the default grouped fp32 loop and with enclosed_liquid: not yet. */
 int mgps_solve_pcg_coupled(mgps_solver *h, mgps_coupling *coupling, float *x_dev, const float *b_dev, double tolerance,
                            int max_iterations, int use_mg_preconditioner, mgps_pcg_stats *stats);
+
+/* The projection with rigid bodies the liquid moves, in one call on the DEVICE fields of one slab rank: a
+ * collective over `comm` with the contract of mgps_project_free_surface_slab -- the same steps, plane exchanges, agreements,
+ * no-liquid path, interrupt rule, surface tension and stage_ms -- around the parts above.  With comm->size = 1 it is the
+ * device-resident coupled projection on one GPU and no transport entry is called.  What differs from the plain call:
+ *   * the bodies' count travels in the first agreement (as a max and a min: a count that differs between the ranks is refused on
+ *     every rank), with the rank's own failures -- a missing `body` grid, an allocation, a HIP error;
+ *   * after the solver is built the rank makes its coupling (mgps_coupling_create_slab on its material labels, cut weights and
+ *     `body`); one more agreement carries a failure of it and sums coupled_cells.  Then what mgps_solve_pcg_coupled refuses is
+ *     asked, with that entry's message and on every rank alike: a solver with an enclosed component (options.enclosed_liquid = 1
+ *     on a domain without one is accepted; options.precision = 1 is refused before, by the slab solver's constructor).  After
+ *     either refusal pressure, velocity and solid_velocity_out hold what they held (valid_faces are written);
+ *   * sv -- in solid_velocity_out when given, in buffers of the call otherwise -- is a copy of projection->solid_velocity (zeros when
+ *     that is all NULL) with V* = `motions` written over the bodies' faces by mgps_fields_slab_rigid_velocity; the right-hand side
+ *     is mgps_fields_slab_rhs with this sv;
+ *   * the solve is mgps_solve_pcg_coupled (the loop of pcg_fp64_vectors = 1, whatever the option says); residual_inf and
+ *     residual_l2 are norms of b - (A + G K G^T) x: mgps_coupling_apply into a zeroed grid, subtracted from mgps_residual's output;
+ *   * mgps_coupling_velocities (a collective) gives motions_out and impulses, the same bits on every rank;
+ *     mgps_fields_slab_rigid_velocity writes V_out over sv and the divergence report is taken against that sv, which
+ *     solid_velocity_out publishes (both copies of a cut's z-face plane alike);
+ *   * no liquid anywhere: the plain call's path with motions_out = motions, zero impulses and zero counts (solid_velocity_out, when
+ *     given, holds sv of V*);
+ *   * MGPS_ERR_INTERRUPTED publishes the iterate handed back as the plain call does; motions_out, impulses and solid_velocity_out
+ *     are those of that iterate.
+ * Refused before any collective, on what the ranks share: NULL or a struct_size mismatch of either struct, the transport checks of
+ * the plain call, bodies outside 1 .. 255, a NULL table, a negative or non-finite inv_mass or diagonal entry of inv_inertia, NULL
+ * motions or motions_out, solid_velocity_out partly set. */
+typedef struct mgps_projection_rigid_slab {
+    int struct_size;                  /* sizeof(mgps_projection_rigid_slab) */
+    mgps_projection_slab *projection; /* fields, switches and results of the plain call (its struct_size is checked).  Its
+                                         solid_velocity (or all NULL = 0) supplies the faces no body owns and is not written */
+    int bodies;                       /* 1 .. 255 */
+    const int32_t *body[3];           /* device, the window's face grids of body ids (as mgps_coupling_create_slab) */
+    const double *centres, *inv_mass, *inv_inertia; /* host tables as in mgps_coupling_desc; the same on every rank */
+    const double *motions;            /* host, (bodies + 1) * 6: V* = (U, omega) per row */
+    float *solid_velocity_out[3];     /* device, window face grids, all three or none: the solid velocity the projected
+                                         velocity is divergence free against (above) */
+    double *motions_out;              /* host, (bodies + 1) * 6: V_out; required */
+    double *impulses;                 /* host, (bodies + 1) * 6, or NULL */
+    int64_t coupled_cells, coupled_cells_rank; /* results: the whole grid's count, this rank's */
+} mgps_projection_rigid_slab;
+int mgps_project_free_surface_rigid_slab(mgps_projection_rigid_slab *r, const mgps_options *opt, const mgps_comm *comm,
+                                         const int *splits, void *stream);
 
 #ifdef __cplusplus
 }
