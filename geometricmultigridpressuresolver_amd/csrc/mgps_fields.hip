@@ -1300,6 +1300,14 @@ bool okHalo(const Slab &s, const T *own, const T *lo, const T *hi)
 }
 }  // namespace
 
+namespace mgps {
+bool fieldsSlabWindow(const mgps_fields_slab *d, const char *fn)
+{
+    Slab s;
+    return readSlab(d, s, fn);
+}
+}  // namespace mgps
+
 extern "C" {
 
 int mgps_fields_slab_describe(mgps_fields_slab *out, int gx, int gy, int gz, int power_of_two, const int *splits, int size, int rank)

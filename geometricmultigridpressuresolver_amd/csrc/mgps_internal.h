@@ -613,6 +613,7 @@ int launchUnpack(void *stream, float *a, const float *buf, const int32_t *idx, i
 
 // ---- the rigid-body coupling (mgps_fields.hip) as pcg64 sees it: fp64 grids of the expanded extents ----------
 struct mgps_coupling;
+struct mgps_fields_slab;
 namespace mgps {
 void couplingExtents(const mgps_coupling *c, int e[3]);  // the whole expanded grid's
 // true for a slab coupling (mgps_coupling_create_slab); planes: the expanded planes [e0, e1) its list and grids cover, rank / size:
@@ -630,6 +631,9 @@ int couplingResidual64(mgps_coupling *c, void *stream, double *r, const double *
 // What mgps_solve_pcg_coupled refuses of a solver and a coupling (mgps_solver.hip): MGPS_OK, or the status with "<fn>: ..." as the
 // solver's last error.  No device work, no collective
 int coupledSolveRefusal(mgps_solver *h, mgps_coupling *coupling, const char *fn);
+// readSlab of mgps_fields.hip for the other units: false, with "<fn>: not a slab window ..." as the last error, when *d is not a
+// window of a layout
+bool fieldsSlabWindow(const mgps_fields_slab *d, const char *fn);
 }  // namespace mgps
 
 namespace mgps {

@@ -880,3 +880,100 @@ def project_free_surface_rigid_slab(comm, splits, global_shape, liquid_phi, soli
         e.info, e.valid_faces = info, valid
         raise
     return valid, info
+
+
+# ---- rigid bodies rasterised on the device (include/mgps_fields.h) ---------------------------------------------
+BODY_SPHERE, BODY_BOX, BODY_GRID = 0, 1, 2
+
+
+class BodyShape(C.Structure):
+    """mgps_body_shape: kind, pose (centre, rotation body -> world) and extent of one rigid body; lengths in cells from the grid's
+    corner, arrays in (x, y, z) order.  Make one with BodyShape.sphere, BodyShape.box or BodyShape.sdf_grid."""
+
+    _fields_ = [
+        ("kind", C.c_int), ("centre", C.c_double * 3), ("rotation", C.c_double * 9), ("half", C.c_double * 3), ("sdf", C.c_void_p),
+        ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("origin", C.c_double * 3), ("spacing", C.c_double),
+    ]
+
+    @classmethod
+    def _posed(cls, kind, centre, rotation):
+        s = cls()
+        s.kind = kind
+        s.centre[:] = [float(v) for v in centre]
+        rot = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0) if rotation is None else [float(v) for row in rotation for v in row]
+        s.rotation[:] = rot
+        return s
+
+    @classmethod
+    def sphere(cls, centre, radius):
+        s = cls._posed(BODY_SPHERE, centre, None)
+        s.half[0] = float(radius)
+        return s
+
+    @classmethod
+    def box(cls, centre, half, rotation=None):
+        """`rotation`: 3 x 3 rows, body -> world (None: the identity)"""
+        s = cls._posed(BODY_BOX, centre, rotation)
+        s.half[:] = [float(v) for v in half]
+        return s
+
+    @classmethod
+    def sdf_grid(cls, centre, sdf, origin, spacing, rotation=None):
+        """`sdf`: a CUDA float32 tensor (nz, ny, nx) of body-frame samples, negative inside, in cells; sample (0, 0, 0) sits at the
+        body-frame position `origin`, the samples are `spacing` cells apart.  The tensor is kept alive with the shape."""
+        s = cls._posed(BODY_GRID, centre, rotation)
+        assert sdf.is_cuda and sdf.is_contiguous() and sdf.dtype == torch.float32 and sdf.dim() == 3, (sdf.shape, sdf.dtype)
+        s.nz, s.ny, s.nx = (int(v) for v in sdf.shape)
+        s.sdf, s._keep = sdf.data_ptr(), sdf
+        s.origin[:] = [float(v) for v in origin]
+        s.spacing = float(spacing)
+        return s
+
+
+class RasterDesc(C.Structure):
+    """mgps_raster_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("bodies", C.c_int), ("shapes", C.POINTER(BodyShape)),
+        ("band", C.c_double), ("min_open", C.c_double), ("static_solid_phi", C.c_void_p), ("static_cut_weights", C.c_void_p * 3),
+        ("solid_phi", C.c_void_p), ("cut_weights", C.c_void_p * 3), ("body", C.c_void_p * 3),
+    ]
+
+
+def _raster(entry, window, grid_shape, array_shape, shapes, band, min_open, static_solid_phi, static_cut_weights):
+    faces = _face3(array_shape)
+    device = static_solid_phi.device if static_solid_phi is not None else torch.device("cuda", torch.cuda.current_device())
+    rows = (BodyShape * (len(shapes) + 1))(BodyShape(), *shapes)  # (row 0 is not read)
+    d = RasterDesc()
+    d.struct_size = C.sizeof(RasterDesc)
+    d.gz, d.gy, d.gx = grid_shape
+    d.bodies, d.shapes, d.band, d.min_open = len(shapes), rows, float(band), float(min_open)
+    if static_solid_phi is not None:
+        d.static_solid_phi = _chk(static_solid_phi, array_shape, torch.float32).data_ptr()
+    if static_cut_weights is not None:
+        for a in range(3):
+            d.static_cut_weights[a] = _chk(static_cut_weights[a], faces[a], torch.float32).data_ptr()
+    solid_phi = torch.empty(array_shape, dtype=torch.float32, device=device)
+    cut_weights = [torch.empty(faces[a], dtype=torch.float32, device=device) for a in range(3)]
+    body = [torch.empty(faces[a], dtype=torch.int32, device=device) for a in range(3)]
+    d.solid_phi = solid_phi.data_ptr()
+    for a in range(3):
+        d.cut_weights[a], d.body[a] = cut_weights[a].data_ptr(), body[a].data_ptr()
+    with torch.cuda.device(device):
+        check(entry(C.byref(d), _stream()) if window is None else entry(C.byref(window), C.byref(d), _stream()))
+    return solid_phi, cut_weights, body
+
+
+def rasterizeBodies(shape, shapes, band=3.0, min_open=0.0, static_solid_phi=None, static_cut_weights=None):
+    """mgps_fields_rasterize_bodies: the solid SDF, the three cut-weight face grids and the three int32 body-id face grids of the
+    rigid bodies `shapes` (a list of BodyShape: body r is shapes[r - 1]) on the grid `shape` = (gz, gy, gx), merged with the static
+    solids' grids where given (read, never written).  Returns (solid_phi, cut_weights, body): new CUDA tensors, what
+    project_free_surface_rigid, RigidCoupling and solidForces take.  Does not synchronise."""
+    return _raster(lib().mgps_fields_rasterize_bodies, None, tuple(shape), tuple(shape), shapes, band, min_open, static_solid_phi, static_cut_weights)
+
+
+def rasterizeBodiesSlab(d, shapes, band=3.0, min_open=0.0, static_solid_phi=None, static_cut_weights=None):
+    """mgps_fields_slab_rasterize_bodies: rasterizeBodies on the window `d` (fields.slab_window): the window's grids (z-faces
+    c0 .. c1) with the bits of the whole-grid pass on the rank's planes.  No halo, no communication."""
+    return _raster(lib().mgps_fields_slab_rasterize_bodies, d, (d.gz, d.gy, d.gx), d.base_shape, shapes, band, min_open, static_solid_phi,
+                   static_cut_weights)

@@ -526,6 +526,69 @@ typedef struct mgps_projection_rigid_slab {
 int mgps_project_free_surface_rigid_slab(mgps_projection_rigid_slab *r, const mgps_options *opt, const mgps_comm *comm,
                                          const int *splits, void *stream);
 
+/* ---- rigid bodies rasterised on the device: solid SDF, cut weights, body ids ------------------------------
+ * The entries above take solid_phi, cut_weights and the body face grids from the caller; this pass writes them from a host table
+ * of shapes and poses, for the sub-step after the bodies have moved.  No counterpart in the reference (Houdini hands it `collision`
+ * and `cutCellWeights`); the definition here is the contract.
+ *   Lengths are in cells from the grid's corner (section "pressure feedback"): node (i, j, k) at (i, j, k), a cell centre at + 1/2
+ *   in every direction, the x-face (i, j, k) at (i, j + 1/2, k + 1/2).  All geometry is fp64 from the host tables, every output is
+ *   rounded to float32 once; no atomics on values: the same inputs give the same bits on every run.
+ *   x_b = R^T (x - centre) is the position in the body frame.  sdf_r(x):
+ *     SPHERE  |x_b| - half[0];
+ *     BOX     q = |x_b| - half, |max(q, 0)|_2 + min(max(q.x, q.y, q.z), 0);
+ *     GRID    g = (x_b - origin) / spacing clamped per axis into [0, n - 1], i0 = min(floor(g), n - 2), f = g - i0, the samples
+ *             interpolated along x, then y, then z as (1 - f) a + f b in fp64, plus the Euclidean distance from x_b to the sample
+ *             box [origin, origin + (n - 1) spacing] (per axis max(lo - x_b, x_b - hi, 0)).
+ *   The frame box of a body is [-radius, radius]^3, [-half, half] or the sample box; its reach box is the world AABB of the frame
+ *   box (centre of the frame box carried to the world, +- |R| h) grown by `band` on every side, made in fp64 on the host.  At a point
+ *   inside its reach box (bounds included) body r contributes min(sdf_r, band), outside it contributes band.
+ *   Node field (internal): phi_n = min(band, min_r contribution_r(node)); owner_n = the lowest r that attains phi_n when
+ *   phi_n < band, else 0.
+ *   solid_phi[c] = min(static_solid_phi[c], float(min(band, min_r contribution_r(cell centre)))); static term +1e30f when NULL.
+ *   w_b of a face: the open fraction from its four corner nodes' phi_n in cyclic order -- for axis a with in-plane axes u < v the
+ *   corners (0,0), (1,0), (1,1), (0,1) in (u, v).  The polygon has, in that order, every corner with phi >= 0 and, on every edge
+ *   a -> b whose ends differ in that test, the crossing at t = phi_a / (phi_a - phi_b); w_b is its shoelace area clamped into
+ *   [0, 1] (two diagonal non-negative corners: one hexagon through the middle; exact for a planar SDF).  Then w_b < min_open
+ *   becomes 0 and w_b > 1 - min_open becomes 1.
+ *   cut_weights[a][f] = min(static_cut_weights[a][f], float(w_b)); static term 1 when the static grids are NULL.
+ *   body[a][f] = owner of the corner with the smallest phi_n (ties: the first in cyclic order) when float(w_b) < 1.f, else 0:
+ *   static solids land in row 0 of the sections above.
+ * The static grids are inputs and never written; the outputs are separate arrays, all written everywhere. */
+enum { MGPS_BODY_SPHERE = 0, MGPS_BODY_BOX = 1, MGPS_BODY_GRID = 2 };
+typedef struct mgps_body_shape {
+    int kind;            /* MGPS_BODY_SPHERE, MGPS_BODY_BOX, MGPS_BODY_GRID */
+    double centre[3];    /* world position of the body frame's origin, cells */
+    double rotation[9];  /* row-major, body -> world, orthonormal */
+    double half[3];      /* BOX: half extents; SPHERE: half[0] = radius */
+    const float *sdf;    /* GRID: device array, x fastest, negative inside, cells */
+    int nx, ny, nz;      /* GRID: samples, each >= 2 */
+    double origin[3];    /* GRID: body-frame position of sample (0,0,0) */
+    double spacing;      /* GRID: cells, > 0 */
+} mgps_body_shape;
+typedef struct mgps_raster_desc {
+    int struct_size;                     /* sizeof(mgps_raster_desc) */
+    int gx, gy, gz;                      /* whole grid */
+    int bodies;                          /* 1 .. 255 */
+    const mgps_body_shape *shapes;       /* host, bodies + 1 rows; row 0 is not read */
+    double band, min_open;               /* 2 <= band <= 16 cells; 0 <= min_open < 0.5 */
+    const float *static_solid_phi;       /* device cell grid, or NULL */
+    const float *static_cut_weights[3];  /* device face grids: all three, or all NULL */
+    float *solid_phi;                    /* out, device cell grid */
+    float *cut_weights[3];               /* out, device face grids */
+    int32_t *body[3];                    /* out, device face grids */
+} mgps_raster_desc;
+/* One launch over tiles of 64 x 4 x 4 cells; the shape rows and reach boxes are uploaded per call.  Does not synchronise the
+ * stream; the host table may be reused once the call returns.  Refuses with a message, before any device work: NULL desc or a
+ * struct_size mismatch, a non-positive extent (or more than 262140 cells along y or z: launch-grid dimensions), bodies outside
+ * 1 .. 255, NULL shapes, an unknown kind, a non-finite centre or rotation, |R^T R - I|_inf > 1e-6, a radius or half extent that is
+ * not positive and finite, a GRID body with NULL sdf, a dimension < 2, a spacing that is not positive and finite or a non-finite
+ * origin, band or min_open out of range, a NULL output, static weights only partly given. */
+int mgps_fields_rasterize_bodies(const mgps_raster_desc *d, void *stream);
+/* The same on a slab window, without halo and without communication: the arrays are the window's (z-face grids: the faces
+ * c0 .. c1), positions use the plane index of the whole grid, the bits are those of the whole-grid pass on the rank's planes and
+ * both copies of a cut's z-face plane come out alike.  Refuses also: not a slab window, or not one of the desc's extents. */
+int mgps_fields_slab_rasterize_bodies(const mgps_fields_slab *w, const mgps_raster_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
