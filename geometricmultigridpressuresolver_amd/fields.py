@@ -888,7 +888,7 @@ BODY_SPHERE, BODY_BOX, BODY_GRID = 0, 1, 2
 
 class BodyShape(C.Structure):
     """mgps_body_shape: kind, pose (centre, rotation body -> world) and extent of one rigid body; lengths in cells from the grid's
-    corner, arrays in (x, y, z) order.  Make one with BodyShape.sphere, BodyShape.box or BodyShape.sdf_grid."""
+    corner, arrays in (x, y, z) order.  Make one with BodyShape.sphere, BodyShape.box, BodyShape.sdf_grid or BodyShape.mesh (below)."""
 
     _fields_ = [
         ("kind", C.c_int), ("centre", C.c_double * 3), ("rotation", C.c_double * 9), ("half", C.c_double * 3), ("sdf", C.c_void_p),
@@ -927,6 +927,17 @@ class BodyShape(C.Structure):
         s.sdf, s._keep = sdf.data_ptr(), sdf
         s.origin[:] = [float(v) for v in origin]
         s.spacing = float(spacing)
+        return s
+
+    @classmethod
+    def mesh(cls, centre, vertices, triangles, spacing, band, rotation=None):
+        """The GRID shape of a closed triangle mesh given in the body frame: sizes the sample box
+        (meshSampleBox), samples the signed distance on the device (meshSDF) and keeps the tensor alive, as sdf_grid does.  For a
+        rasteriser band of B cells give band >= B + sqrt(3) * spacing.  `.mass_properties`: (volume, centre, inertia) of
+        meshMassProperties, for unit density in the body frame."""
+        n, origin = meshSampleBox(vertices, spacing, band)
+        s = cls.sdf_grid(centre, meshSDF(vertices, triangles, n, origin, spacing, band), origin, spacing, rotation)
+        s.mass_properties = meshMassProperties(vertices, triangles)
         return s
 
 
@@ -977,3 +988,70 @@ def rasterizeBodiesSlab(d, shapes, band=3.0, min_open=0.0, static_solid_phi=None
     c0 .. c1) with the bits of the whole-grid pass on the rank's planes.  No halo, no communication."""
     return _raster(lib().mgps_fields_slab_rasterize_bodies, d, (d.gz, d.gy, d.gx), d.base_shape, shapes, band, min_open, static_solid_phi,
                    static_cut_weights)
+
+
+# ---- triangle-mesh rigid bodies (include/mgps_fields.h, DESIGN.md section 19) --------------------------------------------------------
+class MeshDesc(C.Structure):
+    """mgps_mesh_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("vertices", C.c_int), ("triangles", C.c_int), ("xyz", C.c_void_p), ("tri", C.c_void_p),
+        ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("origin", C.c_double * 3), ("spacing", C.c_double), ("band", C.c_double),
+        ("sdf", C.c_void_p),
+    ]
+
+
+class MassProperties(C.Structure):
+    """mgps_mass_properties (include/mgps_fields.h)."""
+
+    _fields_ = [("volume", C.c_double), ("centre", C.c_double * 3), ("inertia", C.c_double * 9)]
+
+
+def _mesh(vertices, triangles):
+    import numpy as np
+
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    t = np.ascontiguousarray(triangles, dtype=np.int32)
+    assert v.ndim == 2 and v.shape[1] == 3 and t.ndim == 2 and t.shape[1] == 3, (v.shape, t.shape)
+    return v, t
+
+
+def meshSDF(vertices, triangles, n, origin, spacing, band, device=None):
+    """mgps_fields_mesh_sdf: the body-frame signed distance of the closed mesh (`vertices` (V, 3) float64 in (x, y, z), `triangles`
+    (T, 3) vertex indices, outward orientation) at the samples origin + spacing (i, j, k), `n` = (nx, ny, nz) of them: a CUDA float32
+    tensor (nz, ny, nx), negative inside, exact up to `band` and clamped there.  What BodyShape.sdf_grid takes.  Does not synchronise."""
+    v, t = _mesh(vertices, triangles)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    d = MeshDesc()
+    d.struct_size = C.sizeof(MeshDesc)
+    d.vertices, d.triangles, d.xyz, d.tri = len(v), len(t), v.ctypes.data, t.ctypes.data
+    d.nx, d.ny, d.nz = (int(q) for q in n)
+    d.origin[:] = [float(q) for q in origin]
+    d.spacing, d.band = float(spacing), float(band)
+    nx, ny, nz = (min(max(int(q), 1), 1024) for q in n)  # (the library refuses a dimension outside 2 .. 1024 before it writes)
+    sdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=device)
+    d.sdf = sdf.data_ptr()
+    with torch.cuda.device(device):
+        check(lib().mgps_fields_mesh_sdf(C.byref(d), _stream()))
+    return sdf
+
+
+def meshMassProperties(vertices, triangles):
+    """mgps_mesh_mass_properties: (volume, centre (3,), inertia (3, 3) about the centre) of the closed mesh for unit density, in the
+    body frame, in cells.  Host only."""
+    import numpy as np
+
+    v, t = _mesh(vertices, triangles)
+    m = MassProperties()
+    check(lib().mgps_mesh_mass_properties(len(v), len(t), v.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), C.byref(m)))
+    return m.volume, np.array(m.centre[:]), np.array(m.inertia[:]).reshape(3, 3)
+
+
+def meshSampleBox(vertices, spacing, band):
+    """mgps_mesh_sample_box: ((nx, ny, nz), origin (3,)) of the samples that hold the mesh's bounding box grown by band + spacing"""
+    import numpy as np
+
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    n, origin = (C.c_int * 3)(), (C.c_double * 3)()
+    check(lib().mgps_mesh_sample_box(len(v), v.ctypes.data_as(C.c_void_p), C.c_double(spacing), C.c_double(band), n, origin))
+    return tuple(n[:]), np.array(origin[:])

@@ -589,6 +589,66 @@ int mgps_fields_rasterize_bodies(const mgps_raster_desc *d, void *stream);
  * both copies of a cut's z-face plane come out alike.  Refuses also: not a slab window, or not one of the desc's extents. */
 int mgps_fields_slab_rasterize_bodies(const mgps_fields_slab *w, const mgps_raster_desc *d, void *stream);
 
+/* ---- triangle-mesh rigid bodies: signed distance sampled on the device, mass properties --------------------
+ * A closed triangle mesh, given in the body frame, becomes the float32 samples a MGPS_BODY_GRID body reads; its volume, centre of
+ * mass and inertia tensor give the inv_mass and inv_inertia rows of the coupling sections.  No counterpart in the reference; the
+ * definition here is the contract.
+ *   Sample (i, j, k) sits at s = origin + spacing (i, j, k): one product and one sum per axis, each rounded.  All geometry is fp64,
+ *   the output is rounded to float32 once.
+ *   d(s) = the minimum over all triangles of the exact Euclidean distance from s to the triangle (the closest point may lie on the
+ *   face, an edge or a vertex).   sdf[s] = float(sigma(s) min(d(s), band)), sigma = -1 inside, +1 outside: |sdf| is exact up to band
+ *   and clamped there.
+ *   Inside or outside is the parity of the crossings along +x of the column (y + eps, z + eps^2), eps -> 0+.  For a projected edge
+ *   a -> b: e = (b.y - a.y)(s.z - a.z) - (b.z - a.z)(s.y - a.y), every difference, both products and their difference rounded in
+ *   that order, evaluated with the ends in ascending vertex index and negated when that swaps them, so both triangles on an edge see
+ *   the same number.  The sign of e is the sign of the first non-zero term of (e, -(b.z - a.z), b.y - a.y), with a and b the ends as
+ *   evaluated (negated with e).  A triangle is crossed when its three signs agree; one of zero projected area -- (b.y - a.y)(c.z -
+ *   a.z) - (b.z - a.z)(c.y - a.y) == 0 -- or with e_a + e_b + e_c == 0 never is.  The crossing's depth is x_c = (e_a x_a + e_b x_b +
+ *   e_c x_c) / (e_a + e_b + e_c), each e the edge function of the edge opposite its vertex, summed left to right.  s is inside when
+ *   the number of crossed triangles with x_c > s.x is odd.  (The shift makes the parity right on a closed mesh when a column runs
+ *   exactly through an edge or a vertex; "zero counts as positive" does not.)
+ *   The result is a function of the mesh as a set: a triangle is first turned so that its lowest vertex index comes first, minimum
+ *   and parity do not depend on the triangles' order, and nothing is summed across triangles: the same mesh gives the same bits in
+ *   any triangle order, under any cyclic turn of a triangle's vertices, on every run.
+ *   Band and the rasteriser: a GRID body's trilinear interpolation sees the clamp.  For a rasteriser band of B cells the samples must
+ *   be exact over B plus one sample cell's diagonal: band >= B + sqrt(3) spacing, in a box that holds the mesh's bounding box grown
+ *   by band + spacing, which is what the sample-box entry below returns.
+ *   Slab ranks: nothing to add.  The samples live in the body frame: every rank makes its own copy from the same mesh, with no
+ *   message, and gets the same bits.
+ * Limits: closed, consistently oriented, manifold-edged meshes only (several shells are fine, an inward-oriented shell inside
+ * another is a cavity); no open surfaces, no capsules. */
+typedef struct mgps_mesh_desc {
+    int struct_size;           /* sizeof(mgps_mesh_desc) */
+    int vertices, triangles;   /* counts, each >= 4 */
+    const double *xyz;         /* host, vertices * 3, body frame, cells */
+    const int32_t *tri;        /* host, triangles * 3, vertex indices, outward orientation (counter-clockwise seen from outside) */
+    int nx, ny, nz;            /* samples, each 2 .. 1024 */
+    double origin[3], spacing; /* as mgps_body_shape's GRID fields */
+    double band;               /* body-frame cells, > 0 */
+    float *sdf;                /* out, device, nz * ny * nx, x fastest, negative inside */
+} mgps_mesh_desc;
+/* The mesh is uploaded per call from the host tables with the lists that bin its triangles (the tiles of 64 x 4 x 4 samples a
+ * triangle's box grown by band touches, the tiles of 16 x 16 columns its y-z projection touches), then three launches: list fill,
+ * parity bits, distance with sign and clamp.  Does not synchronise the stream; the host tables may be reused once the call returns.
+ * Refuses with a message, before any device work: NULL desc or a struct_size mismatch, a NULL output, a dimension outside
+ * 2 .. 1024, a spacing or band that is not positive and finite, a non-finite origin, and of the mesh: fewer than 4 vertices or
+ * triangles, NULL tables, a non-finite coordinate, an index out of range, a triangle with a repeated index or of zero area in fp64,
+ * a mesh that is not closed and consistently oriented (every directed edge must occur exactly once and its reverse exactly once:
+ * the message names the first edge that does not), a signed volume that is not positive (inward orientation); lists of more than
+ * 2^31 - 1 entries. */
+int mgps_fields_mesh_sdf(const mgps_mesh_desc *d, void *stream);
+
+/* Volume, centre of mass and inertia tensor about the centre of mass (row-major, symmetric) for unit density, in the body frame, in
+ * cells: fp64 sums of the signed tetrahedra's polynomial integrals over the triangles, taken about the middle of the bounding box.
+ * The caller multiplies volume and inertia by the density; a body's world-frame inverse inertia is R I^-1 R^T.  Host only, no
+ * device call.  Refuses a NULL out and the mesh faults above. */
+typedef struct mgps_mass_properties { double volume, centre[3], inertia[9]; } mgps_mass_properties;
+int mgps_mesh_mass_properties(int vertices, int triangles, const double *xyz, const int32_t *tri, mgps_mass_properties *out);
+/* The sample box of a mesh: out_origin = the bounding box's lower corner - (band + spacing), out_n (x, y, z) the least counts
+ * (>= 2) whose last sample reaches the upper corner + (band + spacing).  Host only.  Refuses NULL pointers, no vertices, a non-finite
+ * coordinate, a spacing or band that is not positive and finite, a box of more than 1024 samples along an axis. */
+int mgps_mesh_sample_box(int vertices, const double *xyz, double spacing, double band, int out_n[3], double out_origin[3]);
+
 #ifdef __cplusplus
 }
 #endif
