@@ -3159,7 +3159,7 @@ __global__ void mixSigmaKernel(const double *__restrict__ maxAbs, float *__restr
 {
     const double m = *maxAbs;
     int e = 0;
-    if (m > 0.0 && m < 1e300) (void)frexp(m, &e);  // m = f 2^e, f in [1/2, 1)
+    if (m > 0.0 && m < 1e300 && frexp(m, &e) == 0.5) --e;  // m = f 2^e, f in [1/2, 1): an exact power of two goes to 1, not to 1/2
     *sigma = ldexpf(1.f, -e);
 }
 int launchMixSigma(void *stream, const double *maxAbsDev, float *sigmaDev)

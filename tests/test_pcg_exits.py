@@ -189,7 +189,9 @@ def test_iteration_cap_from_an_initial_guess(use_gs, use_mg, mode, domain_factor
 @pytest.mark.parametrize("use_gs", [False, True])
 def test_iteration_cap_with_the_binary16_cycle(use_gs, mode, domain_factory, oracle, torch_cuda):
     """options.precision = 1: the binary16 V-cycle is another preconditioner (2e-3 from the oracle's per cycle,
-    tests/test_mixed_precision.py), so iterate k has no derived bound against the oracle's.  The exit itself is checked:
+    tests/test_mixed_precision.py), so iterate k has no derived bound against the UNROUNDED oracle's.  Against the cycle restated
+    with the device's rounding points it has one: tests/test_mixed_restated.py::test_capped_pcg_leaves_the_restated_iterate holds
+    iterate 1 to it (tests/mixed_reference.py).  Here the exit itself is checked:
     outcome, iterations, zeros outside active cells, and that the x handed back is the iterate the stats describe (its
     fp64-evaluated residual against rel_residual_recomputed)."""
     _truncated_against_oracle("solid", 48, use_gs, True, mode, False, domain_factory, oracle, compare_iterate=False, precision=1)
