@@ -93,6 +93,14 @@ def lib():
         L.mgps_destroy.restype = None
         L.mgps_hierarchy_destroy.argtypes = [C.c_void_p]
         L.mgps_hierarchy_destroy.restype = None
+        # deforming mesh colliders (include/mgps_fields.h): desc by reference, stream; the face pass takes sv[3], body[3], bodies,
+        # the shape rows, the velocity rows, then the extents (whole grid) -- or the window first (slab)
+        L.mgps_fields_mesh_sdf_velocity.argtypes = [C.c_void_p, C.c_void_p]
+        L.mgps_fields_mesh_sdf_velocity.restype = C.c_int
+        L.mgps_fields_sampled_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.mgps_fields_sampled_velocity.restype = C.c_int
+        L.mgps_fields_slab_sampled_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mgps_fields_slab_sampled_velocity.restype = C.c_int
         _lib = L
     return _lib
 

@@ -10,6 +10,11 @@
 //                       triangle the column crosses, the mask of the samples below the crossing: one bit per sample, set inside;
 //   meshDistanceKernel  a workgroup per tile walks its list, each thread keeps the least squared distance of its kTZ samples in
 //                       registers, then applies sign and clamp and stores once.  An empty list stores +-band.
+// Deforming colliders: mgps_fields_mesh_sdf_velocity runs the same host pass and the first two launches, and
+// as its third
+//   meshVelocityKernel  the distance kernel's walk, which also keeps the table row of the triangle that attains the minimum (ties by
+//                       the turned index triple, read from the table only on an equal d^2); after the walk a thread classifies the
+//                       closest point on its winner once more for the weights, gathers the three vertex velocities and stores.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -231,6 +236,123 @@ __global__ __launch_bounds__(kThreads) void meshDistanceKernel(MeshArgs a)
     }
 }
 
+// ---- vertex velocities at the closest point ---------------------------------------------------------------------
+struct MeshVelocityArgs {
+    MeshArgs m;              // m.sdf may be NULL
+    const double *velocity;  // per vertex, (x, y, z)
+    float *vel[3];
+};
+
+// The weights (wa, wb, wc) of the closest point of the triangle (a, b, c) to x: the region tests of pointTriangle2, in its order
+__device__ __forceinline__ void closestWeights(const double *p, double x, double y, double z, double &wa, double &wb, double &wc)
+{
+    const auto dot = [](const double u[3], const double w[3]) { return u[0] * w[0] + u[1] * w[1] + u[2] * w[2]; };
+    const double ab[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, ac[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+    const double ap[3] = {x - p[0], y - p[1], z - p[2]};
+    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
+    wa = 1.0, wb = 0.0, wc = 0.0;
+    if (d1 <= 0.0 && d2 <= 0.0) return;
+    const double bp[3] = {x - p[3], y - p[4], z - p[5]};
+    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
+    if (d3 >= 0.0 && d4 <= d3) {
+        wa = 0.0, wb = 1.0;
+        return;
+    }
+    if (d1 * d4 - d3 * d2 <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
+        const double v = d1 / (d1 - d3);
+        wa = 1.0 - v, wb = v;
+        return;
+    }
+    const double cp[3] = {x - p[6], y - p[7], z - p[8]};
+    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
+    if (d6 >= 0.0 && d5 <= d6) {
+        wa = 0.0, wc = 1.0;
+        return;
+    }
+    if (d5 * d2 - d1 * d6 <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
+        const double w = d2 / (d2 - d6);
+        wa = 1.0 - w, wc = w;
+        return;
+    }
+    if (d3 * d6 - d5 * d4 <= 0.0 && d4 - d3 >= 0.0 && d5 - d6 >= 0.0) {
+        const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+        wa = 0.0, wb = 1.0 - w, wc = w;
+        return;
+    }
+    const double va = d3 * d6 - d5 * d4, vb = d5 * d2 - d1 * d6, vc = d1 * d4 - d3 * d2;
+    const double den = (va + vb) + vc;
+    wb = vb / den, wc = vc / den;
+    wa = (1.0 - wb) - wc;
+}
+
+// row r comes before row w in the order of the turned index triples (two rows never hold the same triple on a checked mesh)
+__device__ __forceinline__ bool keyBefore(const MeshTri *table, int r, int w)
+{
+    const int32_t *a = table[r].v, *b = table[w].v;
+    if (a[0] != b[0]) return a[0] < b[0];
+    if (a[1] != b[1]) return a[1] < b[1];
+    return a[2] < b[2];
+}
+
+__global__ __launch_bounds__(kThreads) void meshVelocityKernel(MeshVelocityArgs va)
+{
+    const MeshArgs &a = va.m;
+    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
+    const int i = int(blockIdx.x) * kTX + lane, j = int(blockIdx.y) * kTY + wave, k0 = int(blockIdx.z) * kTZ;
+    // the samples of meshDistanceKernel's thread, and its walk: d^2 by the same expressions, so its minimum is that kernel's
+    const double x = samplePos(a.origin[0], a.spacing, min(i, a.nx - 1)), y = samplePos(a.origin[1], a.spacing, min(j, a.ny - 1));
+    double z[kTZ], best[kTZ];
+    int winner[kTZ];
+#pragma unroll
+    for (int kk = 0; kk < kTZ; ++kk) {
+        z[kk] = samplePos(a.origin[2], a.spacing, min(k0 + kk, a.nz - 1));
+        best[kk] = std::numeric_limits<double>::infinity();
+        winner[kk] = -1;
+    }
+    const int bin = (int(blockIdx.z) * a.tilesY + int(blockIdx.y)) * a.tilesX + int(blockIdx.x);
+    const int begin = a.offsets[bin], end = a.offsets[bin + 1];
+    for (int q = begin; q < end; ++q) {
+        const int r = __builtin_amdgcn_readfirstlane(a.list[q]);
+        const double *p = a.table[r].p;
+        const double ab[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, ac[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+        const double n[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
+        const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+#pragma unroll
+        for (int kk = 0; kk < kTZ; ++kk) {
+            const double d2 = pointTriangle2(p, ab, ac, n, nn, x, y, z[kk]);
+            // (an equal d^2 is rare -- a vertex's fan, an edge's pair: only then are the keys read)
+            bool take = d2 < best[kk];
+            if (d2 == best[kk] && winner[kk] >= 0) take = keyBefore(a.table, r, winner[kk]);
+            best[kk] = take ? d2 : best[kk];
+            winner[kk] = take ? r : winner[kk];
+        }
+    }
+    if (i >= a.nx || j >= a.ny) return;
+#pragma unroll
+    for (int kk = 0; kk < kTZ; ++kk) {
+        const int k = k0 + kk;
+        if (k >= a.nz) break;
+        const size_t row = size_t(k) * a.ny + j;
+        const double root = sqrt(best[kk]);
+        if (a.sdf) {
+            const bool in = (a.inside[row * a.words + blockIdx.x] >> lane) & 1ull;
+            const double d = fmin(root, a.band);
+            a.sdf[row * a.nx + i] = float(in ? -d : d);
+        }
+        float out[3] = {0.f, 0.f, 0.f};
+        if (root < a.band && winner[kk] >= 0) {  // (beyond band the tile's list no longer holds every triangle)
+            const MeshTri &T = a.table[winner[kk]];
+            double wa, wb, wc;
+            closestWeights(T.p, x, y, z[kk], wa, wb, wc);
+            const double *Va = va.velocity + 3 * size_t(T.v[0]), *Vb = va.velocity + 3 * size_t(T.v[1]), *Vc = va.velocity + 3 * size_t(T.v[2]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c] = float((wa * Va[c] + wb * Vb[c]) + wc * Vc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) va.vel[c][row * a.nx + i] = out[c];
+    }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 bool allFinite(const double *v, size_t n)
 {
@@ -355,48 +477,11 @@ bool sampleRange(double from, double to, double origin, double spacing, int n, i
 }
 
 size_t roundUp(size_t v) { return (v + 255) / 256 * 256; }
-}  // namespace
 
-extern "C" {
-
-int mgps_mesh_mass_properties(int vertices, int triangles, const double *xyz, const int32_t *tri, mgps_mass_properties *out)
-try {
-    const char *fn = "mgps_mesh_mass_properties";
-    if (!out) return refuse(fn, "out is NULL");
-    return checkedMass(fn, vertices, triangles, xyz, tri, out, nullptr);
-}
-MGPS_API_CATCH(nullptr)
-
-int mgps_mesh_sample_box(int vertices, const double *xyz, double spacing, double band, int out_n[3], double out_origin[3])
-try {
-    const char *fn = "mgps_mesh_sample_box";
-    if (!xyz || !out_n || !out_origin) return refuse(fn, "xyz, out_n or out_origin is NULL");
-    if (vertices < 1) return refuse(fn, "no vertices");
-    if (!allFinite(xyz, size_t(vertices) * 3)) return refuse(fn, "non-finite coordinate");
-    if (!(spacing > 0 && std::isfinite(spacing))) return refuse(fn, "the spacing must be positive and finite");
-    if (!(band > 0 && std::isfinite(band))) return refuse(fn, "band must be positive and finite");
-    const double grow = band + spacing;
-    int n[3];
-    double origin[3];
-    for (int c = 0; c < 3; ++c) {
-        double lo = xyz[c], hi = xyz[c];
-        for (size_t v = 1; v < size_t(vertices); ++v) lo = std::min(lo, xyz[3 * v + c]), hi = std::max(hi, xyz[3 * v + c]);
-        origin[c] = lo - grow;
-        const double steps = std::ceil((hi + grow - origin[c]) / spacing);
-        if (!(steps + 1.0 <= double(kMaxSamples)))
-            return refuse(fn, "the box needs more than " + std::to_string(kMaxSamples) + " samples along an axis: choose a larger spacing");
-        n[c] = std::max(int(steps) + 1, 2);
-    }
-    for (int c = 0; c < 3; ++c) out_n[c] = n[c], out_origin[c] = origin[c];
-    return MGPS_OK;
-}
-MGPS_API_CATCH(nullptr)
-
-int mgps_fields_mesh_sdf(const mgps_mesh_desc *d, void *stream)
-try {
-    const char *fn = "mgps_fields_mesh_sdf";
-    if (!d || d->struct_size != int(sizeof(mgps_mesh_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_mesh_desc)");
-    if (!d->sdf) return refuse(fn, "sdf (output) is NULL");
+// One mesh pass: the checks both entries share, the bins, the upload and the three launches.  `velocity` NULL: the signed distance
+// alone (meshDistanceKernel); else the third launch is meshVelocityKernel, which writes vel and, where d->sdf is given, the same sdf
+int runMesh(const char *fn, const mgps_mesh_desc *d, const double *velocity, float *const vel[3], void *stream)
+{
     for (const int n : {d->nx, d->ny, d->nz})
         if (n < 2 || n > kMaxSamples) return refuse(fn, "every sample dimension must lie in 2 .. " + std::to_string(kMaxSamples));
     if (!(d->spacing > 0 && std::isfinite(d->spacing))) return refuse(fn, "the spacing must be positive and finite");
@@ -405,6 +490,7 @@ try {
     std::vector<int32_t> turned;
     mgps_mass_properties mass;
     if (int rc = checkedMass(fn, d->vertices, d->triangles, d->xyz, d->tri, &mass, &turned); rc != MGPS_OK) return rc;
+    if (velocity && !allFinite(velocity, size_t(d->vertices) * 3)) return refuse(fn, "non-finite vertex velocity");
 
     // the bins of every triangle, and from them the lists' offsets
     MeshArgs a{};
@@ -458,7 +544,8 @@ try {
     const size_t xyzBytes = size_t(d->vertices) * 3 * sizeof(double), triBytes = nt * 3 * sizeof(int32_t), binBytes = nt * sizeof(TriBins);
     const size_t offBytes = offsets.size() * sizeof(int);
     const size_t atXyz = 0, atTri = atXyz + roundUp(xyzBytes), atBins = atTri + roundUp(triBytes), atOff = atBins + roundUp(binBytes);
-    const size_t hostBytes = atOff + roundUp(offBytes);
+    const size_t atVel = atOff + roundUp(offBytes);  // (the vertex velocities, where given, as the host block's last part)
+    const size_t hostBytes = atVel + (velocity ? roundUp(xyzBytes) : 0);
     const size_t atTable = hostBytes, atCursor = atTable + roundUp(nt * sizeof(MeshTri)), atList = atCursor + roundUp(size_t(binCount) * sizeof(int));
     const size_t atInside = atList + roundUp(std::max(entries, size_t(1)) * sizeof(int));
     const size_t bytes = atInside + roundUp(size_t(d->nz) * d->ny * a.words * sizeof(unsigned long long));
@@ -467,6 +554,7 @@ try {
     std::copy_n(reinterpret_cast<const unsigned char *>(turned.data()), triBytes, stage.data() + atTri);
     std::copy_n(reinterpret_cast<const unsigned char *>(bins.data()), binBytes, stage.data() + atBins);
     std::copy_n(reinterpret_cast<const unsigned char *>(offsets.data()), offBytes, stage.data() + atOff);
+    if (velocity) std::copy_n(reinterpret_cast<const unsigned char *>(velocity), xyzBytes, stage.data() + atVel);
 
     const hipStream_t st = static_cast<hipStream_t>(stream);
     void *dev = nullptr;
@@ -487,11 +575,79 @@ try {
     if (rc == MGPS_OK) {
         meshFillKernel<<<unsigned((nt + kThreads - 1) / kThreads), kThreads, 0, st>>>(a);
         meshSignKernel<<<dim3(unsigned(a.words), unsigned(a.colsY), unsigned(a.colsZ)), kThreads, 0, st>>>(a);
-        meshDistanceKernel<<<dim3(unsigned(a.tilesX), unsigned(a.tilesY), unsigned(a.tilesZ)), kThreads, 0, st>>>(a);
+        const dim3 tilesGrid(unsigned(a.tilesX), unsigned(a.tilesY), unsigned(a.tilesZ));
+        if (velocity) {
+            MeshVelocityArgs va{};
+            va.m = a, va.velocity = reinterpret_cast<const double *>(base + atVel);
+            for (int c = 0; c < 3; ++c) va.vel[c] = vel[c];
+            meshVelocityKernel<<<tilesGrid, kThreads, 0, st>>>(va);
+        } else {
+            meshDistanceKernel<<<tilesGrid, kThreads, 0, st>>>(a);
+        }
         rc = hipStatus(fn, hipGetLastError());
     }
     const int freed = hipStatus(fn, hipFreeAsync(dev, st));
     return rc != MGPS_OK ? rc : freed;
+}
+}  // namespace
+
+extern "C" {
+
+int mgps_mesh_mass_properties(int vertices, int triangles, const double *xyz, const int32_t *tri, mgps_mass_properties *out)
+try {
+    const char *fn = "mgps_mesh_mass_properties";
+    if (!out) return refuse(fn, "out is NULL");
+    return checkedMass(fn, vertices, triangles, xyz, tri, out, nullptr);
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_mesh_sample_box(int vertices, const double *xyz, double spacing, double band, int out_n[3], double out_origin[3])
+try {
+    const char *fn = "mgps_mesh_sample_box";
+    if (!xyz || !out_n || !out_origin) return refuse(fn, "xyz, out_n or out_origin is NULL");
+    if (vertices < 1) return refuse(fn, "no vertices");
+    if (!allFinite(xyz, size_t(vertices) * 3)) return refuse(fn, "non-finite coordinate");
+    if (!(spacing > 0 && std::isfinite(spacing))) return refuse(fn, "the spacing must be positive and finite");
+    if (!(band > 0 && std::isfinite(band))) return refuse(fn, "band must be positive and finite");
+    const double grow = band + spacing;
+    int n[3];
+    double origin[3];
+    for (int c = 0; c < 3; ++c) {
+        double lo = xyz[c], hi = xyz[c];
+        for (size_t v = 1; v < size_t(vertices); ++v) lo = std::min(lo, xyz[3 * v + c]), hi = std::max(hi, xyz[3 * v + c]);
+        origin[c] = lo - grow;
+        const double steps = std::ceil((hi + grow - origin[c]) / spacing);
+        if (!(steps + 1.0 <= double(kMaxSamples)))
+            return refuse(fn, "the box needs more than " + std::to_string(kMaxSamples) + " samples along an axis: choose a larger spacing");
+        n[c] = std::max(int(steps) + 1, 2);
+    }
+    for (int c = 0; c < 3; ++c) out_n[c] = n[c], out_origin[c] = origin[c];
+    return MGPS_OK;
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_mesh_sdf(const mgps_mesh_desc *d, void *stream)
+try {
+    const char *fn = "mgps_fields_mesh_sdf";
+    if (!d || d->struct_size != int(sizeof(mgps_mesh_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_mesh_desc)");
+    if (!d->sdf) return refuse(fn, "sdf (output) is NULL");
+    return runMesh(fn, d, nullptr, nullptr, stream);
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_mesh_sdf_velocity(const mgps_mesh_velocity_desc *d, void *stream)
+try {
+    const char *fn = "mgps_fields_mesh_sdf_velocity";
+    if (!d || d->struct_size != int(sizeof(mgps_mesh_velocity_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_mesh_velocity_desc)");
+    if (!d->velocity) return refuse(fn, "velocity is NULL");
+    for (int c = 0; c < 3; ++c)
+        if (!d->vel[c]) return refuse(fn, "vel (output): three grids are required");
+    mgps_mesh_desc m{};
+    m.struct_size = int(sizeof(mgps_mesh_desc));
+    m.vertices = d->vertices, m.triangles = d->triangles, m.xyz = d->xyz, m.tri = d->tri;
+    m.nx = d->nx, m.ny = d->ny, m.nz = d->nz, m.spacing = d->spacing, m.band = d->band, m.sdf = d->sdf;
+    for (int c = 0; c < 3; ++c) m.origin[c] = d->origin[c];
+    return runMesh(fn, &m, d->velocity, d->vel, stream);
 }
 MGPS_API_CATCH(nullptr)
 }

@@ -372,6 +372,144 @@ int runRaster(const char *fn, const mgps_raster_desc *d, int c0, int planes, hip
     const int freed = hipStatus(fn, hipFreeAsync(dev, st));
     return rc != MGPS_OK ? rc : freed;
 }
+
+// ---- velocity samples of deforming colliders on the face grids (include/mgps_fields.h, "deforming mesh colliders"; DESIGN.md
+// section 20) -----------------------------------------------------------------------------------------------------------------------
+// one row of the device table: the pose and sample box of a GRID body, its three sample arrays and the motion of its frame
+struct SampledBody {
+    double centre[3], rot[9], origin[3], spacing, motion[6];
+    const float *vel[3];  // all NULL: the body's faces are not written
+    int nx, ny, nz, pad;
+};
+
+struct SampledArgs {
+    int gx, gy, planes, c0;  // as RasterArgs
+    int bodies;
+    const SampledBody *table;  // bodies + 1 rows
+    float *sv[3];
+    const int32_t *body[3];
+};
+
+// the value of face f of `axis` at (i, j, k) of the box, owned by body b
+__device__ __forceinline__ float sampledFace(const SampledBody &b, int axis, int i, int j, int kg)
+{
+    double pos[3] = {i + 0.5, j + 0.5, kg + 0.5};
+    const int ijk[3] = {i, j, kg};
+    pos[axis] = double(ijk[axis]);
+    const double dx = pos[0] - b.centre[0], dy = pos[1] - b.centre[1], dz = pos[2] - b.centre[2];
+    const double p[3] = {b.rot[0] * dx + b.rot[3] * dy + b.rot[6] * dz, b.rot[1] * dx + b.rot[4] * dy + b.rot[7] * dz,
+                         b.rot[2] * dx + b.rot[5] * dy + b.rot[8] * dz};  // R^T (x - centre)
+    const int n[3] = {b.nx, b.ny, b.nz};
+    int i0[3];
+    double f[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double g = fmin(fmax((p[a] - b.origin[a]) / b.spacing, 0.0), double(n[a] - 1));
+        i0[a] = min(int(floor(g)), n[a] - 2);
+        f[a] = g - double(i0[a]);
+    }
+    const size_t at = (size_t(i0[2]) * b.ny + i0[1]) * b.nx + i0[0], sy = size_t(b.nx), sz = size_t(b.nx) * b.ny;
+    const auto lerp = [](double t, double u, double v) { return (1.0 - t) * u + t * v; };
+    double u[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float *s = b.vel[c] + at;
+        const double x00 = lerp(f[0], double(s[0]), double(s[1])), x10 = lerp(f[0], double(s[sy]), double(s[sy + 1]));
+        const double x01 = lerp(f[0], double(s[sz]), double(s[sz + 1])), x11 = lerp(f[0], double(s[sz + sy]), double(s[sz + sy + 1]));
+        u[c] = lerp(f[2], lerp(f[1], x00, x10), lerp(f[1], x01, x11));
+    }
+    const double d[3] = {dx, dy, dz};
+    const int uu = (axis + 1) % 3, vv = (axis + 2) % 3;
+    const double *m = b.motion;
+    const double frame = m[axis] + m[3 + uu] * d[vv] - m[3 + vv] * d[uu];  // (U + omega x (x_f - centre))_axis, as the rigid pass forms it
+    const double *R = b.rot + 3 * axis;
+    return float(((R[0] * u[0] + R[1] * u[1]) + R[2] * u[2]) + frame);
+}
+
+// A thread per cell and kTZ planes, as the rasteriser's tiles: a cell's backward face per axis, and the forward one where the box
+// ends.  Three id loads per cell; the table row and the samples are read only where a sampled body owns the face
+__global__ __launch_bounds__(kThreads) void sampledVelocityKernel(SampledArgs s)
+{
+    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
+    const int i = int(blockIdx.x) * kTX + lane, j = int(blockIdx.y) * kTY + wave, k0 = int(blockIdx.z) * kTZ;
+    if (i >= s.gx || j >= s.gy) return;
+    RasterArgs box{};  // (CellFaces reads the box's extents only)
+    box.gx = s.gx, box.gy = s.gy, box.planes = s.planes;
+#pragma unroll
+    for (int kk = 0; kk < kTZ; ++kk) {
+        const int k = k0 + kk;
+        if (k >= s.planes) break;
+        const CellFaces at(box, i, j, k);
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax)
+            for (int side = 0; side <= int(at.more[ax]); ++side) {
+                const size_t f = at.f[ax] + size_t(side) * at.step[ax];
+                const int r = s.body[ax][f];
+                if (r < 1 || r > s.bodies) continue;
+                const SampledBody &b = s.table[r];
+                if (!b.vel[0]) continue;
+                s.sv[ax][f] = sampledFace(b, ax, i + (ax == 0 ? side : 0), j + (ax == 1 ? side : 0), k + s.c0 + (ax == 2 ? side : 0));
+            }
+    }
+}
+
+// what both entries refuse, before any device work
+int checkSampled(const char *fn, float *const sv[3], const int32_t *const body[3], int bodies, const mgps_body_shape *shapes,
+                 const mgps_body_velocity *velocities, int gx, int gy, int gz)
+{
+    if (bodies < 1 || bodies > 255) return refuse(fn, "bodies = " + std::to_string(bodies) + " is outside 1 .. 255");
+    if (gx <= 0 || gy <= 0 || gz <= 0)
+        return refuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(gx) + ", " + std::to_string(gy) + ", " + std::to_string(gz) + ")");
+    if ((gy + kTY - 1) / kTY > 65535 || (gz + kTZ - 1) / kTZ > 65535) return refuse(fn, "more than 262140 cells along y or z");
+    if (!sv || !sv[0] || !sv[1] || !sv[2]) return refuse(fn, "solid velocity: three grids are required");
+    if (!body || !body[0] || !body[1] || !body[2]) return refuse(fn, "body: three grids are required");
+    if (!shapes) return refuse(fn, "shapes is NULL");
+    if (!velocities) return refuse(fn, "velocities is NULL");
+    for (int r = 1; r <= bodies; ++r) {
+        if (int rc = checkShape(fn, r, shapes[r]); rc != MGPS_OK) return rc;
+        const mgps_body_velocity &v = velocities[r];
+        const std::string who = "body " + std::to_string(r) + ": ";
+        const int given = (v.vel[0] != nullptr) + (v.vel[1] != nullptr) + (v.vel[2] != nullptr);
+        if (given != 0 && given != 3) return refuse(fn, who + "vel: all three sample arrays, or none");
+        if (given == 0) continue;
+        if (shapes[r].kind != MGPS_BODY_GRID) return refuse(fn, who + "velocity samples need a GRID body (kind = " + std::to_string(shapes[r].kind) + ")");
+        if (!finite3(v.motion, 6)) return refuse(fn, who + "non-finite motion");
+    }
+    return MGPS_OK;
+}
+
+// the launch on the planes [c0, c0 + planes) of checked arguments; the table goes up as the rasteriser's does
+int runSampled(const char *fn, float *const sv[3], const int32_t *const body[3], int bodies, const mgps_body_shape *shapes,
+               const mgps_body_velocity *velocities, int gx, int gy, int c0, int planes, hipStream_t st)
+{
+    std::vector<SampledBody> rows(size_t(bodies) + 1);
+    for (int r = 1; r <= bodies; ++r) {
+        const mgps_body_shape &s = shapes[r];
+        SampledBody &b = rows[size_t(r)];
+        b = SampledBody{};
+        for (int q = 0; q < 3; ++q) b.centre[q] = s.centre[q], b.origin[q] = s.origin[q], b.vel[q] = velocities[r].vel[q];
+        for (int q = 0; q < 9; ++q) b.rot[q] = s.rotation[q];
+        for (int q = 0; q < 6; ++q) b.motion[q] = velocities[r].motion[q];
+        b.spacing = s.spacing, b.nx = s.nx, b.ny = s.ny, b.nz = s.nz;
+    }
+    void *dev = nullptr;
+    if (const hipError_t e = hipMallocAsync(&dev, rows.size() * sizeof(SampledBody), st); e != hipSuccess) {
+        (void)hipGetLastError();
+        setLastGlobalError(std::string(fn) + ": device allocation failed (" + hipGetErrorString(e) + ")");
+        return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MGPS_ERR_NO_DEVICE : MGPS_ERR_ALLOC;
+    }
+    int rc = hipStatus(fn, hipMemcpyAsync(dev, rows.data(), rows.size() * sizeof(SampledBody), hipMemcpyHostToDevice, st));
+    if (rc == MGPS_OK) {
+        SampledArgs a{};
+        a.gx = gx, a.gy = gy, a.planes = planes, a.c0 = c0, a.bodies = bodies, a.table = static_cast<const SampledBody *>(dev);
+        for (int q = 0; q < 3; ++q) a.sv[q] = sv[q], a.body[q] = body[q];
+        const dim3 grid(unsigned((gx + kTX - 1) / kTX), unsigned((gy + kTY - 1) / kTY), unsigned((planes + kTZ - 1) / kTZ));
+        sampledVelocityKernel<<<grid, kThreads, 0, st>>>(a);
+        rc = hipStatus(fn, hipGetLastError());
+    }
+    const int freed = hipStatus(fn, hipFreeAsync(dev, st));
+    return rc != MGPS_OK ? rc : freed;
+}
 }  // namespace
 
 extern "C" {
@@ -391,6 +529,25 @@ try {
     if (!fieldsSlabWindow(w, fn)) return MGPS_ERR_INVALID_ARGUMENT;
     if (w->gx != d->gx || w->gy != d->gy || w->gz != d->gz) return refuse(fn, "the window is not one of the desc's extents (gx, gy, gz are the whole grid's in both)");
     return runRaster(fn, d, w->c0, w->c1 - w->c0, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_sampled_velocity(float *const sv[3], const int32_t *const body[3], int bodies, const mgps_body_shape *shapes,
+                                 const mgps_body_velocity *velocities, int gx, int gy, int gz, void *stream)
+try {
+    const char *fn = "mgps_fields_sampled_velocity";
+    if (int rc = checkSampled(fn, sv, body, bodies, shapes, velocities, gx, gy, gz); rc != MGPS_OK) return rc;
+    return runSampled(fn, sv, body, bodies, shapes, velocities, gx, gy, 0, gz, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_sampled_velocity(const mgps_fields_slab *w, float *const sv[3], const int32_t *const body[3], int bodies,
+                                      const mgps_body_shape *shapes, const mgps_body_velocity *velocities, void *stream)
+try {
+    const char *fn = "mgps_fields_slab_sampled_velocity";
+    if (!fieldsSlabWindow(w, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    if (int rc = checkSampled(fn, sv, body, bodies, shapes, velocities, w->gx, w->gy, w->gz); rc != MGPS_OK) return rc;
+    return runSampled(fn, sv, body, bodies, shapes, velocities, w->gx, w->gy, w->c0, w->c1 - w->c0, static_cast<hipStream_t>(stream));
 }
 MGPS_API_CATCH(nullptr)
 }

@@ -930,13 +930,21 @@ class BodyShape(C.Structure):
         return s
 
     @classmethod
-    def mesh(cls, centre, vertices, triangles, spacing, band, rotation=None):
+    def mesh(cls, centre, vertices, triangles, spacing, band, rotation=None, vertex_velocities=None):
         """The GRID shape of a closed triangle mesh given in the body frame: sizes the sample box
         (meshSampleBox), samples the signed distance on the device (meshSDF) and keeps the tensor alive, as sdf_grid does.  For a
         rasteriser band of B cells give band >= B + sqrt(3) * spacing.  `.mass_properties`: (volume, centre, inertia) of
-        meshMassProperties, for unit density in the body frame."""
+        meshMassProperties, for unit density in the body frame.
+        `vertex_velocities` ((V, 3), body frame, cells per step): a deforming collider.  The samples come
+        from meshSDFVelocity and `.velocity`, the (3, nz, ny, nx) velocity samples sampledVelocity reads, is kept alive with the
+        shape."""
         n, origin = meshSampleBox(vertices, spacing, band)
-        s = cls.sdf_grid(centre, meshSDF(vertices, triangles, n, origin, spacing, band), origin, spacing, rotation)
+        if vertex_velocities is None:
+            s = cls.sdf_grid(centre, meshSDF(vertices, triangles, n, origin, spacing, band), origin, spacing, rotation)
+        else:
+            sdf, vel = meshSDFVelocity(vertices, triangles, vertex_velocities, n, origin, spacing, band)
+            s = cls.sdf_grid(centre, sdf, origin, spacing, rotation)
+            s.velocity = vel
         s.mass_properties = meshMassProperties(vertices, triangles)
         return s
 
@@ -1055,3 +1063,92 @@ def meshSampleBox(vertices, spacing, band):
     n, origin = (C.c_int * 3)(), (C.c_double * 3)()
     check(lib().mgps_mesh_sample_box(len(v), v.ctypes.data_as(C.c_void_p), C.c_double(spacing), C.c_double(band), n, origin))
     return tuple(n[:]), np.array(origin[:])
+
+
+# ---- deforming mesh colliders: vertex velocities to the solid-velocity grids (include/mgps_fields.h) ----------
+class MeshVelocityDesc(C.Structure):
+    """mgps_mesh_velocity_desc (include/mgps_fields.h): mgps_mesh_desc's fields, then the vertex velocities and the outputs."""
+
+    _fields_ = MeshDesc._fields_ + [("velocity", C.c_void_p), ("vel", C.c_void_p * 3)]
+
+
+class BodyVelocity(C.Structure):
+    """mgps_body_velocity (include/mgps_fields.h)."""
+
+    _fields_ = [("vel", C.c_void_p * 3), ("motion", C.c_double * 6)]
+
+
+def meshSDFVelocity(vertices, triangles, vertex_velocities, n, origin, spacing, band, device=None):
+    """mgps_fields_mesh_sdf_velocity: (sdf, vel) of a deforming closed mesh at the samples of meshSDF.  `sdf` holds meshSDF's bits;
+    `vel` is a CUDA float32 tensor (3, nz, ny, nx): the vertex velocities (`vertex_velocities` (V, 3) float64, body frame, cells per
+    step) interpolated at the closest point of the mesh, 0 where the distance is not below `band`.  Does not synchronise."""
+    import numpy as np
+
+    v, t = _mesh(vertices, triangles)
+    w = np.ascontiguousarray(vertex_velocities, dtype=np.float64)
+    assert w.shape == v.shape, (w.shape, v.shape)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    d = MeshVelocityDesc()
+    d.struct_size = C.sizeof(MeshVelocityDesc)
+    d.vertices, d.triangles, d.xyz, d.tri, d.velocity = len(v), len(t), v.ctypes.data, t.ctypes.data, w.ctypes.data
+    d.nx, d.ny, d.nz = (int(q) for q in n)
+    d.origin[:] = [float(q) for q in origin]
+    d.spacing, d.band = float(spacing), float(band)
+    nx, ny, nz = (min(max(int(q), 1), 1024) for q in n)  # (the library refuses a dimension outside 2 .. 1024 before it writes)
+    sdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=device)
+    vel = torch.empty((3, nz, ny, nx), dtype=torch.float32, device=device)
+    d.sdf = sdf.data_ptr()
+    for c in range(3):
+        d.vel[c] = vel[c].data_ptr()
+    with torch.cuda.device(device):
+        check(lib().mgps_fields_mesh_sdf_velocity(C.byref(d), _stream()))
+    return sdf, vel
+
+
+def _sampled_rows(shapes, frame_motions):
+    """(shape rows, velocity rows, what keeps them alive) of `shapes` (body r is shapes[r - 1]); row 0 is not read"""
+    import numpy as np
+
+    bodies = len(shapes)
+    motions = np.zeros((bodies, 6)) if frame_motions is None else np.ascontiguousarray(frame_motions, dtype=np.float64).reshape(-1, 6)
+    assert motions.shape[0] == bodies, (motions.shape, bodies)
+    rows = (BodyShape * (bodies + 1))(BodyShape(), *shapes)
+    vrows = (BodyVelocity * (bodies + 1))()
+    for r, s in enumerate(shapes, start=1):
+        vel = getattr(s, "velocity", None)
+        if vel is not None:
+            assert vel.is_cuda and vel.dtype == torch.float32 and tuple(vel.shape) == (3, s.nz, s.ny, s.nx), (vel.shape, vel.dtype)
+            for c in range(3):
+                assert vel[c].is_contiguous()
+                vrows[r].vel[c] = vel[c].data_ptr()
+        vrows[r].motion[:] = [float(q) for q in motions[r - 1]]
+    return rows, vrows
+
+
+def sampledVelocity(solid_velocity, body, shapes, frame_motions=None):
+    """mgps_fields_sampled_velocity (in place on the three solid-velocity face grids): on the faces whose body id r is in
+    1 .. len(shapes) and whose shape (shapes[r - 1], made by BodyShape.mesh with vertex_velocities) carries `.velocity`, the body's
+    velocity samples interpolated at the face, turned into the world frame, plus the motion of the body frame (`frame_motions`:
+    (len(shapes), 6) host array, U then omega per body, about the shape's centre; None: at rest).  Every other face keeps its
+    value: call rigidVelocity first and this after it.  Does not synchronise."""
+    shape = list(solid_velocity[2].shape)
+    shape[0] -= 1
+    faces = _face3(tuple(shape))
+    sv = [_chk(solid_velocity[a], faces[a], torch.float32) for a in range(3)]
+    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
+    rows, vrows = _sampled_rows(shapes, frame_motions)
+    with torch.cuda.device(sv[0].device):
+        check(lib().mgps_fields_sampled_velocity(_arr3(sv), _arr3(ids), len(shapes), rows, vrows, *_g(tuple(shape)), _stream()))
+    return solid_velocity
+
+
+def sampledVelocitySlab(d, solid_velocity, body, shapes, frame_motions=None):
+    """mgps_fields_slab_sampled_velocity: sampledVelocity on the window `d` (in place on the window's three face grids; positions use
+    the whole grid's plane index): the bits of the whole-grid pass on the rank's planes.  No halo, no communication."""
+    faces = _face3(d.base_shape)
+    sv = [_chk(solid_velocity[a], faces[a], torch.float32) for a in range(3)]
+    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
+    rows, vrows = _sampled_rows(shapes, frame_motions)
+    with torch.cuda.device(sv[0].device):
+        check(lib().mgps_fields_slab_sampled_velocity(C.byref(d), _arr3(sv), _arr3(ids), len(shapes), rows, vrows, _stream()))
+    return solid_velocity

@@ -616,7 +616,7 @@ int mgps_fields_slab_rasterize_bodies(const mgps_fields_slab *w, const mgps_rast
  *   Slab ranks: nothing to add.  The samples live in the body frame: every rank makes its own copy from the same mesh, with no
  *   message, and gets the same bits.
  * Limits: closed, consistently oriented, manifold-edged meshes only (several shells are fine, an inward-oriented shell inside
- * another is a cavity); no open surfaces, no capsules. */
+ * another is a cavity); no open surfaces, no capsules.  (A deforming mesh's vertex velocities: the section after this one.) */
 typedef struct mgps_mesh_desc {
     int struct_size;           /* sizeof(mgps_mesh_desc) */
     int vertices, triangles;   /* counts, each >= 4 */
@@ -648,6 +648,74 @@ int mgps_mesh_mass_properties(int vertices, int triangles, const double *xyz, co
  * (>= 2) whose last sample reaches the upper corner + (band + spacing).  Host only.  Refuses NULL pointers, no vertices, a non-finite
  * coordinate, a spacing or band that is not positive and finite, a box of more than 1024 samples along an axis. */
 int mgps_mesh_sample_box(int vertices, const double *xyz, double spacing, double band, int out_n[3], double out_origin[3]);
+
+/* ---- deforming mesh colliders: vertex velocities to the solid-velocity grids --------------------------------
+ * An animated, deforming closed mesh is a scripted solid whose surface moves with per-vertex velocities.  Two device passes, split
+ * as the two sections above are: mesh -> body-frame velocity samples beside the SDF samples, then samples -> the three
+ * solid-velocity face grids.  No counterpart in the reference; the definition here is the contract.
+ *   Samples.  For a sample s (section 19's positions) and a turned triangle T = (a, b, c), d2_T(s) is section 19's squared distance,
+ *   formed by the distance pass's own expressions, so min_T d2_T is the number whose root the SDF stores.  The closest point's
+ *   weights (wa, wb, wc) come from the same region tests in the same order, with d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp,
+ *   d5 = ab.cp, d6 = ac.cp:
+ *     vertex a (1, 0, 0); vertex b (0, 1, 0); edge ab (1 - v, v, 0), v = d1 / (d1 - d3); vertex c (0, 0, 1);
+ *     edge ac (1 - w, 0, w), w = d2 / (d2 - d6); edge bc (0, 1 - w, w), w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
+ *     face: va = d3 d6 - d5 d4, vb = d5 d2 - d1 d6, vc = d1 d4 - d3 d2, den = (va + vb) + vc, wb = vb / den, wc = vc / den,
+ *     wa = (1 - wb) - wc.
+ *   The winner is the triangle with the least (d2, v0, v1, v2) in lexicographic order, v the turned index triple: a strict order on
+ *   the mesh as a set, so the triangles' order and their cyclic turns change no bit.
+ *   vel[c][s] = float((wa V_a,c + wb V_b,c) + wc V_c,c) of the winner, in fp64 and rounded once, where d(s) < band; where
+ *   !(d(s) < band) all three components are 0 (the SDF is clamped there and the tile's list no longer holds every triangle).
+ *   sdf, when given, holds the bits mgps_fields_mesh_sdf writes for the same mesh and box.
+ *   Face grids.  For a face f of axis a with r = body[a][f] in 1 .. bodies and velocities[r].vel set: x_f as in
+ *   mgps_fields_rigid_velocity, x_b = R^T (x_f - centre_r) as in the rasteriser, g, i0 and f exactly section 18's GRID rule (clamped
+ *   into the sample box, with no out-of-box term), u_c the trilinear interpolant of vel[c] taken along x, then y, then z as
+ *   (1 - t) p + t q in fp64, and
+ *     sv_a[f] = float(((R_a0 u_0 + R_a1 u_1) + R_a2 u_2) + (U + omega x (x_f - centre_r))_a),
+ *   (U, omega) = velocities[r].motion, the motion of the body frame.  Every other face keeps its bits: row 0, ids out of range and
+ *   bodies without samples are untouched, so a caller writes mgps_fields_rigid_velocity first and this pass after it.
+ *   How it composes: deforming colliders are scripted solids.  Give them the highest ids in the rasteriser's table, pass the coupled
+ *   entries (mgps_coupling_create, the rigid one-calls on one device and on slab ranks) the count of RIGID bodies only and this sv as
+ *   their solid_velocity: the deforming bodies' faces then fall into row 0 ("walls and scripted solids, the caller's"), keep the
+ *   sampled values and enter the right-hand side through mgps_fields_rhs.  Nothing in those entries changes.
+ * Limits: vertex velocities are given, not differenced from two poses; one-way only (the liquid does not deform the collider); the
+ * samples' band limits how far from the surface a face may lie (as for the SDF: band >= B + sqrt(3) spacing). */
+typedef struct mgps_mesh_velocity_desc {
+    int struct_size;           /* sizeof(mgps_mesh_velocity_desc) */
+    int vertices, triangles;   /* as mgps_mesh_desc, down to sdf */
+    const double *xyz;
+    const int32_t *tri;
+    int nx, ny, nz;
+    double origin[3], spacing;
+    double band;
+    float *sdf;                /* out, device, or NULL: not written */
+    const double *velocity;    /* host, vertices * 3, body frame, cells per step */
+    float *vel[3];             /* out, device, each nz * ny * nx, x fastest: the (x, y, z) components in the body frame */
+} mgps_mesh_velocity_desc;
+/* One host pass (check, turn, bin, upload: mgps_fields_mesh_sdf's, with the vertex velocities in the same copy), the list fill and
+ * the parity bits unchanged, and a third launch that walks the lists as the distance pass does and also carries the winner: per
+ * sample d2 and the winner's table row stay in registers, the index triples are read only on an equal d2, and after the walk the
+ * thread classifies the closest point once for the weights, gathers the three vertex velocities and stores.  No atomics on values.
+ * Does not synchronise the stream.  Refuses with a message, before any device work: whatever mgps_fields_mesh_sdf refuses (but a
+ * NULL sdf), a NULL velocity or a NULL vel[], a non-finite vertex velocity. */
+int mgps_fields_mesh_sdf_velocity(const mgps_mesh_velocity_desc *d, void *stream);
+
+typedef struct mgps_body_velocity {
+    const float *vel[3];   /* device samples of a GRID body, all three, or all NULL: this body's faces are not written */
+    double motion[6];      /* (U, omega) of the body frame, world frame, about the shape's centre */
+} mgps_body_velocity;
+/* The samples on the face grids (the rule above).  sv and body: the three face grids; shapes and velocities: host, bodies + 1 rows,
+ * row 0 is not read; the samples of body r lie on the sample box of shapes[r].  One launch over the three axes: the ids are read
+ * once, with a store only where a sampled body owns the face; the rows are uploaded per call.  Does not synchronise the stream.
+ * Refuses with a message, before any device work: everything mgps_fields_rasterize_bodies refuses of a shape row, a body with
+ * samples whose kind is not GRID, a partly set vel, a non-finite motion of a body with samples, a NULL grid or table, a non-positive
+ * extent (or more than 262140 cells along y or z), bodies outside 1 .. 255. */
+int mgps_fields_sampled_velocity(float *const sv[3], const int32_t *const body[3], int bodies, const mgps_body_shape *shapes,
+                                 const mgps_body_velocity *velocities, int gx, int gy, int gz, void *stream);
+/* The same on a slab window, without halo and without communication: the grids are the window's (z-face grids: the faces c0 .. c1),
+ * positions use the plane index of the whole grid, the bits are those of the whole-grid pass on the rank's planes and both copies
+ * of a cut's z-face plane come out alike.  Refuses also: not a slab window. */
+int mgps_fields_slab_sampled_velocity(const mgps_fields_slab *w, float *const sv[3], const int32_t *const body[3], int bodies,
+                                      const mgps_body_shape *shapes, const mgps_body_velocity *velocities, void *stream);
 
 #ifdef __cplusplus
 }
