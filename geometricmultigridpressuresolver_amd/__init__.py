@@ -18,6 +18,7 @@ from .solver import (  # noqa: E402,F401
     unit_test_coarsening,
     unit_test_exterior_cells,
 )
+from .fields import AdvectDesc, advect, advectSlab  # noqa: E402,F401  (the rest of the fields layer: `from ... import fields`)
 
 
 def trim_host_cache():

@@ -101,6 +101,12 @@ def lib():
         L.mgps_fields_sampled_velocity.restype = C.c_int
         L.mgps_fields_slab_sampled_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mgps_fields_slab_sampled_velocity.restype = C.c_int
+        # advection (include/mgps_fields.h): desc by reference, stream -- or the window first, then the halo width and the four
+        # arrays of halo planes
+        L.mgps_fields_advect.argtypes = [C.c_void_p, C.c_void_p]
+        L.mgps_fields_advect.restype = C.c_int
+        L.mgps_fields_slab_advect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mgps_fields_slab_advect.restype = C.c_int
         _lib = L
     return _lib
 

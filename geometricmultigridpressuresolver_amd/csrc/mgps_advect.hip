@@ -1,0 +1,399 @@
+// Advection on the device (include/mgps_fields.h, "advection"): semi-Lagrangian and MacCormack passes over the three
+// face grids of the velocity and up to four cell grids, on a whole grid or a slab window.
+// One launch over the rasteriser's tiles of kTX x kTY x kTZ cells, two under MacCormack.  A thread owns its cell's scalars and the backward
+// face of its cell per axis, and the forward face where the box ends (sampledVelocityKernel's ownership).  The first velocity sample of a
+// trace, U(x), sits at a fixed offset from the thread's cell: the workgroup stages its tile of the three components with a rim in LDS and
+// every U(x) is read from there.  The midpoint and departure samples depend on the data and go to global memory.
+// Every rule is stated once: latticeOf (where a grid's nodes are and which planes are held), stencilAt (section 20's interpolant: indices
+// and weights), combine (the eight values, their least and greatest), departure (the trace).  Both launches and both forms inline the
+// same functions, with explicit fused multiply-adds where a product feeds a sum, so a departure point has the same bits wherever it is
+// formed again.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "mgps_fields.h"
+#include "mgps_internal.h"
+#include "mgps_slab_call.h"
+
+using namespace mgps;
+
+namespace {
+
+constexpr int kTX = 64, kTY = 4, kTZ = 4, kThreads = 256;
+// the staged box: the tile's nodes and one node below and above per axis; along z one more above, which the z-face lattice asks for
+// (with weight 0) at the forward face of a window that ends inside the grid
+constexpr int kSX = kTX + 2, kSY = kTY + 2, kSZ = kTZ + 3, kStage = kSX * kSY * kSZ;
+constexpr int kGrids = 7;  // vx, vy, vz, then four scalars
+static_assert(kTX == 64 && kTY * 64 == kThreads, "one wave per row of a tile plane");
+
+// the planes of a grid that the call holds: the window's, and the halo planes below and above it
+struct Held {
+    const float *win, *lo, *hi;
+};
+
+struct AdvectArgs {
+    int gx, gy, gz;    // the whole grid
+    int c0, planes;    // the window's base planes [c0, c0 + planes); the whole grid: 0, gz
+    int below, above;  // halo planes held on either side
+    int order, scalars, faces;  // trace order; scalar grids; 1 = the velocity is advected too
+    double dt;
+    Held in[kGrids];
+    const float *hat[kGrids];  // second launch: the semi-Lagrangian result of the first
+    float *out[kGrids];
+    unsigned long long *counts;
+};
+
+// Grid kinds: 0 = cells, 1 + a = faces of axis a.  n: the nodes of the WHOLE grid, o: the position of node (0, 0, 0); [w0, w1) the planes
+// of the window and [h0, h1) the planes held, both in the whole grid's plane index
+struct Lattice {
+    int n[3];
+    double o[3];
+    int w0, w1, h0, h1;
+};
+
+__device__ __forceinline__ Lattice latticeOf(const AdvectArgs &a, int kind)
+{
+    Lattice L;
+    L.n[0] = a.gx + (kind == 1), L.n[1] = a.gy + (kind == 2), L.n[2] = a.gz + (kind == 3);
+    L.o[0] = kind == 1 ? 0.0 : 0.5, L.o[1] = kind == 2 ? 0.0 : 0.5, L.o[2] = kind == 3 ? 0.0 : 0.5;
+    L.w0 = a.c0, L.w1 = a.c0 + a.planes + (kind == 3);
+    L.h0 = L.w0 - a.below, L.h1 = L.w1 + a.above;
+    return L;
+}
+
+// the plane z (held) of a grid
+__device__ __forceinline__ const float *planeOf(const Held &h, const Lattice &L, int z)
+{
+    const size_t plane = size_t(L.n[0]) * size_t(L.n[1]);
+    if (z < L.w0) return h.lo + size_t(z - L.h0) * plane;
+    if (z < L.w1) return h.win + size_t(z - L.w0) * plane;
+    return h.hi + size_t(z - L.w1) * plane;
+}
+
+// S's indices and weights at the point p.  missed: a plane inside the grid that is not held was asked for; the nearest held one is read
+struct Stencil {
+    int i0[3], i1[3];
+    double t[3];
+    bool missed;
+};
+
+__device__ __forceinline__ Stencil stencilAt(const Lattice &L, double px, double py, double pz)
+{
+    Stencil s;
+    const double p[3] = {px, py, pz};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double g = fmin(fmax(p[c] - L.o[c], 0.0), double(L.n[c] - 1));
+        s.i0[c] = min(int(floor(g)), L.n[c] - 1);
+        s.i1[c] = min(s.i0[c] + 1, L.n[c] - 1);
+        s.t[c] = g - double(s.i0[c]);
+    }
+    s.missed = s.i0[2] < L.h0 || s.i1[2] >= L.h1;
+    s.i0[2] = min(max(s.i0[2], L.h0), L.h1 - 1);
+    s.i1[2] = min(max(s.i1[2], L.h0), L.h1 - 1);
+    return s;
+}
+
+__device__ __forceinline__ double lerp(double t, double u, double v)
+{
+    return fma(t, v, (1.0 - t) * u);
+}
+
+// the eight values along x, then y, then z; lo and hi: the least and the greatest of them
+__device__ __forceinline__ double combine(const Stencil &s, const float v[8], double &lo, double &hi)
+{
+    lo = hi = double(v[0]);
+#pragma unroll
+    for (int q = 1; q < 8; ++q) lo = fmin(lo, double(v[q])), hi = fmax(hi, double(v[q]));
+    const double x00 = lerp(s.t[0], double(v[0]), double(v[1])), x10 = lerp(s.t[0], double(v[2]), double(v[3]));
+    const double x01 = lerp(s.t[0], double(v[4]), double(v[5])), x11 = lerp(s.t[0], double(v[6]), double(v[7]));
+    return lerp(s.t[2], lerp(s.t[1], x00, x10), lerp(s.t[1], x01, x11));
+}
+
+__device__ __forceinline__ double sampleHeld(const Held &h, const Lattice &L, const Stencil &s, double &lo, double &hi)
+{
+    const float *p0 = planeOf(h, L, s.i0[2]), *p1 = planeOf(h, L, s.i1[2]);
+    const size_t r0 = size_t(s.i0[1]) * size_t(L.n[0]), r1 = size_t(s.i1[1]) * size_t(L.n[0]);
+    const float v[8] = {p0[r0 + s.i0[0]], p0[r0 + s.i1[0]], p0[r1 + s.i0[0]], p0[r1 + s.i1[0]],
+                        p1[r0 + s.i0[0]], p1[r0 + s.i1[0]], p1[r1 + s.i0[0]], p1[r1 + s.i1[0]]};
+    return combine(s, v, lo, hi);
+}
+
+// the staged box of one component: node (x, y, z) of the whole grid's index lives at (x - xb, y - yb, z - zb)
+struct Staged {
+    const float *at;
+    int xb, yb, zb;
+};
+
+__device__ __forceinline__ double sampleStaged(const Staged &g, const Stencil &s)
+{
+    const int z0 = (s.i0[2] - g.zb) * kSY, z1 = (s.i1[2] - g.zb) * kSY;
+    const int r00 = (z0 + s.i0[1] - g.yb) * kSX - g.xb, r10 = (z0 + s.i1[1] - g.yb) * kSX - g.xb;
+    const int r01 = (z1 + s.i0[1] - g.yb) * kSX - g.xb, r11 = (z1 + s.i1[1] - g.yb) * kSX - g.xb;
+    const float v[8] = {g.at[r00 + s.i0[0]], g.at[r00 + s.i1[0]], g.at[r10 + s.i0[0]], g.at[r10 + s.i1[0]],
+                        g.at[r01 + s.i0[0]], g.at[r01 + s.i1[0]], g.at[r11 + s.i0[0]], g.at[r11 + s.i1[0]]};
+    double lo, hi;
+    return combine(s, v, lo, hi);
+}
+
+// U(p) from global memory
+__device__ __forceinline__ void velocityAt(const AdvectArgs &a, const double p[3], double u[3], bool &missed)
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const Lattice L = latticeOf(a, c + 1);
+        const Stencil s = stencilAt(L, p[0], p[1], p[2]);
+        missed |= s.missed;
+        double lo, hi;
+        u[c] = sampleHeld(a.in[c], L, s, lo, hi);
+    }
+}
+
+// The departure point of x under the step dt (the forward point: -dt), given u0 = U(x).  clamped: a clamp into the box moved a coordinate
+__device__ __forceinline__ void departure(const AdvectArgs &a, const double x[3], const double u0[3], double dt, double p[3], bool &clamped,
+                                          bool &missed)
+{
+    const double box[3] = {double(a.gx), double(a.gy), double(a.gz)};
+    double u[3] = {u0[0], u0[1], u0[2]};
+    if (a.order == 2) {
+        double p1[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double q = fma(-(0.5 * dt), u0[c], x[c]);
+            p1[c] = fmin(fmax(q, 0.0), box[c]);
+            clamped |= p1[c] != q;
+        }
+        velocityAt(a, p1, u, missed);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double q = fma(-dt, u[c], x[c]);
+        p[c] = fmin(fmax(q, 0.0), box[c]);
+        clamped |= p[c] != q;
+    }
+}
+
+// a store of a streamed tile: the pass does not read its outputs again
+__device__ __forceinline__ void put(float *p, float v)
+{
+    __builtin_nontemporal_store(v, p);
+}
+
+// PASS 0: out = the semi-Lagrangian value (under MacCormack `out` is the scratch).  PASS 1: the MacCormack correction from in and hat
+template <int PASS>
+__global__ __launch_bounds__(kThreads) void advectKernel(AdvectArgs a)
+{
+    __shared__ float stage[3][kStage];
+    __shared__ unsigned int tally[2];
+
+    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
+    const int ti0 = int(blockIdx.x) * kTX, tj0 = int(blockIdx.y) * kTY, k0 = int(blockIdx.z) * kTZ;
+    const int kg0 = k0 + a.c0;
+    if (t < 2) tally[t] = 0;
+
+    // the three components' nodes around the tile; a node outside the grid or outside the held planes is the nearest one inside
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const Lattice L = latticeOf(a, c + 1);
+        for (int n = t; n < kStage; n += kThreads) {
+            const int lx = n % kSX, ly = (n / kSX) % kSY, lz = n / (kSX * kSY);
+            const int x = min(max(ti0 - 1 + lx, 0), L.n[0] - 1), y = min(max(tj0 - 1 + ly, 0), L.n[1] - 1);
+            const int z = min(max(min(max(kg0 - 1 + lz, 0), L.n[2] - 1), L.h0), L.h1 - 1);
+            stage[c][n] = planeOf(a.in[c], L, z)[size_t(y) * size_t(L.n[0]) + x];
+        }
+    }
+    __syncthreads();
+
+    const int i = ti0 + lane, j = tj0 + wave;
+    unsigned int nClamped = 0, nMissed = 0;
+    if (i < a.gx && j < a.gy) {
+        for (int kk = 0; kk < kTZ; ++kk) {
+            const int k = k0 + kk;
+            if (k >= a.planes) break;
+            for (int kind = 0; kind <= (a.faces ? 3 : 0); ++kind) {
+                const int first = kind == 0 ? 3 : kind - 1, grids = kind == 0 ? a.scalars : 1;
+                if (grids == 0) continue;
+                const Lattice L = latticeOf(a, kind);
+                const int more = kind == 1 ? i == a.gx - 1 : kind == 2 ? j == a.gy - 1 : kind == 3 ? k == a.planes - 1 : 0;
+                for (int side = 0; side <= more; ++side) {
+                    const int fi = i + (kind == 1 ? side : 0), fj = j + (kind == 2 ? side : 0), fk = k + (kind == 3 ? side : 0);
+                    const size_t at = (size_t(fk) * size_t(L.n[1]) + size_t(fj)) * size_t(L.n[0]) + size_t(fi);
+                    const double x[3] = {kind == 1 ? double(fi) : double(fi) + 0.5, kind == 2 ? double(fj) : double(fj) + 0.5,
+                                         kind == 3 ? double(fk + a.c0) : double(fk + a.c0) + 0.5};
+                    bool clamped = false, missed = false;
+                    double u0[3];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const Stencil s = stencilAt(latticeOf(a, c + 1), x[0], x[1], x[2]);
+                        missed |= s.missed;
+                        u0[c] = sampleStaged(Staged{stage[c], ti0 - 1, tj0 - 1, kg0 - 1}, s);
+                    }
+                    double p[3];
+                    departure(a, x, u0, a.dt, p, clamped, missed);
+                    const Stencil s = stencilAt(L, p[0], p[1], p[2]);
+                    missed |= s.missed;
+                    if (PASS == 0) {
+                        for (int g = 0; g < grids; ++g) {
+                            double lo, hi;
+                            put(a.out[first + g] + at, float(sampleHeld(a.in[first + g], L, s, lo, hi)));
+                        }
+                        // of the z-faces the planes c0 .. c1 - 1 count, and plane gz: a sum over the ranks counts every target once
+                        if (kind != 3 || side == 0 || a.c0 + a.planes == a.gz) {
+                            nClamped += clamped ? grids : 0;
+                            nMissed += missed ? grids : 0;
+                        }
+                    } else {
+                        double pf[3];
+                        bool unused = false;
+                        departure(a, x, u0, -a.dt, pf, unused, unused);
+                        const Stencil sf = stencilAt(L, pf[0], pf[1], pf[2]);
+                        for (int g = 0; g < grids; ++g) {
+                            double lo, hi, lo2, hi2;
+                            (void)sampleHeld(a.in[first + g], L, s, lo, hi);
+                            const double back = sampleHeld(Held{a.hat[first + g], nullptr, nullptr}, L, sf, lo2, hi2);
+                            const double m = fma(0.5, double(a.in[first + g].win[at]) - back, double(a.hat[first + g][at]));
+                            put(a.out[first + g] + at, float(fmin(fmax(m, lo), hi)));
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (PASS == 0 && a.counts) {
+        if (nClamped) atomicAdd(&tally[0], nClamped);
+        if (nMissed) atomicAdd(&tally[1], nMissed);
+        __syncthreads();
+        if (t < 2 && tally[t]) atomicAdd(a.counts + t, (unsigned long long)tally[t]);
+    }
+}
+
+int hipStatus(const char *fn, hipError_t e)
+{
+    if (e == hipSuccess) return MGPS_OK;
+    setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(e));
+    return MGPS_ERR_HIP;
+}
+
+// a byte range of one array of the call
+struct Range {
+    const char *p;
+    size_t bytes;
+    int role;  // 0 read, 1 scratch, 2 out
+    std::string name;
+};
+
+// What both entries refuse of a desc, before any device work; [c0, c0 + planes) with the halo planes held is the box of the arrays.
+// Fills the kernel's arguments
+int checkDesc(const char *fn, const mgps_advect_desc *d, int c0, int planes, int below, int above, const float *const vlo[3],
+              const float *const vhi[3], const float *const slo[4], const float *const shi[4], AdvectArgs &a)
+{
+    if (!d || d->struct_size != int(sizeof(mgps_advect_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_advect_desc)");
+    if (d->gx < 1 || d->gy < 1 || d->gz < 1)
+        return refuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(d->gx) + ", " + std::to_string(d->gy) + ", " + std::to_string(d->gz) + ")");
+    if ((d->gy + kTY - 1) / kTY > 65535 || (d->gz + kTZ - 1) / kTZ > 65535) return refuse(fn, "more than 262140 cells along y or z");
+    if (d->scheme != 0 && d->scheme != 1) return refuse(fn, "scheme = " + std::to_string(d->scheme) + " is neither 0 (semi-Lagrangian) nor 1 (MacCormack)");
+    if (d->trace_order != 1 && d->trace_order != 2) return refuse(fn, "trace_order = " + std::to_string(d->trace_order) + " is neither 1 nor 2");
+    if (!std::isfinite(d->dt)) return refuse(fn, "dt is not finite");
+    if (d->scalars < 0 || d->scalars > 4) return refuse(fn, "scalars = " + std::to_string(d->scalars) + " is outside 0 .. 4");
+    const int outs = (d->velocity_out[0] != nullptr) + (d->velocity_out[1] != nullptr) + (d->velocity_out[2] != nullptr);
+    if (outs != 0 && outs != 3) return refuse(fn, "velocity_out: all three grids, or none (scalars only)");
+    if (outs == 0 && d->scalars == 0) return refuse(fn, "nothing to advect: velocity_out is NULL and scalars = 0");
+
+    const size_t gx = size_t(d->gx), gy = size_t(d->gy), pl = size_t(planes);
+    const size_t plane[4] = {gx * gy, (gx + 1) * gy, gx * (gy + 1), gx * gy};  // by grid kind
+    const size_t held[4] = {pl, pl, pl, pl + 1};
+    std::vector<Range> ranges;
+    const auto add = [&](const void *p, int kind, int role, const std::string &name) {
+        ranges.push_back(Range{static_cast<const char *>(p), plane[kind] * held[kind] * sizeof(float), role, name});
+    };
+    const auto addHalo = [&](const void *p, int kind, int count, const std::string &name) {
+        ranges.push_back(Range{static_cast<const char *>(p), plane[kind] * size_t(count) * sizeof(float), 0, name});
+    };
+    a = AdvectArgs{};
+    a.gx = d->gx, a.gy = d->gy, a.gz = d->gz, a.c0 = c0, a.planes = planes, a.below = below, a.above = above;
+    a.order = d->trace_order, a.scalars = d->scalars, a.faces = outs == 3, a.dt = d->dt, a.counts = d->counts_dev;
+    for (int g = 0; g < 3 + d->scalars; ++g) {
+        const bool face = g < 3;
+        const int q = face ? g : g - 3, kind = face ? g + 1 : 0;
+        const std::string idx = "[" + std::to_string(q) + "]", base = face ? "velocity" : "scalar";
+        const float *in = face ? d->velocity_in[q] : d->scalar_in[q];
+        float *out = face ? d->velocity_out[q] : d->scalar_out[q];
+        float *scratch = face ? d->velocity_scratch[q] : d->scalar_scratch[q];
+        const float *lo = face ? (vlo ? vlo[q] : nullptr) : (slo ? slo[q] : nullptr);
+        const float *hi = face ? (vhi ? vhi[q] : nullptr) : (shi ? shi[q] : nullptr);
+        if (!in) return refuse(fn, base + "_in" + idx + " is NULL");
+        add(in, kind, 0, base + "_in" + idx);
+        if (below > 0 && !lo) return refuse(fn, base + "_lo" + idx + " is NULL: " + std::to_string(below) + " halo planes lie below the window");
+        if (above > 0 && !hi) return refuse(fn, base + "_hi" + idx + " is NULL: " + std::to_string(above) + " halo planes lie above the window");
+        if (below > 0) addHalo(lo, kind, below, base + "_lo" + idx);
+        if (above > 0) addHalo(hi, kind, above, base + "_hi" + idx);
+        a.in[g] = Held{in, below > 0 ? lo : nullptr, above > 0 ? hi : nullptr};
+        if (face && outs == 0) continue;
+        if (!out) return refuse(fn, base + "_out" + idx + " is NULL");
+        add(out, kind, 2, base + "_out" + idx);
+        if (d->scheme == 1) {
+            if (!scratch) return refuse(fn, base + "_scratch" + idx + " is NULL: MacCormack needs scratch grids of the outputs' shapes");
+            add(scratch, kind, 1, base + "_scratch" + idx);
+        }
+        a.out[g] = out, a.hat[g] = scratch;
+    }
+    // an array that is written (out, scratch) overlaps no other array of the call
+    for (size_t p = 0; p < ranges.size(); ++p)
+        for (size_t q = p + 1; q < ranges.size(); ++q) {
+            const Range &r = ranges[p], &s = ranges[q];
+            if (r.role == 0 && s.role == 0) continue;  // (two arrays that are only read may be one)
+            if (r.p < s.p + s.bytes && s.p < r.p + r.bytes) return refuse(fn, r.name + " and " + s.name + " overlap: the pass is out of place");
+        }
+    return MGPS_OK;
+}
+
+// one launch for the semi-Lagrangian scheme, two under MacCormack: the first fills the scratch grids, the second corrects and limits
+int runAdvect(const char *fn, const AdvectArgs &args, int scheme, hipStream_t st)
+{
+    const dim3 grid(unsigned((args.gx + kTX - 1) / kTX), unsigned((args.gy + kTY - 1) / kTY), unsigned((args.planes + kTZ - 1) / kTZ));
+    AdvectArgs first = args;
+    if (scheme == 1)
+        for (int g = 0; g < kGrids; ++g) first.out[g] = const_cast<float *>(args.hat[g]);
+    advectKernel<0><<<grid, kThreads, 0, st>>>(first);
+    if (int rc = hipStatus(fn, hipGetLastError()); rc != MGPS_OK || scheme == 0) return rc;
+    advectKernel<1><<<grid, kThreads, 0, st>>>(args);
+    return hipStatus(fn, hipGetLastError());
+}
+}  // namespace
+
+extern "C" {
+
+int mgps_fields_advect(const mgps_advect_desc *d, void *stream)
+try {
+    const char *fn = "mgps_fields_advect";
+    AdvectArgs a;
+    if (int rc = checkDesc(fn, d, 0, d ? d->gz : 0, 0, 0, nullptr, nullptr, nullptr, nullptr, a); rc != MGPS_OK) return rc;
+    return runAdvect(fn, a, d->scheme, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_fields_slab_advect(const mgps_fields_slab *w, const mgps_advect_desc *d, int halo, const float *const velocity_lo[3],
+                            const float *const velocity_hi[3], const float *const scalar_lo[4], const float *const scalar_hi[4], void *stream)
+try {
+    const char *fn = "mgps_fields_slab_advect";
+    if (!fieldsSlabWindow(w, fn)) return MGPS_ERR_INVALID_ARGUMENT;
+    if (halo < 0) return refuse(fn, "halo = " + std::to_string(halo) + " is negative");
+    if (d && d->struct_size == int(sizeof(mgps_advect_desc))) {
+        if (w->gx != d->gx || w->gy != d->gy || w->gz != d->gz)
+            return refuse(fn, "the window is not one of the desc's extents (gx, gy, gz are the whole grid's in both)");
+        if (d->scheme == 1)
+            return refuse(fn, "scheme = 1 (MacCormack) on a window needs the semi-Lagrangian result on the halo planes too: the window form takes "
+                              "scheme = 0 only");
+    }
+    AdvectArgs a;
+    const int below = std::min(halo, w->c0), above = std::min(halo, w->gz - w->c1);
+    if (int rc = checkDesc(fn, d, w->c0, w->c1 - w->c0, below, above, velocity_lo, velocity_hi, scalar_lo, scalar_hi, a); rc != MGPS_OK) return rc;
+    return runAdvect(fn, a, 0, static_cast<hipStream_t>(stream));
+}
+MGPS_API_CATCH(nullptr)
+}

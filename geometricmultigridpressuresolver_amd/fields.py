@@ -1152,3 +1152,101 @@ def sampledVelocitySlab(d, solid_velocity, body, shapes, frame_motions=None):
     with torch.cuda.device(sv[0].device):
         check(lib().mgps_fields_slab_sampled_velocity(C.byref(d), _arr3(sv), _arr3(ids), len(shapes), rows, vrows, _stream()))
     return solid_velocity
+
+
+# ---- advection: semi-Lagrangian and MacCormack passes (include/mgps_fields.h) ----------------------------------
+SCHEMES = {"semi_lagrangian": 0, "maccormack": 1}
+
+
+class AdvectDesc(C.Structure):
+    """mgps_advect_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("dt", C.c_double), ("scheme", C.c_int),
+        ("trace_order", C.c_int), ("velocity_in", C.c_void_p * 3), ("velocity_out", C.c_void_p * 3), ("velocity_scratch", C.c_void_p * 3),
+        ("scalars", C.c_int), ("scalar_in", C.c_void_p * 4), ("scalar_out", C.c_void_p * 4), ("scalar_scratch", C.c_void_p * 4),
+        ("counts_dev", C.c_void_p),
+    ]
+
+
+def _advect_desc(grid_shape, array_shape, velocity, dt, scalars, scheme, trace_order, out, scratch, counts):
+    """the desc of a call on arrays of `array_shape` (the whole grid's, or a window's), and what it keeps alive: (desc, velocity_out or
+    None, scalars_out).  out = None: everything is advected into new tensors; out = (velocity_out or None, scalars_out): into these,
+    and with velocity_out None the scalars only.  scratch: as out, read under MacCormack only"""
+    faces = _face3(array_shape)
+    v = [_chk(velocity[a], faces[a], torch.float32) for a in range(3)]
+    s = [_chk(q, array_shape, torch.float32) for q in scalars]
+    new = lambda like: [torch.empty_like(t) for t in like]  # noqa: E731
+    vout, sout = (new(v), new(s)) if out is None else out
+    sout = list(sout) if sout is not None else []
+    assert len(sout) == len(s), "one output per scalar grid"
+    d = AdvectDesc()
+    d.struct_size = C.sizeof(AdvectDesc)
+    d.gz, d.gy, d.gx = grid_shape
+    d.dt, d.scheme, d.trace_order, d.scalars = float(dt), SCHEMES[scheme], int(trace_order), len(s)
+    vscr, sscr = (None, None) if scratch is None else scratch
+    if d.scheme == 1 and scratch is None:
+        vscr, sscr = (new(v) if vout is not None else None), new(s)
+    for a in range(3):
+        d.velocity_in[a] = v[a].data_ptr()
+        if vout is not None:
+            d.velocity_out[a] = _chk(vout[a], faces[a], torch.float32).data_ptr()
+        if vscr is not None:
+            d.velocity_scratch[a] = _chk(vscr[a], faces[a], torch.float32).data_ptr()
+    for q in range(len(s)):
+        d.scalar_in[q], d.scalar_out[q] = s[q].data_ptr(), _chk(sout[q], array_shape, torch.float32).data_ptr()
+        if sscr is not None:
+            d.scalar_scratch[q] = _chk(sscr[q], array_shape, torch.float32).data_ptr()
+    if counts is not None:
+        assert counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
+        d.counts_dev = counts.data_ptr()
+    return d, vout, sout, (v, s, vscr, sscr)
+
+
+def advect(velocity, dt, scalars=(), scheme="maccormack", trace_order=2, out=None, counts=None, scratch=None):
+    """mgps_fields_advect: the three face grids of `velocity` (self-advection) and the cell grids `scalars` (0 .. 4; liquid_phi, say)
+    carried along `velocity` over `dt` (time step over cell size), out of place.  scheme: "maccormack" (two launches, limited to the
+    values around the departure point) or "semi_lagrangian" (one); trace_order 2 is the midpoint rule, 1 one Euler step.  Outputs
+    and MacCormack's scratch grids are allocated unless given: out = (velocity_out or None, scalars_out), where None for the
+    velocity advects the scalars only; scratch likewise.  counts: an int64 CUDA tensor of 2 that the pass adds to ([0] targets
+    whose trace was clamped into the grid's box), or None.  Returns (velocity_out, scalars_out).  Does not synchronise."""
+    shape = list(velocity[0].shape)
+    shape[2] -= 1
+    shape = tuple(shape)
+    d, vout, sout, keep = _advect_desc(shape, shape, velocity, dt, scalars, scheme, trace_order, out, scratch, counts)
+    with torch.cuda.device(keep[0][0].device):
+        check(lib().mgps_fields_advect(C.byref(d), _stream()))
+    return vout, sout
+
+
+def _halo_planes(ts, shapes, dtype, n):
+    """n grids' halo planes of one side -> a pointer array of 4 (None: NULL)"""
+    if ts is None:
+        return None
+    assert len(ts) == n, "one halo tensor per grid"
+    return (C.c_void_p * 4)(*[_chk(t, s, dtype).data_ptr() for t, s in zip(ts, shapes)])
+
+
+def advectSlab(d, velocity, dt, halo, velocity_halo, scalars=(), scalar_halo=(), scheme="semi_lagrangian", trace_order=2, out=None,
+               counts=None):
+    """mgps_fields_slab_advect: advect on the window `d` (fields.slab_window), without communication; the arrays are the window's
+    (z-faces c0 .. c1).  velocity_halo = (below[3] or None, above[3] or None): per face grid the min(halo, c0) planes below the window
+    and the min(halo, gz - c1) planes above it as (planes, ny, nx) tensors (of the z-face grid: the face planes below c0 and above
+    c1); scalar_halo likewise, one tensor per scalar grid.  None where no plane is held.  counts[1] is raised by the targets that
+    asked for a plane that is not held.  The window form is semi-Lagrangian only: scheme = "maccormack" is refused by the library."""
+    shape, n = d.base_shape, len(scalars)
+    below, above = min(int(halo), d.c0), min(int(halo), d.gz - d.c1)
+    plane = [(d.gy, d.gx + 1), (d.gy + 1, d.gx), (d.gy, d.gx)]
+    vlo, vhi = velocity_halo if velocity_halo else (None, None)
+    slo, shi = scalar_halo if scalar_halo else (None, None)
+    ptr = []
+    for side, count, (vh, sh) in ((0, below, (vlo, slo)), (1, above, (vhi, shi))):
+        if count == 0:
+            vh, sh = None, None
+        ptr.append(_halo_planes(vh, [(count,) + p for p in plane], torch.float32, 3))
+        ptr.append(_halo_planes(sh, [(count, d.gy, d.gx)] * n, torch.float32, n))
+    desc, vout, sout, keep = _advect_desc((d.gz, d.gy, d.gx), shape, velocity, dt, scalars, "semi_lagrangian", trace_order, out, None, counts)
+    desc.scheme = SCHEMES[scheme]
+    with torch.cuda.device(keep[0][0].device):
+        check(lib().mgps_fields_slab_advect(C.byref(d), C.byref(desc), int(halo), ptr[0], ptr[2], ptr[1], ptr[3], _stream()))
+    return vout, sout

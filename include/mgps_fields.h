@@ -717,6 +717,74 @@ int mgps_fields_sampled_velocity(float *const sv[3], const int32_t *const body[3
 int mgps_fields_slab_sampled_velocity(const mgps_fields_slab *w, float *const sv[3], const int32_t *const body[3], int bodies,
                                       const mgps_body_shape *shapes, const mgps_body_velocity *velocities, void *stream);
 
+/* ---- advection: semi-Lagrangian and MacCormack field passes ------------------------------------------------
+ * The step the extrapolated velocity is for: the three face grids of the velocity (self-advection) and up to four cell grids
+ * (liquid_phi is the first user) carried along `velocity_in`, out of place, on the device.  With it a level-set liquid step is
+ * made of this header's calls only: advect, add forces, rasterise, project, extrapolate.  No counterpart in the reference, where
+ * Houdini advects; the definition here is the contract.
+ *   Lengths are in cells: cell (i, j, k) has its centre at (i + 1/2, j + 1/2, k + 1/2), the x-face (i, j, k) lies at
+ *   (i, j + 1/2, k + 1/2), the y- and z-faces alike.  dt is the time step over the cell size, so dt u is a displacement in cells
+ *   (section 17's convention).
+ *   Sampling.  A grid with n_c nodes along c whose node (0, 0, 0) lies at o -- o = (1/2, 1/2, 1/2) for cells, (0, 1/2, 1/2) for
+ *   x-faces, and so on -- is sampled at a point p per axis with g = p - o, g' = clamp(g, 0, n_c - 1), i0 = min(int(floor(g')), n_c - 1),
+ *   i1 = min(i0 + 1, n_c - 1), t = g' - i0; S(q, p) combines the eight values along x, then y, then z as (1 - t) a + t b in fp64
+ *   (section 20's interpolant; the product t b and the sum are one fused multiply-add).  S is continuous in p; an extent of one
+ *   node is allowed.  U(p) = (S(vx, p), S(vy, p), S(vz, p)) of velocity_in.
+ *   Trace.  B = [0, gx] x [0, gy] x [0, gz]; clampB clamps a point into it per component.  trace_order = 1:
+ *   p_dep = clampB(x - dt U(x)).  trace_order = 2, the midpoint rule and the default of the Python layer:
+ *   p1 = clampB(x - (dt / 2) U(x)), p_dep = clampB(x - dt U(p1)).  The velocity traced with is always velocity_in.
+ *   Targets: every cell of every scalar grid and every face of the three face grids.
+ *   scheme = 0, semi-Lagrangian: out[x] = float(S(q_in, p_dep(x))), fp64 rounded once.
+ *   scheme = 1, MacCormack (Selle et al. 2008): qh = the semi-Lagrangian result of all grids (float32, in the scratch grids);
+ *   qt[x] = S(qh, p_fwd(x)) with p_fwd the same trace under -dt; m = qh[x] + (q_in[x] - qt[x]) / 2 in fp64;
+ *   out[x] = float(clamp(m, lo, hi)), lo and hi the least and the greatest of the eight q_in values S read at p_dep(x).  With zero
+ *   velocity out equals in bit for bit.
+ *   Buffers.  Out of place: an array the call writes (out, and scratch under MacCormack) overlaps no other array of the call;
+ *   pointer ranges are compared and an overlap is refused.  MacCormack needs caller-supplied scratch grids of the outputs' shapes
+ *   for qh; its second launch forms p_dep again with the first launch's expressions instead of storing it.  No atomics on values,
+ *   every target is written by its own thread: the same inputs give the same bits on every run.
+ *   counts_dev (device, unsigned long long[2], may be NULL) is ADDED to, as filled_dev is (initialise it): [0] the targets for
+ *   which a clampB moved a coordinate of p1 or p_dep, [1] the window form's missed planes (below).  A cell counts once per scalar grid.
+ * Limits: solids are not consulted -- a departure point inside a solid reads what is there; the caller extrapolates at least
+ * ceil(max |dt u|) + 2 layers first (mgps_fields_extrapolate3); liquid_phi is not redistanced; float32 grids only. */
+typedef struct mgps_advect_desc {
+    int struct_size;             /* sizeof(mgps_advect_desc) */
+    int gx, gy, gz;              /* the WHOLE simulation grid */
+    double dt;                   /* time step over cell size; finite */
+    int scheme;                  /* 0 semi-Lagrangian, 1 MacCormack */
+    int trace_order;             /* 1 or 2 */
+    const float *velocity_in[3]; /* device face grids: the velocity traced with, and the one advected */
+    float *velocity_out[3];      /* all three, or all NULL: scalars only */
+    float *velocity_scratch[3];  /* scheme = 1: face grids for qh; not read otherwise */
+    int scalars;                 /* 0 .. 4 */
+    const float *scalar_in[4];   /* device cell grids */
+    float *scalar_out[4];
+    float *scalar_scratch[4];    /* scheme = 1 */
+    unsigned long long *counts_dev;
+} mgps_advect_desc;
+/* One launch over tiles of 64 x 4 x 4 cells for scheme = 0, two for scheme = 1.  Does not synchronise the stream.  Refuses with a
+ * message, before any device work: NULL desc or a struct_size mismatch, an extent < 1 (or more than 262140 cells along y or z), a
+ * scheme or trace_order out of range, a non-finite dt, scalars outside 0 .. 4, velocity_out partly set, nothing to advect
+ * (velocity_out NULL and scalars = 0), a NULL velocity_in / scalar_in / scalar_out of a grid in use, a NULL scratch under
+ * MacCormack, overlapping buffers. */
+int mgps_fields_advect(const mgps_advect_desc *d, void *stream);
+/* The pass on a slab window, without communication.  The arrays in `d` are the window's, in section 14's shapes (z-face grids: the
+ * faces c0 .. c1); d->gx, gy, gz are the whole grid's.  velocity_lo / scalar_lo hold the min(halo, c0) planes below the window,
+ * contiguous and ascending, velocity_hi / scalar_hi the min(halo, gz - c1) planes above it; for the z-face grid these are the face
+ * planes below c0 and above c1.  They are not read (may be NULL) where that count is 0.  Positions use the whole grid's plane
+ * index: the window's bits are the whole grid's, and both copies of a cut's z-face plane come out alike.  A sample whose i0 or i1
+ * along z is a plane inside the grid but outside window plus halo reads the nearest plane held instead, and its target is counted
+ * in counts_dev[1]: the caller's test for "halo too small" is counts[1] != 0.  Of the z-face targets the planes c0 .. c1 - 1 count,
+ * on the last rank also plane gz (filled_dev's rule): a sum over the ranks counts every target once.  The whole grid is the window
+ * [0, gz) with no halo.
+ * MacCormack on a window needs qh on the halo planes too: the window form takes scheme = 0 only and refuses scheme = 1 with a
+ * message.  The collective that exchanges the halos and qh is not part of this header yet.
+ * Refuses also: not a slab window, a window of other extents than the desc's, a negative halo, a NULL halo array where planes are
+ * held. */
+int mgps_fields_slab_advect(const mgps_fields_slab *w, const mgps_advect_desc *d, int halo, const float *const velocity_lo[3],
+                            const float *const velocity_hi[3], const float *const scalar_lo[4], const float *const scalar_hi[4],
+                            void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,486 @@
+"""Advection on the device (include/mgps_fields.h, "advection") against tests/advection_reference.py.
+
+CPU: the restatement against analysis (a constant velocity carries an affine scalar exactly under both schemes; under a rigid
+rotation the midpoint departure point is the closed form), MacCormack against the semi-Lagrangian scheme on a translated Gaussian,
+the condition that the seeded scenes are in generic position, the C ABI's refusals and the ctypes mirror's size.
+GPU: both entries against the restatement on section 18's grid, rows across tile edges and a grid one cell thick, both trace
+orders and both schemes; walls; the limiter; exact cases; the same bits twice; slab windows against the whole grid; a drop in free
+flight through project, extrapolate, advect.
+
+Tolerance.  |got - want| <= 2^-24 |want| + 1e-9 max|q_in|: the one float32 rounding, and the fp64 round-off of positions and weights
+(the device fuses t * b into the sum) with orders of margin; S is continuous, so an index decided the other way at a node moves the
+value by no more.  Two decisions are not continuous -- which eight values the limiter sees, and whether a point was clamped: the
+restatement counts the targets closer than 1e-9 to either, and a CPU test asserts that count is 0 for every seeded scene used here.
+Scenes with zero or whole-cell displacement are exact by construction and tested apart."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import advection_reference as AR
+
+DT = 0.7
+GRID = (19, 22, 37)  # section 18's grid: off every multiple of the 64 x 4 x 4 tile
+SCENES = {  # name -> (shape, seed, kind, max |dt u|)
+    "grid": (GRID, 11, "noise", 2.5),
+    "row64": ((5, 6, 64), 12, "noise", 2.5),
+    "row65": ((5, 6, 65), 13, "noise", 2.5),
+    "row131": ((5, 6, 131), 14, "noise", 2.5),
+    "sheet": ((1, 7, 70), 15, "noise", 2.5),  # an extent of one cell
+    "walls": (GRID, 16, "walls", 3.0),  # the velocity points out of all six walls: MacCormack's forward points leave the box
+    "inflow": (GRID, 18, "inflow", 3.0),  # ... and into the box through all six: the departure points leave it
+    "step": (GRID, 17, "step", 2.5),
+}
+WINDOWS = {2: [0, 9, 19], 3: [0, 6, 13, 19]}  # base planes of the cuts: off the tile's 4 planes
+
+
+def _positions(shape, kind):
+    x, s, _ = AR.targets(shape, kind)
+    return [x[:, c].reshape(s) for c in range(3)]
+
+
+@functools.lru_cache(maxsize=None)
+def scene(name):
+    """(velocity[3], scalars[2]) float32, read-only: a smooth field plus seeded noise, scaled to the scene's max |dt u|"""
+    shape, seed, kind, reach = SCENES[name]
+    rng = np.random.default_rng(seed)
+    box = np.array([shape[2], shape[1], shape[0]], dtype=np.float64)
+    velocity = []
+    for a in range(3):
+        x, y, z = _positions(shape, a + 1)
+        if kind in ("walls", "inflow"):
+            smooth = (1.0 if kind == "walls" else -1.0) * ((x, y, z)[a] - 0.5 * box[a]) / (0.5 * box[a])
+            noise = 0.1
+        else:
+            smooth = np.sin(0.31 * x + 0.17 * y + 0.23 * z + 1.3 * a)
+            noise = 0.3
+        velocity.append(smooth + noise * rng.uniform(-1.0, 1.0, smooth.shape))
+    scale = reach / (DT * max(float(np.abs(v).max()) for v in velocity))
+    velocity = [(scale * v).astype(np.float32) for v in velocity]
+    x, y, z = _positions(shape, 0)
+    if kind == "step":  # a step across x with a wavy front
+        first = (x > 0.5 * box[0] + 3.0 * np.sin(0.4 * y + 0.3 * z)).astype(np.float64)
+    else:
+        first = np.cos(0.27 * x - 0.19 * y + 0.33 * z)
+    second = np.sqrt((x - 0.4 * box[0]) ** 2 + (y - 0.5 * box[1]) ** 2 + (z - 0.6 * box[2]) ** 2) - 0.3 * box.min()
+    scalars = [(first + 0.02 * rng.uniform(-1.0, 1.0, first.shape)).astype(np.float32),
+               (second + 0.02 * rng.uniform(-1.0, 1.0, first.shape)).astype(np.float32)]
+    for q in velocity + scalars:
+        q.setflags(write=False)
+    return velocity, scalars
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name, scheme, order, window=None):
+    velocity, scalars = scene(name)
+    r = AR.advect(velocity, scalars, DT, scheme, order, window)
+    for q in r["velocity"] + r["scalars"]:
+        q.setflags(write=False)
+    return r
+
+
+CASES = [(name, scheme, order) for name in ("grid", "row64", "row65", "row131", "sheet") for scheme in (0, 1) for order in (1, 2)]
+CASES += [("walls", 0, 2), ("walls", 1, 2), ("inflow", 0, 2), ("inflow", 1, 2), ("step", 1, 2)]
+WINDOW_CASES = [("grid", 0, 2, (c[r], c[r + 1], halo)) for c in WINDOWS.values() for r in range(len(c) - 1) for halo in (4, 1)]
+
+
+# ---- CPU: the restatement ------------------------------------------------------------------------------------------------------------
+def _inside(shape, points, margin):
+    box = np.array([shape[2], shape[1], shape[0]], dtype=np.float64)
+    return ((points >= margin) & (points <= box - margin)).all(axis=1)
+
+
+@pytest.mark.parametrize("scheme", [0, 1])
+@pytest.mark.parametrize("order", [1, 2])
+def test_restated_constant_velocity_carries_an_affine_scalar_exactly(scheme, order):
+    """U constant with dt U = (0.625, 0.375, -0.25) cells (not whole cells; every number below is a short binary fraction, so float32
+    holds it): both schemes return q(x - dt U) to 1e-12 max|q| on the targets whose stencils stay inside the box"""
+    shape = (12, 14, 16)
+    U = np.array([0.625, 0.375, -0.25])
+    velocity = [np.full(AR.grid_shape(shape, a + 1), U[a], dtype=np.float32) for a in range(3)]
+    q = lambda p: 0.25 * p[..., 0] - 0.5 * p[..., 1] + 0.125 * p[..., 2] + 1.0  # noqa: E731
+    x, s, _ = AR.targets(shape, 0)
+    phi = q(x).reshape(s).astype(np.float32)
+    assert np.array_equal(phi.astype(np.float64).ravel(), q(x))
+    r = AR.advect(velocity, [phi], 1.0, scheme, order)
+    ok = _inside(shape, x, 3.0)
+    assert ok.sum() > 400
+    err = np.abs(r["scalars"][0].ravel().astype(np.float64) - q(x - U))[ok].max()
+    assert err <= 1e-12 * np.abs(phi).max(), err
+    assert all(np.array_equal(r["velocity"][a], velocity[a]) for a in range(3))  # (a constant is carried as it is)
+
+
+def test_restated_midpoint_trace_under_a_rigid_rotation_is_the_closed_form():
+    """u = w J (x - c) about the z axis, J (x, y) = (-y, x): trilinear interpolation is exact on an affine field, so the midpoint rule
+    gives r - dt w J r - (dt w)^2 r / 2 from r = x - c, to 1e-12 of the grid's size, on targets whose points stay inside the lattices"""
+    shape = (6, 24, 28)
+    w, c, dt = 2.0 ** -5, np.array([14.0, 12.0, 3.0]), 1.5
+    X = [_positions(shape, a + 1) for a in range(3)]
+    velocity = [(-w * (X[0][1] - c[1])).astype(np.float32), (w * (X[1][0] - c[0])).astype(np.float32), np.zeros(AR.grid_shape(shape, 3), np.float32)]
+    for kind in range(4):
+        x, _, _ = AR.targets(shape, kind)
+        p, clamped, _, _ = AR.departure(velocity, shape, x, dt, 2)
+        r = x - c
+        Jr = np.stack([-r[:, 1], r[:, 0], np.zeros(len(r))], axis=1)
+        rxy = r * np.array([1.0, 1.0, 0.0])
+        want = c + r - dt * w * Jr - 0.5 * (dt * w) ** 2 * rxy
+        ok = _inside(shape, x, 1.0) & _inside(shape, want, 1.0) & _inside(shape, x - 0.5 * dt * w * Jr, 1.0)
+        assert ok.sum() > 1000 and not clamped[ok].any()
+        assert np.abs(p - want)[ok].max() <= 1e-12 * max(shape)
+
+
+def test_maccormack_earns_its_second_launch():
+    """A Gaussian of sigma = 3 cells on 40^3 carried twelve steps of dt U = 1.7 (0.37, 0.21, -0.13): relative L2 error against the
+    translated Gaussian.  A prototype of the definition gave 0.073 (MacCormack) against 0.220 (semi-Lagrangian)."""
+    shape, sigma, steps, dt = (40, 40, 40), 3.0, 12, 1.7
+    U = np.array([0.37, 0.21, -0.13], dtype=np.float32)
+    velocity = [np.full(AR.grid_shape(shape, a + 1), U[a], dtype=np.float32) for a in range(3)]
+    x, s, _ = AR.targets(shape, 0)
+    start = np.array([14.0, 16.0, 22.0])
+    gauss = lambda centre: np.exp(-((x - centre) ** 2).sum(axis=1) / (2 * sigma ** 2)).reshape(s)  # noqa: E731
+    want = gauss(start + steps * dt * U.astype(np.float64))
+    err = {}
+    for scheme in (0, 1):
+        q = gauss(start).astype(np.float32)
+        for _ in range(steps):
+            q = AR.advect(velocity, [q], dt, scheme, 2, advect_velocity=False)["scalars"][0]
+        err[scheme] = float(np.linalg.norm(q - want) / np.linalg.norm(want))
+    print(f"relative L2 after {steps} steps: MacCormack {err[1]:.4f}, semi-Lagrangian {err[0]:.4f}")
+    assert err[1] < err[0], err
+
+
+@pytest.mark.parametrize("case", CASES + WINDOW_CASES, ids=str)
+def test_scenes_are_in_generic_position(case):
+    """no target of a seeded scene lies within 1e-9 of a decision that is not continuous (a node of a sampled grid, a face of the box,
+    a limiter bound): the device's value is then the restatement's to the tolerance, whichever way its own round-off falls"""
+    assert restated(*case)["nongeneric"] == 0
+
+
+def test_the_step_scene_engages_the_limiter_and_the_inflow_scene_the_clamp():
+    assert restated("step", 1, 2)["limited"] > 100
+    assert restated("inflow", 0, 2)["counts"][0] > 1000
+    for c in WINDOWS.values():
+        for r in range(len(c) - 1):
+            assert restated("grid", 0, 2, (c[r], c[r + 1], 4))["counts"][1] == 0
+    assert sum(restated("grid", 0, 2, (c[r], c[r + 1], 1))["counts"][1] for c in WINDOWS.values() for r in range(len(c) - 1)) > 0
+
+
+# ---- CPU: refusals and the mirror ------------------------------------------------------------------------------------------------------
+def _refused(status, *words):
+    from geometricmultigridpressuresolver_amd._lib import lib
+
+    msg = lib().mgps_last_error(None).decode()
+    assert status == 1 and all(w in msg for w in words), (status, msg)
+
+
+def _desc(shape=(4, 4, 4), scalars=1, scheme=1, **kw):
+    """a good desc on made-up addresses, 1 MiB apart (never dereferenced: every call below is refused on the host)"""
+    from geometricmultigridpressuresolver_amd import fields as F
+
+    d = F.AdvectDesc()
+    d.struct_size = C.sizeof(F.AdvectDesc)
+    d.gz, d.gy, d.gx = shape
+    d.dt, d.scheme, d.trace_order, d.scalars = 0.5, scheme, 2, scalars
+    slot = iter(range(1, 64))
+    for a in range(3):
+        d.velocity_in[a], d.velocity_out[a], d.velocity_scratch[a] = (next(slot) << 20, next(slot) << 20, next(slot) << 20)
+    for q in range(max(0, min(scalars, 4))):
+        d.scalar_in[q], d.scalar_out[q], d.scalar_scratch[q] = (next(slot) << 20, next(slot) << 20, next(slot) << 20)
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def test_argument_refusals_need_no_device_and_the_mirror_has_the_library_size():
+    from geometricmultigridpressuresolver_amd import fields as F
+    from geometricmultigridpressuresolver_amd._lib import lib
+
+    L = lib()
+    assert C.sizeof(F.AdvectDesc) == 216
+    fn = "mgps_fields_advect"
+    run = lambda d: L.mgps_fields_advect(C.byref(d), None)  # noqa: E731
+
+    def checks(run, fn, make):
+        # the mirror's size is the library's: a good struct gets as far as the last field's neighbours, another size is refused as such
+        d = make()
+        d.struct_size -= 8
+        _refused(run(d), fn, "struct_size")
+        for k in ("gx", "gy", "gz"):
+            _refused(run(make(**{k: 0})), fn, "extent")
+        _refused(run(make(trace_order=0)), fn, "trace_order")
+        _refused(run(make(trace_order=3)), fn, "trace_order")
+        for bad in (float("nan"), float("inf")):
+            _refused(run(make(dt=bad)), fn, "dt", "finite")
+        _refused(run(make(scalars=5)), fn, "scalars", "0 .. 4")
+        _refused(run(make(scalars=-1)), fn, "scalars")
+        for name, idx in (("velocity_in", 1), ("velocity_out", 2), ("scalar_in", 0), ("scalar_out", 0)):
+            d = make()
+            getattr(d, name)[idx] = None
+            _refused(run(d), fn, name)
+        d = make(scalars=0)
+        for a in range(3):
+            d.velocity_out[a] = None
+        _refused(run(d), fn, "nothing to advect")
+        # out of place: an output on an input, on another output; the ranges are compared, not the first addresses
+        d = make()
+        d.velocity_out[0] = d.velocity_in[2] + 4 * 4 * 4 * 4
+        _refused(run(d), fn, "velocity_out[0]", "velocity_in[2]", "overlap")
+        d = make()
+        d.scalar_out[0] = d.velocity_out[1] + 16
+        _refused(run(d), fn, "scalar_out[0]", "velocity_out[1]", "overlap")
+        d = make()
+        d.scalar_out[0] = d.scalar_in[0]
+        _refused(run(d), fn, "scalar_out[0]", "scalar_in[0]", "overlap")
+
+    checks(run, fn, _desc)
+    _refused(L.mgps_fields_advect(None, None), fn, "struct_size")
+    _refused(run(_desc(scheme=2)), fn, "scheme")
+    _refused(run(_desc(scheme=-1)), fn, "scheme")
+    # MacCormack: scratch is required, and overlaps neither an output, an input nor another scratch
+    d = _desc()
+    d.velocity_scratch[1] = None
+    _refused(run(d), fn, "velocity_scratch[1]", "MacCormack")
+    d = _desc()
+    d.scalar_scratch[0] = None
+    _refused(run(d), fn, "scalar_scratch[0]", "MacCormack")
+    d = _desc()
+    d.velocity_scratch[0] = d.velocity_out[0]
+    _refused(run(d), fn, "velocity_scratch[0]", "velocity_out[0]", "overlap")
+    d = _desc()
+    d.scalar_scratch[0] = d.scalar_in[0] + 4
+    _refused(run(d), fn, "scalar_scratch[0]", "scalar_in[0]", "overlap")
+    d = _desc()
+    d.velocity_scratch[2] = d.velocity_scratch[1]
+    _refused(run(d), fn, "velocity_scratch", "overlap")
+
+    # the window form
+    fn = "mgps_fields_slab_advect"
+    shape = (32, 4, 4)
+    splits = F.projection_slab_layout(shape, True, 2, False)["splits"]
+    w0, w1 = F.slab_window(shape, True, splits, 0), F.slab_window(shape, True, splits, 1)
+    assert w0.c0 == 0 and 0 < w0.c1 == w1.c0 and w1.c1 == 32
+    halo3, halo4 = (C.c_void_p * 3)(60 << 20, 61 << 20, 62 << 20), (C.c_void_p * 4)(63 << 20, 0, 0, 0)
+    make = lambda **kw: _desc(**{"shape": (w0.c1, 4, 4), "scheme": 0, "gz": 32, **kw})  # noqa: E731  (the window's arrays, the whole grid's gz)
+    slab = lambda d, w=w0, halo=2, vlo=None, vhi=halo3, slo=None, shi=halo4: L.mgps_fields_slab_advect(  # noqa: E731
+        C.byref(w) if w is not None else None, C.byref(d), halo, vlo, vhi, slo, shi, None)
+    checks(slab, fn, make)
+    _refused(L.mgps_fields_slab_advect(C.byref(w0), None, 2, None, halo3, None, halo4, None), fn, "struct_size")
+    _refused(slab(make(), w=None), "slab window")
+    _refused(slab(make(gz=16)), fn, "extents")
+    _refused(slab(make(scheme=1)), fn, "MacCormack", "window", "scheme = 0")
+    _refused(slab(make(scheme=2)), fn, "scheme")
+    _refused(slab(make(), halo=-1), fn, "halo", "negative")
+    _refused(slab(make(), vhi=None), fn, "velocity_hi", "above the window")
+    _refused(slab(make(), shi=None), fn, "scalar_hi", "above the window")
+    _refused(slab(make(), w=w1, vlo=None, vhi=None), fn, "velocity_lo", "below the window")
+    part = (C.c_void_p * 3)(60 << 20, 0, 62 << 20)
+    _refused(slab(make(), vhi=part), fn, "velocity_hi[1]")
+    d = make()
+    d.scalar_out[0] = halo4[0]
+    _refused(slab(d), fn, "scalar_out[0]", "scalar_hi[0]", "overlap")
+
+
+# ---- GPU --------------------------------------------------------------------------------------------------------------------------------
+NAMES = ["semi_lagrangian", "maccormack"]
+
+
+def _dev(a):
+    import torch
+
+    return torch.from_numpy(np.array(a, order="C")).cuda()  # (a copy: the scenes are read-only)
+
+
+def _close(got, want, q_in, what):
+    """the tolerance of the module's docstring; prints the worst error in units of it"""
+    got, want = got.cpu().numpy().astype(np.float64), want.astype(np.float64)
+    bound = 2.0 ** -24 * np.abs(want) + 1e-9 * float(np.abs(q_in).max())
+    err = np.abs(got - want)
+    print(f"{what}: worst |got - want| = {err.max():.3e}, worst error / bound = {(err / bound).max():.3f}")
+    assert got.shape == want.shape and (err <= bound).all(), (what, float((err / bound).max()), int((~(err <= bound)).sum()))
+
+
+def _run(name, scheme, order, counts=None):
+    """the device's (velocity_out, scalars_out) for a scene, into outputs pre-filled with a pattern"""
+    import torch
+
+    from geometricmultigridpressuresolver_amd import fields as F
+
+    velocity, scalars = [[_dev(q) for q in qs] for qs in scene(name)]
+    out = ([torch.full_like(v, 7777.0) for v in velocity], [torch.full_like(s, 7777.0) for s in scalars])
+    return F.advect(velocity, DT, scalars, NAMES[scheme], order, out=out, counts=counts)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=str)
+def test_device_equals_the_restatement(case):
+    """every grid of every scene, overwritten everywhere (the outputs start as a pattern), with the clamp count of the restatement"""
+    import torch
+
+    name, scheme, order = case
+    counts = torch.zeros(2, dtype=torch.int64, device="cuda")
+    vout, sout = _run(name, scheme, order, counts)
+    want = restated(*case)
+    velocity, scalars = scene(name)
+    for a in range(3):
+        _close(vout[a], want["velocity"][a], velocity[a], f"{case} velocity[{a}]")
+    for q in range(2):
+        _close(sout[q], want["scalars"][q], scalars[q], f"{case} scalar[{q}]")
+    assert counts.tolist() == want["counts"] and counts[1] == 0
+    if name == "inflow":
+        assert counts[0] > 1000
+    if name == "step":
+        assert want["limited"] > 100
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scheme", NAMES)
+def test_zero_velocity_and_a_whole_cell_shift_are_exact(scheme):
+    import torch
+
+    from geometricmultigridpressuresolver_amd import fields as F
+
+    _, scalars = scene("grid")
+    shape = scalars[0].shape
+    phi = _dev(scalars[0])
+    rng = np.random.default_rng(3)
+    zero = [torch.zeros(AR.grid_shape(shape, a + 1), device="cuda") for a in range(3)]
+    vout, sout = F.advect(zero, DT, [phi], scheme)
+    assert torch.equal(sout[0], phi) and all(torch.equal(vout[a], zero[a]) for a in range(3))
+    # U = (1, 0, 0), dt = 1: everything moves one cell along x (scalars only, then with the velocity): out[i] == in[i - 1] for i >= 1.
+    # Under MacCormack that holds up to the last column but one: in the last column the forward point is clamped into the box, q~ is
+    # read one cell short, and m = in[i - 1] + (in[i] - in[i - 1]) / 2 lies between the two values S read at the departure point
+    # (in[i] with weight 0), so the limiter lets it stand.  That column is compared with the restatement instead
+    last = shape[2] if scheme == "semi_lagrangian" else shape[2] - 1
+    shift = [torch.ones_like(zero[0]), zero[1], zero[2]]
+    _, sout = F.advect(shift, 1.0, [phi], scheme, out=(None, [torch.empty_like(phi)]))
+    assert torch.equal(sout[0][..., 1:last], phi[..., :last - 1])
+    if scheme == "maccormack":
+        ones = [np.ones(AR.grid_shape(shape, 1), np.float32), np.zeros(AR.grid_shape(shape, 2), np.float32), np.zeros(AR.grid_shape(shape, 3), np.float32)]
+        want = AR.advect(ones, [scalars[0]], 1.0, 1, 2, advect_velocity=False)["scalars"][0]
+        _close(sout[0], want, scalars[0], "whole-cell shift under MacCormack")
+        assert not np.array_equal(want[..., -1], scalars[0][..., -2])
+    for a in (1, 2):
+        # The advected face grids are the traced velocity itself, so a y- or z-face grid with values to follow is a velocity component:
+        # seeded values of 1e-30, normal float32 numbers that no position of the trace can see (x - dt u rounds to x)
+        tiny = _dev((1e-30 * rng.uniform(1.0, 2.0, AR.grid_shape(shape, a + 1))).astype(np.float32))
+        v = [shift[0], tiny if a == 1 else zero[1], tiny if a == 2 else zero[2]]
+        vout, _ = F.advect(v, 1.0, (), scheme)
+        assert torch.equal(vout[a][..., 1:last], v[a][..., :last - 1]) and int((v[a][..., 1:] != v[a][..., :-1]).sum()) > 1000
+
+
+@pytest.mark.gpu
+def test_two_calls_give_the_same_bits_whatever_the_scratch_holds():
+    import torch
+
+    from geometricmultigridpressuresolver_amd import fields as F
+
+    velocity, scalars = [[_dev(q) for q in qs] for qs in scene("grid")]
+    runs = []
+    for fill in (float("nan"), -3.0e7):
+        scratch = ([torch.full_like(v, fill) for v in velocity], [torch.full_like(s, fill) for s in scalars])
+        runs.append(F.advect(velocity, DT, scalars, "maccormack", 2, scratch=scratch))
+    for a, b in zip(runs[0][0] + runs[0][1], runs[1][0] + runs[1][1]):
+        assert torch.equal(a, b) and bool(torch.isfinite(a).all())
+    vout, sout = _run("grid", 1, 2)
+    assert all(torch.equal(a, b) for a, b in zip(runs[0][0] + runs[0][1], vout + sout))
+
+
+def _window_call(d, name, halo, counts, scheme="semi_lagrangian"):
+    from geometricmultigridpressuresolver_amd import fields as F
+
+    window = (d.c0, d.c1, halo)
+    velocity, scalars = scene(name)
+    cut = lambda q, kind: [None if part is None else _dev(part) for part in AR.window_of(q, kind, window)]  # noqa: E731
+    v, s = [cut(velocity[a], a + 1) for a in range(3)], [cut(q, 0) for q in scalars]
+    side = lambda parts, n: None if parts[0][n] is None else [p[n] for p in parts]  # noqa: E731
+    return F.advectSlab(d, [p[0] for p in v], DT, halo, (side(v, 1), side(v, 2)), [p[0] for p in s], (side(s, 1), side(s, 2)), scheme, 2,
+                        counts=counts)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [2, 3])
+def test_windows_equal_the_whole_grid(size):
+    """cuts at base planes off the tile's four, halo 4: the window's bits are the whole grid's, both copies of a cut's z-face plane
+    are alike, no plane is missed, and the ranks' clamp counts add up to the whole grid's.  With halo 1 planes are missed: values
+    and counts are the restatement's.  MacCormack on a window is refused"""
+    import torch
+
+    from geometricmultigridpressuresolver_amd import fields as F
+    from geometricmultigridpressuresolver_amd._lib import MgpsError
+
+    lay = F.projection_slab_layout(GRID, True, 1, False)
+    cuts = WINDOWS[size]
+    splits = [0] + [lay["offset"] + c for c in cuts[1:-1]] + [lay["expanded"][0]]
+    whole_counts = torch.zeros(2, dtype=torch.int64, device="cuda")
+    whole_v, whole_s = _run("grid", 0, 2, whole_counts)
+    total = torch.zeros(2, dtype=torch.int64, device="cuda")
+    tops, missed = [], 0
+    velocity, scalars = scene("grid")
+    for rank in range(size):
+        d = F.slab_window(GRID, True, splits, rank)
+        assert (d.c0, d.c1) == (cuts[rank], cuts[rank + 1])
+        vout, sout = _window_call(d, "grid", 4, total)
+        for a in range(3):
+            assert torch.equal(vout[a], whole_v[a][d.c0:d.c1 + (a == 2)]), (rank, a)
+        for q in range(2):
+            assert torch.equal(sout[q], whole_s[q][d.c0:d.c1]), (rank, q)
+        if rank > 0:
+            assert torch.equal(tops.pop(), vout[2][0])
+        tops.append(vout[2][-1].clone())
+        # halo 1
+        counts = torch.zeros(2, dtype=torch.int64, device="cuda")
+        vout, sout = _window_call(d, "grid", 1, counts)
+        want = restated("grid", 0, 2, (d.c0, d.c1, 1))
+        for a in range(3):
+            _close(vout[a], want["velocity"][a], velocity[a], f"rank {rank} of {size}, halo 1, velocity[{a}]")
+        for q in range(2):
+            _close(sout[q], want["scalars"][q], scalars[q], f"rank {rank} of {size}, halo 1, scalar[{q}]")
+        assert counts.tolist() == want["counts"]
+        missed += int(counts[1])
+        with pytest.raises(MgpsError, match="MacCormack"):
+            _window_call(d, "grid", 4, None, "maccormack")
+    assert total.tolist() == whole_counts.tolist() and total[1] == 0 and missed > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scheme", NAMES)
+def test_a_drop_in_free_flight(scheme):
+    """A ball of radius 8 cells in 40^3 without solids, moving at dt U = 1.7 (0.37, 0.21, -0.13): twelve rounds of project_free_surface,
+    extrapolateVelocity (8 layers), advect(velocity, dt, scalars=(liquid_phi,)).  Every projection converges; on the valid faces the
+    projected velocity stays within the solve's tolerance (1e-5, relative to |U|) of U -- the field it is handed differs from U by
+    float32 round-off of the extrapolation's means, and the pressure a divergence of that size asks for is of that size --; the
+    centroid of {phi < 0} lands within 0.25 cell of the start plus 12 dt U (a prototype of the definition, advection only: 0.03).
+    The cell count of {phi < 0} is printed, not asserted (prototype: 2151 -> 2145 under MacCormack, 1894 under semi-Lagrangian)."""
+    import torch
+
+    from geometricmultigridpressuresolver_amd import fields as F
+
+    shape, radius, steps, dt, tolerance = (40, 40, 40), 8.0, 12, 1.7, 1e-5
+    U = np.array([0.37, 0.21, -0.13], dtype=np.float32)
+    start = np.array([14.0, 16.0, 22.0])
+    x, s, _ = AR.targets(shape, 0)
+    phi = (np.sqrt(((x - start) ** 2).sum(axis=1)) - radius).reshape(s).astype(np.float32)
+    velocity = []
+    for a in range(3):
+        xf, sf, _ = AR.targets(shape, a + 1)
+        velocity.append(np.where(np.sqrt(((xf - start) ** 2).sum(axis=1)) < radius + 1.0, U[a], np.float32(0)).reshape(sf).astype(np.float32))
+    solid_phi = np.full(shape, -1.0, dtype=np.float32)  # (a cell that is not liquid is solid where solid_phi >= 0: none is)
+    cw = [np.ones(AR.grid_shape(shape, a + 1), dtype=np.float32) for a in range(3)]
+    pressure = np.zeros(shape, dtype=np.float32)
+    centroid = lambda p: x[(p < 0).ravel()].mean(axis=0)  # noqa: E731
+    cells = [int((phi < 0).sum())]
+    for step in range(steps):
+        valid, info = F.project_free_surface(phi, solid_phi, cw, velocity, pressure, tolerance=tolerance)
+        assert info["outcome"] in (0, 1, 2), (step, info)  # converged, zero right-hand side, converged at the start
+        for a in range(3):
+            off = np.abs(velocity[a][valid[a] == 1] - U[a]).max()
+            assert off <= tolerance * float(np.abs(U).max()), (step, a, off)
+        vd = [_dev(v) for v in velocity]
+        F.extrapolateVelocity(vd, [_dev(v) for v in valid], 8)
+        vout, sout = F.advect(vd, dt, scalars=(_dev(phi),), scheme=scheme)
+        velocity, phi = [v.cpu().numpy() for v in vout], sout[0].cpu().numpy()
+        cells.append(int((phi < 0).sum()))
+    off = float(np.linalg.norm(centroid(phi) - (start + steps * dt * U.astype(np.float64))))
+    print(f"{scheme}: cells of phi < 0 {cells[0]} -> {cells[-1]}, centroid off by {off:.4f} cell")
+    assert off <= 0.25, off
