@@ -19,6 +19,7 @@ from .solver import (  # noqa: E402,F401
     unit_test_exterior_cells,
 )
 from .fields import AdvectDesc, advect, advectSlab  # noqa: E402,F401  (the rest of the fields layer: `from ... import fields`)
+from .fields import RedistanceDesc, redistance, redistanceInitSlab, redistanceRoundSlab  # noqa: E402,F401
 
 
 def trim_host_cache():

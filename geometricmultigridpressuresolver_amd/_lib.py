@@ -107,6 +107,14 @@ def lib():
         L.mgps_fields_advect.restype = C.c_int
         L.mgps_fields_slab_advect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mgps_fields_slab_advect.restype = C.c_int
+        # redistancing (include/mgps_fields.h): desc by reference, stream -- or the window first, then the halo width, the halo
+        # planes below and above, (the round: `last`,) stream
+        L.mgps_fields_redistance.argtypes = [C.c_void_p, C.c_void_p]
+        L.mgps_fields_redistance.restype = C.c_int
+        L.mgps_fields_slab_redistance_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mgps_fields_slab_redistance_init.restype = C.c_int
+        L.mgps_fields_slab_redistance_round.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.mgps_fields_slab_redistance_round.restype = C.c_int
         _lib = L
     return _lib
 

@@ -1250,3 +1250,103 @@ def advectSlab(d, velocity, dt, halo, velocity_halo, scalars=(), scalar_halo=(),
     with torch.cuda.device(keep[0][0].device):
         check(lib().mgps_fields_slab_advect(C.byref(d), C.byref(desc), int(halo), ptr[0], ptr[2], ptr[1], ptr[3], _stream()))
     return vout, sout
+
+
+# ---- redistancing: a fast iterative Eikonal pass (include/mgps_fields.h) ---------------------------------------
+class RedistanceDesc(C.Structure):
+    """mgps_redistance_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("band", C.c_double), ("dx", C.c_double),
+        ("rounds", C.c_int), ("inner", C.c_int), ("phi_in", C.c_void_p), ("phi_out", C.c_void_p), ("scratch", C.c_void_p),
+        ("counts_dev", C.c_void_p),
+    ]
+
+
+def _redistance_desc(grid_shape, array_shape, phi_in, band, dx, rounds, inner, out, scratch, counts):
+    """the desc of a call on arrays of `array_shape` (the whole grid's, or a window's); out is allocated unless given"""
+    _chk(phi_in, array_shape, torch.float32)
+    out = torch.empty_like(phi_in) if out is None else _chk(out, array_shape, torch.float32)
+    d = RedistanceDesc()
+    d.struct_size = C.sizeof(RedistanceDesc)
+    d.gz, d.gy, d.gx = grid_shape
+    d.band, d.dx, d.rounds, d.inner = float(band), float(dx), int(rounds), int(inner)
+    d.phi_in, d.phi_out = phi_in.data_ptr(), out.data_ptr()
+    if scratch is not None:
+        d.scratch = _chk(scratch, array_shape, torch.float32).data_ptr()
+    if counts is not None:
+        assert counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
+        d.counts_dev = counts.data_ptr()
+    return d, out
+
+
+def _halo_pair(d, halo, planes):
+    """(below, above) plane tensors of a cell grid -> two pointers; None where no plane is held"""
+    lo, hi = planes if planes else (None, None)
+    below, above = min(int(halo), d.c0), min(int(halo), d.gz - d.c1)
+    lo = _chk(lo, (below, d.gy, d.gx), torch.float32) if below > 0 and lo is not None else None
+    hi = _chk(hi, (above, d.gy, d.gx), torch.float32) if above > 0 and hi is not None else None
+    return _p(lo), _p(hi)
+
+
+def redistanceInitSlab(d, liquid_phi, band, halo, phi_halo=None, out=None, counts=None):
+    """mgps_fields_slab_redistance_init on the window `d` (fields.slab_window): the initial pass, phi -> the unscaled state s T of
+    the window's planes.  phi_halo = (below or None, above or None): the min(halo, c0) planes below the window and the
+    min(halo, gz - c1) planes above it as (planes, ny, nx) tensors; one plane either way is needed.  counts[0] is raised by the
+    window's interface cells.  Returns the state.  Does not synchronise."""
+    desc, out = _redistance_desc((d.gz, d.gy, d.gx), d.base_shape, liquid_phi, band, 1.0, 0, 1, out, None, counts)
+    lo, hi = _halo_pair(d, halo, phi_halo)
+    with torch.cuda.device(liquid_phi.device):
+        check(lib().mgps_fields_slab_redistance_init(C.byref(d), C.byref(desc), int(halo), lo, hi, _stream()))
+    return out
+
+
+def redistanceRoundSlab(d, state, band, halo, state_halo=None, inner=4, last=False, dx=1.0, out=None, counts=None):
+    """mgps_fields_slab_redistance_round on the window `d`: one round of `inner` block-Jacobi iterations, state -> state.
+    state_halo: as phi_halo, of the neighbours' states before this round; a round of inner > 1 reads the planes
+    4 floor(c0 / 4) - 1 .. 4 ceil(c1 / 4) (halo = 4 always suffices), inner = 1 one plane either way; fewer is refused.  With `last`
+    the stores are multiplied by dx and counts[1] is raised by the window's cells the round changed.  Does not synchronise."""
+    desc, out = _redistance_desc((d.gz, d.gy, d.gx), d.base_shape, state, band, dx, 0, inner, out, None, counts)
+    lo, hi = _halo_pair(d, halo, state_halo)
+    with torch.cuda.device(state.device):
+        check(lib().mgps_fields_slab_redistance_round(C.byref(d), C.byref(desc), int(halo), lo, hi, int(bool(last)), _stream()))
+    return out
+
+
+def redistance(liquid_phi, band, dx=1.0, rounds=None, inner=4, out=None, scratch=None, counts=None):
+    """mgps_fields_redistance: liquid_phi -> the signed distance (in phi's units, dx per cell) within `band` cells of its zero
+    level set, +-band dx beyond; the sign of every cell (phi <= 0 is inside) is kept.  Out of place.
+    rounds = an integer: the single library call -- one initial launch and `rounds` rounds of `inner` block-Jacobi iterations, no
+    synchronisation; scratch (a grid like out; allocated unless given) is needed for rounds > 0; counts (an int64 CUDA tensor of 2)
+    is added to: [0] interface cells, [1] the cells the last round changed.
+    rounds = None, the convenience form: the initial pass, then batches of max(2, ceil(band)) rounds through the window entries on
+    [0, gz) until a round changes nothing.  The last round of a batch is the one that counts, and it writes dx state to `out`; where
+    it did change a cell the next batch goes on from that round's input.  One synchronisation (a read of the count) per batch.
+    counts then receives [0] and, as the fixpoint's property, [1] += 0.
+    Returns out."""
+    shape = tuple(liquid_phi.shape)
+    if rounds is not None:
+        if scratch is None and int(rounds) > 0:
+            scratch = torch.empty_like(liquid_phi)
+        d, out = _redistance_desc(shape, shape, liquid_phi, band, dx, rounds, inner, out, scratch, counts)
+        with torch.cuda.device(liquid_phi.device):
+            check(lib().mgps_fields_redistance(C.byref(d), _stream()))
+        return out
+    from .solver import expanded_layout
+
+    w = slab_window(shape, True, [0, expanded_layout(shape)[0][0]], 0)  # the whole grid as a window: [0, gz), no halo
+    tally = torch.zeros(2, dtype=torch.int64, device=liquid_phi.device)
+    out = torch.empty_like(liquid_phi) if out is None else out
+    a = redistanceInitSlab(w, liquid_phi, band, 0, counts=tally)
+    b = torch.empty_like(liquid_phi) if scratch is None else scratch
+    batch = max(2, -int(-float(band) // 1))
+    while True:
+        for _ in range(batch - 1):
+            a, b = redistanceRoundSlab(w, a, band, 0, inner=inner, out=b), a
+        tally[1] = 0
+        redistanceRoundSlab(w, a, band, 0, inner=inner, last=True, dx=dx, out=out, counts=tally)
+        if int(tally[1]) == 0:
+            break
+    if counts is not None:
+        counts += tally
+    return out

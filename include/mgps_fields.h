@@ -746,7 +746,8 @@ int mgps_fields_slab_sampled_velocity(const mgps_fields_slab *w, float *const sv
  *   counts_dev (device, unsigned long long[2], may be NULL) is ADDED to, as filled_dev is (initialise it): [0] the targets for
  *   which a clampB moved a coordinate of p1 or p_dep, [1] the window form's missed planes (below).  A cell counts once per scalar grid.
  * Limits: solids are not consulted -- a departure point inside a solid reads what is there; the caller extrapolates at least
- * ceil(max |dt u|) + 2 layers first (mgps_fields_extrapolate3); liquid_phi is not redistanced; float32 grids only. */
+ * ceil(max |dt u|) + 2 layers first (mgps_fields_extrapolate3); transport does not keep |grad phi| = 1 (mgps_fields_redistance,
+ * below, restores it); float32 grids only. */
 typedef struct mgps_advect_desc {
     int struct_size;             /* sizeof(mgps_advect_desc) */
     int gx, gy, gz;              /* the WHOLE simulation grid */
@@ -784,6 +785,65 @@ int mgps_fields_advect(const mgps_advect_desc *d, void *stream);
 int mgps_fields_slab_advect(const mgps_fields_slab *w, const mgps_advect_desc *d, int halo, const float *const velocity_lo[3],
                             const float *const velocity_hi[3], const float *const scalar_lo[4], const float *const scalar_hi[4],
                             void *stream);
+
+/* ---- redistancing: a fast iterative Eikonal pass -------------------------------------------------------------
+ * Transport does not keep |grad phi| = 1; this pass turns liquid_phi back into a signed distance within `band` cells of the surface,
+ * deterministically, out of place, on the device.  No counterpart in the reference; the definition here is the contract, and
+ * tests/redistance_reference.py restates it in numpy operation by operation.
+ *   Lengths are in cells; dx is the cell size in phi's units; band > 0 is in cells, B = (double)(float)band.  Inside means
+ *   phi <= 0 (mgps_fields_material_labels' rule: a redistanced phi labels exactly as its input does).
+ *   State.  The state of a cell is the float32 value s T: T >= 0 the distance in cells, s = - inside and + outside; an inside cell
+ *   with T = 0 is -0.0f.  All arithmetic is fp64 on float32 data and EVERY operation is rounded on its own (no contraction into
+ *   fused multiply-adds); a value is rounded to float32 where it is stored.
+ *   Interface cells: a cell x with an in-grid 6-neighbour of the other sign.  They are fixed by the initial pass and never
+ *   updated: d_cross = min over those neighbours n of phi_x / (phi_x - phi_n), in [0, 1]; g_c = (phi_+ - phi_-) / 2 where both
+ *   neighbours along c exist, else the one-sided difference, else 0; d_grad = |phi_x| / sqrt((g_x^2 + g_y^2) + g_z^2) where that sum
+ *   is > 0, else +inf; T0 = float(min(d_grad, d_cross, B)).  Every other cell starts at T0 = float(B).
+ *   Update G, of cells that are no interface cells: a_c = the least T of the two neighbours along c, a neighbour outside the whole
+ *   grid counting as +inf; sorted a1 <= a2 <= a3; t = a1 + 1; if t > a2: d = a1 - a2, t = 0.5 ((a1 + a2) + sqrt(2 - d d)); if
+ *   t > a3: s = (a1 + a2) + a3, q = (a1 a1 + a2 a2) + a3 a3, disc = max(s s - 3 (q - 1), 0), t = (s + sqrt(disc)) / 3;
+ *   T_new = min(T_old, float(min(t, B))).  (First-order Godunov; T only falls, and never below an interface cell's.)
+ *   A round is block Jacobi on tiles of 64 x 4 x 4 cells anchored at cell (0, 0, 0) of the WHOLE grid: a tile takes its cells and
+ *   a one-cell rim from the round's input, runs `inner` (1 .. 8) Jacobi iterations of G on its own cells with the rim held, and
+ *   writes its cells.  inner = 1 is plain Jacobi and does not depend on the tiling.  The fixpoint does not depend on inner.
+ *   Result.  After `rounds` rounds out = float(dx state); cells the front never reached hold +-B dx.
+ *   counts_dev (device, unsigned long long[2], may be NULL) is ADDED to: [0] the interface cells, [1] the cells whose value the
+ *   LAST round changed: the caller's test for "enough rounds" is counts[1] == 0.
+ *   No atomics on values, every cell is written by its own thread: the same inputs give the same bits on every run.
+ * Limits: solids are not consulted; first order; float32 grids only; the slab collective (the state's halo exchange per round) is
+ * not part of this header yet. */
+typedef struct mgps_redistance_desc {
+    int struct_size;      /* sizeof(mgps_redistance_desc) */
+    int gx, gy, gz;       /* the WHOLE simulation grid */
+    double band, dx;      /* finite, > 0 */
+    int rounds, inner;    /* rounds >= 0, inner 1 .. 8 */
+    const float *phi_in;  /* device cell grids */
+    float *phi_out;
+    float *scratch;       /* of phi_out's shape; may be NULL when rounds == 0, not read by the window entries */
+    unsigned long long *counts_dev;
+} mgps_redistance_desc;
+/* One initial launch and `rounds` launches that ping-pong between phi_out and scratch so that the last one writes phi_out.  Does
+ * not synchronise the stream.  Out of place: phi_out and scratch overlap no other array of the call; pointer ranges are compared.
+ * Refuses with a message, before any device work: NULL desc or a struct_size mismatch, an extent < 1 (or more than 262136 cells
+ * along y or z), a band or dx that is not finite and > 0, rounds < 0, inner outside 1 .. 8, a NULL array that is in use,
+ * overlapping buffers. */
+int mgps_fields_redistance(const mgps_redistance_desc *d, void *stream);
+/* The pass on a slab window, launch by launch and without communication.  The arrays in `d` are the window's planes c0 .. c1 - 1;
+ * d->gx, gy, gz are the whole grid's; d->rounds and d->scratch are not read.  *_lo holds the min(halo, c0) planes below the window,
+ * contiguous and ascending, *_hi the min(halo, gz - c1) planes above it (not read, may be NULL, where that count is 0).  Positions
+ * and the tiles' anchor are the whole grid's: the window's bits are the whole grid's.
+ * _init reads phi from phi_in and writes the state, unscaled, to phi_out; it reads one plane either way and adds the own planes'
+ * interface cells to counts_dev[0].  _round reads a state from phi_in and writes phi_out; with `last` set it multiplies its stores
+ * by dx and adds the own cells it changed to counts_dev[1], so the ranks' counts add up to the whole grid's.  A rank computes every
+ * whole-grid tile that meets its window from window plus halo and writes its own planes: a round reads the planes
+ * 4 floor(c0 / 4) - 1 .. 4 ceil(c1 / 4), clipped to the grid (inner = 1: c0 - 1 .. c1).  Four planes either way always suffice.
+ * Fewer planes than that is refused, not counted.  The whole grid is the window [0, gz) without halo; one kernel serves both forms.
+ * Refuses also: not a slab window, a window of other extents than the desc's, a negative halo, a NULL halo array where planes are
+ * held, too few halo planes. */
+int mgps_fields_slab_redistance_init(const mgps_fields_slab *w, const mgps_redistance_desc *d, int halo, const float *phi_lo,
+                                     const float *phi_hi, void *stream);
+int mgps_fields_slab_redistance_round(const mgps_fields_slab *w, const mgps_redistance_desc *d, int halo, const float *state_lo,
+                                      const float *state_hi, int last, void *stream);
 
 #ifdef __cplusplus
 }
