@@ -1,40 +1,25 @@
 // Advection on the device (include/mgps_fields.h, "advection"): semi-Lagrangian and MacCormack passes over the three
 // face grids of the velocity and up to four cell grids, on a whole grid or a slab window.
-// One launch over the rasteriser's tiles of kTX x kTY x kTZ cells, two under MacCormack.  A thread owns its cell's scalars and the backward
-// face of its cell per axis, and the forward face where the box ends (sampledVelocityKernel's ownership).  The first velocity sample of a
+// One launch over the tiles of mgps_tile_pass.h, two under MacCormack.  A thread owns its cell's scalars and the
+// backward face of its cell per axis, and the forward face where the box ends (CellFaces' ownership).  The first velocity sample of a
 // trace, U(x), sits at a fixed offset from the thread's cell: the workgroup stages its tile of the three components with a rim in LDS and
 // every U(x) is read from there.  The midpoint and departure samples depend on the data and go to global memory.
 // Every rule is stated once: latticeOf (where a grid's nodes are and which planes are held), stencilAt (section 20's interpolant: indices
 // and weights), combine (the eight values, their least and greatest), departure (the trace).  Both launches and both forms inline the
 // same functions, with explicit fused multiply-adds where a product feeds a sum, so a departure point has the same bits wherever it is
 // formed again.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <string>
-#include <vector>
 
-#include "mgps_fields.h"
-#include "mgps_internal.h"
-#include "mgps_slab_call.h"
+#include "mgps_tile_pass.h"
 
 using namespace mgps;
 
 namespace {
 
-constexpr int kTX = 64, kTY = 4, kTZ = 4, kThreads = 256;
 // the staged box: the tile's nodes and one node below and above per axis; along z one more above, which the z-face lattice asks for
 // (with weight 0) at the forward face of a window that ends inside the grid
 constexpr int kSX = kTX + 2, kSY = kTY + 2, kSZ = kTZ + 3, kStage = kSX * kSY * kSZ;
 constexpr int kGrids = 7;  // vx, vy, vz, then four scalars
-static_assert(kTX == 64 && kTY * 64 == kThreads, "one wave per row of a tile plane");
-
-// the planes of a grid that the call holds: the window's, and the halo planes below and above it
-struct Held {
-    const float *win, *lo, *hi;
-};
 
 struct AdvectArgs {
     int gx, gy, gz;    // the whole grid
@@ -42,7 +27,7 @@ struct AdvectArgs {
     int below, above;  // halo planes held on either side
     int order, scalars, faces;  // trace order; scalar grids; 1 = the velocity is advected too
     double dt;
-    Held in[kGrids];
+    HeldPlanes in[kGrids];
     const float *hat[kGrids];  // second launch: the semi-Lagrangian result of the first
     float *out[kGrids];
     unsigned long long *counts;
@@ -67,12 +52,9 @@ __device__ __forceinline__ Lattice latticeOf(const AdvectArgs &a, int kind)
 }
 
 // the plane z (held) of a grid
-__device__ __forceinline__ const float *planeOf(const Held &h, const Lattice &L, int z)
+__device__ __forceinline__ const float *planeOf(const HeldPlanes &h, const Lattice &L, int z)
 {
-    const size_t plane = size_t(L.n[0]) * size_t(L.n[1]);
-    if (z < L.w0) return h.lo + size_t(z - L.h0) * plane;
-    if (z < L.w1) return h.win + size_t(z - L.w0) * plane;
-    return h.hi + size_t(z - L.w1) * plane;
+    return heldPlane(h, size_t(L.n[0]) * size_t(L.n[1]), L.w0, L.w1, L.h0, z);
 }
 
 // S's indices and weights at the point p.  missed: a plane inside the grid that is not held was asked for; the nearest held one is read
@@ -115,7 +97,7 @@ __device__ __forceinline__ double combine(const Stencil &s, const float v[8], do
     return lerp(s.t[2], lerp(s.t[1], x00, x10), lerp(s.t[1], x01, x11));
 }
 
-__device__ __forceinline__ double sampleHeld(const Held &h, const Lattice &L, const Stencil &s, double &lo, double &hi)
+__device__ __forceinline__ double sampleHeld(const HeldPlanes &h, const Lattice &L, const Stencil &s, double &lo, double &hi)
 {
     const float *p0 = planeOf(h, L, s.i0[2]), *p1 = planeOf(h, L, s.i1[2]);
     const size_t r0 = size_t(s.i0[1]) * size_t(L.n[0]), r1 = size_t(s.i1[1]) * size_t(L.n[0]);
@@ -178,12 +160,6 @@ __device__ __forceinline__ void departure(const AdvectArgs &a, const double x[3]
     }
 }
 
-// a store of a streamed tile: the pass does not read its outputs again
-__device__ __forceinline__ void put(float *p, float v)
-{
-    __builtin_nontemporal_store(v, p);
-}
-
 // PASS 0: out = the semi-Lagrangian value (under MacCormack `out` is the scratch).  PASS 1: the MacCormack correction from in and hat
 template <int PASS>
 __global__ __launch_bounds__(kThreads) void advectKernel(AdvectArgs a)
@@ -191,10 +167,11 @@ __global__ __launch_bounds__(kThreads) void advectKernel(AdvectArgs a)
     __shared__ float stage[3][kStage];
     __shared__ unsigned int tally[2];
 
+    // TileThread's mapping (mgps_tile_pass.h), restated: through the struct the staging loops cost 20 instructions more (LABNOTES R14)
     const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
     const int ti0 = int(blockIdx.x) * kTX, tj0 = int(blockIdx.y) * kTY, k0 = int(blockIdx.z) * kTZ;
     const int kg0 = k0 + a.c0;
-    if (t < 2) tally[t] = 0;
+    zeroTally(tally);
 
     // the three components' nodes around the tile; a node outside the grid or outside the held planes is the nearest one inside
 #pragma unroll
@@ -219,6 +196,7 @@ __global__ __launch_bounds__(kThreads) void advectKernel(AdvectArgs a)
                 const int first = kind == 0 ? 3 : kind - 1, grids = kind == 0 ? a.scalars : 1;
                 if (grids == 0) continue;
                 const Lattice L = latticeOf(a, kind);
+                // CellFaces' rule, restated: indexing its arrays by a run-time `kind` cost 7 and 11 VGPRs and 72 B of scratch (R14)
                 const int more = kind == 1 ? i == a.gx - 1 : kind == 2 ? j == a.gy - 1 : kind == 3 ? k == a.planes - 1 : 0;
                 for (int side = 0; side <= more; ++side) {
                     const int fi = i + (kind == 1 ? side : 0), fj = j + (kind == 2 ? side : 0), fk = k + (kind == 3 ? side : 0);
@@ -255,7 +233,7 @@ __global__ __launch_bounds__(kThreads) void advectKernel(AdvectArgs a)
                         for (int g = 0; g < grids; ++g) {
                             double lo, hi, lo2, hi2;
                             (void)sampleHeld(a.in[first + g], L, s, lo, hi);
-                            const double back = sampleHeld(Held{a.hat[first + g], nullptr, nullptr}, L, sf, lo2, hi2);
+                            const double back = sampleHeld(HeldPlanes{a.hat[first + g], nullptr, nullptr}, L, sf, lo2, hi2);
                             const double m = fma(0.5, double(a.in[first + g].win[at]) - back, double(a.hat[first + g][at]));
                             put(a.out[first + g] + at, float(fmin(fmax(m, lo), hi)));
                         }
@@ -265,27 +243,10 @@ __global__ __launch_bounds__(kThreads) void advectKernel(AdvectArgs a)
         }
     }
     if (PASS == 0 && a.counts) {
-        if (nClamped) atomicAdd(&tally[0], nClamped);
-        if (nMissed) atomicAdd(&tally[1], nMissed);
-        __syncthreads();
-        if (t < 2 && tally[t]) atomicAdd(a.counts + t, (unsigned long long)tally[t]);
+        const unsigned int found[2] = {nClamped, nMissed};
+        addTally(tally, found, a.counts);
     }
 }
-
-int hipStatus(const char *fn, hipError_t e)
-{
-    if (e == hipSuccess) return MGPS_OK;
-    setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(e));
-    return MGPS_ERR_HIP;
-}
-
-// a byte range of one array of the call
-struct Range {
-    const char *p;
-    size_t bytes;
-    int role;  // 0 read, 1 scratch, 2 out
-    std::string name;
-};
 
 // What both entries refuse of a desc, before any device work; [c0, c0 + planes) with the halo planes held is the box of the arrays.
 // Fills the kernel's arguments
@@ -293,9 +254,7 @@ int checkDesc(const char *fn, const mgps_advect_desc *d, int c0, int planes, int
               const float *const vhi[3], const float *const slo[4], const float *const shi[4], AdvectArgs &a)
 {
     if (!d || d->struct_size != int(sizeof(mgps_advect_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_advect_desc)");
-    if (d->gx < 1 || d->gy < 1 || d->gz < 1)
-        return refuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(d->gx) + ", " + std::to_string(d->gy) + ", " + std::to_string(d->gz) + ")");
-    if ((d->gy + kTY - 1) / kTY > 65535 || (d->gz + kTZ - 1) / kTZ > 65535) return refuse(fn, "more than 262140 cells along y or z");
+    if (int rc = checkTileExtents(fn, d->gx, d->gy, d->gz, false); rc != MGPS_OK) return rc;
     if (d->scheme != 0 && d->scheme != 1) return refuse(fn, "scheme = " + std::to_string(d->scheme) + " is neither 0 (semi-Lagrangian) nor 1 (MacCormack)");
     if (d->trace_order != 1 && d->trace_order != 2) return refuse(fn, "trace_order = " + std::to_string(d->trace_order) + " is neither 1 nor 2");
     if (!std::isfinite(d->dt)) return refuse(fn, "dt is not finite");
@@ -307,12 +266,12 @@ int checkDesc(const char *fn, const mgps_advect_desc *d, int c0, int planes, int
     const size_t gx = size_t(d->gx), gy = size_t(d->gy), pl = size_t(planes);
     const size_t plane[4] = {gx * gy, (gx + 1) * gy, gx * (gy + 1), gx * gy};  // by grid kind
     const size_t held[4] = {pl, pl, pl, pl + 1};
-    std::vector<Range> ranges;
-    const auto add = [&](const void *p, int kind, int role, const std::string &name) {
-        ranges.push_back(Range{static_cast<const char *>(p), plane[kind] * held[kind] * sizeof(float), role, name});
+    ArrayRanges arrays;
+    const auto add = [&](const void *p, int kind, bool written, const std::string &name) {
+        arrays.add(name, p, plane[kind] * held[kind] * sizeof(float), written);
     };
     const auto addHalo = [&](const void *p, int kind, int count, const std::string &name) {
-        ranges.push_back(Range{static_cast<const char *>(p), plane[kind] * size_t(count) * sizeof(float), 0, name});
+        arrays.add(name, p, plane[kind] * size_t(count) * sizeof(float), false);
     };
     a = AdvectArgs{};
     a.gx = d->gx, a.gy = d->gy, a.gz = d->gz, a.c0 = c0, a.planes = planes, a.below = below, a.above = above;
@@ -327,35 +286,27 @@ int checkDesc(const char *fn, const mgps_advect_desc *d, int c0, int planes, int
         const float *lo = face ? (vlo ? vlo[q] : nullptr) : (slo ? slo[q] : nullptr);
         const float *hi = face ? (vhi ? vhi[q] : nullptr) : (shi ? shi[q] : nullptr);
         if (!in) return refuse(fn, base + "_in" + idx + " is NULL");
-        add(in, kind, 0, base + "_in" + idx);
-        if (below > 0 && !lo) return refuse(fn, base + "_lo" + idx + " is NULL: " + std::to_string(below) + " halo planes lie below the window");
-        if (above > 0 && !hi) return refuse(fn, base + "_hi" + idx + " is NULL: " + std::to_string(above) + " halo planes lie above the window");
+        add(in, kind, false, base + "_in" + idx);
+        if (int rc = checkHaloArrays(fn, base + "_lo" + idx, lo, below, base + "_hi" + idx, hi, above); rc != MGPS_OK) return rc;
         if (below > 0) addHalo(lo, kind, below, base + "_lo" + idx);
         if (above > 0) addHalo(hi, kind, above, base + "_hi" + idx);
-        a.in[g] = Held{in, below > 0 ? lo : nullptr, above > 0 ? hi : nullptr};
+        a.in[g] = HeldPlanes{in, below > 0 ? lo : nullptr, above > 0 ? hi : nullptr};
         if (face && outs == 0) continue;
         if (!out) return refuse(fn, base + "_out" + idx + " is NULL");
-        add(out, kind, 2, base + "_out" + idx);
+        add(out, kind, true, base + "_out" + idx);
         if (d->scheme == 1) {
             if (!scratch) return refuse(fn, base + "_scratch" + idx + " is NULL: MacCormack needs scratch grids of the outputs' shapes");
-            add(scratch, kind, 1, base + "_scratch" + idx);
+            add(scratch, kind, true, base + "_scratch" + idx);
         }
         a.out[g] = out, a.hat[g] = scratch;
     }
-    // an array that is written (out, scratch) overlaps no other array of the call
-    for (size_t p = 0; p < ranges.size(); ++p)
-        for (size_t q = p + 1; q < ranges.size(); ++q) {
-            const Range &r = ranges[p], &s = ranges[q];
-            if (r.role == 0 && s.role == 0) continue;  // (two arrays that are only read may be one)
-            if (r.p < s.p + s.bytes && s.p < r.p + r.bytes) return refuse(fn, r.name + " and " + s.name + " overlap: the pass is out of place");
-        }
-    return MGPS_OK;
+    return arrays.refuseOverlap(fn);  // (out and scratch are written)
 }
 
 // one launch for the semi-Lagrangian scheme, two under MacCormack: the first fills the scratch grids, the second corrects and limits
 int runAdvect(const char *fn, const AdvectArgs &args, int scheme, hipStream_t st)
 {
-    const dim3 grid(unsigned((args.gx + kTX - 1) / kTX), unsigned((args.gy + kTY - 1) / kTY), unsigned((args.planes + kTZ - 1) / kTZ));
+    const dim3 grid = tileGrid(args.gx, args.gy, args.planes);
     AdvectArgs first = args;
     if (scheme == 1)
         for (int g = 0; g < kGrids; ++g) first.out[g] = const_cast<float *>(args.hat[g]);
@@ -381,17 +332,12 @@ int mgps_fields_slab_advect(const mgps_fields_slab *w, const mgps_advect_desc *d
                             const float *const velocity_hi[3], const float *const scalar_lo[4], const float *const scalar_hi[4], void *stream)
 try {
     const char *fn = "mgps_fields_slab_advect";
-    if (!fieldsSlabWindow(w, fn)) return MGPS_ERR_INVALID_ARGUMENT;
-    if (halo < 0) return refuse(fn, "halo = " + std::to_string(halo) + " is negative");
-    if (d && d->struct_size == int(sizeof(mgps_advect_desc))) {
-        if (w->gx != d->gx || w->gy != d->gy || w->gz != d->gz)
-            return refuse(fn, "the window is not one of the desc's extents (gx, gy, gz are the whole grid's in both)");
-        if (d->scheme == 1)
-            return refuse(fn, "scheme = 1 (MacCormack) on a window needs the semi-Lagrangian result on the halo planes too: the window form takes "
-                              "scheme = 0 only");
-    }
+    int below = 0, above = 0;
+    if (int rc = checkWindowOf(fn, w, d, halo, below, above); rc != MGPS_OK) return rc;
+    if (d && d->struct_size == int(sizeof(mgps_advect_desc)) && d->scheme == 1)
+        return refuse(fn, "scheme = 1 (MacCormack) on a window needs the semi-Lagrangian result on the halo planes too: the window form takes "
+                          "scheme = 0 only");
     AdvectArgs a;
-    const int below = std::min(halo, w->c0), above = std::min(halo, w->gz - w->c1);
     if (int rc = checkDesc(fn, d, w->c0, w->c1 - w->c0, below, above, velocity_lo, velocity_hi, scalar_lo, scalar_hi, a); rc != MGPS_OK) return rc;
     return runAdvect(fn, a, 0, static_cast<hipStream_t>(stream));
 }

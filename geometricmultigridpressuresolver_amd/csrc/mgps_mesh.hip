@@ -15,28 +15,19 @@
 //   meshVelocityKernel  the distance kernel's walk, which also keeps the table row of the triangle that attains the minimum (ties by
 //                       the turned index triple, read from the table only on an equal d^2); after the walk a thread classifies the
 //                       closest point on its winner once more for the weights, gathers the three vertex velocities and stores.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
 #include <limits>
-#include <string>
-#include <vector>
 
-#include "mgps_fields.h"
-#include "mgps_internal.h"
-#include "mgps_slab_call.h"
+#include "mgps_tile_pass.h"
 
 using namespace mgps;
 
 namespace {
 
-// a wave per x-row of 64 samples: 256 B per store request, and one word of inside bits per row
-constexpr int kTX = 64, kTY = 4, kTZ = 4, kThreads = 256;
+// (the tiles of mgps_tile_pass.h: a wave per x-row of 64 samples is also one word of inside bits per row)
 constexpr int kCY = 16, kCZ = 16;  // columns (y, z) per workgroup of the sign pass
 constexpr int kMaxSamples = 1024;
-static_assert(kTX == 64 && kTY * 64 == kThreads && kCY * kCZ == kThreads, "one wave per row of a tile plane, one thread per column");
+static_assert(kCY * kCZ == kThreads, "one thread per column");
 
 // one row of the device table: the turned triangle's coordinates (a, b, c) and vertex indices
 struct MeshTri {
@@ -203,8 +194,8 @@ __device__ __forceinline__ double pointTriangle2(const double *p, const double a
 
 __global__ __launch_bounds__(kThreads) void meshDistanceKernel(MeshArgs a)
 {
-    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
-    const int i = int(blockIdx.x) * kTX + lane, j = int(blockIdx.y) * kTY + wave, k0 = int(blockIdx.z) * kTZ;
+    const TileThread th;
+    const int lane = th.lane, i = th.i, j = th.j, k0 = th.k0;
     // thread (lane, wave) owns the samples (i, j, k0 + kk), kk = 0 .. kTZ - 1; a thread past the box's end works on the last sample
     const double x = samplePos(a.origin[0], a.spacing, min(i, a.nx - 1)), y = samplePos(a.origin[1], a.spacing, min(j, a.ny - 1));
     double z[kTZ], best[kTZ];
@@ -297,8 +288,8 @@ __device__ __forceinline__ bool keyBefore(const MeshTri *table, int r, int w)
 __global__ __launch_bounds__(kThreads) void meshVelocityKernel(MeshVelocityArgs va)
 {
     const MeshArgs &a = va.m;
-    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
-    const int i = int(blockIdx.x) * kTX + lane, j = int(blockIdx.y) * kTY + wave, k0 = int(blockIdx.z) * kTZ;
+    const TileThread th;
+    const int lane = th.lane, i = th.i, j = th.j, k0 = th.k0;
     // the samples of meshDistanceKernel's thread, and its walk: d^2 by the same expressions, so its minimum is that kernel's
     const double x = samplePos(a.origin[0], a.spacing, min(i, a.nx - 1)), y = samplePos(a.origin[1], a.spacing, min(j, a.ny - 1));
     double z[kTZ], best[kTZ];
@@ -459,13 +450,6 @@ int checkedMass(const char *fn, int vertices, int triangles, const double *xyz, 
     return MGPS_OK;
 }
 
-int hipStatus(const char *fn, hipError_t e)
-{
-    if (e == hipSuccess) return MGPS_OK;
-    setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(e));
-    return MGPS_ERR_HIP;
-}
-
 // the inclusive range [lo, hi] of the samples 0 .. n - 1 of one axis within [from, to], one sample wider on each side than the
 // quotient says (its rounding must not lose a sample); false when empty
 bool sampleRange(double from, double to, double origin, double spacing, int n, int &lo, int &hi)
@@ -539,8 +523,7 @@ int runMesh(const char *fn, const mgps_mesh_desc *d, const double *velocity, flo
     }
     const size_t entries = size_t(offsets[size_t(binCount)]);
 
-    // one block, allocated and released in stream order; the host tables go up in one copy from pageable memory (hipMemcpyAsync
-    // returns once it is staged): no synchronisation here
+    // one block in stream order; the host tables, its first part, go up in one copy
     const size_t xyzBytes = size_t(d->vertices) * 3 * sizeof(double), triBytes = nt * 3 * sizeof(int32_t), binBytes = nt * sizeof(TriBins);
     const size_t offBytes = offsets.size() * sizeof(int);
     const size_t atXyz = 0, atTri = atXyz + roundUp(xyzBytes), atBins = atTri + roundUp(triBytes), atOff = atBins + roundUp(binBytes);
@@ -557,37 +540,28 @@ int runMesh(const char *fn, const mgps_mesh_desc *d, const double *velocity, flo
     if (velocity) std::copy_n(reinterpret_cast<const unsigned char *>(velocity), xyzBytes, stage.data() + atVel);
 
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    void *dev = nullptr;
-    if (const hipError_t e = hipMallocAsync(&dev, bytes, st); e != hipSuccess) {
-        (void)hipGetLastError();
-        setLastGlobalError(std::string(fn) + ": device allocation failed (" + hipGetErrorString(e) + ")");
-        return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MGPS_ERR_NO_DEVICE : MGPS_ERR_ALLOC;
-    }
-    unsigned char *base = static_cast<unsigned char *>(dev);
-    a.xyz = reinterpret_cast<const double *>(base + atXyz), a.tri = reinterpret_cast<const int32_t *>(base + atTri);
-    a.bins = reinterpret_cast<const TriBins *>(base + atBins), a.offsets = reinterpret_cast<const int *>(base + atOff);
-    a.table = reinterpret_cast<MeshTri *>(base + atTable), a.cursor = reinterpret_cast<int *>(base + atCursor);
-    a.list = reinterpret_cast<int *>(base + atList), a.inside = reinterpret_cast<unsigned long long *>(base + atInside);
-    a.sdf = d->sdf;
-    int rc = hipStatus(fn, hipMemcpyAsync(dev, stage.data(), hostBytes, hipMemcpyHostToDevice, st));
-    // (the cursors must start at zero; the lists that follow them are cleared along with them, so that every entry is a triangle)
-    if (rc == MGPS_OK) rc = hipStatus(fn, hipMemsetAsync(a.cursor, 0, atInside - atCursor, st));
-    if (rc == MGPS_OK) {
+    return withStreamBlock(fn, st, bytes, stage.data(), hostBytes, [&](void *dev) {
+        unsigned char *base = static_cast<unsigned char *>(dev);
+        a.xyz = reinterpret_cast<const double *>(base + atXyz), a.tri = reinterpret_cast<const int32_t *>(base + atTri);
+        a.bins = reinterpret_cast<const TriBins *>(base + atBins), a.offsets = reinterpret_cast<const int *>(base + atOff);
+        a.table = reinterpret_cast<MeshTri *>(base + atTable), a.cursor = reinterpret_cast<int *>(base + atCursor);
+        a.list = reinterpret_cast<int *>(base + atList), a.inside = reinterpret_cast<unsigned long long *>(base + atInside);
+        a.sdf = d->sdf;
+        // (the cursors must start at zero; the lists that follow them are cleared along with them, so that every entry is a triangle)
+        if (int rc = hipStatus(fn, hipMemsetAsync(a.cursor, 0, atInside - atCursor, st)); rc != MGPS_OK) return rc;
         meshFillKernel<<<unsigned((nt + kThreads - 1) / kThreads), kThreads, 0, st>>>(a);
         meshSignKernel<<<dim3(unsigned(a.words), unsigned(a.colsY), unsigned(a.colsZ)), kThreads, 0, st>>>(a);
-        const dim3 tilesGrid(unsigned(a.tilesX), unsigned(a.tilesY), unsigned(a.tilesZ));
+        const dim3 tiles = tileGrid(d->nx, d->ny, d->nz);
         if (velocity) {
             MeshVelocityArgs va{};
             va.m = a, va.velocity = reinterpret_cast<const double *>(base + atVel);
             for (int c = 0; c < 3; ++c) va.vel[c] = vel[c];
-            meshVelocityKernel<<<tilesGrid, kThreads, 0, st>>>(va);
+            meshVelocityKernel<<<tiles, kThreads, 0, st>>>(va);
         } else {
-            meshDistanceKernel<<<tilesGrid, kThreads, 0, st>>>(a);
+            meshDistanceKernel<<<tiles, kThreads, 0, st>>>(a);
         }
-        rc = hipStatus(fn, hipGetLastError());
-    }
-    const int freed = hipStatus(fn, hipFreeAsync(dev, st));
-    return rc != MGPS_OK ? rc : freed;
+        return hipStatus(fn, hipGetLastError());
+    });
 }
 }  // namespace
 

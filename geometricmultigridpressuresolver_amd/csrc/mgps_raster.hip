@@ -1,30 +1,21 @@
 // Rigid bodies rasterised on the device (include/mgps_fields.h, "rigid bodies rasterised"): solid_phi, the three
 // cut-weight face grids and the three body-id face grids from a host table of shapes and poses, on a whole grid or a slab window.
-// One launch over tiles of kTX x kTY x kTZ cells.  A workgroup tests the bodies' reach boxes against its tile and compacts the hits
+// One launch over the tiles of mgps_tile_pass.h.  A workgroup tests the bodies' reach boxes against its tile and compacts the hits
 // into an LDS list in ascending id; with an empty list it streams the static values through.  Otherwise it evaluates the tile's
 // (kTX + 1)(kTY + 1)(kTZ + 1) nodes over the list into LDS (fp64 phi, uint8 owner) and writes its cells and the faces it owns from
 // them: a tile owns the backward face of each of its cells per axis, and the forward face where the grid ends.  A node on a tile's
 // rim is evaluated by every tile that holds it, each over its own list -- the same value, since a body off a tile's list does not
 // reach any of its nodes and contributes `band` there either way.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <new>
-#include <string>
-#include <vector>
 
-#include "mgps_fields.h"
-#include "mgps_internal.h"
-#include "mgps_slab_call.h"
+#include "mgps_tile_pass.h"
 
 using namespace mgps;
 
 namespace {
 
-// a wave per x-row of 64 cells: 256 B per request on the cell grid, and the face grids' rows (gx + 1 or gx entries) stay unit stride
-constexpr int kTX = 64, kTY = 4, kTZ = 4, kThreads = 256;
 constexpr int kNX = kTX + 1, kNY = kTY + 1, kNZ = kTZ + 1, kNodes = kNX * kNY * kNZ;
-static_assert(kTX == 64 && kTY * 64 == kThreads, "one wave per row of a tile plane");
 
 // one row of the device table: the shape, and its reach box
 struct RasterBody {
@@ -131,27 +122,6 @@ __device__ __forceinline__ void faceFromCorners(const double p[4], const uint8_t
     owner = w < 1.f ? leastOwner : 0;
 }
 
-// where cell (i, j, k) of the box and the faces it writes live: its backward face per axis, and the forward one (f + step) where the
-// box ends
-struct CellFaces {
-    size_t c, f[3], step[3];
-    bool more[3];
-    __device__ __forceinline__ CellFaces(const RasterArgs &a, int i, int j, int k)
-    {
-        c = (size_t(k) * a.gy + j) * a.gx + i;
-        f[0] = (size_t(k) * a.gy + j) * (size_t(a.gx) + 1) + i, f[1] = (size_t(k) * (size_t(a.gy) + 1) + j) * a.gx + i, f[2] = c;
-        step[0] = 1, step[1] = size_t(a.gx), step[2] = size_t(a.gx) * a.gy;
-        more[0] = i == a.gx - 1, more[1] = j == a.gy - 1, more[2] = k == a.planes - 1;
-    }
-};
-
-// a store of a streamed tile: the pass does not read its outputs again (measured at 480^3: 9 % of the pass)
-template <class T>
-__device__ __forceinline__ void put(T *p, T v)
-{
-    __builtin_nontemporal_store(v, p);
-}
-
 // A tile no body reaches: the static values go through (phi against band, the weights against 1), with ids 0.  The loads of the
 // thread's kTZ cells are all issued before the first store
 __device__ __forceinline__ void streamCells(const RasterArgs &a, int i, int j, int k0)
@@ -190,6 +160,7 @@ __global__ __launch_bounds__(kThreads) void rasterKernel(RasterArgs a)
     __shared__ uint8_t list[256];
     __shared__ unsigned long long hitMask[kThreads / 64];
 
+    // (TileThread's mapping, restated: through the struct the node loop below compiles to other code, LABNOTES R14)
     const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
     const int i0 = int(blockIdx.x) * kTX, j0 = int(blockIdx.y) * kTY, k0 = int(blockIdx.z) * kTZ;
     const int kg0 = k0 + a.c0;
@@ -320,9 +291,7 @@ int checkShape(const char *fn, int r, const mgps_body_shape &s)
 int checkDesc(const char *fn, const mgps_raster_desc *d)
 {
     if (!d || d->struct_size != int(sizeof(mgps_raster_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_raster_desc)");
-    if (d->gx <= 0 || d->gy <= 0 || d->gz <= 0)
-        return refuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(d->gx) + ", " + std::to_string(d->gy) + ", " + std::to_string(d->gz) + ")");
-    if ((d->gy + kTY - 1) / kTY > 65535 || (d->gz + kTZ - 1) / kTZ > 65535) return refuse(fn, "more than 262140 cells along y or z");
+    if (int rc = checkTileExtents(fn, d->gx, d->gy, d->gz, false); rc != MGPS_OK) return rc;
     if (d->bodies < 1 || d->bodies > 255) return refuse(fn, "bodies = " + std::to_string(d->bodies) + " is outside 1 .. 255");
     if (!d->shapes) return refuse(fn, "shapes is NULL");
     if (!(d->band >= 2.0 && d->band <= 16.0)) return refuse(fn, "band must lie in 2 .. 16 cells");
@@ -339,38 +308,21 @@ int checkDesc(const char *fn, const mgps_raster_desc *d)
     return MGPS_OK;
 }
 
-int hipStatus(const char *fn, hipError_t e)
-{
-    if (e == hipSuccess) return MGPS_OK;
-    setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(e));
-    return MGPS_ERR_HIP;
-}
-
-// the launch on the planes [c0, c0 + planes) of a checked desc.  The table goes up from a host copy (pageable memory: hipMemcpyAsync
-// returns once it is staged) into a block that is allocated and released in stream order: no synchronisation here
+// the launch on the planes [c0, c0 + planes) of a checked desc; the table goes up from a host copy into a block in stream order
 int runRaster(const char *fn, const mgps_raster_desc *d, int c0, int planes, hipStream_t st)
 {
     std::vector<RasterBody> rows(size_t(d->bodies) + 1);
     for (int r = 1; r <= d->bodies; ++r) rows[size_t(r)] = tableRow(d->shapes[r], d->band);
-    void *dev = nullptr;
-    if (const hipError_t e = hipMallocAsync(&dev, rows.size() * sizeof(RasterBody), st); e != hipSuccess) {
-        (void)hipGetLastError();
-        setLastGlobalError(std::string(fn) + ": device allocation failed (" + hipGetErrorString(e) + ")");
-        return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MGPS_ERR_NO_DEVICE : MGPS_ERR_ALLOC;
-    }
-    int rc = hipStatus(fn, hipMemcpyAsync(dev, rows.data(), rows.size() * sizeof(RasterBody), hipMemcpyHostToDevice, st));
-    if (rc == MGPS_OK) {
+    const size_t bytes = rows.size() * sizeof(RasterBody);
+    return withStreamBlock(fn, st, bytes, rows.data(), bytes, [&](void *dev) {
         RasterArgs a{};
         a.gx = d->gx, a.gy = d->gy, a.planes = planes, a.c0 = c0, a.bodies = d->bodies, a.band = d->band, a.minOpen = d->min_open;
         a.table = static_cast<const RasterBody *>(dev);
         a.staticPhi = d->static_solid_phi, a.phi = d->solid_phi;
         for (int q = 0; q < 3; ++q) a.staticCw[q] = d->static_cut_weights[q], a.cw[q] = d->cut_weights[q], a.body[q] = d->body[q];
-        const dim3 grid(unsigned((d->gx + kTX - 1) / kTX), unsigned((d->gy + kTY - 1) / kTY), unsigned((planes + kTZ - 1) / kTZ));
-        rasterKernel<<<grid, kThreads, 0, st>>>(a);
-        rc = hipStatus(fn, hipGetLastError());
-    }
-    const int freed = hipStatus(fn, hipFreeAsync(dev, st));
-    return rc != MGPS_OK ? rc : freed;
+        rasterKernel<<<tileGrid(d->gx, d->gy, planes), kThreads, 0, st>>>(a);
+        return hipStatus(fn, hipGetLastError());
+    });
 }
 
 // ---- velocity samples of deforming colliders on the face grids (include/mgps_fields.h, "deforming mesh colliders"; DESIGN.md
@@ -426,15 +378,14 @@ __device__ __forceinline__ float sampledFace(const SampledBody &b, int axis, int
     return float(((R[0] * u[0] + R[1] * u[1]) + R[2] * u[2]) + frame);
 }
 
-// A thread per cell and kTZ planes, as the rasteriser's tiles: a cell's backward face per axis, and the forward one where the box
-// ends.  Three id loads per cell; the table row and the samples are read only where a sampled body owns the face
+// A thread per cell and kTZ planes: the faces a cell owns (CellFaces).  Three id loads per cell; the table row and the samples are
+// read only where a sampled body owns the face
 __global__ __launch_bounds__(kThreads) void sampledVelocityKernel(SampledArgs s)
 {
-    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
-    const int i = int(blockIdx.x) * kTX + lane, j = int(blockIdx.y) * kTY + wave, k0 = int(blockIdx.z) * kTZ;
+    const TileThread th;
+    const int i = th.i, j = th.j, k0 = th.k0;
     if (i >= s.gx || j >= s.gy) return;
-    RasterArgs box{};  // (CellFaces reads the box's extents only)
-    box.gx = s.gx, box.gy = s.gy, box.planes = s.planes;
+    const TileBox box{s.gx, s.gy, s.planes};
 #pragma unroll
     for (int kk = 0; kk < kTZ; ++kk) {
         const int k = k0 + kk;
@@ -458,9 +409,7 @@ int checkSampled(const char *fn, float *const sv[3], const int32_t *const body[3
                  const mgps_body_velocity *velocities, int gx, int gy, int gz)
 {
     if (bodies < 1 || bodies > 255) return refuse(fn, "bodies = " + std::to_string(bodies) + " is outside 1 .. 255");
-    if (gx <= 0 || gy <= 0 || gz <= 0)
-        return refuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(gx) + ", " + std::to_string(gy) + ", " + std::to_string(gz) + ")");
-    if ((gy + kTY - 1) / kTY > 65535 || (gz + kTZ - 1) / kTZ > 65535) return refuse(fn, "more than 262140 cells along y or z");
+    if (int rc = checkTileExtents(fn, gx, gy, gz, false); rc != MGPS_OK) return rc;
     if (!sv || !sv[0] || !sv[1] || !sv[2]) return refuse(fn, "solid velocity: three grids are required");
     if (!body || !body[0] || !body[1] || !body[2]) return refuse(fn, "body: three grids are required");
     if (!shapes) return refuse(fn, "shapes is NULL");
@@ -478,7 +427,7 @@ int checkSampled(const char *fn, float *const sv[3], const int32_t *const body[3
     return MGPS_OK;
 }
 
-// the launch on the planes [c0, c0 + planes) of checked arguments; the table goes up as the rasteriser's does
+// the launch on the planes [c0, c0 + planes) of checked arguments; the table goes up into a block in stream order
 int runSampled(const char *fn, float *const sv[3], const int32_t *const body[3], int bodies, const mgps_body_shape *shapes,
                const mgps_body_velocity *velocities, int gx, int gy, int c0, int planes, hipStream_t st)
 {
@@ -492,23 +441,14 @@ int runSampled(const char *fn, float *const sv[3], const int32_t *const body[3],
         for (int q = 0; q < 6; ++q) b.motion[q] = velocities[r].motion[q];
         b.spacing = s.spacing, b.nx = s.nx, b.ny = s.ny, b.nz = s.nz;
     }
-    void *dev = nullptr;
-    if (const hipError_t e = hipMallocAsync(&dev, rows.size() * sizeof(SampledBody), st); e != hipSuccess) {
-        (void)hipGetLastError();
-        setLastGlobalError(std::string(fn) + ": device allocation failed (" + hipGetErrorString(e) + ")");
-        return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? MGPS_ERR_NO_DEVICE : MGPS_ERR_ALLOC;
-    }
-    int rc = hipStatus(fn, hipMemcpyAsync(dev, rows.data(), rows.size() * sizeof(SampledBody), hipMemcpyHostToDevice, st));
-    if (rc == MGPS_OK) {
+    const size_t bytes = rows.size() * sizeof(SampledBody);
+    return withStreamBlock(fn, st, bytes, rows.data(), bytes, [&](void *dev) {
         SampledArgs a{};
         a.gx = gx, a.gy = gy, a.planes = planes, a.c0 = c0, a.bodies = bodies, a.table = static_cast<const SampledBody *>(dev);
         for (int q = 0; q < 3; ++q) a.sv[q] = sv[q], a.body[q] = body[q];
-        const dim3 grid(unsigned((gx + kTX - 1) / kTX), unsigned((gy + kTY - 1) / kTY), unsigned((planes + kTZ - 1) / kTZ));
-        sampledVelocityKernel<<<grid, kThreads, 0, st>>>(a);
-        rc = hipStatus(fn, hipGetLastError());
-    }
-    const int freed = hipStatus(fn, hipFreeAsync(dev, st));
-    return rc != MGPS_OK ? rc : freed;
+        sampledVelocityKernel<<<tileGrid(gx, gy, planes), kThreads, 0, st>>>(a);
+        return hipStatus(fn, hipGetLastError());
+    });
 }
 }  // namespace
 
@@ -526,8 +466,8 @@ int mgps_fields_slab_rasterize_bodies(const mgps_fields_slab *w, const mgps_rast
 try {
     const char *fn = "mgps_fields_slab_rasterize_bodies";
     if (int rc = checkDesc(fn, d); rc != MGPS_OK) return rc;
-    if (!fieldsSlabWindow(w, fn)) return MGPS_ERR_INVALID_ARGUMENT;
-    if (w->gx != d->gx || w->gy != d->gy || w->gz != d->gz) return refuse(fn, "the window is not one of the desc's extents (gx, gy, gz are the whole grid's in both)");
+    int below, above;  // (no halo: a cell's values depend on the bodies alone)
+    if (int rc = checkWindowOf(fn, w, d, 0, below, above); rc != MGPS_OK) return rc;
     return runRaster(fn, d, w->c0, w->c1 - w->c0, static_cast<hipStream_t>(stream));
 }
 MGPS_API_CATCH(nullptr)

@@ -1,23 +1,15 @@
 // Redistancing on the device (include/mgps_fields.h, "redistancing"): a fast iterative Eikonal pass that turns
 // liquid_phi back into a signed distance within a band, on a whole grid or a slab window.
 // The state of a cell is the float32 value s T: T >= 0 the distance in cells, s = - where phi <= 0.  One streaming launch fixes the
-// interface cells (initKernel); every round is one launch of block Jacobi over the rasteriser's tiles of kTX x kTY x kTZ cells anchored
+// interface cells (initKernel); every round is one launch of block Jacobi over the tiles of mgps_tile_pass.h, anchored
 // at cell (0, 0, 0) of the whole grid (roundKernel): the tile and a one-cell rim are staged in LDS once, a thread owns a z-column of
 // four cells in registers and reads its x/y neighbours from LDS, the rim is held, and `inner` Jacobi iterations of the first-order
 // Godunov update run before the tile's cells are stored.  Whether a cell is an interface cell is the sign test on the staged box.
 // All arithmetic is fp64 on float32 data and every operation is rounded on its own -- no contraction in this unit -- so that
 // tests/redistance_reference.py, which states the same operations in numpy, has the same bits.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <string>
-#include <vector>
 
-#include "mgps_fields.h"
-#include "mgps_internal.h"
-#include "mgps_slab_call.h"
+#include "mgps_tile_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -25,14 +17,7 @@ using namespace mgps;
 
 namespace {
 
-constexpr int kTX = 64, kTY = 4, kTZ = 4, kThreads = 256;
 constexpr int kSX = kTX + 2, kSY = kTY + 2, kSZ = kTZ + 2, kBox = kSX * kSY * kSZ;  // the tile and a one-cell rim
-static_assert(kTX == 64 && kTY * 64 == kThreads, "one wave per row of a tile plane");
-
-// the planes of a cell grid that the call holds: the window's, and the halo planes below and above it
-struct Held {
-    const float *win, *lo, *hi;
-};
 
 struct RedistanceArgs {
     int gx, gy, gz;    // the whole grid
@@ -42,7 +27,7 @@ struct RedistanceArgs {
     int scale;  // 1: the stores are float(dx state)
     int count;  // 1: the round adds the own cells it changed to counts[1]
     double B, dx;
-    Held in;
+    HeldPlanes in;
     float *out;
     unsigned long long *counts;
 };
@@ -50,10 +35,7 @@ struct RedistanceArgs {
 // the plane z (held) of the input, z in the whole grid's plane index
 __device__ __forceinline__ const float *planeOf(const RedistanceArgs &a, int z)
 {
-    const size_t plane = size_t(a.gx) * size_t(a.gy);
-    if (z < a.c0) return a.in.lo + size_t(z - (a.c0 - a.below)) * plane;
-    if (z < a.c0 + a.planes) return a.in.win + size_t(z - a.c0) * plane;
-    return a.in.hi + size_t(z - (a.c0 + a.planes)) * plane;
+    return heldPlane(a.in, size_t(a.gx) * size_t(a.gy), a.c0, a.c0 + a.planes, a.c0 - a.below, z);
 }
 
 __device__ __forceinline__ float stored(const RedistanceArgs &a, float state)
@@ -61,21 +43,13 @@ __device__ __forceinline__ float stored(const RedistanceArgs &a, float state)
     return a.scale ? float(a.dx * double(state)) : state;
 }
 
-// adds a workgroup's tally to counts[slot]: one LDS atomic per thread that has something, one global atomic per workgroup
-__device__ __forceinline__ void addCount(const RedistanceArgs &a, unsigned int *tally, int slot, unsigned int mine)
-{
-    if (mine) atomicAdd(tally, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && *tally) atomicAdd(a.counts + slot, (unsigned long long)*tally);
-}
-
 // The initial pass: T0 of every own cell from phi's seven-point neighbourhood.  A streaming kernel over tiles of the window's planes
 __global__ __launch_bounds__(kThreads) void initKernel(RedistanceArgs a)
 {
-    __shared__ unsigned int tally;
-    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
-    const int i = int(blockIdx.x) * kTX + lane, j = int(blockIdx.y) * kTY + wave, k0 = int(blockIdx.z) * kTZ;
-    if (t == 0) tally = 0;
+    __shared__ unsigned int tally[1];
+    const TileThread th;
+    const int i = th.i, j = th.j, k0 = th.k0;
+    zeroTally(tally);
     __syncthreads();
     unsigned int interfaces = 0;
     if (i < a.gx && j < a.gy) {
@@ -120,7 +94,8 @@ __global__ __launch_bounds__(kThreads) void initKernel(RedistanceArgs a)
             a.out[size_t(k) * size_t(a.gx) * size_t(a.gy) + row] = stored(a, state);
         }
     }
-    if (a.counts) addCount(a, &tally, 0, interfaces);
+    const unsigned int found[1] = {interfaces};
+    if (a.counts) addTally(tally, found, a.counts);
 }
 
 // G: the first-order Godunov update of a cell from the least T of its two neighbours per axis (+inf outside the whole grid)
@@ -151,13 +126,14 @@ __device__ __forceinline__ int boxAt(int lx, int ly, int lz)
 __global__ __launch_bounds__(kThreads) void roundKernel(RedistanceArgs a)
 {
     __shared__ float box[kBox];
-    __shared__ unsigned int tally;
+    __shared__ unsigned int tally[1];
 
-    const int t = int(threadIdx.x), lane = t & 63, wave = t >> 6;
-    const int ti0 = int(blockIdx.x) * kTX, tj0 = int(blockIdx.y) * kTY, k0 = (a.c0 / kTZ + int(blockIdx.z)) * kTZ;
+    const TileThread th;
+    const int t = th.t, lane = th.lane, wave = th.wave;
+    const int ti0 = th.i0, tj0 = th.j0, k0 = (a.c0 / kTZ + int(blockIdx.z)) * kTZ;
     const int h0 = a.c0 - a.below, h1 = a.c0 + a.planes + a.above;
     const float Bf = float(a.B);
-    if (t == 0) tally = 0;
+    zeroTally(tally);
 
     // the tile's cells and the rim; a plane inside the grid that is not held is the nearest one held (no own cell depends on it),
     // a cell outside the whole grid holds +inf
@@ -176,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void roundKernel(RedistanceArgs a)
     }
     const int any = __syncthreads_or(live);
 
-    const int i = ti0 + lane, j = tj0 + wave;
+    const int i = th.i, j = th.j;
     const bool column = i < a.gx && j < a.gy;
     const size_t row = size_t(j) * size_t(a.gx) + size_t(i), plane = size_t(a.gx) * size_t(a.gy);
     const int lx = lane + 1, ly = wave + 1;
@@ -241,23 +217,9 @@ __global__ __launch_bounds__(kThreads) void roundKernel(RedistanceArgs a)
             a.out[size_t(k) * plane + row] = stored(a, cur[kk]);
         }
     }
-    if (a.count && a.counts) addCount(a, &tally, 1, changed);
+    const unsigned int found[1] = {changed};
+    if (a.count && a.counts) addTally(tally, found, a.counts + 1);
 }
-
-int hipStatus(const char *fn, hipError_t e)
-{
-    if (e == hipSuccess) return MGPS_OK;
-    setLastGlobalError(std::string(fn) + ": " + hipGetErrorString(e));
-    return MGPS_ERR_HIP;
-}
-
-// a byte range of one array of the call
-struct Range {
-    const char *p;
-    size_t bytes;
-    bool written;
-    std::string name;
-};
 
 // What the three entries refuse of a desc, before any device work.  [c0, c0 + planes) with the halo planes held is the box of the
 // arrays; `scratch`: the call ping-pongs through d->scratch; in_name: what phi_in holds for this entry.  Fills the kernels' arguments
@@ -265,10 +227,7 @@ int checkDesc(const char *fn, const mgps_redistance_desc *d, int c0, int planes,
               bool scratch, const char *lo_name, const char *hi_name, RedistanceArgs &a)
 {
     if (!d || d->struct_size != int(sizeof(mgps_redistance_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_redistance_desc)");
-    if (d->gx < 1 || d->gy < 1 || d->gz < 1)
-        return refuse(fn, "non-positive extent (gx, gy, gz = " + std::to_string(d->gx) + ", " + std::to_string(d->gy) + ", " + std::to_string(d->gz) + ")");
-    // (launch-grid dimensions; a window off the tile's four planes meets one tile layer more than it has planes for)
-    if ((d->gy + kTY - 1) / kTY + 1 > 65535 || (d->gz + kTZ - 1) / kTZ + 1 > 65535) return refuse(fn, "more than 262136 cells along y or z");
+    if (int rc = checkTileExtents(fn, d->gx, d->gy, d->gz, true); rc != MGPS_OK) return rc;
     if (!std::isfinite(d->band) || !(float(d->band) > 0.0f) || !std::isfinite(float(d->band)))
         return refuse(fn, "band is not finite and > 0 (as a float32 number of cells)");
     if (!std::isfinite(d->dx) || !(d->dx > 0.0)) return refuse(fn, "dx is not finite and > 0");
@@ -277,35 +236,27 @@ int checkDesc(const char *fn, const mgps_redistance_desc *d, int c0, int planes,
     if (!d->phi_in) return refuse(fn, "phi_in is NULL");
     if (!d->phi_out) return refuse(fn, "phi_out is NULL");
     if (scratch && !d->scratch) return refuse(fn, "scratch is NULL: rounds > 0 ping-pong between phi_out and a scratch grid of its shape");
-    if (below > 0 && !lo) return refuse(fn, std::string(lo_name) + " is NULL: " + std::to_string(below) + " halo planes lie below the window");
-    if (above > 0 && !hi) return refuse(fn, std::string(hi_name) + " is NULL: " + std::to_string(above) + " halo planes lie above the window");
+    if (int rc = checkHaloArrays(fn, lo_name, lo, below, hi_name, hi, above); rc != MGPS_OK) return rc;
 
     const size_t plane = size_t(d->gx) * size_t(d->gy) * sizeof(float);
-    std::vector<Range> ranges;
-    ranges.push_back(Range{reinterpret_cast<const char *>(d->phi_in), plane * size_t(planes), false, "phi_in"});
-    ranges.push_back(Range{reinterpret_cast<const char *>(d->phi_out), plane * size_t(planes), true, "phi_out"});
-    if (scratch) ranges.push_back(Range{reinterpret_cast<const char *>(d->scratch), plane * size_t(planes), true, "scratch"});
-    if (below > 0) ranges.push_back(Range{reinterpret_cast<const char *>(lo), plane * size_t(below), false, lo_name});
-    if (above > 0) ranges.push_back(Range{reinterpret_cast<const char *>(hi), plane * size_t(above), false, hi_name});
-    // an array that is written overlaps no other array of the call
-    for (size_t p = 0; p < ranges.size(); ++p)
-        for (size_t q = p + 1; q < ranges.size(); ++q) {
-            const Range &r = ranges[p], &s = ranges[q];
-            if (!r.written && !s.written) continue;
-            if (r.p < s.p + s.bytes && s.p < r.p + r.bytes) return refuse(fn, r.name + " and " + s.name + " overlap: the pass is out of place");
-        }
+    ArrayRanges arrays;
+    arrays.add("phi_in", d->phi_in, plane * size_t(planes), false);
+    arrays.add("phi_out", d->phi_out, plane * size_t(planes), true);
+    if (scratch) arrays.add("scratch", d->scratch, plane * size_t(planes), true);
+    if (below > 0) arrays.add(lo_name, lo, plane * size_t(below), false);
+    if (above > 0) arrays.add(hi_name, hi, plane * size_t(above), false);
+    if (int rc = arrays.refuseOverlap(fn); rc != MGPS_OK) return rc;
     a = RedistanceArgs{};
     a.gx = d->gx, a.gy = d->gy, a.gz = d->gz, a.c0 = c0, a.planes = planes, a.below = below, a.above = above;
     a.inner = d->inner, a.B = double(float(d->band)), a.dx = d->dx;
-    a.in = Held{d->phi_in, below > 0 ? lo : nullptr, above > 0 ? hi : nullptr};
+    a.in = HeldPlanes{d->phi_in, below > 0 ? lo : nullptr, above > 0 ? hi : nullptr};
     a.out = d->phi_out, a.counts = d->counts_dev;
     return MGPS_OK;
 }
 
 int launchInit(const char *fn, const RedistanceArgs &a, hipStream_t st)
 {
-    const dim3 grid(unsigned((a.gx + kTX - 1) / kTX), unsigned((a.gy + kTY - 1) / kTY), unsigned((a.planes + kTZ - 1) / kTZ));
-    initKernel<<<grid, kThreads, 0, st>>>(a);
+    initKernel<<<tileGrid(a.gx, a.gy, a.planes), kThreads, 0, st>>>(a);
     return hipStatus(fn, hipGetLastError());
 }
 
@@ -313,29 +264,8 @@ int launchInit(const char *fn, const RedistanceArgs &a, hipStream_t st)
 int launchRound(const char *fn, const RedistanceArgs &a, hipStream_t st)
 {
     const int layers = (a.c0 + a.planes + kTZ - 1) / kTZ - a.c0 / kTZ;
-    const dim3 grid(unsigned((a.gx + kTX - 1) / kTX), unsigned((a.gy + kTY - 1) / kTY), unsigned(layers));
-    roundKernel<<<grid, kThreads, 0, st>>>(a);
+    roundKernel<<<tileGrid(a.gx, a.gy, layers * kTZ), kThreads, 0, st>>>(a);
     return hipStatus(fn, hipGetLastError());
-}
-
-// what both window entries refuse of the window; the planes held on either side
-int checkWindow(const char *fn, const mgps_fields_slab *w, const mgps_redistance_desc *d, int halo, int &below, int &above)
-{
-    if (!fieldsSlabWindow(w, fn)) return MGPS_ERR_INVALID_ARGUMENT;
-    if (halo < 0) return refuse(fn, "halo = " + std::to_string(halo) + " is negative");
-    if (d && d->struct_size == int(sizeof(mgps_redistance_desc)) && (w->gx != d->gx || w->gy != d->gy || w->gz != d->gz))
-        return refuse(fn, "the window is not one of the desc's extents (gx, gy, gz are the whole grid's in both)");
-    below = std::min(halo, w->c0), above = std::min(halo, w->gz - w->c1);
-    return MGPS_OK;
-}
-
-// the planes [n0, n1) a pass over the window [c0, c1) reads, against the planes held: fewer is refused
-int checkHalo(const char *fn, const mgps_fields_slab *w, int halo, int below, int above, int n0, int n1, const std::string &why)
-{
-    n0 = std::max(n0, 0), n1 = std::min(n1, w->gz);
-    if (w->c0 - below <= n0 && w->c1 + above >= n1) return MGPS_OK;
-    return refuse(fn, "too few halo planes: halo = " + std::to_string(halo) + " holds the planes " + std::to_string(w->c0 - below) + " .. " +
-                          std::to_string(w->c1 + above - 1) + ", " + why + " reads " + std::to_string(n0) + " .. " + std::to_string(n1 - 1));
 }
 }  // namespace
 
@@ -367,10 +297,12 @@ int mgps_fields_slab_redistance_init(const mgps_fields_slab *w, const mgps_redis
 try {
     const char *fn = "mgps_fields_slab_redistance_init";
     int below = 0, above = 0;
-    if (int rc = checkWindow(fn, w, d, halo, below, above); rc != MGPS_OK) return rc;
+    if (int rc = checkWindowOf(fn, w, d, halo, below, above); rc != MGPS_OK) return rc;
     RedistanceArgs a;
     if (int rc = checkDesc(fn, d, w->c0, w->c1 - w->c0, below, above, phi_lo, phi_hi, false, "phi_lo", "phi_hi", a); rc != MGPS_OK) return rc;
-    if (int rc = checkHalo(fn, w, halo, below, above, w->c0 - 1, w->c1 + 1, "the initial pass"); rc != MGPS_OK) return rc;
+    int n0, n1;
+    planesRead(w->c0, w->c1, false, n0, n1);
+    if (int rc = checkHalo(fn, w->c0, w->c1, w->gz, halo, below, above, n0, n1, "the initial pass"); rc != MGPS_OK) return rc;
     return launchInit(fn, a, static_cast<hipStream_t>(stream));
 }
 MGPS_API_CATCH(nullptr)
@@ -380,12 +312,13 @@ int mgps_fields_slab_redistance_round(const mgps_fields_slab *w, const mgps_redi
 try {
     const char *fn = "mgps_fields_slab_redistance_round";
     int below = 0, above = 0;
-    if (int rc = checkWindow(fn, w, d, halo, below, above); rc != MGPS_OK) return rc;
+    if (int rc = checkWindowOf(fn, w, d, halo, below, above); rc != MGPS_OK) return rc;
     RedistanceArgs a;
     if (int rc = checkDesc(fn, d, w->c0, w->c1 - w->c0, below, above, state_lo, state_hi, false, "state_lo", "state_hi", a); rc != MGPS_OK) return rc;
     // inner = 1 reads the own cells' neighbours only; more iterations read every tile that meets the window, and its rim
-    const int n0 = d->inner == 1 ? w->c0 - 1 : w->c0 / kTZ * kTZ - 1, n1 = d->inner == 1 ? w->c1 + 1 : (w->c1 + kTZ - 1) / kTZ * kTZ + 1;
-    if (int rc = checkHalo(fn, w, halo, below, above, n0, n1, "a round of inner = " + std::to_string(d->inner)); rc != MGPS_OK) return rc;
+    int n0, n1;
+    planesRead(w->c0, w->c1, d->inner > 1, n0, n1);
+    if (int rc = checkHalo(fn, w->c0, w->c1, w->gz, halo, below, above, n0, n1, "a round of inner = " + std::to_string(d->inner)); rc != MGPS_OK) return rc;
     a.scale = a.count = last != 0;
     return launchRound(fn, a, static_cast<hipStream_t>(stream));
 }

@@ -23,6 +23,10 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _current_device():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 def _g(shape):
     gz, gy, gx = shape
     return gx, gy, gz
@@ -961,7 +965,7 @@ class RasterDesc(C.Structure):
 
 def _raster(entry, window, grid_shape, array_shape, shapes, band, min_open, static_solid_phi, static_cut_weights):
     faces = _face3(array_shape)
-    device = static_solid_phi.device if static_solid_phi is not None else torch.device("cuda", torch.cuda.current_device())
+    device = static_solid_phi.device if static_solid_phi is not None else _current_device()
     rows = (BodyShape * (len(shapes) + 1))(BodyShape(), *shapes)  # (row 0 is not read)
     d = RasterDesc()
     d.struct_size = C.sizeof(RasterDesc)
@@ -1024,20 +1028,26 @@ def _mesh(vertices, triangles):
     return v, t
 
 
-def meshSDF(vertices, triangles, n, origin, spacing, band, device=None):
-    """mgps_fields_mesh_sdf: the body-frame signed distance of the closed mesh (`vertices` (V, 3) float64 in (x, y, z), `triangles`
-    (T, 3) vertex indices, outward orientation) at the samples origin + spacing (i, j, k), `n` = (nx, ny, nz) of them: a CUDA float32
-    tensor (nz, ny, nx), negative inside, exact up to `band` and clamped there.  What BodyShape.sdf_grid takes.  Does not synchronise."""
-    v, t = _mesh(vertices, triangles)
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    d = MeshDesc()
-    d.struct_size = C.sizeof(MeshDesc)
+def _mesh_desc(cls, v, t, n, origin, spacing, band):
+    """(desc of class `cls` with the mesh and the sample box filled in, the shape (nz, ny, nx) to allocate the outputs with)"""
+    d = cls()
+    d.struct_size = C.sizeof(cls)
     d.vertices, d.triangles, d.xyz, d.tri = len(v), len(t), v.ctypes.data, t.ctypes.data
     d.nx, d.ny, d.nz = (int(q) for q in n)
     d.origin[:] = [float(q) for q in origin]
     d.spacing, d.band = float(spacing), float(band)
     nx, ny, nz = (min(max(int(q), 1), 1024) for q in n)  # (the library refuses a dimension outside 2 .. 1024 before it writes)
-    sdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=device)
+    return d, (nz, ny, nx)
+
+
+def meshSDF(vertices, triangles, n, origin, spacing, band, device=None):
+    """mgps_fields_mesh_sdf: the body-frame signed distance of the closed mesh (`vertices` (V, 3) float64 in (x, y, z), `triangles`
+    (T, 3) vertex indices, outward orientation) at the samples origin + spacing (i, j, k), `n` = (nx, ny, nz) of them: a CUDA float32
+    tensor (nz, ny, nx), negative inside, exact up to `band` and clamped there.  What BodyShape.sdf_grid takes.  Does not synchronise."""
+    v, t = _mesh(vertices, triangles)
+    device = _current_device() if device is None else torch.device(device)
+    d, shape = _mesh_desc(MeshDesc, v, t, n, origin, spacing, band)
+    sdf = torch.empty(shape, dtype=torch.float32, device=device)
     d.sdf = sdf.data_ptr()
     with torch.cuda.device(device):
         check(lib().mgps_fields_mesh_sdf(C.byref(d), _stream()))
@@ -1087,16 +1097,11 @@ def meshSDFVelocity(vertices, triangles, vertex_velocities, n, origin, spacing, 
     v, t = _mesh(vertices, triangles)
     w = np.ascontiguousarray(vertex_velocities, dtype=np.float64)
     assert w.shape == v.shape, (w.shape, v.shape)
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    d = MeshVelocityDesc()
-    d.struct_size = C.sizeof(MeshVelocityDesc)
-    d.vertices, d.triangles, d.xyz, d.tri, d.velocity = len(v), len(t), v.ctypes.data, t.ctypes.data, w.ctypes.data
-    d.nx, d.ny, d.nz = (int(q) for q in n)
-    d.origin[:] = [float(q) for q in origin]
-    d.spacing, d.band = float(spacing), float(band)
-    nx, ny, nz = (min(max(int(q), 1), 1024) for q in n)  # (the library refuses a dimension outside 2 .. 1024 before it writes)
-    sdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=device)
-    vel = torch.empty((3, nz, ny, nx), dtype=torch.float32, device=device)
+    device = _current_device() if device is None else torch.device(device)
+    d, shape = _mesh_desc(MeshVelocityDesc, v, t, n, origin, spacing, band)
+    d.velocity = w.ctypes.data
+    sdf = torch.empty(shape, dtype=torch.float32, device=device)
+    vel = torch.empty((3,) + shape, dtype=torch.float32, device=device)
     d.sdf = sdf.data_ptr()
     for c in range(3):
         d.vel[c] = vel[c].data_ptr()
@@ -1125,6 +1130,20 @@ def _sampled_rows(shapes, frame_motions):
     return rows, vrows
 
 
+def _sampled_velocity(d, shape, solid_velocity, body, shapes, frame_motions):
+    """both forms on arrays of `shape`: the whole grid's (d None) or the window d's"""
+    faces = _face3(shape)
+    sv = [_chk(solid_velocity[a], faces[a], torch.float32) for a in range(3)]
+    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
+    rows, vrows = _sampled_rows(shapes, frame_motions)
+    with torch.cuda.device(sv[0].device):
+        if d is None:
+            check(lib().mgps_fields_sampled_velocity(_arr3(sv), _arr3(ids), len(shapes), rows, vrows, *_g(shape), _stream()))
+        else:
+            check(lib().mgps_fields_slab_sampled_velocity(C.byref(d), _arr3(sv), _arr3(ids), len(shapes), rows, vrows, _stream()))
+    return solid_velocity
+
+
 def sampledVelocity(solid_velocity, body, shapes, frame_motions=None):
     """mgps_fields_sampled_velocity (in place on the three solid-velocity face grids): on the faces whose body id r is in
     1 .. len(shapes) and whose shape (shapes[r - 1], made by BodyShape.mesh with vertex_velocities) carries `.velocity`, the body's
@@ -1133,25 +1152,13 @@ def sampledVelocity(solid_velocity, body, shapes, frame_motions=None):
     value: call rigidVelocity first and this after it.  Does not synchronise."""
     shape = list(solid_velocity[2].shape)
     shape[0] -= 1
-    faces = _face3(tuple(shape))
-    sv = [_chk(solid_velocity[a], faces[a], torch.float32) for a in range(3)]
-    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
-    rows, vrows = _sampled_rows(shapes, frame_motions)
-    with torch.cuda.device(sv[0].device):
-        check(lib().mgps_fields_sampled_velocity(_arr3(sv), _arr3(ids), len(shapes), rows, vrows, *_g(tuple(shape)), _stream()))
-    return solid_velocity
+    return _sampled_velocity(None, tuple(shape), solid_velocity, body, shapes, frame_motions)
 
 
 def sampledVelocitySlab(d, solid_velocity, body, shapes, frame_motions=None):
     """mgps_fields_slab_sampled_velocity: sampledVelocity on the window `d` (in place on the window's three face grids; positions use
     the whole grid's plane index): the bits of the whole-grid pass on the rank's planes.  No halo, no communication."""
-    faces = _face3(d.base_shape)
-    sv = [_chk(solid_velocity[a], faces[a], torch.float32) for a in range(3)]
-    ids = [_chk(body[a], faces[a], torch.int32) for a in range(3)]
-    rows, vrows = _sampled_rows(shapes, frame_motions)
-    with torch.cuda.device(sv[0].device):
-        check(lib().mgps_fields_slab_sampled_velocity(C.byref(d), _arr3(sv), _arr3(ids), len(shapes), rows, vrows, _stream()))
-    return solid_velocity
+    return _sampled_velocity(d, d.base_shape, solid_velocity, body, shapes, frame_motions)
 
 
 # ---- advection: semi-Lagrangian and MacCormack passes (include/mgps_fields.h, DESIGN.md section 21) ----------------------------------
@@ -1167,6 +1174,28 @@ class AdvectDesc(C.Structure):
         ("scalars", C.c_int), ("scalar_in", C.c_void_p * 4), ("scalar_out", C.c_void_p * 4), ("scalar_scratch", C.c_void_p * 4),
         ("counts_dev", C.c_void_p),
     ]
+
+
+def _counts_ptr(counts):
+    """the counts_dev of a desc: an int64 CUDA tensor of 2 that the pass adds to, or None"""
+    assert counts is None or (counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous())
+    return None if counts is None else counts.data_ptr()
+
+
+def _held_planes(d, halo, sides, planes, array=0):
+    """Halo planes -> the two pointers (below, above) of a window entry.  sides = (below, above) or None; planes: each grid's (ny, nx).
+    array = 0: one grid, a side is a (count, ny, nx) tensor -> its pointer; array = n: a side is a list of one such tensor per grid ->
+    a pointer array of n.  NULL where no plane is held (count = min(halo, the planes on that side) is 0) or none is given"""
+    out = []
+    for count, ts in zip((min(int(halo), d.c0), min(int(halo), d.gz - d.c1)), sides if sides else (None, None)):
+        if count == 0 or ts is None:
+            out.append(None)
+            continue
+        ts = ts if array else [ts]
+        assert len(ts) == len(planes), "one halo tensor per grid"
+        ptrs = [_chk(t, (count,) + tuple(p), torch.float32).data_ptr() for t, p in zip(ts, planes)]
+        out.append((C.c_void_p * array)(*ptrs) if array else C.c_void_p(ptrs[0]))
+    return out
 
 
 def _advect_desc(grid_shape, array_shape, velocity, dt, scalars, scheme, trace_order, out, scratch, counts):
@@ -1197,9 +1226,7 @@ def _advect_desc(grid_shape, array_shape, velocity, dt, scalars, scheme, trace_o
         d.scalar_in[q], d.scalar_out[q] = s[q].data_ptr(), _chk(sout[q], array_shape, torch.float32).data_ptr()
         if sscr is not None:
             d.scalar_scratch[q] = _chk(sscr[q], array_shape, torch.float32).data_ptr()
-    if counts is not None:
-        assert counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
-        d.counts_dev = counts.data_ptr()
+    d.counts_dev = _counts_ptr(counts)
     return d, vout, sout, (v, s, vscr, sscr)
 
 
@@ -1219,14 +1246,6 @@ def advect(velocity, dt, scalars=(), scheme="maccormack", trace_order=2, out=Non
     return vout, sout
 
 
-def _halo_planes(ts, shapes, dtype, n):
-    """n grids' halo planes of one side -> a pointer array of 4 (None: NULL)"""
-    if ts is None:
-        return None
-    assert len(ts) == n, "one halo tensor per grid"
-    return (C.c_void_p * 4)(*[_chk(t, s, dtype).data_ptr() for t, s in zip(ts, shapes)])
-
-
 def advectSlab(d, velocity, dt, halo, velocity_halo, scalars=(), scalar_halo=(), scheme="semi_lagrangian", trace_order=2, out=None,
                counts=None):
     """mgps_fields_slab_advect: advect on the window `d` (fields.slab_window), without communication; the arrays are the window's
@@ -1234,21 +1253,12 @@ def advectSlab(d, velocity, dt, halo, velocity_halo, scalars=(), scalar_halo=(),
     and the min(halo, gz - c1) planes above it as (planes, ny, nx) tensors (of the z-face grid: the face planes below c0 and above
     c1); scalar_halo likewise, one tensor per scalar grid.  None where no plane is held.  counts[1] is raised by the targets that
     asked for a plane that is not held.  The window form is semi-Lagrangian only: scheme = "maccormack" is refused by the library."""
-    shape, n = d.base_shape, len(scalars)
-    below, above = min(int(halo), d.c0), min(int(halo), d.gz - d.c1)
-    plane = [(d.gy, d.gx + 1), (d.gy + 1, d.gx), (d.gy, d.gx)]
-    vlo, vhi = velocity_halo if velocity_halo else (None, None)
-    slo, shi = scalar_halo if scalar_halo else (None, None)
-    ptr = []
-    for side, count, (vh, sh) in ((0, below, (vlo, slo)), (1, above, (vhi, shi))):
-        if count == 0:
-            vh, sh = None, None
-        ptr.append(_halo_planes(vh, [(count,) + p for p in plane], torch.float32, 3))
-        ptr.append(_halo_planes(sh, [(count, d.gy, d.gx)] * n, torch.float32, n))
-    desc, vout, sout, keep = _advect_desc((d.gz, d.gy, d.gx), shape, velocity, dt, scalars, "semi_lagrangian", trace_order, out, None, counts)
+    vlo, vhi = _held_planes(d, halo, velocity_halo, [(d.gy, d.gx + 1), (d.gy + 1, d.gx), (d.gy, d.gx)], 4)
+    slo, shi = _held_planes(d, halo, scalar_halo, [(d.gy, d.gx)] * len(scalars), 4)
+    desc, vout, sout, keep = _advect_desc((d.gz, d.gy, d.gx), d.base_shape, velocity, dt, scalars, "semi_lagrangian", trace_order, out, None, counts)
     desc.scheme = SCHEMES[scheme]
     with torch.cuda.device(keep[0][0].device):
-        check(lib().mgps_fields_slab_advect(C.byref(d), C.byref(desc), int(halo), ptr[0], ptr[2], ptr[1], ptr[3], _stream()))
+        check(lib().mgps_fields_slab_advect(C.byref(d), C.byref(desc), int(halo), vlo, vhi, slo, shi, _stream()))
     return vout, sout
 
 
@@ -1274,19 +1284,8 @@ def _redistance_desc(grid_shape, array_shape, phi_in, band, dx, rounds, inner, o
     d.phi_in, d.phi_out = phi_in.data_ptr(), out.data_ptr()
     if scratch is not None:
         d.scratch = _chk(scratch, array_shape, torch.float32).data_ptr()
-    if counts is not None:
-        assert counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == 2 and counts.is_contiguous()
-        d.counts_dev = counts.data_ptr()
+    d.counts_dev = _counts_ptr(counts)
     return d, out
-
-
-def _halo_pair(d, halo, planes):
-    """(below, above) plane tensors of a cell grid -> two pointers; None where no plane is held"""
-    lo, hi = planes if planes else (None, None)
-    below, above = min(int(halo), d.c0), min(int(halo), d.gz - d.c1)
-    lo = _chk(lo, (below, d.gy, d.gx), torch.float32) if below > 0 and lo is not None else None
-    hi = _chk(hi, (above, d.gy, d.gx), torch.float32) if above > 0 and hi is not None else None
-    return _p(lo), _p(hi)
 
 
 def redistanceInitSlab(d, liquid_phi, band, halo, phi_halo=None, out=None, counts=None):
@@ -1295,7 +1294,7 @@ def redistanceInitSlab(d, liquid_phi, band, halo, phi_halo=None, out=None, count
     min(halo, gz - c1) planes above it as (planes, ny, nx) tensors; one plane either way is needed.  counts[0] is raised by the
     window's interface cells.  Returns the state.  Does not synchronise."""
     desc, out = _redistance_desc((d.gz, d.gy, d.gx), d.base_shape, liquid_phi, band, 1.0, 0, 1, out, None, counts)
-    lo, hi = _halo_pair(d, halo, phi_halo)
+    lo, hi = _held_planes(d, halo, phi_halo, [(d.gy, d.gx)])
     with torch.cuda.device(liquid_phi.device):
         check(lib().mgps_fields_slab_redistance_init(C.byref(d), C.byref(desc), int(halo), lo, hi, _stream()))
     return out
@@ -1307,7 +1306,7 @@ def redistanceRoundSlab(d, state, band, halo, state_halo=None, inner=4, last=Fal
     4 floor(c0 / 4) - 1 .. 4 ceil(c1 / 4) (halo = 4 always suffices), inner = 1 one plane either way; fewer is refused.  With `last`
     the stores are multiplied by dx and counts[1] is raised by the window's cells the round changed.  Does not synchronise."""
     desc, out = _redistance_desc((d.gz, d.gy, d.gx), d.base_shape, state, band, dx, 0, inner, out, None, counts)
-    lo, hi = _halo_pair(d, halo, state_halo)
+    lo, hi = _held_planes(d, halo, state_halo, [(d.gy, d.gx)])
     with torch.cuda.device(state.device):
         check(lib().mgps_fields_slab_redistance_round(C.byref(d), C.byref(desc), int(halo), lo, hi, int(bool(last)), _stream()))
     return out

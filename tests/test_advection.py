@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import advection_reference as AR
+from refusals import refused as _refused
 
 DT = 0.7
 GRID = (19, 22, 37)  # section 18's grid: off every multiple of the 64 x 4 x 4 tile
@@ -167,13 +168,6 @@ def test_the_step_scene_engages_the_limiter_and_the_inflow_scene_the_clamp():
 
 
 # ---- CPU: refusals and the mirror ------------------------------------------------------------------------------------------------------
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
-
-
 def _desc(shape=(4, 4, 4), scalars=1, scheme=1, **kw):
     """a good desc on made-up addresses, 1 MiB apart (never dereferenced: every call below is refused on the host)"""
     from geometricmultigridpressuresolver_amd import fields as F

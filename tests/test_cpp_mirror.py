@@ -86,6 +86,26 @@ def test_slab_call_scaffold_under_sanitizers():
     assert "ERROR" not in res.stdout and "runtime error" not in res.stdout and "FAILED" not in res.stdout, res.stdout[-4000:]
 
 
+def test_tile_pass_checks_under_sanitizers():
+    """The host part of csrc/mgps_tile_pass.h (what the tiled field passes refuse before any device work) compiled with
+    g++ -fsanitize=address,undefined (tests/cpp/tile_pass_check.cpp): the overlap rule on every pair of read and written arrays, the
+    halo rule at the grid's ends, the planes a redistance pass reads against the planes held, as tests/redistance_reference.py
+    states them, and the launch-grid limit with its number."""
+    src = os.path.join(ROOT, "tests", "cpp", "tile_pass_check.cpp")
+    out = os.path.join(ROOT, "tests", "cpp", "build", "tile_pass_check")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    subprocess.check_call([
+        "g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+        "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, src, os.path.join(CSRC, "mgps_host.cpp"), "-o", out, "-lpthread",
+    ])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
+    env.pop("LD_PRELOAD", None)
+    res = subprocess.run([out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120, env=env)
+    assert res.returncode == 0, res.stdout[-4000:]
+    assert res.stdout.count(" ok: 1") == 4 and "tile pass check ok" in res.stdout, res.stdout[-4000:]
+    assert "ERROR" not in res.stdout and "runtime error" not in res.stdout and "FAILED" not in res.stdout, res.stdout[-4000:]
+
+
 def test_flatten_roundtrip_and_cmake_configures_without_houdini(tmp_path):
     """The HDK-free half of the Houdini shim (geometricmultigridpressuresolver_amd/host/): flattenGrid / unflattenGrid
     round-trip on a 16^3-tiled stand-in for UT_VoxelArray (tests/cpp/flatten_roundtrip.cpp), and the top-level

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import extrapolation_reference as R
+from refusals import refused as _refused
 
 SHAPE = (24, 20, 28)  # (gz, gy, gx)
 L = 6
@@ -63,13 +64,6 @@ def test_restatement_float32_against_float64():
 
 
 # ---- CPU: the C ABI refuses bad arguments on the host, before any HIP call -------------------------------------------------------------
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
-
-
 def test_argument_refusals_need_no_device():
     from geometricmultigridpressuresolver_amd._lib import lib
 

@@ -26,6 +26,7 @@ import pytest
 
 import mesh_reference as MR
 import raster_reference as RR
+from refusals import refused as _refused
 
 SPACING, BAND = 0.37, 2.5
 GRIDS = ((19, 17, 13), (70, 9, 6))  # (nx, ny, nz): the second has a row longer than one wave
@@ -182,13 +183,6 @@ def test_icosphere_inertia_converges_to_two_fifths_m_r2_from_below():
 
 
 # ---- CPU: the C ABI refuses bad arguments on the host --------------------------------------------------------------------------------
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
-
-
 def _desc(mesh=None, **kw):
     from geometricmultigridpressuresolver_amd import fields as F
 

@@ -22,6 +22,7 @@ import mesh_reference as MR
 import mesh_velocity_reference as MV
 import raster_reference as RR
 import test_mesh_bodies as TM
+from refusals import refused as _refused
 
 SPACING, BAND, GRIDS = TM.SPACING, TM.BAND, TM.GRIDS
 NAMES = ["tetrahedron", "box", "icosphere", "l_prism", "shell"]
@@ -78,13 +79,6 @@ def test_scenes_are_in_generic_position(name, n):
     print(f"{name} {n}: {details['ambiguous']} ambiguous samples, up to {details['fan']} candidates at one point")
     assert details["ambiguous"] == 0
     assert 1 <= details["fan"] <= 6 and (d < BAND).sum() > 300
-
-
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
 
 
 def _mesh_desc(mesh=None, velocity=True, **kw):

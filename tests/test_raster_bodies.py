@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import raster_reference as RR
+from refusals import refused as _refused
 
 GRID = (19, 22, 37)  # (gz, gy, gx): off every multiple of the 64 x 4 x 4 tile
 TILE = (4, 4, 64)
@@ -154,13 +155,6 @@ def test_min_open_snaps_and_ties_go_to_the_lowest_id():
 
 
 # ---- CPU: the C ABI refuses bad arguments on the host ----------------------------------------------------------------------------------
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
-
-
 def _desc(shapes=None, **kw):
     from geometricmultigridpressuresolver_amd import fields as F
 

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import redistance_reference as RR
+from refusals import refused as _refused
 
 GRID = (19, 22, 37)  # section 21's grids: off every multiple of the 64 x 4 x 4 tile, rows across tile edges, a sheet one cell thick
 SCENES = {"grid": (GRID, 21), "row64": ((5, 6, 64), 22), "row65": ((5, 6, 65), 23), "row131": ((5, 6, 131), 24), "sheet": ((1, 7, 70), 25)}
@@ -175,13 +176,6 @@ def test_restated_windows_equal_the_whole_grid(size):
 
 
 # ---- CPU: refusals and the mirror ------------------------------------------------------------------------------------------------------
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
-
-
 def _desc(shape=(4, 4, 4), **kw):
     """a good desc on made-up addresses, 1 MiB apart (never dereferenced: every call below is refused on the host)"""
     from geometricmultigridpressuresolver_amd import fields as F

@@ -28,6 +28,7 @@ import pytest
 import rigid_coupling_reference as RC
 import solid_forces_reference as R
 from conftest import rel_l2
+from refusals import refused as _refused
 
 SMALL, LARGE = (24, 16, 40), (45, 113, 131)
 POOL = (28, 32, 40)  # the voxel pool: room for a 24 x 20 x 12 box under the free surface
@@ -246,13 +247,6 @@ def test_coupling_norm_is_small_against_the_operator(name):
 
 
 # ---- CPU: the C ABI refuses bad arguments on the host ----------------------------------------------------------------------------------
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
-
-
 def _desc(**kw):
     from geometricmultigridpressuresolver_amd import fields as F
 

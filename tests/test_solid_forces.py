@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import solid_forces_reference as R
+from refusals import refused as _refused
 
 # (gz, gy, gx).  The second: a row longer than one 256-thread block, face rows of 261.  The third, odd in every extent, has 666 135
 # cells, 2.5 times the 262 144 threads of the pass's fixed launch: threads take a second and a third trip through the walk, and the
@@ -126,13 +127,6 @@ def test_force_total_does_not_depend_on_the_ids():
 
 
 # ---- CPU: the C ABI refuses bad arguments on the host, before any device work -------------------------------------------------------
-def _refused(status, *words):
-    from geometricmultigridpressuresolver_amd._lib import lib
-
-    msg = lib().mgps_last_error(None).decode()
-    assert status == 1 and all(w in msg for w in words), (status, msg)
-
-
 def test_argument_refusals_need_no_device():
     from geometricmultigridpressuresolver_amd import fields as F
     from geometricmultigridpressuresolver_amd._lib import lib
