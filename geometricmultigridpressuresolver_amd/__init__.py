@@ -32,3 +32,6 @@ def trim_device_cache():
     """Return the device blocks released solvers left for the next one (mgps_trim_device_cache)."""
     lib().mgps_trim_device_cache.restype = None
     lib().mgps_trim_device_cache()
+from .fields import (  # noqa: E402,F401
+    ParticlesBinDesc, ParticlesToGridDesc, ParticlesUpdateDesc, binParticles, particlesToGrid, seedParticles, updateParticles,
+)

@@ -115,6 +115,10 @@ def lib():
         L.mgps_fields_slab_redistance_init.restype = C.c_int
         L.mgps_fields_slab_redistance_round.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.mgps_fields_slab_redistance_round.restype = C.c_int
+        # FLIP particles (include/mgps_fields.h): desc by reference, stream
+        for entry in (L.mgps_particles_bin, L.mgps_particles_to_grid, L.mgps_particles_update):
+            entry.argtypes = [C.c_void_p, C.c_void_p]
+            entry.restype = C.c_int
         _lib = L
     return _lib
 

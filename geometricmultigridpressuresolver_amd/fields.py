@@ -1349,3 +1349,160 @@ def redistance(liquid_phi, band, dx=1.0, rounds=None, inner=4, out=None, scratch
     if counts is not None:
         counts += tally
     return out
+
+
+# ---- FLIP particles: bin, particles -> grid, grid -> particles and move (include/mgps_fields.h) -----------------
+class ParticlesBinDesc(C.Structure):
+    """mgps_particles_bin_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("n", C.c_int), ("position_in", C.c_void_p * 3),
+        ("velocity_in", C.c_void_p * 3), ("position_out", C.c_void_p * 3), ("velocity_out", C.c_void_p * 3), ("order", C.c_void_p),
+        ("cell_start", C.c_void_p), ("counts_dev", C.c_void_p),
+    ]
+
+
+class ParticlesToGridDesc(C.Structure):
+    """mgps_particles_to_grid_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("n", C.c_int), ("form", C.c_int), ("radius", C.c_double),
+        ("dx", C.c_double), ("position", C.c_void_p * 3), ("velocity", C.c_void_p * 3), ("cell_start", C.c_void_p), ("velocity_out", C.c_void_p * 3),
+        ("weight_out", C.c_void_p * 3), ("known_out", C.c_void_p * 3), ("liquid_phi_out", C.c_void_p), ("counts_dev", C.c_void_p),
+    ]
+
+
+class ParticlesUpdateDesc(C.Structure):
+    """mgps_particles_update_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("n", C.c_int), ("trace_order", C.c_int), ("dt", C.c_double),
+        ("flip", C.c_double), ("position_in", C.c_void_p * 3), ("velocity_in", C.c_void_p * 3), ("position_out", C.c_void_p * 3),
+        ("velocity_out", C.c_void_p * 3), ("grid_new", C.c_void_p * 3), ("grid_old", C.c_void_p * 3), ("counts_dev", C.c_void_p),
+    ]
+
+
+def _particles(arrays, n=None):
+    """three float32 CUDA arrays of n entries each"""
+    assert len(arrays) == 3
+    n = int(arrays[0].numel()) if n is None else n
+    return [_chk(t, (n,), torch.float32) for t in arrays], n
+
+
+def binParticles(position, velocity, shape, out=None):
+    """mgps_particles_bin: the particles (three float32 CUDA arrays of positions in cells, three of velocities or None) in cell order
+    on the grid `shape` = (gz, gy, gx), out of place.  Returns (position, velocity or None, order, cell_start, counts): the gathered
+    arrays, order[s] = the input index of slot s (int32), cell_start (int32, cells + 2: the first slot of every cell, of the outside bin,
+    and n) and counts (int64 of 2: [0] outside particles, [1] occupied cells).  out = (position[3], velocity[3] or None, order,
+    cell_start) to write into given arrays.  Does not synchronise."""
+    pos, n = _particles(position)
+    vel = _particles(velocity, n)[0] if velocity is not None else None
+    dev = pos[0].device
+    d = ParticlesBinDesc()
+    d.struct_size = C.sizeof(ParticlesBinDesc)
+    d.gz, d.gy, d.gx = shape
+    d.n = n
+    cells = int(shape[0]) * int(shape[1]) * int(shape[2])
+    if out is None:
+        out = ([torch.empty_like(t) for t in pos], [torch.empty_like(t) for t in vel] if vel is not None else None,
+               torch.empty(n, dtype=torch.int32, device=dev), torch.empty(cells + 2, dtype=torch.int32, device=dev))
+    pout, vout, order, cell_start = out
+    pout = _particles(pout, n)[0]
+    vout = _particles(vout, n)[0] if vel is not None else None
+    _chk(order, (n,), torch.int32), _chk(cell_start, (cells + 2,), torch.int32)
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    for a in range(3):
+        d.position_in[a], d.position_out[a] = pos[a].data_ptr(), pout[a].data_ptr()
+        if vel is not None:
+            d.velocity_in[a], d.velocity_out[a] = vel[a].data_ptr(), vout[a].data_ptr()
+    d.order, d.cell_start, d.counts_dev = order.data_ptr(), cell_start.data_ptr(), counts.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib().mgps_particles_bin(C.byref(d), _stream()))
+    return pout, vout, order, cell_start, counts
+
+
+TO_GRID_FORMS = {"default": 0, "gather": 1, "staged": 2}
+
+
+def particlesToGrid(position, velocity, cell_start, shape, radius, dx=1.0, want_phi=True, out=None, form="default"):
+    """mgps_particles_to_grid: BINNED particles (binParticles' position, velocity and cell_start) -> the face grids of the velocity
+    (the weighted mean of the particles within one cell of a face, 0 where there is none), of the weights and of the known faces
+    (uint8: the `valid_faces` of extrapolateVelocity), and liquid_phi = dx (min(distance to the nearest particle, 1.5) - radius), a
+    union of spheres of `radius` cells (redistance makes it a distance).  out = (velocity[3], weight[3] or None, known[3], liquid_phi
+    or None) to write into given grids.  Returns (velocity[3], weight[3], known[3], liquid_phi or None, counts): counts is int64 of
+    2, [0] known faces, [1] cells with phi <= 0.  form: "gather" or "staged" picks the kernel ("default": the library's choice); the
+    bits are the same.  Does not synchronise."""
+    shape = tuple(int(s) for s in shape)
+    pos, n = _particles(position)
+    vel, _ = _particles(velocity, n)
+    dev = cell_start.device
+    _chk(cell_start, (shape[0] * shape[1] * shape[2] + 2,), torch.int32)
+    faces = _face3(shape)
+    if out is None:
+        out = ([torch.empty(f, dtype=torch.float32, device=dev) for f in faces], [torch.empty(f, dtype=torch.float32, device=dev) for f in faces],
+               [torch.empty(f, dtype=torch.uint8, device=dev) for f in faces], torch.empty(shape, dtype=torch.float32, device=dev) if want_phi else None)
+    vout, wout, known, phi = out
+    d = ParticlesToGridDesc()
+    d.struct_size = C.sizeof(ParticlesToGridDesc)
+    d.gz, d.gy, d.gx = shape
+    d.n, d.form, d.radius, d.dx = n, TO_GRID_FORMS[form], float(radius), float(dx)
+    for a in range(3):
+        d.position[a], d.velocity[a] = pos[a].data_ptr(), vel[a].data_ptr()
+        d.velocity_out[a] = _chk(vout[a], faces[a], torch.float32).data_ptr()
+        if wout is not None:
+            d.weight_out[a] = _chk(wout[a], faces[a], torch.float32).data_ptr()
+        d.known_out[a] = _chk(known[a], faces[a], torch.uint8).data_ptr()
+    d.cell_start = cell_start.data_ptr()
+    if phi is not None:
+        d.liquid_phi_out = _chk(phi, shape, torch.float32).data_ptr()
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    d.counts_dev = counts.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib().mgps_particles_to_grid(C.byref(d), _stream()))
+    return vout, wout, known, phi, counts
+
+
+def updateParticles(position, velocity, grid_new, dt, grid_old=None, flip=0.95, trace_order=2, out=None, counts=None):
+    """mgps_particles_update: grid -> particles, then move.  Every particle inside the box takes
+    (1 - flip) U_new(x) + flip (v + U_new(x) - U_old(x)) as its velocity and moves along grid_new over `dt` (time step over cell size;
+    trace_order 2 is the midpoint rule), clamped into the box; particles outside are copied through.  grid_new: the projected,
+    extrapolated face grids; grid_old: the particlesToGrid result before forces and projection (None only with flip = 0).
+    out = (position_out[3], velocity_out[3]): each array the input itself (in place) or one that overlaps nothing; None: new arrays.
+    counts: an int64 CUDA tensor of 2 that the pass adds to ([0] particles a clamp moved, [1] outside particles), or None.
+    Returns (position_out, velocity_out).  Does not synchronise."""
+    pos, n = _particles(position)
+    vel, _ = _particles(velocity, n)
+    shape = list(grid_new[0].shape)
+    shape[2] -= 1
+    faces = _face3(tuple(shape))
+    pout, vout = ([torch.empty_like(t) for t in pos], [torch.empty_like(t) for t in vel]) if out is None else out
+    d = ParticlesUpdateDesc()
+    d.struct_size = C.sizeof(ParticlesUpdateDesc)
+    d.gz, d.gy, d.gx = shape
+    d.n, d.trace_order, d.dt, d.flip = n, int(trace_order), float(dt), float(flip)
+    for a in range(3):
+        d.position_in[a], d.velocity_in[a] = pos[a].data_ptr(), vel[a].data_ptr()
+        d.position_out[a], d.velocity_out[a] = _particles(pout, n)[0][a].data_ptr(), _particles(vout, n)[0][a].data_ptr()
+        d.grid_new[a] = _chk(grid_new[a], faces[a], torch.float32).data_ptr()
+        if grid_old is not None:
+            d.grid_old[a] = _chk(grid_old[a], faces[a], torch.float32).data_ptr()
+    d.counts_dev = _counts_ptr(counts)
+    with torch.cuda.device(pos[0].device):
+        check(lib().mgps_particles_update(C.byref(d), _stream()))
+    return pout, vout
+
+
+def seedParticles(liquid_phi, per_cell=8, seed=0, jitter=1.0):
+    """A helper for tests, examples and the benchmark, in plain torch (not an entry of the C ABI): per_cell = m^3 particles in every
+    cell with liquid_phi < 0, on a jittered m x m x m lattice (2 x 2 x 2 by default) -- sub-cell q of a cell holds one particle at
+    its centre plus jitter * uniform(-1/2, 1/2) of its size per axis.  Returns three float32 arrays of positions in cells, on
+    liquid_phi's device, in cell order; the same seed gives the same particles."""
+    m = round(per_cell ** (1.0 / 3.0))
+    assert m >= 1 and m ** 3 == per_cell, "per_cell is a cube: 1, 8, 27, ..."
+    cells = torch.nonzero(liquid_phi.detach().cpu() < 0)  # (cells, 3) as (k, j, i)
+    sub = torch.stack(torch.meshgrid(*([torch.arange(m)] * 3), indexing="ij"), dim=-1).reshape(-1, 3)
+    gen = torch.Generator().manual_seed(int(seed))
+    u = torch.rand((cells.shape[0], per_cell, 3), generator=gen, dtype=torch.float64) - 0.5
+    p = cells[:, None, :].double() + (sub[None, :, :].double() + 0.5 + float(jitter) * u) / m
+    p = p.reshape(-1, 3).float()
+    return [p[:, 2 - a].contiguous().to(liquid_phi.device) for a in range(3)]

@@ -845,6 +845,123 @@ int mgps_fields_slab_redistance_init(const mgps_fields_slab *w, const mgps_redis
 int mgps_fields_slab_redistance_round(const mgps_fields_slab *w, const mgps_redistance_desc *d, int halo, const float *state_lo,
                                       const float *state_hi, int last, void *stream);
 
+/* ---- FLIP particles: bin, particles -> grid, grid -> particles and move ------------------------------------------
+ * A FLIP liquid's mass is its particles, so it does not lose volume as an advected level set does.  With these three calls a
+ * FLIP/PIC sub-step is made of this header's calls only: bin, particles -> grid, extrapolate, (add forces), project, extrapolate,
+ * grid -> particles and move.  No counterpart in the reference, where Houdini owns the particles; the definition here is the
+ * contract, and tests/particles_reference.py restates it in numpy operation by operation.
+ *   Conventions (those of advection, above).  Lengths are in cells; the box is B = [0, gx] x [0, gy] x [0, gz]; cell (i, j, k) has
+ *   its centre at (i + 1/2, j + 1/2, k + 1/2), the x-face (i, j, k) lies at (i, j + 1/2, k + 1/2), the y- and z-faces alike; dt is
+ *   the time step over the cell size.  A particle set is structure-of-arrays on the device: three float32 position arrays and three
+ *   float32 velocity arrays of n entries each, 0 <= n < 2^31.  A particle is INSIDE if 0 <= x_c <= g_c for all three components
+ *   (false for NaN); its cell is i_c = min(int(floor(x_c)), g_c - 1), exactly -- no arithmetic precedes the floor.  Every other
+ *   particle is OUTSIDE: it takes part in nothing and is carried through unchanged.  gx gy gz + 1 must be < 2^31.
+ *
+ * 1. mgps_particles_bin: particles in cell order, out of place.
+ *   order (int32[n]): the input index of sorted slot s.  cell_start (int32[cells + 2], cells = gx gy gz): entry c is the first slot of
+ *   cell c in the linear order (k gy + j) gx + i, entry `cells` the first slot of the outside bin, entry cells + 1 is n.  The
+ *   position arrays, and the velocity arrays unless velocity_out is all NULL (velocity_in is then not read), gathered into that
+ *   order.  Within a cell slots ascend by input index (a stable sort): the result is a function of the inputs alone.
+ *   counts_dev (device, unsigned long long[2], may be NULL) is ADDED to: [0] outside particles, [1] occupied cells.
+ *   A key kernel, rocprim::radix_sort_pairs over exactly the bits cells + 1 needs, a lower-bound kernel and one gather kernel, in
+ *   stream order with temporary storage from the stream's pool: no host synchronisation. */
+typedef struct mgps_particles_bin_desc {
+    int struct_size;               /* sizeof(mgps_particles_bin_desc) */
+    int gx, gy, gz;                /* the WHOLE simulation grid */
+    int n;                         /* particles, >= 0 */
+    const float *position_in[3];   /* device, n entries each; not read (may be NULL) when n == 0 */
+    const float *velocity_in[3];   /* not read when velocity_out is all NULL */
+    float *position_out[3];
+    float *velocity_out[3];        /* all three, or all NULL */
+    int32_t *order;                /* n entries */
+    int32_t *cell_start;           /* cells + 2 entries */
+    unsigned long long *counts_dev;
+} mgps_particles_bin_desc;
+/* Does not synchronise the stream.  Refuses with a message, before any device work: NULL desc or a struct_size mismatch, an
+ * extent < 1, gx gy gz + 1 >= 2^31, n < 0, a NULL array that is in use, velocity_out partly set, overlapping buffers (every output
+ * overlaps no other array of the call). */
+int mgps_particles_bin(const mgps_particles_bin_desc *d, void *stream);
+
+/* 2. mgps_particles_to_grid: velocity, weights, known faces and liquid_phi from BINNED particles (position, velocity and cell_start
+ * as mgps_particles_bin left them).
+ *   All arithmetic is fp64 on float32 data and EVERY operation is rounded on its own (no contraction into fused multiply-adds); a
+ *   value is rounded to float32 once, where it is stored.
+ *   Hat function h(d) = max(0, 1 - |d|).  The weight of particle p at a node x: w = (h(x_p,x - x_x) h(x_p,y - x_y)) h(x_p,z - x_z).
+ *   Face of axis a: num = sum w v_p,a and den = sum w, each step `num = num + w * v` and `den = den + w`, over the particles of the
+ *   cells that can reach the face: for the x-face (i, j, k) the cells i - 1 .. i along x and j - 1 .. j + 1, k - 1 .. k + 1 along
+ *   the other axes, the y- and z-faces alike; cells outside the grid hold nothing.  The order is ascending k, then j, then i, then
+ *   slot; particles of weight 0 are included.  velocity_out = float(num / den) where den > 0, else 0; weight_out = float(den) (all
+ *   three, or all NULL); known_out (uint8) = den > 0 -- the `valid` input of mgps_fields_extrapolate3.
+ *   Cell centre c: m = the least (dx^2 + dy^2) + dz^2 over the particles of the 3 x 3 x 3 cells around c, +inf with none;
+ *   liquid_phi_out = float(dx (min(sqrt(m), 1.5) - radius)) (may be NULL).  A particle outside those 27 cells is at least 1.5 cells
+ *   from the centre, so the clamp makes the 27-cell minimum exact.  0 < radius <= 1.5; dx finite and > 0.  The result is a union
+ *   of spheres, not a distance: mgps_fields_redistance makes it one.
+ *   counts_dev (device, unsigned long long[2], may be NULL) is ADDED to: [0] known faces, [1] cells with phi <= 0 (counted whether
+ *   or not liquid_phi_out is given).
+ *   Determinism.  No floating-point atomics; every target is written by its own thread, which gathers its sources in the stated
+ *   order: the same inputs give the same bits.  Safety.  Device data cannot be refused: every slot range taken from cell_start is
+ *   clamped into [0, n], so a wrong cell_start gives wrong values, never an out-of-range read. */
+typedef struct mgps_particles_to_grid_desc {
+    int struct_size;            /* sizeof(mgps_particles_to_grid_desc) */
+    int gx, gy, gz;             /* the WHOLE simulation grid */
+    int n;                      /* particles, >= 0 */
+    int form;                   /* the kernel: 0 the default, 1 the plain gather, 2 the staged march; all give the same bits */
+    double radius, dx;          /* radius in cells, 0 < radius <= 1.5; dx the cell size in phi's units, finite and > 0 */
+    const float *position[3];   /* binned; not read (may be NULL) when n == 0 */
+    const float *velocity[3];
+    const int32_t *cell_start;  /* cells + 2 entries */
+    float *velocity_out[3];     /* device face grids */
+    float *weight_out[3];       /* all three, or all NULL */
+    uint8_t *known_out[3];
+    float *liquid_phi_out;      /* device cell grid, may be NULL */
+    unsigned long long *counts_dev;
+} mgps_particles_to_grid_desc;
+/* One launch over tiles of 64 x 4 x 4 cells; a thread owns its cell's phi, its three backward faces and the forward faces where the
+ * grid ends.  form = 2 (and 0, the default) marches the source planes of a tile upward and takes each row's particles -- binned, so
+ * one run of slots -- through LDS in chunks of 768; form = 1 gathers every target's 27 cells from global memory.  Both visit a
+ * target's sources in the stated order and give the same bits (DESIGN.md section 23 has the times).  Tiles whose 6 x 6 x 66 cells
+ * hold no particle stream zeros and phi = dx (1.5 - radius) through.  Does not synchronise the stream.  Refuses with a message,
+ * before any device work: NULL desc or a struct_size mismatch, an extent < 1 (or more than 262140 cells along y or z),
+ * gx gy gz + 1 >= 2^31, n < 0, a form outside 0 .. 2, a radius outside (0, 1.5], a dx that is not finite and > 0, a NULL array that is
+ * in use, weight_out partly set, overlapping buffers. */
+int mgps_particles_to_grid(const mgps_particles_to_grid_desc *d, void *stream);
+
+/* 3. mgps_particles_update: grid -> particles, then move; one thread per particle in one launch.
+ *   Per inside particle, with S and U advection's sampling rule (above), its explicit fused multiply-adds included, of grid_new
+ *   (the projected, extrapolated velocity) and grid_old (the particles -> grid result before forces and projection):
+ *   pic = U_new(x), old = U_old(x) (with grid_old all NULL, allowed only when flip = 0: old = pic);
+ *   v_out,a = float((1 - flip) pic_a + flip (double(v_a) + (pic_a - old_a))), each operation rounded on its own: flip = 0 gives
+ *   float(pic) exactly, flip = 1 with grid_old being grid_new gives v back bit for bit.
+ *   Position: advection's trace with -dt in grid_new.  trace_order = 1: x_out = float(clampB(x + dt pic)); trace_order = 2:
+ *   p1 = clampB(x + (dt / 2) pic), x_out = float(clampB(x + dt U_new(p1))); the product and the sum are one fused multiply-add, as
+ *   in the trace of advection.  dt = 0 leaves positions bit-equal; an inside particle stays inside.
+ *   Outside particles are copied through.
+ *   counts_dev (device, unsigned long long[2], may be NULL) is ADDED to: [0] particles for which a clampB moved a coordinate (of p1
+ *   or of the end point), [1] outside particles.
+ *   Buffers.  Each output array is either exactly its input array (in place is safe: one thread per particle) or overlaps no
+ *   other array of the call; a partial overlap is refused.
+ * Out of scope, for all three: slab windows and particle migration between ranks; reseeding and deletion; collision with solids
+ * (solid_phi is not consulted; clampB is the only wall); APIC / affine transfers; wiring into the one-calls. */
+typedef struct mgps_particles_update_desc {
+    int struct_size;              /* sizeof(mgps_particles_update_desc) */
+    int gx, gy, gz;               /* the WHOLE simulation grid */
+    int n;                        /* particles, >= 0 */
+    int trace_order;              /* 1 or 2 */
+    double dt;                    /* time step over cell size; finite */
+    double flip;                  /* in [0, 1]: 0 is PIC, 1 is FLIP */
+    const float *position_in[3];  /* device, n entries each; not read (may be NULL) when n == 0 */
+    const float *velocity_in[3];
+    float *position_out[3];
+    float *velocity_out[3];
+    const float *grid_new[3];     /* device face grids */
+    const float *grid_old[3];     /* all three, or all NULL (flip = 0 only) */
+    unsigned long long *counts_dev;
+} mgps_particles_update_desc;
+/* Does not synchronise the stream.  Refuses with a message, before any device work: NULL desc or a struct_size mismatch, an
+ * extent < 1, gx gy gz + 1 >= 2^31, n < 0, a trace_order that is neither 1 nor 2, a non-finite dt, a flip outside [0, 1], a NULL
+ * array that is in use, grid_old partly set, or NULL with flip > 0, overlapping buffers. */
+int mgps_particles_update(const mgps_particles_update_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
