@@ -3,8 +3,9 @@
  * around the multigrid solve: material labels, valid faces, multigrid domain labels
  * and boundary weights, right-hand side, pressure copy in / out, pressure-gradient update and the
  * post-projection divergence report.  TEST INFRASTRUCTURE ONLY, like mg_oracle.c: nothing in the product
- * path may include, link, import or call this file.  PARITY UNPINNED for the same reason (no fixtures in the
- * reference, HDK not buildable here); pinned by properties in tests/test_fields.py (the projected velocity
+ * path may include, link, import or call this file.  PARITY UNPINNED, unlike mg_oracle.c: the reference's
+ * plugin file needs SIM_RawField, which the stand-in headers of oracle/ref_standin/ do not cover, and the
+ * reference has no fixtures; pinned by properties in tests/test_fields.py (the projected velocity
  * is divergence-free to solver tolerance -- the reference's own check, Plug.cpp:704-706).
  *
  * "Plug.cpp" = Source/HDK_GeometricFreeSurfacePressureSolver.cpp, "Util.h/.cpp" = Source/HDK_Utilities.*.

@@ -5,14 +5,18 @@
  * tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it, and only as the
  * checker / the timed CPU baseline.
  *
- * PARITY UNPINNED: the reference (rgoldade/GeometricMultigridPressureSolver) ships no golden
- * vectors, no fixtures and no known-answer tests for this path, and it cannot be compiled here
- * (every translation unit needs the Houdini HDK and Eigen3, neither is in the image).  What pins
- * this restatement instead are the reference's own *property* checks, re-expressed in
- * tests/test_oracle_*.py: the operator symmetry identities (Test.cpp:1197-1875), the structural
- * label invariants (Ops.cpp:471-632, Ops.h:1771-1870), the 50-V-cycle convergence trace
- * (Test.cpp:1877-1960), the CG test (Test.cpp:675-1009) and an independent SciPy assembly of the
- * same matrix (row rules Test.cpp:1350-1433).
+ * PARITY: pinned to the reference (rgoldade/GeometricMultigridPressureSolver) itself.  The reference
+ * ships no golden vectors, but its solver core compiles, unchanged, against the stand-in headers of
+ * oracle/ref_standin/ (`make ref`, see the Makefile and ref_driver.cpp); tests/golden/ref_*.npz hold
+ * what that binary computes and tests/test_reference_parity.py holds every entry of this file to it:
+ * per-cell results bit for bit on every level (visiting and accumulation order included), reductions
+ * within the bound of a different summation order, V-cycles and PCG within the measured sensitivity
+ * to the coarse direct solve.  The reference's own *property* checks,
+ * re-expressed in tests/test_oracle_*.py, stay as a second, independent pin: the operator symmetry
+ * identities (Test.cpp:1197-1875), the structural label invariants (Ops.cpp:471-632,
+ * Ops.h:1771-1870), the 50-V-cycle convergence trace (Test.cpp:1877-1960), the CG test
+ * (Test.cpp:675-1009) and an independent SciPy assembly of the same matrix (row rules
+ * Test.cpp:1350-1433).
  *
  * Every function cites the reference file:line it follows ("Ops.h" =
  * Source/HDK_GeometricMultigridOperators.h, "Ops.cpp" = ...Operators.cpp, "MG.cpp" =

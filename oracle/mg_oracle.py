@@ -1,9 +1,10 @@
 """ctypes front end of the CPU oracle (oracle/mg_oracle.c).
 
 TEST INFRASTRUCTURE ONLY -- imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
-leg, never by the product package.  PARITY UNPINNED (see the header of mg_oracle.c): the reference
-ships no golden vectors and cannot be built here; behaviour is pinned by the reference's own
-property checks re-expressed in tests/test_oracle_*.py.
+leg, never by the product package.  Parity (see the header of mg_oracle.c): pinned bit for bit to the
+reference's own solver core, compiled against stand-in headers (oracle/mg_ref.py,
+tests/test_reference_parity.py), and by the reference's property checks re-expressed in
+tests/test_oracle_*.py.
 
 All grids are numpy arrays indexed [k, j, i] (x fastest in memory), labels int32, reals float64
 (or float32 with Oracle(f32=True), a same-algorithm single-precision build used to separate

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/*.npz.  ORACLE-GENERATED, not reference-generated: the reference cannot
-be built or run here (Houdini HDK + Eigen3 missing) and ships no vectors of its own, so these
-fixtures freeze the behaviour of oracle/mg_oracle.c (itself pinned by tests/test_oracle_properties.py)
-on small domains: both smoothers, 1 and 4 chained V-cycles, MG-PCG and diagonal-PCG iteration counts.
+"""Regenerates the ORACLE-GENERATED fixtures: tests/golden/golden_*.npz, sweeps22_solid24.npz and
+fields_scene20.npz.  They freeze the behaviour of oracle/mg_oracle.c and oracle/mg_fields_oracle.c on small
+domains: both smoothers, 1 and 4 chained V-cycles, MG-PCG and diagonal-PCG iteration counts, the field
+passes.  The REFERENCE-GENERATED fixtures, tests/golden/ref_*.npz, come from make_ref_golden.py, which runs
+the reference's own solver core (compiled against stand-in headers, `make -C oracle ref`); mg_oracle.c is
+pinned to those bit for bit by tests/test_reference_parity.py, and by tests/test_oracle_properties.py.
 
     python tests/golden/make_golden.py
 """
