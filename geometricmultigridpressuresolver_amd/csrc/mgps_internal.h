@@ -409,6 +409,17 @@ int launchResidualZ(void *stream, const GridP &fine, float *rz, const float *x, 
 int launchRestrictY(void *stream, const GridP &coarse, float *coarseOut, const float *rzx, const GridP &fine);
 int launchResidualEdgePlanes(void *stream, const GridP &g, float *r, const float *x, const float *b);
 int launchRestrictXY(void *stream, const GridP &coarse, float *coarseOut, const float *rz);
+// The Jacobi sweep of a down-stroke inside the x-folded residual march (round 15): out = x' on every cell whose bit in `keep`
+// (launchMarkClosure) is clear -- the kept cells hold what the plain band launch wrote before and are read, never written --, rz as
+// launchResidualZ(.., xfold) leaves it for x' (the terms across the tiles' rims added by a fix-up launch: last bits differ).
+// keptT: launchKeptTiles of `keep`, keptTileWords words in GridP::plainT's layout.  downFusedFits: the levels the march takes
+bool downFusedFits(const GridP &fine);
+size_t keptTileWords(const GridP &g);
+int launchKeptTiles(void *stream, const GridP &g, const uint32_t *keep, unsigned long long *keptT);
+// colX: downFusedColumnFloats floats, zeroed once by the caller -- the march leaves the tiles' first / last columns there for the fix-up
+size_t downFusedColumnFloats(const GridP &fine);
+int launchDownFused(void *stream, const GridP &fine, float *out, float *rz, const float *x, const float *b, float omega, const int32_t *edges, int nedges,
+                    const uint32_t *keep, const unsigned long long *keptT, float *colX);
 // ---- mixed precision (options.precision = 1): binary16 grids of the fine level, passed as void* -----------------------
 bool mixedPrecisionShapeOk(int nx, int ny, int nz);  // the fine level must take the quad sweep and the block prolongation
 int launchStencilMixed(void *stream, StencilOp op, const GridP &g, void *outH, const void *xH, const float *b, float omega, const MixScale &ms,

@@ -1042,6 +1042,270 @@ __global__ __launch_bounds__(64 * kPlaneRows) void residualZEdgeKernel(GridP g, 
     storeXFolded(keepIf(wr, live), rz + size_t(K) * (sz >> 1), offX, storeX, false, seam + size_t(K) * sl.planeFloats(), seamOff, seamW);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The down-stroke's Jacobi sweep inside the residual march (round 15).  A down-stroke from an initial guess is "closure launch,
+// sweep, plain launch" and then residualZKernel<true> on the result x': the sweep writes x' (4 B per cell), the march reads it back
+// with its halo and reads the rhs a second time.  Here the plain launch goes FIRST, into the spare grid (it reads the snapshot and
+// the rhs alone), and one march forms x'(k + 1) = Jacobi(x) of its own quad -- stencilPlaneKernel<OP_JACOBI>'s expressions on the
+// same staged values: the same bits --, stores it, stages it in a second LDS ring and forms r(k) = b(k) - A x'(k) from that ring.
+//   * Kept cells (launchMarkClosure's bits: what the plain launch wrote) are never stored, not even with their own value: the block
+//     above or below may be reading them.  Where a quad holds one (`keptT`: a word per plane, row and tile like GridP::plainT, the
+//     branch's execution mask) its x' is taken from `out`, cell by cell, and the other cells are stored one by one.
+//   * Along z a block forms x' on k0 - 2 .. k1 + 1 (r on k0 - 1 .. k1 needs them) and stores [k0, k1).
+//   * In x-y nothing is formed twice: the x' ring has a halo of zeros.  A cell on the tile's rim misses x' of its neighbour in the
+//     next tile -- exactly "+ x'(neighbour)" of a simple active cell's r -- and downSeamFixKernel adds it to what this kernel
+//     stored, folded with the same weights.
+// One barrier per step: step kk stages x(kk + 1) before it, behind it the x' ring is written at (kk + 1) & 1 -- the thread's own
+// slot, whose old value x'(kk - 1) it alone has just read -- and read at kk & 1, which the step before wrote.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned gLoadWord(const uint32_t *base, unsigned idx) { return *(const MGPS_GLOBAL_AS uint32_t *)((const MGPS_GLOBAL_AS char *)base + idx * 4u); }
+__device__ __forceinline__ void gStore1(float *base, unsigned cell, float v) { *(MGPS_GLOBAL_AS float *)((MGPS_GLOBAL_AS char *)base + cell * 4u) = v; }
+__global__ __launch_bounds__(64 * kPlaneRows, 8) void jacobiResidualZKernel(GridP g, float *out, float *__restrict__ rz, const float *__restrict__ x,
+                                                                           const float *__restrict__ b, float omega, unsigned nbx, unsigned nby, int zc,
+                                                                           const int32_t *__restrict__ blocks, float *__restrict__ seam,
+                                                                           const uint32_t *__restrict__ keep, const unsigned long long *__restrict__ keptT,
+                                                                           float *__restrict__ colX)
+{
+    __shared__ float plane[2][kPlaneBufFloats];   // x
+    __shared__ float smooth[2][kPlaneBufFloats];  // x': the halo stays 0
+    const PlaneTile t = planeTile(g, nbx, nby, zc, blocks);
+    const bool live = t.live, valid = t.valid, rowTop = t.rowTop, rowBot = t.rowBot, colL = t.colL, colR = t.colR;
+    const size_t sz = size_t(t.sz);
+    const int k0 = t.k0, k1 = t.k1;  // both even
+    const int ks = max(k0 - 1, 0), ke = min(k1, g.nz - 1);  // the planes r is formed on (residualZKernel)
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = threadIdx.x; q < 2 * kPlaneBufFloats / 4; q += 64 * kPlaneRows) reinterpret_cast<float4 *>(&smooth[0][0])[q] = zero4;  // (the first barrier of the march orders it)
+    // loads: unconditional, in the order of their use, aimed like residualZKernel's (offL, offHy, offHx)
+    const unsigned offL = unsigned(t.jc) * unsigned(g.nx) + unsigned(min(max(t.ic, g.xlo), max(g.xhi - 4, g.xlo)));
+    float *const mine0 = plane[0] + (t.ty + 1) * kPlanePitch + 4 + t.lane * 4;
+    float *const smooth0 = smooth[0] + (t.ty + 1) * kPlanePitch + 4 + t.lane * 4;
+    const unsigned offHy = (rowTop && t.jc > 0) ? offL - unsigned(g.nx) : (rowBot && t.jc < g.ny - 1) ? offL + unsigned(g.nx) : offL;
+    const int p0 = ks - 1;  // the first plane x' is formed on (planes outside the grid: clamped, EXTERIOR shell -- x' = x there)
+    {
+        const float4 xm = gLoad4(t.planeOf(x, p0 - 1), offL);
+        *reinterpret_cast<float4 *>(mine0 + kPlaneBufFloats) = keepIf(xm, live);
+    }
+    const float *xk = t.planeOf(x, p0);
+    float4 xc = gLoad4(xk, offL);
+    float4 xp = gLoad4(t.planeOf(x, p0 + 1), offL);
+    float4 hy = gLoad4(xk, offHy);
+    const bool useHx = live && t.hasHx();
+    const unsigned offHx = t.offHx(useHx, offL);
+    float hx = gLoad1(xk, offHx);
+    constexpr float w0 = 0.125f, w1 = 0.375f, w2 = 0.375f, w3 = 0.125f;
+    float accPrev[4] = {0.f, 0.f, 0.f, 0.f}, accCur[4] = {0.f, 0.f, 0.f, 0.f};
+    const unsigned rowX = t.rowS * (unsigned(g.nx) >> 1) + t.bx * 128u;
+    const bool storeX = t.i < g.nx && t.j < g.ny && t.ic >= g.xlo - 4 && t.ic < g.xhi + 4;
+    const bool seamL = colL && t.bx > 0, seamR = colR && t.i + 4 < g.nx;
+    const bool seamW = valid && (seamL || seamR);
+    const SeamLayout sl = seamLayout(g.nx, g.ny);
+    auto storeFolded = [&](int K, bool nt) {  // (every lane of the wave comes here)
+        const float4 v = keepIf(make_float4(accPrev[0], accPrev[1], accPrev[2], accPrev[3]), valid);
+        storeXFolded(v, scalarBase(rz + size_t(K) * (sz >> 1)), rowX + 2u * laneHere(), storeX, nt, scalarBase(seam + size_t(K) * sl.planeFloats()),
+                     colL ? sl.entry(t.rowS, t.bx, 1u) : sl.entry(t.rowS, t.bx + 1u, 0u), seamW);
+    };
+    auto inGrid = [&](int k) { return min(max(k, 0), g.nz - 1); };
+    const unsigned long long *const pt = g.plainT;
+    unsigned long long pw = pt ? plainWord64(pt, t.plainIdx(inGrid(p0))) : 0ull;
+    unsigned long long kw = plainWord64(keptT, t.plainIdx(inGrid(p0)));
+    float4 bPrev = zero4;   // rhs and codes of plane kk: what the step before loaded for its x'
+    unsigned lcPrev = 0x01010101u * unsigned(MGPS_EXTERIOR_CELL);
+    // (offsets laundered at their use, as in prolongJacobiPlaneKernel: no 64-bit copy of an offset is kept across the march)
+    auto opq = [](unsigned v) {
+        asm volatile("" : "+v"(v));
+        return v;
+    };
+    int buf = 0;
+    for (int kk = p0 - 1; kk <= ke; ++kk) {
+        const int p = kk + 1, pc = inGrid(p);  // x' is formed on plane p, r on plane kk
+        float *me = mine0 + buf * kPlaneBufFloats;
+        xc = keepIf(xc, live);
+        stagePlane(me, t, xc, keepIf(hy, live), hx, useHx);
+        const size_t cb = size_t(pc) * sz;
+        const float *bk = scalarBase(b + cb);
+        const uint8_t *lk = scalarBase(g.lab + cb);
+        const float *xn = t.planeOf(x, p + 1), *xq2 = t.planeOf(x, p + 2);
+        unsigned lcw = 0u;
+        if (!plainLane(pw)) lcw = gLoadCodesWnt(lk, opq(offL));
+        if (pt) pw = plainWord64(pt, t.plainIdx(inGrid(p + 1)));  // (the next step's)
+        const float4 bc = gLoad4nt(bk, opq(offL));
+        // a quad with kept cells: their bits and what the plain launch left (a wave without one issues neither load)
+        float4 kept4 = zero4;
+        unsigned nib = 0u;
+        if (plainLane(kw)) {
+            const unsigned q = unsigned(cb & 31u) + offL;
+            nib = (gLoadWord(scalarBase(keep + (cb >> 5)), q >> 5) >> (q & 31u)) & 15u;
+            kept4 = gLoad4(scalarBase(out + cb), opq(offL));
+        }
+        kw = plainWord64(keptT, t.plainIdx(inGrid(p + 1)));
+        const float hxn = gLoad1(xn, opq(offHx));
+        float4 hyn = hy;
+        if (rowTop || rowBot) hyn = gLoad4(xn, opq(offHy));  // (wave-uniform)
+        const float4 xq = gLoad4(xq2, opq(offL));
+        __syncthreads();
+        const StagedPlane n = readStaged(me, mine0 + (buf ^ 1) * kPlaneBufFloats);
+        float res[4];
+        simpleQuad<OP_JACOBI>(n.xl, xc, n.xr, n.ym, n.yp, n.zm, xp, bc, lcw, omega, res);
+        if (valid && p >= k0 && p < k1) {  // (x' of the block's own planes)
+            float *op = scalarBase(out + size_t(p) * sz);
+            if (!nib) gStore4nt(op, opq(offL), make_float4(res[0], res[1], res[2], res[3]));
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)  // (the cell inside the quad goes into the scalar base: one offset register for all four)
+                    if (!(nib & (1u << e))) gStore1(scalarBase(op + e), opq(offL), res[e]);
+            }
+        }
+        const float4 sp = keepIf(make_float4((nib & 1u) ? kept4.x : res[0], (nib & 2u) ? kept4.y : res[1], (nib & 4u) ? kept4.z : res[2], (nib & 8u) ? kept4.w : res[3]), live);
+        // the tile's first / last column at a boundary inside the grid, for the fix-up: x' and "a simple active cell" (colX, below)
+        if (colX && seamW && p >= k0 && p < k1) {
+            const bool simple = simpleCell(colL ? (lcw & 255u) : (lcw >> 24));
+            gStore2(scalarBase(colX + (size_t(p) * size_t(g.ny) + t.rowS) * (sl.nseam * 4u)), colL ? t.bx * 4u - 2u : t.bx * 4u,
+                    make_float2(colL ? sp.x : sp.w, simple ? 1.f : 0.f));
+        }
+        float *sm = smooth0 + buf * kPlaneBufFloats;
+        if (kk >= ks) {  // (wave-uniform) r on plane kk: x'(kk) and its neighbours from the ring, x'(kk - 1) from this thread's own slot
+            const float *sc = smooth0 + (buf ^ 1) * kPlaneBufFloats;
+            const StagedPlane m = readStaged(sc, sm);
+            const float4 xs = *reinterpret_cast<const float4 *>(sc);
+            *reinterpret_cast<float4 *>(sm) = sp;
+            float r[4];
+            simpleQuad<OP_RESIDUAL>(m.xl, xs, m.xr, m.ym, m.yp, m.zm, sp, bPrev, lcPrev, 0.f, r);
+            const int k = kk;
+            if (k & 1) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    accPrev[e] = accCur[e] + w2 * r[e];
+                    accCur[e] = w0 * r[e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    accPrev[e] += w3 * r[e];
+                    accCur[e] += w1 * r[e];
+                }
+                if (k >= k0 + 2) storeFolded((k >> 1) - 1, true);
+            }
+        } else {
+            *reinterpret_cast<float4 *>(sm) = sp;
+        }
+        bPrev = bc;
+        lcPrev = lcw;
+        xc = xp;
+        xp = xq;
+        hy = hyn;
+        hx = hxn;
+        buf ^= 1;
+    }
+    if (k1 == g.nz) storeFolded((g.nz >> 1) - 1, false);  // (wave-uniform) the last coarse plane is complete with three terms
+}
+
+// What jacobiResidualZKernel left out: the term "+ x'(neighbour in the next tile)" of the cells on a tile's rim, added into the
+// entries that kernel stored.  One workgroup per block of the same list.  First the two rim rows of the tile (rows 16 m and
+// 16 m - 1 of the grid): a wave per row and pair of coarse planes reads the six fine planes once (its own codes, the neighbour
+// row's x' from the grid), folds the gated row along z with the march's weights and along x with storeXFolded's shuffles, and adds
+// the pair into rzx and -- first / last lane at a boundary inside the grid -- the quad into the seam entry, whose columns
+// restrictYKernel takes from there.  Behind a barrier the two rim columns (fine 256 s and 256 s - 1): a thread per row, coarse plane
+// and side adds its term into `.x` of side 1 / `.w` of side 0 of the seam entry.  The columns come from colX, which the march wrote
+// beside x': per plane, row and boundary s four floats -- x'(256 s - 1), "simple active" (1 / 0), x'(256 s), "simple active" --,
+// zero where no block ever writes (a column read from the grid costs a line per cell: 3.2 GB per 1024^3 launch, LABNOTES R15).
+// Every entry gets its additions from this one workgroup in this order: a second call gives the same bits.
+constexpr size_t colXFloats(int nx, int ny, int nz) { return size_t(nz) * ny * seamLayout(nx, ny).nseam * 4u; }
+__global__ __launch_bounds__(64 * kPlaneRows) void downSeamFixKernel(GridP g, float *__restrict__ rz, float *__restrict__ seam, const float *__restrict__ xs,
+                                                                    const float *__restrict__ colX, unsigned nbx, unsigned nby, int zc,
+                                                                    const int32_t *__restrict__ blocks)
+{
+    PlaneCoords t;
+    planeCoords(t, g, blocks ? unsigned(blocks[blockIdx.x]) : blockIdx.x, nbx, nby, zc);
+    const size_t sy = size_t(g.nx), sz = sy * g.ny;
+    const SeamLayout sl = seamLayout(g.nx, g.ny);
+    const int nK = (t.k1 - t.k0) >> 1, K0 = t.k0 >> 1;
+    const float wz[4] = {0.125f, 0.375f, 0.375f, 0.125f};
+    const int j0 = int(t.by) * kPlaneRows;
+    {  // rim rows
+        const int i = t.i;
+        const bool mine = i < g.nx && i >= g.xlo && i < g.xhi;
+        const bool storeX = i < g.nx && i >= g.xlo - 4 && i < g.xhi + 4;
+        const bool seamL = t.lane == 0 && t.bx > 0, seamR = t.lane == kWave - 1 && i + 4 < g.nx;
+        for (int task = t.ty; task < 2 * ((nK + 1) >> 1); task += kPlaneRows) {  // (wave-uniform)
+            const int side = task & 1, Ka = K0 + 2 * (task >> 1), nKa = min(2, K0 + nK - Ka);  // coarse planes Ka (and Ka + 1): fine 2 Ka - 1 .. 2 Ka + 4
+            const int j = side ? j0 + kPlaneRows - 1 : j0, jn = side ? j + 1 : j - 1;
+            if (side ? jn >= g.ny : j == 0) continue;
+            float4 tq[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                const int k = 2 * Ka - 1 + c;
+                tq[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!mine || k < 0 || k >= g.nz || c >= 2 * nKa + 2) continue;
+                const size_t cell = size_t(k) * sz + size_t(j) * sy + size_t(i);
+                const uchar4 lc = codes4(*reinterpret_cast<const unsigned *>(g.lab + cell));
+                const float4 xn = *reinterpret_cast<const float4 *>(xs + size_t(k) * sz + size_t(jn) * sy + size_t(i));
+                tq[c] = make_float4(simpleCell(lc.x) ? xn.x : 0.f, simpleCell(lc.y) ? xn.y : 0.f, simpleCell(lc.z) ? xn.z : 0.f, simpleCell(lc.w) ? xn.w : 0.f);
+            }
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if (q >= nKa) break;  // (wave-uniform)
+                const int K = Ka + q;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    v.x += wz[c] * tq[2 * q + c].x;
+                    v.y += wz[c] * tq[2 * q + c].y;
+                    v.z += wz[c] * tq[2 * q + c].z;
+                    v.w += wz[c] * tq[2 * q + c].w;
+                }
+                const float2 o = make_float2(foldX4(fromLeftLane(v.w), v.x, v.y, v.z), foldX4(v.y, v.z, v.w, fromRightLane(v.x)));
+                if (storeX) {
+                    float2 *e = reinterpret_cast<float2 *>(rz + size_t(K) * (sz >> 1) + size_t(j) * (sy >> 1) + size_t(i >> 1));
+                    const float2 old = *e;
+                    *e = make_float2(old.x + o.x, old.y + o.y);
+                }
+                if (mine && (seamL || seamR)) {
+                    float4 *e = reinterpret_cast<float4 *>(seam + size_t(K) * sl.planeFloats() + (seamL ? sl.entry(unsigned(j), t.bx, 1u) : sl.entry(unsigned(j), t.bx + 1u, 0u)));
+                    const float4 old = *e;
+                    *e = make_float4(old.x + v.x, old.y + v.y, old.z + v.z, old.w + v.w);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int tid = threadIdx.x;
+    if (colX && tid < 2 * kPlaneRows * nK) {  // rim columns
+        const int side = tid & 1, j = j0 + ((tid >> 1) & (kPlaneRows - 1)), K = K0 + tid / (2 * kPlaneRows);
+        const int i = int(t.bx) * kPlaneCols + (side ? kPlaneCols - 1 : 0);
+        const int iq = i & ~3;  // (the quad the march's lane owns)
+        const unsigned s = t.bx + unsigned(side);  // the boundary at fine x = 256 s
+        if (j < g.ny && (side ? i + 1 < g.nx : i > 0) && iq >= g.xlo && iq < g.xhi) {
+            float v = 0.f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int k = 2 * K - 1 + c;
+                if (k < 0 || k >= g.nz) continue;
+                const float4 e = *reinterpret_cast<const float4 *>(colX + ((size_t(k) * g.ny + size_t(j)) * sl.nseam + (s - 1u)) * 4u);
+                v += wz[c] * (side ? (e.y != 0.f ? e.z : 0.f) : (e.w != 0.f ? e.x : 0.f));
+            }
+            float *e = seam + size_t(K) * sl.planeFloats() + (side ? sl.entry(unsigned(j), s, 0u) + 3u : sl.entry(unsigned(j), s, 1u));
+            *e += v;
+        }
+    }
+}
+
+// GridP::plainT's layout for the keep bits of a level (launchMarkClosure): bit = lane, set where the lane's quad holds a kept cell
+__global__ __launch_bounds__(256) void keptTilesKernel(const uint32_t *__restrict__ keep, unsigned nx, unsigned nbx, size_t rows, unsigned long long *__restrict__ keptT)
+{
+    const size_t t = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (t >= rows * nbx) return;
+    const size_t row = t / nbx;
+    const unsigned tile = unsigned(t - row * nbx);
+    unsigned long long v = 0ull;
+    for (unsigned lane = 0; lane < 64u; ++lane) {
+        const unsigned i = tile * unsigned(kPlaneCols) + 4u * lane;
+        if (i >= nx) break;
+        const size_t c = row * nx + i;
+        if ((keep[c >> 5] >> (c & 31)) & 15u) v |= 1ull << lane;
+    }
+    keptT[t] = v;
+}
+
 // Scalar fallback for levels whose nx is not a multiple of 4 (only the tiniest coarse levels).
 template <int OP, bool DOT = false>
 __global__ void stencilScalarKernel(GridP g, float *__restrict__ out, const float *__restrict__ x,
@@ -3339,6 +3603,37 @@ int launchResidualZ(void *stream, const GridP &fine, float *rz, const float *x, 
     if (list && nedges > 0) residualZEdgeKernel<false><<<unsigned(nedges), 64 * kPlaneRows, 0, s>>>(fine, rz, x, b, nbx, nby, zc, edges, nullptr);
     if (fine.nbnd > 0)  // the general BOUNDARY cells' part (their entries lie in blocks the launches above have just written)
         for (int phase = 0; phase < 4; ++phase) residualZGeneralKernel<<<blocksFor(size_t(fine.nbnd), 256), 256, 0, s>>>(fine, rz, x, b, phase);
+    return int(hipGetLastError());
+}
+// The Jacobi sweep of a down-stroke and launchResidualZ's x-folded form on its result in one march (jacobiResidualZKernel, then
+// downSeamFixKernel, then the edge blocks as launchResidualZ serves them).  `out` holds what the plain band launch wrote on the
+// cells of `keep` (launchMarkClosure) and receives x' everywhere else; keptT: launchKeptTiles of the same bits.
+bool downFusedFits(const GridP &fine) { return fine.nbnd == 0 && fine.planeZc >= 4 && (fine.planeZc & 1) == 0 && (fine.nz & 1) == 0 && !fine.ghostLo && !fine.ghostHi; }
+int launchDownFused(void *stream, const GridP &fine, float *out, float *rz, const float *x, const float *b, float omega, const int32_t *edges, int nedges,
+                    const uint32_t *keep, const unsigned long long *keptT, float *colX)
+{
+    if (!downFusedFits(fine) || !keep || !keptT || (!colX && downFusedColumnFloats(fine) > 0)) return int(hipErrorInvalidValue);
+    const int zc = fine.planeZc;
+    const PlaneTiles pt = planeTiles(fine.nx, fine.ny, fine.nz, zc);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool list = fine.planeBlocks != nullptr;
+    const unsigned nb = list ? unsigned(fine.nplaneBlocks) : unsigned(pt.count());
+    const int32_t *blocks = list ? fine.planeBlocks : nullptr;
+    float *seam = rz + rzxGridFloats(fine);
+    if (nb > 0) {
+        jacobiResidualZKernel<<<nb, 64 * kPlaneRows, 0, s>>>(fine, out, rz, x, b, omega, pt.nbx, pt.nby, zc, blocks, seam, keep, keptT, colX);
+        downSeamFixKernel<<<nb, 64 * kPlaneRows, 0, s>>>(fine, rz, seam, out, colX, pt.nbx, pt.nby, zc, blocks);
+    }
+    if (list && nedges > 0) residualZEdgeKernel<true><<<unsigned(nedges), 64 * kPlaneRows, 0, s>>>(fine, rz, out, b, pt.nbx, pt.nby, zc, edges, seam);
+    return int(hipGetLastError());
+}
+size_t downFusedColumnFloats(const GridP &fine) { return colXFloats(fine.nx, fine.ny, fine.nz); }
+size_t keptTileWords(const GridP &g) { return size_t(g.ny) * g.nz * planeTiles(g.nx, g.ny, g.nz, 0).nbx; }
+int launchKeptTiles(void *stream, const GridP &g, const uint32_t *keep, unsigned long long *keptT)
+{
+    const unsigned nbx = planeTiles(g.nx, g.ny, g.nz, 0).nbx;
+    const size_t rows = size_t(g.ny) * g.nz;
+    keptTilesKernel<<<blocksFor(rows * nbx, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(keep, unsigned(g.nx), nbx, rows, keptT);
     return int(hipGetLastError());
 }
 int launchRestrictXY(void *stream, const GridP &coarse, float *coarseOut, const float *rz)

@@ -71,6 +71,8 @@ struct DevLevel {
     float *rz = nullptr;            // the residual folded along z (residualRestrictFuses; nx x ny x nz / 2, made on first use, zero where nothing writes)
     uint8_t *snapTile = nullptr;    // Gauss-Seidel strokes: a byte per 16^3 tile, set where a box group reads (launchMarkSnapTiles; made on first use)
     uint32_t *keepBits = nullptr;   // launchStrokeFront: one bit per cell, the owned band / closure-output cells of the boxes (made on first use)
+    unsigned long long *keptT = nullptr;  // launchDownFused: keepBits per quad in GridP::plainT's layout (launchKeptTiles; made on first use)
+    float *seamCols = nullptr;            // launchDownFused: the tiles' first / last columns of x' (downFusedColumnFloats, zeroed; made on first use)
     // A cut level of a slab run built on the device (round 5): the box form of the band stage with the neighbours' cells its
     // regions read kept in the deep ghost planes of the grids (mgps_solver::ghost planes on either side of every grid).  recvIdx:
     // those cells, offsets into the ghost planes below [0] / above [1] the owned planes (ascending); sendIdx: the cells of this
@@ -465,6 +467,8 @@ void freeAll(mgps_solver *h)
         (void)cacheFree(L.bandBoxes.list);
         (void)cacheFree(L.planeFlags);
         (void)cacheFree(L.keepBits);
+        (void)cacheFree(L.keptT);
+        (void)cacheFree(L.seamCols);
         (void)cacheFree(L.snapTile);
         (void)cacheFree(L.rz);
         (void)cacheFree(L.rzEdges);
@@ -775,6 +779,15 @@ int ensureKeepBits(mgps_solver *h, int l)
     MGPS_LAUNCH(h, launchMarkClosure(h->stream, L.g, L.bandBoxes, L.keepBits));
     return MGPS_OK;
 }
+int ensureKeptTiles(mgps_solver *h, int l)
+{
+    DevLevel &L = h->lv[l];
+    if (L.keptT) return MGPS_OK;
+    MGPS_TRY(ensureKeepBits(h, l));
+    MGPS_TRY(devAlloc(h, &L.keptT, keptTileWords(L.g), false));
+    MGPS_LAUNCH(h, launchKeptTiles(h->stream, L.g, L.keepBits, L.keptT));
+    return MGPS_OK;
+}
 
 // The forms a stroke runs in: 3 x band Jacobi -> full-domain smoother -> 3 x band Jacobi (MG.cpp:445-513 down, 806-879 up), the
 // smoother run options.pre_sweeps (down) / post_sweeps (up) times.  strokeForm picks one; smoothStroke runs it.
@@ -783,6 +796,7 @@ enum StrokeForm {
     SF_THREE_LAUNCH,   // Jacobi, one sweep: closure launch, sweep, plain launch (threeLaunchStroke)
     SF_FRONT,          // the same with the closure launch and the sweep merged (frontStroke)
     SF_PROLONG_FUSED,  // an up-stroke of the three-launch form with the prolongation inside its first two launches (prolongFusedStroke)
+    SF_DOWN_FUSED,     // a down-stroke from an initial guess of the three-launch form with its sweep inside the residual march (fusedDownStroke)
     SF_FIRST_FUSED,    // Jacobi, several sweeps: the first band stage and the first sweep in two launches (firstFusedStroke)
     SF_GENERIC,        // band passes, sweeps, band passes
 };
@@ -812,8 +826,19 @@ enum StrokeForm {
 // SF_FRONT (launchStrokeFront): whole-grid levels that take the quad sweep, up to 2^24 cells (a 256^3 level) -- where a launch is
 // a latency chain, one chain instead of two (512^3 level: 618-629 -> 565-593 cycles/s merged).  Stage timers and the sweep timer
 // want the launches apart.
-StrokeForm strokeForm(const mgps_solver *h, int l, bool down, const float *cur, const float *other, const float *b, bool dot)
+//
+// SF_DOWN_FUSED (launchDownFused, round 15): the stroke AND the residual + restriction behind it -- closure launch, plain launch
+// into the spare grid, one march that forms x' and the x-folded residual of x', a fix-up for the tiles' rims, restrictYKernel.
+// Only where the caller says the iterate is a guess (fromGuess: level 0 of a cycle with an initial guess; zero-start strokes keep
+// their forms) and the level would take SF_THREE_LAUNCH and the x-folded residual pair; planes of 4 MiB and more.
+// MGPS_FUSE_DOWN=0: never (A/B); =1: every level where it is valid (tests).
+bool residualRestrictXFolded(const mgps_solver *h, int l);
+StrokeForm strokeForm(const mgps_solver *h, int l, bool down, const float *cur, const float *other, const float *b, bool dot, bool fromGuess = false)
 {
+    static const int fuseDown = [] {  // -1: by size
+        const char *e = getenv("MGPS_FUSE_DOWN");
+        return !e ? -1 : (e[0] == '0' ? 0 : 1);
+    }();
     static const bool gsSnapshots = [] {
         const char *e = getenv("MGPS_GS_SNAPSHOT");
         return !(e && e[0] == '0');
@@ -831,6 +856,9 @@ StrokeForm strokeForm(const mgps_solver *h, int l, bool down, const float *cur, 
     if (!down && fuseUp != 0 && (fuseUp > 0 || planes) && l + 1 < int(h->lv.size()) && !dot && !h->dist && !h->tailOfSlabRun && h->opt.precision == 0 &&
         !L.boxForm && prolongJacobiPlaneFits(L.g) && boxPlaneFits(L.d))
         return SF_PROLONG_FUSED;
+    if (down && fromGuess && fuseDown != 0 && (fuseDown > 0 || planes) && l + 1 < int(h->lv.size()) && !dot && !h->dist && !h->tailOfSlabRun &&
+        h->opt.precision == 0 && !L.boxForm && L.g.planeBlocks && downFusedFits(L.g) && (L.d.cells() & 31) == 0 && residualRestrictXFolded(h, l))
+        return SF_DOWN_FUSED;
     if (!dot && !sweepTimed(h, l) && !stageTimingOn(h) && !h->dist && L.d.cells() <= (size_t(1) << 24) && stencilKernelOf(L.g) == 1 && (L.d.cells() & 31) == 0)
         return SF_FRONT;
     return SF_THREE_LAUNCH;
@@ -881,26 +909,32 @@ bool residualRestrictXFolded(const mgps_solver *h, int l)
     }();
     return allowed && residualRestrictFuses(h, l) && residualRestrictXFolds(h->lv[l].g);
 }
+// the level's rz and the list of its edge blocks, made once
+int ensureRz(mgps_solver *h, int l, bool xfold)
+{
+    DevLevel &F = h->lv[l];
+    if (F.rz) return MGPS_OK;
+    MGPS_TRY(devAlloc(h, &F.rz, xfold ? rzxFloats(F.g) : F.d.cells() / 2, true));
+    if (F.g.planeBlocks) {  // once: which blocks off the activity list sit below / above a listed one
+        if (!F.planeFlags) {
+            MGPS_TRY(devAlloc(h, &F.planeFlags, planeBlockCount(F.g), true));
+            MGPS_LAUNCH(h, launchPlaneBlockFlags(h->stream, F.g, F.planeFlags));
+        }
+        std::vector<uint8_t> flags(planeBlockCount(F.g));
+        MGPS_HIP(h, hipMemcpyAsync(flags.data(), F.planeFlags, flags.size(), hipMemcpyDeviceToHost, h->stream));
+        MGPS_HIP(h, hipStreamSynchronize(h->stream));
+        const std::vector<int32_t> edges = planeBlockEdges(F.g, flags);
+        F.nrzEdges = int(edges.size());
+        if (F.nrzEdges) MGPS_TRY(devUpload(h, &F.rzEdges, edges));
+    }
+    return MGPS_OK;
+}
 // out (optional): where the coarse rhs goes instead of the coarse level's own rhs grid (mgps_residual_downsample)
 int residualRestrict(mgps_solver *h, int l, const float *x, const float *rhs, float *out = nullptr)
 {
     DevLevel &F = h->lv[l], &C = h->lv[l + 1];
     const bool xfold = residualRestrictXFolded(h, l);  // (the same answer at every call: the level's rz keeps its layout)
-    if (!F.rz) {
-        MGPS_TRY(devAlloc(h, &F.rz, xfold ? rzxFloats(F.g) : F.d.cells() / 2, true));
-        if (F.g.planeBlocks) {  // once: which blocks off the activity list sit below / above a listed one
-            if (!F.planeFlags) {
-                MGPS_TRY(devAlloc(h, &F.planeFlags, planeBlockCount(F.g), true));
-                MGPS_LAUNCH(h, launchPlaneBlockFlags(h->stream, F.g, F.planeFlags));
-            }
-            std::vector<uint8_t> flags(planeBlockCount(F.g));
-            MGPS_HIP(h, hipMemcpyAsync(flags.data(), F.planeFlags, flags.size(), hipMemcpyDeviceToHost, h->stream));
-            MGPS_HIP(h, hipStreamSynchronize(h->stream));
-            const std::vector<int32_t> edges = planeBlockEdges(F.g, flags);
-            F.nrzEdges = int(edges.size());
-            if (F.nrzEdges) MGPS_TRY(devUpload(h, &F.rzEdges, edges));
-        }
-    }
+    MGPS_TRY(ensureRz(h, l, xfold));
     {
         StageScope scope(h, ST_RESIDUAL, l);
         const bool cut = h->dist && (F.g.ghostLo || F.g.ghostHi);
@@ -1111,6 +1145,7 @@ int smoothStroke(mgps_solver *h, int l, float *&cur, float *&other, const float 
     case SF_FRONT: return frontStroke(h, l, cur, other, b, xZero);
     case SF_PROLONG_FUSED: return prolongFusedStroke(h, l, cur, other, b, coarse);
     case SF_FIRST_FUSED: return firstFusedStroke(h, l, cur, other, b, down, dot);
+    case SF_DOWN_FUSED:  // (never without fromGuess: fusedDownStroke)
     case SF_GENERIC: break;
     }
     {
@@ -1137,6 +1172,33 @@ int poisonSpares(mgps_solver *h, int l, float *a, float *b2)
     const float nan = std::numeric_limits<float>::quiet_NaN();
     MGPS_LAUNCH(h, launchScale(h->stream, h->lv[l].g, a, nan));
     MGPS_LAUNCH(h, launchScale(h->stream, h->lv[l].g, b2, nan));
+    return MGPS_OK;
+}
+
+// SF_DOWN_FUSED: the down-stroke of level l from the guess in `cur`, and the residual of its result restricted into the coarse
+// level's rhs (out: somewhere else, mgps_down_stroke).  The closure launch reads the un-smoothed iterate and the rhs and leaves the
+// snapshot; the plain launch reads the snapshot and the rhs alone, so it can come before the sweep: it writes the kept cells into
+// the spare grid, the march fills in the rest around them.  The march is booked under the residual stage: the sweep timer and
+// bench.py's roofline see the up-stroke's sweep launches alone.  MGPS_POISON_SPARES=1: the spare grid starts as NaN.
+int fusedDownStroke(mgps_solver *h, int l, float *&cur, float *&other, const float *b, float *out = nullptr)
+{
+    DevLevel &L = h->lv[l], &C = h->lv[l + 1];
+    MGPS_TRY(ensureKeptTiles(h, l));
+    MGPS_TRY(ensureRz(h, l, true));
+    if (!L.seamCols && downFusedColumnFloats(L.g) > 0) MGPS_TRY(devAlloc(h, &L.seamCols, downFusedColumnFloats(L.g), true));
+    MGPS_TRY(poisonSpares(h, l, other, other));
+    {
+        StageScope scope(h, ST_BAND, l);
+        MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, true, cur, b, nullptr, L.r, h->opt.jacobi_weight));
+        MGPS_LAUNCH(h, launchBandBox(h->stream, L.g, L.bandBoxes, false, L.r, b, other, nullptr, h->opt.jacobi_weight, false, MixScale{}, nullptr, nullptr, true));
+    }
+    {
+        StageScope scope(h, ST_RESIDUAL, l);
+        MGPS_LAUNCH(h, launchDownFused(h->stream, L.g, other, L.rz, cur, b, h->opt.jacobi_weight, L.rzEdges, L.nrzEdges, L.keepBits, L.keptT, L.seamCols));
+    }
+    std::swap(cur, other);
+    StageScope scope(h, ST_RESTRICT, l);
+    MGPS_LAUNCH(h, launchRestrictY(h->stream, C.g, out ? out : C.b, L.rz, L.g));
     return MGPS_OK;
 }
 
@@ -1200,7 +1262,8 @@ int downStrokeFromZero(mgps_solver *h, int l, float *&cur, float *&other, const 
 // rhs; on return x holds the level's result.  Level 0 (vcycle) comes with its down-stroke done; a coarser level starts from zero.
 // poll: options.interrupt is polled once per level and stroke (single-device fp32 cycles: the reference polls inside every
 // operator loop, e.g. Ops.h:319; slab runs poll between CG iterations only, where the ranks can agree)
-int cycleLevels(mgps_solver *h, int first, float *&x, float *spare, const float *b, bool poll)
+// restricted: level first's residual is restricted already (fusedDownStroke)
+int cycleLevels(mgps_solver *h, int first, float *&x, float *spare, const float *b, bool poll, bool restricted = false)
 {
     const int nlv = int(h->lv.size()), bottom = nlv - 1;
     std::vector<float *> cur(nlv, nullptr), other(nlv, nullptr);
@@ -1218,6 +1281,7 @@ int cycleLevels(mgps_solver *h, int first, float *&x, float *spare, const float 
             }
             MGPS_TRY(downStrokeFromZero(h, l, cur[l], other[l], rhsOf(l), true, false));
         }
+        if (l == first && restricted) continue;
         if (residualRestrictFuses(h, l)) {
             MGPS_TRY(residualRestrict(h, l, cur[l], rhsOf(l)));
             continue;
@@ -1264,9 +1328,11 @@ int vcycle(mgps_solver *h, float *x, const float *b, bool useInitialGuess, bool 
     // slab run), unless the whole hierarchy is a single level (MG.cpp:516-517)
     const bool hasBottom = nlv > 1;
     float *cur = x, *other = h->lv[0].tmp;
-    if (useInitialGuess) MGPS_TRY(smoothStroke(h, 0, cur, other, b, true, false, h->gatherDot && !hasBottom));
+    const bool fused = useInitialGuess && hasBottom && strokeForm(h, 0, true, cur, other, b, false, true) == SF_DOWN_FUSED;
+    if (fused) MGPS_TRY(fusedDownStroke(h, 0, cur, other, b));
+    else if (useInitialGuess) MGPS_TRY(smoothStroke(h, 0, cur, other, b, true, false, h->gatherDot && !hasBottom));
     else MGPS_TRY(downStrokeFromZero(h, 0, cur, other, b, ownGrid, h->gatherDot && !hasBottom));
-    if (hasBottom) MGPS_TRY(cycleLevels(h, 0, cur, other, b, !h->dist && !h->tailOfSlabRun));
+    if (hasBottom) MGPS_TRY(cycleLevels(h, 0, cur, other, b, !h->dist && !h->tailOfSlabRun, fused));
     if (cur != x)  // single-level Jacobi cycle: the iterate ended in the spare grid
         MGPS_HIP(h, hipMemcpyAsync(x, cur, h->lv[0].d.cells() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     if (h->gatherDot) MGPS_LAUNCH(h, launchFoldDot(h->stream, h->dotPartials, h->dotUsed, h->dotTarget ? h->dotTarget : h->resultDev));
@@ -4738,6 +4804,12 @@ try {
         return rc;
     }
     case 15: src = L.g.plainQ, n = L.g.plainQ ? (L.d.cells() / 4 + 31) / 32 : 0; break;  // (the canonical layout; empty: every code is loaded)
+    case 17:  // (launchDownFused's kept quads, GridP::plainT's layout; empty: the level's down-strokes do not take that form)
+        if (strokeForm(h, level, true, nullptr, nullptr, nullptr, false, true) == SF_DOWN_FUSED) {
+            MGPS_TRY(ensureKeptTiles(h, level));
+            src = L.keptT, n = keptTileWords(L.g), elem = 8;
+        } else src = nullptr, n = 0, elem = 8;
+        break;
     case 16: src = L.g.plainT, n = L.g.plainT ? size_t(L.d.ny) * L.d.nz * planeTiles(L.d.nx, L.d.ny, L.d.nz, 0).nbx : 0, elem = 8; break;  // (the marches' copy)
     default: return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_level_array: unknown array");
     }
@@ -4769,6 +4841,13 @@ int mgps_up_stroke_fused(const mgps_solver *h, int level, int *fused)
 try {
     if (!h || !fused || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
     *fused = strokeForm(h, level, false, nullptr, nullptr, nullptr, false) == SF_PROLONG_FUSED ? 1 : 0;  // (the cycle's own grids)
+    return MGPS_OK;
+}
+MGPS_API_CATCH(h)
+int mgps_down_stroke_fused(const mgps_solver *h, int level, int *fused)
+try {
+    if (!h || !fused || level < 0 || level >= int(h->lv.size())) return MGPS_ERR_INVALID_ARGUMENT;
+    *fused = strokeForm(h, level, true, nullptr, nullptr, nullptr, false, true) == SF_DOWN_FUSED ? 1 : 0;  // (the cycle's own grids, from a guess)
     return MGPS_OK;
 }
 MGPS_API_CATCH(h)
@@ -4981,6 +5060,25 @@ try {
     MGPS_TRY(applyOp(h, OP_RESIDUAL, fine_level, F.r, const_cast<float *>(x_dev), b_dev, true));
     MGPS_TRY(exchangeGhosts(h, fine_level, F.r));
     MGPS_LAUNCH(h, launchRestrict(h->stream, h->lv[fine_level + 1].g, coarse_dev, F.r));
+    return MGPS_OK;
+}
+MGPS_API_CATCH(h)
+
+int mgps_down_stroke(mgps_solver *h, int fine_level, float *x_dev, float *coarse_dev, const float *b_dev)
+try {
+    MGPS_TRY(checkLevel(h, fine_level + 1, "mgps_down_stroke"));
+    if (fine_level < 0 || !coarse_dev || !x_dev || !b_dev) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_down_stroke: bad arguments");
+    DevLevel &F = h->lv[fine_level];
+    if (h->dist || h->opt.precision != 0 || !F.tmp) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_down_stroke: single-device fp32 solvers only");
+    MGPS_LAUNCH(h, launchZero(h->stream, coarse_dev, h->lv[fine_level + 1].d.cells()));  // "destination cleared first" (Ops.h:756)
+    float *cur = x_dev, *other = F.tmp;
+    if (strokeForm(h, fine_level, true, cur, other, b_dev, false, true) == SF_DOWN_FUSED) MGPS_TRY(fusedDownStroke(h, fine_level, cur, other, b_dev, coarse_dev));
+    else {
+        MGPS_TRY(smoothStroke(h, fine_level, cur, other, b_dev, true, false));
+        if (!residualRestrictFuses(h, fine_level)) return failH(h, MGPS_ERR_INVALID_ARGUMENT, "mgps_down_stroke: the level does not take the residual pair");
+        MGPS_TRY(residualRestrict(h, fine_level, cur, b_dev, coarse_dev));
+    }
+    if (cur != x_dev) MGPS_HIP(h, hipMemcpyAsync(x_dev, cur, F.d.cells() * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     return MGPS_OK;
 }
 MGPS_API_CATCH(h)

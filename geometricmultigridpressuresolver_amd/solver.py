@@ -260,7 +260,7 @@ class GeometricMultigridPoissonSolver:
     LEVEL_ARRAYS = {"codes": (0, np.uint8), "band": (1, np.int32), "band_diag": (2, np.uint8), "rows": (3, np.float32), "chunks": (4, np.int32),
                     "plane_blocks": (5, np.int32), "pure_even": (6, np.int32), "pure_odd": (7, np.int32), "mixed_even": (8, np.int32),
                     "mixed_odd": (9, np.int32), "tile_bnd_start": (10, np.int32), "box_info": (11, np.int32), "box_list": (12, np.uint32),
-                    "box_general": (13, np.int32), "plain_quads": (15, np.uint32), "plain_tiles": (16, np.uint64)}
+                    "box_general": (13, np.int32), "plain_quads": (15, np.uint32), "plain_tiles": (16, np.uint64), "kept_tiles": (17, np.uint64)}
 
     def level_array(self, level, name):
         """mgps_level_array: one of the set-up arrays of a level as it sits on the device (tests / tools)."""
@@ -328,6 +328,10 @@ class GeometricMultigridPoissonSolver:
     def residualDownsample(self, destination, solution, rhs, fine_level=0):
         """mgps_residual_downsample: destination (level fine_level + 1) = downsample(rhs - A solution) as a down-stroke forms it"""
         check(lib().mgps_residual_downsample(self.h, fine_level, self._g(destination, fine_level + 1), self._g(solution, fine_level), self._g(rhs, fine_level)), self.h)
+
+    def downStroke(self, solution, destination, rhs, fine_level=0):
+        """mgps_down_stroke: one down-stroke on `solution` (in place) and destination (level fine_level + 1) = downsample(rhs - A solution')"""
+        check(lib().mgps_down_stroke(self.h, fine_level, self._g(solution, fine_level), self._g(destination, fine_level + 1), self._g(rhs, fine_level)), self.h)
 
     def upsampleAndAdd(self, destination, source, fine_level=0):
         check(lib().mgps_upsample_add(self.h, fine_level, self._g(destination, fine_level), self._g(source, fine_level + 1)), self.h)
@@ -466,6 +470,12 @@ class GeometricMultigridPoissonSolver:
         """mgps_up_stroke_fused: does an up-stroke of this level run the prolongation inside its Jacobi sweep?"""
         f = C.c_int()
         check(lib().mgps_up_stroke_fused(self.h, int(level), C.byref(f)), self.h)
+        return bool(f.value)
+
+    def down_stroke_fused(self, level=0):
+        """mgps_down_stroke_fused: does a down-stroke of this level from an initial guess run its sweep inside the residual march?"""
+        f = C.c_int()
+        check(lib().mgps_down_stroke_fused(self.h, int(level), C.byref(f)), self.h)
         return bool(f.value)
 
     def stencil_kernel(self, level=0):

@@ -338,6 +338,11 @@ int mgps_downsample(mgps_solver *h, int fine_level, float *coarse_dev, const flo
  * mgps_residual_restrict_fused says so -- as the pair that folds the residual along z while it is formed and restricts in x-y
  * from there, without writing the residual.  coarse_dev: a grid of level fine_level + 1 (cleared first, Ops.h:756). */
 int mgps_residual_downsample(mgps_solver *h, int fine_level, float *coarse_dev, const float *x_dev, const float *b_dev);
+/* One down-stroke of level fine_level from the guess in x_dev, then coarse = downsample(b - A x') of its result, in the form a
+ * V-cycle with an initial guess picks for the level (mgps_down_stroke_fused): x_dev receives x', coarse_dev (a grid of level
+ * fine_level + 1, cleared first) the coarse rhs.  Single-device fp32 solvers, levels that take the residual pair
+ * (mgps_residual_restrict_fused). */
+int mgps_down_stroke(mgps_solver *h, int fine_level, float *x_dev, float *coarse_dev, const float *b_dev);
 
 /* upsampleAndAdd (Ops.h:873-972): fine (level) += 4 * Trilerp(coarse (level+1)) */
 int mgps_upsample_add(mgps_solver *h, int fine_level, float *fine_dev, const float *coarse_dev);
@@ -559,6 +564,14 @@ int mgps_residual_restrict_xfolded(const mgps_solver *h, int level, int *xfolded
  * off / onto every level where it is valid (tests).  The stroke that gathers <z, r> for MG-PCG keeps the separate pass on level 0.
  * The same bits either way. */
 int mgps_up_stroke_fused(const mgps_solver *h, int level, int *fused);
+/* *fused = 1 when a down-stroke of level `level` from an initial guess runs its Jacobi sweep inside the x-folded residual march
+ * (closure launch, plain launch into the spare grid, one march for x' and the folded residual of x', a fix-up for the terms across
+ * the tiles' rims, y restriction), 0 when sweep and residual are passes of their own.  By size (x-y planes >= 4 MiB) on
+ * single-device fp32 Jacobi levels that take the three-launch stroke and the x-folded residual pair and kept their plane blocks,
+ * one pre-sweep; MGPS_FUSE_DOWN=0 / 1 forces it off / onto every level where it is valid (tests).  Strokes that start from zero
+ * and the stroke that gathers <z, r> keep their forms.  x' has the same bits either way; the coarse rhs differs in its last bits
+ * (the rim terms are added after the folds).  mgps_level_array index 17: the march's kept-quad words. */
+int mgps_down_stroke_fused(const mgps_solver *h, int level, int *fused);
 /* kept for callers of round 4's ABI: always 0.  Round 4 queued the ghost exchanges that follow a sweep on a second stream beside
  * the sweep's interior part; round 5 runs every exchange on the solver's stream until a first run on real links has shown
  * where the time goes. */
