@@ -35,3 +35,6 @@ def trim_device_cache():
 from .fields import (  # noqa: E402,F401
     ParticlesBinDesc, ParticlesToGridDesc, ParticlesUpdateDesc, binParticles, particlesToGrid, seedParticles, updateParticles,
 )
+from .fields import (  # noqa: E402,F401
+    ParticlesCollideDesc, ParticlesResampleDesc, collideParticles, resampleParticles, updateParticlesSolid,
+)

@@ -119,6 +119,12 @@ def lib():
         for entry in (L.mgps_particles_bin, L.mgps_particles_to_grid, L.mgps_particles_update):
             entry.argtypes = [C.c_void_p, C.c_void_p]
             entry.restype = C.c_int
+        # ... next to solids: collide and resample alike; the fused update takes the update's desc, the collide desc, the stream
+        for entry in (L.mgps_particles_collide, L.mgps_particles_resample):
+            entry.argtypes = [C.c_void_p, C.c_void_p]
+            entry.restype = C.c_int
+        L.mgps_particles_update_solid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mgps_particles_update_solid.restype = C.c_int
         _lib = L
     return _lib
 

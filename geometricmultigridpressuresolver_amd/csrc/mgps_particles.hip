@@ -11,10 +11,16 @@
 // states the same operations in numpy, has the same bits.
 // update: one thread per particle; the grids are sampled with mgps_sample.h's rule, which advection shares and which pins its own
 // contraction; the trace's fused multiply-adds are written out.
+// collide: the push-out rule of the header, one device function that the standalone kernel applies to the
+// arrays and the update applies to its own float32 results in registers -- updateKernel is written once, over its argument type.
+// resample: a count per cell, rocprim's exclusive scan into cell_start_out, a copy per input slot (its cell from its position, its
+// rank from the stride rule in closed form) and a seeding kernel over (cell, q); stream order, temporary storage from the pool.
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "mgps_sample.h"
 #include "mgps_tile_pass.h"
@@ -414,25 +420,95 @@ struct UpdateArgs {
     unsigned long long *counts;
 };
 
-// U(p) of three face grids of the whole grid
-__device__ __forceinline__ void velocityAt(const UpdateArgs &a, const float *const grid[3], const double p[3], double u[3])
+// S(p) of a whole grid of `kind` (0 cells, 1 + a the faces of axis a)
+__device__ __forceinline__ double sampleAt(int gx, int gy, int gz, int kind, const float *grid, double px, double py, double pz)
 {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const Lattice L = latticeOf(a.gx, a.gy, a.gz, 0, a.gz, 0, 0, c + 1);
-        const Stencil s = stencilAt(L, p[0], p[1], p[2]);
-        double lo, hi;
-        u[c] = sampleHeld(HeldPlanes{grid[c], nullptr, nullptr}, L, s, lo, hi);
-    }
+    const Lattice L = latticeOf(gx, gy, gz, 0, gz, 0, 0, kind);
+    const Stencil s = stencilAt(L, px, py, pz);
+    double lo, hi;
+    return sampleHeld(HeldPlanes{grid, nullptr, nullptr}, L, s, lo, hi);
 }
 
-__global__ __launch_bounds__(kFlat) void updateKernel(UpdateArgs a)
+// U(p) of three face grids of the whole grid
+template <class Box>
+__device__ __forceinline__ void velocityAt(const Box &a, const float *const grid[3], const double p[3], double u[3])
 {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) u[c] = sampleAt(a.gx, a.gy, a.gz, c + 1, grid[c], p[0], p[1], p[2]);
+}
+
+// ---- collision with solids: the rule (include/mgps_fields.h, "4. mgps_particles_collide") ----------------------------------------
+struct SolidArgs {
+    int gx, gy, gz, iterations;
+    double margin, friction;
+    const float *phi;
+    const float *sv[3];  // sv[0] == nullptr: the solid is at rest
+    unsigned long long *counts;
+};
+
+// the rule on one particle's float32 position and velocity, in place; found: [0] pushed, [1] still inside the solid, [2] stuck
+__device__ __forceinline__ void collideRule(const SolidArgs &s, float (&xf)[3], float (&vf)[3], unsigned int (&found)[3])
+{
+    if (!insideBox(xf[0], xf[1], xf[2], s.gx, s.gy, s.gz)) return;
+    const double box[3] = {double(s.gx), double(s.gy), double(s.gz)};
+    double x[3] = {double(xf[0]), double(xf[1]), double(xf[2])}, n[3] = {0.0, 0.0, 0.0};
+    bool pushed = false;
+    for (int it = 0; it < s.iterations; ++it) {
+        const double phi = sampleAt(s.gx, s.gy, s.gz, 0, s.phi, x[0], x[1], x[2]);
+        if (phi >= s.margin) break;
+        const double g[3] = {sampleAt(s.gx, s.gy, s.gz, 0, s.phi, x[0] + 0.5, x[1], x[2]) - sampleAt(s.gx, s.gy, s.gz, 0, s.phi, x[0] - 0.5, x[1], x[2]),
+                             sampleAt(s.gx, s.gy, s.gz, 0, s.phi, x[0], x[1] + 0.5, x[2]) - sampleAt(s.gx, s.gy, s.gz, 0, s.phi, x[0], x[1] - 0.5, x[2]),
+                             sampleAt(s.gx, s.gy, s.gz, 0, s.phi, x[0], x[1], x[2] + 0.5) - sampleAt(s.gx, s.gy, s.gz, 0, s.phi, x[0], x[1], x[2] - 0.5)};
+        const double m = (g[0] * g[0] + g[1] * g[1]) + g[2] * g[2];
+        if (!(m > 1e-12)) {  // (NaN as well)
+            found[2] = 1;
+            break;
+        }
+        const double length = sqrt(m), push = s.margin - phi;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            n[c] = g[c] / length;
+            x[c] = fmin(fmax(fma(push, n[c], x[c]), 0.0), box[c]);
+        }
+        pushed = true;
+    }
+    if (!pushed) return;
+    found[0] = 1;
+    double us[3] = {0.0, 0.0, 0.0}, r[3];
+    if (s.sv[0]) velocityAt(s, s.sv, x, us);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = double(vf[c]) - us[c];
+    const double vn = (r[0] * n[0] + r[1] * n[1]) + r[2] * n[2];
+    if (vn < 0.0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            r[c] = r[c] - vn * n[c];
+            r[c] = (1.0 - s.friction) * r[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) vf[c] = float(r[c] + us[c]), xf[c] = float(x[c]);
+    if (sampleAt(s.gx, s.gy, s.gz, 0, s.phi, double(xf[0]), double(xf[1]), double(xf[2])) < 0.0) found[1] = 1;
+}
+
+// the update's arguments with a solid: the fused form
+struct UpdateSolidArgs : UpdateArgs {
+    SolidArgs solid;
+};
+
+// Args: UpdateArgs, or UpdateSolidArgs -- the collision rule then runs on the float32 results before they are stored
+template <class Args>
+__global__ __launch_bounds__(kFlat) void updateKernel(Args a)
+{
+    constexpr bool kSolids = std::is_same_v<Args, UpdateSolidArgs>;
     __shared__ unsigned int tally[2];
+    __shared__ unsigned int hits[3];
     zeroTally(tally);
+    if constexpr (kSolids) zeroTally(hits);
     __syncthreads();
     const long long p = (long long)blockIdx.x * kFlat + int(threadIdx.x);
     unsigned int found[2] = {0, 0};
+    [[maybe_unused]] unsigned int hit[3] = {0, 0, 0};
     if (p < a.n) {
         const float xf[3] = {a.pin[0][p], a.pin[1][p], a.pin[2][p]}, vf[3] = {a.vin[0][p], a.vin[1][p], a.vin[2][p]};
         float xo[3] = {xf[0], xf[1], xf[2]}, vo[3] = {vf[0], vf[1], vf[2]};
@@ -468,10 +544,219 @@ __global__ __launch_bounds__(kFlat) void updateKernel(UpdateArgs a)
         } else {
             found[1] = 1;
         }
+        if constexpr (kSolids) collideRule(a.solid, xo, vo, hit);
 #pragma unroll
         for (int c = 0; c < 3; ++c) a.pout[c][p] = xo[c], a.vout[c][p] = vo[c];
     }
     if (a.counts) addTally(tally, found, a.counts);
+    if constexpr (kSolids) {
+        if (a.solid.counts) addTally(hits, hit, a.solid.counts);
+    }
+}
+
+// ---- collision with solids: the standalone pass ------------------------------------------------------------------------------------
+struct CollideArgs {
+    int n;
+    const float *pin[3], *vin[3];
+    float *pout[3], *vout[3];
+    SolidArgs solid;
+};
+
+__global__ __launch_bounds__(kFlat) void collideKernel(CollideArgs a)
+{
+    __shared__ unsigned int hits[3];
+    zeroTally(hits);
+    __syncthreads();
+    const long long p = (long long)blockIdx.x * kFlat + int(threadIdx.x);
+    unsigned int hit[3] = {0, 0, 0};
+    if (p < a.n) {
+        float x[3] = {a.pin[0][p], a.pin[1][p], a.pin[2][p]}, v[3] = {a.vin[0][p], a.vin[1][p], a.vin[2][p]};
+        collideRule(a.solid, x, v, hit);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.pout[c][p] = x[c], a.vout[c][p] = v[c];
+    }
+    if (a.solid.counts) addTally(hits, hit, a.solid.counts);
+}
+
+// ---- resample: thin crowded cells, seed deep ones -----------------------------------------------------------------------------------
+struct ResampleArgs {
+    int gx, gy, gz, n, cells, capacity, minPer, maxPer, keepOutside;
+    uint32_t seed;
+    float deepBelow;  // -float(seed_depth dx)
+    const float *pos[3], *vel[3];
+    const int32_t *cellStart;
+    const float *liquidPhi, *solidPhi, *grid[3];
+    float *pout[3], *vout[3];
+    int32_t *cellStartOut, *nOut;
+    unsigned long long *counts;
+};
+
+// bin c (a cell, or `cells`: the outside bin): its first slot and its slots m, as slotsOf clamps them, the slots it keeps and the
+// particles it is given
+struct CellPlan {
+    int first, m, kept, seeds;
+    bool deep;
+};
+__device__ __forceinline__ CellPlan planOf(const ResampleArgs &a, int c)
+{
+    CellPlan p;
+    p.first = min(max(a.cellStart[c], 0), a.n);
+    p.m = max(min(max(a.cellStart[c + 1], 0), a.n) - p.first, 0);
+    p.deep = false, p.seeds = 0;
+    if (c == a.cells) {
+        p.kept = a.keepOutside ? p.m : 0;
+        return p;
+    }
+    p.kept = min(p.m, a.maxPer);
+    p.deep = a.liquidPhi && a.liquidPhi[c] <= a.deepBelow && (!a.solidPhi || a.solidPhi[c] > 0.0f);
+    if (p.deep && p.kept < a.minPer) p.seeds = a.minPer - p.kept;
+    return p;
+}
+
+__global__ __launch_bounds__(kFlat) void resampleCountKernel(ResampleArgs a, int32_t *count)
+{
+    __shared__ unsigned int tally[3];
+    zeroTally(tally);
+    __syncthreads();
+    const long long c = (long long)blockIdx.x * kFlat + int(threadIdx.x);
+    unsigned int found[3] = {0, 0, 0};
+    if (c <= a.cells) {
+        const CellPlan p = planOf(a, int(c));
+        count[c] = p.kept + p.seeds;
+        if (c < a.cells) found[0] = unsigned(p.m - p.kept), found[1] = unsigned(p.seeds), found[2] = p.deep;
+    } else if (c == (long long)a.cells + 1) {
+        count[c] = 0;
+    }
+    if (a.counts) addTally(tally, found, a.counts);
+}
+
+// one thread per input slot (and at least one: thread 0 publishes the total)
+__global__ __launch_bounds__(kFlat) void resampleCopyKernel(ResampleArgs a)
+{
+    const long long s = (long long)blockIdx.x * kFlat + int(threadIdx.x);
+    if (s == 0) {
+        const int total = a.cellStartOut[a.cells + 1];
+        *a.nOut = total;
+        if (total > a.capacity && a.counts) atomicAdd(a.counts + 3, 1ull);
+    }
+    if (s >= a.n) return;
+    const float x = a.pos[0][s], y = a.pos[1][s], z = a.pos[2][s];
+    int c = a.cells;
+    if (insideBox(x, y, z, a.gx, a.gy, a.gz)) {
+        const int i = min(int(floorf(x)), a.gx - 1), j = min(int(floorf(y)), a.gy - 1), k = min(int(floorf(z)), a.gz - 1);
+        c = (k * a.gy + j) * a.gx + i;
+    }
+    const CellPlan p = planOf(a, c);
+    const long long t = s - p.first;
+    if (t < 0 || t >= p.m) return;  // (a wrong cell_start: the slot is not one of its cell's)
+    long long rank = t;
+    if (c == a.cells) {
+        if (!a.keepOutside) return;
+    } else if (p.m > a.maxPer) {
+        rank = t * a.maxPer / p.m;
+        if ((t + 1) * a.maxPer / p.m == rank) return;
+    }
+    const long long to = (long long)a.cellStartOut[c] + rank;
+    if (to < 0 || to >= a.capacity) return;
+    a.pout[0][to] = x, a.pout[1][to] = y, a.pout[2][to] = z;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) a.vout[q][to] = a.vel[q][s];
+}
+
+__device__ __forceinline__ uint32_t mix(uint32_t x)
+{
+    x ^= x >> 16, x *= 0x7feb352du, x ^= x >> 15, x *= 0x846ca68bu, x ^= x >> 16;
+    return x;
+}
+
+// one thread per (cell, q), q = 0 .. min_per_cell - 1
+__global__ __launch_bounds__(kFlat) void resampleSeedKernel(ResampleArgs a)
+{
+    const long long at = (long long)blockIdx.x * kFlat + int(threadIdx.x);
+    if (at >= (long long)a.cells * a.minPer) return;
+    const int c = int(at / a.minPer), q = int(at % a.minPer);
+    const CellPlan p = planOf(a, c);
+    if (q >= p.seeds) return;
+    const long long to = (long long)a.cellStartOut[c] + p.kept + q;
+    if (to < 0 || to >= a.capacity) return;
+    const int cell[3] = {c % a.gx, c / a.gx % a.gy, c / a.gx / a.gy};
+    const uint32_t base = mix(mix(a.seed ^ 0x9e3779b9u) + uint32_t(c));
+    float xf[3];
+    double x[3], u[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const uint32_t h = mix(base + uint32_t(3 * (p.kept + q) + ax));
+        const double r = double(h >> 8) * 0x1p-24;
+        const float top = __uint_as_float(__float_as_uint(float(cell[ax] + 1)) - 1u);  // the float32 just below i + 1
+        xf[ax] = fminf(float(double(cell[ax]) + r), top);
+        x[ax] = double(xf[ax]);
+    }
+    velocityAt(a, a.grid, x, u);
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) a.pout[ax][to] = xf[ax], a.vout[ax][to] = float(u[ax]);
+}
+
+// ---- what the per-particle entries refuse, stated once ------------------------------------------------------------------------------
+// the arrays of component c of a per-particle pass: an output that is exactly its input is one array, written in place; any other
+// output overlaps nothing
+int particleArrays(const char *fn, ArrayRanges &arrays, int c, int n, const float *pin, const float *vin, float *pout, float *vout)
+{
+    const size_t bytes = size_t(n) * sizeof(float);
+    const float *in[2] = {pin, vin};
+    float *out[2] = {pout, vout};
+    const char *names[2][2] = {{"position_in", "position_out"}, {"velocity_in", "velocity_out"}};
+    for (int q = 0; q < 2; ++q) {
+        if (!in[q]) return refuse(fn, indexed(names[q][0], c) + " is NULL");
+        if (!out[q]) return refuse(fn, indexed(names[q][1], c) + " is NULL");
+        arrays.add(indexed(names[q][0], c), in[q], bytes, in[q] == out[q]);
+        if (in[q] != out[q]) arrays.add(indexed(names[q][1], c), out[q], bytes, true);
+    }
+    return MGPS_OK;
+}
+
+// the update desc: refusals, the arrays' ranges, the kernel's arguments
+int updateArgs(const char *fn, const mgps_particles_update_desc *d, ArrayRanges &arrays, UpdateArgs &a)
+{
+    if (!d || d->struct_size != int(sizeof(mgps_particles_update_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_particles_update_desc)");
+    if (int rc = checkParticleGrid(fn, d->gx, d->gy, d->gz, d->n); rc != MGPS_OK) return rc;
+    if (d->trace_order != 1 && d->trace_order != 2) return refuse(fn, "trace_order = " + std::to_string(d->trace_order) + " is neither 1 nor 2");
+    if (!std::isfinite(d->dt)) return refuse(fn, "dt is not finite");
+    if (!(d->flip >= 0.0 && d->flip <= 1.0)) return refuse(fn, "flip is outside [0, 1]");
+    int olds = 0;
+    if (int rc = allOrNone(fn, reinterpret_cast<const void *const *>(d->grid_old), "grid_old", olds); rc != MGPS_OK) return rc;
+    if (olds == 0 && d->flip > 0.0) return refuse(fn, "grid_old is NULL with flip > 0: the FLIP part needs the velocity before forces and projection");
+    a.gx = d->gx, a.gy = d->gy, a.gz = d->gz, a.n = d->n, a.order = d->trace_order, a.dt = d->dt, a.flip = d->flip, a.counts = d->counts_dev;
+    for (int c = 0; c < 3; ++c) {
+        if (!d->grid_new[c]) return refuse(fn, indexed("grid_new", c) + " is NULL");
+        const size_t faces = faceElems(d->gx, d->gy, d->gz, c) * sizeof(float);
+        arrays.add(indexed("grid_new", c), d->grid_new[c], faces, false);
+        if (olds) arrays.add(indexed("grid_old", c), d->grid_old[c], faces, false);
+        a.gnew[c] = d->grid_new[c], a.gold[c] = d->grid_old[c];
+        if (d->n == 0) continue;
+        if (int rc = particleArrays(fn, arrays, c, d->n, d->position_in[c], d->velocity_in[c], d->position_out[c], d->velocity_out[c]); rc != MGPS_OK) return rc;
+        a.pin[c] = d->position_in[c], a.vin[c] = d->velocity_in[c], a.pout[c] = d->position_out[c], a.vout[c] = d->velocity_out[c];
+    }
+    return MGPS_OK;
+}
+
+// the collide desc without its particle arrays: refusals, the grids' ranges, the rule's arguments
+int solidArgs(const char *fn, const mgps_particles_collide_desc *d, ArrayRanges &arrays, SolidArgs &s)
+{
+    if (!d || d->struct_size != int(sizeof(mgps_particles_collide_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_particles_collide_desc)");
+    if (int rc = checkParticleGrid(fn, d->gx, d->gy, d->gz, 0); rc != MGPS_OK) return rc;
+    if (!(std::isfinite(d->margin) && d->margin >= 0.0)) return refuse(fn, "margin is not finite and >= 0");
+    if (d->iterations < 1 || d->iterations > 4) return refuse(fn, "iterations = " + std::to_string(d->iterations) + " is outside 1 .. 4");
+    if (!(d->friction >= 0.0 && d->friction <= 1.0)) return refuse(fn, "friction is outside [0, 1]");
+    if (!d->solid_phi) return refuse(fn, "solid_phi is NULL");
+    int moving = 0;
+    if (int rc = allOrNone(fn, reinterpret_cast<const void *const *>(d->solid_velocity), "solid_velocity", moving); rc != MGPS_OK) return rc;
+    arrays.add("solid_phi", d->solid_phi, size_t(d->gx) * size_t(d->gy) * size_t(d->gz) * sizeof(float), false);
+    for (int c = 0; c < 3 && moving; ++c) arrays.add(indexed("solid_velocity", c), d->solid_velocity[c], faceElems(d->gx, d->gy, d->gz, c) * sizeof(float), false);
+    if (d->counts_dev) arrays.add("counts_dev (collide)", d->counts_dev, 3 * sizeof(unsigned long long), true);
+    s.gx = d->gx, s.gy = d->gy, s.gz = d->gz, s.iterations = d->iterations, s.margin = d->margin, s.friction = d->friction;
+    s.phi = d->solid_phi, s.counts = d->counts_dev;
+    for (int c = 0; c < 3; ++c) s.sv[c] = d->solid_velocity[c];
+    return MGPS_OK;
 }
 
 }  // namespace
@@ -587,41 +872,125 @@ MGPS_API_CATCH(nullptr)
 int mgps_particles_update(const mgps_particles_update_desc *d, void *stream)
 try {
     const char *fn = "mgps_particles_update";
-    if (!d || d->struct_size != int(sizeof(mgps_particles_update_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_particles_update_desc)");
-    if (int rc = checkParticleGrid(fn, d->gx, d->gy, d->gz, d->n); rc != MGPS_OK) return rc;
-    if (d->trace_order != 1 && d->trace_order != 2) return refuse(fn, "trace_order = " + std::to_string(d->trace_order) + " is neither 1 nor 2");
-    if (!std::isfinite(d->dt)) return refuse(fn, "dt is not finite");
-    if (!(d->flip >= 0.0 && d->flip <= 1.0)) return refuse(fn, "flip is outside [0, 1]");
-    int olds = 0;
-    if (int rc = allOrNone(fn, reinterpret_cast<const void *const *>(d->grid_old), "grid_old", olds); rc != MGPS_OK) return rc;
-    if (olds == 0 && d->flip > 0.0) return refuse(fn, "grid_old is NULL with flip > 0: the FLIP part needs the velocity before forces and projection");
-    const size_t bytes = size_t(d->n) * sizeof(float);
     ArrayRanges arrays;
     UpdateArgs a{};
-    a.gx = d->gx, a.gy = d->gy, a.gz = d->gz, a.n = d->n, a.order = d->trace_order, a.dt = d->dt, a.flip = d->flip, a.counts = d->counts_dev;
-    for (int c = 0; c < 3; ++c) {
-        if (!d->grid_new[c]) return refuse(fn, indexed("grid_new", c) + " is NULL");
-        const size_t faces = faceElems(d->gx, d->gy, d->gz, c) * sizeof(float);
-        arrays.add(indexed("grid_new", c), d->grid_new[c], faces, false);
-        if (olds) arrays.add(indexed("grid_old", c), d->grid_old[c], faces, false);
-        a.gnew[c] = d->grid_new[c], a.gold[c] = d->grid_old[c];
-        if (d->n == 0) continue;
-        // an output that is exactly its input is one array, written in place; any other output overlaps nothing
-        const float *in[2] = {d->position_in[c], d->velocity_in[c]};
-        float *out[2] = {d->position_out[c], d->velocity_out[c]};
-        const char *names[2][2] = {{"position_in", "position_out"}, {"velocity_in", "velocity_out"}};
-        for (int q = 0; q < 2; ++q) {
-            if (!in[q]) return refuse(fn, indexed(names[q][0], c) + " is NULL");
-            if (!out[q]) return refuse(fn, indexed(names[q][1], c) + " is NULL");
-            arrays.add(indexed(names[q][0], c), in[q], bytes, in[q] == out[q]);
-            if (in[q] != out[q]) arrays.add(indexed(names[q][1], c), out[q], bytes, true);
-        }
-        a.pin[c] = in[0], a.vin[c] = in[1], a.pout[c] = out[0], a.vout[c] = out[1];
-    }
+    if (int rc = updateArgs(fn, d, arrays, a); rc != MGPS_OK) return rc;
     if (int rc = arrays.refuseOverlap(fn); rc != MGPS_OK) return rc;
     if (d->n == 0) return MGPS_OK;
     updateKernel<<<flatBlocks(size_t(d->n)), kFlat, 0, static_cast<hipStream_t>(stream)>>>(a);
     return hipStatus(fn, hipGetLastError());
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_particles_collide(const mgps_particles_collide_desc *d, void *stream)
+try {
+    const char *fn = "mgps_particles_collide";
+    ArrayRanges arrays;
+    CollideArgs a{};
+    if (int rc = solidArgs(fn, d, arrays, a.solid); rc != MGPS_OK) return rc;
+    if (d->n < 0) return refuse(fn, "n = " + std::to_string(d->n) + " is negative");
+    a.n = d->n;
+    for (int c = 0; c < 3 && d->n > 0; ++c) {
+        if (int rc = particleArrays(fn, arrays, c, d->n, d->position_in[c], d->velocity_in[c], d->position_out[c], d->velocity_out[c]); rc != MGPS_OK) return rc;
+        a.pin[c] = d->position_in[c], a.vin[c] = d->velocity_in[c], a.pout[c] = d->position_out[c], a.vout[c] = d->velocity_out[c];
+    }
+    if (int rc = arrays.refuseOverlap(fn); rc != MGPS_OK) return rc;
+    if (d->n == 0) return MGPS_OK;
+    collideKernel<<<flatBlocks(size_t(d->n)), kFlat, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return hipStatus(fn, hipGetLastError());
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_particles_update_solid(const mgps_particles_update_desc *d, const mgps_particles_collide_desc *solid, void *stream)
+try {
+    const char *fn = "mgps_particles_update_solid";
+    ArrayRanges arrays;
+    UpdateSolidArgs a{};
+    if (int rc = updateArgs(fn, d, arrays, a); rc != MGPS_OK) return rc;
+    if (int rc = solidArgs(fn, solid, arrays, a.solid); rc != MGPS_OK) return rc;
+    if (solid->gx != d->gx || solid->gy != d->gy || solid->gz != d->gz) return refuse(fn, "the two descs are not of one grid (gx, gy, gz differ)");
+    if (int rc = arrays.refuseOverlap(fn); rc != MGPS_OK) return rc;
+    if (d->n == 0) return MGPS_OK;
+    updateKernel<<<flatBlocks(size_t(d->n)), kFlat, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return hipStatus(fn, hipGetLastError());
+}
+MGPS_API_CATCH(nullptr)
+
+int mgps_particles_resample(const mgps_particles_resample_desc *d, void *stream)
+try {
+    const char *fn = "mgps_particles_resample";
+    if (!d || d->struct_size != int(sizeof(mgps_particles_resample_desc))) return refuse(fn, "NULL or struct_size mismatch (mgps_particles_resample_desc)");
+    if (int rc = checkParticleGrid(fn, d->gx, d->gy, d->gz, d->n); rc != MGPS_OK) return rc;
+    if (d->capacity < 0) return refuse(fn, "capacity = " + std::to_string(d->capacity) + " is negative");
+    if (d->max_per_cell < 1 || d->max_per_cell > 64) return refuse(fn, "max_per_cell = " + std::to_string(d->max_per_cell) + " is outside 1 .. 64");
+    if (d->min_per_cell < 0 || d->min_per_cell > d->max_per_cell)
+        return refuse(fn, "min_per_cell = " + std::to_string(d->min_per_cell) + " is outside 0 .. max_per_cell");
+    if (d->keep_outside != 0 && d->keep_outside != 1) return refuse(fn, "keep_outside = " + std::to_string(d->keep_outside) + " is neither 0 nor 1");
+    if (!(std::isfinite(d->dx) && d->dx > 0.0)) return refuse(fn, "dx is not finite and > 0");
+    if (!(std::isfinite(d->seed_depth) && d->seed_depth >= 0.0)) return refuse(fn, "seed_depth is not finite and >= 0");
+    const long long cells = (long long)d->gx * d->gy * d->gz;
+    if (d->n + cells * d->min_per_cell >= (1LL << 31)) return refuse(fn, "the total can pass int32: n + gx gy gz min_per_cell must be < 2^31");
+    int grids = 0;
+    if (int rc = allOrNone(fn, reinterpret_cast<const void *const *>(d->grid), "grid", grids); rc != MGPS_OK) return rc;
+    if (d->min_per_cell > 0 && !d->liquid_phi) return refuse(fn, "liquid_phi is NULL with min_per_cell > 0: seeding needs the deep cells");
+    if (d->min_per_cell > 0 && grids == 0) return refuse(fn, "grid is NULL with min_per_cell > 0: seeded particles take their velocity from it");
+    const size_t bytes = size_t(d->n) * sizeof(float), outBytes = size_t(d->capacity) * sizeof(float);
+    ArrayRanges arrays;
+    ResampleArgs a{};
+    a.gx = d->gx, a.gy = d->gy, a.gz = d->gz, a.n = d->n, a.cells = int(cells), a.capacity = d->capacity, a.minPer = d->min_per_cell;
+    a.maxPer = d->max_per_cell, a.keepOutside = d->keep_outside, a.seed = d->seed, a.deepBelow = -float(d->seed_depth * d->dx), a.counts = d->counts_dev;
+    for (int c = 0; c < 3; ++c) {
+        if (d->n > 0) {
+            if (!d->position[c]) return refuse(fn, indexed("position", c) + " is NULL");
+            if (!d->velocity[c]) return refuse(fn, indexed("velocity", c) + " is NULL");
+            arrays.add(indexed("position", c), d->position[c], bytes, false);
+            arrays.add(indexed("velocity", c), d->velocity[c], bytes, false);
+        }
+        if (d->capacity > 0) {
+            if (!d->position_out[c]) return refuse(fn, indexed("position_out", c) + " is NULL");
+            if (!d->velocity_out[c]) return refuse(fn, indexed("velocity_out", c) + " is NULL");
+            arrays.add(indexed("position_out", c), d->position_out[c], outBytes, true);
+            arrays.add(indexed("velocity_out", c), d->velocity_out[c], outBytes, true);
+        }
+        if (grids) arrays.add(indexed("grid", c), d->grid[c], faceElems(d->gx, d->gy, d->gz, c) * sizeof(float), false);
+        a.pos[c] = d->position[c], a.vel[c] = d->velocity[c], a.pout[c] = d->position_out[c], a.vout[c] = d->velocity_out[c], a.grid[c] = d->grid[c];
+    }
+    if (!d->cell_start) return refuse(fn, "cell_start is NULL");
+    if (!d->cell_start_out) return refuse(fn, "cell_start_out is NULL");
+    if (!d->n_out_dev) return refuse(fn, "n_out_dev is NULL");
+    arrays.add("cell_start", d->cell_start, (size_t(cells) + 2) * sizeof(int32_t), false);
+    arrays.add("cell_start_out", d->cell_start_out, (size_t(cells) + 2) * sizeof(int32_t), true);
+    arrays.add("n_out_dev", d->n_out_dev, sizeof(int32_t), true);
+    if (d->liquid_phi) arrays.add("liquid_phi", d->liquid_phi, size_t(cells) * sizeof(float), false);
+    if (d->solid_phi) arrays.add("solid_phi", d->solid_phi, size_t(cells) * sizeof(float), false);
+    if (d->counts_dev) arrays.add("counts_dev", d->counts_dev, 4 * sizeof(unsigned long long), true);
+    if (int rc = arrays.refuseOverlap(fn); rc != MGPS_OK) return rc;
+    a.cellStart = d->cell_start, a.cellStartOut = d->cell_start_out, a.nOut = d->n_out_dev, a.liquidPhi = d->liquid_phi, a.solidPhi = d->solid_phi;
+
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t bins = size_t(cells) + 2;
+    size_t scanBytes = 0;
+    int32_t *none = nullptr;
+    if (int rc = hipStatus(fn, rocprim::exclusive_scan(nullptr, scanBytes, none, none, int32_t(0), bins, rocprim::plus<int32_t>(), st)); rc != MGPS_OK) return rc;
+    // one block of the stream's pool: the bins' counts and the scan's own storage
+    const size_t ints = (bins * sizeof(int32_t) + 255) / 256 * 256;
+    void *block = nullptr;
+    if (int rc = streamAlloc(fn, st, ints + std::max<size_t>(scanBytes, 256), &block); rc != MGPS_OK) return rc;
+    int32_t *count = static_cast<int32_t *>(block);
+    void *scanTemp = count + ints / sizeof(int32_t);
+    resampleCountKernel<<<flatBlocks(bins), kFlat, 0, st>>>(a, count);
+    int rc = hipStatus(fn, hipGetLastError());
+    if (rc == MGPS_OK) rc = hipStatus(fn, rocprim::exclusive_scan(scanTemp, scanBytes, count, a.cellStartOut, int32_t(0), bins, rocprim::plus<int32_t>(), st));
+    if (rc == MGPS_OK) {
+        resampleCopyKernel<<<flatBlocks(std::max<size_t>(size_t(d->n), 1)), kFlat, 0, st>>>(a);
+        rc = hipStatus(fn, hipGetLastError());
+    }
+    if (rc == MGPS_OK && d->min_per_cell > 0) {
+        resampleSeedKernel<<<flatBlocks(size_t(cells) * size_t(d->min_per_cell)), kFlat, 0, st>>>(a);
+        rc = hipStatus(fn, hipGetLastError());
+    }
+    const int freed = hipStatus(fn, hipFreeAsync(block, st));
+    return rc != MGPS_OK ? rc : freed;
 }
 MGPS_API_CATCH(nullptr)
 }

@@ -1462,14 +1462,8 @@ def particlesToGrid(position, velocity, cell_start, shape, radius, dx=1.0, want_
     return vout, wout, known, phi, counts
 
 
-def updateParticles(position, velocity, grid_new, dt, grid_old=None, flip=0.95, trace_order=2, out=None, counts=None):
-    """mgps_particles_update: grid -> particles, then move.  Every particle inside the box takes
-    (1 - flip) U_new(x) + flip (v + U_new(x) - U_old(x)) as its velocity and moves along grid_new over `dt` (time step over cell size;
-    trace_order 2 is the midpoint rule), clamped into the box; particles outside are copied through.  grid_new: the projected,
-    extrapolated face grids; grid_old: the particlesToGrid result before forces and projection (None only with flip = 0).
-    out = (position_out[3], velocity_out[3]): each array the input itself (in place) or one that overlaps nothing; None: new arrays.
-    counts: an int64 CUDA tensor of 2 that the pass adds to ([0] particles a clamp moved, [1] outside particles), or None.
-    Returns (position_out, velocity_out).  Does not synchronise."""
+def _update_desc(position, velocity, grid_new, dt, grid_old, flip, trace_order, out, counts):
+    """the desc of updateParticles and updateParticlesSolid, and (position_out, velocity_out)"""
     pos, n = _particles(position)
     vel, _ = _particles(velocity, n)
     shape = list(grid_new[0].shape)
@@ -1487,9 +1481,146 @@ def updateParticles(position, velocity, grid_new, dt, grid_old=None, flip=0.95, 
         if grid_old is not None:
             d.grid_old[a] = _chk(grid_old[a], faces[a], torch.float32).data_ptr()
     d.counts_dev = _counts_ptr(counts)
-    with torch.cuda.device(pos[0].device):
+    return d, pout, vout
+
+
+def updateParticles(position, velocity, grid_new, dt, grid_old=None, flip=0.95, trace_order=2, out=None, counts=None):
+    """mgps_particles_update: grid -> particles, then move.  Every particle inside the box takes
+    (1 - flip) U_new(x) + flip (v + U_new(x) - U_old(x)) as its velocity and moves along grid_new over `dt` (time step over cell size;
+    trace_order 2 is the midpoint rule), clamped into the box; particles outside are copied through.  grid_new: the projected,
+    extrapolated face grids; grid_old: the particlesToGrid result before forces and projection (None only with flip = 0).
+    out = (position_out[3], velocity_out[3]): each array the input itself (in place) or one that overlaps nothing; None: new arrays.
+    counts: an int64 CUDA tensor of 2 that the pass adds to ([0] particles a clamp moved, [1] outside particles), or None.
+    Returns (position_out, velocity_out).  Does not synchronise."""
+    d, pout, vout = _update_desc(position, velocity, grid_new, dt, grid_old, flip, trace_order, out, counts)
+    with torch.cuda.device(position[0].device):
         check(lib().mgps_particles_update(C.byref(d), _stream()))
     return pout, vout
+
+
+# ---- FLIP particles next to solids: collide, resample (include/mgps_fields.h, DESIGN.md section 24) -----------------------------------
+class ParticlesCollideDesc(C.Structure):
+    """mgps_particles_collide_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("n", C.c_int), ("iterations", C.c_int), ("margin", C.c_double),
+        ("friction", C.c_double), ("position_in", C.c_void_p * 3), ("velocity_in", C.c_void_p * 3), ("position_out", C.c_void_p * 3),
+        ("velocity_out", C.c_void_p * 3), ("solid_phi", C.c_void_p), ("solid_velocity", C.c_void_p * 3), ("counts_dev", C.c_void_p),
+    ]
+
+
+class ParticlesResampleDesc(C.Structure):
+    """mgps_particles_resample_desc (include/mgps_fields.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int), ("gx", C.c_int), ("gy", C.c_int), ("gz", C.c_int), ("n", C.c_int), ("capacity", C.c_int), ("min_per_cell", C.c_int),
+        ("max_per_cell", C.c_int), ("keep_outside", C.c_int), ("seed", C.c_uint32), ("dx", C.c_double), ("seed_depth", C.c_double),
+        ("position", C.c_void_p * 3), ("velocity", C.c_void_p * 3), ("cell_start", C.c_void_p), ("liquid_phi", C.c_void_p), ("solid_phi", C.c_void_p),
+        ("grid", C.c_void_p * 3), ("position_out", C.c_void_p * 3), ("velocity_out", C.c_void_p * 3), ("cell_start_out", C.c_void_p),
+        ("n_out_dev", C.c_void_p), ("counts_dev", C.c_void_p),
+    ]
+
+
+def _counts_of(counts, entries):
+    """an int64 CUDA tensor of `entries` that a pass adds to, or None -> its pointer"""
+    assert counts is None or (counts.is_cuda and counts.dtype == torch.int64 and counts.numel() == entries and counts.is_contiguous())
+    return None if counts is None else counts.data_ptr()
+
+
+def _solid_desc(solid_phi, solid_velocity, margin, iterations, friction, counts):
+    """the collide desc without its particle arrays"""
+    shape = tuple(solid_phi.shape)
+    faces = _face3(shape)
+    d = ParticlesCollideDesc()
+    d.struct_size = C.sizeof(ParticlesCollideDesc)
+    d.gz, d.gy, d.gx = shape
+    d.iterations, d.margin, d.friction = int(iterations), float(margin), float(friction)
+    d.solid_phi = _chk(solid_phi, shape, torch.float32).data_ptr()
+    if solid_velocity is not None:
+        for a in range(3):
+            d.solid_velocity[a] = _chk(solid_velocity[a], faces[a], torch.float32).data_ptr()
+    d.counts_dev = _counts_of(counts, 3)
+    return d
+
+
+def collideParticles(position, velocity, solid_phi, solid_velocity=None, margin=0.1, iterations=2, friction=0.0, out=None, counts=None):
+    """mgps_particles_collide: every particle inside the box whose solid_phi (a CUDA cell grid, negative inside the solid, in cells:
+    rasterizeBodies' first result) is below `margin` is pushed along the grid's gradient to solid_phi = margin, at most `iterations`
+    times (1 .. 4), and loses the velocity it has into the solid relative to solid_velocity (the three face grids the projection
+    takes, or None: at rest), and the fraction `friction` of the rest.  Every other particle keeps its bits.
+    out = (position_out[3], velocity_out[3]): each array the input itself (in place) or one that overlaps nothing; None: new arrays.
+    counts: an int64 CUDA tensor of 3 that the pass adds to ([0] pushed, [1] pushed and still inside the solid, [2] stuck where the
+    gradient vanishes), or None.  Returns (position_out, velocity_out).  Does not synchronise."""
+    pos, n = _particles(position)
+    vel, _ = _particles(velocity, n)
+    pout, vout = ([torch.empty_like(t) for t in pos], [torch.empty_like(t) for t in vel]) if out is None else out
+    d = _solid_desc(solid_phi, solid_velocity, margin, iterations, friction, counts)
+    d.n = n
+    for a in range(3):
+        d.position_in[a], d.velocity_in[a] = pos[a].data_ptr(), vel[a].data_ptr()
+        d.position_out[a], d.velocity_out[a] = _particles(pout, n)[0][a].data_ptr(), _particles(vout, n)[0][a].data_ptr()
+    with torch.cuda.device(pos[0].device):
+        check(lib().mgps_particles_collide(C.byref(d), _stream()))
+    return pout, vout
+
+
+def updateParticlesSolid(position, velocity, grid_new, dt, solid_phi, grid_old=None, flip=0.95, trace_order=2, solid_velocity=None, margin=0.1,
+                         iterations=2, friction=0.0, out=None, counts=None, solid_counts=None):
+    """mgps_particles_update_solid: updateParticles and collideParticles in one launch, with the bits of the two calls in a row and
+    without the second pass over the six arrays.  The arguments are updateParticles' and collideParticles'; counts (int64 of 2) takes
+    the update's counts, solid_counts (int64 of 3) the collision's.  Returns (position_out, velocity_out).  Does not synchronise."""
+    d, pout, vout = _update_desc(position, velocity, grid_new, dt, grid_old, flip, trace_order, out, counts)
+    s = _solid_desc(solid_phi, solid_velocity, margin, iterations, friction, solid_counts)
+    with torch.cuda.device(position[0].device):
+        check(lib().mgps_particles_update_solid(C.byref(d), C.byref(s), _stream()))
+    return pout, vout
+
+
+def resampleParticles(position, velocity, cell_start, shape, capacity, min_per_cell, max_per_cell, liquid_phi=None, dx=1.0, seed_depth=1.0,
+                      solid_phi=None, grid=None, seed=0, keep_outside=False, out=None):
+    """mgps_particles_resample: BINNED particles (binParticles' position, velocity and cell_start) -> a binned set in arrays of
+    `capacity` entries in which no cell holds more than max_per_cell particles (the surplus is dropped at an even stride) and every
+    deep cell -- liquid_phi <= -seed_depth dx, and solid_phi > 0 where given -- holds at least min_per_cell: the new ones lie at
+    hashed places of their cell (`seed`) and take the velocity of the face grids `grid`.  min_per_cell = 0: thinning only.  The
+    outside bin is kept behind the last cell, or dropped.  out = (position[3], velocity[3], cell_start, n_out) to write into given
+    arrays.  Returns (position, velocity, cell_start, n_out, counts): n_out an int32 CUDA tensor of 1, the particles of the new set
+    (valid only if <= capacity), counts int64 of 4: [0] thinned away, [1] seeded, [2] deep cells, [3] 1 if the set did not fit.
+    Does not synchronise."""
+    shape = tuple(int(s) for s in shape)
+    pos, n = _particles(position)
+    vel, _ = _particles(velocity, n)
+    dev = cell_start.device
+    cells = shape[0] * shape[1] * shape[2]
+    _chk(cell_start, (cells + 2,), torch.int32)
+    faces = _face3(shape)
+    capacity = int(capacity)
+    if out is None:
+        out = ([torch.empty(capacity, dtype=torch.float32, device=dev) for _ in range(3)], [torch.empty(capacity, dtype=torch.float32, device=dev) for _ in range(3)],
+               torch.empty(cells + 2, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+    pout, vout, start_out, n_out = out
+    pout, vout = _particles(pout, capacity)[0], _particles(vout, capacity)[0]
+    d = ParticlesResampleDesc()
+    d.struct_size = C.sizeof(ParticlesResampleDesc)
+    d.gz, d.gy, d.gx = shape
+    d.n, d.capacity, d.min_per_cell, d.max_per_cell, d.keep_outside = n, capacity, int(min_per_cell), int(max_per_cell), int(bool(keep_outside))
+    d.seed, d.dx, d.seed_depth = int(seed) & 0xFFFFFFFF, float(dx), float(seed_depth)
+    for a in range(3):
+        d.position[a], d.velocity[a] = pos[a].data_ptr(), vel[a].data_ptr()
+        d.position_out[a], d.velocity_out[a] = pout[a].data_ptr(), vout[a].data_ptr()
+        if grid is not None:
+            d.grid[a] = _chk(grid[a], faces[a], torch.float32).data_ptr()
+    d.cell_start = cell_start.data_ptr()
+    d.cell_start_out = _chk(start_out, (cells + 2,), torch.int32).data_ptr()
+    d.n_out_dev = _chk(n_out, (1,), torch.int32).data_ptr()
+    if liquid_phi is not None:
+        d.liquid_phi = _chk(liquid_phi, shape, torch.float32).data_ptr()
+    if solid_phi is not None:
+        d.solid_phi = _chk(solid_phi, shape, torch.float32).data_ptr()
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    d.counts_dev = counts.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib().mgps_particles_resample(C.byref(d), _stream()))
+    return pout, vout, start_out, n_out, counts
 
 
 def seedParticles(liquid_phi, per_cell=8, seed=0, jitter=1.0):

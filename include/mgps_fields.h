@@ -940,8 +940,10 @@ int mgps_particles_to_grid(const mgps_particles_to_grid_desc *d, void *stream);
  *   or of the end point), [1] outside particles.
  *   Buffers.  Each output array is either exactly its input array (in place is safe: one thread per particle) or overlaps no
  *   other array of the call; a partial overlap is refused.
- * Out of scope, for all three: slab windows and particle migration between ranks; reseeding and deletion; collision with solids
- * (solid_phi is not consulted; clampB is the only wall); APIC / affine transfers; wiring into the one-calls. */
+ * Out of scope, for all the particle entries: slab windows and particle migration between ranks; APIC / affine transfers; wiring
+ * into the one-calls; continuous collision (entries 4 and 5 test a particle where it is and do not trace its path: a particle that a
+ * step carries across a solid thinner than the step is not found); seeding near the surface (entry 6 seeds no cell shallower than
+ * seed_depth). */
 typedef struct mgps_particles_update_desc {
     int struct_size;              /* sizeof(mgps_particles_update_desc) */
     int gx, gy, gz;               /* the WHOLE simulation grid */
@@ -961,6 +963,111 @@ typedef struct mgps_particles_update_desc {
  * extent < 1, gx gy gz + 1 >= 2^31, n < 0, a trace_order that is neither 1 nor 2, a non-finite dt, a flip outside [0, 1], a NULL
  * array that is in use, grid_old partly set, or NULL with flip > 0, overlapping buffers. */
 int mgps_particles_update(const mgps_particles_update_desc *d, void *stream);
+
+/* ---- FLIP particles next to solids: collide, and resample ------------------------------------------------------
+ * With these the sub-step is: bin, RESAMPLE, particles -> grid, extrapolate, (add forces), project, extrapolate, update WITH
+ * COLLISION.  Conventions, arithmetic and determinism are those of entries 1 to 3: fp64 on float32 data, every operation rounded on
+ * its own, an fma only where one is written, one rounding to float32 where a value is stored, no floating-point atomics.
+ * tests/particles_solids_reference.py restates both in numpy.
+ *
+ * 4. mgps_particles_collide: push the particles out of the solid and take the normal velocity into it away; one thread per particle.
+ *   solid_phi: a device cell grid, negative inside the solid, IN CELLS, as mgps_fields_rasterize_bodies writes it.  solid_velocity:
+ *   the three face grids the projection takes, all three or all NULL (the solid is at rest).  S is advection's sampling rule on the
+ *   cell lattice, U on the three face lattices.  Per inside particle (x, v), x in fp64:
+ *   Push-out loop, at most `iterations` times (1 .. 4):
+ *     phi = S(solid_phi)(x); if phi >= margin the loop ends.
+ *     g_c = S(x + e_c / 2) - S(x - e_c / 2) for c = x, y, z (the sample points are not clamped: S clamps into its lattice);
+ *     m = (g_x g_x + g_y g_y) + g_z g_z.  If not m > 1e-12 (NaN as well) the particle is STUCK and the loop ends: it is not moved
+ *     from where it is (a push of an earlier iteration stays, and the particle counts as pushed as well).
+ *     Otherwise n_c = g_c / sqrt(m) and x_c = clampB(fma(margin - phi, n_c, x_c)): a PUSH.
+ *   A particle that was not pushed leaves with its input bits, position and velocity.  A pushed one, n being that of its last push:
+ *     u_s = U(solid_velocity)(x) at the fp64 end point, or 0; r_c = double(v_c) - u_s,c; vn = (r_x n_x + r_y n_y) + r_z n_z;
+ *     if vn < 0: r_c = r_c - vn n_c, then r_c = (1 - friction) r_c (friction acts on a particle that moves into the solid, and on
+ *     no other); v_out,c = float(r_c + u_s,c); x_out,c = float(x_c), the one rounding of the position.
+ *   Outside particles are copied through.
+ *   counts_dev (device, unsigned long long[3], may be NULL) is ADDED to: [0] pushed particles, [1] pushed particles with
+ *   S(solid_phi)(x_out) < 0 at the float32 position, one more sample (iterations too few, or a solid thinner than a step), [2] stuck
+ *   particles.
+ *   Buffers: as entry 3, in place or out of place.  The pass tests a particle where it is; it does not trace through the solid. */
+typedef struct mgps_particles_collide_desc {
+    int struct_size;                 /* sizeof(mgps_particles_collide_desc) */
+    int gx, gy, gz;                  /* the WHOLE simulation grid */
+    int n;                           /* particles, >= 0 */
+    int iterations;                  /* 1 .. 4 */
+    double margin;                   /* cells, finite and >= 0: a particle ends at solid_phi = margin */
+    double friction;                 /* in [0, 1] */
+    const float *position_in[3];     /* device, n entries each; not read (may be NULL) when n == 0 */
+    const float *velocity_in[3];
+    float *position_out[3];
+    float *velocity_out[3];
+    const float *solid_phi;          /* device cell grid, cells */
+    const float *solid_velocity[3];  /* device face grids: all three, or all NULL */
+    unsigned long long *counts_dev;  /* 3 entries, or NULL */
+} mgps_particles_collide_desc;
+/* Does not synchronise the stream.  Refuses with a message, before any device work: NULL desc or a struct_size mismatch, an
+ * extent < 1, gx gy gz + 1 >= 2^31, n < 0, a margin that is not finite and >= 0, iterations outside 1 .. 4, a friction outside
+ * [0, 1], a NULL solid_phi, solid_velocity partly set, a NULL particle array with n > 0, overlapping buffers. */
+int mgps_particles_collide(const mgps_particles_collide_desc *d, void *stream);
+
+/* 5. mgps_particles_update_solid: entry 3 and entry 4 in ONE launch.  The update is done exactly as mgps_particles_update does it,
+ * position and velocity are rounded to float32, and rule 4 is applied to those float32 values in registers: all six arrays and both
+ * sets of counts (d->counts_dev[2], solid->counts_dev[3]) are BIT-EQUAL to mgps_particles_update followed by
+ * mgps_particles_collide, without the second pass over six arrays.  Of `solid`, n and the particle arrays are not read; its gx, gy,
+ * gz are d's.  Refuses what either entry refuses of these fields, and two descs of different extents. */
+int mgps_particles_update_solid(const mgps_particles_update_desc *d, const mgps_particles_collide_desc *solid, void *stream);
+
+/* 6. mgps_particles_resample: keep the particle count per cell in range -- thin crowded cells, seed deep empty ones.  From BINNED
+ * particles (position, velocity, cell_start as mgps_particles_bin left them), out of place, into arrays of `capacity` entries; the
+ * output is a binned set again (cell order, cell_start_out of cells + 2 entries, *n_out_dev), so particles -> grid follows
+ * without another bin.
+ *   Per cell c, with m_c = its slots, every slot range taken from cell_start clamped into [0, n] (and an end before its start: 0):
+ *   Thin.  m_c <= max_per_cell: every slot is kept.  Otherwise slot t (from 0 within the cell) is kept if
+ *     floor((t + 1) max / m_c) > floor(t max / m_c) in integers: exactly max slots, evenly strided, in their order.
+ *   Seed.  c is DEEP if liquid_phi is given, liquid_phi[c] <= -float(seed_depth dx), and solid_phi[c] > 0 where solid_phi is given.
+ *     A deep cell with k < min_per_cell kept slots gets min - k new particles behind its kept ones.  New particle q = 0 .. of cell
+ *     (i_x, i_y, i_z): x_a = min(float(double(i_a) + r), the float32 just below i_a + 1), r = (h >> 8) 2^-24,
+ *     h = mix(mix(mix(seed ^ 0x9e3779b9) + uint32(c)) + uint32(3 (k + q) + a)),
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 in wrapping uint32 -- so it lies in its
+ *     cell.  Its velocity is float(U(grid)(x)) at that float32 position.  min_per_cell = 0: no seeding.
+ *   The outside bin follows the last cell when keep_outside is 1 and is dropped otherwise: cell_start_out[cells] is its first slot,
+ *   cell_start_out[cells + 1] = *n_out_dev the total.
+ *   Capacity.  *n_out_dev is the total the rule asks for, whether or not it fits; no slot >= capacity is written; the outputs are a
+ *   valid set only if *n_out_dev <= capacity.
+ *   counts_dev (device, unsigned long long[4], may be NULL) is ADDED to: [0] particles removed by thinning, [1] particles seeded,
+ *   [2] deep cells, [3] 1 when the total does not fit.
+ *   The result is a function of the inputs alone.  A wrong cell_start gives wrong values (a slot that is not within the range
+ *   cell_start gives for the cell of its position is dropped), never an out-of-range read or write.
+ *   A count kernel over the cells, rocprim::exclusive_scan into cell_start_out, a copy kernel over the input slots (its cell from its
+ *   position, its rank floor(t max / m_c) in closed form) and a seeding kernel over (cell, q), in stream order with temporary storage
+ *   from the stream's pool: no host synchronisation. */
+typedef struct mgps_particles_resample_desc {
+    int struct_size;                 /* sizeof(mgps_particles_resample_desc) */
+    int gx, gy, gz;                  /* the WHOLE simulation grid */
+    int n;                           /* input particles, >= 0 */
+    int capacity;                    /* entries of each output array, >= 0 */
+    int min_per_cell, max_per_cell;  /* 0 <= min <= max, 1 <= max <= 64 */
+    int keep_outside;                /* 0 or 1 */
+    uint32_t seed;
+    double dx;                       /* the cell size in liquid_phi's units, finite and > 0 */
+    double seed_depth;               /* cells, finite and >= 0 */
+    const float *position[3];        /* binned; not read (may be NULL) when n == 0 */
+    const float *velocity[3];
+    const int32_t *cell_start;       /* cells + 2 entries */
+    const float *liquid_phi;         /* device cell grid; required when min_per_cell > 0 */
+    const float *solid_phi;          /* device cell grid, or NULL */
+    const float *grid[3];            /* device face grids, all three or all NULL; required when min_per_cell > 0 */
+    float *position_out[3];          /* capacity entries each */
+    float *velocity_out[3];
+    int32_t *cell_start_out;         /* cells + 2 entries */
+    int32_t *n_out_dev;              /* one entry */
+    unsigned long long *counts_dev;  /* 4 entries, or NULL */
+} mgps_particles_resample_desc;
+/* Does not synchronise the stream.  Refuses with a message, before any device work: NULL desc or a struct_size mismatch, an
+ * extent < 1, gx gy gz + 1 >= 2^31, n < 0, capacity < 0, max_per_cell outside 1 .. 64, min_per_cell outside 0 .. max_per_cell,
+ * keep_outside neither 0 nor 1, a dx that is not finite and > 0, a seed_depth that is not finite and >= 0,
+ * n + gx gy gz min_per_cell >= 2^31, grid partly set, liquid_phi or grid NULL with min_per_cell > 0, a NULL array that is in use,
+ * overlapping buffers. */
+int mgps_particles_resample(const mgps_particles_resample_desc *d, void *stream);
 
 #ifdef __cplusplus
 }
