@@ -11,6 +11,12 @@
  * f - e_a (backward) and f (forward).  Material labels (int32): 0 SOLID, 1 LIQUID, 2 AIR (Util.h:17).
  * HDK samples the solid SDF and the solid velocity by interpolation at a position (Util.cpp:25,
  * Plug.cpp:925); here the caller passes them sampled at cell centres / face centres.
+ * Deviations from the reference, both pinned by tests/test_reference_fields_parity.py against the reference's
+ * plugin compiled unchanged: (1) the pre-sampled solid inputs above; with solid fields
+ * aligned with the samples they are read at the two agree.  (2) Arithmetic is fp32 where the reference
+ * computes in double on its fpreal32 fields, theta's clamp constant included (0.01f, 2.2e-8 below 0.01):
+ * labels, valid faces and both pressure copies are bit-equal, weights within 4 eps32, right-hand side,
+ * gradient and report within the per-element rounding bounds stated there.
  * `stream` is a hipStream_t (NULL = the null stream).  Return values: the status codes of mgps.h. */
 #ifndef MGPS_FIELDS_H
 #define MGPS_FIELDS_H

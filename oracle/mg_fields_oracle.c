@@ -3,10 +3,14 @@
  * around the multigrid solve: material labels, valid faces, multigrid domain labels
  * and boundary weights, right-hand side, pressure copy in / out, pressure-gradient update and the
  * post-projection divergence report.  TEST INFRASTRUCTURE ONLY, like mg_oracle.c: nothing in the product
- * path may include, link, import or call this file.  PARITY UNPINNED, unlike mg_oracle.c: the reference's
- * plugin file needs SIM_RawField, which the stand-in headers of oracle/ref_standin/ do not cover, and the
- * reference has no fixtures; pinned by properties in tests/test_fields.py (the projected velocity
- * is divergence-free to solver tolerance -- the reference's own check, Plug.cpp:704-706).
+ * path may include, link, import or call this file.  PARITY PINNED, like mg_oracle.c: the reference's plugin
+ * files compile unchanged against the stand-in headers of oracle/ref_standin/ behind oracle/ref_fields_driver.cpp
+ * (`make -C oracle ref`), and tests/test_reference_fields_parity.py holds every function below to what that
+ * binary computes on float32 inputs, bit for bit once a result is rounded to the type the reference stores it
+ * in (tests/golden/ref_fields_*.npz).  One thing had to change for that: the reference
+ * forms the difference of two pressures in fpreal32 (mgf_pressure_gradient_raw).  Also pinned by properties in
+ * tests/test_fields.py (the projected velocity is divergence-free to solver tolerance -- the reference's own
+ * check, Plug.cpp:704-706).
  *
  * "Plug.cpp" = Source/HDK_GeometricFreeSurfacePressureSolver.cpp, "Util.h/.cpp" = Source/HDK_Utilities.*.
  * Grids are dense, x fastest; the face grid of axis a has one more entry along a; face f of axis a lies
@@ -175,12 +179,13 @@ void mgf_solution_to_pressure(double *pressure, const double *expanded_x, const 
                     pressure[cell(gx, gy, i, j, k)] = expanded_x[cell(ex, ey, i + offset, j + offset, k + offset)];
 }
 
-/* applyPressureGradient (Plug.cpp:1049-1131) */
-void mgf_pressure_gradient(int axis, double *velocity, const double *cw, const double *liquid_phi, const double *pressure,
-                           const uint8_t *valid, const int32_t *material, int gx, int gy, int gz)
+/* applyPressureGradient (Plug.cpp:1049-1131).  raw_fields: the pressure is a SIM_RawField, whose samples getFieldValue hands out
+ * as fpreal32, so the reference forms the difference of the two pressures in fpreal32 (Plug.cpp:1102) before it goes on in
+ * double; with raw_fields = 0 the difference is formed in double like everything else (pressures that are not float32 values). */
+static void pressure_gradient(int axis, double *velocity, const double *liquid_phi, const double *pressure, const uint8_t *valid,
+                              const int32_t *material, int gx, int gy, int gz, int raw_fields)
 {
     const int f[3] = {gx + (axis == 0), gy + (axis == 1), gz + (axis == 2)}, g[3] = {gx, gy, gz};
-    (void)cw;
     for (int k = 0; k < f[2]; ++k)
         for (int j = 0; j < f[1]; ++j)
             for (int i = 0; i < f[0]; ++i) {
@@ -190,10 +195,22 @@ void mgf_pressure_gradient(int axis, double *velocity, const double *cw, const d
                 b[axis] -= 1;
                 if (b[axis] < 0 || fw[axis] >= g[axis]) continue;
                 const size_t cb = cell(gx, gy, b[0], b[1], b[2]), cf = cell(gx, gy, fw[0], fw[1], fw[2]);
-                double grad = pressure[cf] - pressure[cb];
+                double grad = raw_fields ? (double)((float)pressure[cf] - (float)pressure[cb]) : pressure[cf] - pressure[cb];
                 if (material[cb] != MAT_LIQUID || material[cf] != MAT_LIQUID) grad /= ghost_fluid_theta(liquid_phi[cb], liquid_phi[cf]);
                 velocity[fc] -= grad;
             }
+}
+void mgf_pressure_gradient(int axis, double *velocity, const double *cw, const double *liquid_phi, const double *pressure,
+                           const uint8_t *valid, const int32_t *material, int gx, int gy, int gz)
+{
+    (void)cw;
+    pressure_gradient(axis, velocity, liquid_phi, pressure, valid, material, gx, gy, gz, 0);
+}
+void mgf_pressure_gradient_raw(int axis, double *velocity, const double *cw, const double *liquid_phi, const double *pressure,
+                               const uint8_t *valid, const int32_t *material, int gx, int gy, int gz)
+{
+    (void)cw;
+    pressure_gradient(axis, velocity, liquid_phi, pressure, valid, material, gx, gy, gz, 1);
 }
 
 /* computeResultingDivergence (Plug.cpp:1133-1207): out = {sum, max (from 0), liquid cell count} */

@@ -405,11 +405,16 @@ class FieldsOracle:
         self.lib.mgf_solution_to_pressure(_ptr(pressure), _ptr(self._f64(solution)), _ptr(material), gx, gy, gz, ex, ey, ez, int(offset))
         return pressure
 
-    def pressure_gradient(self, vel, cw, liquid_phi, pressure, valid, material):
+    def pressure_gradient(self, vel, cw, liquid_phi, pressure, valid, material, raw_fields=False):
+        """raw_fields: `pressure` holds float32 values as a SIM_RawField does, and the difference of two of them is formed in
+        float32 as the reference forms it (Plug.cpp:1102)"""
         gz, gy, gx = material.shape
+        if raw_fields:
+            assert (np.asarray(pressure, dtype=np.float32) == pressure).all()
+        entry = self.lib.mgf_pressure_gradient_raw if raw_fields else self.lib.mgf_pressure_gradient
         for a in range(3):
             assert vel[a].dtype == np.float64 and vel[a].flags.c_contiguous
-            self.lib.mgf_pressure_gradient(a, _ptr(vel[a]), _ptr(self._f64(cw[a])), _ptr(self._f64(liquid_phi)), _ptr(self._f64(pressure)),
+            entry(a, _ptr(vel[a]), _ptr(self._f64(cw[a])), _ptr(self._f64(liquid_phi)), _ptr(self._f64(pressure)),
                                            _ptr(valid[a]), _ptr(material), gx, gy, gz)
         return vel
 

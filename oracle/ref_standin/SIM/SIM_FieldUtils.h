@@ -1,8 +1,11 @@
 /* Stand-in for the index maps of the HDK's SIM::FieldUtils (cell-centred grid, face grids with one more
- * entry along their axis): face f of axis a lies between cells f - e_a and f.  See SYS/SYS_Types.h. */
+ * entry along their axis): face f of axis a lies between cells f - e_a and f; and for its getFieldValue /
+ * setFieldValue on voxel arrays and raw fields (a raw field's sample is handed out as fpreal32, an index
+ * field's as exint).  See SYS/SYS_Types.h. */
 #ifndef REFSTANDIN_SIM_FIELDUTILS_H
 #define REFSTANDIN_SIM_FIELDUTILS_H
 
+#include <SIM/SIM_RawField.h>
 #include <UT/UT_Vector3.h>
 #include <UT/UT_VoxelArray.h>
 
@@ -50,6 +53,11 @@ namespace FieldUtils
     {
         field.setValue(cell, value);
     }
+    // raw fields: the sample at an index of field(); a value written is rounded to the field's storage type
+    inline fpreal32 getFieldValue(const SIM_RawField &field, const UT_Vector3I &cell) { return (*field.field())(cell); }
+    inline exint getFieldValue(const SIM_RawIndexField &field, const UT_Vector3I &cell) { return (*field.field())(cell); }
+    inline void setFieldValue(SIM_RawField &field, const UT_Vector3I &cell, fpreal32 value) { field.fieldNC()->setValue(cell, value); }
+    inline void setFieldValue(SIM_RawIndexField &field, const UT_Vector3I &cell, exint value) { field.fieldNC()->setValue(cell, value); }
 } // namespace FieldUtils
 } // namespace SIM
 

@@ -1,6 +1,6 @@
 /*
  * Stand-in for the HDK's SYS basics, written from the HDK's documented behaviour for the one purpose of
- * compiling the reference solver core into oracle/_ref/ (see oracle/Makefile, target `ref`).  TEST
+ * compiling the reference solver core and its plugin into oracle/_ref/ (see oracle/Makefile, target `ref`).  TEST
  * INFRASTRUCTURE ONLY.  Nothing here is taken from the HDK or from the reference.
  *
  * Semantics of the whole oracle/ref_standin/ tree ("Reference parity"):
@@ -11,7 +11,13 @@
  *   - every UTparallelFor* / UT_ThreadedAlgorithm::run body runs once, serially, over the whole range
  *     (one job, one processor); UTparallelSort is std::sort; the interrupt never fires;
  *   - assert() stays armed and throws refstandin::AssertionFailed instead of aborting, so a violated
- *     reference assertion reaches the driver as an error code.
+ *     reference assertion reaches the driver as an error code;
+ *   - for the plugin files (SIM/SIM_RawField.h has the detail): raw fields store fpreal32 and
+ *     SIM::FieldUtils::getFieldValue hands a sample out as fpreal32; tiles are never constant and
+ *     makeConstant fills, while the ARRAY's isConstant(&v) answers by value; indexToPos uses the sample's
+ *     offset for centre and face sampling; getValue(pos) is the trilinear interpolant in the form
+ *     (1 - t) a + t b, clamped at the border, and returns a sample bit for bit at a sample's position;
+ *     SIM_Object is a table of named fields, GAS_SubSolver a table of options.
  */
 #ifndef REFSTANDIN_SYS_TYPES_H
 #define REFSTANDIN_SYS_TYPES_H

@@ -23,6 +23,7 @@ public:
     T x() const { return v[0]; }
     T y() const { return v[1]; }
     T z() const { return v[2]; }
+    T maxComponent() const { return std::max(v[0], std::max(v[1], v[2])); }
 
     bool operator==(const UT_Vector3T &o) const { return v[0] == o.v[0] && v[1] == o.v[1] && v[2] == o.v[2]; }
     bool operator!=(const UT_Vector3T &o) const { return !(*this == o); }

@@ -9,8 +9,10 @@
  *     true once the tile number reaches myTileEnd; advanceTile() goes to the first voxel of the next tile;
  *     getTileVoxels(start, end) gives the tile's voxel box, end exclusive; splitByTile(info) keeps the whole
  *     tile range (one job);
- *   - nothing is ever compressed: isTileConstant() / isConstant() return false, uncompress(),
- *     collapseAllTiles() do nothing, constant(v) fills;
+ *   - nothing is ever compressed: isTileConstant() and a tile's isConstant() return false, uncompress(),
+ *     collapseAllTiles() and setCompressOnExit() do nothing, constant(v) fills.  The ARRAY's isConstant(&v)
+ *     answers by value: true, with the value in v, where every voxel holds the same value (what the HDK
+ *     reports of an array after constant(v)); the plugin asks it of the density field only;
  *   - UT_VoxelProbe and UT_VoxelProbeCube hold only an index: getValue reads the array, setValue writes it,
  *     at once (write-through, no cached line).  A read or write outside the array throws: the reference
  *     never relies on border behaviour, and a stand-in that invented one would hide it if it did.
@@ -71,7 +73,13 @@ public:
     }
     UT_VoxelTileStandin *getLinearTile(exint) const { return &theTile(); }
     void collapseAllTiles() {}
-    bool isConstant(T * = nullptr) const { return false; }
+    bool isConstant(T *value = nullptr) const
+    {
+        for (const T &v : myData)
+            if (!(v == myData.front())) return false;
+        if (value && !myData.empty()) *value = myData.front();
+        return true;
+    }
 
     T operator()(const UT_Vector3I &c) const { return myData[index(c[0], c[1], c[2])]; }
     T operator()(exint x, exint y, exint z) const { return myData[index(x, y, z)]; }
@@ -111,6 +119,9 @@ template <typename T>
 class UT_VoxelArrayIterator
 {
 public:
+    UT_VoxelArrayIterator() = default;
+    explicit UT_VoxelArrayIterator(UT_VoxelArray<T> *array) { setArray(array); }
+    void setCompressOnExit(bool) {}
     void setArray(UT_VoxelArray<T> *array)
     {
         myArray = array;
@@ -209,6 +220,13 @@ public:
 private:
     UT_VoxelArrayIterator<T> myIt;
 };
+
+using UT_VoxelArrayF = UT_VoxelArray<fpreal32>;
+using UT_VoxelArrayI = UT_VoxelArray<int64>;
+using UT_VoxelArrayIteratorF = UT_VoxelArrayIterator<fpreal32>;
+using UT_VoxelArrayIteratorI = UT_VoxelArrayIterator<int64>;
+using UT_VoxelTileIteratorF = UT_VoxelTileIterator<fpreal32>;
+using UT_VoxelTileIteratorI = UT_VoxelTileIterator<int64>;
 
 // One row along x around an index; prex / postx (the cached span in the HDK) carry no meaning here.
 template <typename T, bool DoRead, bool DoWrite, bool TestForWrites>
