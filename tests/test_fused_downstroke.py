@@ -8,6 +8,10 @@ x' must be EQUAL between the two (the march forms it with the sweep's expression
 tiles' rims after the folds instead of inside r: within 2e-6 of its maximum of the separate passes' (the project's bound between the
 residual pair and the separate passes).
 
+MEASURED on an MI355X, balanced inputs (tests/operator_bounds.py), worst error / bound over the seven cases, fused and
+apart (bound = 1): x' against the oracle's stroke 0.21; the coarse rhs against the oracle's downsample(residual(x')) 0.045; fused
+against apart per coarse cell 0.012 of twice the bound.
+
 The numpy model at the end (no GPU) is the layout the fix-up kernel was written from: partial march + fix-up = the full formula."""
 import json
 import os
@@ -18,6 +22,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import operator_bounds as OB
 from conftest import ROOT
 
 OP_TOL = 5e-6       # tests/test_rz_xfold.py
@@ -123,6 +128,26 @@ if what != 'cycles':
     assert np.array_equal(xs2, xs) and np.array_equal(coarse2, coarse)
     np.save(out, np.concatenate([xs.ravel(), coarse.ravel()]))
     res['err'] = float(err)
+    # per cell on balanced inputs (tests/operator_bounds.py; the weights as the float32 values the device holds): x' against the
+    # oracle's stroke -- three band passes, the sweep, three band passes, every pass's bound carried through the later ones -- and
+    # the coarse rhs against the oracle's downsample(residual(x')) of the device's own x'
+    import operator_bounds as OB
+    wf = [OB.as_f32(a) for a in w]
+    st = OB.Stencil(lab, wf)
+    xb, bb = OB.balanced_inputs(lab, wf, 115, st)
+    xbd, cbd = s.to_device(xb), s.new_grid(1)
+    s.downStroke(xbd, cbd, s.to_device(bb), 0)
+    xsb, cb = xbd.cpu().numpy(), cbd.cpu().numpy()
+    xref, e = OB.smooth_stroke(st, orc, xb, bb, lab32, orc.build_boundary_cells(lab32, 3), wf)
+    tag = 'downstroke %%s fused=%%d ' %% (case, fuse)
+    res['x'] = OB.assert_within(tag + "x'", xsb, xref, e)
+    rb = np.zeros(lab.shape)
+    orc.residual(rb, xsb.astype(np.float64), bb, lab32, wf)
+    refb = np.zeros(lab1.shape)
+    orc.downsample(refb, rb, lab1)
+    bound = OB.bound_residual_restrict(st, xsb, bb, lab1)
+    res['coarse'] = OB.assert_within(tag + 'coarse rhs', cb, refb, bound)
+    np.savez(out + '.balanced.npz', x=xsb, coarse=cb, bound=bound)
 else:
     b = np.where(act, rng.standard_normal(lab.shape) * dx * dx, 0.0).astype(np.float32)
     bd = s.to_device(b)
@@ -154,7 +179,14 @@ def _run(case, fuse, path, what="operator", poison=False):
     res = subprocess.run([sys.executable, "-c", code, case, fuse, path, what], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
                          timeout=600, env=env)
     assert res.returncode == 0 and "FUSE_DOWN_OK" in res.stdout, res.stdout[-3000:]
+    print("".join(line for line in res.stdout.splitlines(True) if line.startswith("PERCELL")), end="")
+    if os.path.exists(path + ".balanced.npz"):  # the operator child's stroke on balanced inputs
+        with np.load(path + ".balanced.npz") as z:
+            BALANCED[(case, fuse)] = {k: z[k] for k in z.files}
     return np.load(path)
+
+
+BALANCED = {}  # (case, MGPS_FUSE_DOWN) -> x', coarse rhs and the coarse rhs's per-cell bound of the last operator child
 
 
 def _both(case, what="operator"):
@@ -173,6 +205,10 @@ def _compare(case, fused, apart):
     d, m = float(np.abs(fused[n:] - apart[n:]).max()), float(np.abs(apart[n:]).max())
     print(case, "coarse rhs: max |fused - apart|", d, "max |apart|", m, "ratio", d / m)
     assert m > 0 and d <= PAIR_TOL * m, (d, m)
+    # on balanced inputs: x' equal again, the coarse rhs per coarse cell within twice the per-cell bound (both sides carry it)
+    f, a = BALANCED[(case, "1")], BALANCED[(case, "0")]
+    assert np.array_equal(f["x"], a["x"]), (int((f["x"] != a["x"]).sum()), float(np.abs(f["x"] - a["x"]).max()))
+    OB.assert_within(f"downstroke {case} fused against apart, coarse rhs", f["coarse"], a["coarse"], 2.0 * a["bound"])
 
 
 @pytest.mark.gpu
@@ -181,7 +217,9 @@ def test_fused_down_stroke_equals_sweep_then_march(case):
     """One down-stroke through mgps_down_stroke on a random guess and rhs, MGPS_FUSE_DOWN=1 against =0: x' bit for bit, inactive
     cells exactly 0, the coarse rhs within 2e-6 of its maximum; in each child the coarse rhs within 5e-6 of the oracle's
     downsample(residual(x')), a second call with the same bits, and the level reports the form the child was started for (with its
-    kept-quad words made or not).  seams776 / mid520 / stair520: tests/test_rz_xfold.py's domains; rag264: ragged last tiles on every
+    kept-quad words made or not).  The same stroke on balanced inputs (tests/operator_bounds.py): in each child x' per cell against
+    the oracle's stroke and the coarse rhs per coarse cell against the oracle's downsample(residual(x')); here x' bit for bit and
+    the coarse rhs of the two forms within twice the per-cell bound in every coarse cell.  seams776 / mid520 / stair520: tests/test_rz_xfold.py's domains; rag264: ragged last tiles on every
     axis; tall264: solver shape (72, 36, 264), liquid from one cell inside the padding -- 18 z-blocks of 4 planes (the block depth
     the launcher takes at this size); ragz264: (10, 20, 264), two levels, z-blocks of 4, 4 and 2 planes."""
     fused, apart = _both(case)
